@@ -10,6 +10,9 @@ the automaton and broadcasts the image, every rank scans its own shard of haysta
 no collective on the data path), match counts are summed with an all-reduce at the end.
 
 Prints ONE JSON line on rank 0 (see the contract in the task statement / DESIGN.md "Measurement").
+A plain run sets up, warms up, times --steps steps and prints the line; --full adds everything else the line can carry
+(count-only pass, parity gate, PCIe-inclusive leg, CPU baseline, the other BASELINE configurations); --dump-outputs DIR
+writes what the last timed step computed as .npy files.
 """
 import argparse
 import ctypes as C
@@ -23,6 +26,10 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0     # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_BUDGET = 60 << 20     # --dump-outputs: bytes of .npy data at most
+DUMP_SEED = 20240607       # --dump-outputs: the seed of the haystacks sampled from a larger result
+DUMP_CHUNK = 1 << 22       # --dump-outputs: records copied to the host at a time (64 MiB)
+NPY_HEADER = 128           # bytes of an .npy file's header
 
 
 def main():
@@ -42,12 +49,17 @@ def main():
     ap.add_argument("--no-parity", action="store_true", help="skip the fold-checksum parity gate (kernel vs kernel on every haystack, oracle on a sample)")
     ap.add_argument("--parity-oracle-mib", type=int, default=1024, help="haystack bytes of rank 0's shard the oracle re-scans for the parity gate")
     ap.add_argument("--plants", type=int, default=1, help="needles planted per 1-KiB cell of the synthetic haystacks (robustness sweep: 0, 1, 8, 64; BASELINE = 1)")
-    ap.add_argument("--workloads", default=None, help="comma-separated BASELINE configurations measured AFTER the headline into the line's `workloads` object "
+    ap.add_argument("--workloads", default=None, help="with --full: comma-separated BASELINE configurations measured AFTER the headline into the line's `workloads` object "
                     "(default: all of %s when the headline is the default cfg3 run on one GPU; 'none' switches them off)" % ", ".join(EXTRA_WORKLOADS))
     ap.add_argument("--workload-steps", type=int, default=5, help="timed steps of each entry of `workloads` (after 2 warm-up steps)")
     ap.add_argument("--workloads-oracle-mib", type=int, default=64, help="haystack bytes the oracle re-scans in each `workloads` entry's parity gate")
     ap.add_argument("--torch-collectives", action="store_true", help="N ranks: broadcast the automaton image and sum the counts with torch.distributed "
                     "instead of libam's own RCCL entry points (am_multi_*): cross-check of the product path")
+    ap.add_argument("--full", action="store_true", help="after the headline, everything else the benchmark measures and checks: the count-only pass, the parity gate, "
+                    "the resident-waves probe, the PCIe-inclusive leg, the CPU baseline, the other BASELINE configurations, the replacer's host-results and "
+                    "per-kernel step (without it: set-up, warm-up, the timed steps, --dump-outputs and the result line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float64, float32 for text "
+                    "bytes): per-haystack sizes in full, the results of a fixed, seeded sample of haystacks, %d MiB at most over all ranks / devices" % (DUMP_BUDGET >> 20))
     args = ap.parse_args()
 
     import numpy as np
@@ -165,11 +177,16 @@ def main():
     batch = C.c_void_p()
     am.api.check(lib.am_batch_from_device(text.data_ptr(), offs.data_ptr(), n_hay, n_bytes, C.byref(batch)))
 
-    def step():
+    last = []                                          # the last timed step's result, kept for --dump-outputs
+
+    def step(keep=False):
         m = C.c_void_p()
         am.api.check(lib.am_run_batch(handle, case, batch, C.byref(m)))   # synchronises its stream before returning
         n = int(lib.am_matches_size(m))
-        lib.am_matches_free(m)
+        if keep:
+            last.append(m)
+        else:
+            lib.am_matches_free(m)
         return n
 
     def fence():
@@ -184,17 +201,29 @@ def main():
     am.api.check(lib.am_profile_enable(1))
     fence()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        n_records = step()
+    for i in range(args.steps):
+        n_records = step(keep=i == args.steps - 1)
     fence()
     elapsed = time.perf_counter() - t0
     am.api.check(lib.am_profile_enable(0))
     elapsed = amdist.allreduce_max(elapsed, dev)
+    if args.dump_outputs and last:
+        dump_matches(args.dump_outputs, last[0], n_hay, lib, writers=world, prefix="rank%d_" % rank if world > 1 else "")
+    for m in last:
+        lib.am_matches_free(m)
 
-    # values folded (= reference's countMatches) via the count-only entry point, summed over ranks
-    total_values = C.c_uint64(0)
+    # values folded (= reference's countMatches) via the count-only entry point, summed over ranks (--full)
+    total_values, total_matches = C.c_uint64(0), None
     t1 = time.perf_counter()
-    if multi is not None:
+    if not args.full:
+        # the headline needs the bytes (and records) of every rank only
+        sums = np.array([n_records, n_bytes], dtype=np.uint64)
+        if multi is not None:
+            am.api.check(lib.am_multi_allreduce_sum(multi, sums.ctypes.data, 2))
+        else:
+            sums = amdist.allreduce_sum(sums.tolist(), dev)
+        total_records, amdist_total_bytes = (int(x) for x in sums)
+    elif multi is not None:
         # the device-resident multi-GPU entry point: count on this rank's resident batch, ncclAllReduce of the totals inside libam
         autos1, batches1 = (C.c_void_p * 1)(handle), (C.c_void_p * 1)(batch)
         local_total, job_total = C.c_uint64(0), C.c_uint64(0)
@@ -212,7 +241,7 @@ def main():
         total_matches, total_records, amdist_total_bytes = amdist.allreduce_sum([int(total_values.value), n_records, n_bytes], dev)
 
     parity = None
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         parity = parity_gate(args, w, needles, machine, handle, case, batch, text, n_hay, rank, world, dev, lib)
 
     kname = b"sf" if args.kernel != 1 else b"ac"
@@ -261,9 +290,9 @@ def main():
                        "parallelism": "haystack-sharded x%d%s" % (world, ", automaton broadcast + count all-reduce by libam (am_multi_*, RCCL)" if multi is not None else ""), "kernel": kname.decode(),
                        "automaton_image_bytes": image_bytes, "build_s": round(build_s, 2)},
             "build": build, "gpu_build_plus_run": build_plus_run(n_bytes, build, ms_per_step) if build else None,
-            "matches_per_s": round(total_matches * args.steps / elapsed, 1),
-            "matches_per_step": total_matches, "records_per_step": total_records,
-            "count_only_gibps": round(n_bytes / float(1 << 30) / count_only_s, 3),
+            **({"matches_per_s": round(total_matches * args.steps / elapsed, 1), "matches_per_step": total_matches} if total_matches is not None else {}),
+            "records_per_step": total_records,
+            **({"count_only_gibps": round(n_bytes / float(1 << 30) / count_only_s, 3)} if total_matches is not None else {}),
             "roofline": {"bound": "hbm", "kernel": "k_dfa + k_dfa_place" if pair_ms else "k_" + kname.decode(), **({"per_kernel_ms": pair_ms} if pair_ms else {}), "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS,
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic, "traffic_source": traffic_source,
                          "avg_launch_ms": round(avg_ms, 4), "launches": int(launches.value), "alg_bytes_per_launch": int(alg_bytes)},
@@ -272,18 +301,20 @@ def main():
         if multi is not None:
             out["rccl"] = dict(rccl_ms, ranks=int(lib.am_multi_world_size(multi)), image_bytes=image_bytes,
                                data_path_collectives=0, what="am_multi_create_rank + am_multi_broadcast_automaton + am_multi_count_batch / am_multi_allreduce_sum (csrc/am_multi.cpp)")
-        if rank == 0:
+        if args.full:
             # what the box gives: the kernels that count on two workgroups per CU (k_dfa, k_rp_lds, the small-filter k_sf) lose 10-45 % where a CU runs 16 wavefronts at a time
             waves, one_ms, two_ms = am.api.resident_waves()
             out["machine"] = {"resident_waves_per_cu": waves, "spin_16_per_cu_ms": one_ms, "spin_32_per_cu_ms": two_ms,
                               "what": "am_debug_resident_waves: a spinning kernel with 16 and with 32 wavefronts per CU; equal times = 32 resident (the architecture's number), twice = 16"}
         if parity is not None:
             out["parity"] = parity
-        if world == 1 and not args.no_h2d:
+        if args.full and world == 1 and not args.no_h2d:
             out["h2d_inclusive"] = h2d_inclusive(args, w, handle, case, text, n_hay, lib, settle=VRAM_WIPE_SETTLE_S if w.get("natural") else 0.0)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, w, needles, case, hay_cells, handle, batch, lib)
-        if args.workloads is None:
+        if not args.full:
+            args.workloads = "none"
+        elif args.workloads is None:
             args.workloads = ",".join(EXTRA_WORKLOADS) if (world == 1 and args.workload == "cfg3_runLower_100k_10GiB" and not args.hay_count and args.plants == 1 and args.kernel == 0) else "none"
         if world == 1 and args.workloads != "none":
             lib.am_batch_destroy(batch); batch = None
@@ -533,6 +564,81 @@ def extra_workloads(args, dev, lib, cfg3_machine, cfg3_needles):
     return out
 
 
+def dump_sample(n_hay, k):
+    """The haystacks --dump-outputs writes in full: k of the n_hay, drawn with a fixed seed (so the same on every run and every build), ascending."""
+    import numpy as np
+    if n_hay <= k:
+        return np.arange(n_hay)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_hay, k, replace=False))
+
+
+def dump_matches(out_dir, m, n_hay, lib, writers=1, prefix=""):
+    """--dump-outputs for the scan: what a caller of am_run_batch receives -- the am_match records of the last timed step -- as float64 arrays
+    (every field is an integer below 2^53, so exactly): records_per_haystack for every haystack, and end_pos / haystack / state of every record of
+    a fixed, seeded sample of 256 / writers haystacks (all of them in a smaller batch), in the result's order.  DUMP_BUDGET is the run's: each of
+    the `writers` ranks or devices that dump their own result keeps to its share.  The result is read in pieces of DUMP_CHUNK records, so the host
+    holds one piece at a time however large the result is."""
+    import numpy as np
+    import alfred_margaret_amd as am
+    os.makedirs(out_dir, exist_ok=True)
+    sample = dump_sample(n_hay, max(1, 256 // writers))
+    room = (DUMP_BUDGET // writers - 5 * NPY_HEADER - 8 * n_hay - 8 * sample.size) // 24          # records of the sample this writer may keep
+    if room < 0:
+        raise SystemExit("--dump-outputs: the record counts of %d haystacks alone exceed a %d-writer run's share of %d bytes" % (n_hay, writers, DUMP_BUDGET))
+    in_sample = np.zeros(n_hay, bool)
+    in_sample[sample] = True
+    n = int(lib.am_matches_size(m)) if m else 0
+    per_hay = np.zeros(n_hay, np.int64)
+    buf = np.zeros(min(n, DUMP_CHUNK), am.api.MATCH_DTYPE)
+    picked = []
+    for first in range(0, n, DUMP_CHUNK):
+        k = min(DUMP_CHUNK, n - first)
+        am.api.check(lib.am_matches_copy(m, first, k, buf.ctypes.data))
+        hay = buf["haystack"][:k]
+        per_hay += np.bincount(hay, minlength=n_hay)
+        if room:
+            sel = buf[:k][in_sample[hay]][:room]
+            room -= sel.size
+            picked.append(sel)
+    picked = np.concatenate(picked) if picked else np.zeros(0, am.api.MATCH_DTYPE)
+    np.save(os.path.join(out_dir, prefix + "records_per_haystack.npy"), per_hay.astype(np.float64))
+    np.save(os.path.join(out_dir, prefix + "sample_haystacks.npy"), sample.astype(np.float64))
+    for f in ("end_pos", "haystack", "state"):
+        np.save(os.path.join(out_dir, prefix + "records_" + f + ".npy"), picked[f].astype(np.float64))
+
+
+def dump_replaced(out_dir, res, n_hay, lib, writers=1, prefix=""):
+    """--dump-outputs for the replacer: what a caller of am_replacer_run_batch_device receives from the last timed step -- the rewritten texts --
+    as text_lengths (float64, every haystack; -1 for Nothing) and the bytes of a fixed, seeded sample of 128 / writers haystacks' texts, one after
+    another (sample_bytes, float32: exact for bytes), with their lengths (sample_lengths); each of the `writers` ranks keeps to its share of DUMP_BUDGET."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    ptr, ln = C.c_void_p(), C.c_size_t(0)
+    lengths = np.zeros(n_hay, np.float64)
+    for i in range(n_hay):
+        lengths[i] = ln.value if lib.am_replaced_get(res, i, C.byref(ptr), C.byref(ln)) == 1 else -1
+    sample = dump_sample(n_hay, max(1, 128 // writers))
+    room = (DUMP_BUDGET // writers - 4 * NPY_HEADER - 8 * n_hay - 16 * sample.size) // 4
+    if room < 0:
+        raise SystemExit("--dump-outputs: the text lengths of %d haystacks alone exceed a %d-writer run's share of %d bytes" % (n_hay, writers, DUMP_BUDGET))
+    texts, sample_lengths = [], []
+    for i in sample:
+        want = max(int(lengths[i]), 0)
+        buf = np.zeros(max(want, 1), np.uint8)
+        got = C.c_size_t(0)
+        rc = lib.am_replaced_read(res, int(i), buf.ctypes.data, buf.size, C.byref(got))
+        if rc < 0:
+            raise SystemExit("--dump-outputs: am_replaced_read of text %d failed" % i)
+        take = buf[:min(got.value, room)] if rc == 1 else buf[:0]
+        room -= take.size
+        texts.append(take)
+        sample_lengths.append(float(got.value) if rc == 1 else -1.0)
+    np.save(os.path.join(out_dir, prefix + "text_lengths.npy"), lengths)
+    np.save(os.path.join(out_dir, prefix + "sample_haystacks.npy"), sample.astype(np.float64))
+    np.save(os.path.join(out_dir, prefix + "sample_lengths.npy"), np.array(sample_lengths, np.float64))
+    np.save(os.path.join(out_dir, prefix + "sample_bytes.npy"), np.concatenate(texts).astype(np.float32) if texts else np.zeros(0, np.float32))
+
+
 class stdout_to_stderr:
     """File descriptor 1 points at stderr inside the block (RCCL prints a version banner on stdout when a communicator is
     made; rank 0's stdout must carry the one JSON line only)."""
@@ -599,13 +705,18 @@ def bench_single_process(args, w):
     autos_arr = (C.c_void_p * N)(*[autos[i] for i in range(N)])
     batches_arr = (C.c_void_p * N)(*[b.value for b in batches])
 
-    def step():
+    last = []                                          # the last timed step's results (one per device), kept for --dump-outputs
+
+    def step(keep=False):
         res = (C.c_void_p * N)()
         total = C.c_uint64(0)
         am.api.check(lib.am_multi_run_batch(multi, autos_arr, case, batches_arr, res, C.byref(total)))
         recs = [int(lib.am_matches_size(res[i])) if res[i] else 0 for i in range(N)]
-        for i in range(N):
-            lib.am_matches_free(res[i])
+        if keep:
+            last.extend(res[i] for i in range(N))
+        else:
+            for i in range(N):
+                lib.am_matches_free(res[i])
         assert sum(recs) == int(total.value)
         return recs
 
@@ -615,18 +726,27 @@ def bench_single_process(args, w):
     for i in range(N):
         torch.cuda.synchronize(i)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        recs = step()
+    for s in range(args.steps):
+        recs = step(keep=s == args.steps - 1)
     for i in range(N):
         torch.cuda.synchronize(i)
     elapsed = time.perf_counter() - t0
     am.api.check(lib.am_profile_enable(0))
+    if args.dump_outputs:
+        for i in range(N):
+            torch.cuda.set_device(i)
+            dump_matches(args.dump_outputs, C.c_void_p(last[i]), hays[i], lib, writers=N, prefix="gpu%d_" % i if N > 1 else "")
+        torch.cuda.set_device(0)
+    for m in last:
+        lib.am_matches_free(m)
 
-    local_totals = (C.c_uint64 * N)()
-    job_total = C.c_uint64(0)
-    am.api.check(lib.am_multi_count_batch(multi, autos_arr, case, batches_arr, None, local_totals, C.byref(job_total)))   # ncclAllReduce over the N devices
-    total_matches, total_records, total_bytes = int(job_total.value), sum(recs), sum(sizes)
-    assert total_matches == sum(int(x) for x in local_totals)
+    total_matches, total_records, total_bytes = None, sum(recs), sum(sizes)
+    if args.full:
+        local_totals = (C.c_uint64 * N)()
+        job_total = C.c_uint64(0)
+        am.api.check(lib.am_multi_count_batch(multi, autos_arr, case, batches_arr, None, local_totals, C.byref(job_total)))   # ncclAllReduce over the N devices
+        total_matches = int(job_total.value)
+        assert total_matches == sum(int(x) for x in local_totals)
     kname = b"sf" if args.kernel != 1 else b"ac"
     ms, launches = C.c_double(0), C.c_uint64(0)
     am.api.check(lib.am_profile_read(kname, C.byref(ms), C.byref(launches)))
@@ -643,14 +763,15 @@ def bench_single_process(args, w):
         "config": {"workload": args.workload, "n_needles": len(needles), "case": "IgnoreCase" if case else "CaseSensitive", "haystacks_per_gpu": hays[0],
                    "haystack_bytes": w["hay_bytes"], "bytes_per_gpu": sizes[0], "parallelism": "haystack-sharded x%d, one process (am_multi_create: ncclCommInitAll, image broadcast; am_multi_run_batch / am_multi_count_batch on device-resident batches)" % N,
                    "kernel": kname.decode(), "automaton_image_bytes": int(nbytes.value), "build_s": round(build_s, 2)},
-        "matches_per_s": round(total_matches * args.steps / elapsed, 1), "matches_per_step": total_matches, "records_per_step": total_records,
+        **({"matches_per_s": round(total_matches * args.steps / elapsed, 1), "matches_per_step": total_matches} if total_matches is not None else {}),
+        "records_per_step": total_records,
         "roofline": {"bound": "hbm", "kernel": "k_" + kname.decode(), "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": None, "avg_launch_ms": round(avg_ms, 4), "launches": int(launches.value),
                      "alg_bytes_per_launch": int(alg_bytes)},
         "collectives": "libam-rccl",
         "rccl": {"ranks": N, "self_check": "am_multi_create: one-word all-reduce of (rank + 1) verified on every device", "data_path_collectives": 0},
     }
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         # the same gate as the one-process-per-GPU path, device by device: on every device the route's kernel == k_ac on every haystack of its batch; the oracle's spread
         # sample in full on device 0, a few haystacks of each of the others
         import copy
@@ -730,34 +851,48 @@ def measure_replacer(args, workload, rank, world, dev, steps=None, warmup=None, 
         passes, scanned = step()
     fence()
     elapsed = amdist.allreduce_max(time.perf_counter() - t0, dev)
-    # the same steps with the results brought to the host (PCIe-inclusive; reported next to `value`, never as `value`).
-    # First let the driver finish wiping VRAM that was freed a moment ago (the workload before this one, the generator's temporaries): amdgpu clears freed
-    # VRAM in the background THROUGH THE SDMA ENGINES, and for about a second after a large hipFree every device->host copy runs at 27 instead of 53 GiB/s
-    # (measured in round 5, tools/experiments/host_results/: 39 ms per step in that second, 22.4 ms before and after; LABNOTES R5.6)
-    fence()
-    time.sleep(VRAM_WIPE_SETTLE_S)
-    step(False)
-    fence()
-    t0 = time.perf_counter()
-    for _ in range(steps):
+    if args.dump_outputs and not extra:
+        dump_replaced(args.dump_outputs, last["res"], n_hay, lib, writers=world, prefix="rank%d_" % rank if world > 1 else "")
+    full = args.full or extra
+    if full:
+        # the same steps with the results brought to the host (PCIe-inclusive; reported next to `value`, never as `value`).
+        # First let the driver finish wiping VRAM that was freed a moment ago (the workload before this one, the generator's temporaries): amdgpu clears freed
+        # VRAM in the background THROUGH THE SDMA ENGINES, and for about a second after a large hipFree every device->host copy runs at 27 instead of 53 GiB/s
+        # (measured in round 5: 39 ms per step in that second, 22.4 ms before and after; LABNOTES R5.6)
+        fence()
+        time.sleep(VRAM_WIPE_SETTLE_S)
         step(False)
-    fence()
-    elapsed_host = amdist.allreduce_max(time.perf_counter() - t0, dev)
-    # the per-kernel breakdown comes from ONE extra step with the HIP-event brackets on: a pass is a few dozen launches of
-    # microseconds each, and two event records per launch would be part of what is measured
-    am.api.check(lib.am_profile_reset()); am.api.check(lib.am_profile_enable(1))
-    step()
-    fence()
-    am.api.check(lib.am_profile_enable(0))
-    prof_steps = 1
-    prof = {}
-    for k in (b"sf", b"ac", b"rp_lds", b"rp_loop", b"rp_pass", b"rp_splice", b"rp_scans", b"rp_windows", b"rp_merge", b"permute", b"rp_ranges", b"rp_route", b"pt_build", b"pt_materialise", b"scan", b"hidx"):
-        ms, n = C.c_double(0), C.c_uint64(0)
-        am.api.check(lib.am_profile_read(k, C.byref(ms), C.byref(n)))
-        prof[k.decode()] = (ms.value, int(n.value))
+        fence()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            step(False)
+        fence()
+        elapsed_host = amdist.allreduce_max(time.perf_counter() - t0, dev)
+        # the per-kernel breakdown comes from ONE extra step with the HIP-event brackets on: a pass is a few dozen launches of
+        # microseconds each, and two event records per launch would be part of what is measured
+        am.api.check(lib.am_profile_reset()); am.api.check(lib.am_profile_enable(1))
+        step()
+        fence()
+        am.api.check(lib.am_profile_enable(0))
+        prof_steps = 1
+        prof = {}
+        for k in (b"sf", b"ac", b"rp_lds", b"rp_loop", b"rp_pass", b"rp_splice", b"rp_scans", b"rp_windows", b"rp_merge", b"permute", b"rp_ranges", b"rp_route", b"pt_build", b"pt_materialise", b"scan", b"hidx"):
+            ms, n = C.c_double(0), C.c_uint64(0)
+            am.api.check(lib.am_profile_read(k, C.byref(ms), C.byref(n)))
+            prof[k.decode()] = (ms.value, int(n.value))
     total_scanned = amdist.allreduce_sum([scanned], dev)[0]
     spliced = int(lib.am_replaced_spliced_bytes(last["res"]))
     if rank == 0:
+        out = {
+            "metric": "GiB/s of input rewritten by Replacer.run (50k pairs, all passes)", "value": round(n_bytes * world / float(1 << 30) * steps / elapsed, 3),
+            "unit": "GiB/s", "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(elapsed / steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+            "config": {"workload": workload, "n_pairs": len(pairs), "case": "IgnoreCase" if case else "CaseSensitive", "haystacks_per_gpu": n_hay,
+                       "haystack_bytes": w["hay_bytes"], "bytes_per_gpu": n_bytes, "parallelism": "haystack-sharded x%d" % world, "build_s": round(build_s, 2)},
+            "results": "device-resident (am_replacer_run_batch_device)",
+            "passes": passes, "scanned_gib_per_step": round(total_scanned / float(1 << 30), 2), "spliced_gib_per_step": round(spliced / float(1 << 30), 2),
+        }
+    if rank == 0 and full:
         # dominant kernel: since the scans after the first pass only cover windows around the replacements, it is
         # k_rp_splice (replace, Replacer.hs:163-180).  Algorithmic bytes per launch: every byte of the rewritten text is
         # read once and written once.
@@ -773,17 +908,10 @@ def measure_replacer(args, workload, rank, world, dev, steps=None, warmup=None, 
         step_ms = elapsed / steps * 1e3
         step_achieved = float(n_bytes + spliced) / (step_ms * 1e-3) / 1e9 if step_ms > 0 else 0.0
         rp_traffic, rp_traffic_source = pmc_traffic_entry(workload, "k_" + kname, n_bytes)
-        out = {
-            "metric": "GiB/s of input rewritten by Replacer.run (50k pairs, all passes)", "value": round(n_bytes * world / float(1 << 30) * steps / elapsed, 3),
-            "unit": "GiB/s", "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(elapsed / steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-            "config": {"workload": workload, "n_pairs": len(pairs), "case": "IgnoreCase" if case else "CaseSensitive", "haystacks_per_gpu": n_hay,
-                       "haystack_bytes": w["hay_bytes"], "bytes_per_gpu": n_bytes, "parallelism": "haystack-sharded x%d" % world, "build_s": round(build_s, 2)},
-            "results": "device-resident (am_replacer_run_batch_device)",
+        out.update({
             "host_results": {"value": round(n_bytes * world / float(1 << 30) * steps / elapsed_host, 3), "unit": "GiB/s", "ms_per_step": round(elapsed_host / steps * 1e3, 3),
                              "what": "am_replacer_run_batch: the same passes plus every rewritten text copied over PCIe into pinned host memory",
                              "settled_s": VRAM_WIPE_SETTLE_S},
-            "passes": passes, "scanned_gib_per_step": round(total_scanned / float(1 << 30), 2), "spliced_gib_per_step": round(spliced / float(1 << 30), 2),
             "kernel_ms_per_step": {k: round(v[0] / prof_steps, 3) for k, v in prof.items() if v[1]},
             "roofline": {"bound": "hbm", "kernel": "the step: first scan + k_%s + k_pt_materialise" % kname if kname in ("rp_loop", "rp_lds") else "k_" + kname,
                          "achieved": round(step_achieved if kname in ("rp_loop", "rp_lds") else achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
@@ -792,7 +920,7 @@ def measure_replacer(args, workload, rank, world, dev, steps=None, warmup=None, 
                          "traffic": rp_traffic, "traffic_source": rp_traffic_source, "avg_launch_ms": round(step_ms if kname in ("rp_loop", "rp_lds") else avg_ms, 4), "launches": prof[kname][1],
                          "alg_bytes_per_launch": int(alg_bytes),
                          "note": "k_%s runs every pass of every haystack (one wavefront per haystack): bound by dependent-load latency, not by HBM" % kname if kname in ("rp_loop", "rp_lds") else None},
-        }
+        })
         if world == 1 and not args.no_parity:
             out["parity"] = replacer_parity(args, w, pairs, case, rdev, batch, text, n_hay, n_bytes, last["res"], lib, dev, cpu_seconds=2.0 if extra else args.cpu_seconds)
             if not args.no_cpu_baseline:

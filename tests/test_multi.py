@@ -271,7 +271,7 @@ def test_bench_line_reduced(single_process):
     import json
     import sys
     env = dict(os.environ)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--hay-count", "96", "--steps", "2", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--hay-count", "96", "--steps", "2", "--warmup", "1"]
     if single_process:
         env["AM_BENCH_SINGLE_PROCESS"] = "1"
     else:
@@ -288,3 +288,59 @@ def test_bench_line_reduced(single_process):
     else:
         assert d["parity"]["hashed"] == 96 and d["parity"]["kernels_agree"] is True and d["parity"]["oracle_checked"] == 16
         assert d["cpu_baseline"]["cores"] == 1 and d["cpu_baseline"]["run_s"]["min"] > 0
+
+
+def _bench_plain(args, out_dir):
+    import json
+    import sys
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", str(out_dir)] + args
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.split("\n") if l.strip()]
+    assert len(lines) == 1, lines                                # ONE JSON line on stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["higher_is_better"] is True and d["unit"] == "GiB/s" and d["dtype"] == "u8" and d["value"] > 0
+    for extra in ("parity", "cpu_baseline", "h2d_inclusive", "workloads", "machine", "count_only_gibps", "host_results"):
+        assert extra not in d, extra                             # behind --full
+    files = {f: np.load(os.path.join(out_dir, f)) for f in sorted(os.listdir(out_dir))}
+    assert sum(os.path.getsize(os.path.join(out_dir, f)) for f in files) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    return d, files
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """bench.py without --full: the headline only (no parity gate, CPU baseline or other workloads), and --dump-outputs writes the last timed
+    step's records -- the same arrays on a second run with the same arguments."""
+    args = ["--hay-count", "96", "--steps", "3", "--warmup", "1"]
+    d, files = _bench_plain(args, tmp_path / "a")
+    per_hay = files["records_per_haystack.npy"]
+    assert per_hay.shape == (96,) and per_hay.sum() == d["records_per_step"] > 0
+    hay = files["records_haystack.npy"]
+    assert np.array_equal(files["sample_haystacks.npy"], np.arange(96))              # a batch of fewer than 256 haystacks: every record
+    assert hay.size == files["records_end_pos.npy"].size == files["records_state.npy"].size == d["records_per_step"]
+    assert np.all(np.diff(hay) >= 0) and np.array_equal(np.bincount(hay.astype(np.int64), minlength=96), per_hay)
+    # each column is what it says: three haystacks' records expanded against the oracle's run over the same generated text
+    w = synth.WORKLOADS["cfg3_runLower_100k_10GiB"]
+    needles = synth.needles_for("cfg3_runLower_100k_10GiB")
+    m = oracle.Machine(needles)
+    picks = [0, 47, 95]
+    cells = w["hay_bytes"] // synth.CELL
+    texts = [synth.haystacks_host(needles, w["mixed"], h * cells, cells).tobytes() for h in picks]
+    exp = [(picks[i], p, v) for i, p, v in oracle_triples(m, am.IGNORE_CASE, texts)]
+    sel = np.isin(hay, picks)
+    got = expand_records(m.values_off(), m.values(), hay[sel].astype(np.int64), files["records_state.npy"][sel].astype(np.int64),
+                         files["records_end_pos.npy"][sel].astype(np.int64))
+    assert got == exp and len(got) > 100
+    _, again = _bench_plain(args, tmp_path / "b")
+    assert files.keys() == again.keys() and all(np.array_equal(files[k], again[k]) for k in files)
+
+
+@pytest.mark.gpu
+def test_bench_replacer_plain_line_and_dump_outputs(tmp_path):
+    """The replacer workload without --full: the device-resident steps only; --dump-outputs writes the rewritten texts of the last timed step."""
+    d, files = _bench_plain(["--workload", "cfg5_replacer_50k_1GiB", "--hay-count", "64", "--steps", "3", "--warmup", "1"], tmp_path)
+    lengths, sample = files["text_lengths.npy"], files["sample_haystacks.npy"]
+    assert lengths.shape == (64,) and np.all(lengths >= 0) and np.array_equal(sample, np.arange(64))
+    assert np.array_equal(files["sample_lengths.npy"], lengths) and files["sample_bytes.npy"].size == lengths.sum()
+    assert files["sample_bytes.npy"].max() < 256 and d["passes"] >= 1

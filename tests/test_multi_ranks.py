@@ -143,7 +143,7 @@ def test_bench_n_rank_path_with_the_stand_in(tmp_path):
     env = dict(os.environ, AM_BENCH_SAME_DEVICE="1", AM_BENCH_BACKEND="gloo", AM_RCCL_LIBRARY=am.build.build_rccl_stub(),
                MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29617",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "cfg4_100k_1M_haystacks", "--total-haystacks", "4096", "--parity-oracle-mib", "16"]
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "cfg4_100k_1M_haystacks", "--total-haystacks", "4096", "--parity-oracle-mib", "16"]
     try:
         p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     finally:
@@ -157,3 +157,30 @@ def test_bench_n_rank_path_with_the_stand_in(tmp_path):
     assert out["rccl"]["ranks"] == 2 and out["rccl"]["image_broadcast_ms"] > 0 and out["rccl"]["allreduce_ms"] > 0 and out["rccl"]["data_path_collectives"] == 0
     assert out["config"]["haystacks_per_gpu"] == 2048 and out["parity"]["hashed"] == 4096 and out["parity"]["kernels_agree"] is True
     assert out["parity"]["oracle_checked"] >= 100
+
+
+@pytest.mark.gpu
+def test_bench_n_rank_plain_line_with_the_stand_in(tmp_path):
+    """The same two-rank bench.py run without --full: the headline only (bytes and records summed over the ranks by am_multi_allreduce_sum), and
+    --dump-outputs writes each rank's records of the last timed step with a rank prefix."""
+    env = dict(os.environ, AM_BENCH_SAME_DEVICE="1", AM_BENCH_BACKEND="gloo", AM_RCCL_LIBRARY=am.build.build_rccl_stub(),
+               MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29618",
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "cfg4_100k_1M_haystacks", "--total-haystacks", "4096",
+           "--dump-outputs", str(tmp_path)]
+    try:
+        p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
+    finally:
+        for d in glob.glob("/dev/shm/am_rccl_stub_*"):
+            shutil.rmtree(d, ignore_errors=True)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    line = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(line) == 1, p.stdout
+    out = json.loads(line[0])
+    assert out["n_gpus"] == 2 and out["collectives"] == "libam-rccl" and out["config"]["haystacks_per_gpu"] == 2048
+    assert "parity" not in out and "matches_per_step" not in out and out["value"] > 0 and out["ms_per_step"] > 0
+    per_rank = [np.load(str(tmp_path / ("rank%d_records_per_haystack.npy" % r))) for r in range(2)]
+    assert all(a.shape == (2048,) and a.dtype == np.float64 for a in per_rank)
+    assert sum(a.sum() for a in per_rank) == out["records_per_step"] > 0
+    assert sum(os.path.getsize(str(f)) for f in tmp_path.iterdir()) <= 64 * 10 ** 6                # the run's budget, over both ranks' files
+    assert all(np.load(str(tmp_path / ("rank%d_sample_haystacks.npy" % r))).size == 128 for r in range(2))   # 256 sampled haystacks shared by 2 writers

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/$1; mkdir -p $OUT
 cd $R
 (timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; echo "pytest rc $?" >> $OUT/pytest.log); tail -3 $OUT/pytest.log
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.log 2> $OUT/bench_default.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.log 2> $OUT/bench_default.err; echo "bench rc=$?"
 bash tools/experiments/prof_trace.sh $1
 bash $R/tools/pmc_traffic.sh $OUT/traffic
 bash tools/experiments/dfa_pmc6.sh $1/dfa_pmc 0 > $OUT/dfa_pmc_summary.txt 2>&1; rm -rf $OUT/dfa_pmc/*/; tail -2 $OUT/dfa_pmc_summary.txt

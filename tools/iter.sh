@@ -10,7 +10,7 @@ if [ "$MODE" = "full" ]; then
 else
   timeout 600 python -m pytest tests/test_gpu_parity.py tests/test_gpu_configs.py -m gpu -x -q -k "golden or edge or fragment or synthetic or full_size or soak or cfg4 or fold_hash or pool" > $OUT/tests.log 2>&1; echo "tests rc=$?"; tail -3 $OUT/tests.log
 fi
-timeout 600 python bench.py --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench.log 2>&1; echo "bench rc=$?"
+timeout 600 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench.log 2>&1; echo "bench rc=$?"
 python - <<PY
 import json
 for l in open("$OUT/bench.log"):
@@ -18,7 +18,7 @@ for l in open("$OUT/bench.log"):
         d=json.loads(l); r=d["roofline"]; print("BENCH value %.1f GiB/s ms/step %.3f k_sf %.3f ms frac %.4f count_only %.1f parity %s" % (d["value"], d["ms_per_step"], r["avg_launch_ms"], r["frac"], d["count_only_gibps"], d.get("parity",{}).get("kernels_agree")))
 PY
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VMEM_WR --kernel-trace -d $OUT/pmc -o p -- python $R/bench.py --hay-count 2048 --steps 2 --warmup 1 --no-cpu-baseline --no-parity > $OUT/pmc.log 2>&1
+timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VMEM_WR --kernel-trace -d $OUT/pmc -o p -- python $R/bench.py --full --hay-count 2048 --steps 2 --warmup 1 --no-cpu-baseline --no-parity > $OUT/pmc.log 2>&1
 python $R/tools/pmc_summary.py $OUT/pmc "k_sf<true, 1" > $OUT/insts.txt 2>&1
 python - <<PY
 vals={}

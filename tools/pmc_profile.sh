@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 ARGS="--hay-count 2048 --steps 2 --warmup 1 --no-cpu-baseline $*"
 pass() {
   name=$1; shift
-  timeout 600 rocprofv3 --pmc "$@" --kernel-trace -d "$OUT/$name" -o "$name" -- python "$R/bench.py" $ARGS > "$OUT/$name.log" 2>&1
+  timeout 600 rocprofv3 --pmc "$@" --kernel-trace -d "$OUT/$name" -o "$name" -- python "$R/bench.py" --full $ARGS > "$OUT/$name.log" 2>&1
   echo "pass $name rc=$?"
 }
 pass tcc_fetch FETCH_SIZE TCC_HIT_sum

@@ -21,7 +21,7 @@ for f in os.listdir(D):
 cb = plain["cpu_baseline"]
 open(os.path.join(P, "%s_kernel_trace_%s.md" % (RND, V)), "w").write('''# %s -- k_sf (%s), rocprofv3 --kernel-trace --stats
 
-Command on the MI355X box (tools/profile_round.sh): `cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace --stats -d gpurun_out/%s/kt -o kt -- python bench.py --no-cpu-baseline`
+Command on the MI355X box (tools/profile_round.sh): `rocprofv3 --kernel-trace --stats -d <out>/%s/kt -o kt -- python bench.py --full --no-cpu-baseline`
 (default workload: cfg3, 100k-needle IgnoreCase automaton, 10240 x 1 MiB = 10 GiB per step, 1 warm-up + 5 timed steps + 1 count-only call, then the
 parity gate: both kernels over every haystack + k_fold_hash -- the two k_ac launches below belong to the gate, not to the timed steps)
 
@@ -90,7 +90,7 @@ if os.path.exists(os.path.join(D, "bench_cfg5_replacer_50k_1GiB.log")) and os.pa
     r5 = line("bench_cfg5_replacer_50k_1GiB.log")
     open(os.path.join(P, "%s_replacer_trace_%s.md" % (RND, V)), "w").write('''# %s -- Replacer.run on config 5 (%s), rocprofv3 --kernel-trace --stats
 
-    Command: `rocprofv3 --kernel-trace --stats -- python bench.py --workload cfg5_replacer_50k_1GiB --steps 3 --warmup 1 --no-cpu-baseline`
+    Command: `rocprofv3 --kernel-trace --stats -- python bench.py --full --workload cfg5_replacer_50k_1GiB --steps 3 --warmup 1 --no-cpu-baseline`
     (16384 x 64 KiB, 50 000 pairs; every step is one full scan, ONE k_rp_loop launch that runs all ~160 passes of every haystack, and one materialise launch; the trace covers the device-resident steps, the
     host-result steps (am_replacer_run_batch: the `__amd_rocclr_copyBuffer` rows are their device-to-host copies) and one profiled step)
 
