@@ -1184,7 +1184,6 @@ static int run_records_small(const am_automaton* a, int case_mode, am_batch* b, 
     if (b->total == 0 || b->total > kSmallRunBytes || a->kernel_pref == 3) return AM_OK;
     Plan p; AM_TRY(make_plan(a, case_mode, b, p));
     if (p.nothing || p.dense || !p.use_sf) return AM_OK;
-    if (cfg::on(cfg::kNoSmallRun)) return AM_OK;                             // A/B
     std::lock_guard<std::mutex> lk(b->mu);
     ON_DEVICE(b->dev);
     hipStream_t st; AM_TRY(get_stream(b->dev, &st));
@@ -1854,7 +1853,7 @@ extern "C" int am_debug_set_general_kernel(void* launcher, uint32_t image_versio
     return AM_OK;
 }
 
-// cycle sums per k_sf phase for launches made under AM_SF_ABLATE=9
+// cycle sums per k_sf phase for launches made under AM_SF_TRACE
 extern "C" int am_debug_sf_phase_cycles(uint64_t* out5)
 {
     HIP_TRY(hipDeviceSynchronize());

@@ -42,9 +42,9 @@ struct ScanOut {
     // ids mode (containsAll): machineValues in flat form = the needle ids a state reports; one row of ids_words 32-bit words per haystack;
     // ids_missing[h] = ids of haystack h not seen yet (starts at the number of needles: the bit that brings it to 0 raises flags[h])
     const uint64_t* ids_vals_off; const uint32_t* ids_vals; uint32_t* ids_bits; uint32_t* ids_missing; uint32_t ids_words, ids_n;
-    uint32_t probe_two;           // A/B (AM_SF_PROBE_TWO=1): the two-candidates-per-lane instantiation also for automata with few 4-byte-suffix keys
-    uint32_t ablate;              // timing experiments only (AM_SF_ABLATE); 0 in production
-    uint64_t* dbg;                // timing experiments only: per-phase cycle sums
+    uint32_t two_always;          // set by launch_sf: 0.  k_sf<ILP = 1> reads it (non-zero: every probe round takes two candidates per lane).  Like wq_iters a constant
+                                  // that stays an argument: folding it into the kernel changes the code of those instantiations (registers, spills), which is a kernel change to measure
+    uint64_t* dbg;                // AM_SF_TRACE only: per-phase cycle sums
 };
 
 constexpr uint32_t kPoolBlock = 64;   // records per pool block (1 KiB)
@@ -165,7 +165,7 @@ struct RpLoop {
                                                             // priority is minus its index (Replacer.hs:100-104): k_rp_lds needs no payload column (am_rplds.hip, PLI)
 };
 hipError_t launch_rp_loop_caps(const uint64_t* rec_first, uint32_t n_hay, uint32_t* cap_r2, uint32_t* cap_p2, uint32_t* max_records /* atomic max, cleared by the caller */, hipStream_t st);
-hipError_t launch_rp_loop(bool ic, const RpLoop& a, uint32_t n /* haystacks from a.h_first */, int waves_per_simd, hipStream_t st);
+hipError_t launch_rp_loop(bool ic, const RpLoop& a, uint32_t n /* haystacks from a.h_first */, hipStream_t st);
 hipError_t launch_rp_lds(bool ic, const RpLoop& a, uint32_t n /* haystacks from a.h_first */, hipStream_t st);
 hipError_t launch_pt_init(const uint64_t* offsets, uint32_t n_act, RpPiece* pieces, uint64_t* pc_start, uint32_t* pc_cnt, hipStream_t st);
 hipError_t launch_pt_count(const RpHay* hs, const uint32_t* pc_cnt, uint32_t n_act, uint32_t* need, uint32_t* nwin, hipStream_t st);

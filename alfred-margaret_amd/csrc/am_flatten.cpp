@@ -143,6 +143,7 @@ struct Blob {
 uint32_t log2_ceil(uint64_t n) { uint32_t l = 0; while ((1ull << l) < n) l++; return l; }
 
 struct TierEntry { uint32_t key, node; };
+constexpr uint32_t kSfMaxBloomLog2Words = 15; // cap on the LDS filter: 128 KiB of the CU's 160 KiB LDS
 constexpr size_t kDfaSmallStates = 32768;     // automata up to this many states get a DFA section unasked (am_flatten.cpp, DFA section)
 
 }  // namespace
@@ -908,8 +909,7 @@ int flatten(const RefArrays& ref, int case_mode, std::vector<uint8_t>& image, st
                     // 256 bytes of which text touches the first half; here two rows (hot_log2 = 4) share a 128-byte line, and rows of about the same weight are neighbours,
                     // so the L2 of an XCD holds twice the rows per MiB for the classes that are 85 % of natural text.  (Column 0 -- bytes no needle contains -- leads to the
                     // root from everywhere and is in neither LDS nor the hot table: the walk answers it without a load.)
-                    long hot_cfg = cfg::get(cfg::kDfaHotLog2);
-                    uint32_t hot_lc = hot_cfg >= 1 && hot_cfg <= 8 ? (uint32_t)hot_cfg : 4u;
+                    uint32_t hot_lc = 4;          // 16 columns
                     while (hot_lc > 0 && (1u << hot_lc) > C - 1u) hot_lc--;
                     std::vector<uint32_t> hot2((size_t)n_rows << hot_lc);
                     for (uint32_t r = 0; r < n_rows; r++)
@@ -933,9 +933,7 @@ int flatten(const RefArrays& ref, int case_mode, std::vector<uint8_t>& image, st
         if (dfa_cfg == cfg::kUnset && !cfg::on(cfg::kSfNoChildren)) {
             size_t keys = 0, potential = 0;
             for (int t = 0; t < 4; t++) keys += tier_entries[t].size();
-            uint32_t max_lw = 15;
-            { const long v = cfg::get(cfg::kSfMaxBloomLog2Words); if (v >= 8 && v <= 15) max_lw = (uint32_t)v; }
-            if (std::max(8u, std::min(max_lw, log2_ceil((keys * 16 + 31) / 32))) < 15) {
+            if (std::max(8u, std::min(kSfMaxBloomLog2Words, log2_ceil((keys * 16 + 31) / 32))) < 15) {
                 for (const TierEntry& e : tier_entries[3]) { const SfNode& nd = nodes[e.node]; const uint32_t c = nd.w & 0xFFFFu; if (!nd.x && c >= 2) potential += c; }
                 likely = potential >= tier_entries[3].size() && potential > 0;
             }
@@ -952,9 +950,7 @@ int flatten(const RefArrays& ref, int case_mode, std::vector<uint8_t>& image, st
     for (int t = 0; t < 4; t++) { if (!tier_entries[t].empty()) h.sf_tiers |= 1u << t; total_keys += tier_entries[t].size(); }
     {
         uint32_t lw = log2_ceil((total_keys * 16 + 31) / 32);
-        uint32_t max_lw = 15;                                  // 128 KiB of the CU's 160 KiB LDS
-        { const long v = cfg::get(cfg::kSfMaxBloomLog2Words); if (v >= 8 && v <= 15) max_lw = (uint32_t)v; }
-        lw = std::max(8u, std::min(max_lw, lw));
+        lw = std::max(8u, std::min(kSfMaxBloomLog2Words, lw));
         h.sf_bloom_log2_words = lw;
         std::vector<uint32_t> bloom((size_t)1 << lw, 0);
         for (int t = 0; t < 4; t++)

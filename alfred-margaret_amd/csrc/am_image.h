@@ -463,7 +463,7 @@ AM_HD uint32_t t4_slot_diff(uint32_t slot, uint32_t expect)
 // two 8-byte buckets.
 template <int N>
 AM_HD void sf_probe_issue(const SfView& s, const uint32_t (&w)[N], const uint32_t (&nbs)[N], const uint64_t (&avail)[N], const bool (&valid)[N],
-                          u32x2 (&ba)[N], u32x2 (&bb)[N], uint32_t (&expect)[N], const bool one_bucket = false /* timing experiment (AM_SF_ABLATE=12): the second load asks for the first bucket again; wrong results */)
+                          u32x2 (&ba)[N], u32x2 (&bb)[N], uint32_t (&expect)[N])
 {
     const uint32_t lb = s.tier_log2_cap[3];
 #pragma unroll
@@ -474,7 +474,7 @@ AM_HD void sf_probe_issue(const SfView& s, const uint32_t (&w)[N], const uint32_
         ba[k] = u32x2{0, 0}; bb[k] = ba[k];                      // empty buckets for the lanes that do not probe
         if (probe) {
 #if defined(__HIP_DEVICE_COMPILE__)
-            const uint2 ra = *reinterpret_cast<const uint2*>(s.t4_hot + t4_bucket(ha, lb)), rb = *reinterpret_cast<const uint2*>(s.t4_hot + t4_bucket(one_bucket ? ha : hb, lb));
+            const uint2 ra = *reinterpret_cast<const uint2*>(s.t4_hot + t4_bucket(ha, lb)), rb = *reinterpret_cast<const uint2*>(s.t4_hot + t4_bucket(hb, lb));
             ba[k] = u32x2{ra.x, ra.y}; bb[k] = u32x2{rb.x, rb.y};
 #else
             ba[k] = s.t4_hot[t4_bucket(ha, lb)]; bb[k] = s.t4_hot[t4_bucket(hb, lb)];
@@ -882,13 +882,13 @@ AM_HD void sf_resolve_short(const SfView& s, const bool (&valid)[N], const uint3
 template <bool IC, int N, bool SHORT = true, class Between = SfNoHook>
 AM_HD void sf_resolve_n(const SfView& s, const uint8_t* text, const uint64_t (&gpos)[N], const uint64_t (&avail64)[N], const bool (&valid)[N],
                         const uint32_t (&hint)[N], bool (&found)[N], uint32_t (&state)[N], uint32_t (&vlen)[N], Between between = Between(),
-                        uint64_t* dbg_iters = nullptr, uint32_t dbg_ablate = 0)
+                        uint64_t* dbg_iters = nullptr)
 {
     uint32_t w[N], w2[N], avail[N], best_state[N], best_vlen[N], depth[N], node[N], t16[N][4];
     bool go[N], have_rec[N];
     SfNode rec[N];
     sf_resolve_head<IC, N>(s, text, gpos, avail64, valid, hint, between, w, w2, avail, best_state, best_vlen, depth, go, node, rec, have_rec, t16, dbg_iters);
-    if (dbg_ablate != 11) sf_resolve_walk<IC, N>(s, text, gpos, avail, w2, go, node, rec, have_rec, depth, best_state, best_vlen, dbg_iters, 0xFFFFFFFFu, t16);
+    sf_resolve_walk<IC, N>(s, text, gpos, avail, w2, go, node, rec, have_rec, depth, best_state, best_vlen, dbg_iters, 0xFFFFFFFFu, t16);
     if (SHORT) sf_resolve_short<N>(s, valid, avail, w, best_state, best_vlen);
 #pragma unroll
     for (int k = 0; k < N; k++) {

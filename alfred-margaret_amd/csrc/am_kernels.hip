@@ -67,6 +67,7 @@ constexpr uint64_t kSfLightChunks = 16;          // batches of up to 16 KiB take
 constexpr int kSfQ1 = 128;                       // per-wave queue of candidate positions (u16, offset in the chunk); more take several sub-passes
 constexpr int kSfQ2 = 256;                       // per-wave ring of deferred positions (u16: chunk-in-unit << 12 | agreeing slot << 10 | offset): candidates that need the exact look
 constexpr uint32_t kSfMaxUnitChunks = 64;
+constexpr uint32_t kSfWqIters = 2;               // trie steps a resolve batch takes before it parks the walkers that are not done (ScanOut::wq_iters)
 constexpr uint32_t kSfEpochChunks = 16;          // the ring is drained every 16 chunks, so that the chunk index fits the 4 bits an entry has for it
 constexpr int kSfStage = 1056;                   // per-wave copy of the current chunk (folded): 8 bytes before it at offset 8, the chunk at 16, padding
 constexpr uint32_t kSfMaskBytes = kBloomMasks * 4u;      // the Bloom mask table: first thing in LDS, the filter words follow
@@ -91,8 +92,8 @@ constexpr uint32_t kSfMaskBytes = kBloomMasks * 4u;      // the Bloom mask table
 // LW: log2 of the filter size in words when it is the usual 128 KiB (15), so that the word address is a
 // constant shift + constant mask (VOP2 with immediates issues at almost twice the rate of anything that
 // reads an SGPR or needs the VOP3 encoding on gfx950, tools/microbench/valu_rates*.hip); 0 = any size
-// DBG: the timing / ablation experiments (AM_SF_ABLATE) live in their own instantiations, the production kernel
-// carries none of their code, registers or branches.
+// DBG: the phase timing (AM_SF_TRACE) lives in its own instantiations, the production kernel carries none of its
+// code, registers or branches.
 template <bool IC, int MODE, int ILP, int LW, bool SHORT, bool DBG, int NT = kSfThreads, bool CHILDREN = false>
 __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uint64_t n_chunks)
 {
@@ -140,9 +141,8 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
     uint32_t unit_count = 0, unit_slots = 0, cur_block = kNone, first_block = kNone, grant_next = 0, grant_left = 0;   // unit_slots: record slots taken (found + parked walkers); unit_count: records
     bool pool_ok = true;
 
-    // optional phase timing (AM_SF_ABLATE>=8): s_memtime deltas per wavefront, summed into o.dbg
+    // optional phase timing (AM_SF_TRACE): s_memtime deltas per wavefront, summed into o.dbg
     const bool timing = DBG && o.dbg != nullptr;
-    const uint32_t ablate = DBG ? o.ablate : 0u;
     uint64_t t_filter = 0, t_compact = 0, t_probe = 0, t_resolve = 0, t_probe_pre = 0, t_mark = 0;
     uint64_t dbg_iters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t t_r0 = 0, t_r1 = 0, t_r2 = 0, t_r3 = 0, n_batches = 0, n_cand = 0, n_probes = 0, n_defer = 0, n_found = 0;
@@ -253,7 +253,7 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
             uint32_t w[RN], node[RN], t16[RN][4];
             bool go[RN], have_rec[RN], found[RN];
             sf_resolve_head<IC, RN>(s, b.text, gpos, end_pos, valid, hint, locate, w, w2, avail, best_state, best_vlen, depth, go, node, rec, have_rec, t16, timing ? dbg_iters : nullptr);
-            if (ablate != 11) sf_resolve_walk<IC, RN>(s, b.text, gpos, avail, w2, go, node, rec, have_rec, depth, best_state, best_vlen, timing ? dbg_iters : nullptr, wq_cap ? o.wq_iters : 0xFFFFFFFFu, t16, sel);
+            sf_resolve_walk<IC, RN>(s, b.text, gpos, avail, w2, go, node, rec, have_rec, depth, best_state, best_vlen, timing ? dbg_iters : nullptr, wq_cap ? o.wq_iters : 0xFFFFFFFFu, t16, sel);
 #pragma unroll
             for (int k = 0; k < RN; k++) parked[k] = go[k] && valid[k];      // still walking after two steps (only with a walker queue)
             if (SHORT) {
@@ -461,7 +461,6 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
                 sf_probe_heavy<2>(s, p_a, p_b, p_e, defer, heavy);
                 if (wave_any(heavy[0] || heavy[1])) sf_probe_children<2>(s, p_k5, p_e5, heavy, defer, hint);
             }
-            if (ablate == 4) { defer[0] = false; defer[1] = false; }      // timing experiment only: no resolve
             park(defer[0], hint[0], p_pos[0]);
             park(defer[1], hint[1], p_pos[1]);
         } else {
@@ -476,7 +475,6 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
                 sf_probe_heavy<1>(s, a1, b1, e1, defer, heavy);
                 if (wave_any(heavy[0])) { const uint32_t k5[1] = {p_k5[0]}, e5[1] = {p_e5[0]}; sf_probe_children<1>(s, k5, e5, heavy, defer, hint); }
             }
-            if (ablate == 4) defer[0] = false;
             park(defer[0], hint[0], p_pos[0]);
         }
         pending = false;
@@ -653,7 +651,6 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
             }
             __builtin_amdgcn_s_setprio(2);
             if (p0 + 16 > b.total) cand &= p0 < b.total ? (1u << (uint32_t)(b.total - p0)) - 1u : 0u;
-            if (ablate == 1) cand = 0;               // timing experiment only
             if (timing) { asm volatile("" :: "v"(cand)); tick(t_filter); }
 
             // Probe pipeline: the two hot buckets of a round's candidates are REQUESTED at the end of a chunk's iteration and LOOKED AT
@@ -687,11 +684,11 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
                     tick(t_resolve);
                 }
                 // request this round: up to 128 survivors, two per lane
-                if (n_q1 && ablate != 5) {
+                if (n_q1) {
                     uint64_t avail[2] = {0, 0};
                     uint32_t w[2] = {0, 0}, nb[2] = {0, 0};
                     bool valid[2] = {false, false};
-                    const bool two = ILP == 2 || n_q1 > 64u || o.probe_two;      // (uniform; ILP == 2: a constant, the branches below are not there)
+                    const bool two = ILP == 2 || n_q1 > 64u || o.two_always;      // (uniform; ILP == 2: a constant, the branches below are not there)
                     p_pos[1] = 0u;
 #pragma unroll
                     for (int k = 0; k < 2; k++) {
@@ -724,13 +721,13 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
                         if (valid[k] && !single) avail[k] = gpos - b.offsets[find_haystack(b, gpos)] + 1;
                         p_pos[k] = valid[k] ? (pos | 0x8000u) : 0u;
                     }
-                    if (two) sf_probe_issue<2>(s, w, nb, avail, valid, p_a, p_b, p_e, ablate == 12);
+                    if (two) sf_probe_issue<2>(s, w, nb, avail, valid, p_a, p_b, p_e);
                     else {
                         const uint32_t w1[1] = {w[0]}, nb1[1] = {nb[0]};
                         const uint64_t av1[1] = {avail[0]};
                         const bool v1[1] = {valid[0]};
                         u32x2 a1[1], b1[1]; uint32_t e1[1];
-                        sf_probe_issue<1>(s, w1, nb1, av1, v1, a1, b1, e1, ablate == 12);
+                        sf_probe_issue<1>(s, w1, nb1, av1, v1, a1, b1, e1);
                         p_a[0] = a1[0]; p_b[0] = b1[0]; p_e[0] = e1[0];
                     }
                     p_two = two;
@@ -858,12 +855,10 @@ static size_t sf_lds_bytes_w(const SfView& s, int waves) { return kSfMaskBytes +
 // walker-queue entries per wavefront that fit next to the rest (0 when fewer than 64 would: the queue must take a whole batch)
 static uint32_t sf_wq_cap(const SfView& s, int waves)
 {
-    const long forced = cfg::get(cfg::kSfWq);      // A/B: 0 = no queue
     const size_t base = sf_lds_bytes_w(s, waves), limit = 160 * 1024;
     if (base >= limit) return 0;
     size_t cap = (limit - base) / ((size_t)waves * 64);
     if (cap > 128) cap = 128;
-    if (forced >= 0 && (size_t)forced < cap) cap = (size_t)forced;
     return cap >= 64 ? (uint32_t)cap : 0u;
 }
 size_t sf_lds_bytes(const SfView& s) { return sf_lds_bytes_w(s, kSfWaves); }
@@ -891,9 +886,7 @@ static hipError_t launch_sf_v(const SfView& s, const BatchView& b, const ScanOut
     if (blocks == 0) return hipSuccess;
     ScanOut oo = o;
     oo.wq_cap = wq_cap;
-    const long wqi = cfg::get(cfg::kSfWqIters);
-    const uint32_t wq_iters = wqi >= 1 && wqi <= 16 ? (uint32_t)wqi : 2u;   // A/B: steps a batch walks before it parks
-    oo.wq_iters = wq_iters;
+    oo.wq_iters = kSfWqIters;
     if (n_units <= blocks * waves_per_wg) oo.next_unit = nullptr;          // one unit per wavefront at most: nothing to draw
     // (else: *next_unit is zero -- it lives in the batch's 64-byte counter block, which every caller clears before the launch together with
     // its other counters; a memset of its own here was one more dispatch in every call)
@@ -902,7 +895,7 @@ static hipError_t launch_sf_v(const SfView& s, const BatchView& b, const ScanOut
 }
 
 static uint64_t* g_sf_dbg = nullptr;
-// debug: per-phase s_memtime sums of k_sf launches run with AM_SF_ABLATE=9 (filter, compact, probe, resolve, waves)
+// debug: per-phase s_memtime sums of k_sf launches run under AM_SF_TRACE (filter, compact, probe, resolve, waves)
 hipError_t read_sf_wave_records(uint64_t* out, size_t n_waves)
 {
     if (!g_sf_dbg) return hipErrorInvalidValue;
@@ -931,7 +924,7 @@ static hipError_t launch_sf_t(const SfView& s, const BatchView& b, const ScanOut
             return (s.tiers & 7u) ? launch_sf_v<IC, MODE, 2, 0, true, false, kSfLightThreads>(s, b, o, n_cu, st) : launch_sf_v<IC, MODE, 2, 0, false, false, kSfLightThreads>(s, b, o, n_cu, st);
         return (s.tiers & 7u) ? launch_sf_v<IC, MODE, 2, 0, true>(s, b, o, n_cu, st) : launch_sf_v<IC, MODE, 2, 0, false>(s, b, o, n_cu, st);
     } else {
-    if ((o.ablate || o.dbg) && !kFlagMode) {                                          // experiments (AM_SF_ABLATE)
+    if (o.dbg && !kFlagMode) {                                                        // the instrumented instantiations (AM_SF_TRACE)
         if (!lw15) return launch_sf_v<IC, MODE, 2, 0, true, true>(s, b, o, n_cu, st);
         return (s.tiers & 7u) ? launch_sf_v<IC, MODE, 2, 15, true, true>(s, b, o, n_cu, st) : launch_sf_v<IC, MODE, 2, 15, false, true>(s, b, o, n_cu, st);
     }
@@ -941,7 +934,7 @@ static hipError_t launch_sf_t(const SfView& s, const BatchView& b, const ScanOut
     // a dictionary with heavy suffix nodes (the image has five-byte child entries): its own instantiation, two candidates per lane whatever the table's size
     // (such text leaves hundreds of candidates per chunk)
     if (!lw15 && s.t4_children && !(s.tiers & 7u) && !kFlagMode) return launch_sf_v<IC, MODE, 2, 0, false, false, kSfThreads, true>(s, b, o, n_cu, st);
-    const bool few = s.tier_log2_cap[3] <= 15u && !o.probe_two;
+    const bool few = s.tier_log2_cap[3] <= 15u;
     if (s.tiers & 7u) {                                                                     // needles shorter than 4 bytes present
         if (few) return lw15 ? launch_sf_v<IC, MODE, 1, 15, true>(s, b, o, n_cu, st) : launch_sf_v<IC, MODE, 1, 0, true>(s, b, o, n_cu, st);
         return lw15 ? launch_sf_v<IC, MODE, 2, 15, true>(s, b, o, n_cu, st) : launch_sf_v<IC, MODE, 2, 0, true>(s, b, o, n_cu, st);
@@ -954,11 +947,9 @@ static hipError_t launch_sf_t(const SfView& s, const BatchView& b, const ScanOut
 hipError_t launch_sf(bool ic, int mode, const SfView& s, const BatchView& b, const ScanOut& o_in, int n_cu, hipStream_t st)
 {
     ScanOut o = o_in;
-    const uint32_t ablate = cfg::get(cfg::kSfAblate) > 0 ? (uint32_t)cfg::get(cfg::kSfAblate) : 0u;
-    o.ablate = ablate;
-    o.probe_two = cfg::on(cfg::kSfProbeTwo) ? 1u : 0u;
+    o.two_always = 0;
     static uint64_t* dbg = nullptr;
-    if (ablate >= 8 && ablate != 12) {                     // (12: the one-bucket timing experiment, no phase sums)
+    if (cfg::on(cfg::kSfTrace)) {
         if (!dbg) { if (hipMalloc((void**)&dbg, 256 + 16 * 8192) != hipSuccess) dbg = nullptr; else (void)hipMemset(dbg, 0, 256 + 16 * 8192); }
         o.dbg = dbg;
         g_sf_dbg = dbg;

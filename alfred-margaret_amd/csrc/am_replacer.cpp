@@ -609,14 +609,14 @@ int replacer_run(const am_replacer* r, const am_batch* in, uint64_t max_length, 
     if (n_hay == 0) return AM_OK;
     if (in->dev != r->a->dev) return fail(AM_ERR_INVALID, "replacer and batch live on different devices");
     {
-        // CaseSensitive replacers on the suffix-filter route keep the texts as piece tables (AM_RP_SPLICE=1: the splicing loop, for A/B and tests)
+        // CaseSensitive replacers on the suffix-filter route keep the texts as piece tables
         const Flavor* fl = nullptr;
         AM_TRY(prepare(r->a, r->case_mode, &fl));
         // ... when the batch is made of many documents: the piece-table kernels give a haystack to ONE wavefront, the splicing loop
         // cuts every text into 16-KiB tiles.  One 1-MB document with half a million replacements per pass: 472 ms vs 90 ms (measured).
         const bool many_documents = n_hay >= 64 && in->total / n_hay <= (1ull << 20);
         const bool pt = r->case_mode == AM_CASE_SENSITIVE && fl->h.sf_enabled && fl->h.root_vlen == 0 && r->a->kernel_pref != 1 &&
-                        !cfg::on(cfg::kRpFullScans) && !cfg::on(cfg::kRpSplice) && (many_documents || cfg::on(cfg::kRpPieces)) &&
+                        !cfg::on(cfg::kRpFullScans) && (many_documents || cfg::on(cfg::kRpPieces)) &&
                         n_hay < (1u << 24) && in->total < (1ull << 40);        // RpWin::src_abs packs (haystack index << 40 | start): beyond that the splicing loop runs
         if (pt) return replacer_run_pt(r, in, max_length, res, fl);
     }
@@ -875,7 +875,7 @@ static int replacer_run_loop(const am_replacer* r, const am_batch* in, uint64_t 
     if (sw != 1) {
         // unset: batches of many documents, and no switch that asks for one of the other loops
         if (!(n_hay >= 64 && in->total / n_hay <= (1ull << 20))) return AM_OK;
-        for (cfg::Key k : {cfg::kRpFullScans, cfg::kRpSplice, cfg::kRpPieces, cfg::kRpParallelFold, cfg::kRpGroups, cfg::kRpNoFuse, cfg::kRpNoRangeReuse, cfg::kRpNoSpin, cfg::kRpMatMain})
+        for (cfg::Key k : {cfg::kRpFullScans, cfg::kRpPieces, cfg::kRpParallelFold, cfg::kRpGroups, cfg::kRpNoFuse, cfg::kRpNoRangeReuse, cfg::kRpNoSpin, cfg::kRpMatMain})
             if (cfg::get(k) != cfg::kUnset) return AM_OK;
     }
     // how far a replacement's neighbourhood reaches = the longest needle in haystack bytes: for CaseSensitive replacers the byte depth of the
@@ -999,7 +999,7 @@ static int replacer_run_loop(const am_replacer* r, const am_batch* in, uint64_t 
         const uint32_t h0 = group_lo(g), h1 = group_lo(g + 1);
         a.h_first = h0;
         if (use_lds) { Prof pr("rp_lds", st); HIP_TRY(launch_rp_lds(r->case_mode == AM_IGNORE_CASE, a, h1 - h0, st)); }
-        { Prof pr("rp_loop", st); HIP_TRY(launch_rp_loop(r->case_mode == AM_IGNORE_CASE, a, h1 - h0, (int)cfg::get(cfg::kRpLoopWaves), st)); }
+        { Prof pr("rp_loop", st); HIP_TRY(launch_rp_loop(r->case_mode == AM_IGNORE_CASE, a, h1 - h0, st)); }
         HIP_TRY(hipMemcpyAsync(out_h + h0, (const RpLoopOut*)s.lp_out.p + h0, (size_t)(h1 - h0) * sizeof(RpLoopOut), hipMemcpyDeviceToHost, st));
         if (g + 1 == n_groups) HIP_TRY(hipMemcpyAsync(ctrl_h, s.lp_ctrl.p, 64, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipEventCreateWithFlags(&done.ev[g], hipEventDisableTiming));

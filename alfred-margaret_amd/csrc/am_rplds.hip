@@ -24,7 +24,6 @@
 
 #include "am_device.h"
 #include "am_bounds.h"
-#include "am_config.h"
 #include "am_wave.h"
 
 AM_BOUNDS_TU("am_rplds.hip")
@@ -545,7 +544,7 @@ __global__ void __launch_bounds__(64, PLI ? 5 : 4) k_rp_lds(RpLoop a)
 hipError_t launch_rp_lds(bool ic, const RpLoop& a, uint32_t n, hipStream_t st)
 {
     if (n == 0) return hipSuccess;
-    const bool pli = a.pl_implicit != 0 && !cfg::on(cfg::kRpNoPli);
+    const bool pli = a.pl_implicit != 0;
     if (a.pad) { if (ic) hipLaunchKernelGGL((k_rp_lds<true, true>), dim3(n), dim3(64), 0, st, a); else hipLaunchKernelGGL((k_rp_lds<false, true>), dim3(n), dim3(64), 0, st, a); }      // per-phase cycle sums (AM_RP_TRACE >= 3)
     else if (ic) { if (pli) hipLaunchKernelGGL((k_rp_lds<true, false, true>), dim3(n), dim3(64), 0, st, a); else hipLaunchKernelGGL((k_rp_lds<true>), dim3(n), dim3(64), 0, st, a); }
     else { if (pli) hipLaunchKernelGGL((k_rp_lds<false, false, true>), dim3(n), dim3(64), 0, st, a); else hipLaunchKernelGGL((k_rp_lds<false>), dim3(n), dim3(64), 0, st, a); }

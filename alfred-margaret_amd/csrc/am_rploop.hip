@@ -589,20 +589,15 @@ hipError_t launch_rp_loop_caps(const uint64_t* rec_first, uint32_t n_hay, uint32
     return hipGetLastError();
 }
 
-hipError_t launch_rp_loop(bool ic, const RpLoop& a, uint32_t n, int waves, hipStream_t st)
+hipError_t launch_rp_loop(bool ic, const RpLoop& a, uint32_t n, hipStream_t st)
 {
     if (n == 0) return hipSuccess;
-    // wavefronts per SIMD the register budget is cut for (AM_RP_LOOP_WAVES, A/B: the exact phase -- sf_verify -- wants ~125 registers, and cfg5 ran
+    // the register budget is cut for 4 wavefronts per SIMD (the exact phase -- sf_verify -- wants ~125 registers, and cfg5 ran
     // at 68.0 GiB/s with 4 wavefronts per SIMD, 61.9 / 64.4 / 56.4 with budgets cut for 5 / 6 / 8: the spills cost more than the wavefronts bring)
     const dim3 grid(n), block(64);
     if (ic) { hipLaunchKernelGGL((k_rp_loop<true, 4>), grid, block, 0, st, a); return hipGetLastError(); }
     if (a.pad) { hipLaunchKernelGGL((k_rp_loop<false, 4, true>), grid, block, 0, st, a); return hipGetLastError(); }      // per-phase cycle sums (AM_RP_TRACE >= 3)
-    switch (waves) {
-    case 5: hipLaunchKernelGGL((k_rp_loop<false, 5>), grid, block, 0, st, a); break;
-    case 6: hipLaunchKernelGGL((k_rp_loop<false, 6>), grid, block, 0, st, a); break;
-    case 8: hipLaunchKernelGGL((k_rp_loop<false, 8>), grid, block, 0, st, a); break;
-    default: hipLaunchKernelGGL((k_rp_loop<false, 4>), grid, block, 0, st, a); break;
-    }
+    hipLaunchKernelGGL((k_rp_loop<false, 4>), grid, block, 0, st, a);
     return hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
 /*
  * am_debug.h -- the entry points libam.so exports for TESTS AND MEASUREMENTS, next to the product ABI of include/am.h.  Nothing here is
- * needed by (or meant for) a caller of the library: a Haskell / C host binds am.h only.  None of these functions changes a result.
+ * needed by (or meant for) a caller of the library: a Haskell / C host binds am.h only.  None of these functions changes a result (nor does any switch am_debug_set knows).
  */
 #ifndef AM_DEBUG_H
 #define AM_DEBUG_H
@@ -16,7 +16,7 @@ extern "C" {
 AM_API int am_debug_set(const char* name, long value);
 /* Page-locked staging memory of all threads, living or parked (the leak test). */
 AM_API uint64_t am_debug_pinned_bytes(void);
-/* Cycle sums per k_sf phase / per-wavefront record counts of launches made under AM_SF_ABLATE=9 (tools/phase_timing.py). */
+/* Cycle sums per k_sf phase / per-wavefront record counts of launches made under AM_SF_TRACE (tools/phase_timing.py). */
 AM_API int am_debug_sf_phase_cycles(uint64_t* out5);
 AM_API int am_debug_sf_wave_records(uint64_t* out, size_t n_waves);
 /* Haystacks the calling process's last one-kernel Replacer run finished with their lists in LDS (k_rp_lds); the rest took k_rp_loop. */

@@ -1,5 +1,5 @@
 """containsAny's early exit, measured: k_sf's time on one document of N bytes whose first KiB matches, against the same document without the
-match; next to it the count-mode scan of the same document and (AM_SF_ABLATE=9) the slowest wavefront's own duration, which separates the
+match; next to it the count-mode scan of the same document and (AM_SF_TRACE) the slowest wavefront's own duration, which separates the
 launch's fixed cost from the work."""
 import ctypes as C, sys
 import numpy as np, torch
@@ -39,13 +39,13 @@ def main():
         torch.cuda.synchronize()
         miss = prof(lib, b"sf", any_fn); f_miss = int(flags[0])
         cnt = prof(lib, b"sf", cnt_fn)
-        am.api.debug_set("AM_SF_ABLATE", 9)
+        am.api.debug_set("AM_SF_TRACE", 1)
         cnt_fn()
         out = (C.c_uint64 * 16)()
         lib.am_debug_sf_phase_cycles(out)
         cnt_fn()
         lib.am_debug_sf_phase_cycles(out)
-        am.api.debug_set("AM_SF_ABLATE", -1)
+        am.api.debug_set("AM_SF_TRACE", -1)
         print("%5d MiB: any hit %.4f ms (flag %d)  miss %.4f ms (flag %d)  count %.4f ms;  DBG count: slowest wavefront %.4f ms, %d wavefronts, mean %.4f ms"
               % (mib, hit, f_hit, miss, f_miss, cnt, out[15] * 1e-5, out[4], (out[0] + out[1] + out[2] + out[3]) * 1e-5 / max(out[4], 1)), flush=True)
         lib.am_batch_destroy(b)

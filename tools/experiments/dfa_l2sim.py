@@ -13,8 +13,6 @@ l2 = float(sys.argv[3]) if len(sys.argv) > 3 else 4.0
 wl = "natural_100k_10GiB"; w = synth.WORKLOADS[wl]
 needles = synth.needles_for(wl)
 chk = ImgCheck()
-for k, v in (("AM_DFA_HOT_LOG2", os.environ.get("AM_DFA_HOT_LOG2")),):
-    if v: chk.set(k, int(v))
 img = chk.flatten(am.Automaton(needles), w["case"])
 text = np.frombuffer(synth.haystacks_host(needles, w["mixed"], 0, lanes * unit // 1024, natural=True), dtype=np.uint8)
 out = np.zeros(12, np.uint64)

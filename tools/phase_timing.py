@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""GPU-box experiment: where do k_sf's wavefront cycles go?  (AM_SF_ABLATE=9 enables s_memtime sums.)"""
+"""GPU-box experiment: where do k_sf's wavefront cycles go?  (AM_SF_TRACE enables s_memtime sums.)"""
 import ctypes as C, os, sys
-os.environ.setdefault("AM_SF_ABLATE", "9")
+os.environ.setdefault("AM_SF_TRACE", "1")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
