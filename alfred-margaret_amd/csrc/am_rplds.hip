@@ -188,7 +188,7 @@ __device__ __forceinline__ void ld_run_haystack(const RpLoop& a, LpLds<PLI>& L, 
 #pragma unroll
             for (uint32_t b = 0; b < kLdsBlocks; b++) {
                 if (pl_of(p_[b], l_[b]) == kRpWalkList && p_[b] != kDead) {
-                    const uint32_t st = (uint32_t)p_[b];
+                    const uint32_t st = (uint32_t)p_[b]; AM_BOUNDS(p_[b] > 0);      // (a walk-list slot holds a state id, never a priority: vals_off[] is indexed with it)
                     for (uint64_t k = a.t.vals_off[st], ke = a.t.vals_off[st + 1]; k < ke; k++) {
                         const int64_t p = a.t.payloads[a.t.vals[k]].priority;
                         if (p < threshold && p > bw) bw = p;
@@ -217,7 +217,7 @@ __device__ __forceinline__ void ld_run_haystack(const RpLoop& a, LpLds<PLI>& L, 
             for (uint32_t b = 0; b < kLdsBlocks; b++) {
                 bool sel = false;
                 if (pl_of(p_[b], l_[b]) == kRpWalkList && p_[b] != kDead) {
-                    const uint32_t st = (uint32_t)p_[b];
+                    const uint32_t st = (uint32_t)p_[b]; AM_BOUNDS(p_[b] > 0);
                     for (uint64_t k = a.t.vals_off[st], ke = a.t.vals_off[st + 1]; k < ke; k++) {
                         const uint32_t v = a.t.vals[k];
                         if (a.t.payloads[v].priority == best) { sel = true; pw = v; }
@@ -488,7 +488,7 @@ __device__ __forceinline__ void ld_run_haystack(const RpLoop& a, LpLds<PLI>& L, 
                     if ((int64_t)nr + g > (int64_t)kLdsRec) { redo = true; break; }
                     ld_move(L.end, c_gone, nr, g, 0u, lane);
                     ld_move(reinterpret_cast<uint32_t*>(L.prio), c_gone, nr, g, 0u, lane);
-                    if (!PLI) ld_move(L.pl, c_gone, nr, g, 0u, lane);
+                    if (!PLI) ld_move(L.pl, c_gone, nr, g, 0u, lane);      // (not "result only": a slot whose pl says "walk the list" while its prio holds a priority indexes vals_off[] with it; what moves end / prio moves pl, here and at :345)
                     nr = (uint32_t)((int32_t)nr + g);
                 }
                 AM_BOUNDS(c_before + nf <= kLdsRec && staged + nf <= kLdsRec);

@@ -206,7 +206,8 @@ AM_API int am_matches_fold_hash(const am_matches* m, const am_needle_ids* values
  *   payloads        Payload (:59-70) per needle: priority, lengths of the ORIGINAL needle in bytes
  *                   and code points (:112-113), replacement = repl_bytes[repl_off .. +repl_len)
  *   min_priority    1 - numNeedles (:217)
- * Priorities must be distinct and <= 0, as build (:100-104) and compose (:127-131) make them.
+ * Priorities must be distinct and <= 0, as build (:100-104) and compose (:127-131) make them; any such values do, INT64_MIN excepted
+ * (the fold's seed, :222).  min_priority must be <= every priority given: it only ends the loop early (:241); a larger one cuts the lower priorities off.
  * `a` must outlive the replacer.  case_mode is the Replacer's replacerCaseSensitivity.
  * Batches of many documents (>= 64, <= 1 MiB on average, no document with more than 4096 matches) run ALL passes of a
  * haystack inside one kernel (one wavefront per haystack, csrc/am_rploop.hip); everything else goes pass by pass

@@ -476,6 +476,7 @@ typedef struct orc_replacer {
     payload_t* payloads; size_t n_needles;
     uint8_t* repl_store;
     int ignore_case;
+    int64_t min_priority;
 } orc_replacer;
 
 /* Replacer.hs:97-116 build.  IgnoreCase lower-cases the needle (:105-107); the payload lengths
@@ -485,6 +486,7 @@ orc_replacer* orc_replacer_build(int ignore_case, const uint8_t* nbytes, const u
 {
     orc_replacer* r = (orc_replacer*)calloc(1, sizeof(orc_replacer));
     r->ignore_case = ignore_case; r->n_needles = n;
+    r->min_priority = 1 - (int64_t)n;                        /* :217 */
     r->payloads = (payload_t*)calloc(n ? n : 1, sizeof(payload_t));
     size_t rtotal = (size_t)roffs[n];
     r->repl_store = (uint8_t*)malloc(rtotal ? rtotal : 1);
@@ -514,6 +516,14 @@ orc_replacer* orc_replacer_build(int ignore_case, const uint8_t* nbytes, const u
 /* Replacer.hs:148-153 setCaseSensitivity: the needles in the automaton stay as they are (an IgnoreCase-built replacer keeps its
  * lower-cased needles), the payloads keep the ORIGINAL needles' lengths; only the mode of the scan and of makeMatch (:264-274) changes. */
 void orc_replacer_set_case(orc_replacer* r, int ignore_case) { r->ignore_case = ignore_case; }
+
+/* A caller's own priorities (the C ABI's am_replacer_create takes any distinct ones <= 0): the payloads' priority field (:62) and minPriority (:217) are
+ * no longer forced to -index and 1 - n; runWithLimit itself is unchanged.  INT64_MIN is the fold's seed (minBound, :222) and must not be given. */
+void orc_replacer_set_priorities(orc_replacer* r, const int64_t* prio, int64_t min_priority)
+{
+    for (size_t i = 0; i < r->n_needles; i++) r->payloads[i].priority = prio[i];
+    r->min_priority = min_priority;
+}
 
 void orc_replacer_free(orc_replacer* r)
 {
@@ -571,7 +581,7 @@ uint8_t* orc_replacer_run(const orc_replacer* r, const uint8_t* hay, size_t hay_
     memcpy(cur, hay, hay_len);
     size_t cur_len = hay_len;
     int64_t threshold = 1;                                   /* initialThreshold :211 */
-    int64_t min_priority = 1 - (int64_t)r->n_needles;        /* :217 */
+    int64_t min_priority = r->min_priority;                  /* :217 */
     prep_acc s; memset(&s, 0, sizeof(s)); s.r = r;
     for (;;) {
         s.threshold = threshold; s.p_best = INT64_MIN; s.n = 0; s.hay = cur; s.hay_len = cur_len;   /* seed :222 */

@@ -62,6 +62,8 @@ def _load():
     lib.orc_replacer_free.argtypes = [C.c_void_p]
     lib.orc_replacer_set_case.restype = None
     lib.orc_replacer_set_case.argtypes = [C.c_void_p, C.c_int]
+    lib.orc_replacer_set_priorities.restype = None
+    lib.orc_replacer_set_priorities.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int64]
     lib.orc_replacer_run.restype = C.c_void_p
     lib.orc_replacer_run.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int64, C.POINTER(C.c_size_t)]
     lib.orc_free_bytes.argtypes = [C.c_void_p]
@@ -229,11 +231,20 @@ def skip_code_points_backwards(text, index, n):
 class Replacer:
     """Restated Data.Text.AhoCorasick.Replacer (build :97-116, run :200-201, runWithLimit :203-274)."""
 
-    def __init__(self, case, pairs):
+    def __init__(self, case, pairs, priorities=None, min_priority=None):
+        """priorities: the payloads' priorities (distinct, <= 0, above INT64_MIN -- the fold's seed, Replacer.hs:222) instead of build's 0, -1, -2, ...;
+        min_priority: minPriority (:217) instead of the smallest priority.  A min_priority above the smallest priority is the caller's error."""
         nb, no = pack_texts([p[0] for p in pairs])
         rb, ro = pack_texts([p[1] for p in pairs])
         self._h = lib().orc_replacer_build(case, nb, no.ctypes.data_as(C.POINTER(C.c_uint64)),
                                            rb, ro.ctypes.data_as(C.POINTER(C.c_uint64)), len(pairs))
+        if priorities is not None or min_priority is not None:
+            prio = [-i for i in range(len(pairs))] if priorities is None else [int(p) for p in priorities]
+            assert len(prio) == len(pairs) and len(set(prio)) == len(prio) and all(-2**63 < p <= 0 for p in prio), prio
+            if min_priority is None:
+                min_priority = min(prio) if prio else 1
+            arr = (C.c_int64 * max(len(prio), 1))(*prio)
+            lib().orc_replacer_set_priorities(self._h, arr, int(min_priority))
 
     def __del__(self):
         if getattr(self, "_h", None) and lib is not None:      # module globals may be gone at interpreter exit

@@ -107,3 +107,292 @@ class ImgCheck:
         f = struct.unpack_from("<4IQ4I", img.tobytes()[:40])
         return {"magic": f[0], "version": f[1], "case_mode": f[2], "total_bytes": f[4], "n_states": f[5],
                 "max_needle_cps": f[6], "root_vlen": f[7], "ac_chunk": f[8]}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# A Replacer with the CALLER'S OWN priorities (include/am.h: am_replacer_create takes any distinct priorities <= 0), and the inputs that sit on
+# the capacity limits of the one-kernel loop (csrc/am_rplds.hip).  tests/test_oracle_priorities.py checks on the CPU that these inputs are what
+# they claim to be; tests/test_gpu_replacer_priorities.py feeds them to the kernels.
+
+INT32_MIN = -2**31
+WIDE_PRIORITIES = (INT32_MIN, INT32_MIN - 1, -2**40, -2**62)      # the edge of RpStateOne's 32-bit priority and beyond it (INT64_MIN is the fold's seed, Replacer.hs:222: never a priority)
+
+
+def priority_families(rng, n):
+    """{name: priorities of n payloads}: a permutation of 0 .. -(n-1); -3i-1 permuted (gaps, no zero); small ones mixed with 64-bit ones."""
+    def perm():
+        p = list(range(n))
+        rng.shuffle(p)
+        return p
+    fams = {"permuted": [-i for i in perm()], "gaps": [-3 * i - 1 for i in perm()]}
+    wide = [-5 * i for i in perm()]
+    for k, w in zip(rng.sample(range(n), min(n, len(WIDE_PRIORITIES))), rng.sample(WIDE_PRIORITIES, len(WIDE_PRIORITIES))):
+        wide[k] = w
+    fams["wide"] = wide
+    return fams
+
+
+def sorted_by_priority(pairs, priorities):
+    """The pair list that Replacer.build turns into the same replacer: runWithLimit only COMPARES priorities (Replacer.hs:236-258), so the order is all that counts."""
+    return [pairs[i] for i in sorted(range(len(pairs)), key=lambda i: -priorities[i])]
+
+
+def mirror_twin(pairs):
+    """The same replacer as build's (priority = -index), written so that am_replacer_create does not recognise it: the list reversed, priorities -(n-1-i)."""
+    n = len(pairs)
+    return list(reversed(pairs)), [-(n - 1 - i) for i in range(n)]
+
+
+PAYLOAD_DTYPE = np.dtype([("priority", np.int64), ("len_bytes", np.uint32), ("len_code_points", np.uint32), ("repl_off", np.uint64), ("repl_len", np.uint32), ("reserved", np.uint32)])   # am_payload
+
+
+class AbiReplacer:
+    """am_replacer_create called directly (ctypes), as a caller of include/am.h would: the automaton over the needles (lower-cased first under IgnoreCase,
+    Replacer.hs:105-107), machineValues from the host mirror's automaton (value = needle index), the caller's am_payload[] (lengths of the ORIGINAL needle,
+    :112-113) and min_priority.  priorities=None: -index, which the library recognises as Replacer.build's (the payload-implicit kernel)."""
+
+    def __init__(self, case, pairs, priorities=None, min_priority=None, built_case=None):
+        """built_case: the case sensitivity the replacer was BUILT with, where setCaseSensitivity (Replacer.hs:148-153) changed it afterwards: the needles are
+        lower-cased by the built mode, scan and makeMatch run in `case`."""
+        import alfred_margaret_amd as am
+        self.am = am
+        n = len(pairs)
+        prio = [-i for i in range(n)] if priorities is None else [int(p) for p in priorities]
+        if min_priority is None:
+            min_priority = min(prio) if prio else 1
+        orig = [p[0].encode("utf-8") if isinstance(p[0], str) else bytes(p[0]) for p in pairs]
+        repl = [p[1].encode("utf-8") if isinstance(p[1], str) else bytes(p[1]) for p in pairs]
+        self.automaton = am.Automaton([am.lower_utf8(b) if (case if built_case is None else built_case) else b for b in orig])      # must outlive the replacer
+        self.voff = np.ascontiguousarray(self.automaton.values_off(), dtype=np.uint64)
+        self.vals = np.ascontiguousarray(self.automaton.values(), dtype=np.uint32)
+        pl = np.zeros(max(n, 1), PAYLOAD_DTYPE)
+        off = 0
+        for i in range(n):
+            pl[i] = (prio[i], len(orig[i]), len(orig[i].decode("utf-8")), off, len(repl[i]), 0)
+            off += len(repl[i])
+        blob = b"".join(repl)
+        self.payloads, self.priorities, self.min_priority = pl, prio, int(min_priority)
+        h = C.c_void_p()
+        vals_ptr = self.vals.ctypes.data if self.vals.size else None
+        self.rc = am.libam().am_replacer_create(self.automaton.device, case, self.voff.ctypes.data, vals_ptr, pl.ctypes.data if n else None, n,
+                                                blob if blob else None, len(blob), self.min_priority, C.byref(h))
+        self._h = h if self.rc == 0 else None
+        if self.rc != 0:
+            self.error = (am.libam().am_last_error() or b"").decode("utf-8", "replace")
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self.am.libam().am_replacer_destroy(self._h)
+            self._h = None
+
+    def run(self, hays, max_len=-1):
+        """am_replacer_run on slices: ([text or None per haystack], am_replaced_passes)."""
+        am = self.am
+        s = am.api._Slices(hays)
+        res = C.c_void_p()
+        am.api.check(am.libam().am_replacer_run(self._h, s.arr, s.n, 2**64 - 1 if max_len < 0 else int(max_len), C.byref(res)))
+        try:
+            assert int(am.libam().am_replaced_size(res)) == s.n
+            out = []
+            for i in range(s.n):
+                p, ln = C.c_void_p(), C.c_size_t(0)
+                just = am.libam().am_replaced_get(res, i, C.byref(p), C.byref(ln))
+                assert just in (0, 1), just
+                out.append(C.string_at(p, ln.value) if just else None)
+            return out, int(am.libam().am_replaced_passes(res))
+        finally:
+            am.libam().am_replaced_free(res)
+
+    def run_priority(self, hays, thresholds):
+        """am_run_priority: (best priority per haystack, [(haystack, start, len, payload)])."""
+        am = self.am
+        s = am.api._Slices(hays)
+        thr = np.ascontiguousarray(thresholds, dtype=np.int64)
+        best = np.zeros(max(s.n, 1), np.int64)
+        p, n = C.c_void_p(), C.c_size_t(0)
+        am.api.check(am.libam().am_run_priority(self._h, s.arr, s.n, thr.ctypes.data, best.ctypes.data, C.byref(p), C.byref(n)))
+        try:
+            k = int(n.value)
+            dt = am.api.PRIO_MATCH_DTYPE
+            ms = np.frombuffer((C.c_char * (k * dt.itemsize)).from_address(p.value), dtype=dt).copy() if k else np.zeros(0, dt)
+        finally:
+            am.libam().am_prio_matches_free(p)
+        return [int(b) for b in best[:s.n]], [(int(m["haystack"]), int(m["start"]), int(m["len"]), int(m["payload"])) for m in ms]
+
+
+# ---- the limits of k_rp_lds (csrc/am_rplds.hip), one sweep per limit -------------------------------------------------------------------------
+LDS_REC = 512          # kLdsRec   (am_rplds.hip:37): records of a haystack; first scan :126, list + staged new records :461, list growth :488
+LDS_PC = 448           # kLdsPc    (am_rplds.hip:39): piece entries INCLUDING the sentinel (:376: np + s + 1 > kLdsPc gives up), so 447 pieces of text
+LDS_WIN = 448          # kLdsWin   (am_rplds.hip:41): bytes of a re-scan window (:322)
+LDS_NEW = 64           # new records of one window (:461, nf + nfb > kWave)
+NEVER = ("zz", "y")    # the lowest priority of every sweep, never matches: the measured pass is not the last priority (:317, :328 edit the piece list only there)
+NAMES = "abcdefghijklmnopqrstuvwxyz0123456789"
+
+
+def reach(case, pairs):
+    """`ov` of the one-kernel loop (am_replacer.cpp:884-885): the longest needle in bytes for CaseSensitive, 4 * code points + 4 under IgnoreCase."""
+    if case:
+        return 4 * max(len(n) for n, _ in pairs) + 4
+    return max(len(n.encode("utf-8")) for n, _ in pairs)
+
+
+class Sweep:
+    """One quantity of one haystack moves across its documented limit; `fits[i]` says whether haystack i stays within the limit as csrc/am_rplds.hip states it."""
+
+    QUANTITY = {"first-scan records": "first_scan", "list growth": "records_after", "staged records": "new_records", "pieces": "pieces", "window": "window", "new records": "new_records"}
+
+    def __init__(self, name, case, pairs, hays, values, limit, fits):
+        self.name, self.case, self.pairs, self.hays, self.values, self.limit, self.fits = name, case, pairs, hays, values, limit, fits
+        self.quantity = self.QUANTITY[name.split(",")[0]]      # the key of sweep_quantities() that moves
+
+    def __repr__(self):
+        return "Sweep(%s, case=%d)" % (self.name, self.case)
+
+
+def _up(case, s):
+    return s.upper() if case else s
+
+
+def sweep_first_scan_records(case):
+    """1. 508 .. 516 match positions in the FIRST scan (:126 nr0 > kLdsRec).  The needle is eight "a"s in a run of n + 7, not "a" in a run of n: every kept match
+    becomes a piece, and 508 single-byte replacements would cross the piece limit first; here a pass keeps ~64 matches."""
+    pairs = [("a" * 8, "b"), NEVER]
+    values = list(range(LDS_REC - 4, LDS_REC + 5))
+    return Sweep("first-scan records", case, pairs, [_up(case, "a") * (n + 7) for n in values], values, LDS_REC, [n <= LDS_REC for n in values])
+
+
+def sweep_growing_list(case):
+    """2a. The list grows during the first pass: twenty replacements, each brings 25 match positions of the lower-priority needle (eight "q"s in a run of 32) and frees
+    one slot; j + 20 records of the first scan become j + 500.  The new records are STAGED behind the list (:461 nr + nf + nfb > kLdsRec) before they move into it, so a
+    step that frees `room` slots needs nr + nf <= 512 and the list can end at 512 - room = 511 at most; the growth check behind it (:488) can then never fire."""
+    pairs = [("m", "q" * 32), ("q" * 8, "r"), NEVER]
+    values = list(range(LDS_REC - 4, LDS_REC + 5))               # records after the first pass
+    hays = [_up(case, "q" * (n - 500 + 7) + "x" * 40 + ("m" + "x" * 40) * 20) for n in values]
+    return Sweep("list growth", case, pairs, hays, values, LDS_REC - 1, [n <= LDS_REC - 1 for n in values])
+
+
+def sweep_staging(case):
+    """2b. 490 records in the list, ONE window that brings 18 .. 26 new ones (:461): list + staged records <= 512, so 22 fit."""
+    values = list(range(18, 27))
+    pairs = [("m" + NAMES[i], "q" * (w + 7)) for i, w in enumerate(values)] + [("q" * 8, "r"), NEVER]
+    hays = [_up(case, "q" * (489 + 7) + "x" * 40 + "m" + NAMES[i] + "x" * 40) for i, _ in enumerate(values)]
+    return Sweep("staged records", case, pairs, hays, values, LDS_REC - 490, [490 + w <= LDS_REC for w in values])
+
+
+def sweep_pieces(case, variant):
+    """3. k non-adjacent single-byte replacements.  variant "inner": b + (ab)^k, 2k + 1 pieces; "edge": (ab)^k starts with a match, 2k pieces; "tail": (ba)^k ENDS with a
+    match, 2k pieces (no tail piece behind the last replacement, has_tail :374, in a text that goes on to fill the list); "empty": the empty
+    replacement leaves k + 1 pieces of text around k holes (no replacement piece, has_repl :374).  The list holds kLdsPc entries with its sentinel (:376)."""
+    if variant == "empty":
+        values = list(range(LDS_PC - 5, LDS_PC + 4))                # pieces
+        pairs = [("a", ""), NEVER]
+        hays = [_up(case, "b" + "ab" * (p - 1)) for p in values]
+    else:
+        ks = list(range(220, 228))
+        pairs = [("a", "X"), NEVER]
+        hays = [_up(case, "ba" * k if variant == "tail" else ("b" if variant == "inner" else "") + "ab" * k) for k in ks]
+        values = [2 * k + (1 if variant == "inner" else 0) for k in ks]
+    return Sweep("pieces, " + variant, case, pairs, hays, values, LDS_PC - 1, [p + 1 <= LDS_PC for p in values])
+
+
+def sweep_window(case, variant):
+    """4. One match, replacement of rl bytes: the re-scanned window is rl + 2 ov bytes ("middle"), or rl + ov where the text's start ("start") or end ("end") clips it
+    (:318-322 wlen > kLdsWin).  Needles "m?" of two bytes, so ov is the same for every haystack."""
+    ov = reach(case, [("mm", ""), NEVER])
+    values = list(range(LDS_WIN - 8, LDS_WIN + 9))                  # window bytes
+    rls = [w - (2 * ov if variant == "middle" else ov) for w in values]
+    pairs = [("m" + NAMES[i], "R" * rl) for i, rl in enumerate(rls)] + [NEVER]
+    pad = "x" * 600
+    hays = [_up(case, (pad if variant != "start" else "") + "m" + NAMES[i] + (pad if variant != "end" else "")) for i, _ in enumerate(rls)]
+    return Sweep("window, " + variant, case, pairs, hays, values, LDS_WIN, [w <= LDS_WIN for w in values])
+
+
+def sweep_new_records(case, variant):
+    """5. The replacement text holds m match positions of a lower-priority needle ("q").  The window is scanned 64 positions per trip from the replacement's first byte
+    (:437): "one trip": m = 60 .. 64 positions in the first 64 bytes of the replacement, and 65 .. 68 that run into the second; "two trips": 40 in the first trip and
+    20 .. 28 in the second (:461 nf + nfb > kWave)."""
+    values = list(range(LDS_NEW - 4, LDS_NEW + 5))
+    if variant == "one trip":
+        repls = ["q" * m for m in values]
+    else:
+        repls = ["q" * 40 + "x" * 30 + "q" * (m - 40) for m in values]
+    pairs = [("m" + NAMES[i], _up(case, r)) for i, r in enumerate(repls)] + [("q", "r"), NEVER]
+    hays = [_up(case, "x" * 100 + "m" + NAMES[i] + "x" * 100) for i, _ in enumerate(values)]
+    return Sweep("new records, " + variant, case, pairs, hays, values, LDS_NEW, [m <= LDS_NEW for m in values])
+
+
+def sweep_quantities(sw, i):
+    """What haystack i of a sweep does to the lists of k_rp_lds, computed with the oracle's automaton and plain Python (no kernel): the first pass is the one
+    the sweeps measure.  first_scan: positions with a match (= records); pieces: entries of the piece list after the first pass; window: the longest re-scan window
+    (hi - ws, am_rplds.hip:318-321); new_records: the most lower-priority match positions one window finds; records_after: the list after the first pass."""
+    case, hay = sw.case, sw.hays[i].encode("utf-8")
+    orig = [n.encode("utf-8") for n, _ in sw.pairs]
+    repl = [r.encode("utf-8") for _, r in sw.pairs]
+    m = oracle.Machine([oracle.lower_utf8(n) if case else n for n in orig])
+    ov = reach(case, sw.pairs)
+    pos, val = m.run_list(case, hay)
+    first_scan = len(set(int(p) for p in pos))
+    top = min(int(v) for v in val)
+    found = []
+    for p, v in zip(pos, val):
+        if int(v) == top:
+            p = int(p)
+            st = oracle.skip_code_points_backwards(hay, p - 1, len(sw.pairs[top][0]) - 1) if case else p - len(orig[top])
+            found.append((st, p - st))
+    kept = []
+    for st, ln in sorted(found):
+        if not kept or st >= kept[-1][0] + kept[-1][1]:
+            kept.append((st, ln))
+    rl = len(repl[top])
+    out, at, pieces = b"", 0, 0
+    new_start = []
+    for st, ln in kept:
+        pieces += (1 if st > at else 0) + (1 if rl else 0)
+        out += hay[at:st]
+        new_start.append(len(out))
+        out += repl[top]
+        at = st + ln
+    pieces += 1 if at < len(hay) or not kept else 0
+    out += hay[at:]
+    pos2, val2 = m.run_list(case, out)
+    lower = sorted(set(int(p) for p, v in zip(pos2, val2) if int(v) > top))
+    window, new_records = 0, 0
+    for k in range(len(kept) - 1, -1, -1):
+        ms = kept[k][0]
+        newlen = len(out) - (new_start[k] - ms)                  # the text while match k is replaced: old to its left, new to its right
+        hi, ws = min(ms + rl + ov, newlen), max(ms - ov, 0)
+        window = max(window, hi - ws if hi > ms else 0)
+        lo2, hi2 = new_start[k], new_start[k] + (hi - ms)
+        new_records = max(new_records, sum(1 for p in lower if lo2 < p <= hi2))
+    return {"first_scan": first_scan, "pieces": pieces, "window": window, "new_records": new_records, "records_after": len(lower), "kept": len(kept)}
+
+
+def all_sweeps():
+    out = []
+    for case in (0, 1):
+        out += [sweep_first_scan_records(case), sweep_growing_list(case), sweep_staging(case)]
+        out += [sweep_pieces(case, v) for v in ("inner", "edge", "tail", "empty")]
+        out += [sweep_window(case, v) for v in ("middle", "start", "end")]
+        out += [sweep_new_records(case, v) for v in ("one trip", "two trips")]
+    return out
+
+
+def ordinary_documents(n=70, seed=3):
+    """Short documents that finish in LDS under every sweep's replacer: the neighbours of section 7.  The record, piece and growth sweeps rewrite them a little
+    (runs of "a" and "q", "zz"); no "m", so the long replacements of the window sweeps stay out of them and ALL of them stay within every limit."""
+    rng = random.Random(seed)
+    return ["".join(rng.choice(["a", "b", "x", "q", " ", "aaaaaaaa", "qqqqqqqq", "z"]) for _ in range(rng.randint(0, 40))) for _ in range(n)]
+
+
+# 6. the host's route limits (am_replacer.cpp:886-887, :952)
+ROUTE_REPL_LENGTHS = ((4013, 4096), (4076, 4096), (4077, 4160))      # (longest replacement, round_up_64(2 ov + rl + 16)) with ov = 2
+ROUTE_MATCH_PAIRS = [("a" * 8, "b"), NEVER]
+ROUTE_MATCH_COUNTS = (4095, 4096, 4097)
+
+
+def route_window_pairs(rl):
+    return [("m", "R" * rl), NEVER]
+
+
+def route_match_document(n):
+    return "a" * (n + 7)

@@ -8,32 +8,55 @@ import pytest
 import alfred_margaret_amd as am
 from alfred_margaret_amd import synth
 from oracle import oracle
+from tests.helpers import AbiReplacer, mirror_twin
 
 pytestmark = pytest.mark.gpu
 LDS_SEEN = []               # haystacks each one-kernel run finished out of LDS (am_debug_rp_lds_haystacks)
 
 
+def _switched(switches, f):
+    """f() under the given switches of libam, which are unset again whatever f does"""
+    for k, v in switches.items():
+        am.debug_set(k, v)
+    try:
+        return f()
+    finally:
+        for k in switches:
+            am.debug_set(k, -1)
+
+
 def _loop_equals_oracle(pairs, hays, max_len=-1, case=0):
     r = am.Replacer(case, pairs)
-    am.debug_set("AM_RP_LOOP", 0)
-    ref = r.run_batch(hays, max_len)
-    ref_stats = r.last_stats()
-    am.debug_set("AM_RP_LOOP", 1)
-    got = r.run_batch(hays, max_len)                        # k_rp_lds (lists in LDS) + k_rp_loop for the haystacks it gives up
-    stats = r.last_stats()
-    LDS_SEEN.append(int(am.libam().am_debug_rp_lds_haystacks()))
-    am.debug_set("AM_RP_LDS", 0)
-    got_global = r.run_batch(hays, max_len)                 # k_rp_loop alone (lists in global memory: round 4's kernel)
-    stats_global = r.last_stats()
-    am.debug_set("AM_RP_LDS", -1)
-    am.debug_set("AM_RP_LOOP", -1)
+
+    def run():
+        return r.run_batch(hays, max_len), r.last_stats(), int(am.libam().am_debug_rp_lds_haystacks())
+    ref, ref_stats, _ = _switched({"AM_RP_LOOP": 0}, run)
+    got, stats, lds = _switched({"AM_RP_LOOP": 1}, run)                                      # k_rp_lds (lists in LDS) + k_rp_loop for the haystacks it gives up
+    LDS_SEEN.append(lds)
+    got_global, stats_global, _ = _switched({"AM_RP_LOOP": 1, "AM_RP_LDS": 0}, run)          # k_rp_loop alone (lists in global memory: round 4's kernel)
     o = oracle.Replacer(case, pairs)
     exp = [o.run(h, max_len) for h in hays]
     assert got == exp, (case, pairs[:6], max_len)
     assert got_global == exp, (case, pairs[:6], max_len)
     assert ref == exp
     assert stats[0] == ref_stats[0] == stats_global[0], "number of passes"
+    _twin_with_own_priorities(pairs, hays, max_len, case, exp, stats[0], LDS_SEEN[-1])
     return got, stats
+
+
+def _twin_with_own_priorities(pairs, hays, max_len, case, exp, passes, lds_haystacks, built_case=None):
+    """The mirror trick: the pair list reversed with priorities -(n-1-i) is the same replacer, but am_replacer_create does not recognise it as Replacer.build's
+    (am_replacer.cpp:151-152), so k_rp_lds runs with its payload column (am_rplds.hip:43-51) instead of the payload-implicit layout: identical bytes, identical
+    passes, and -- the limits are the same in both layouts -- the same haystacks finished out of LDS."""
+    twin_pairs, twin_prio = mirror_twin(pairs)
+    t = AbiReplacer(case, twin_pairs, twin_prio, built_case=built_case)
+    assert t.rc == 0, t.error
+    got, got_passes, lds = _switched({"AM_RP_LOOP": 1}, lambda: t.run(hays, max_len) + (int(am.libam().am_debug_rp_lds_haystacks()),))
+    ref, ref_passes = _switched({"AM_RP_LOOP": 0}, lambda: t.run(hays, max_len))
+    assert got == exp, ("own priorities", case, pairs[:6], max_len)
+    assert ref == exp
+    assert got_passes == ref_passes == passes, "number of passes"
+    assert lds == lds_haystacks, "haystacks finished out of LDS: payload column vs payload implicit"
 
 
 def test_loop_overlaps_chains_and_long_match_lists():
@@ -107,9 +130,11 @@ def test_long_match_lists_take_the_pass_by_pass_loop():
     got = r.run_batch(hays)
     o = oracle.Replacer(0, pairs)
     assert got == [o.run(h) for h in hays]
-    am.debug_set("AM_RP_LOOP", 1)
-    assert r.run_batch(hays) == got
-    am.debug_set("AM_RP_LOOP", -1)
+    forced, stats, lds = _switched({"AM_RP_LOOP": 1}, lambda: (r.run_batch(hays), r.last_stats(), int(am.libam().am_debug_rp_lds_haystacks())))
+    assert forced == got
+    _twin_with_own_priorities(pairs, hays, -1, 0, got, stats[0], lds)
+    t = AbiReplacer(0, *mirror_twin(pairs))
+    assert t.run(hays)[0] == got                             # the twin on the default route: pass by pass as well
 
 
 def test_loop_cfg5_reduced_and_what_it_scans():
@@ -123,11 +148,16 @@ def test_loop_cfg5_reduced_and_what_it_scans():
     r = am.Replacer(w["case"], pairs)
     got = r.run_batch(hays)                                  # switches unset: >= 64 documents take the one-kernel loop
     passes, scanned = r.last_stats()
-    am.debug_set("AM_RP_LOOP", 0)
-    ref = r.run_batch(hays)
-    ref_passes, ref_scanned = r.last_stats()
-    am.debug_set("AM_RP_LOOP", -1)
+    lds = int(am.libam().am_debug_rp_lds_haystacks())
+    ref, (ref_passes, ref_scanned) = _switched({"AM_RP_LOOP": 0}, lambda: (r.run_batch(hays), r.last_stats()))
     assert got == ref and passes == ref_passes and passes > 100
+    # the twin with own priorities: 50 000 payloads in k_rp_lds's payload column, on the default route and forced either way
+    t = AbiReplacer(w["case"], *mirror_twin(pairs))
+    assert t.rc == 0, t.error
+    twin, twin_passes = t.run(hays)
+    assert int(am.libam().am_debug_rp_lds_haystacks()) == lds > 0
+    assert twin == got and twin_passes == passes
+    _twin_with_own_priorities(pairs, hays, -1, w["case"], got, passes, lds)
     total = sum(len(h) for h in hays)
     assert total < scanned <= ref_scanned < total * 4                    # windows as long as the longest needle needs (the pass-by-pass loop: 4 bytes per code point + 4)
     orc = oracle.Replacer(w["case"], pairs)
@@ -151,14 +181,13 @@ def test_loop_reach_comes_from_the_automaton_not_from_the_payload_lengths():
     o = oracle.Replacer(1, pairs).set_case_sensitivity(0)
     exp = [o.run(h) for h in hays]
     assert any(e != h.encode() for e, h in zip(exp, hays))
-    am.debug_set("AM_RP_LOOP", 0)
-    ref = r.run_batch(hays)
-    am.debug_set("AM_RP_LOOP", 1)
-    got = r.run_batch(hays)
-    am.debug_set("AM_RP_LOOP", -1)
+    ref = _switched({"AM_RP_LOOP": 0}, lambda: r.run_batch(hays))
+    got, stats, lds = _switched({"AM_RP_LOOP": 1}, lambda: (r.run_batch(hays), r.last_stats(), int(am.libam().am_debug_rp_lds_haystacks())))
     assert ref == exp
     assert got == exp
     assert r.run_batch(hays) == exp                          # the default route (>= 64 documents: the one-kernel loop)
+    # the twin with own priorities: the automaton over the LOWER-CASED needles, the payloads with the ORIGINAL lengths, run CaseSensitive = setCaseSensitivity
+    _twin_with_own_priorities(pairs, hays, -1, 0, exp, stats[0], lds, built_case=1)
 
 
 def test_the_lds_kernel_is_what_runs():
