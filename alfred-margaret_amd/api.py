@@ -65,6 +65,9 @@ ABI = {
     "am_matches_copy": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp]),
     "am_matches_free": (None, [_vp]),
     "am_matches_fold_hash": (C.c_int, [_vp, _vp, _sz, _vp, _vp]),
+    "am_count_by_needle_batch": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "am_count_by_needle": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp]),
+    "am_matches_count_by_needle": (C.c_int, [_vp, _vp, _vp]),
     "am_needle_ids_create": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(_vp)]),
     "am_needle_ids_destroy": (None, [_vp]),
     "am_contains_all": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp]),
@@ -135,6 +138,7 @@ _HOST = {
     "amh_device": (_vp, [_vp]),
     "amh_run_list": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp, _vp, _vp, C.c_uint64, _u64p]),
     "amh_count": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp]),
+    "amh_count_by_needle": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _sz, _vp]),
     "amh_searcher_build": (C.c_int, [C.c_int, C.c_char_p, _vp, _sz, C.POINTER(_vp)]),
     "amh_searcher_free": (None, [_vp]),
     "amh_searcher_set_case": (None, [_vp, C.c_int]),
@@ -172,6 +176,7 @@ DEBUG_ABI = {
     "am_debug_resident_waves": (C.c_int, [_vp, _vp]),
     "am_debug_set_general_kernel": (C.c_int, [_vp, C.c_uint32]),
     "am_debug_rp_lds_haystacks": (C.c_uint32, []),
+    "am_debug_hist_adds": (C.c_int, [_vp]),
 }
 
 _libam = None
@@ -399,6 +404,22 @@ class Automaton:
         finally:
             libam().am_matches_free(m)
 
+    def count_by_needle(self, case, texts, n_values=None):
+        """How often every value is matched over all the texts: the fold `Map.insertWith (+) v 1` of runWithCase (Automaton.hs:442-553) as np.uint64[n], index = value
+        handle, n = len(needles) unless given (handles >= n are skipped).  am_count_by_needle: scanned and folded in HBM, n counts come back."""
+        n = len(self.needles) if n_values is None else int(n_values)
+        if n == 0:
+            return np.zeros(0, np.uint64)
+        return ValuesTable(self, n).count_by_needle_texts(case, texts)
+
+    def count_by_needle_host_mirror(self, case, texts, n_values=None):
+        """The same through the C++ host mirror (host/automaton.hpp countByNeedle)."""
+        n = len(self.needles) if n_values is None else int(n_values)
+        s = _Slices(texts)
+        out = np.zeros(max(n, 1), np.uint64)
+        _hcheck(libhost().amh_count_by_needle(self._h, case, s.arr, s.n, n, out.ctypes.data))
+        return out[:n]
+
 
 class ValuesTable:
     """machineValues of an Automaton in flat form on the device (am_needle_ids): what the fold-checksum and
@@ -414,6 +435,7 @@ class ValuesTable:
         n = len(automaton.needles) if n_needles is None else n_needles
         check(libam().am_needle_ids_create(automaton.device, self._off.ctypes.data, self._val.ctypes.data, n, C.byref(h)))
         self._h = h
+        self.n_needles = int(n)
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -429,6 +451,24 @@ class ValuesTable:
         hashes, counts = np.zeros(max(n_hay, 1), np.uint64), np.zeros(max(n_hay, 1), np.uint64)
         check(libam().am_matches_fold_hash(matches, self._h, n_hay, hashes.ctypes.data, counts.ctypes.data))
         return hashes[:n_hay], counts[:n_hay]
+
+    def _counts(self, call):
+        out = np.zeros(max(self.n_needles, 1), np.uint64)
+        check(call(out.ctypes.data))
+        return out[:self.n_needles]
+
+    def count_by_needle(self, matches):
+        """am_matches_count_by_needle: per-value match counts (np.uint64[n_needles]) of an am_matches* result whose records are in HBM."""
+        return self._counts(lambda out: libam().am_matches_count_by_needle(matches, self._h, out))
+
+    def count_by_needle_batch(self, case, batch):
+        """am_count_by_needle_batch: the same over a device-resident batch (an am_batch* handle: am_batch_upload / am_batch_from_device)."""
+        return self._counts(lambda out: libam().am_count_by_needle_batch(self._h, case, batch, out))
+
+    def count_by_needle_texts(self, case, texts):
+        """am_count_by_needle: the one-shot form on host texts."""
+        s = _Slices(texts)
+        return self._counts(lambda out: libam().am_count_by_needle(self._h, case, s.arr, s.n, out))
 
 
 class ImageAutomaton:
@@ -670,7 +710,7 @@ class Splitter:
 
 DEBUG_SWITCHES = ("AM_SF_TRACE", "AM_SF_POOL_BLOCKS", "AM_SF_NO_CHILDREN", "AM_DFA", "AM_DFA_CHUNK", "AM_DFA_RARE_PERMILLE", "AM_DFA_MIN_KIB", "AM_DFA_TUNE", "AM_DFA_NO_CHAINS", "AM_FLATTEN_TRACE", "AM_FLATTEN_SERIAL", "AM_NO_IDS_SCAN",
                   "AM_RP_FULL_SCANS", "AM_RP_PIECES", "AM_RP_PARALLEL_FOLD", "AM_RP_GROUPS", "AM_RP_NO_FUSE", "AM_RP_NO_SPIN",
-                  "AM_RP_MAT_MAIN", "AM_RP_NO_RANGE_REUSE", "AM_RP_TRACE", "AM_RP_LDS", "AM_RP_LOOP", "AM_RUN_SEGMENTS")
+                  "AM_RP_MAT_MAIN", "AM_RP_NO_RANGE_REUSE", "AM_RP_TRACE", "AM_RP_LDS", "AM_RP_LOOP", "AM_RUN_SEGMENTS", "AM_HIST_RECORDS_MIB", "AM_HIST_TRACE", "AM_HIST_FLUSH_TILES")
 
 
 def debug_set(name, value):
@@ -689,6 +729,13 @@ def resident_waves():
     one, two = C.c_float(0), C.c_float(0)
     check(libam().am_debug_resident_waves(C.byref(one), C.byref(two)))
     return (32 if two.value < 1.5 * one.value else 16), round(one.value, 3), round(two.value, 3)
+
+
+def hist_adds():
+    """am_debug_hist_adds: (adds absorbed in LDS, adds that went to HBM one by one, flush adds) of the k_needle_hist launches under AM_HIST_TRACE since the last read."""
+    a = np.zeros(3, np.uint64)
+    check(libam().am_debug_hist_adds(a.ctypes.data))
+    return int(a[0]), int(a[1]), int(a[2])
 
 
 def bounds_report():

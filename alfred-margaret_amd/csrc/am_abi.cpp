@@ -668,6 +668,20 @@ void oneshot_trim(int dev)
 }
 }  // namespace
 
+int am::host::upload_batch(const am_slice* hay, size_t n_hay, am_batch* b, bool oneshot) { return upload_slices(hay, n_hay, b, oneshot); }
+am_batch* am::host::oneshot_batch(int dev) { return oneshot_get(dev); }
+void am::host::oneshot_batch_trim(int dev) { oneshot_trim(dev); }
+int am::host::record_array_get(int dev, size_t need, void** p, size_t* cap)
+{
+    *p = g_record_cache[dev].take(need, cap);
+    if (*p) return AM_OK;
+    *cap = need + need / 16;
+    hipError_t e = hipMalloc(p, *cap);
+    if (e != hipSuccess) { *p = nullptr; *cap = 0; return fail(e == hipErrorOutOfMemory ? AM_ERR_OOM : AM_ERR_HIP, std::string("hipMalloc(records): ") + hipGetErrorString(e)); }
+    return AM_OK;
+}
+void am::host::record_array_put(int dev, void* p, size_t cap) { if (p) g_record_cache[dev].give(p, cap); }
+
 extern "C" int am_batch_from_device(const void* d_bytes, const void* d_offsets, size_t n_hay, uint64_t total_bytes, am_batch** out)
 {
     if (!out) return fail(AM_ERR_INVALID, "out is null");

@@ -1,5 +1,11 @@
-// am_contains_all.cpp -- Searcher.containsAll (Searcher.hs:167-187) and the fold checksum of a result, on the device.
+// am_contains_all.cpp -- what is folded over the records with machineValues in flat form (am_needle_ids), on the device: Searcher.containsAll
+// (Searcher.hs:167-187), the fold checksum of a result, and the per-needle match counts (am_count_by_needle*).
 #include "am_host.h"
+
+#include <memory>
+#include <string>
+#include <thread>
+#include <vector>
 
 using namespace am;
 using namespace am::dev;
@@ -10,6 +16,7 @@ using namespace am::host;
 struct am_needle_ids {
     const am_automaton* a = nullptr;
     uint32_t n_needles = 0;
+    uint64_t n_states = 0, n_values = 0;     // entries of vals_off - 1 / of vals
     DevBuf vals_off, vals;
 };
 
@@ -35,7 +42,7 @@ extern "C" int am_needle_ids_create(const am_automaton* a, const uint64_t* value
     const uint64_t n_values = values_offsets[n_states];
     if (n_values && !values) return fail(AM_ERR_INVALID, "values is null");
     am_needle_ids* ids = new am_needle_ids();
-    ids->a = a; ids->n_needles = n_needles;
+    ids->a = a; ids->n_needles = n_needles; ids->n_states = n_states; ids->n_values = n_values;
     int rc = ids->vals_off.ensure((n_states + 1) * 8);
     if (rc == AM_OK) rc = ids->vals.ensure(n_values * 4 + 4);
     if (rc == AM_OK && hipMemcpy(ids->vals_off.p, values_offsets, (n_states + 1) * 8, hipMemcpyHostToDevice) != hipSuccess) rc = fail(AM_ERR_HIP, "upload failed");
@@ -142,4 +149,223 @@ extern "C" int am_contains_all(const am_needle_ids* ids, int case_mode, const am
     const int rc = am_contains_all_batch(ids, case_mode, b, flags_out);
     am_batch_destroy(b);
     return rc;
+}
+
+// ------------------------------------------------------------------ per-needle match counts (term frequencies)
+// counts[v] = how often runWithCase (Automaton.hs:442-553) hands `Match _ v` to the fold function, over the whole batch: the records of a scan are expanded
+// through the value lists and summed into uint64[n_needles] in HBM by k_needle_hist (am_hist.hip).  No record crosses the wire; the record array of a scan
+// is bounded: a batch whose records would exceed the budget is scanned in groups of whole consecutive haystacks, each group folded before the next (integer
+// adds commute: the same counts).
+
+namespace {
+
+constexpr uint64_t kHistRecordBudget = 1ull << 30;       // bytes of records in HBM at a time (64 Mi records; natural text: ~400 MiB of haystacks a group)
+uint64_t hist_budget() { const long v = cfg::get(cfg::kHistRecordsMiB); return v > 0 ? (uint64_t)v << 20 : kHistRecordBudget; }
+
+std::atomic<uint64_t> g_hist_trace[3];                   // AM_HIST_TRACE: sums of the launches' trace words (am_debug_hist_adds)
+
+// a device array for records out of the cache of freed results; goes back there
+struct RecordArray {
+    int dev; void* p = nullptr; size_t cap = 0;
+    explicit RecordArray(int d) : dev(d) {}
+    int ensure(size_t need)
+    {
+        if (need <= cap) return AM_OK;
+        record_array_put(dev, p, cap); p = nullptr; cap = 0;
+        return record_array_get(dev, need, &p, &cap);
+    }
+    ~RecordArray() { record_array_put(dev, p, cap); }
+};
+
+int hist_launch(const am_needle_ids* ids, const Record* recs, uint64_t n_rec, uint64_t* d_counts, uint64_t* d_trace, int dev, hipStream_t st)
+{
+    Prof pr("needle_hist", st);
+    HIP_TRY(launch_needle_hist(recs, n_rec, (const uint64_t*)ids->vals_off.p, (const uint32_t*)ids->vals.p, ids->n_needles, ids->n_states, ids->n_values,
+                               d_counts, d_trace, cfg::get(cfg::kHistFlushTiles) > 0 ? (uint32_t)std::min<long>(cfg::get(cfg::kHistFlushTiles), 1L << 30) : 0u, g_rt.dev[dev].n_cu, st));
+    return AM_OK;
+}
+
+// one scan of `b`, its records folded into d_counts (accumulating); returns when the fold has finished (the record array is free again)
+int hist_scan(const am_needle_ids* ids, int case_mode, am_batch* b, RecordArray& ra, uint64_t* d_counts, uint64_t* d_trace)
+{
+    uint64_t n_rec = 0;
+    auto sink = [&](uint64_t n, Record** ptr) -> int { AM_TRY(ra.ensure(n * sizeof(Record))); *ptr = (Record*)ra.p; return AM_OK; };
+    AM_TRY(run_records(ids->a, case_mode, b, sink, &n_rec));
+    if (n_rec == 0) return AM_OK;
+    ON_DEVICE(b->dev);
+    hipStream_t st; AM_TRY(get_stream(b->dev, &st));
+    AM_TRY(hist_launch(ids, (const Record*)ra.p, n_rec, d_counts, d_trace, b->dev, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return AM_OK;
+}
+
+// the counts of a device-resident batch into d_counts (accumulating), in bounded record memory
+int hist_batch(const am_needle_ids* ids, int case_mode, am_batch* b, uint64_t* d_counts, uint64_t* d_trace)
+{
+    if (b->n_hay == 0 || b->total == 0) return AM_OK;
+    ON_DEVICE(b->dev);                                     // (segments are folded on threads of their own)
+    RecordArray ra(b->dev);
+    const uint64_t budget = hist_budget();
+    // a record per end position at most (and one more per haystack where the empty needle reports position 0): small batches need no count pass
+    if ((b->total + b->n_hay) * sizeof(Record) <= budget || b->n_hay == 1) return hist_scan(ids, case_mode, b, ra, d_counts, d_trace);
+    // the count pass: values per haystack (>= its records: every record carries at least one value)
+    std::vector<uint64_t> per(b->n_hay);
+    uint64_t total_values = 0;
+    AM_TRY(am_count_batch(ids->a, case_mode, b, per.data(), &total_values));
+    if (total_values == 0) return AM_OK;
+    if (total_values * sizeof(Record) <= budget) return hist_scan(ids, case_mode, b, ra, d_counts, d_trace);
+    // groups of whole consecutive haystacks, each a batch of its own: its text copied (device to device) to a 16-byte aligned start, its offsets rebased
+    hipStream_t st; AM_TRY(get_stream(b->dev, &st));
+    std::vector<uint64_t> offs((size_t)b->n_hay + 1), sub_offs;
+    HIP_TRY(hipMemcpyAsync(offs.data(), b->d_offsets, offs.size() * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::unique_ptr<am_batch, void (*)(am_batch*)> sub(new am_batch(), am_batch_destroy);
+    sub->dev = b->dev;
+    for (uint32_t h0 = 0; h0 < b->n_hay;) {
+        uint32_t h1 = h0; uint64_t values = 0;
+        while (h1 < b->n_hay && (h1 == h0 || (values + per[h1]) * sizeof(Record) <= budget)) values += per[h1++];      // (a haystack beyond the budget by itself: a group of one)
+        const uint64_t bytes = offs[h1] - offs[h0];
+        if (values != 0 && bytes != 0) {
+            const size_t padded = padded_text(bytes);
+            AM_TRY(sub->text_buf.ensure(padded));
+            AM_TRY(sub->offs_buf.ensure((size_t)(h1 - h0 + 1) * 8));
+            sub_offs.resize((size_t)(h1 - h0) + 1);
+            for (uint32_t h = h0; h <= h1; h++) sub_offs[h - h0] = offs[h] - offs[h0];
+            HIP_TRY(hipMemcpyAsync(sub->text_buf.p, (const uint8_t*)b->d_text + offs[h0], bytes, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemsetAsync((uint8_t*)sub->text_buf.p + bytes, 0, padded - bytes, st));                        // zero tail: kernels read whole 16-byte groups
+            HIP_TRY(hipMemcpyAsync(sub->offs_buf.p, sub_offs.data(), sub_offs.size() * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            sub->owns = true; sub->d_text = sub->text_buf.p; sub->d_offsets = (uint64_t*)sub->offs_buf.p;
+            sub->total = bytes; sub->n_hay = h1 - h0;
+            AM_TRY(finish_batch(sub.get()));
+            AM_TRY(hist_scan(ids, case_mode, sub.get(), ra, d_counts, d_trace));
+        }
+        h0 = h1;
+    }
+    return AM_OK;
+}
+
+// the histogram of a call in HBM: n_needles counts + the three trace words, cleared; read back at the end
+struct HistOut {
+    DevBuf buf; uint32_t n = 0; bool trace = false;
+    ~HistOut() { buf.release(); }
+    int begin(uint32_t n_needles, hipStream_t st)
+    {
+        n = n_needles; trace = cfg::on(cfg::kHistTrace);
+        AM_TRY(buf.ensure(((size_t)n + 4) * 8));
+        HIP_TRY(hipMemsetAsync(buf.p, 0, ((size_t)n + 4) * 8, st));
+        HIP_TRY(hipStreamSynchronize(st));                   // (segments are folded on other threads' streams)
+        return AM_OK;
+    }
+    uint64_t* counts() { return (uint64_t*)buf.p; }
+    uint64_t* trace_words() { return trace ? (uint64_t*)buf.p + n : nullptr; }
+    int finish(uint64_t* counts_out, hipStream_t st)
+    {
+        uint64_t tw[3] = {0, 0, 0};
+        HIP_TRY(hipMemcpyAsync(counts_out, buf.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+        if (trace) HIP_TRY(hipMemcpyAsync(tw, (uint64_t*)buf.p + n, sizeof(tw), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (int i = 0; i < 3; i++) g_hist_trace[i].fetch_add(tw[i], std::memory_order_relaxed);
+        return AM_OK;
+    }
+};
+
+}  // namespace
+
+extern "C" int am_debug_hist_adds(uint64_t* out3)
+{
+    for (int i = 0; i < 3; i++) { const uint64_t v = g_hist_trace[i].exchange(0, std::memory_order_relaxed); if (out3) out3[i] = v; }
+    return AM_OK;
+}
+
+extern "C" int am_count_by_needle_batch(const am_needle_ids* ids, int case_mode, const am_batch* cb, uint64_t* counts_out)
+{
+    if (!ids || !cb) return fail(AM_ERR_INVALID, "null needle ids or batch");
+    if (ids->n_needles && !counts_out) return fail(AM_ERR_INVALID, "counts_out is null");
+    if (case_mode != AM_CASE_SENSITIVE && case_mode != AM_IGNORE_CASE) return fail(AM_ERR_INVALID, "case_mode must be AM_CASE_SENSITIVE or AM_IGNORE_CASE");
+    if (ids->a->dev != cb->dev) return fail(AM_ERR_INVALID, "needle ids and batch live on different devices");
+    if (ids->n_needles == 0) return AM_OK;
+    AM_TRY(ensure_runtime());
+    am_batch* b = const_cast<am_batch*>(cb);
+    if (b->n_hay == 0 || b->total == 0) { std::memset(counts_out, 0, (size_t)ids->n_needles * 8); return AM_OK; }
+    ON_DEVICE(b->dev);
+    hipStream_t st; AM_TRY(get_stream(b->dev, &st));
+    HistOut out;
+    AM_TRY(out.begin(ids->n_needles, st));
+    AM_TRY(hist_batch(ids, case_mode, b, out.counts(), out.trace_words()));
+    return out.finish(counts_out, st);
+}
+
+extern "C" int am_matches_count_by_needle(const am_matches* m, const am_needle_ids* ids, uint64_t* counts_out)
+{
+    if (!m || !ids) return fail(AM_ERR_INVALID, "null matches or values table");
+    if (ids->n_needles && !counts_out) return fail(AM_ERR_INVALID, "counts_out is null");
+    if (ids->n_needles == 0) return AM_OK;
+    if (m->n && !m->d_records) return fail(AM_ERR_UNSUPPORTED, "am_matches_count_by_needle: the result was assembled on the host (am_run on a large host batch) and has no records in HBM");
+    AM_TRY(ensure_runtime());
+    if (m->dev != ids->a->dev) return fail(AM_ERR_INVALID, "result and values table live on different devices");
+    if (m->n == 0) { std::memset(counts_out, 0, (size_t)ids->n_needles * 8); return AM_OK; }
+    ON_DEVICE(m->dev);
+    hipStream_t st; AM_TRY(get_stream(m->dev, &st));
+    HistOut out;
+    AM_TRY(out.begin(ids->n_needles, st));
+    AM_TRY(hist_launch(ids, m->d_records + m->first, m->n, out.counts(), out.trace_words(), m->dev, st));
+    return out.finish(counts_out, st);
+}
+
+constexpr uint64_t kHistSegmentedFrom = 1ull << 30;       // as am_run: host batches from here on go up in segments of whole haystacks
+constexpr uint64_t kHistSegment = 256ull << 20;
+
+extern "C" int am_count_by_needle(const am_needle_ids* ids, int case_mode, const am_slice* hay, size_t n_hay, uint64_t* counts_out)
+{
+    if (!ids) return fail(AM_ERR_INVALID, "null needle ids");
+    if (n_hay && !hay) return fail(AM_ERR_INVALID, "hay is null");
+    if (n_hay >= 0xFFFFFFFFull) return fail(AM_ERR_INVALID, "too many haystacks");
+    if (ids->n_needles && !counts_out) return fail(AM_ERR_INVALID, "counts_out is null");
+    if (case_mode != AM_CASE_SENSITIVE && case_mode != AM_IGNORE_CASE) return fail(AM_ERR_INVALID, "case_mode must be AM_CASE_SENSITIVE or AM_IGNORE_CASE");
+    uint64_t total = 0;
+    for (size_t i = 0; i < n_hay; i++) { if (hay[i].len && !hay[i].ptr) return fail(AM_ERR_INVALID, "slice with null ptr"); total += hay[i].len; }
+    if (ids->n_needles == 0) return AM_OK;
+    AM_TRY(ensure_runtime());
+    if (total == 0) { std::memset(counts_out, 0, (size_t)ids->n_needles * 8); return AM_OK; }
+    const int dev = ids->a->dev;
+    ON_DEVICE(dev);
+    const long forced = cfg::get(cfg::kRunSegments);       // (the switch of am_run's segments: 0 = never, k > 0 = always, segments of k KiB)
+    if (n_hay < 2 || forced == 0 || (forced < 0 && total < kHistSegmentedFrom)) {
+        am_batch* b = oneshot_batch(dev);                   // this thread's batch on the automaton's device
+        int rc = upload_batch(hay, n_hay, b, true);
+        if (rc == AM_OK) rc = am_count_by_needle_batch(ids, case_mode, b, counts_out);
+        oneshot_batch_trim(dev);
+        return rc;
+    }
+    // Segments of whole haystacks into two batches that take turns: while this thread uploads segment k + 1, a thread of its own scans segment k and folds its
+    // records in HBM.  What the wire carries is the text, once, and n_needles counts at the end.
+    hipStream_t st; AM_TRY(get_stream(dev, &st));
+    HistOut out;
+    AM_TRY(out.begin(ids->n_needles, st));
+    std::unique_ptr<am_batch, void (*)(am_batch*)> second(new am_batch(), am_batch_destroy);
+    second->dev = dev;
+    am_batch* turn[2] = {oneshot_batch(dev), second.get()};
+    const uint64_t segment = forced > 0 ? (uint64_t)forced << 10 : kHistSegment;
+    std::thread worker;
+    int rc = AM_OK, worker_rc = AM_OK; std::string worker_err;
+    auto join = [&] { if (worker.joinable()) worker.join(); if (rc == AM_OK && worker_rc != AM_OK) rc = fail(worker_rc, worker_err); };
+    size_t k = 0;
+    for (size_t i = 0; i < n_hay && rc == AM_OK; k++) {
+        size_t j = i; uint64_t bytes = 0;
+        while (j < n_hay && bytes < (i == 0 ? segment / 4 : segment)) bytes += hay[j++].len;      // (the first a quarter of the others: no scan runs beside its upload)
+        am_batch* b = turn[k & 1];                          // (its last scan, segment k - 2, was joined before segment k - 1 started)
+        rc = upload_batch(hay + i, j - i, b, false);
+        join();
+        if (rc != AM_OK) break;
+        worker = std::thread([&, b] {
+            worker_rc = hist_batch(ids, case_mode, b, out.counts(), out.trace_words());
+            if (worker_rc != AM_OK) worker_err = am_last_error();
+        });
+        i = j;
+    }
+    join();
+    oneshot_batch_trim(dev);
+    if (rc != AM_OK) return rc;
+    return out.finish(counts_out, st);
 }

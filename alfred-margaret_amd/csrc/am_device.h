@@ -139,6 +139,11 @@ hipError_t launch_idset(const Record* recs, uint64_t r0, uint64_t r1, const uint
 hipError_t launch_fold_hash(const Record* recs, const uint64_t* rec_first, const uint64_t* vals_off, const uint32_t* vals, uint32_t n_hay,
                             uint64_t* hash_out, uint64_t* count_out, hipStream_t st);
 hipError_t launch_idset_all(const uint32_t* bits, uint32_t words, uint32_t n_needles, uint32_t n_hay, uint8_t* flags, hipStream_t st);
+// per-needle match counts (am_hist.hip): counts[id] += occurrences of id < n_needles in the value lists of records [0, n_rec); a persistent grid sized from n_cu.
+// n_states / n_values: entries of vals_off - 1 / of vals (index checks).  trace (nullable; the instrumented instantiation): [0] adds the workgroups' LDS tables absorbed,
+// [1] adds that went to HBM one by one (slot conflicts), [2] adds of the flushes
+hipError_t launch_needle_hist(const Record* recs, uint64_t n_rec, const uint64_t* vals_off, const uint32_t* vals, uint32_t n_needles, uint64_t n_states,
+                              uint64_t n_values, uint64_t* counts, uint64_t* trace, uint32_t flush_tiles /* 0: the kernel's own interval */, int n_cu, hipStream_t st);
 // incremental re-scan between Replacer passes (am_replace.hip)
 struct RpWin { uint64_t src_abs; uint64_t ws; uint32_t len; uint32_t own_lo; };   // window: bytes src_abs.. of the next text; ws = its start inside the haystack; records with end > own_lo are its own
 hipError_t launch_rp_win_count(const RpHay* hs, uint32_t n_act, uint32_t* nwin, hipStream_t st);

@@ -1,0 +1,140 @@
+// am_hist.hip -- per-needle match counts: the fold `Map.insertWith (+) v 1` over every (record, value of machineValues ! record.state)
+// (reference: src/Data/Text/AhoCorasick/Automaton.hs:442-553 runWithCase and the folds over it; the count identity sum(counts) == countMatches is
+// benchmark/haskell/app/Main.hs:67-76), on the records a scan has left in HBM.  A sibling of k_idset / k_fold_hash (am_replace.hip): the same
+// expansion of a record through the flat value lists of am_needle_ids, into a histogram uint64[n_needles] instead of a bitmap or a checksum.
+//
+// Natural text is Zipf-distributed: one global atomic per value would send a large share of all adds to a few dozen addresses, and adders that meet on
+// one row run an order of magnitude below adders that are spread.  So the adds of a workgroup to the same id are combined ON CHIP:
+//   * a persistent grid (a few workgroups per CU) walks the records in tiles of kHistTile;
+//   * every workgroup keeps a direct-mapped table of kHistSlots {id tag, u32 count} in LDS.  A lane claims an empty slot for its id with an LDS
+//     compare-and-swap on the tag; a slot that carries the id is an LDS add; a slot that carries another id is a conflict, and that one add goes to HBM
+//     as a 64-bit global atomic (tags never change once claimed: no eviction, nothing to re-validate);
+//   * at the end the workgroup adds every live slot to HBM with one 64-bit global atomic.
+// No LDS counter can wrap: a record adds at most kHistLdsPerRecord times to LDS (the values of a list beyond that go to HBM directly), a tile has kHistTile
+// records, and the workgroup flushes (and clears) its counts after at most kHistTilesPerFlush tiles
+// (AM_HIST_FLUSH_TILES lets a test ask for fewer, never more): at most 1024 * 1024 * 2048 = 2^31 adds between two flushes,
+// all of them to one slot in the worst case, below 2^32.
+// Lane per RECORD, the value list of a record looped by its lane: the states of a dictionary carry one value almost everywhere (a suffix chain like
+// tshirt / shirt / hirt a few), so a wave-wide prefix sum to spread values over lanes would be paid by every record for the sake of few.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "am_bounds.h"
+#include "am_device.h"
+
+AM_BOUNDS_TU("am_hist.hip")
+
+namespace am {
+namespace dev {
+
+namespace {
+
+constexpr uint32_t kWave = 64;
+constexpr uint32_t kHistThreads = 256;
+constexpr uint32_t kHistPerThread = 4;                    // records a lane takes per tile: their loads are issued together
+constexpr uint32_t kHistTile = kHistThreads * kHistPerThread;
+constexpr uint32_t kHistSlotBits = 12;
+constexpr uint32_t kHistSlots = 1u << kHistSlotBits;      // 4096 slots = 32 KiB of LDS: four workgroups (16 wavefronts) per CU
+constexpr uint32_t kHistLdsPerRecord = 1024;
+constexpr uint32_t kHistTilesPerFlush = 2048;
+constexpr uint32_t kHistEmpty = 0xFFFFFFFFu;              // no id: ids are < n_needles <= 2^32 - 1
+constexpr int kHistGroupsPerCu = 4;
+static_assert((uint64_t)kHistTile * kHistLdsPerRecord * kHistTilesPerFlush < (1ull << 32), "an LDS counter could wrap between two flushes");
+
+// ids are handles in the caller's order (alphabetical, by frequency, ...): a multiplicative hash spreads neighbours over the table
+__device__ __forceinline__ uint32_t hist_slot(uint32_t id) { return (id * 0x9E3779B1u) >> (32 - kHistSlotBits); }
+
+template <bool kTrace>
+__global__ void __launch_bounds__(kHistThreads) k_needle_hist(const Record* __restrict__ recs, uint64_t n_rec, const uint64_t* __restrict__ vals_off,
+                                                              const uint32_t* __restrict__ vals, uint32_t n_needles, uint64_t n_states, uint64_t n_values,
+                                                              unsigned long long* __restrict__ counts, unsigned long long* __restrict__ trace, uint32_t tiles_per_flush)
+{
+    __shared__ uint32_t tag[kHistSlots];
+    __shared__ uint32_t cnt[kHistSlots];
+    for (uint32_t i = threadIdx.x; i < kHistSlots; i += kHistThreads) { tag[i] = kHistEmpty; cnt[i] = 0; }
+    __syncthreads();
+    // every live slot to HBM with one add; `clear`: the counts start again (the tags stay: the hot ids keep their slots)
+    auto flush = [&](bool clear) -> uint64_t {
+        uint64_t adds = 0;
+        for (uint32_t i = threadIdx.x; i < kHistSlots; i += kHistThreads) {
+            const uint32_t c = cnt[i];
+            if (c == 0) continue;
+            const uint32_t id = tag[i];
+            AM_BOUNDS(id < n_needles);
+            if (id < n_needles) atomicAdd(&counts[id], (unsigned long long)c);
+            if (clear) cnt[i] = 0;
+            adds++;
+        }
+        return adds;
+    };
+    uint64_t in_lds = 0, in_hbm = 0, in_flush = 0;        // (kTrace only)
+    const uint64_t n_tiles = (n_rec + kHistTile - 1) / kHistTile;
+    uint32_t since_flush = 0;
+    for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {            // (the same tiles for every lane of the workgroup: the barriers below are uniform)
+        uint64_t k[kHistPerThread], ke[kHistPerThread];
+#pragma unroll
+        for (uint32_t u = 0; u < kHistPerThread; u++) {
+            const uint64_t r = t * kHistTile + u * kHistThreads + threadIdx.x;
+            k[u] = ke[u] = 0;
+            if (r < n_rec) {
+                const uint32_t state = recs[r].state;
+                AM_BOUNDS(state < n_states);
+                if (state < n_states) { k[u] = vals_off[state]; ke[u] = vals_off[state + 1]; }
+                AM_BOUNDS(k[u] <= ke[u] && ke[u] <= n_values);
+                if (ke[u] > n_values) ke[u] = n_values;
+            }
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < kHistPerThread; u++) {
+            for (uint64_t j = 0; k[u] + j < ke[u]; j++) {
+                const uint32_t id = vals[k[u] + j];
+                if (id >= n_needles) continue;                               // a handle beyond the table: skipped, as containsAll skips it (k_idset)
+                uint32_t s = 0;
+                bool hit = false;
+                if (j < kHistLdsPerRecord) {
+                    s = hist_slot(id);
+                    AM_BOUNDS(s < kHistSlots);
+                    uint32_t tg = ((volatile uint32_t*)tag)[s];
+                    if (tg == kHistEmpty) { tg = atomicCAS(&tag[s], kHistEmpty, id); if (tg == kHistEmpty) tg = id; }
+                    hit = tg == id;
+                }
+                if (hit) atomicAdd(&cnt[s], 1u);
+                else atomicAdd(&counts[id], 1ull);
+                if (kTrace) { if (hit) in_lds++; else in_hbm++; }
+            }
+        }
+        if (++since_flush >= tiles_per_flush) {
+            __syncthreads();
+            in_flush += flush(true);
+            __syncthreads();
+            since_flush = 0;
+        }
+    }
+    __syncthreads();
+    in_flush += flush(false);
+    if (kTrace) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) { in_lds += __shfl_xor(in_lds, d, kWave); in_hbm += __shfl_xor(in_hbm, d, kWave); in_flush += __shfl_xor(in_flush, d, kWave); }
+        if ((threadIdx.x & (kWave - 1)) == 0) { atomicAdd(&trace[0], in_lds); atomicAdd(&trace[1], in_hbm); atomicAdd(&trace[2], in_flush); }
+    }
+}
+
+}  // namespace
+
+hipError_t launch_needle_hist(const Record* recs, uint64_t n_rec, const uint64_t* vals_off, const uint32_t* vals, uint32_t n_needles, uint64_t n_states,
+                              uint64_t n_values, uint64_t* counts, uint64_t* trace, uint32_t flush_tiles, int n_cu, hipStream_t st)
+{
+    if (n_rec == 0 || n_needles == 0) return hipSuccess;
+    const uint64_t n_tiles = (n_rec + kHistTile - 1) / kHistTile;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)(n_cu > 0 ? n_cu : 1) * kHistGroupsPerCu);
+    const uint32_t tiles_per_flush = flush_tiles != 0 && flush_tiles < kHistTilesPerFlush ? flush_tiles : kHistTilesPerFlush;      // (never more than the bound the wrap argument rests on)
+    if (trace) hipLaunchKernelGGL(k_needle_hist<true>, dim3(grid), dim3(kHistThreads), 0, st, recs, n_rec, vals_off, vals, n_needles, n_states, n_values,
+                                  (unsigned long long*)counts, (unsigned long long*)trace, tiles_per_flush);
+    else hipLaunchKernelGGL(k_needle_hist<false>, dim3(grid), dim3(kHistThreads), 0, st, recs, n_rec, vals_off, vals, n_needles, n_states, n_values,
+                            (unsigned long long*)counts, (unsigned long long*)nullptr, tiles_per_flush);
+    return hipGetLastError();
+}
+
+}  // namespace dev
+}  // namespace am

@@ -184,6 +184,13 @@ int scan_needle_ids(const am_automaton* a, int case_mode, am_batch* b, const uin
 int run_records(const am_automaton* a, int case_mode, am_batch* b, const std::function<int(uint64_t, Record**)>& sink_final, uint64_t* n_out, bool have_lock = false);
 // the same without a host round trip (suffix-filter route, worst-case pool): the count stays on the device
 int run_records_async(const am_automaton* a, int case_mode, am_batch* b, Record* d_out, const uint64_t** n_dev, hipStream_t st);
+// what am_count_by_needle* (am_contains_all.cpp) shares with the run entry points: the slices of a call into a batch (oneshot: small uploads stay enqueued on the calling
+// thread's stream), the calling thread's one-shot batch on a device, and the device arrays of freed results (kept for the next records: taken from there or allocated, given back)
+int upload_batch(const am_slice* hay, size_t n_hay, am_batch* b, bool oneshot);
+am_batch* oneshot_batch(int dev);
+void oneshot_batch_trim(int dev);
+int record_array_get(int dev, size_t need, void** p, size_t* cap);
+void record_array_put(int dev, void* p, size_t cap);
 inline size_t padded_text(uint64_t total) { return (size_t)((total + 15) & ~15ull) + 16; }
 
 }  // namespace host

@@ -254,6 +254,37 @@ A runWithCase(CaseSensitivity cs, A seed, F f, const AcMachine<V>& machine, cons
 template <class A, class V, class F> A runText(A seed, F f, const AcMachine<V>& m, const Text& t) { return runWithCase(CaseSensitivity::CaseSensitive, std::move(seed), f, m, t); }   // :539-541
 template <class A, class V, class F> A runLower(A seed, F f, const AcMachine<V>& m, const Text& t) { return runWithCase(CaseSensitivity::IgnoreCase, std::move(seed), f, m, t); }     // :551-553
 
+// Term frequencies: the fold  runWithCase cs Map.empty (\m (Match _ v) -> Step (Map.insertWith (+) v 1 m))  (Automaton.hs:442-553) over a batch of haystacks, as a
+// dense vector indexed by the value (V an integral handle): out[v] = how often the reference would call the fold function with `Match _ v`; the sum is countMatches
+// (benchmark/haskell/app/Main.hs:67-76).  nValues: length of the vector (values beyond it and negative values are skipped); by default 1 + the largest value.
+// The records are folded on the device (am_count_by_needle): none travels to the host.
+template <class V>
+std::vector<uint64_t> countByNeedle(CaseSensitivity cs, const AcMachine<V>& machine, const std::vector<Text>& texts, size_t nValues = SIZE_MAX)
+{
+    std::vector<uint64_t> voff(machine.machineValues.size() + 1, 0);
+    std::vector<uint32_t> vals;
+    uint64_t largest = 0; bool any = false;
+    for (size_t st = 0; st < machine.machineValues.size(); st++) {
+        for (const V& v : machine.machineValues[st]) {
+            const bool ok = !(v < V(0)) && (uint64_t)v < UINT32_MAX;
+            vals.push_back(ok ? (uint32_t)v : UINT32_MAX);
+            if (ok) { any = true; if ((uint64_t)v > largest) largest = (uint64_t)v; }
+        }
+        voff[st + 1] = vals.size();
+    }
+    const size_t n = nValues != SIZE_MAX ? nValues : (any ? (size_t)largest + 1 : 0);
+    if (n > UINT32_MAX) throw AmError(AM_ERR_INVALID, "countByNeedle: more than 2^32 - 1 values");
+    std::vector<uint64_t> out(n, 0);
+    if (n == 0) return out;
+    if (vals.empty()) vals.push_back(0);
+    am_needle_ids* raw = nullptr;
+    amCheck(am_needle_ids_create(machine.device.get(), voff.data(), vals.data(), (uint32_t)n, &raw));
+    std::unique_ptr<am_needle_ids, void (*)(am_needle_ids*)> ids(raw, am_needle_ids_destroy);
+    std::vector<am_slice> slices(texts.size());
+    for (size_t i = 0; i < texts.size(); i++) slices[i] = am_slice{texts[i].data, texts[i].off, texts[i].len};
+    amCheck(am_count_by_needle(ids.get(), (int)cs, slices.data(), slices.size(), out.data()));
+    return out;
+}
 
 // Automaton.hs:555-566 needleCasings: every text that lower-cases to the given (lower case) text: the product of unlowerCodePoint over its code
 // points, first code point slowest, each in the reference's order ("abc" -> abc abC aBc aBC Abc AbC ABc ABC; "ABC" -> nothing).

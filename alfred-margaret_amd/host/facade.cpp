@@ -86,6 +86,15 @@ int amh_count(void* h, int case_mode, const am_slice* hay, size_t n_hay, uint64_
     return guarded([&] { amCheck(am_count(static_cast<MachineBox*>(h)->m.device.get(), case_mode, hay, n_hay, counts_out)); });
 }
 
+// per-value match counts of a batch (countByNeedle): counts_out has n_values entries
+int amh_count_by_needle(void* h, int case_mode, const am_slice* hay, size_t n_hay, size_t n_values, uint64_t* counts_out)
+{
+    return guarded([&] {
+        auto r = countByNeedle((CaseSensitivity)case_mode, static_cast<MachineBox*>(h)->m, sliceTexts(hay, n_hay), n_values);
+        for (size_t i = 0; i < r.size(); i++) counts_out[i] = r[i];
+    });
+}
+
 // ---- Searcher
 int amh_searcher_build(int case_mode, const uint8_t* bytes, const uint64_t* offs, size_t n, void** out)
 {

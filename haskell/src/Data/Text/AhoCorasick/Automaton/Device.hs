@@ -25,6 +25,7 @@ module Data.Text.AhoCorasick.Automaton.Device
   , runBatchWithCaseDevice
   , countMatchesDevice
   , containsAnyDevice
+  , countByNeedle
     -- * For the sibling modules
   , AmAutomaton
   , AmSlice (..)
@@ -50,12 +51,14 @@ import qualified Data.Primitive as Prim
 import qualified Data.Primitive.ByteArray as BA
 import qualified Data.Text.Array as TextArray
 import qualified Data.Vector as Vector
+import qualified Data.Vector.Unboxed as UVector
 
 import Data.Text.AhoCorasick.Automaton (AcMachine (..), CaseSensitivity (..), CodeUnitIndex (..), Match (..), Next (..))
 import Data.Text.Utf8 (Text (..))
 
 data AmAutomaton
 data AmMatches
+data AmNeedleIds
 
 -- | @am_slice@ = @U8Slice@ of benchmark/rust-ffi/app/Main.hs:34-45 (= Data.Text.Internal.Text array/offset/length).
 data AmSlice = AmSlice !(Ptr Word8) !CSize !CSize
@@ -97,6 +100,13 @@ foreign import ccall unsafe "am_matches_free"
   c_am_matches_free :: Ptr AmMatches -> IO ()
 foreign import ccall unsafe "am_last_error"
   c_am_last_error :: IO (Ptr CChar)
+-- machineValues in flat form on the device (uploads: `safe`), what am_count_by_needle expands the records with
+foreign import ccall safe "am_needle_ids_create"
+  c_am_needle_ids_create :: Ptr AmAutomaton -> Ptr Word64 -> Ptr Word32 -> Word32 -> Ptr (Ptr AmNeedleIds) -> IO CInt
+foreign import ccall safe "am_needle_ids_destroy"
+  c_am_needle_ids_destroy :: Ptr AmNeedleIds -> IO ()
+foreign import ccall safe "am_count_by_needle"
+  c_am_count_by_needle :: Ptr AmNeedleIds -> CInt -> Ptr AmSlice -> CSize -> Ptr Word64 -> IO CInt
 
 -- | An 'AcMachine' plus its flattened copy in HBM.  'machineValues' never leaves Haskell.
 data DeviceMachine v = DeviceMachine
@@ -192,6 +202,27 @@ containsAnyDevice cs (DeviceMachine _ h) texts =
   allocaArray (max n 1) $ \pFlags -> withForeignPtr h $ \ph -> do
     c_am_contains_any ph (caseFlag cs) pSlices (fromIntegral n) pFlags >>= checkRc
     map (/= (0 :: Word8)) <$> peekArray n pFlags
+
+-- | Term frequencies: the fold @runWithCase cs Map.empty (\m (Match _ v) -> Step (Map.insertWith (+) v 1 m))@ (Automaton.hs:442-553) over all the
+-- texts, as a dense vector indexed by the value: element @v@ = how often the reference would call the fold function with @Match _ v@; the sum is
+-- @countMatches@ (benchmark/haskell/app/Main.hs:67-76).  The vector has @1 + maximum value@ elements; negative values are skipped.  The records are
+-- scanned and folded in HBM (am_count_by_needle): what comes back is the vector.
+countByNeedle :: CaseSensitivity -> DeviceMachine Int -> [Text] -> IO (UVector.Vector Word64)
+countByNeedle cs (DeviceMachine m h) texts = do
+  let lists   = Vector.toList (machineValues m)
+      flat    = [ if v < 0 then maxBound else fromIntegral v :: Word32 | vs <- lists, v <- vs ]
+      offsets = scanl (+) 0 (map (fromIntegral . length) lists) :: [Word64]
+      n       = if null (filter (>= 0) (concat lists)) then 0 else 1 + maximum (concat lists)
+  if n == 0 then pure UVector.empty else
+    withArray offsets $ \pOff -> withArray (if null flat then [0] else flat) $ \pVals ->
+    withPinnedTexts texts $ \pSlices nTexts ->
+    allocaArray n $ \pCounts -> alloca $ \out -> withForeignPtr h $ \ph -> do
+      c_am_needle_ids_create ph pOff pVals (fromIntegral n) out >>= checkRc
+      ids <- peek out
+      rc <- c_am_count_by_needle ids (caseFlag cs) pSlices (fromIntegral nTexts) pCounts
+      c_am_needle_ids_destroy ids
+      checkRc rc
+      UVector.fromList <$> peekArray n pCounts
 
 -- ---- helpers -----------------------------------------------------------------------------------
 

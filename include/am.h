@@ -183,6 +183,28 @@ AM_API void am_needle_ids_destroy(am_needle_ids* ids);
 AM_API int am_contains_all(const am_needle_ids* ids, int case_mode, const am_slice* hay, size_t n_hay, uint8_t* flags_out);
 AM_API int am_contains_all_batch(const am_needle_ids* ids, int case_mode, const am_batch* b, uint8_t* flags_out);
 
+/* ---- per-needle match counts (term frequencies of a dictionary over a corpus) ---------------------
+ * The fold  runWithCase cs Map.empty (\m (Match _ v) -> Step (Map.insertWith (+) v 1 m))  (Automaton.hs:442-553: runWithCase / runText / runLower), summed over all
+ * haystacks of the batch, as a dense vector: counts_out[v] for v < n_needles = how often the reference would call the fold function with `Match _ v`, i.e. the sum over
+ * the records r of the number of k in [values_offsets[r.state], values_offsets[r.state + 1]) with values[k] == v.  Overlapping occurrences count; a needle given twice
+ * with two handles counts under both; a state reached through suffix outputs counts every value of its list; the empty needle counts once per position, as the
+ * reference reports it.  Handles >= n_needles are SKIPPED (the convention of am_needle_ids: containsAll ignores them likewise); when every handle is < n_needles,
+ * the sum of counts_out equals am_count_batch's total (countMatches, benchmark/haskell/app/Main.hs:67-76).  `ids` carries machineValues in flat form
+ * (am_needle_ids_create).  counts_out: n_needles entries of host memory; with n_needles == 0 nothing is written (AM_OK); with no haystacks every count is 0.
+ * The records are produced and folded in HBM (csrc/am_hist.hip) and never cross the wire; what comes back is n_needles counts.
+ *   am_count_by_needle_batch    a device-resident batch, on whatever route the automaton takes.  Record memory is bounded: a batch whose records would exceed 1 GiB is
+ *                               counted first (am_count_batch) and then scanned in groups of whole consecutive haystacks, each group folded before the next is scanned;
+ *                               the counts are the same (integer adds commute).  A single haystack whose records alone exceed the bound is scanned whole, and for an automaton with the
+ *                               empty needle (a record at almost every position) the count pass itself goes through the records of the whole batch: no bound there.
+ *   am_count_by_needle          the one-shot form on host slices.  A batch of 1 GiB and more goes up in segments of whole haystacks (like am_run's), and a segment's
+ *                               records are folded in HBM while the next segment is uploaded.
+ *   am_matches_count_by_needle  the same fold over a result the caller holds (am_run_batch, am_run).  AM_ERR_UNSUPPORTED when the result was assembled on the host
+ *                               (am_run on a large host batch: no records in HBM), AM_ERR_INVALID when result and table live on different devices.
+ * Arguments are checked before any device work: AM_ERR_INVALID for null ids / batch / result, a null counts_out with n_needles > 0, slices without memory. */
+AM_API int am_count_by_needle_batch(const am_needle_ids* ids, int case_mode, const am_batch* b, uint64_t* counts_out /* n_needles, host */);
+AM_API int am_count_by_needle(const am_needle_ids* ids, int case_mode, const am_slice* hay, size_t n_hay, uint64_t* counts_out /* n_needles, host */);
+AM_API int am_matches_count_by_needle(const am_matches* m, const am_needle_ids* ids, uint64_t* counts_out /* n_needles, host */);
+
 /* Checksum of the fold sequence of a result (harness aid; SURVEY 8d "parity check at scale",
  * benchmark/benchmark.py:65-69 asserts count identity on every run).  For every haystack i < n_hay:
  *   hash_out[i]  = foldl (\h (pos, v) -> h * 0x100000001B3 + mix pos v) 0  over the matches the reference's

@@ -36,6 +36,11 @@ AM_API int am_debug_bounds_report(uint64_t* failed_out, uint32_t* first_line_out
  * bench.py prints the answer as `machine.resident_waves_per_cu`. */
 AM_API int am_debug_resident_waves(float* one_ms_out, float* two_ms_out);
 
+/* Under AM_HIST_TRACE the launches of k_needle_hist (am_count_by_needle*, csrc/am_hist.hip) run their instrumented instantiation: out3[0] = adds the workgroups' LDS tables
+ * absorbed, out3[1] = adds that went to HBM one by one (slot conflicts, values far down a long list), out3[2] = adds of the flushes (one per live slot), summed over the
+ * calls since the last read; reading clears the sums (out3 NULL: only clears).  tests/measure/needle_counts.py. */
+AM_API int am_debug_hist_adds(uint64_t* out3);
+
 #ifdef __cplusplus
 }
 #endif
