@@ -20,7 +20,7 @@ enum Key {
     kDfaChunk,            // AM_DFA_CHUNK: bytes of the batch one lane of k_dfa owns (read when an image is flattened; default 2048)
     kDfaRarePermille,     // AM_DFA_RARE_PERMILLE: share of the edges (in thousandths; default 1) whose bytes may go without a column of the DFA table (tests: 300 makes most bytes rare)
     kDfaMinKiB,           // AM_DFA_MIN_KIB: batch size from which a dictionary's scans take the table walk by themselves (default 32 768: below, a unit's walk costs more than the filter's whole scan)
-    kDfaTune,             // AM_DFA_TUNE: launch parameters of k_dfa for A/B measurements (am_dfa.hip dfa_tune)
+    kDfaTune,             // AM_DFA_TUNE: launch parameters of k_dfa for A/B measurements (am_dfa.hip dfa_launch_shape)
     kDfaNoChains,         // AM_DFA_NO_CHAINS: every state of the DFA section gets a dense row (A/B against the chain records; read when an image is flattened)
     kFlattenTrace,        // AM_FLATTEN_TRACE: the flattener prints its phases with their wall time on stderr
     kFlattenSerial,       // AM_FLATTEN_SERIAL: the flattener starts no task (tests: the images are the same byte for byte; am_automaton_create flattens IgnoreCase on first use)

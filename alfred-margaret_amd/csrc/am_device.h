@@ -1,4 +1,4 @@
-// am_device.h -- interface between the C-ABI layer (am_abi.cpp) and the kernels (am_kernels.hip)
+// am_device.h -- interface between the C-ABI layer (am_abi.cpp, am_run.cpp) and the kernels (am_kernels.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -71,17 +71,24 @@ hipError_t launch_ac(bool ic, int mode, const AcView& a, const BatchView& b, con
 // table-walk kernel (am_dfa.hip): same two-pass protocol as the general kernel (count -> scan -> emit), unit = one lane's DfaView::chunk bytes
 uint64_t dfa_units(const DfaView& d, const BatchView& b);
 bool dfa_usable(const DfaView& d);      // on the current device: offsets fit, the LDS attribute could be raised (checked once per device)
-hipError_t launch_dfa(int mode, const DfaView& d, const BatchView& b, const ScanOut& o, int n_cu, hipStream_t st);
+// k_dfa's launch geometry, decided ONCE per entry-point call (dfa_launch_shape, on the current device) and handed to every launch of that call: the walk, its retries
+// and k_dfa_place agree on it whatever AM_DFA_TUNE or the device's probe (am_dfa.hip dfa_resident_sets) would say a moment later
+struct DfaLaunch {
+    int n_cu; uint32_t workgroups, per_cu;        // the grid; workgroups per CU (2, or 1 with all of the LDS)
+    uint32_t lds_rows, hot_rows, lds_n1, lds_n2;  // what a workgroup keeps in LDS: rows (room for / read from LDS: AM_DFA_TUNE bits 8-23 cap the latter), single-entry and two-entry records (bit 24: none)
+    uint32_t walk; bool place_wide;               // AM_DFA_TUNE bits 0-3 (the walk variant) and 25 (k_dfa_place's table of seen states with 8-byte entries)
+};
+DfaLaunch dfa_launch_shape(const DfaView& d, const BatchView& b, int n_cu);
+hipError_t launch_dfa(int mode, const DfaView& d, const BatchView& b, const ScanOut& o, const DfaLaunch& s, hipStream_t st);
 // records in ONE walk: 8-byte tokens into ScanOut::pool (superblocks; ScanOut::block_next = 2 x n_blocks words: their fill counts, zeroed before the launch, then their
 // first groups; pool_ctrl[0] superblocks drawn, [1] pool exhausted; n_blocks = superblocks in the pool), unit_counts as in count mode; then scan(unit_counts) and launch_dfa_place
 // an estimate of the needle ends per byte of a batch: n_samples lanes spread over the text walk len bytes each and add their count to *out (zeroed by the caller)
 hipError_t launch_dfa_sample(const DfaView& d, const uint8_t* text, uint64_t total, uint32_t n_samples, uint32_t len, uint32_t* out, hipStream_t st);
 bool dfa_tokens_ok(const DfaView& d);
-uint32_t dfa_token_waves(const DfaView& d, const BatchView& b, int n_cu);
-uint64_t dfa_token_superblocks(uint64_t records, uint32_t n_waves, uint64_t n_units);
+uint64_t dfa_token_superblocks(uint64_t records, uint32_t n_waves /* 16 x DfaLaunch::workgroups */, uint64_t n_units);
 uint64_t dfa_superblock_bytes();
-hipError_t launch_dfa_tokens(const DfaView& d, const BatchView& b, const ScanOut& o, int n_cu, hipStream_t st);
-hipError_t launch_dfa_place(const DfaView& d, const BatchView& b, const ScanOut& o, uint32_t n_super, const uint64_t* unit_offsets, int n_cu, uint32_t n_waves, uint32_t n_ref_states, Record* out, hipStream_t st);
+hipError_t launch_dfa_tokens(const DfaView& d, const BatchView& b, const ScanOut& o, const DfaLaunch& s, hipStream_t st);
+hipError_t launch_dfa_place(const DfaView& d, const BatchView& b, const ScanOut& o, uint32_t n_super, const uint64_t* unit_offsets, const DfaLaunch& s, uint32_t n_ref_states, Record* out, hipStream_t st);
 hipError_t read_sf_phase_cycles(uint64_t* out5);
 hipError_t read_sf_wave_records(uint64_t* out, size_t n_waves);
 hipError_t scan_temp_bytes(uint64_t n, size_t* bytes);

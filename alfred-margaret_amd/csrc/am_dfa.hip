@@ -33,6 +33,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <mutex>
 
 #include "am_bounds.h"
 #include "am_config.h"
@@ -365,7 +366,7 @@ __global__ __launch_bounds__(1024, 8) void k_dfa(DfaView d, BatchView b, ScanOut
 }
 
 // How dense are needle ends in this batch?  n_samples lanes, spread evenly over the text, each walk `len` bytes from the root (no warm-up, haystack boundaries
-// ignored: an estimate) and count the steps that land on a needle end.  What the ABI layer chooses the route of a dictionary by (am_abi.cpp make_plan).
+// ignored: an estimate) and count the steps that land on a needle end.  What the ABI layer chooses the route of a dictionary by (am_run.cpp make_plan).
 __global__ __launch_bounds__(256) void k_dfa_sample(DfaView d, const uint8_t* __restrict__ text, uint64_t total, uint32_t n_samples, uint32_t len, uint32_t* __restrict__ out)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -486,12 +487,11 @@ uint64_t dfa_units(const DfaView& d, const BatchView& b) { return d.chunk ? (b.t
 // process) must say "twice the time" both times.
 static uint32_t dfa_resident_sets(int dev)
 {
-    static std::atomic<int> state[64];                       // 0: not asked, 1: one set of 16 wavefronts at a time, 2: two
+    static std::once_flag asked[64];                         // concurrent first users of a device wait for its ONE probe and read the same answer
+    static int state[64];                                    // 1: one set of 16 wavefronts at a time, 2: two
     if (dev < 0 || dev >= 64) return 2;
-    int s = state[dev].load(std::memory_order_acquire);
-    if (s == 0) {
-        s = 2;
-        int n_cu = 0;
+    std::call_once(asked[dev], [dev] {
+        int s = 2, n_cu = 0;
         uint32_t* d_out = nullptr;
         hipEvent_t a = nullptr, b = nullptr;
         if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n_cu > 0 && hipMalloc((void**)&d_out, 64) == hipSuccess &&
@@ -513,39 +513,32 @@ static uint32_t dfa_resident_sets(int dev)
         if (a) (void)hipEventDestroy(a);
         if (b) (void)hipEventDestroy(b);
         if (d_out) (void)hipFree(d_out);
-        state[dev].store(s, std::memory_order_release);
-    }
-    return (uint32_t)s;
-}
-static uint32_t dfa_tune();
-static uint32_t dfa_per_cu()
-{
-    const uint32_t asked = (dfa_tune() >> 4) & 15u;
-    if (asked) return asked;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 2;
-    return dfa_resident_sets(dev);
-}
-// what a workgroup keeps in LDS.  Two workgroups per CU (80 KiB each): the first 512 rows (64 KiB) and the 640 hottest records of either kind (measured on the natural-text workload:
-// the first 640 single-entry records take 1.9 % of the steps, the first 640 two-entry ones 1.9 %; a row more takes 0.01 %).  One workgroup per CU: 1 008 rows, 2 048 + 1 024 records.
-struct DfaLds { uint32_t rows, n1, n2; };
-static DfaLds dfa_lds(const DfaView& d, uint32_t per_cu)
-{
-    const bool all = per_cu == 1u;
-    DfaLds l;
-    l.rows = std::min<uint32_t>(d.n_rows, all ? 1008u : 512u);
-    l.n1 = std::min<uint32_t>(d.n_single, all ? 2048u : 640u);
-    l.n2 = std::min<uint32_t>(d.n_states - d.n_rows - d.n_single, all ? 1024u : 640u);
-    return l;
+        state[dev] = s;
+    });
+    return (uint32_t)state[dev];
 }
 // AM_DFA_TUNE (measurements only; no value changes a result): bits 0-3 = the walk (1: 16 bytes of text per request, lanes in step; 2: 64 bytes, lanes in step; 3: 64 bytes, lanes out of step; 0: the default),
 // bits 4-7 = workgroups per CU (0: two, or one with all of the LDS where the device runs 16 wavefronts per CU at a time), bits 8-23 = rows kept in LDS + 1 (0: what fits), bit 24 = no records in LDS, bit 25 = k_dfa_place's table of seen states with 8-byte entries
-static uint32_t dfa_tune() { const long v = cfg::get(cfg::kDfaTune); return v > 0 ? (uint32_t)v : 0u; }
-static uint32_t dfa_workgroups(const DfaView& d, const BatchView& b, int n_cu)
+//
+// What a workgroup keeps in LDS.  Two workgroups per CU (80 KiB each): the first 512 rows (64 KiB) and the 640 hottest records of either kind (measured on the natural-text workload:
+// the first 640 single-entry records take 1.9 % of the steps, the first 640 two-entry ones 1.9 %; a row more takes 0.01 %).  One workgroup per CU: 1 008 rows, 2 048 + 1 024 records.
+DfaLaunch dfa_launch_shape(const DfaView& d, const BatchView& b, int n_cu)
 {
+    const uint32_t tune = cfg::get(cfg::kDfaTune) > 0 ? (uint32_t)cfg::get(cfg::kDfaTune) : 0u;
+    DfaLaunch s; int dev = 0;
+    s.n_cu = n_cu;
+    s.per_cu = (tune >> 4) & 15u;
+    if (!s.per_cu) s.per_cu = hipGetDevice(&dev) == hipSuccess ? dfa_resident_sets(dev) : 2u;
     const uint64_t n_groups = (dfa_units(d, b) + kWave - 1) / kWave;
-    const uint32_t per_cu = dfa_per_cu();
-    return (uint32_t)std::min<uint64_t>((uint64_t)n_cu * per_cu, (n_groups + 15) / 16);
+    s.workgroups = (uint32_t)std::min<uint64_t>((uint64_t)n_cu * s.per_cu, (n_groups + 15) / 16);
+    const bool all = s.per_cu == 1u;
+    s.lds_rows = std::min<uint32_t>(d.n_rows, all ? 1008u : 512u);
+    s.hot_rows = (tune >> 8) & 0xFFFFu ? std::min<uint32_t>(s.lds_rows, ((tune >> 8) & 0xFFFFu) - 1u) : s.lds_rows;
+    s.lds_n1 = (tune >> 24) & 1u ? 0u : std::min<uint32_t>(d.n_single, all ? 2048u : 640u);
+    s.lds_n2 = (tune >> 24) & 1u ? 0u : std::min<uint32_t>(d.n_states - d.n_rows - d.n_single, all ? 1024u : 640u);
+    s.walk = tune & 15u;
+    s.place_wide = (tune >> 25) & 1u;
+    return s;
 }
 // Can this device walk this section at all?  The walk addresses hot table and chain records as 32-bit offsets from the rows and a group's text as 32-bit offsets
 // from its start, and a workgroup wants more than 64 KiB of dynamic LDS (an attribute per instantiation and device, raised here once).  make_plan asks before it
@@ -577,58 +570,50 @@ bool dfa_usable(const DfaView& d)
     return dfa_raise_lds_mode<kModeCount>(dev) && dfa_raise_lds_mode<kModeEmit>(dev) && dfa_raise_lds_mode<kModeAny>(dev) && dfa_raise_lds_mode<kModeTokens>(dev);
 }
 template <int MODE, int TW, int VAR>
-static hipError_t launch_dfa_tw(const DfaView& d, const BatchView& b, const ScanOut& o, int n_cu, hipStream_t st)
+static hipError_t launch_dfa_tw(const DfaView& d, const BatchView& b, const ScanOut& o, const DfaLaunch& s, hipStream_t st)
 {
     const uint64_t n_units = dfa_units(d, b);
     if (n_units == 0) return hipSuccess;
     if (!dfa_usable(d)) return hipErrorInvalidValue;         // (make_plan does not come here with such a section)
-    const DfaLds l = dfa_lds(d, dfa_per_cu());
-    uint32_t hot = l.rows;
-    if ((dfa_tune() >> 8) & 0xFFFFu) hot = std::min<uint32_t>(hot, ((dfa_tune() >> 8) & 0xFFFFu) - 1u);
-    const size_t lds_fixed = ((size_t)l.rows << (kLdsLog2Cols + 2u)) + 128 * 4 + 256;
-    uint32_t n1 = l.n1, n2 = l.n2;
-    if ((dfa_tune() >> 24) & 1u) n1 = n2 = 0u;
-    const size_t lds = lds_fixed + 8u * (n1 + 2u) + 16u * n2;
-    hipLaunchKernelGGL((k_dfa<MODE, TW, VAR>), dim3(dfa_workgroups(d, b, n_cu)), dim3(1024), lds, st, d, b, o, n_units, hot, n1, n2);
+    const size_t lds = ((size_t)s.lds_rows << (kLdsLog2Cols + 2u)) + 128 * 4 + 256 + 8u * (s.lds_n1 + 2u) + 16u * s.lds_n2;
+    hipLaunchKernelGGL((k_dfa<MODE, TW, VAR>), dim3(s.workgroups), dim3(1024), lds, st, d, b, o, n_units, s.hot_rows, s.lds_n1, s.lds_n2);
     return hipGetLastError();
 }
 template <int MODE>
-static hipError_t launch_dfa_t(const DfaView& d, const BatchView& b, const ScanOut& o, int n_cu, hipStream_t st)
+static hipError_t launch_dfa_t(const DfaView& d, const BatchView& b, const ScanOut& o, const DfaLaunch& s, hipStream_t st)
 {
-    switch (dfa_tune() & 15u) {
-    case 1: return launch_dfa_tw<MODE, 16, 0>(d, b, o, n_cu, st);
-    case 3: return launch_dfa_tw<MODE, 64, 1>(d, b, o, n_cu, st);
-    default: return launch_dfa_tw<MODE, 64, 0>(d, b, o, n_cu, st);
+    switch (s.walk) {
+    case 1: return launch_dfa_tw<MODE, 16, 0>(d, b, o, s, st);
+    case 3: return launch_dfa_tw<MODE, 64, 1>(d, b, o, s, st);
+    default: return launch_dfa_tw<MODE, 64, 0>(d, b, o, s, st);
     }
 }
-hipError_t launch_dfa(int mode, const DfaView& d, const BatchView& b, const ScanOut& o, int n_cu, hipStream_t st)
+hipError_t launch_dfa(int mode, const DfaView& d, const BatchView& b, const ScanOut& o, const DfaLaunch& s, hipStream_t st)
 {
-    if (mode == kModeCount) return launch_dfa_t<kModeCount>(d, b, o, n_cu, st);
-    if (mode == kModeEmit) return launch_dfa_t<kModeEmit>(d, b, o, n_cu, st);
-    if (mode == kModeAny) return launch_dfa_t<kModeAny>(d, b, o, n_cu, st);
+    if (mode == kModeCount) return launch_dfa_t<kModeCount>(d, b, o, s, st);
+    if (mode == kModeEmit) return launch_dfa_t<kModeEmit>(d, b, o, s, st);
+    if (mode == kModeAny) return launch_dfa_t<kModeAny>(d, b, o, s, st);
     return hipErrorInvalidValue;
 }
 
-// records in one walk: is the unit small enough for a token's 13-bit fields, and how many wavefronts walk (= superblocks that may end up partly filled)
+// records in one walk: is the unit small enough for a token's 13-bit fields
 bool dfa_tokens_ok(const DfaView& d) { return d.chunk != 0 && d.chunk <= kTokMaxChunk; }
-uint32_t dfa_token_waves(const DfaView& d, const BatchView& b, int n_cu) { return dfa_workgroups(d, b, n_cu) * 16u; }
-// superblocks that hold `records` tokens whatever the split between the wavefronts: a sealed superblock holds at least kDfaSuper - kDfaSuperReserve tokens unless it was
-// sealed for its age -- after 16 groups of its wavefront, so at most one such per 16 groups
+// superblocks that hold `records` tokens whatever the split between the n_waves = 16 x DfaLaunch::workgroups wavefronts that walk (each may leave one partly filled): a sealed
+// superblock holds at least kDfaSuper - kDfaSuperReserve tokens unless it was sealed for its age -- after 16 groups of its wavefront, so at most one such per 16 groups
 uint64_t dfa_token_superblocks(uint64_t records, uint32_t n_waves, uint64_t n_units) { return records / (kDfaSuper - kDfaSuperReserve) + n_waves + 16 + n_units / (kWave * kTokMaxOrd); }
 uint64_t dfa_superblock_bytes() { return (uint64_t)kDfaSuper * sizeof(u32x2_v); }
-hipError_t launch_dfa_tokens(const DfaView& d, const BatchView& b, const ScanOut& o, int n_cu, hipStream_t st) { return launch_dfa_t<kModeTokens>(d, b, o, n_cu, st); }
+hipError_t launch_dfa_tokens(const DfaView& d, const BatchView& b, const ScanOut& o, const DfaLaunch& s, hipStream_t st) { return launch_dfa_t<kModeTokens>(d, b, o, s, st); }
 // o.block_next = [n_blocks fill counts | n_blocks first groups]
-// n_waves = dfa_token_waves() as it was when the walk was launched: a token names its group by an ordinal counted in steps of it
-hipError_t launch_dfa_place(const DfaView& d, const BatchView& b, const ScanOut& o, uint32_t n_super, const uint64_t* unit_offsets, int n_cu, uint32_t n_waves, uint32_t n_ref_states, Record* out, hipStream_t st)
+// s: the shape the walk was launched with: a token names its group by an ordinal counted in steps of its 16 x workgroups wavefronts
+hipError_t launch_dfa_place(const DfaView& d, const BatchView& b, const ScanOut& o, uint32_t n_super, const uint64_t* unit_offsets, const DfaLaunch& s, uint32_t n_ref_states, Record* out, hipStream_t st)
 {
     if (n_super == 0) return hipSuccess;
-    if (n_waves != dfa_token_waves(d, b, n_cu)) return hipErrorInvalidValue;       // (the launch parameters changed between the walk and the placement)
     // a table entry of 4 bytes = the state's bits above the slot index | its reference state + 1, where both fit (645k states, 640k reference states: 7 + 20 bits)
     uint32_t rb = 1; while ((1ull << rb) <= (uint64_t)n_ref_states + 1u) rb++;
     uint32_t sb = 1; while ((1ull << sb) < (uint64_t)d.n_states) sb++;
     const uint32_t tag_bits = sb > kPlaceCacheLog2 + 1u ? sb - (kPlaceCacheLog2 + 1u) : 0u;
-    const uint32_t ref_bits = (rb < 32u && rb + tag_bits <= 32u && !((dfa_tune() >> 25) & 1u)) ? rb : 0u;
-    hipLaunchKernelGGL(k_dfa_place, dim3(std::min<uint32_t>(n_super, (uint32_t)n_cu * 2u)), dim3(1024), 0, st, reinterpret_cast<const u32x2_v*>(o.pool), o.block_next, o.block_next + o.n_blocks, n_super, unit_offsets, b, d.out, d.n_states, d.chunk, n_waves, ref_bits, out);
+    const uint32_t ref_bits = (rb < 32u && rb + tag_bits <= 32u && !s.place_wide) ? rb : 0u;
+    hipLaunchKernelGGL(k_dfa_place, dim3(std::min<uint32_t>(n_super, (uint32_t)s.n_cu * 2u)), dim3(1024), 0, st, reinterpret_cast<const u32x2_v*>(o.pool), o.block_next, o.block_next + o.n_blocks, n_super, unit_offsets, b, d.out, d.n_states, d.chunk, s.workgroups * 16u, ref_bits, out);
     return hipGetLastError();
 }
 

@@ -1197,7 +1197,7 @@ int flatten(const RefArrays& ref, int case_mode, std::vector<uint8_t>& image, st
     {
         const long dfa_cfg = cfg::get(cfg::kDfa);
         // unset: dictionaries (the suffix tables gave heavy depth-4 nodes their children), and every SMALL automaton -- its table costs nothing (32k states x 64 classes = 8 MiB
-        // at most) and whether a batch takes it is the sample walk's decision (am_abi.cpp make_plan): three needles that end at every position of the text (needles a, aa, aaa
+        // at most) and whether a batch takes it is the sample walk's decision (am_run.cpp make_plan): three needles that end at every position of the text (needles a, aa, aaa
         // over a...a: 43 GiB/s on the filter, output-bound) are the table walk's case as much as a dictionary over its language
         const bool want = dfa_cfg == cfg::kUnset ? (h.sf_t4_children > 0 || S <= kDfaSmallStates) : dfa_cfg != 0;
         DfaOut o;

@@ -1,6 +1,6 @@
-// am_host.h -- what the host-side translation units of libam share (am_abi.cpp: runtime, automata, batches, scans, results; am_replacer.cpp: the
-// Replacer; am_contains_all.cpp: containsAll and the fold checksum): error handling, the per-device runtime, device buffers, the handle structs of
-// include/am.h and the few scan entry points the Replacer drives.  Internal: nothing here is part of the C ABI.
+// am_host.h -- what the host-side translation units of libam share (am_abi.cpp: runtime and thread state, automata, batches, one-shot entry points, results;
+// am_run.cpp: routes and scans; am_replacer.cpp: the Replacer; am_contains_all.cpp: containsAll and the fold checksum): error handling, the per-device runtime,
+// device buffers, the handle structs of include/am.h and the few scan entry points the Replacer drives.  Internal: nothing here is part of the C ABI.
 #pragma once
 #include "../../include/am.h"
 #include "../../include/am_debug.h"
@@ -155,7 +155,7 @@ struct am_batch {
     am::host::DevBuf combo;               // ... or ONE buffer [offsets | text] for small batches that went up with a single copy
     am::host::DevBuf hidx, unit_counts, unit_offsets, scan_tmp, small, hay_counts, flags, unit_first, pool, block_next;
     am::host::DevBuf sparse, dense_counts, dense_offsets, dense_out;      // automata with the empty needle (dense pass)
-    // the route a dictionary's image took on this batch the last time it was asked (am_abi.cpp make_plan: a sample walk decides once per batch and image)
+    // the route a dictionary's image took on this batch the last time it was asked (am_run.cpp make_plan: a sample walk decides once per batch and image)
     uint64_t route_image = 0; bool route_dfa = false;        // (the image's generation; 0: not asked)
     uint32_t route_ends_per_kib = 0;                         // what the sample walk counted: sizes the token pool's first guess
 };
@@ -172,19 +172,31 @@ struct am_matches {
 namespace am {
 namespace host {
 
-// am_abi.cpp: what the Replacer and containsAll drive
+// Results of a call, device -> caller: small ones travel through the calling thread's pinned result buffer (an asynchronous copy into pageable
+// memory is a blocking, staged copy inside the runtime), the caller's buffers are filled after the call's ONE stream synchronisation.  (Defined next
+// to the thread state in am_abi.cpp.)
+struct ResultCopies {
+    struct Item { void* dst; size_t off, n; };
+    Item items[4]; int n_items = 0; size_t used = 0;
+    int add(void* dst, const void* d_src, size_t n, hipStream_t st);
+    int finish(hipStream_t st);
+};
+
+// am_abi.cpp: what the scans, the Replacer and containsAll drive
 int prepare(const am_automaton* ca, int case_mode, const Flavor** out);                      // the automaton's image for a case mode, on its device
 int finish_batch(am_batch* b);                                                               // workspaces of a batch whose text and offsets are in place
-// sorted records of a batch: sink_final(n, &ptr) names the destination once the count is known
+// am_run.cpp, the scans.  am_run_batch (allow_small: the one-document path may take the call); am_run_range and the segmented am_run ask for the general path
+int run_batch_impl(const am_automaton* a, int case_mode, const am_batch* cb, am_matches** out, bool allow_small);
 // Searcher.containsAll without records (k_sf's ids mode): every reported needle id into the haystack's row of d_bits (n_hay x words, cleared here),
 // flags_out[h] = 1 iff all n_needles ids were seen; *taken = false when the automaton does not go this way (general kernel forced, the empty needle's
 // dense pass, nothing to scan) and the caller folds the records instead.
 int scan_needle_ids(const am_automaton* a, int case_mode, am_batch* b, const uint64_t* d_vals_off, const uint32_t* d_vals, uint32_t n_needles,
                     uint32_t* d_bits, uint32_t words, uint32_t* d_missing, uint8_t* flags_out, bool* taken);
+// sorted records of a batch: sink_final(n, &ptr) names the destination once the count is known
 int run_records(const am_automaton* a, int case_mode, am_batch* b, const std::function<int(uint64_t, Record**)>& sink_final, uint64_t* n_out, bool have_lock = false);
 // the same without a host round trip (suffix-filter route, worst-case pool): the count stays on the device
 int run_records_async(const am_automaton* a, int case_mode, am_batch* b, Record* d_out, const uint64_t** n_dev, hipStream_t st);
-// what am_count_by_needle* (am_contains_all.cpp) shares with the run entry points: the slices of a call into a batch (oneshot: small uploads stay enqueued on the calling
+// am_abi.cpp: what am_count_by_needle* (am_contains_all.cpp) shares with the run entry points: the slices of a call into a batch (oneshot: small uploads stay enqueued on the calling
 // thread's stream), the calling thread's one-shot batch on a device, and the device arrays of freed results (kept for the next records: taken from there or allocated, given back)
 int upload_batch(const am_slice* hay, size_t n_hay, am_batch* b, bool oneshot);
 am_batch* oneshot_batch(int dev);

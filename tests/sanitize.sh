@@ -2,7 +2,7 @@
 # Sanitiser pass over everything under the C ABI that runs on the host (SURVEY 5 "race detection / sanitizers").
 #   1. AddressSanitizer + UndefinedBehaviorSanitizer builds (clang, shared runtime) of: the oracle (oracle/am_oracle.c), the flattener + the host interpreter of the
 #      image (libam_imgcheck.so: am_flatten.cpp + the walk code of am_image.h that the kernels share), the host mirror (libam_host.so) and every host translation unit
-#      of libam.so (am_abi.cpp, am_replacer.cpp, am_contains_all.cpp, am_flatten.cpp, am_multi.cpp) -- into build/sanitize/, apart from the product's libraries;
+#      of libam.so (am_abi.cpp, am_run.cpp, am_replacer.cpp, am_contains_all.cpp, am_flatten.cpp, am_multi.cpp) -- into build/sanitize/, apart from the product's libraries;
 #   2. the whole CPU suite (`-m "not gpu"`) on them, python getting the runtime through LD_PRELOAD; any report aborts the run.
 # The kernels are not instrumented (GPU sanitizers are not available on this pool); their index arithmetic is what the -DAM_BOUNDS_CHECK build of the
 # kernels checks on the GPU box (tools/bounds_check.sh).

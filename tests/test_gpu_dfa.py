@@ -78,7 +78,7 @@ def test_fragment_pool_on_the_table_walk(dfa_everywhere, seed):
 
 @pytest.mark.parametrize("tune", [3, 1, 0x1000000, 0x103, 0x10, 0x13])
 def test_the_walks_variants_report_the_same_records(dfa_everywhere, tune):
-    """AM_DFA_TUNE (am_dfa.hip dfa_tune): lanes out of step inside a 16-byte block (3), 16 bytes of text per request (1), no records in LDS (bit 24), no rows in LDS
+    """AM_DFA_TUNE (am_dfa.hip dfa_launch_shape): lanes out of step inside a 16-byte block (3), 16 bytes of text per request (1), no records in LDS (bit 24), no rows in LDS
     with lanes out of step (0x103), one workgroup per CU with all of its LDS (0x10, 0x13: what a device that runs 16 wavefronts per CU at a time gets) -- measurement switches, each the same walk by other loads: records, counts and flags against the oracle, image version 17's
     records (one and two entries, leaning on a row state) on every path."""
     am.debug_set("AM_DFA_TUNE", tune)
@@ -227,7 +227,7 @@ def test_dictionary_takes_the_table_walk_by_itself(dfa_from_one_mib):
 
 
 def test_large_batches_choose_their_route_by_a_sample_walk():
-    """From 64 MiB on a dictionary's batch is asked which route it wants (am_abi.cpp make_plan: 4 096 lanes walk 128 bytes each): natural-language text takes the
+    """From 64 MiB on a dictionary's batch is asked which route it wants (am_run.cpp make_plan: 4 096 lanes walk 128 bytes each): natural-language text takes the
     table walk, the same dictionary over text in which its words are rare takes the suffix filter; the records are the same either way."""
     import torch
     w = synth.WORKLOADS["natural_100k_10GiB"]

@@ -1,4 +1,4 @@
-"""Round 6: k_dfa on the natural-text workload under the launch switches of AM_DFA_TUNE (am_dfa.hip dfa_tune): bytes of text a lane asks for at a time,
+"""Round 6: k_dfa on the natural-text workload under the launch switches of AM_DFA_TUNE (am_dfa.hip dfa_launch_shape): bytes of text a lane asks for at a time,
 workgroups per CU, rows kept in LDS.  Per variant: kernel times from HIP events inside libam (am_profile_*), counting and emitting; totals must agree.
 usage: dfa_tune.py [GiB] [variant ...]     a variant is name=value (value = the integer AM_DFA_TUNE takes)"""
 import ctypes as C, os, sys, time
