@@ -4,6 +4,7 @@ The classes mirror the reference modules (same names and argument meaning):
   Automaton  ~ Data.Text.AhoCorasick.Automaton  (build, run_with_case / run_text / run_lower, count_matches)
   Searcher   ~ Data.Text.AhoCorasick.Searcher   (build, contains_any, contains_all, set_case_sensitivity)
   Replacer   ~ Data.Text.AhoCorasick.Replacer   (build, run, run_with_limit)
+  Splitter   ~ Data.Text.AhoCorasick.Splitter   (build, split, split_ignore_case; split_batch_device / fragments_batch / lines_batch: the fold on the device)
 Every match position comes from the HIP kernels; there is no Python or CPU matching path, and
 importing this module fails loudly if the native libraries are missing and cannot be built.
 """
@@ -32,6 +33,7 @@ class Slice(C.Structure):          # am_slice
 
 
 MATCH_DTYPE = np.dtype([("end_pos", np.uint64), ("haystack", np.uint32), ("state", np.uint32)])   # am_match
+FRAGMENT_DTYPE = np.dtype([("start", np.uint64), ("len", np.uint64)])   # am_fragment
 PRIO_MATCH_DTYPE = np.dtype([("start", np.uint64), ("len", np.uint64), ("haystack", np.uint32), ("payload", np.uint32)])   # am_prio_match
 
 _u8p, _u32p, _u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
@@ -68,6 +70,18 @@ ABI = {
     "am_count_by_needle_batch": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "am_count_by_needle": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp]),
     "am_matches_count_by_needle": (C.c_int, [_vp, _vp, _vp]),
+    "am_splitter_create": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
+    "am_splitter_destroy": (None, [_vp]),
+    "am_split_batch": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_vp)]),
+    "am_split": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, C.POINTER(_vp)]),
+    "am_fragments_size": (C.c_uint64, [_vp]),
+    "am_fragments_haystacks": (C.c_uint64, [_vp]),
+    "am_fragments_offsets": (_vp, [_vp]),
+    "am_fragments_data": (_vp, [_vp]),
+    "am_fragments_device_offsets": (_vp, [_vp]),
+    "am_fragments_device_data": (_vp, [_vp]),
+    "am_fragments_free": (None, [_vp]),
+    "am_batch_from_fragments": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "am_needle_ids_create": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(_vp)]),
     "am_needle_ids_destroy": (None, [_vp]),
     "am_contains_all": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp]),
@@ -159,6 +173,10 @@ _HOST = {
     "amh_splitter_build": (C.c_int, [C.c_char_p, _sz, C.POINTER(_vp)]),
     "amh_splitter_free": (None, [_vp]),
     "amh_splitter_split_batch": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, C.POINTER(_vp), C.POINTER(_vp), _u64p, _vp]),
+    "amh_splitter_device": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "amh_splitter_automaton": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "amh_splitter_split_batch_device": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, C.POINTER(_vp), C.POINTER(_vp), _u64p, _vp]),
+    "amh_splitter_fragments_batch": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
     "amh_free_u64": (None, [_vp]),
     "amh_skip_code_points_backwards": (C.c_int64, [C.c_char_p, _sz, _sz, _sz]),
     "amh_lower_utf8": (_sz, [C.c_char_p, _sz, _vp, _sz]),
@@ -177,6 +195,7 @@ DEBUG_ABI = {
     "am_debug_set_general_kernel": (C.c_int, [_vp, C.c_uint32]),
     "am_debug_rp_lds_haystacks": (C.c_uint32, []),
     "am_debug_hist_adds": (C.c_int, [_vp]),
+    "am_debug_split_rounds": (C.c_uint32, []),
 }
 
 _libam = None
@@ -522,6 +541,17 @@ def matches_to_numpy(m):
     return np.frombuffer((C.c_char * (n * MATCH_DTYPE.itemsize)).from_address(p), dtype=MATCH_DTYPE).copy()
 
 
+def fragments_to_numpy(f):
+    """(offsets np.uint64[n_hay + 1], fragments FRAGMENT_DTYPE[n]) of an am_fragments* result (host copies)."""
+    n, n_hay = int(libam().am_fragments_size(f)), int(libam().am_fragments_haystacks(f))
+    po, pd = libam().am_fragments_offsets(f), libam().am_fragments_data(f)
+    if not po or not pd:
+        raise AmError(AM_ERR_HIP, (libam().am_last_error() or b"").decode())
+    offs = np.frombuffer((C.c_char * ((n_hay + 1) * 8)).from_address(po), dtype=np.uint64).copy()
+    frags = np.frombuffer((C.c_char * (n * FRAGMENT_DTYPE.itemsize)).from_address(pd), dtype=FRAGMENT_DTYPE).copy() if n else np.zeros(0, FRAGMENT_DTYPE)
+    return offs, frags
+
+
 def matches_of_haystack(m, haystack):
     """The records of ONE haystack of a (possibly huge, device-resident) result as a numpy array: binary search + one small copy (am_matches_haystack_range / am_matches_copy)."""
     first, count = C.c_uint64(0), C.c_uint64(0)
@@ -684,11 +714,16 @@ class Splitter:
             self._h = None
 
     def split_batch(self, texts, ignore_case=False):
+        """The fragments of every text with the fold on the host (host/splitter.hpp splitBatch)."""
+        return self._blob_lists(libhost().amh_splitter_split_batch, texts, ignore_case)
+
+    def _blob_lists(self, fn, texts, ignore_case):
+        """Lists of fragments out of one of the facade's blob + offsets + per-haystack-count calls."""
         s = _Slices(texts)
         blob, offs = _vp(), _vp()
         nf = C.c_uint64(0)
         per = np.zeros(max(s.n, 1), np.uint32)
-        _hcheck(libhost().amh_splitter_split_batch(self._h, 1 if ignore_case else 0, s.arr, s.n, C.byref(blob), C.byref(offs), C.byref(nf), per.ctypes.data))
+        _hcheck(fn(self._h, 1 if ignore_case else 0, s.arr, s.n, C.byref(blob), C.byref(offs), C.byref(nf), per.ctypes.data))
         try:
             o = np.ctypeslib.as_array(C.cast(offs, _u64p), shape=(nf.value + 1,)).copy()
             raw = C.string_at(blob, int(o[-1]))
@@ -701,6 +736,69 @@ class Splitter:
             k += int(per[i])
         return out
 
+    def split_batch_device(self, texts, ignore_case=False):
+        """The same lists of fragments with the fold on the device (am_split: stepAccum in HBM, csrc/am_split.hip); what crosses the wire is (start, length) per fragment."""
+        return self._blob_lists(libhost().amh_splitter_split_batch_device, texts, ignore_case)
+
+    def fragments_texts(self, texts, ignore_case=False):
+        """TEST AID: (offsets[n + 1], fragments) of host texts through the C++ host mirror's splitBatchFragments (am_split)."""
+        s = _Slices(texts)
+        offs, frags = _vp(), _vp()
+        nf = C.c_uint64(0)
+        _hcheck(libhost().amh_splitter_fragments_batch(self._h, 1 if ignore_case else 0, s.arr, s.n, C.byref(offs), C.byref(frags), C.byref(nf)))
+        try:
+            o = np.ctypeslib.as_array(C.cast(offs, _u64p), shape=(s.n + 1,)).copy()
+            fr = np.ctypeslib.as_array(C.cast(frags, _u64p), shape=(max(int(nf.value), 1) * 2,)).copy()[:int(nf.value) * 2].view(FRAGMENT_DTYPE)
+        finally:
+            libhost().amh_free_u64(offs)
+            libhost().amh_free_u64(frags)
+        return o, fr
+
+    @property
+    def device(self):
+        """TEST AID (like Replacer.device): the am_splitter* for calls on the raw ABI."""
+        h = _vp()
+        _hcheck(libhost().amh_splitter_device(self._h, C.byref(h)))
+        return h.value
+
+    def set_kernel(self, k):
+        """TEST AID: the scan route of the separator's automaton (am_automaton_set_kernel), so that the tests reach every route."""
+        h = _vp()
+        _hcheck(libhost().amh_splitter_automaton(self._h, C.byref(h)))
+        check(libam().am_automaton_set_kernel(h, k))
+
+    def split_fragments(self, batch, ignore_case=False):
+        """TEST / MEASUREMENT AID: am_split_batch on an am_batch* handle, the raw am_fragments* result (free it with libam().am_fragments_free); fragments_batch and
+        lines_batch are the front end."""
+        f = _vp()
+        check(libam().am_split_batch(self.device, IGNORE_CASE if ignore_case else CASE_SENSITIVE, batch, C.byref(f)))
+        return f
+
+    def fragments_batch(self, batch, ignore_case=False):
+        """am_split_batch on a device-resident batch (an am_batch* handle): (offsets np.uint64[n_hay + 1], fragments FRAGMENT_DTYPE[offsets[-1]]); the fragments of
+        haystack i are fragments[offsets[i]:offsets[i + 1]], start and len in bytes relative to the haystack."""
+        f = self.split_fragments(batch, ignore_case)
+        try:
+            return fragments_to_numpy(f)
+        finally:
+            libam().am_fragments_free(f)
+
+    def lines_batch(self, batch, ignore_case=False):
+        """document -> lines without leaving HBM: splits the batch and gathers the fragments into a new batch (am_batch_from_fragments), one haystack per fragment.
+        Returns (am_batch* handle of the new batch -- destroy it with libam().am_batch_destroy --, offsets np.uint64[n_hay + 1] that map a line back to its document)."""
+        f = self.split_fragments(batch, ignore_case)
+        try:
+            nb = _vp()
+            check(libam().am_batch_from_fragments(batch, f, C.byref(nb)))
+            n_hay = int(libam().am_fragments_haystacks(f))
+            p = libam().am_fragments_offsets(f)
+            if not p:
+                libam().am_batch_destroy(nb)
+                raise AmError(AM_ERR_HIP, (libam().am_last_error() or b"").decode())
+            return nb, np.frombuffer((C.c_char * ((n_hay + 1) * 8)).from_address(p), dtype=np.uint64).copy()
+        finally:
+            libam().am_fragments_free(f)
+
     def split(self, text):
         return self.split_batch([text], False)[0]
 
@@ -710,7 +808,7 @@ class Splitter:
 
 DEBUG_SWITCHES = ("AM_SF_TRACE", "AM_SF_POOL_BLOCKS", "AM_SF_NO_CHILDREN", "AM_DFA", "AM_DFA_CHUNK", "AM_DFA_RARE_PERMILLE", "AM_DFA_MIN_KIB", "AM_DFA_TUNE", "AM_DFA_NO_CHAINS", "AM_FLATTEN_TRACE", "AM_FLATTEN_SERIAL", "AM_NO_IDS_SCAN",
                   "AM_RP_FULL_SCANS", "AM_RP_PIECES", "AM_RP_PARALLEL_FOLD", "AM_RP_GROUPS", "AM_RP_NO_FUSE", "AM_RP_NO_SPIN",
-                  "AM_RP_MAT_MAIN", "AM_RP_NO_RANGE_REUSE", "AM_RP_TRACE", "AM_RP_LDS", "AM_RP_LOOP", "AM_RUN_SEGMENTS", "AM_HIST_RECORDS_MIB", "AM_HIST_TRACE", "AM_HIST_FLUSH_TILES")
+                  "AM_RP_MAT_MAIN", "AM_RP_NO_RANGE_REUSE", "AM_RP_TRACE", "AM_RP_LDS", "AM_RP_LOOP", "AM_RUN_SEGMENTS", "AM_HIST_RECORDS_MIB", "AM_HIST_TRACE", "AM_HIST_FLUSH_TILES", "AM_SPLIT_CHAIN_LIMIT")
 
 
 def debug_set(name, value):

@@ -164,19 +164,6 @@ uint64_t hist_budget() { const long v = cfg::get(cfg::kHistRecordsMiB); return v
 
 std::atomic<uint64_t> g_hist_trace[3];                   // AM_HIST_TRACE: sums of the launches' trace words (am_debug_hist_adds)
 
-// a device array for records out of the cache of freed results; goes back there
-struct RecordArray {
-    int dev; void* p = nullptr; size_t cap = 0;
-    explicit RecordArray(int d) : dev(d) {}
-    int ensure(size_t need)
-    {
-        if (need <= cap) return AM_OK;
-        record_array_put(dev, p, cap); p = nullptr; cap = 0;
-        return record_array_get(dev, need, &p, &cap);
-    }
-    ~RecordArray() { record_array_put(dev, p, cap); }
-};
-
 int hist_launch(const am_needle_ids* ids, const Record* recs, uint64_t n_rec, uint64_t* d_counts, uint64_t* d_trace, int dev, hipStream_t st)
 {
     Prof pr("needle_hist", st);

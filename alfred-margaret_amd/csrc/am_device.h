@@ -151,6 +151,26 @@ hipError_t launch_idset_all(const uint32_t* bits, uint32_t words, uint32_t n_nee
 // [1] adds that went to HBM one by one (slot conflicts), [2] adds of the flushes
 hipError_t launch_needle_hist(const Record* recs, uint64_t n_rec, const uint64_t* vals_off, const uint32_t* vals, uint32_t n_needles, uint64_t n_states,
                               uint64_t n_values, uint64_t* counts, uint64_t* trace, uint32_t flush_tiles /* 0: the kernel's own interval */, int n_cu, hipStream_t st);
+// Splitter's fold over the sorted records of a one-needle automaton, and the gather of the fragments into a batch (am_split.hip)
+struct Fragment { uint64_t start, len; };                   // = am_fragment in include/am.h: code units, relative to the haystack
+struct SplitIn { const Record* recs; uint64_t n_rec; const uint8_t* text; const uint64_t* offsets; uint64_t total; uint32_t n_hay, sep_bytes, sep_cps; };
+// start[i] = sepStart of record i (Splitter.hs:105-107 / :117-121), head[i] = first of its haystack or starting at or after the end of record i - 1, kept = head;
+// kept has n_rec + 1 entries (the last one 0: the scan's trailing element)
+hipError_t launch_split_start(bool ic, const SplitIn& in, uint64_t* start, uint8_t* head, uint32_t* kept, hipStream_t st);
+// greedy selection inside the chains between heads: the head's lane looks at up to `limit` records; *long_chains (cleared by the caller) != 0 when a chain needed more
+hipError_t launch_split_walk(const Record* recs, uint64_t n_rec, const uint64_t* start, const uint8_t* head, uint32_t* kept, uint32_t limit, uint32_t* long_chains, hipStream_t st);
+// ... finished by pointer doubling: jump[i] = next[i] (i itself: none), then rounds of { kept records mark jump_in[i]; jump_out = jump_in o jump_in } until a round leaves
+// *marked (cleared by the caller before each) at 0
+hipError_t launch_split_next(const Record* recs, uint64_t n_rec, const uint64_t* start, const uint8_t* head, uint64_t* jump, hipStream_t st);
+hipError_t launch_split_double(const uint64_t* jump_in, uint64_t* jump_out, uint64_t n_rec, uint32_t* kept, uint32_t* marked, hipStream_t st);
+// kidx = exclusive sum of kept (n_rec + 1), rec_first = first record of every haystack (n_hay + 1): frag_off (n_hay + 1) and the n_frag = kidx[n_rec] + n_hay fragments
+hipError_t launch_split_emit(const SplitIn& in, const uint64_t* start, const uint32_t* kept, const uint64_t* kidx, const uint64_t* rec_first, uint64_t* frag_off,
+                             Fragment* frags, uint64_t n_frag, hipStream_t st);
+// am_batch_from_fragments: lens (n_frag + 1, the last one 0) and the source position of every fragment; then, with dst_off = exclusive sum of lens, the bytes
+hipError_t launch_split_sources(const Fragment* frags, uint64_t n_frag, const uint64_t* frag_off, const uint64_t* src_offsets, uint64_t n_hay, uint64_t src_total,
+                                uint64_t* lens, uint64_t* src_at, hipStream_t st);
+hipError_t launch_split_gather(const uint8_t* src, uint64_t src_total, const uint64_t* src_at, const uint64_t* dst_off, uint64_t n_frag, uint64_t total, uint8_t* dst,
+                               int n_cu, hipStream_t st);
 // incremental re-scan between Replacer passes (am_replace.hip)
 struct RpWin { uint64_t src_abs; uint64_t ws; uint32_t len; uint32_t own_lo; };   // window: bytes src_abs.. of the next text; ws = its start inside the haystack; records with end > own_lo are its own
 hipError_t launch_rp_win_count(const RpHay* hs, uint32_t n_act, uint32_t* nwin, hipStream_t st);

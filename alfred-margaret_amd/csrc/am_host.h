@@ -1,5 +1,5 @@
 // am_host.h -- what the host-side translation units of libam share (am_abi.cpp: runtime and thread state, automata, batches, one-shot entry points, results;
-// am_run.cpp: routes and scans; am_replacer.cpp: the Replacer; am_contains_all.cpp: containsAll and the fold checksum): error handling, the per-device runtime,
+// am_run.cpp: routes and scans; am_replacer.cpp: the Replacer; am_contains_all.cpp: containsAll and the fold checksum; am_splitter.cpp: the Splitter): error handling, the per-device runtime,
 // device buffers, the handle structs of include/am.h and the few scan entry points the Replacer drives.  Internal: nothing here is part of the C ABI.
 #pragma once
 #include "../../include/am.h"
@@ -203,6 +203,18 @@ am_batch* oneshot_batch(int dev);
 void oneshot_batch_trim(int dev);
 int record_array_get(int dev, size_t need, void** p, size_t* cap);
 void record_array_put(int dev, void* p, size_t cap);
+// a device array for records out of the cache of freed results; goes back there
+struct RecordArray {
+    int dev; void* p = nullptr; size_t cap = 0;
+    explicit RecordArray(int d) : dev(d) {}
+    int ensure(size_t need)
+    {
+        if (need <= cap) return AM_OK;
+        record_array_put(dev, p, cap); p = nullptr; cap = 0;
+        return record_array_get(dev, need, &p, &cap);
+    }
+    ~RecordArray() { record_array_put(dev, p, cap); }
+};
 inline size_t padded_text(uint64_t total) { return (size_t)((total + 15) & ~15ull) + 16; }
 
 }  // namespace host

@@ -1,0 +1,262 @@
+// am_splitter.cpp -- Data.Text.AhoCorasick.Splitter on the device (reference: src/Data/Text/AhoCorasick/Splitter.hs): one scan of the batch with the one-needle
+// automaton, then stepAccum / finalizeAccum (:141-170) over the sorted records in HBM (am_split.hip).  What comes back is a list of (start, length) per haystack that
+// stays in HBM until asked for, and am_batch_from_fragments turns it into a batch of its own: document -> lines -> any *_batch entry point, without the host.
+#include "am_host.h"
+
+using namespace am;
+using namespace am::dev;
+using namespace am::host;
+
+struct am_splitter {
+    const am_automaton* a = nullptr;
+    uint32_t sep_bytes = 0, sep_cps = 0;
+};
+
+struct am_fragments {
+    int dev = 0;
+    uint64_t n_frag = 0, n_hay = 0, src_total = 0;        // src_total: bytes of the batch they were cut from (am_batch_from_fragments checks it)
+    DevBuf data, offsets;                                 // Fragment[n_frag], uint64[n_hay + 1] in HBM (none when n_hay == 0)
+    std::vector<am_fragment> h_data; std::vector<uint64_t> h_offsets;
+    bool data_fetched = false, offsets_fetched = false;
+};
+
+static_assert(sizeof(am_fragment) == sizeof(Fragment), "am_fragment and the kernels' Fragment are one layout");
+
+namespace {
+
+constexpr uint32_t kSplitChainLimit = 32;                 // records the lane of a chain's head looks at before the chain goes to the doubling rounds
+std::atomic<uint32_t> g_split_rounds{0};                  // doubling rounds of the last am_split_batch (am_debug_split_rounds)
+
+struct Bufs {
+    DevBuf start, head, kept, kidx, scan_tmp, rec_first, flag, jump0, jump1;
+    ~Bufs() { for (DevBuf* d : {&start, &head, &kept, &kidx, &scan_tmp, &rec_first, &flag, &jump0, &jump1}) d->release(); }
+};
+
+int read_u64(const void* d_src, uint64_t* out, hipStream_t st)
+{
+    HIP_TRY(hipMemcpyAsync(out, d_src, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return AM_OK;
+}
+
+int check_case(int case_mode)
+{
+    return case_mode == AM_CASE_SENSITIVE || case_mode == AM_IGNORE_CASE ? AM_OK : fail(AM_ERR_INVALID, "case_mode must be AM_CASE_SENSITIVE or AM_IGNORE_CASE");
+}
+
+// no haystacks: zero fragments, offsets = [0], nothing in HBM
+int no_fragments(int dev, am_fragments** out)
+{
+    am_fragments* f = new am_fragments();
+    f->dev = dev;
+    f->h_offsets.assign(1, 0); f->h_data.assign(1, am_fragment{0, 0});
+    f->offsets_fetched = f->data_fetched = true;
+    *out = f;
+    return AM_OK;
+}
+
+}  // namespace
+
+extern "C" uint32_t am_debug_split_rounds(void) { return g_split_rounds.load(std::memory_order_relaxed); }
+
+extern "C" int am_splitter_create(const am_automaton* a, uint32_t sep_len_bytes, uint32_t sep_len_code_points, am_splitter** out)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    if (!a) return fail(AM_ERR_INVALID, "null automaton");
+    if (sep_len_bytes == 0 || sep_len_code_points == 0) return fail(AM_ERR_INVALID, "the empty separator is refused");
+    if (sep_len_code_points > sep_len_bytes) return fail(AM_ERR_INVALID, "sep_len_code_points exceeds sep_len_bytes");
+    // Splitter.hs:66 `Aho.build [(sep, ())]`: exactly one state reports, and it reports one value
+    if (!a->has_ref) return fail(AM_ERR_UNSUPPORTED, "am_splitter_create: a handle made from an image does not keep values_len");
+    size_t reporting = 0, values = 0;
+    for (uint32_t v : a->values_len) if (v) { reporting++; values += v; }
+    if (reporting != 1 || values != 1) return fail(AM_ERR_INVALID, "am_splitter_create: not a one-needle automaton");
+    am_splitter* s = new am_splitter();
+    s->a = a; s->sep_bytes = sep_len_bytes; s->sep_cps = sep_len_code_points;
+    *out = s;
+    return AM_OK;
+}
+
+extern "C" void am_splitter_destroy(am_splitter* s) { delete s; }
+
+extern "C" int am_split_batch(const am_splitter* s, int case_mode, const am_batch* cb, am_fragments** out)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    if (!s || !cb) return fail(AM_ERR_INVALID, "null splitter or batch");
+    AM_TRY(check_case(case_mode));
+    if (s->a->dev != cb->dev) return fail(AM_ERR_INVALID, "splitter and batch live on different devices");
+    AM_TRY(ensure_runtime());
+    am_batch* b = const_cast<am_batch*>(cb);
+    std::unique_ptr<am_fragments, void (*)(am_fragments*)> f(new am_fragments(), am_fragments_free);
+    f->dev = b->dev; f->n_hay = b->n_hay; f->src_total = b->total;
+    g_split_rounds.store(0, std::memory_order_relaxed);
+    if (b->n_hay == 0) return no_fragments(b->dev, out);
+    ON_DEVICE(b->dev);
+    hipStream_t st; AM_TRY(get_stream(b->dev, &st));
+    RecordArray ra(b->dev);
+    uint64_t n_rec = 0;
+    if (b->total != 0) {
+        auto sink = [&](uint64_t n, Record** ptr) -> int { AM_TRY(ra.ensure(n * sizeof(Record))); *ptr = (Record*)ra.p; return AM_OK; };
+        AM_TRY(run_records(s->a, case_mode, b, sink, &n_rec));
+    }
+    const SplitIn in{(const Record*)ra.p, n_rec, (const uint8_t*)b->d_text, b->d_offsets, b->total, b->n_hay, s->sep_bytes, s->sep_cps};
+    Bufs w;
+    AM_TRY(w.start.ensure((n_rec + 1) * 8));
+    AM_TRY(w.head.ensure(n_rec + 1));
+    AM_TRY(w.kept.ensure((n_rec + 1) * 4));
+    AM_TRY(w.kidx.ensure((n_rec + 1) * 8));
+    AM_TRY(w.rec_first.ensure(((uint64_t)b->n_hay + 1) * 8));
+    AM_TRY(w.flag.ensure(64));
+    size_t tmp_bytes = 0;
+    HIP_TRY(scan_temp_bytes(n_rec + 1, &tmp_bytes));
+    AM_TRY(w.scan_tmp.ensure(tmp_bytes));
+    uint32_t* const flag = (uint32_t*)w.flag.p;
+    uint32_t* const kept = (uint32_t*)w.kept.p;
+    HIP_TRY(hipMemsetAsync(flag, 0, 64, st));
+    { Prof pr("split_start", st);
+      HIP_TRY(launch_split_start(case_mode == AM_IGNORE_CASE, in, (uint64_t*)w.start.p, (uint8_t*)w.head.p, kept, st)); }
+    HIP_TRY(launch_rp_ranges(in.recs, n_rec, (uint64_t*)w.rec_first.p, RpRoute{nullptr, nullptr, nullptr, nullptr, nullptr}, b->n_hay, st));
+    const long lim = cfg::get(cfg::kSplitChainLimit);
+    { Prof pr("split_walk", st);
+      HIP_TRY(launch_split_walk(in.recs, n_rec, (const uint64_t*)w.start.p, (const uint8_t*)w.head.p, kept, lim > 0 ? (uint32_t)std::min<long>(lim, 1L << 30) : kSplitChainLimit, flag, st)); }
+    uint32_t long_chains = 0;
+    if (n_rec > 1) {
+        HIP_TRY(hipMemcpyAsync(&long_chains, flag, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (long_chains) {
+        AM_TRY(w.jump0.ensure(n_rec * 8));
+        AM_TRY(w.jump1.ensure(n_rec * 8));
+        uint64_t* jump[2] = {(uint64_t*)w.jump0.p, (uint64_t*)w.jump1.p};
+        { Prof pr("split_next", st);
+          HIP_TRY(launch_split_next(in.recs, n_rec, (const uint64_t*)w.start.p, (const uint8_t*)w.head.p, jump[0], st)); }
+        uint32_t rounds = 0;
+        for (uint32_t marked = 1; marked != 0 && rounds < 64; rounds++) {      // (a path of k records is marked after log2(k) + 1 rounds: 64 is no limit for 64-bit indices)
+            HIP_TRY(hipMemsetAsync(flag + 1, 0, 4, st));
+            { Prof pr("split_double", st);
+              HIP_TRY(launch_split_double(jump[rounds & 1], jump[(rounds & 1) ^ 1], n_rec, kept, flag + 1, st)); }
+            HIP_TRY(hipMemcpyAsync(&marked, flag + 1, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        g_split_rounds.store(rounds, std::memory_order_relaxed);
+    }
+    HIP_TRY(launch_scan(w.scan_tmp.p, w.scan_tmp.cap, kept, (uint64_t*)w.kidx.p, n_rec + 1, st));
+    uint64_t n_kept = 0;
+    AM_TRY(read_u64((const uint64_t*)w.kidx.p + n_rec, &n_kept, st));
+    f->n_frag = n_kept + b->n_hay;
+    AM_TRY(f->data.ensure(f->n_frag * sizeof(Fragment)));
+    AM_TRY(f->offsets.ensure(((uint64_t)b->n_hay + 1) * 8));
+    { Prof pr("split_emit", st);
+      HIP_TRY(launch_split_emit(in, (const uint64_t*)w.start.p, kept, (const uint64_t*)w.kidx.p, (const uint64_t*)w.rec_first.p, (uint64_t*)f->offsets.p,
+                                (Fragment*)f->data.p, f->n_frag, st)); }
+    HIP_TRY(hipStreamSynchronize(st));                      // (the record array goes back to the cache, the workspaces are freed)
+    *out = f.release();
+    return AM_OK;
+}
+
+extern "C" int am_split(const am_splitter* s, int case_mode, const am_slice* hay, size_t n_hay, am_fragments** out)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    if (!s) return fail(AM_ERR_INVALID, "null splitter");
+    if (n_hay && !hay) return fail(AM_ERR_INVALID, "hay is null");
+    if (n_hay >= 0xFFFFFFFFull) return fail(AM_ERR_INVALID, "too many haystacks");
+    AM_TRY(check_case(case_mode));
+    for (size_t i = 0; i < n_hay; i++) if (hay[i].len && !hay[i].ptr) return fail(AM_ERR_INVALID, "slice with null ptr");
+    AM_TRY(ensure_runtime());
+    const int dev = s->a->dev;
+    if (n_hay == 0) return no_fragments(dev, out);
+    ON_DEVICE(dev);
+    am_batch* b = oneshot_batch(dev);                       // this thread's batch on the automaton's device
+    int rc = upload_batch(hay, n_hay, b, true);
+    if (rc == AM_OK) rc = am_split_batch(s, case_mode, b, out);
+    oneshot_batch_trim(dev);
+    return rc;
+}
+
+extern "C" uint64_t am_fragments_size(const am_fragments* f) { return f ? f->n_frag : 0; }
+extern "C" uint64_t am_fragments_haystacks(const am_fragments* f) { return f ? f->n_hay : 0; }
+extern "C" const void* am_fragments_device_offsets(const am_fragments* f) { return f ? f->offsets.p : nullptr; }
+extern "C" const void* am_fragments_device_data(const am_fragments* f) { return f ? f->data.p : nullptr; }
+
+namespace {
+template <class T>
+const T* fetch(am_fragments* f, std::vector<T>& host, bool& fetched, const DevBuf& d, uint64_t n)
+{
+    if (fetched) return host.data();
+    try { host.resize((size_t)std::max<uint64_t>(n, 1)); } catch (const std::exception&) { fail(AM_ERR_OOM, "no host memory for the fragments"); return nullptr; }
+    if (n) {
+        if (ensure_runtime() != AM_OK) return nullptr;
+        OnDevice od(f->dev);
+        hipStream_t st;
+        if (od.rc != AM_OK || get_stream(f->dev, &st) != AM_OK) return nullptr;
+        if (hipMemcpyAsync(host.data(), d.p, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+            fail(AM_ERR_HIP, "copying the fragments to the host failed");
+            return nullptr;
+        }
+    }
+    fetched = true;
+    return host.data();
+}
+}  // namespace
+
+extern "C" const uint64_t* am_fragments_offsets(am_fragments* f)
+{
+    if (!f) { fail(AM_ERR_INVALID, "null fragments"); return nullptr; }
+    return fetch(f, f->h_offsets, f->offsets_fetched, f->offsets, f->n_hay + 1);
+}
+
+extern "C" const am_fragment* am_fragments_data(am_fragments* f)
+{
+    if (!f) { fail(AM_ERR_INVALID, "null fragments"); return nullptr; }
+    return fetch(f, f->h_data, f->data_fetched, f->data, f->n_frag);
+}
+
+extern "C" void am_fragments_free(am_fragments* f)
+{
+    if (!f) return;
+    f->data.release(); f->offsets.release();
+    delete f;
+}
+
+extern "C" int am_batch_from_fragments(const am_batch* src, const am_fragments* f, am_batch** out)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    if (!src || !f) return fail(AM_ERR_INVALID, "null batch or fragments");
+    if (f->n_hay != src->n_hay || f->src_total != src->total || f->dev != src->dev)
+        return fail(AM_ERR_INVALID, "the fragments were not produced from a batch with this haystack count and size");
+    if (f->n_frag >= 0xFFFFFFFFull) return fail(AM_ERR_UNSUPPORTED, "am_batch_from_fragments: 2^32 - 1 fragments and more do not fit a batch");
+    AM_TRY(ensure_runtime());
+    ON_DEVICE(src->dev);
+    hipStream_t st; AM_TRY(get_stream(src->dev, &st));
+    std::unique_ptr<am_batch, void (*)(am_batch*)> nb(new am_batch(), am_batch_destroy);
+    nb->dev = src->dev; nb->owns = true;
+    const uint64_t n = f->n_frag;
+    DevBuf lens, src_at, scan_tmp;
+    struct Release { DevBuf &a, &b, &c; ~Release() { a.release(); b.release(); c.release(); } } rel{lens, src_at, scan_tmp};
+    AM_TRY(lens.ensure((n + 1) * 8));
+    AM_TRY(src_at.ensure((n + 1) * 8));
+    AM_TRY(nb->offs_buf.ensure((n + 1) * 8));
+    size_t tmp_bytes = 0;
+    HIP_TRY(scan64_temp_bytes(n + 1, &tmp_bytes));
+    AM_TRY(scan_tmp.ensure(tmp_bytes));
+    HIP_TRY(launch_split_sources((const Fragment*)f->data.p, n, (const uint64_t*)f->offsets.p, src->d_offsets, src->n_hay, src->total, (uint64_t*)lens.p, (uint64_t*)src_at.p, st));
+    HIP_TRY(launch_scan64(scan_tmp.p, scan_tmp.cap, (const uint64_t*)lens.p, (uint64_t*)nb->offs_buf.p, n + 1, st));
+    uint64_t total = 0;
+    AM_TRY(read_u64((const uint64_t*)nb->offs_buf.p + n, &total, st));
+    const size_t padded = padded_text(total);
+    AM_TRY(nb->text_buf.ensure(padded));
+    const uint64_t whole = total & ~15ull;
+    HIP_TRY(hipMemsetAsync((uint8_t*)nb->text_buf.p + whole, 0, padded - whole, st));            // zero tail: kernels read whole 16-byte groups
+    { Prof pr("split_gather", st);
+      HIP_TRY(launch_split_gather((const uint8_t*)src->d_text, src->total, (const uint64_t*)src_at.p, (const uint64_t*)nb->offs_buf.p, n, total, (uint8_t*)nb->text_buf.p,
+                                  g_rt.dev[src->dev].n_cu, st)); }
+    HIP_TRY(hipStreamSynchronize(st));                      // a batch object may be used from any thread and stream afterwards
+    nb->d_text = nb->text_buf.p; nb->d_offsets = (uint64_t*)nb->offs_buf.p;
+    nb->total = total; nb->n_hay = (uint32_t)n;
+    AM_TRY(finish_batch(nb.get()));
+    *out = nb.release();
+    return AM_OK;
+}

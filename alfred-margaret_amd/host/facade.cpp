@@ -239,6 +239,58 @@ int amh_splitter_split_batch(void* sp, int ignore_case, const am_slice* hay, siz
         *blob_out = blob; *offs_out = offs; *n_frag_out = nf;
     });
 }
+// the same lists with the fold on the device (Splitter::splitBatchDevice)
+int amh_splitter_split_batch_device(void* sp, int ignore_case, const am_slice* hay, size_t n_hay, uint8_t** blob_out, uint64_t** offs_out,
+                                    uint64_t* n_frag_out, uint32_t* frags_per_hay)
+{
+    *blob_out = nullptr; *offs_out = nullptr;
+    return guarded([&] {
+        const std::vector<Text> ts = sliceTexts(hay, n_hay);
+        const Splitter::Fragments fr = static_cast<Splitter*>(sp)->splitBatchFragments(ts, ignore_case != 0);
+        const uint64_t nf = fr.fragments.size();
+        uint64_t total = 0;
+        for (auto& f : fr.fragments) total += f.len;
+        uint8_t* blob = (uint8_t*)malloc(total ? total : 1);
+        uint64_t* offs = (uint64_t*)malloc((nf + 1) * sizeof(uint64_t));
+        uint64_t at = 0;
+        for (size_t i = 0; i < n_hay; i++) {
+            frags_per_hay[i] = (uint32_t)(fr.offsets[i + 1] - fr.offsets[i]);
+            for (uint64_t k = fr.offsets[i]; k < fr.offsets[i + 1]; k++) {
+                offs[k] = at;
+                if (fr.fragments[k].len) std::memcpy(blob + at, ts[i].begin() + fr.fragments[k].start, (size_t)fr.fragments[k].len);
+                at += fr.fragments[k].len;
+            }
+        }
+        offs[nf] = at;
+        *blob_out = blob; *offs_out = offs; *n_frag_out = nf;
+    });
+}
+// (start, length) per fragment: offsets (n_hay + 1) and 2 x n_frag words; free both with amh_free_u64
+int amh_splitter_fragments_batch(void* sp, int ignore_case, const am_slice* hay, size_t n_hay, uint64_t** offs_out, uint64_t** frags_out, uint64_t* n_frag_out)
+{
+    *offs_out = nullptr; *frags_out = nullptr; *n_frag_out = 0;
+    return guarded([&] {
+        const Splitter::Fragments fr = static_cast<Splitter*>(sp)->splitBatchFragments(sliceTexts(hay, n_hay), ignore_case != 0);
+        const uint64_t nf = fr.fragments.size();
+        uint64_t* offs = (uint64_t*)malloc((n_hay + 1) * sizeof(uint64_t));
+        uint64_t* frags = (uint64_t*)malloc((nf ? nf : 1) * 2 * sizeof(uint64_t));
+        std::memcpy(offs, fr.offsets.data(), (n_hay + 1) * sizeof(uint64_t));
+        for (uint64_t k = 0; k < nf; k++) { frags[2 * k] = fr.fragments[k].start; frags[2 * k + 1] = fr.fragments[k].len; }
+        *offs_out = offs; *frags_out = frags; *n_frag_out = nf;
+    });
+}
+// the am_splitter* behind this Splitter, for callers that keep their batches on the device
+int amh_splitter_device(void* sp, const void** out)
+{
+    *out = nullptr;
+    return guarded([&] { *out = static_cast<Splitter*>(sp)->device(); });
+}
+// the am_automaton* of the separator (tests choose the scan route on it)
+int amh_splitter_automaton(void* sp, const void** out)
+{
+    *out = nullptr;
+    return guarded([&] { *out = static_cast<Splitter*>(sp)->automaton().device.get(); });
+}
 void amh_free_u64(uint64_t* p) { free(p); }
 
 // ---- Utf8 helpers

@@ -66,6 +66,8 @@ typedef struct am_needle_ids am_needle_ids;
 typedef struct am_replaced am_replaced;
 typedef struct am_batch am_batch;
 typedef struct am_matches am_matches;
+typedef struct am_splitter am_splitter;
+typedef struct am_fragments am_fragments;
 
 /* A Text slice: bytes ptr[off .. off+len).  Same shape as U8Slice in
  * benchmark/rust-ffi/app/Main.hs:34-45 (= Data.Text.Internal.Text array/offset/length). */
@@ -204,6 +206,45 @@ AM_API int am_contains_all_batch(const am_needle_ids* ids, int case_mode, const 
 AM_API int am_count_by_needle_batch(const am_needle_ids* ids, int case_mode, const am_batch* b, uint64_t* counts_out /* n_needles, host */);
 AM_API int am_count_by_needle(const am_needle_ids* ids, int case_mode, const am_slice* hay, size_t n_hay, uint64_t* counts_out /* n_needles, host */);
 AM_API int am_matches_count_by_needle(const am_matches* m, const am_needle_ids* ids, uint64_t* counts_out /* n_needles, host */);
+
+/* ---- Splitter: split every haystack of a batch on one separator, in HBM (src/Data/Text/AhoCorasick/Splitter.hs) ---------------
+ * A Splitter is a one-needle automaton, `Aho.build [(sep, ())]` (Splitter.hs:64-67), plus the separator's length.  The scan leaves its sorted records in HBM and the
+ * fold stepAccum / finalizeAccum (Splitter.hs:141-170) runs there too (csrc/am_split.hip); no record crosses the wire.  For haystack i the fragments are exactly
+ * `split` (Splitter.hs:84-85) in forward order, with AM_IGNORE_CASE exactly `splitIgnoreCase` (Splitter.hs:96-97): a match that starts before the current fragment
+ * start is ignored (Splitter.hs:163-164), empty fragments are kept, and every haystack has at least one fragment (finalizeAccum, Splitter.hs:141-147; an empty haystack
+ * gives one empty fragment).  The start of a separator that ends at end_pos is end_pos - sep_len_bytes when case sensitive (Splitter.hs:105-107) and
+ * skipCodePointsBackwards text (end_pos - 1) (sep_len_code_points - 1) when ignoring case (Splitter.hs:117-121, Utf8.hs:256-276: a K matched by U+212A is three bytes
+ * long); that walk never leaves the haystack: one that would is clamped to 0 where the reference calls `error`, which no match the automaton reports can cause.
+ *   am_splitter_create       `a`: the automaton of the separator (it must outlive the splitter), given in the case the caller will split in (Splitter.hs:92-93: a
+ *                            lower-case needle for splitIgnoreCase).  Checked before any device work: AM_ERR_INVALID for null arguments, sep_len_bytes == 0,
+ *                            sep_len_code_points == 0 or > sep_len_bytes (the empty separator is refused: the reference's own arithmetic is meaningless for it) and for
+ *                            an automaton that is not a one-needle automaton (exactly one state with values, and one value there, by the values_len given to
+ *                            am_automaton_create); AM_ERR_UNSUPPORTED for a handle made from an image, which does not keep values_len.
+ *   am_split_batch           a device-resident batch; the result stays in HBM.  AM_ERR_INVALID for null arguments and for splitter and batch on different devices.
+ *                            Record memory is NOT bounded here: the whole batch is scanned once and all its records are in HBM while they are folded (one record
+ *                            per separator occurrence, 16 bytes each, plus 21 bytes of workspace per record, 37 when a chain of overlapping matches needs the doubling rounds; the
+ *                            library's device buffers are allocated an eighth larger than asked: count 48 / 66 bytes per occurrence, and 16 per fragment of the result).
+ *   am_split                 the one-shot form on host slices.  n_hay == 0 gives zero fragments and AM_OK.
+ *   am_fragments_*           size = fragments of the whole batch; the fragments of haystack i are [offsets[i], offsets[i + 1]) of data, start and len in code units relative
+ *                            to the start of the haystack's slice.  offsets / data are host copies made on first use and owned by the result (NULL on error); the device_
+ *                            forms are the arrays in HBM (NULL when there is no haystack).  All indices are 64-bit.
+ *   am_batch_from_fragments  gathers the fragments' bytes into a NEW batch that the library owns (am_batch_destroy), on src's device: one haystack per fragment, in
+ *                            order, offsets = the running sum of the lengths, text 16-byte aligned and readable to round_up(total, 16): usable by every *_batch entry
+ *                            point.  am_fragments_offsets maps a line back to its document.  `src` must be the batch the fragments were cut from: AM_ERR_INVALID when its
+ *                            haystack count or total bytes differ; AM_ERR_UNSUPPORTED for 0xFFFFFFFF fragments and more (the limit of am_batch_from_device). */
+typedef struct am_fragment { uint64_t start; uint64_t len; } am_fragment;
+AM_API int am_splitter_create(const am_automaton* a, uint32_t sep_len_bytes, uint32_t sep_len_code_points, am_splitter** out);
+AM_API void am_splitter_destroy(am_splitter* s);
+AM_API int am_split_batch(const am_splitter* s, int case_mode, const am_batch* b, am_fragments** out);
+AM_API int am_split(const am_splitter* s, int case_mode, const am_slice* hay, size_t n_hay, am_fragments** out);
+AM_API uint64_t am_fragments_size(const am_fragments* f);
+AM_API uint64_t am_fragments_haystacks(const am_fragments* f);
+AM_API const uint64_t* am_fragments_offsets(am_fragments* f);
+AM_API const am_fragment* am_fragments_data(am_fragments* f);
+AM_API const void* am_fragments_device_offsets(const am_fragments* f);
+AM_API const void* am_fragments_device_data(const am_fragments* f);
+AM_API void am_fragments_free(am_fragments* f);
+AM_API int am_batch_from_fragments(const am_batch* src, const am_fragments* f, am_batch** out);
 
 /* Checksum of the fold sequence of a result (harness aid; SURVEY 8d "parity check at scale",
  * benchmark/benchmark.py:65-69 asserts count identity on every run).  For every haystack i < n_hay:

@@ -41,6 +41,10 @@ AM_API int am_debug_resident_waves(float* one_ms_out, float* two_ms_out);
  * calls since the last read; reading clears the sums (out3 NULL: only clears).  tests/measure/needle_counts.py. */
 AM_API int am_debug_hist_adds(uint64_t* out3);
 
+/* Rounds of pointer doubling the last am_split_batch / am_split of the process needed (csrc/am_split.hip k_split_double): 0 when no chain of overlapping matches was longer
+ * than the walk limit (AM_SPLIT_CHAIN_LIMIT), else about log2 of the separators kept in the longest chain.  tests/measure/splitter.py. */
+AM_API uint32_t am_debug_split_rounds(void);
+
 #ifdef __cplusplus
 }
 #endif
