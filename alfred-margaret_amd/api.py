@@ -188,6 +188,7 @@ _HOST = {
 DEBUG_ABI = {
     "am_debug_set": (C.c_int, [C.c_char_p, C.c_long]),
     "am_debug_pinned_bytes": (C.c_uint64, []),
+    "am_debug_device_buffer_bytes": (C.c_uint64, []),
     "am_debug_bounds_report": (C.c_int, [_u64p, _u32p, _u32p]),
     "am_debug_sf_phase_cycles": (C.c_int, [_vp]),
     "am_debug_sf_wave_records": (C.c_int, [_vp, _sz]),

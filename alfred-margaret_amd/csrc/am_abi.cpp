@@ -702,8 +702,7 @@ extern "C" int am_batch_from_device(const void* d_bytes, const void* d_offsets, 
 extern "C" void am_batch_destroy(am_batch* b)
 {
     if (!b) return;
-    for (DevBuf* d : {&b->text_buf, &b->offs_buf, &b->combo, &b->hidx, &b->unit_counts, &b->unit_offsets, &b->scan_tmp, &b->small, &b->hay_counts, &b->flags, &b->unit_first, &b->pool, &b->block_next,
-                      &b->sparse, &b->dense_counts, &b->dense_offsets, &b->dense_out}) d->release();
+    OnDevice od(b->dev);
     delete b;
 }
 
@@ -1318,6 +1317,7 @@ extern "C" int am_debug_bounds_report(uint64_t* failed_out, uint32_t* first_line
 }
 
 extern "C" uint64_t am_debug_pinned_bytes(void) { return (uint64_t)g_pinned_staging_bytes.load(std::memory_order_relaxed); }
+extern "C" uint64_t am_debug_device_buffer_bytes(void) { return g_device_buffer_bytes.load(std::memory_order_relaxed); }
 
 extern "C" int am_debug_resident_waves(float* one_ms_out, float* two_ms_out)
 {

@@ -47,17 +47,12 @@ extern "C" int am_needle_ids_create(const am_automaton* a, const uint64_t* value
     if (rc == AM_OK) rc = ids->vals.ensure(n_values * 4 + 4);
     if (rc == AM_OK && hipMemcpy(ids->vals_off.p, values_offsets, (n_states + 1) * 8, hipMemcpyHostToDevice) != hipSuccess) rc = fail(AM_ERR_HIP, "upload failed");
     if (rc == AM_OK && n_values && hipMemcpy(ids->vals.p, values, n_values * 4, hipMemcpyHostToDevice) != hipSuccess) rc = fail(AM_ERR_HIP, "upload failed");
-    if (rc != AM_OK) { am_needle_ids_destroy(ids); return rc; }
+    if (rc != AM_OK) { delete ids; return rc; }
     *out = ids;
     return AM_OK;
 }
 
-extern "C" void am_needle_ids_destroy(am_needle_ids* ids)
-{
-    if (!ids) return;
-    ids->vals_off.release(); ids->vals.release();
-    delete ids;
-}
+extern "C" void am_needle_ids_destroy(am_needle_ids* ids) { delete ids; }
 
 extern "C" int am_contains_all_batch(const am_needle_ids* ids, int case_mode, const am_batch* cb, uint8_t* flags_out)
 {
@@ -70,7 +65,6 @@ extern "C" int am_contains_all_batch(const am_needle_ids* ids, int case_mode, co
     ON_DEVICE(b->dev);
     hipStream_t st; AM_TRY(get_stream(b->dev, &st));
     DevBuf records, rec_first, bits, flags;
-    struct Release { DevBuf &a, &b, &c, &d; ~Release() { a.release(); b.release(); c.release(); d.release(); } } rel{records, rec_first, bits, flags};
     const uint32_t words = (ids->n_needles + 31) / 32;
     // The direct route (round 5): the scan itself sets the bit of every needle id it reports -- no record is written -- and a haystack whose set is
     // complete is not looked at any further (`Done`, Searcher.hs:181), like containsAny's first match.  One bitmap row per haystack, up to 8 GiB of them;
@@ -84,8 +78,7 @@ extern "C" int am_contains_all_batch(const am_needle_ids* ids, int case_mode, co
         if (taken) return AM_OK;
     }
     uint64_t n_rec = 0;
-    auto sink = [&](uint64_t n, Record** ptr) -> int { AM_TRY(records.ensure(n * sizeof(Record))); *ptr = (Record*)records.p; return AM_OK; };
-    AM_TRY(run_records(ids->a, case_mode, b, sink, &n_rec));
+    AM_TRY(run_records(ids->a, case_mode, b, records_into(records), &n_rec));
     if (n_rec == 0) { std::memset(flags_out, 0, n_hay); return AM_OK; }
     // one bitmap row per haystack; very wide batches go through in groups of haystacks (records are sorted by haystack)
     const uint64_t budget = 1ull << 30;
@@ -93,7 +86,7 @@ extern "C" int am_contains_all_batch(const am_needle_ids* ids, int case_mode, co
     AM_TRY(rec_first.ensure(((uint64_t)n_hay + 1) * 8));
     AM_TRY(bits.ensure((uint64_t)group * words * 4));
     AM_TRY(flags.ensure(n_hay));
-    HIP_TRY(launch_rp_ranges((const Record*)records.p, n_rec, (uint64_t*)rec_first.p, RpRoute{nullptr, nullptr, nullptr, nullptr, nullptr}, n_hay, st));
+    HIP_TRY(launch_rp_ranges((const Record*)records.p, n_rec, (uint64_t*)rec_first.p, kNoRoute, n_hay, st));
     std::vector<uint64_t> first;
     if (group < n_hay) {
         first.resize((size_t)n_hay + 1);
@@ -125,12 +118,11 @@ extern "C" int am_matches_fold_hash(const am_matches* m, const am_needle_ids* id
     ON_DEVICE(m->dev);
     hipStream_t st; AM_TRY(get_stream(m->dev, &st));
     DevBuf rec_first, out, dummy;
-    struct Release { DevBuf &a, &b, &c; ~Release() { a.release(); b.release(); c.release(); } } rel{rec_first, out, dummy};
     AM_TRY(rec_first.ensure((n_hay + 1) * 8));
     AM_TRY(out.ensure(n_hay * 16));
     AM_TRY(dummy.ensure(sizeof(Record)));
     const Record* recs = m->n ? m->d_records + m->first : (const Record*)dummy.p;
-    HIP_TRY(launch_rp_ranges(recs, m->n, (uint64_t*)rec_first.p, RpRoute{nullptr, nullptr, nullptr, nullptr, nullptr}, (uint32_t)n_hay, st));
+    HIP_TRY(launch_rp_ranges(recs, m->n, (uint64_t*)rec_first.p, kNoRoute, (uint32_t)n_hay, st));
     { Prof pr("fold_hash", st);
       HIP_TRY(launch_fold_hash(recs, (const uint64_t*)rec_first.p, (const uint64_t*)ids->vals_off.p, (const uint32_t*)ids->vals.p, (uint32_t)n_hay,
                                (uint64_t*)out.p, (uint64_t*)out.p + n_hay, st)); }
@@ -176,8 +168,7 @@ int hist_launch(const am_needle_ids* ids, const Record* recs, uint64_t n_rec, ui
 int hist_scan(const am_needle_ids* ids, int case_mode, am_batch* b, RecordArray& ra, uint64_t* d_counts, uint64_t* d_trace)
 {
     uint64_t n_rec = 0;
-    auto sink = [&](uint64_t n, Record** ptr) -> int { AM_TRY(ra.ensure(n * sizeof(Record))); *ptr = (Record*)ra.p; return AM_OK; };
-    AM_TRY(run_records(ids->a, case_mode, b, sink, &n_rec));
+    AM_TRY(run_records(ids->a, case_mode, b, records_into(ra), &n_rec));
     if (n_rec == 0) return AM_OK;
     ON_DEVICE(b->dev);
     hipStream_t st; AM_TRY(get_stream(b->dev, &st));
@@ -235,7 +226,6 @@ int hist_batch(const am_needle_ids* ids, int case_mode, am_batch* b, uint64_t* d
 // the histogram of a call in HBM: n_needles counts + the three trace words, cleared; read back at the end
 struct HistOut {
     DevBuf buf; uint32_t n = 0; bool trace = false;
-    ~HistOut() { buf.release(); }
     int begin(uint32_t n_needles, hipStream_t st)
     {
         n = n_needles; trace = cfg::on(cfg::kHistTrace);

@@ -101,19 +101,32 @@ struct Prof {
     }
 };
 
+// Device memory of one owner; the destructor frees it, so an owner names its buffers once, as members.  THE RULE: no DevBuf, and no struct that holds one, has
+// static or thread storage duration -- its destructor would call into HIP while the runtime is being torn down at process exit (the reason Orphans and
+// pinned_cache() in am_abi.cpp are never destroyed).  Handles and workspaces live on the heap or on a call's stack.
+inline std::atomic<uint64_t> g_device_buffer_bytes{0};      // bytes all live DevBufs hold (am_debug_device_buffer_bytes: the leak test)
 struct DevBuf {
     void* p = nullptr; size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     int ensure(size_t n)
     {
         if (n <= cap) return AM_OK;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+        release();
         size_t want = n + n / 8 + 256;
         hipError_t e = hipMalloc(&p, want);
         if (e != hipSuccess) { p = nullptr; return fail(e == hipErrorOutOfMemory ? AM_ERR_OOM : AM_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e)); }
         cap = want;
+        g_device_buffer_bytes.fetch_add(want, std::memory_order_relaxed);
         return AM_OK;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    void release()
+    {
+        if (p) { (void)hipFree(p); g_device_buffer_bytes.fetch_sub(cap, std::memory_order_relaxed); }
+        p = nullptr; cap = 0;
+    }
 };
 
 struct Flavor {
@@ -216,6 +229,14 @@ struct RecordArray {
     ~RecordArray() { record_array_put(dev, p, cap); }
 };
 inline size_t padded_text(uint64_t total) { return (size_t)((total + 15) & ~15ull) + 16; }
+// the sink of run_records that puts the records into `d` (a DevBuf or a RecordArray), with room for `spare` more
+template <class Buf>
+auto records_into(Buf& d, uint64_t spare = 0)
+{
+    return [&d, spare](uint64_t n, Record** ptr) -> int { AM_TRY(d.ensure((n + spare) * sizeof(Record))); *ptr = (Record*)d.p; return AM_OK; };
+}
+// launch_rp_ranges for callers that want the record ranges alone
+inline constexpr RpRoute kNoRoute{nullptr, nullptr, nullptr, nullptr, nullptr};
 
 }  // namespace host
 }  // namespace am

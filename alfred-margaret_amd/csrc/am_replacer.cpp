@@ -13,6 +13,88 @@ static_assert(sizeof(am_payload) == sizeof(RpPayload) && offsetof(am_payload, re
                   offsetof(am_payload, len_code_points) == offsetof(RpPayload, len_code_points) && offsetof(am_payload, repl_len) == offsetof(RpPayload, repl_len),
               "am_payload must mirror the device payload");
 
+namespace {
+
+// growing page-locked host memory.  DevBuf's rule (am_host.h) holds here too: never static or thread storage -- the destructor calls into HIP.
+struct PinBuf {
+    void* p = nullptr; size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+    int ensure(size_t bytes)
+    {
+        if (bytes <= cap) return AM_OK;
+        if (p) (void)hipHostFree(p);
+        p = nullptr; cap = 0;
+        const size_t want = bytes + bytes / 2 + 4096;
+        if (hipHostMalloc(&p, want, hipHostMallocPortable) != hipSuccess) { p = nullptr; return fail(AM_ERR_OOM, "hipHostMalloc failed"); }
+        cap = want;
+        return AM_OK;
+    }
+};
+
+// The workspace of one run: device buffers, pinned scratch, copy stream.  A replacer keeps the sessions of finished runs for the next ones (SessionLease).
+struct RpSession {
+    DevBuf text[2], offs[2], orig[2], thr[2];
+    DevBuf totals; uint64_t* tot_host = nullptr; uint64_t tot_seq = 0;       // the per-pass totals, read back through pinned memory (tot_host[15]: sequence number of the last pass written)
+    hipStream_t copy_stream = nullptr; hipEvent_t ev_spliced = nullptr;     // finished texts travel home next to the window scans
+    PinBuf fin_host;                     // RpFin[] of the haystacks a pass finished
+    DevBuf recbuf[2];                    // sorted records of the current pass / of the next one (incremental re-scan)
+    DevBuf nwin, win_off, wins, wlen, woffs, wtext, wrec, wrec_first, mcount, moff, tile_hay;
+    am_batch ws2;                        // workspace of the window scans
+    DevBuf rec_first, rec_first2, kept, hs, len_next, len_fin, tiles, act, fin, off_next, off_fin, tile_off, act_idx, fin_idx, scan_tmp, fin_text, fin_meta;      // (rec_first2: the piece-table loop's second ranges buffer -- a pass's merge writes the next pass's ranges)
+    am_batch ws;                         // workspace holder for the scans; never owns its text
+    DevBuf first_orig, first_thr;
+    DevBuf pt_pieces[2], pt_start[2], pt_cnt[2], pt_need, pt_need_off, pt_fin_start, pt_fin_cnt;      // piece-table path
+    DevBuf lp_rec, lp_pc, lp_kept, lp_wtext, lp_out, lp_ctrl, lp_cap_r, lp_cap_p, lp_rec_base, lp_pc_base, lp_fin, lp_fin_start, lp_fin_cnt, lp_redo;      // one-kernel loops (am_rplds.hip, am_rploop.hip)
+    DevBuf lp_stage[8];                  // device staging of the haystack groups' finished texts on their way to the host
+    PinBuf lp_host;                      // the loop's per-haystack results, then the materialise tables
+    DevBuf pf_best, pf_delta, pf_payload, pf_selflag, pf_sidx, pf_cand, pf_sel, pf_keep, pf_kflag, pf_kdelta, pf_kidx, pf_kdpre, pf_tmp;   // record-parallel fold
+    // what counts against the limits of the session cache: the buffers that grow with the texts and the records
+    size_t device_bytes() const
+    {
+        size_t n = 0;
+        for (const DevBuf* d : {&text[0], &text[1], &recbuf[0], &recbuf[1], &kept, &wins, &wtext, &wrec, &fin_text, &ws.pool, &ws2.pool, &ws.hidx, &ws2.hidx, &pf_cand, &pf_sel, &pf_sidx,
+                                &lp_rec, &lp_pc, &lp_kept, &lp_wtext, &lp_stage[0], &lp_stage[1], &lp_stage[2], &lp_stage[3], &lp_stage[4], &lp_stage[5], &lp_stage[6], &lp_stage[7]}) n += d->cap;
+        return n;
+    }
+    // the block the totals of a pass come home in
+    int pinned_totals()
+    {
+        AM_TRY(totals.ensure(128));
+        if (tot_host) return AM_OK;
+        if (hipHostMalloc((void**)&tot_host, 128, hipHostMallocPortable | hipHostMallocCoherent) != hipSuccess) { tot_host = nullptr; return fail(AM_ERR_OOM, "hipHostMalloc failed"); }
+        std::memset(tot_host, 0, 128);                    // (fine-grained: a device store is visible to the host while the kernel is still running)
+        return AM_OK;
+    }
+    int copy_lane()
+    {
+        if (!copy_stream && (hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&ev_spliced, hipEventDisableTiming) != hipSuccess))
+            return fail(AM_ERR_HIP, "could not create the copy stream");
+        return AM_OK;
+    }
+    // the first pass's arrays: haystack i is haystack i of the caller, initialThreshold = 1 (Replacer.hs:211)
+    int first_pass_arrays(uint32_t n_hay, hipStream_t st)
+    {
+        std::vector<uint32_t> o(n_hay); std::vector<int64_t> t(n_hay, 1);
+        for (uint32_t i = 0; i < n_hay; i++) o[i] = i;
+        AM_TRY(first_orig.ensure(n_hay * sizeof(uint32_t))); AM_TRY(first_thr.ensure(n_hay * sizeof(int64_t)));
+        HIP_TRY(hipMemcpyAsync(first_orig.p, o.data(), n_hay * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(first_thr.p, t.data(), n_hay * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return AM_OK;
+    }
+    ~RpSession()      // (the device buffers free themselves afterwards: nothing is in flight on the copy stream by then)
+    {
+        if (tot_host) (void)hipHostFree(tot_host);
+        if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }
+        if (ev_spliced) (void)hipEventDestroy(ev_spliced);
+    }
+};
+
+}  // namespace
+
 struct am_replacer {
     const am_automaton* a = nullptr;
     int case_mode = 0;
@@ -25,8 +107,7 @@ struct am_replacer {
     // the workspace of the last run (device buffers, pinned scratch, copy stream) is kept for the next one: a caller that
     // rewrites one document per call would otherwise pay ~40 hipMalloc/hipFree (4 ms) each time
     mutable std::mutex session_mu;
-    mutable std::vector<void*> sessions;              // workspaces of finished runs, kept for the next ones (several: concurrent groups / threads)
-    void (*session_delete)(void*) = nullptr;
+    mutable std::vector<std::unique_ptr<RpSession>> sessions;      // workspaces of finished runs, kept for the next ones (several: concurrent groups / threads), oldest first
 };
 
 // Finished texts are copied D2H straight into pinned slabs that the result object keeps (no second host
@@ -176,78 +257,56 @@ extern "C" int am_replacer_create(const am_automaton* a, int case_mode, const ui
     return AM_OK;
 }
 
-extern "C" void am_replacer_destroy(am_replacer* r)
-{
-    if (!r) return;
-    if (r->session_delete) for (void* p : r->sessions) r->session_delete(p);
-    for (DevBuf* d : {&r->vals_off, &r->vals, &r->payloads, &r->repl, &r->one}) d->release();
-    delete r;
-}
+extern "C" void am_replacer_destroy(am_replacer* r) { delete r; }
 
 namespace {
 
-struct RpSession {
-    DevBuf text[2], offs[2], orig[2], thr[2];
-    DevBuf totals; uint64_t* tot_host = nullptr; uint64_t tot_seq = 0;       // the per-pass totals, read back through pinned memory (tot_host[15]: sequence number of the last pass written)
-    hipStream_t copy_stream = nullptr; hipEvent_t ev_spliced = nullptr;     // finished texts travel home next to the window scans
-    RpFin* fin_host = nullptr; size_t fin_host_cap = 0;                     // pinned
-    int pin_meta(size_t bytes)
+// A run's hold on a session: the replacer's newest cached one (or a new one), given back when the run ends unless it holds more than `keep` bytes of device
+// memory.  The cache holds at most 8 sessions and 4 GiB in all; the oldest go first, and they are deleted outside the lock.
+struct SessionLease {
+    const am_replacer* r; size_t keep; std::unique_ptr<RpSession> s;
+    SessionLease(const am_replacer* r_, size_t keep_) : r(r_), keep(keep_)
     {
-        if (bytes <= fin_host_cap) return AM_OK;
-        if (fin_host) (void)hipHostFree(fin_host);
-        fin_host = nullptr; fin_host_cap = 0;
-        const size_t want = bytes + bytes / 2 + 4096;
-        if (hipHostMalloc((void**)&fin_host, want, hipHostMallocPortable) != hipSuccess) { fin_host = nullptr; return fail(AM_ERR_OOM, "hipHostMalloc failed"); }
-        fin_host_cap = want;
-        return AM_OK;
+        { std::lock_guard<std::mutex> lk(r->session_mu); if (!r->sessions.empty()) { s = std::move(r->sessions.back()); r->sessions.pop_back(); } }
+        if (!s) s = std::make_unique<RpSession>();
     }
-    DevBuf recbuf[2];                    // sorted records of the current pass / of the next one (incremental re-scan)
-    DevBuf nwin, win_off, wins, wlen, woffs, wtext, wrec, wrec_first, mcount, moff, tile_hay;
-    am_batch ws2;                        // workspace of the window scans
-    DevBuf rec_first, rec_first2, kept, hs, len_next, len_fin, tiles, act, fin, off_next, off_fin, tile_off, act_idx, fin_idx, scan_tmp, fin_text, fin_meta;      // (rec_first2: the piece-table loop's second ranges buffer -- a pass's merge writes the next pass's ranges)
-    am_batch ws;                         // workspace holder for the scans; never owns its text
-    DevBuf first_orig, first_thr;
-    DevBuf pt_pieces[2], pt_start[2], pt_cnt[2], pt_need, pt_need_off, pt_fin_start, pt_fin_cnt;      // piece-table path
-    DevBuf lp_rec, lp_pc, lp_kept, lp_wtext, lp_out, lp_ctrl, lp_cap_r, lp_cap_p, lp_rec_base, lp_pc_base, lp_fin, lp_fin_start, lp_fin_cnt, lp_redo;      // one-kernel loops (am_rplds.hip, am_rploop.hip)
-    DevBuf lp_stage[8];                  // device staging of the haystack groups' finished texts on their way to the host
-    void* lp_host = nullptr; size_t lp_host_cap = 0;                        // pinned: the loop's per-haystack results, then the materialise tables
-    int pin_loop(size_t bytes)
+    ~SessionLease()
     {
-        if (bytes <= lp_host_cap) return AM_OK;
-        if (lp_host) (void)hipHostFree(lp_host);
-        lp_host = nullptr; lp_host_cap = 0;
-        const size_t want = bytes + bytes / 2 + 4096;
-        if (hipHostMalloc(&lp_host, want, hipHostMallocPortable) != hipSuccess) { lp_host = nullptr; return fail(AM_ERR_OOM, "hipHostMalloc failed"); }
-        lp_host_cap = want;
-        return AM_OK;
-    }
-    DevBuf pf_best, pf_delta, pf_payload, pf_selflag, pf_sidx, pf_cand, pf_sel, pf_keep, pf_kflag, pf_kdelta, pf_kidx, pf_kdpre, pf_tmp;   // record-parallel fold
-    size_t device_bytes() const
-    {
-        size_t n = 0;
-        for (const DevBuf* d : {&text[0], &text[1], &recbuf[0], &recbuf[1], &kept, &wins, &wtext, &wrec, &fin_text, &ws.pool, &ws2.pool, &ws.hidx, &ws2.hidx, &pf_cand, &pf_sel, &pf_sidx,
-                                &lp_rec, &lp_pc, &lp_kept, &lp_wtext, &lp_stage[0], &lp_stage[1], &lp_stage[2], &lp_stage[3], &lp_stage[4], &lp_stage[5], &lp_stage[6], &lp_stage[7]}) n += d->cap;
-        return n;
-    }
-    ~RpSession()
-    {
-        for (DevBuf* d : {&text[0], &text[1], &offs[0], &offs[1], &orig[0], &orig[1], &thr[0], &thr[1], &rec_first, &kept, &hs, &len_next, &len_fin,
-                          &recbuf[0], &recbuf[1], &nwin, &win_off, &wins, &wlen, &woffs, &wtext, &wrec, &wrec_first, &mcount, &moff, &tile_hay,
-                          &totals, &tiles, &act, &fin, &off_next, &off_fin, &tile_off, &act_idx, &fin_idx, &scan_tmp, &fin_text, &fin_meta, &first_orig, &first_thr,
-                          &pf_best, &pf_delta, &pf_payload, &pf_selflag, &pf_sidx, &pf_cand, &pf_sel, &pf_keep, &pf_kflag, &pf_kdelta, &pf_kidx, &pf_kdpre, &pf_tmp,
-                          &pt_pieces[0], &pt_pieces[1], &pt_start[0], &pt_start[1], &pt_cnt[0], &pt_cnt[1], &pt_need, &pt_need_off, &pt_fin_start, &pt_fin_cnt,
-                          &lp_rec, &lp_pc, &lp_kept, &lp_wtext, &lp_out, &lp_ctrl, &lp_cap_r, &lp_cap_p, &lp_rec_base, &lp_pc_base, &lp_fin, &lp_fin_start, &lp_fin_cnt, &lp_redo, &lp_stage[0], &lp_stage[1], &lp_stage[2], &lp_stage[3], &lp_stage[4], &lp_stage[5], &lp_stage[6], &lp_stage[7]}) d->release();
-        if (lp_host) (void)hipHostFree(lp_host);
-        if (tot_host) (void)hipHostFree(tot_host);
-        if (fin_host) (void)hipHostFree(fin_host);
-        if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }
-        if (ev_spliced) (void)hipEventDestroy(ev_spliced);
-        for (am_batch* w : {&ws, &ws2})
-            for (DevBuf* d : {&w->hidx, &w->unit_counts, &w->unit_offsets, &w->scan_tmp, &w->small, &w->hay_counts, &w->flags, &w->unit_first, &w->pool, &w->block_next}) d->release();
-    }
+        if (s->copy_stream) (void)hipStreamSynchronize(s->copy_stream);
+        if (s->device_bytes() > keep) return;
+        std::vector<std::unique_ptr<RpSession>> doomed;
+        std::lock_guard<std::mutex> lk(r->session_mu);
+        r->sessions.push_back(std::move(s));
+        for (;;) {
+            size_t held = 0;
+            for (const auto& q : r->sessions) held += q->device_bytes();
+            if (r->sessions.size() <= 1 || (r->sessions.size() <= 8 && held <= (4096ull << 20))) break;
+            doomed.push_back(std::move(r->sessions.front()));
+            r->sessions.erase(r->sessions.begin());
+        }
+    }      // (the lock goes first, then `doomed`)
 };
+constexpr size_t kKeepPassByPass = 2048ull << 20;      // workspaces of the pass-by-pass loops
+constexpr size_t kKeepLoop = 8192ull << 20;            // (the one-kernel loop's regions + the groups' staging of a 1-GiB batch are ~3 GiB of the 288)
 
+// points a workspace batch (it never owns its text) at a text and gets it ready for a scan
+int bind_workspace(am_batch& w, int dev, const void* text, const uint64_t* offsets, uint64_t total, uint32_t n_hay)
+{
+    w.dev = dev; w.d_text = const_cast<void*>(text); w.d_offsets = const_cast<uint64_t*>(offsets); w.owns = false; w.total = total; w.n_hay = n_hay;
+    return finish_batch(&w);
+}
 
+// The prefix sums of a pass over n1 elements: up to 2^18 in one launch (k_scan_jobs) instead of a launch or two per sum, else one scan per job in the list's order.
+int scan_pass(const ScanJobs& jobs, uint64_t n1, void* tmp, size_t tmp_bytes, hipStream_t st)
+{
+    if (n1 <= (1u << 18)) { HIP_TRY(launch_scan_jobs(jobs, st)); return AM_OK; }
+    for (uint32_t i = 0; i < jobs.n_jobs; i++) {
+        const ScanJob& j = jobs.j[i];
+        if (j.in64) HIP_TRY(launch_scan64(tmp, tmp_bytes, j.in64, j.out, j.n, st));
+        else HIP_TRY(launch_scan(tmp, tmp_bytes, j.in32, j.out, j.n, st));
+    }
+    return AM_OK;
+}
 
 // prependMatch + makeMatch + removeOverlap of one pass (Replacer.hs:252-274,191-198): one wavefront per haystack, or -- few
 // haystacks with very many matches each -- parallel over the records.  Writes kept[], hs[] and the route arrays.
@@ -292,6 +351,20 @@ static int rp_fold(RpSession& s, const am_replacer* r, bool ic, const uint8_t* t
     return AM_OK;
 }
 
+// The haystacks a pass finished, once their bytes (at `home`) and metadata have arrived on the copy stream: into the result.
+static int scatter_finished(RpSession& s, uint64_t n_fin, uint64_t total_fin, uint8_t* home, uint32_t n_hay, am_replaced* res)
+{
+    HIP_TRY(hipStreamSynchronize(s.copy_stream));
+    const RpFin* fin = (const RpFin*)s.fin_host.p;
+    for (uint64_t i = 0; i < n_fin; i++) {
+        const RpFin& f = fin[i];
+        if (f.orig >= n_hay || f.off + f.len > total_fin) return fail(AM_ERR_HIP, "replacer pass produced inconsistent metadata (internal error)");
+        if (f.status == kRpNothing) res->just[f.orig] = 0;
+        else res->text[f.orig] = am_replaced::Item{home + f.off, (size_t)f.len};
+    }
+    return AM_OK;
+}
+
 // The same loop with the text of the active haystacks kept as PIECE TABLES (am_replace.hip): no pass rewrites a text; bytes
 // move into the re-scanned windows and, once per haystack, into the result.  CaseSensitive replacers on the suffix-filter
 // route (the incremental re-scan is part of the design: after the first pass only windows are scanned).
@@ -300,50 +373,15 @@ int replacer_run_pt(const am_replacer* r, const am_batch* in, uint64_t max_lengt
     const uint32_t n_hay = in->n_hay;
     ON_DEVICE(in->dev);
     hipStream_t st; AM_TRY(get_stream(in->dev, &st));
-    RpSession* sp = nullptr;
-    { std::lock_guard<std::mutex> lk(r->session_mu); if (!r->sessions.empty()) { sp = static_cast<RpSession*>(r->sessions.back()); r->sessions.pop_back(); } }
-    if (!sp) sp = new RpSession();
-    struct Return {
-        const am_replacer* r; RpSession* sp;
-        ~Return()
-        {
-            if (sp->copy_stream) (void)hipStreamSynchronize(sp->copy_stream);
-            if (sp->device_bytes() > (2048ull << 20)) { delete sp; return; }      // keep workspaces of up to 2 GiB between calls
-            std::vector<RpSession*> doomed;
-            { std::lock_guard<std::mutex> lk(r->session_mu);
-              const_cast<am_replacer*>(r)->session_delete = [](void* p) { delete static_cast<RpSession*>(p); };
-              r->sessions.push_back(sp);
-              // at most 8 cached workspaces and at most 4 GiB of device memory in all of them (each is below 2 GiB): the oldest go first
-              for (;;) {
-                  size_t held = 0;
-                  for (void* q : r->sessions) held += static_cast<RpSession*>(q)->device_bytes();
-                  if (r->sessions.size() <= 1 || (r->sessions.size() <= 8 && held <= (4096ull << 20))) break;
-                  doomed.push_back(static_cast<RpSession*>(r->sessions.front()));
-                  r->sessions.erase(r->sessions.begin());
-              } }
-            for (RpSession* q : doomed) delete q;
-        }
-    } give_back{r, sp};
-    RpSession& s = *sp;
-    AM_TRY(s.totals.ensure(128));
-    if (!s.tot_host) {
-        if (hipHostMalloc((void**)&s.tot_host, 128, hipHostMallocPortable | hipHostMallocCoherent) != hipSuccess) { s.tot_host = nullptr; return fail(AM_ERR_OOM, "hipHostMalloc failed"); }
-        std::memset(s.tot_host, 0, 128);                  // (fine-grained: a device store is visible to the host while the kernel is still running)
-    }
-    if (!s.copy_stream && (hipStreamCreateWithFlags(&s.copy_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&s.ev_spliced, hipEventDisableTiming) != hipSuccess))
-        return fail(AM_ERR_HIP, "could not create the copy stream");
+    SessionLease lease(r, kKeepPassByPass);
+    RpSession& s = *lease.s;
+    AM_TRY(s.pinned_totals());
+    AM_TRY(s.copy_lane());
     const uint8_t* base_text = (const uint8_t*)in->d_text;               // never modified: every text piece points into it
     const uint64_t* cur_offs = in->d_offsets;                            // logical offsets of the active haystacks (lengths only after pass 0)
     uint32_t n_act = n_hay;
     int nxt = 0;
-    {
-        std::vector<uint32_t> o(n_hay); std::vector<int64_t> t(n_hay, 1);      // initialThreshold = 1 (Replacer.hs:211)
-        for (uint32_t i = 0; i < n_hay; i++) o[i] = i;
-        AM_TRY(s.first_orig.ensure(n_hay * sizeof(uint32_t))); AM_TRY(s.first_thr.ensure(n_hay * sizeof(int64_t)));
-        HIP_TRY(hipMemcpyAsync(s.first_orig.p, o.data(), n_hay * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(s.first_thr.p, t.data(), n_hay * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
+    AM_TRY(s.first_pass_arrays(n_hay, st));
     const uint32_t* cur_orig = (const uint32_t*)s.first_orig.p;
     const int64_t* cur_thr = (const int64_t*)s.first_thr.p;
     const uint32_t ov = 4u * (flavor->h.max_needle_cps ? flavor->h.max_needle_cps : 1u) + 4u;
@@ -358,10 +396,8 @@ int replacer_run_pt(const am_replacer* r, const am_batch* in, uint64_t max_lengt
     int cur_rec = 0;
     {
         res->scanned += in->total;
-        s.ws.dev = in->dev; s.ws.d_text = in->d_text; s.ws.d_offsets = in->d_offsets; s.ws.owns = false; s.ws.total = in->total; s.ws.n_hay = n_hay;
-        AM_TRY(finish_batch(&s.ws));
-        auto sink = [&](uint64_t n, Record** ptr) -> int { AM_TRY(s.recbuf[0].ensure(n * sizeof(Record))); *ptr = (Record*)s.recbuf[0].p; return AM_OK; };
-        AM_TRY(run_records(r->a, r->case_mode, &s.ws, sink, &n_rec));
+        AM_TRY(bind_workspace(s.ws, in->dev, in->d_text, in->d_offsets, in->total, n_hay));
+        AM_TRY(run_records(r->a, r->case_mode, &s.ws, records_into(s.recbuf[0]), &n_rec));
     }
     const bool trace = cfg::on(cfg::kRpTrace);
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -377,13 +413,7 @@ int replacer_run_pt(const am_replacer* r, const am_batch* in, uint64_t max_lengt
         if (!copies_pending) return AM_OK;
         HIP_TRY(hipStreamSynchronize(s.copy_stream));
         copies_pending = false;
-        for (uint64_t i = 0; i < prev_n_fin; i++) {
-            const RpFin& f = s.fin_host[i];
-            if (f.orig >= n_hay || f.off + f.len > prev_total_fin) return fail(AM_ERR_HIP, "replacer pass produced inconsistent metadata (internal error)");
-            if (f.status == kRpNothing) res->just[f.orig] = 0;
-            else res->text[f.orig] = am_replaced::Item{prev_home + f.off, (size_t)f.len};
-        }
-        return AM_OK;
+        return scatter_finished(s, prev_n_fin, prev_total_fin, prev_home, n_hay, res);
     };
 
     int cur_rf = 0; bool have_ranges = false;           // (see the ranges buffers below)
@@ -432,24 +462,15 @@ int replacer_run_pt(const am_replacer* r, const am_batch* in, uint64_t max_lengt
         const bool small = n1 <= (1u << 18);
         { Prof pr("rp_scans", st);
           if (!fused) HIP_TRY(launch_pt_count((const RpHay*)s.hs.p, (const uint32_t*)s.pt_cnt[cur_pt].p, n_act, (uint32_t*)s.pt_need.p, (uint32_t*)s.nwin.p, st));
-          if (small) {
-              ScanJobs jobs{};
-              jobs.j[0] = ScanJob{nullptr, route.len_next, (uint64_t*)s.off_next.p, n1, nullptr};
-              jobs.j[1] = ScanJob{nullptr, route.len_fin, (uint64_t*)s.off_fin.p, n1, nullptr};
-              jobs.j[2] = ScanJob{(const uint32_t*)s.pt_need.p, nullptr, (uint64_t*)s.pt_need_off.p, n1, nullptr};
-              jobs.j[3] = ScanJob{route.act, nullptr, (uint64_t*)s.act_idx.p, n1, nullptr};
-              jobs.j[4] = ScanJob{route.fin, nullptr, (uint64_t*)s.fin_idx.p, n1, nullptr};
-              jobs.j[5] = ScanJob{(const uint32_t*)s.nwin.p, nullptr, (uint64_t*)s.win_off.p, n1, nullptr};
-              jobs.n_jobs = 6;
-              HIP_TRY(launch_scan_jobs(jobs, st));
-          } else {
-              HIP_TRY(launch_scan64(s.scan_tmp.p, tmp2, route.len_next, (uint64_t*)s.off_next.p, n1, st));
-              HIP_TRY(launch_scan64(s.scan_tmp.p, tmp2, route.len_fin, (uint64_t*)s.off_fin.p, n1, st));
-              HIP_TRY(launch_scan(s.scan_tmp.p, tmp2, (const uint32_t*)s.pt_need.p, (uint64_t*)s.pt_need_off.p, n1, st));
-              HIP_TRY(launch_scan(s.scan_tmp.p, tmp2, route.act, (uint64_t*)s.act_idx.p, n1, st));
-              HIP_TRY(launch_scan(s.scan_tmp.p, tmp2, route.fin, (uint64_t*)s.fin_idx.p, n1, st));
-              HIP_TRY(launch_scan(s.scan_tmp.p, tmp2, (const uint32_t*)s.nwin.p, (uint64_t*)s.win_off.p, n1, st));
-          } }
+          ScanJobs jobs{};
+          jobs.j[0] = ScanJob{nullptr, route.len_next, (uint64_t*)s.off_next.p, n1, nullptr};
+          jobs.j[1] = ScanJob{nullptr, route.len_fin, (uint64_t*)s.off_fin.p, n1, nullptr};
+          jobs.j[2] = ScanJob{(const uint32_t*)s.pt_need.p, nullptr, (uint64_t*)s.pt_need_off.p, n1, nullptr};
+          jobs.j[3] = ScanJob{route.act, nullptr, (uint64_t*)s.act_idx.p, n1, nullptr};
+          jobs.j[4] = ScanJob{route.fin, nullptr, (uint64_t*)s.fin_idx.p, n1, nullptr};
+          jobs.j[5] = ScanJob{(const uint32_t*)s.nwin.p, nullptr, (uint64_t*)s.win_off.p, n1, nullptr};
+          jobs.n_jobs = 6;
+          AM_TRY(scan_pass(jobs, n1, s.scan_tmp.p, tmp2, st)); }
         uint64_t woffs_last = n_rec;
         { Prof pr("rp_windows", st);
           if (!small) HIP_TRY(hipMemsetAsync(s.wlen.p, 0, (n_rec + 2) * 4, st));
@@ -509,7 +530,7 @@ int replacer_run_pt(const am_replacer* r, const am_batch* in, uint64_t max_lengt
         if (n_fin) {
             uint8_t* home = nullptr;
             if (total_fin) AM_TRY(res->room((size_t)total_fin, &home));
-            AM_TRY(s.pin_meta((n_fin + 1) * sizeof(RpFin)));
+            AM_TRY(s.fin_host.ensure((n_fin + 1) * sizeof(RpFin)));
             // the finished texts are written out on the COPY stream (64 us of a 270-us pass that nothing of the next pass waits for): it starts when
             // this pass's piece lists and metadata are complete; what it reads is not touched before the next pass's host-side look at the copy
             // stream (finished_home, after the totals) -- and the next rp_route waits for the event as well
@@ -521,7 +542,7 @@ int replacer_run_pt(const am_replacer* r, const am_batch* in, uint64_t max_lengt
                                             (uint32_t)n_fin, base_text, r->t.repl, res->dev >= 0 && total_fin ? home : (uint8_t*)s.fin_text.p, mst)); }
             if (mat_main) { HIP_TRY(hipEventRecord(s.ev_spliced, st)); HIP_TRY(hipStreamWaitEvent(s.copy_stream, s.ev_spliced, 0)); }
             if (total_fin && res->dev < 0) HIP_TRY(hipMemcpyAsync(home, s.fin_text.p, total_fin, hipMemcpyDeviceToHost, s.copy_stream));
-            HIP_TRY(hipMemcpyAsync(s.fin_host, s.fin_meta.p, n_fin * sizeof(RpFin), hipMemcpyDeviceToHost, s.copy_stream));
+            HIP_TRY(hipMemcpyAsync(s.fin_host.p, s.fin_meta.p, n_fin * sizeof(RpFin), hipMemcpyDeviceToHost, s.copy_stream));
             HIP_TRY(hipEventRecord(ev_copied, s.copy_stream));
             ev_copied_used = true;
             prev_n_fin = n_fin; prev_total_fin = total_fin; prev_home = home; copies_pending = true;
@@ -537,10 +558,8 @@ int replacer_run_pt(const am_replacer* r, const am_batch* in, uint64_t max_lengt
                 HIP_TRY(launch_pt_materialise_next((const RpPiece*)s.pt_pieces[cur_pt ^ 1].p, (const uint64_t*)s.pt_start[cur_pt ^ 1].p, (const uint32_t*)s.pt_cnt[cur_pt ^ 1].p,
                                                    (const uint64_t*)s.offs[nxt].p, (uint32_t)n_next, base_text, r->t.repl, (uint8_t*)s.text[0].p, st));
                 HIP_TRY(hipMemsetAsync((uint8_t*)s.text[0].p + total_next, 0, padded_text(total_next) - (size_t)total_next, st));
-                s.ws.dev = in->dev; s.ws.d_text = s.text[0].p; s.ws.d_offsets = (uint64_t*)s.offs[nxt].p; s.ws.owns = false; s.ws.total = total_next; s.ws.n_hay = (uint32_t)n_next;
-                AM_TRY(finish_batch(&s.ws));
-                auto sink = [&](uint64_t n, Record** ptr) -> int { AM_TRY(next_records.ensure(n * sizeof(Record))); *ptr = (Record*)next_records.p; return AM_OK; };
-                AM_TRY(run_records(r->a, r->case_mode, &s.ws, sink, &next_n_rec));
+                AM_TRY(bind_workspace(s.ws, in->dev, s.text[0].p, (const uint64_t*)s.offs[nxt].p, total_next, (uint32_t)n_next));
+                AM_TRY(run_records(r->a, r->case_mode, &s.ws, records_into(next_records), &next_n_rec));
                 res->scanned += total_next;
             } else {
                 // windows around the replacements (gathered from the new piece lists) + the shifted old records; no host round trip when the
@@ -553,30 +572,24 @@ int replacer_run_pt(const am_replacer* r, const am_batch* in, uint64_t max_lengt
                     { Prof pr("rp_windows", st);
                       HIP_TRY(launch_pt_win_copy((const RpWin*)s.wins.p, (const uint64_t*)s.woffs.p, (const RpPiece*)s.pt_pieces[cur_pt ^ 1].p, (const uint64_t*)s.pt_start[cur_pt ^ 1].p,
                                                  (const uint32_t*)s.pt_cnt[cur_pt ^ 1].p, base_text, r->t.repl, (uint8_t*)s.wtext.p, n_win, total_w, padded_text(total_w), st)); }
-                    s.ws2.dev = in->dev; s.ws2.d_text = s.wtext.p; s.ws2.d_offsets = (uint64_t*)s.woffs.p; s.ws2.owns = false; s.ws2.total = total_w; s.ws2.n_hay = (uint32_t)n_win;
-                    AM_TRY(finish_batch(&s.ws2));
+                    AM_TRY(bind_workspace(s.ws2, in->dev, s.wtext.p, (const uint64_t*)s.woffs.p, total_w, (uint32_t)n_win));
                     if (lean) AM_TRY(run_records_async(r->a, r->case_mode, &s.ws2, (Record*)s.wrec.p, &n_wrec_dev, st));
-                    else {
-                        auto wsink = [&](uint64_t n, Record** ptr) -> int { AM_TRY(s.wrec.ensure(n * sizeof(Record))); *ptr = (Record*)s.wrec.p; return AM_OK; };
-                        AM_TRY(run_records(r->a, r->case_mode, &s.ws2, wsink, &n_wrec));
-                    }
+                    else AM_TRY(run_records(r->a, r->case_mode, &s.ws2, records_into(s.wrec), &n_wrec));
                     res->scanned += total_w;
                 }
                 const uint64_t wrec_bound = n_wrec_dev ? total_w : n_wrec;
                 AM_TRY(s.wrec_first.ensure((n_win + 2) * 8)); AM_TRY(s.mcount.ensure((n_next + 1) * 4)); AM_TRY(rfb_next.ensure((n_next + 1) * 8));
                 AM_TRY(next_records.ensure((n_rec + wrec_bound + 1) * sizeof(Record)));
                 Prof pr("rp_merge", st);
-                if (n_wrec_dev) HIP_TRY(launch_rp_ranges_dev((const Record*)s.wrec.p, n_wrec_dev, (uint64_t*)s.wrec_first.p, RpRoute{nullptr, nullptr, nullptr, nullptr, nullptr}, (uint32_t)n_win, st));
-                else HIP_TRY(launch_rp_ranges((const Record*)s.wrec.p, n_wrec, (uint64_t*)s.wrec_first.p, RpRoute{nullptr, nullptr, nullptr, nullptr, nullptr}, (uint32_t)n_win, st));
+                if (n_wrec_dev) HIP_TRY(launch_rp_ranges_dev((const Record*)s.wrec.p, n_wrec_dev, (uint64_t*)s.wrec_first.p, kNoRoute, (uint32_t)n_win, st));
+                else HIP_TRY(launch_rp_ranges((const Record*)s.wrec.p, n_wrec, (uint64_t*)s.wrec_first.p, kNoRoute, (uint32_t)n_win, st));
                 HIP_TRY(launch_rp_merge(false, (const Record*)records.p, (const uint64_t*)rfb.p, (const RpKept*)s.kept.p, (const RpHay*)s.hs.p, cur_offs, rt,
                                         (const uint64_t*)s.win_off.p, (const RpWin*)s.wins.p, (const Record*)s.wrec.p, (const uint64_t*)s.wrec_first.p, ov, n_act,
                                         (uint32_t*)s.mcount.p, nullptr, nullptr, st));
-                if (n_next + 1 <= (1u << 18)) {
-                    ScanJobs jobs{};
-                    jobs.j[0] = ScanJob{(const uint32_t*)s.mcount.p, nullptr, (uint64_t*)rfb_next.p, n_next + 1, nullptr};
-                    jobs.n_jobs = 1;
-                    HIP_TRY(launch_scan_jobs(jobs, st));
-                } else HIP_TRY(launch_scan(s.scan_tmp.p, tmp2, (const uint32_t*)s.mcount.p, (uint64_t*)rfb_next.p, n_next + 1, st));
+                { ScanJobs jobs{};
+                  jobs.j[0] = ScanJob{(const uint32_t*)s.mcount.p, nullptr, (uint64_t*)rfb_next.p, n_next + 1, nullptr};
+                  jobs.n_jobs = 1;
+                  AM_TRY(scan_pass(jobs, n_next + 1, s.scan_tmp.p, tmp2, st)); }
                 HIP_TRY(launch_rp_merge(true, (const Record*)records.p, (const uint64_t*)rfb.p, (const RpKept*)s.kept.p, (const RpHay*)s.hs.p, cur_offs, rt,
                                         (const uint64_t*)s.win_off.p, (const RpWin*)s.wins.p, (const Record*)s.wrec.p, (const uint64_t*)s.wrec_first.p, ov, n_act,
                                         (uint32_t*)s.mcount.p, (const uint64_t*)rfb_next.p, (Record*)next_records.p, st));
@@ -623,55 +636,20 @@ int replacer_run(const am_replacer* r, const am_batch* in, uint64_t max_length, 
     }
     ON_DEVICE(in->dev);
     hipStream_t st; AM_TRY(get_stream(in->dev, &st));
-    // take the replacer's cached workspace (or make one); it goes back at the end unless it has grown large
-    RpSession* sp = nullptr;
-    { std::lock_guard<std::mutex> lk(r->session_mu); if (!r->sessions.empty()) { sp = static_cast<RpSession*>(r->sessions.back()); r->sessions.pop_back(); } }
-    if (!sp) sp = new RpSession();
-    struct Return {
-        const am_replacer* r; RpSession* sp;
-        ~Return()
-        {
-            if (sp->copy_stream) (void)hipStreamSynchronize(sp->copy_stream);
-            if (sp->device_bytes() > (2048ull << 20)) { delete sp; return; }      // keep workspaces of up to 2 GiB between calls
-            std::vector<RpSession*> doomed;
-            { std::lock_guard<std::mutex> lk(r->session_mu);
-              const_cast<am_replacer*>(r)->session_delete = [](void* p) { delete static_cast<RpSession*>(p); };
-              r->sessions.push_back(sp);
-              // at most 8 cached workspaces and at most 4 GiB of device memory in all of them (each is below 2 GiB): the oldest go first
-              for (;;) {
-                  size_t held = 0;
-                  for (void* q : r->sessions) held += static_cast<RpSession*>(q)->device_bytes();
-                  if (r->sessions.size() <= 1 || (r->sessions.size() <= 8 && held <= (4096ull << 20))) break;
-                  doomed.push_back(static_cast<RpSession*>(r->sessions.front()));
-                  r->sessions.erase(r->sessions.begin());
-              } }
-            for (RpSession* q : doomed) delete q;
-        }
-    } give_back{r, sp};
-    RpSession& s = *sp;
-    AM_TRY(s.totals.ensure(128));
-    if (!s.tot_host) {
-        if (hipHostMalloc((void**)&s.tot_host, 128, hipHostMallocPortable | hipHostMallocCoherent) != hipSuccess) { s.tot_host = nullptr; return fail(AM_ERR_OOM, "hipHostMalloc failed"); }
-        std::memset(s.tot_host, 0, 128);                  // (fine-grained: a device store is visible to the host while the kernel is still running)
-    }
+    // the replacer's cached workspace (or a new one); it goes back at the end unless it has grown large
+    SessionLease lease(r, kKeepPassByPass);
+    RpSession& s = *lease.s;
+    AM_TRY(s.pinned_totals());
     // pass 0 reads the caller's batch in place; afterwards the text ping-pongs between s.text[0] and s.text[1]
     const uint8_t* cur_text = (const uint8_t*)in->d_text;
     const uint64_t* cur_offs = in->d_offsets;
     uint64_t total = in->total;
     uint32_t n_act = n_hay;
     int nxt = 0;
-    DevBuf& first_orig = s.first_orig; DevBuf& first_thr = s.first_thr;
-    {
-        std::vector<uint32_t> o(n_hay); std::vector<int64_t> t(n_hay, 1);      // initialThreshold = 1 (Replacer.hs:211)
-        for (uint32_t i = 0; i < n_hay; i++) o[i] = i;
-        AM_TRY(first_orig.ensure(n_hay * sizeof(uint32_t))); AM_TRY(first_thr.ensure(n_hay * sizeof(int64_t)));
-        HIP_TRY(hipMemcpy(first_orig.p, o.data(), n_hay * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(first_thr.p, t.data(), n_hay * sizeof(int64_t), hipMemcpyHostToDevice));
-    }
-    const uint32_t* cur_orig = (const uint32_t*)first_orig.p;
-    const int64_t* cur_thr = (const int64_t*)first_thr.p;
-    if (!s.copy_stream && (hipStreamCreateWithFlags(&s.copy_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&s.ev_spliced, hipEventDisableTiming) != hipSuccess))
-        return fail(AM_ERR_HIP, "could not create the copy stream");
+    AM_TRY(s.first_pass_arrays(n_hay, st));
+    const uint32_t* cur_orig = (const uint32_t*)s.first_orig.p;
+    const int64_t* cur_thr = (const int64_t*)s.first_thr.p;
+    AM_TRY(s.copy_lane());
     // Incremental re-scan (am_replace.hip): after the first pass only windows around the replacements are scanned and
     // merged with the shifted records of the previous pass.  Needs the suffix-filter kernel's position-local semantics
     // (automata with the empty needle re-scan everything); AM_RP_FULL_SCANS=1 turns it off (A/B, tests).
@@ -697,12 +675,8 @@ int replacer_run(const am_replacer* r, const am_batch* in, uint64_t max_length, 
         if (have_inc) { n_rec = inc_n_rec; have_inc = false; }
         else {
             res->scanned += total;
-            s.ws.dev = in->dev;
-            s.ws.d_text = const_cast<uint8_t*>(cur_text); s.ws.d_offsets = const_cast<uint64_t*>(cur_offs); s.ws.owns = false;
-            s.ws.total = total; s.ws.n_hay = n_act;
-            AM_TRY(finish_batch(&s.ws));
-            auto sink = [&](uint64_t n, Record** ptr) -> int { AM_TRY(records.ensure(n * sizeof(Record))); *ptr = (Record*)records.p; return AM_OK; };
-            AM_TRY(run_records(r->a, r->case_mode, &s.ws, sink, &n_rec));
+            AM_TRY(bind_workspace(s.ws, in->dev, cur_text, cur_offs, total, n_act));
+            AM_TRY(run_records(r->a, r->case_mode, &s.ws, records_into(records), &n_rec));
         }
         t_scan += now() - t0; t0 = now();
         // ---- per-haystack fold of the records
@@ -734,24 +708,15 @@ int replacer_run(const am_replacer* r, const am_batch* in, uint64_t max_length, 
             HIP_TRY(launch_rp_win_count((const RpHay*)s.hs.p, n_act, (uint32_t*)s.nwin.p, st));
         }
         { Prof pr("rp_scans", st);
-          if (small) {
-              ScanJobs jobs{};
-              jobs.j[0] = ScanJob{nullptr, route.len_next, (uint64_t*)s.off_next.p, n1, nullptr};
-              jobs.j[1] = ScanJob{nullptr, route.len_fin, (uint64_t*)s.off_fin.p, n1, nullptr};
-              jobs.j[2] = ScanJob{route.tiles, nullptr, (uint64_t*)s.tile_off.p, n1, nullptr};
-              jobs.j[3] = ScanJob{route.act, nullptr, (uint64_t*)s.act_idx.p, n1, nullptr};
-              jobs.j[4] = ScanJob{route.fin, nullptr, (uint64_t*)s.fin_idx.p, n1, nullptr};
-              jobs.n_jobs = 5;
-              if (try_inc) { jobs.j[5] = ScanJob{(const uint32_t*)s.nwin.p, nullptr, (uint64_t*)s.win_off.p, n1, nullptr}; jobs.n_jobs = 6; }
-              HIP_TRY(launch_scan_jobs(jobs, st));
-          } else {
-              HIP_TRY(launch_scan64(s.scan_tmp.p, tmp2, route.len_next, (uint64_t*)s.off_next.p, n1, st));
-              HIP_TRY(launch_scan64(s.scan_tmp.p, tmp2, route.len_fin, (uint64_t*)s.off_fin.p, n1, st));
-              HIP_TRY(launch_scan(s.scan_tmp.p, tmp2, route.tiles, (uint64_t*)s.tile_off.p, n1, st));
-              HIP_TRY(launch_scan(s.scan_tmp.p, tmp2, route.act, (uint64_t*)s.act_idx.p, n1, st));
-              HIP_TRY(launch_scan(s.scan_tmp.p, tmp2, route.fin, (uint64_t*)s.fin_idx.p, n1, st));
-              if (try_inc) HIP_TRY(launch_scan(s.scan_tmp.p, tmp2, (const uint32_t*)s.nwin.p, (uint64_t*)s.win_off.p, n1, st));
-          } }
+          ScanJobs jobs{};
+          jobs.j[0] = ScanJob{nullptr, route.len_next, (uint64_t*)s.off_next.p, n1, nullptr};
+          jobs.j[1] = ScanJob{nullptr, route.len_fin, (uint64_t*)s.off_fin.p, n1, nullptr};
+          jobs.j[2] = ScanJob{route.tiles, nullptr, (uint64_t*)s.tile_off.p, n1, nullptr};
+          jobs.j[3] = ScanJob{route.act, nullptr, (uint64_t*)s.act_idx.p, n1, nullptr};
+          jobs.j[4] = ScanJob{route.fin, nullptr, (uint64_t*)s.fin_idx.p, n1, nullptr};
+          jobs.n_jobs = 5;
+          if (try_inc) { jobs.j[5] = ScanJob{(const uint32_t*)s.nwin.p, nullptr, (uint64_t*)s.win_off.p, n1, nullptr}; jobs.n_jobs = 6; }
+          AM_TRY(scan_pass(jobs, n1, s.scan_tmp.p, tmp2, st)); }
         if (try_inc) {
             Prof pr("rp_windows", st);
             if (!small) HIP_TRY(hipMemsetAsync(s.wlen.p, 0, (n_rec + 2) * 4, st));     // at most one window per record; unused entries scan as zeros
@@ -788,21 +753,11 @@ int replacer_run(const am_replacer* r, const am_batch* in, uint64_t max_length, 
         // ---- finished haystacks go home: the copy runs on its own stream, next to the window scans below
         uint8_t* home = nullptr;
         if (total_fin) AM_TRY(res->room((size_t)total_fin, &home));
-        AM_TRY(s.pin_meta((n_fin + 1) * sizeof(RpFin)));
+        AM_TRY(s.fin_host.ensure((n_fin + 1) * sizeof(RpFin)));
         HIP_TRY(hipEventRecord(s.ev_spliced, st));
         HIP_TRY(hipStreamWaitEvent(s.copy_stream, s.ev_spliced, 0));
         if (total_fin) HIP_TRY(hipMemcpyAsync(home, s.fin_text.p, total_fin, hipMemcpyDefault, s.copy_stream));      // the slab is pinned host memory, or device memory for results that stay there
-        if (n_fin) HIP_TRY(hipMemcpyAsync(s.fin_host, s.fin_meta.p, n_fin * sizeof(RpFin), hipMemcpyDeviceToHost, s.copy_stream));
-        auto finished_home = [&]() -> int {
-            HIP_TRY(hipStreamSynchronize(s.copy_stream));
-            for (uint64_t i = 0; i < n_fin; i++) {
-                const RpFin& f = s.fin_host[i];
-                if (f.orig >= n_hay || f.off + f.len > total_fin) return fail(AM_ERR_HIP, "replacer pass produced inconsistent metadata (internal error)");
-                if (f.status == kRpNothing) res->just[f.orig] = 0;
-                else res->text[f.orig] = am_replaced::Item{home + f.off, (size_t)f.len};
-            }
-            return AM_OK;
-        };
+        if (n_fin) HIP_TRY(hipMemcpyAsync(s.fin_host.p, s.fin_meta.p, n_fin * sizeof(RpFin), hipMemcpyDeviceToHost, s.copy_stream));
         t_splice += now() - t0; t0 = now();
         t_home += now() - t0; t0 = now();
         // ---- next pass's records without a full scan: windows around the replacements + the shifted old records
@@ -812,29 +767,24 @@ int replacer_run(const am_replacer* r, const am_batch* in, uint64_t max_length, 
             { Prof pr("rp_windows", st);
               HIP_TRY(launch_rp_win_copy((const RpWin*)s.wins.p, (const uint64_t*)s.woffs.p, text_next, (uint8_t*)s.wtext.p, n_win, st));
               HIP_TRY(hipMemsetAsync((uint8_t*)s.wtext.p + total_w, 0, padded_text(total_w) - (size_t)total_w, st)); }
-            s.ws2.dev = in->dev;
-            s.ws2.d_text = s.wtext.p; s.ws2.d_offsets = (uint64_t*)s.woffs.p; s.ws2.owns = false; s.ws2.total = total_w; s.ws2.n_hay = (uint32_t)n_win;
-            AM_TRY(finish_batch(&s.ws2));
+            AM_TRY(bind_workspace(s.ws2, in->dev, s.wtext.p, (const uint64_t*)s.woffs.p, total_w, (uint32_t)n_win));
             uint64_t n_wrec = 0;
-            auto wsink = [&](uint64_t n, Record** ptr) -> int { AM_TRY(s.wrec.ensure(n * sizeof(Record))); *ptr = (Record*)s.wrec.p; return AM_OK; };
-            AM_TRY(run_records(r->a, r->case_mode, &s.ws2, wsink, &n_wrec));
+            AM_TRY(run_records(r->a, r->case_mode, &s.ws2, records_into(s.wrec), &n_wrec));
             res->scanned += total_w;
             AM_TRY(s.wrec.ensure(sizeof(Record)));
             AM_TRY(s.wrec_first.ensure((n_win + 1) * 8)); AM_TRY(s.mcount.ensure((n_next + 1) * 4)); AM_TRY(s.moff.ensure((n_next + 1) * 8));
             DevBuf& next_records = s.recbuf[cur_rec ^ 1];
             AM_TRY(next_records.ensure((n_rec + n_wrec + 1) * sizeof(Record)));          // upper bound; the exact count arrives with the end-of-pass sync
             Prof pr("rp_merge", st);
-            HIP_TRY(launch_rp_ranges((const Record*)s.wrec.p, n_wrec, (uint64_t*)s.wrec_first.p, RpRoute{nullptr, nullptr, nullptr, nullptr, nullptr}, (uint32_t)n_win, st));
+            HIP_TRY(launch_rp_ranges((const Record*)s.wrec.p, n_wrec, (uint64_t*)s.wrec_first.p, kNoRoute, (uint32_t)n_win, st));
             HIP_TRY(hipMemsetAsync((uint32_t*)s.mcount.p + n_next, 0, 4, st));
             HIP_TRY(launch_rp_merge(false, (const Record*)records.p, (const uint64_t*)s.rec_first.p, (const RpKept*)s.kept.p, (const RpHay*)s.hs.p, cur_offs, rt,
                                     (const uint64_t*)s.win_off.p, (const RpWin*)s.wins.p, (const Record*)s.wrec.p, (const uint64_t*)s.wrec_first.p, ov, n_act,
                                     (uint32_t*)s.mcount.p, nullptr, nullptr, st));
-            if (n_next + 1 <= (1u << 18)) {
-                ScanJobs jobs{};
-                jobs.j[0] = ScanJob{(const uint32_t*)s.mcount.p, nullptr, (uint64_t*)s.moff.p, n_next + 1, nullptr};
-                jobs.n_jobs = 1;
-                HIP_TRY(launch_scan_jobs(jobs, st));
-            } else HIP_TRY(launch_scan(s.scan_tmp.p, tmp2, (const uint32_t*)s.mcount.p, (uint64_t*)s.moff.p, n_next + 1, st));
+            { ScanJobs jobs{};
+              jobs.j[0] = ScanJob{(const uint32_t*)s.mcount.p, nullptr, (uint64_t*)s.moff.p, n_next + 1, nullptr};
+              jobs.n_jobs = 1;
+              AM_TRY(scan_pass(jobs, n_next + 1, s.scan_tmp.p, tmp2, st)); }
             HIP_TRY(launch_rp_merge(true, (const Record*)records.p, (const uint64_t*)s.rec_first.p, (const RpKept*)s.kept.p, (const RpHay*)s.hs.p, cur_offs, rt,
                                     (const uint64_t*)s.win_off.p, (const RpWin*)s.wins.p, (const Record*)s.wrec.p, (const uint64_t*)s.wrec_first.p, ov, n_act,
                                     (uint32_t*)s.mcount.p, (const uint64_t*)s.moff.p, (Record*)next_records.p, st));
@@ -844,7 +794,7 @@ int replacer_run(const am_replacer* r, const am_batch* in, uint64_t max_length, 
         HIP_TRY(hipStreamSynchronize(st));            // end of pass: the merged record count (if any) is on the host now
         if (have_inc) inc_n_rec = s.tot_host[7];
         t_scan += now() - t0; t0 = now();
-        AM_TRY(finished_home());
+        AM_TRY(scatter_finished(s, n_fin, total_fin, home, n_hay, res));
         t_home += now() - t0; t0 = now();
         cur_rec ^= 1;
         cur_text = (const uint8_t*)s.text[nxt].p; cur_offs = (const uint64_t*)s.offs[nxt].p;
@@ -888,41 +838,15 @@ static int replacer_run_loop(const am_replacer* r, const am_batch* in, uint64_t 
     if (wcap64 > 4096 || wcap64 * n_hay > (1ull << 30) || in->total >= (1ull << 40)) return AM_OK;
     ON_DEVICE(in->dev);
     hipStream_t st; AM_TRY(get_stream(in->dev, &st));
-    RpSession* sp = nullptr;
-    { std::lock_guard<std::mutex> lk(r->session_mu); if (!r->sessions.empty()) { sp = static_cast<RpSession*>(r->sessions.back()); r->sessions.pop_back(); } }
-    if (!sp) sp = new RpSession();
-    struct Return {
-        const am_replacer* r; RpSession* sp;
-        ~Return()
-        {
-            if (sp->copy_stream) (void)hipStreamSynchronize(sp->copy_stream);
-            if (sp->device_bytes() > (8192ull << 20)) { delete sp; return; }      // (the loop's regions + the groups' staging of a 1-GiB batch are ~3 GiB of the 288)
-            std::vector<RpSession*> doomed;
-            { std::lock_guard<std::mutex> lk(r->session_mu);
-              const_cast<am_replacer*>(r)->session_delete = [](void* p) { delete static_cast<RpSession*>(p); };
-              r->sessions.push_back(sp);
-              for (;;) {
-                  size_t held = 0;
-                  for (void* q : r->sessions) held += static_cast<RpSession*>(q)->device_bytes();
-                  if (r->sessions.size() <= 1 || (r->sessions.size() <= 8 && held <= (4096ull << 20))) break;
-                  doomed.push_back(static_cast<RpSession*>(r->sessions.front()));
-                  r->sessions.erase(r->sessions.begin());
-              } }
-            for (RpSession* q : doomed) delete q;
-        }
-    } give_back{r, sp};
-    RpSession& s = *sp;
+    SessionLease lease(r, kKeepLoop);
+    RpSession& s = *lease.s;
     const bool trace = cfg::on(cfg::kRpTrace);
     auto say = [&](const char* what) { if (trace) { (void)hipStreamSynchronize(st); std::fprintf(stderr, "[am_replacer loop] %s\n", what); std::fflush(stderr); } };
     // the first (and only full) scan
     say("first scan");
     uint64_t n_rec = 0;
-    s.ws.dev = in->dev; s.ws.d_text = in->d_text; s.ws.d_offsets = in->d_offsets; s.ws.owns = false; s.ws.total = in->total; s.ws.n_hay = n_hay;
-    AM_TRY(finish_batch(&s.ws));
-    {
-        auto sink = [&](uint64_t n, Record** ptr) -> int { AM_TRY(s.recbuf[0].ensure((n + 1) * sizeof(Record))); *ptr = (Record*)s.recbuf[0].p; return AM_OK; };
-        AM_TRY(run_records(r->a, r->case_mode, &s.ws, sink, &n_rec));
-    }
+    AM_TRY(bind_workspace(s.ws, in->dev, in->d_text, in->d_offsets, in->total, n_hay));
+    AM_TRY(run_records(r->a, r->case_mode, &s.ws, records_into(s.recbuf[0], 1), &n_rec));
     if (n_rec >= (1ull << 26)) return AM_OK;                 // (the regions below would not fit: the pass-by-pass loop scans again)
     const uint64_t n1 = (uint64_t)n_hay + 1;
     const uint64_t rec_total = 4 * n_rec + 128ull * n_hay, pc_total = 8 * n_rec + 128ull * n_hay;      // = the sums of k_rp_loop_caps' region sizes
@@ -936,7 +860,7 @@ static int replacer_run_loop(const am_replacer* r, const am_batch* in, uint64_t 
     if (scan_temp_bytes(n1, &t32) != hipSuccess) return fail(AM_ERR_HIP, "scan sizing failed");
     AM_TRY(s.scan_tmp.ensure(t32 + 16));
     { Prof pr("rp_ranges", st);
-      HIP_TRY(launch_rp_ranges((const Record*)s.recbuf[0].p, n_rec, (uint64_t*)s.rec_first.p, RpRoute{nullptr, nullptr, nullptr, nullptr, nullptr}, n_hay, st)); }
+      HIP_TRY(launch_rp_ranges((const Record*)s.recbuf[0].p, n_rec, (uint64_t*)s.rec_first.p, kNoRoute, n_hay, st)); }
     HIP_TRY(hipMemsetAsync(s.lp_ctrl.p, 0, 128, st));
     { Prof pr("rp_scans", st);
       HIP_TRY(launch_rp_loop_caps((const uint64_t*)s.rec_first.p, n_hay, (uint32_t*)s.lp_cap_r.p, (uint32_t*)s.lp_cap_p.p, (uint32_t*)s.lp_ctrl.p + 6, st));
@@ -946,8 +870,8 @@ static int replacer_run_loop(const am_replacer* r, const am_batch* in, uint64_t 
     if (sw != 1) {
         // a wavefront walks its haystack's whole record list in every pass: one document with very many matches would be the tail of the launch
         // (the pass-by-pass loop folds such lists in parallel over the records)
-        AM_TRY(s.pin_loop(64));
-        uint32_t* c = (uint32_t*)s.lp_host;
+        AM_TRY(s.lp_host.ensure(64));
+        uint32_t* c = (uint32_t*)s.lp_host.p;
         HIP_TRY(hipMemcpyAsync(c, s.lp_ctrl.p, 64, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (c[6] > 4096u) return AM_OK;
@@ -978,14 +902,13 @@ static int replacer_run_loop(const am_replacer* r, const am_batch* in, uint64_t 
     // range of them (RpLoop::h_first).
     uint32_t n_groups = 1;
     if (res->dev < 0 && n_hay >= 4096 && in->total >= (64ull << 20) && !a.pad && !cfg::on(cfg::kRpMatMain)) { n_groups = n_hay / 2048u; if (n_groups > 8) n_groups = 8; }
-    if (n_groups > 1 && !s.copy_stream && (hipStreamCreateWithFlags(&s.copy_stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&s.ev_spliced, hipEventDisableTiming) != hipSuccess))
-        return fail(AM_ERR_HIP, "could not create the copy stream");
+    if (n_groups > 1) AM_TRY(s.copy_lane());
     const size_t out_bytes = (size_t)n_hay * sizeof(RpLoopOut);
     const size_t tab_bytes = (size_t)n_hay * (sizeof(RpFin) + 8 + 4) + 64;
-    AM_TRY(s.pin_loop(64 + out_bytes + tab_bytes));
-    uint32_t* ctrl_h = (uint32_t*)s.lp_host;
-    RpLoopOut* out_h = (RpLoopOut*)((uint8_t*)s.lp_host + 64);
-    RpFin* fin_h = (RpFin*)((uint8_t*)s.lp_host + 64 + out_bytes);
+    AM_TRY(s.lp_host.ensure(64 + out_bytes + tab_bytes));
+    uint32_t* ctrl_h = (uint32_t*)s.lp_host.p;
+    RpLoopOut* out_h = (RpLoopOut*)((uint8_t*)s.lp_host.p + 64);
+    RpFin* fin_h = (RpFin*)((uint8_t*)s.lp_host.p + 64 + out_bytes);
     uint64_t* fstart_h = (uint64_t*)(fin_h + n_hay);
     uint32_t* fcnt_h = (uint32_t*)(fstart_h + n_hay);
     AM_TRY(s.lp_fin.ensure((size_t)n_hay * sizeof(RpFin))); AM_TRY(s.lp_fin_start.ensure((size_t)n_hay * 8)); AM_TRY(s.lp_fin_cnt.ensure((size_t)n_hay * 4));
@@ -1172,9 +1095,6 @@ static int replacer_run_groups(const am_replacer* r, const am_batch* in, uint64_
         for (const Slab& sl : x.part.slabs) res->slabs.push_back(sl);      // the result keeps the group's pinned slabs (its texts point into them)
         x.part.slabs.clear();
         res->passes = std::max(res->passes, x.part.passes); res->scanned += x.part.scanned; res->spliced += x.part.spliced;
-        for (DevBuf* d : {&x.b.hidx, &x.b.unit_counts, &x.b.unit_offsets, &x.b.scan_tmp, &x.b.small, &x.b.hay_counts, &x.b.flags, &x.b.unit_first, &x.b.pool, &x.b.block_next,
-                          &x.b.sparse, &x.b.dense_counts, &x.b.dense_offsets, &x.b.dense_out}) d->release();
-        x.offs.release();
     }
     return rc;
 }
@@ -1229,10 +1149,8 @@ extern "C" int am_run_priority(const am_replacer* r, const am_slice* hay, size_t
     const uint32_t n = (uint32_t)n_hay;
     const uint64_t n1 = (uint64_t)n + 1;
     DevBuf records, rec_first, kept, hs, nk, off, thr, best, out, tmp;
-    struct Release { std::vector<DevBuf*> l; ~Release() { for (DevBuf* d : l) d->release(); } } rel{{&records, &rec_first, &kept, &hs, &nk, &off, &thr, &best, &out, &tmp}};
     uint64_t n_rec = 0;
-    auto sink = [&](uint64_t k, Record** ptr) -> int { AM_TRY(records.ensure(k * sizeof(Record))); *ptr = (Record*)records.p; return AM_OK; };
-    AM_TRY(run_records(r->a, r->case_mode, b, sink, &n_rec));
+    AM_TRY(run_records(r->a, r->case_mode, b, records_into(records), &n_rec));
     AM_TRY(records.ensure(sizeof(Record)));
     AM_TRY(rec_first.ensure(n1 * 8)); AM_TRY(kept.ensure((n_rec + 1) * sizeof(RpKept))); AM_TRY(hs.ensure(n1 * sizeof(RpHay)));
     AM_TRY(nk.ensure(n1 * 4)); AM_TRY(off.ensure(n1 * 8)); AM_TRY(thr.ensure(n1 * 8)); AM_TRY(best.ensure(n1 * 8));
@@ -1242,7 +1160,7 @@ extern "C" int am_run_priority(const am_replacer* r, const am_slice* hay, size_t
     HIP_TRY(hipMemcpyAsync(thr.p, thresholds, (size_t)n * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync((uint32_t*)nk.p + n, 0, 4, st));
     RpRoute route{nullptr, nullptr, (uint32_t*)nk.p, nullptr, nullptr};
-    HIP_TRY(launch_rp_ranges((const Record*)records.p, n_rec, (uint64_t*)rec_first.p, RpRoute{nullptr, nullptr, nullptr, nullptr, nullptr}, n, st));
+    HIP_TRY(launch_rp_ranges((const Record*)records.p, n_rec, (uint64_t*)rec_first.p, kNoRoute, n, st));
     HIP_TRY(launch_rp_pass(r->case_mode == AM_IGNORE_CASE, r->t, (const uint8_t*)b->d_text, b->d_offsets, (const Record*)records.p, (const uint64_t*)rec_first.p,
                            (const int64_t*)thr.p, UINT64_MAX, (RpKept*)kept.p, (RpHay*)hs.p, route, n, 1u, st));
     HIP_TRY(launch_scan(tmp.p, tmp_bytes, (const uint32_t*)nk.p, (uint64_t*)off.p, n1, st));

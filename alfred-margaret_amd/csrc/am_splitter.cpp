@@ -29,7 +29,6 @@ std::atomic<uint32_t> g_split_rounds{0};                  // doubling rounds of 
 
 struct Bufs {
     DevBuf start, head, kept, kidx, scan_tmp, rec_first, flag, jump0, jump1;
-    ~Bufs() { for (DevBuf* d : {&start, &head, &kept, &kidx, &scan_tmp, &rec_first, &flag, &jump0, &jump1}) d->release(); }
 };
 
 int read_u64(const void* d_src, uint64_t* out, hipStream_t st)
@@ -96,10 +95,7 @@ extern "C" int am_split_batch(const am_splitter* s, int case_mode, const am_batc
     hipStream_t st; AM_TRY(get_stream(b->dev, &st));
     RecordArray ra(b->dev);
     uint64_t n_rec = 0;
-    if (b->total != 0) {
-        auto sink = [&](uint64_t n, Record** ptr) -> int { AM_TRY(ra.ensure(n * sizeof(Record))); *ptr = (Record*)ra.p; return AM_OK; };
-        AM_TRY(run_records(s->a, case_mode, b, sink, &n_rec));
-    }
+    if (b->total != 0) AM_TRY(run_records(s->a, case_mode, b, records_into(ra), &n_rec));
     const SplitIn in{(const Record*)ra.p, n_rec, (const uint8_t*)b->d_text, b->d_offsets, b->total, b->n_hay, s->sep_bytes, s->sep_cps};
     Bufs w;
     AM_TRY(w.start.ensure((n_rec + 1) * 8));
@@ -116,7 +112,7 @@ extern "C" int am_split_batch(const am_splitter* s, int case_mode, const am_batc
     HIP_TRY(hipMemsetAsync(flag, 0, 64, st));
     { Prof pr("split_start", st);
       HIP_TRY(launch_split_start(case_mode == AM_IGNORE_CASE, in, (uint64_t*)w.start.p, (uint8_t*)w.head.p, kept, st)); }
-    HIP_TRY(launch_rp_ranges(in.recs, n_rec, (uint64_t*)w.rec_first.p, RpRoute{nullptr, nullptr, nullptr, nullptr, nullptr}, b->n_hay, st));
+    HIP_TRY(launch_rp_ranges(in.recs, n_rec, (uint64_t*)w.rec_first.p, kNoRoute, b->n_hay, st));
     const long lim = cfg::get(cfg::kSplitChainLimit);
     { Prof pr("split_walk", st);
       HIP_TRY(launch_split_walk(in.recs, n_rec, (const uint64_t*)w.start.p, (const uint8_t*)w.head.p, kept, lim > 0 ? (uint32_t)std::min<long>(lim, 1L << 30) : kSplitChainLimit, flag, st)); }
@@ -213,12 +209,7 @@ extern "C" const am_fragment* am_fragments_data(am_fragments* f)
     return fetch(f, f->h_data, f->data_fetched, f->data, f->n_frag);
 }
 
-extern "C" void am_fragments_free(am_fragments* f)
-{
-    if (!f) return;
-    f->data.release(); f->offsets.release();
-    delete f;
-}
+extern "C" void am_fragments_free(am_fragments* f) { delete f; }
 
 extern "C" int am_batch_from_fragments(const am_batch* src, const am_fragments* f, am_batch** out)
 {
@@ -235,7 +226,6 @@ extern "C" int am_batch_from_fragments(const am_batch* src, const am_fragments* 
     nb->dev = src->dev; nb->owns = true;
     const uint64_t n = f->n_frag;
     DevBuf lens, src_at, scan_tmp;
-    struct Release { DevBuf &a, &b, &c; ~Release() { a.release(); b.release(); c.release(); } } rel{lens, src_at, scan_tmp};
     AM_TRY(lens.ensure((n + 1) * 8));
     AM_TRY(src_at.ensure((n + 1) * 8));
     AM_TRY(nb->offs_buf.ensure((n + 1) * 8));

@@ -16,6 +16,10 @@ extern "C" {
 AM_API int am_debug_set(const char* name, long value);
 /* Page-locked staging memory of all threads, living or parked (the leak test). */
 AM_API uint64_t am_debug_pinned_bytes(void);
+/* Bytes of device memory in the library's own buffers (csrc/am_host.h DevBuf: batches and their workspaces, the tables of replacers and needle ids, cached
+ * Replacer sessions, fragments): back at its earlier value once every handle and result is destroyed and am_release_device_memory was called (the leak test).
+ * Automaton images, record arrays and result slabs are not counted. */
+AM_API uint64_t am_debug_device_buffer_bytes(void);
 /* Cycle sums per k_sf phase / per-wavefront record counts of launches made under AM_SF_TRACE (tools/phase_timing.py). */
 AM_API int am_debug_sf_phase_cycles(uint64_t* out5);
 AM_API int am_debug_sf_wave_records(uint64_t* out, size_t n_waves);

@@ -913,6 +913,104 @@ def test_threads_started_per_call_do_not_leak_pinned_memory():
     assert seen[-1] < (256 << 20)
 
 
+def _device_buffer_bytes():
+    """Bytes in the library's own device buffers after am_release_device_memory (include/am_debug.h am_debug_device_buffer_bytes)."""
+    import gc
+    gc.collect()                                         # handles of earlier tests that are only waiting for the collector
+    lib = am.api.libam()
+    am.api.check(lib.am_release_device_memory())
+    return int(lib.am_debug_device_buffer_bytes())
+
+
+def _device_buffer_baseline():
+    """_device_buffer_bytes() with nothing left that a later call could take over and free: the one-shot batches of threads that have ended (earlier tests started
+    some) wait for the next thread that asks for one (am_abi.cpp Orphans) -- this thread, once am_release_device_memory has taken its own away.  So it asks, and
+    releases, until the reading no longer falls."""
+    a = am.Automaton(["x"])
+    v = _device_buffer_bytes()
+    while True:
+        assert int(a.count_matches(0, ["x"])[0]) == 1      # a one-shot call: adopts a parked batch, or makes one
+        w = _device_buffer_bytes()
+        if w == v:
+            return v
+        v = w
+
+
+def test_every_handle_gives_back_its_device_buffers():
+    """Every owner of device buffers, once: automaton scans, containsAll on both routes, per-needle counts, the fold checksum, Splitter + batch from fragments,
+    am_run_priority and the Replacer's four loops.  With every handle and result destroyed the library holds exactly what it held before."""
+    lib = am.api.libam()
+    v0 = _device_buffer_baseline()
+    rng = random.Random(41)
+    needles = ["tshirt", "shirts", "shorts", "ab", "bca"]
+    hays = ["short tshirts and shorts abcab " * 60, "", "bcabca", "shirts" * 300]
+    a, o = am.Automaton(needles), oracle.Machine(needles)
+    exp = oracle_triples(o, 0, hays)
+    recs = a.run_records(0, hays)
+    assert expand_records(o.values_off(), o.values(), recs["haystack"], recs["state"], recs["end_pos"]) == exp
+    assert [int(c) for c in a.count_matches(0, hays)] == [o.count_matches(0, h) for h in hays]
+    s = am.Searcher(0, needles)
+    assert [bool(x) for x in s.contains_any_batch(hays)] == [o.contains_any(0, h) for h in hays]
+    want_all = [all(n in h for n in needles) for h in hays]
+    for no_ids_scan in (0, 1):
+        am.debug_set("AM_NO_IDS_SCAN", no_ids_scan)
+        assert [bool(x) for x in s.contains_all_batch(hays)] == want_all
+    am.debug_set("AM_NO_IDS_SCAN", -1)
+    counts = a.count_by_needle(0, hays)
+    assert [int(c) for c in counts] == [sum(1 for _, _, v in exp if v == i) for i in range(len(needles))]
+    # the fold checksum of a result in HBM
+    sl = am.api._Slices(hays)
+    b, m = C.c_void_p(), C.c_void_p()
+    am.api.check(lib.am_batch_upload(sl.arr, sl.n, C.byref(b)))
+    am.api.check(lib.am_run_batch(a.device, 0, b, C.byref(m)))
+    vt = am.api.ValuesTable(a)
+    _, fold_counts = vt.fold_hash(m, len(hays))
+    assert [int(c) for c in fold_counts] == [sum(1 for h, _, _ in exp if h == i) for i in range(len(hays))]
+    lib.am_matches_free(m)
+    # Splitter: fragments, and a batch made of them
+    sp = am.Splitter("ab")
+    nb, line_offs = sp.lines_batch(b)
+    assert [int(x) for x in np.diff(line_offs)] == [h.count("ab") + 1 for h in hays]
+    assert sp.split_batch_device(hays) == [[f.encode() for f in h.split("ab")] for h in hays]
+    lib.am_batch_destroy(nb); lib.am_batch_destroy(b)
+    # the Replacer: one pass of the fold, then every loop
+    pairs = [("".join(rng.choice("abcd") for _ in range(3)), "".join(rng.choice("XY") for _ in range(rng.randint(0, 3)))) for _ in range(20)]
+    rhays = ["".join(rng.choice("abcd ") for _ in range(rng.choice((50, 900, 4000)))) for _ in range(120)]
+    r, ro = am.Replacer(0, pairs), oracle.Replacer(0, pairs)
+    rexp = [ro.run(h) for h in rhays]
+    best, _ = r.run_priority(rhays[:8], [1] * 8)
+    assert len(best) == 8
+    # (one kernel; piece tables; fewer than 64 haystacks: the splicing loop; three groups of 40, each through the splicing loop on a thread of its own)
+    for n, switches in ((120, {"AM_RP_LOOP": 1}), (120, {"AM_RP_LOOP": 0, "AM_RP_PIECES": 1}), (40, {"AM_RP_LOOP": 0}), (120, {"AM_RP_LOOP": 0, "AM_RP_GROUPS": 3})):
+        for k, v in switches.items():
+            am.debug_set(k, v)
+        assert r.run_batch(rhays[:n]) == rexp[:n], switches
+        for k in switches:
+            am.debug_set(k, -1)
+    assert _device_buffer_bytes() > v0                    # (the handles still hold their tables and the replacer its sessions)
+    del a, s, vt, sp, r
+    assert _device_buffer_bytes() == v0
+
+
+def test_empty_needle_replacer_sessions_leave_nothing_behind():
+    """A replacer with the empty needle runs the splicing loop, whose scans fill the dense-pass buffers of the session's workspace batch (sparse, dense_counts,
+    dense_offsets, dense_out): they go with the session, like everything else in it."""
+    pairs = [("", "-"), ("ab", "c")]
+    rng = random.Random(43)
+    hays = ["".join(rng.choice("abx") for _ in range(rng.choice((0, 1, 2, 40, 700, 5000)))) for _ in range(40)]
+    o = oracle.Replacer(0, pairs)
+    exp = [o.run(h) for h in hays]
+    v0 = _device_buffer_baseline()
+    seen = []
+    for _ in range(4):
+        r = am.Replacer(0, pairs)
+        assert r.run_batch(hays) == exp
+        del r
+        seen.append(_device_buffer_bytes())
+        assert seen[-1] == v0, (v0, seen)
+    assert len(set(seen)) == 1, seen
+
+
 @pytest.mark.parametrize("segment_kib", [64, 300])
 def test_am_run_in_segments_equals_the_call_in_one_piece(segment_kib):
     """am_run on a large host batch goes up in segments of whole haystacks; a segment's records are rebased on the device and travel back while the next segment is
