@@ -34,6 +34,7 @@ class Slice(C.Structure):          # am_slice
 
 MATCH_DTYPE = np.dtype([("end_pos", np.uint64), ("haystack", np.uint32), ("state", np.uint32)])   # am_match
 FRAGMENT_DTYPE = np.dtype([("start", np.uint64), ("len", np.uint64)])   # am_fragment
+NEEDLE_COUNT_DTYPE = np.dtype([("count", np.uint64), ("needle", np.uint32), ("haystack", np.uint32)])   # am_needle_count
 PRIO_MATCH_DTYPE = np.dtype([("start", np.uint64), ("len", np.uint64), ("haystack", np.uint32), ("payload", np.uint32)])   # am_prio_match
 
 _u8p, _u32p, _u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
@@ -70,6 +71,16 @@ ABI = {
     "am_count_by_needle_batch": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "am_count_by_needle": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp]),
     "am_matches_count_by_needle": (C.c_int, [_vp, _vp, _vp]),
+    "am_count_matrix_batch": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_vp)]),
+    "am_count_matrix": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, C.POINTER(_vp)]),
+    "am_matches_count_matrix": (C.c_int, [_vp, _vp, _sz, C.POINTER(_vp)]),
+    "am_needle_matrix_size": (C.c_uint64, [_vp]),
+    "am_needle_matrix_haystacks": (C.c_uint64, [_vp]),
+    "am_needle_matrix_offsets": (_vp, [_vp]),
+    "am_needle_matrix_data": (_vp, [_vp]),
+    "am_needle_matrix_device_offsets": (_vp, [_vp]),
+    "am_needle_matrix_device_data": (_vp, [_vp]),
+    "am_needle_matrix_free": (None, [_vp]),
     "am_splitter_create": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
     "am_splitter_destroy": (None, [_vp]),
     "am_split_batch": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_vp)]),
@@ -153,6 +164,7 @@ _HOST = {
     "amh_run_list": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp, _vp, _vp, C.c_uint64, _u64p]),
     "amh_count": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp]),
     "amh_count_by_needle": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _sz, _vp]),
+    "amh_count_matrix": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _sz, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
     "amh_searcher_build": (C.c_int, [C.c_int, C.c_char_p, _vp, _sz, C.POINTER(_vp)]),
     "amh_searcher_free": (None, [_vp]),
     "amh_searcher_set_case": (None, [_vp, C.c_int]),
@@ -197,6 +209,7 @@ DEBUG_ABI = {
     "am_debug_rp_lds_haystacks": (C.c_uint32, []),
     "am_debug_hist_adds": (C.c_int, [_vp]),
     "am_debug_split_rounds": (C.c_uint32, []),
+    "am_debug_needle_matrix_limits": (C.c_int, [_vp]),
 }
 
 _libam = None
@@ -441,6 +454,31 @@ class Automaton:
         return out[:n]
 
 
+    def count_matrix(self, case, texts, n_values=None):
+        """Which values are matched in which text, and how often: (offsets np.uint64[len(texts) + 1], entries NEEDLE_COUNT_DTYPE[offsets[-1]]); row i =
+        entries[offsets[i]:offsets[i + 1]] = Map.toAscList of the fold `Map.insertWith (+) v 1` of runWithCase (Automaton.hs:442-553) over texts[i], ascending by
+        value, n = len(needles) unless given (handles >= n are skipped).  am_count_matrix: scanned and folded in HBM, the matrix comes back."""
+        n = len(self.needles) if n_values is None else int(n_values)
+        if n == 0:
+            return np.zeros(len(texts) + 1, np.uint64), np.zeros(0, NEEDLE_COUNT_DTYPE)
+        return ValuesTable(self, n).count_matrix_texts(case, texts)
+
+    def count_matrix_host_mirror(self, case, texts, n_values=None):
+        """The same through the C++ host mirror (host/automaton.hpp countMatrix)."""
+        n = len(self.needles) if n_values is None else int(n_values)
+        s = _Slices(texts)
+        po, pe, ne = _vp(), _vp(), C.c_uint64(0)
+        _hcheck(libhost().amh_count_matrix(self._h, case, s.arr, s.n, n, C.byref(po), C.byref(pe), C.byref(ne)))
+        try:
+            offs = np.frombuffer((C.c_char * ((s.n + 1) * 8)).from_address(po.value), dtype=np.uint64).copy()
+            k = int(ne.value)
+            ents = np.frombuffer((C.c_char * (k * 16)).from_address(pe.value), dtype=NEEDLE_COUNT_DTYPE).copy() if k else np.zeros(0, NEEDLE_COUNT_DTYPE)
+        finally:
+            libhost().amh_free_u64(po)
+            libhost().amh_free_u64(pe)
+        return offs, ents
+
+
 class ValuesTable:
     """machineValues of an Automaton in flat form on the device (am_needle_ids): what the fold-checksum and
     containsAll kernels expand records with."""
@@ -489,6 +527,31 @@ class ValuesTable:
         """am_count_by_needle: the one-shot form on host texts."""
         s = _Slices(texts)
         return self._counts(lambda out: libam().am_count_by_needle(self._h, case, s.arr, s.n, out))
+
+
+    def _matrix(self, call, raw):
+        x = _vp()
+        check(call(C.byref(x)))
+        if raw:
+            return x
+        try:
+            return matrix_to_numpy(x)
+        finally:
+            libam().am_needle_matrix_free(x)
+
+    def count_matrix(self, matches, n_hay, raw=False):
+        """am_matches_count_matrix: the term-document matrix (offsets np.uint64[n_hay + 1], entries NEEDLE_COUNT_DTYPE) of an am_matches* result whose records are in
+        HBM.  raw: the am_needle_matrix* itself, in HBM (measurements; free with am_needle_matrix_free)."""
+        return self._matrix(lambda out: libam().am_matches_count_matrix(matches, self._h, n_hay, out), raw)
+
+    def count_matrix_batch(self, case, batch, raw=False):
+        """am_count_matrix_batch: the same over a device-resident batch (an am_batch* handle: am_batch_upload / am_batch_from_device / Splitter.lines_batch)."""
+        return self._matrix(lambda out: libam().am_count_matrix_batch(self._h, case, batch, out), raw)
+
+    def count_matrix_texts(self, case, texts, raw=False):
+        """am_count_matrix: the one-shot form on host texts."""
+        s = _Slices(texts)
+        return self._matrix(lambda out: libam().am_count_matrix(self._h, case, s.arr, s.n, out), raw)
 
 
 class ImageAutomaton:
@@ -551,6 +614,17 @@ def fragments_to_numpy(f):
     offs = np.frombuffer((C.c_char * ((n_hay + 1) * 8)).from_address(po), dtype=np.uint64).copy()
     frags = np.frombuffer((C.c_char * (n * FRAGMENT_DTYPE.itemsize)).from_address(pd), dtype=FRAGMENT_DTYPE).copy() if n else np.zeros(0, FRAGMENT_DTYPE)
     return offs, frags
+
+
+def matrix_to_numpy(x):
+    """(offsets np.uint64[n_hay + 1], entries NEEDLE_COUNT_DTYPE[n]) of an am_needle_matrix* result (host copies)."""
+    n, n_hay = int(libam().am_needle_matrix_size(x)), int(libam().am_needle_matrix_haystacks(x))
+    po, pd = libam().am_needle_matrix_offsets(x), libam().am_needle_matrix_data(x)
+    if not po or not pd:
+        raise AmError(AM_ERR_HIP, (libam().am_last_error() or b"").decode())
+    offs = np.frombuffer((C.c_char * ((n_hay + 1) * 8)).from_address(po), dtype=np.uint64).copy()
+    ents = np.frombuffer((C.c_char * (n * NEEDLE_COUNT_DTYPE.itemsize)).from_address(pd), dtype=NEEDLE_COUNT_DTYPE).copy() if n else np.zeros(0, NEEDLE_COUNT_DTYPE)
+    return offs, ents
 
 
 def matches_of_haystack(m, haystack):
@@ -835,6 +909,13 @@ def hist_adds():
     a = np.zeros(3, np.uint64)
     check(libam().am_debug_hist_adds(a.ctypes.data))
     return int(a[0]), int(a[1]), int(a[2])
+
+
+def needle_matrix_limits():
+    """am_debug_needle_matrix_limits: {wave_row, lds_row, lds_slots, chunk_records} of csrc/am_matrix.hip."""
+    out = (C.c_uint32 * 4)()
+    check(libam().am_debug_needle_matrix_limits(out))
+    return dict(zip(("wave_row", "lds_row", "lds_slots", "chunk_records"), (int(v) for v in out)))
 
 
 def bounds_report():

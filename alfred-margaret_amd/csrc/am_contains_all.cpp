@@ -164,34 +164,39 @@ int hist_launch(const am_needle_ids* ids, const Record* recs, uint64_t n_rec, ui
     return AM_OK;
 }
 
-// one scan of `b`, its records folded into d_counts (accumulating); returns when the fold has finished (the record array is free again)
-int hist_scan(const am_needle_ids* ids, int case_mode, am_batch* b, RecordArray& ra, uint64_t* d_counts, uint64_t* d_trace)
+// what is done with the sorted records of a scan while they are in HBM: records [0, n_rec) belong to haystacks [h0, h0 + n_hay) of the batch the caller handed to
+// fold_batch, their haystack fields count from h0.  Returns when the device has finished with the records.
+using RecordFold = std::function<int(const Record* recs, uint64_t n_rec, uint32_t h0, uint32_t n_hay, int dev, hipStream_t st)>;
+
+// one scan of `b` (haystacks h0 ... of the caller's batch), its records handed to `fold`; returns when the fold has finished (the record array is free again)
+int fold_scan(const am_needle_ids* ids, int case_mode, am_batch* b, RecordArray& ra, uint32_t h0, const RecordFold& fold)
 {
     uint64_t n_rec = 0;
     AM_TRY(run_records(ids->a, case_mode, b, records_into(ra), &n_rec));
     if (n_rec == 0) return AM_OK;
     ON_DEVICE(b->dev);
     hipStream_t st; AM_TRY(get_stream(b->dev, &st));
-    AM_TRY(hist_launch(ids, (const Record*)ra.p, n_rec, d_counts, d_trace, b->dev, st));
+    AM_TRY(fold((const Record*)ra.p, n_rec, h0, b->n_hay, b->dev, st));
     HIP_TRY(hipStreamSynchronize(st));
     return AM_OK;
 }
 
-// the counts of a device-resident batch into d_counts (accumulating), in bounded record memory
-int hist_batch(const am_needle_ids* ids, int case_mode, am_batch* b, uint64_t* d_counts, uint64_t* d_trace)
+// a device-resident batch scanned and folded in bounded record memory: in one piece, or in groups of whole consecutive haystacks (am_count_by_needle* and
+// am_count_matrix* share this loop)
+int fold_batch(const am_needle_ids* ids, int case_mode, am_batch* b, const RecordFold& fold)
 {
     if (b->n_hay == 0 || b->total == 0) return AM_OK;
     ON_DEVICE(b->dev);                                     // (segments are folded on threads of their own)
     RecordArray ra(b->dev);
     const uint64_t budget = hist_budget();
     // a record per end position at most (and one more per haystack where the empty needle reports position 0): small batches need no count pass
-    if ((b->total + b->n_hay) * sizeof(Record) <= budget || b->n_hay == 1) return hist_scan(ids, case_mode, b, ra, d_counts, d_trace);
+    if ((b->total + b->n_hay) * sizeof(Record) <= budget || b->n_hay == 1) return fold_scan(ids, case_mode, b, ra, 0, fold);
     // the count pass: values per haystack (>= its records: every record carries at least one value)
     std::vector<uint64_t> per(b->n_hay);
     uint64_t total_values = 0;
     AM_TRY(am_count_batch(ids->a, case_mode, b, per.data(), &total_values));
     if (total_values == 0) return AM_OK;
-    if (total_values * sizeof(Record) <= budget) return hist_scan(ids, case_mode, b, ra, d_counts, d_trace);
+    if (total_values * sizeof(Record) <= budget) return fold_scan(ids, case_mode, b, ra, 0, fold);
     // groups of whole consecutive haystacks, each a batch of its own: its text copied (device to device) to a 16-byte aligned start, its offsets rebased
     hipStream_t st; AM_TRY(get_stream(b->dev, &st));
     std::vector<uint64_t> offs((size_t)b->n_hay + 1), sub_offs;
@@ -216,11 +221,19 @@ int hist_batch(const am_needle_ids* ids, int case_mode, am_batch* b, uint64_t* d
             sub->owns = true; sub->d_text = sub->text_buf.p; sub->d_offsets = (uint64_t*)sub->offs_buf.p;
             sub->total = bytes; sub->n_hay = h1 - h0;
             AM_TRY(finish_batch(sub.get()));
-            AM_TRY(hist_scan(ids, case_mode, sub.get(), ra, d_counts, d_trace));
+            AM_TRY(fold_scan(ids, case_mode, sub.get(), ra, h0, fold));
         }
         h0 = h1;
     }
     return AM_OK;
+}
+
+// the counts of a device-resident batch into d_counts (accumulating)
+int hist_batch(const am_needle_ids* ids, int case_mode, am_batch* b, uint64_t* d_counts, uint64_t* d_trace)
+{
+    return fold_batch(ids, case_mode, b, [&](const Record* recs, uint64_t n_rec, uint32_t, uint32_t, int dev, hipStream_t st) {
+        return hist_launch(ids, recs, n_rec, d_counts, d_trace, dev, st);
+    });
 }
 
 // the histogram of a call in HBM: n_needles counts + the three trace words, cleared; read back at the end
@@ -346,3 +359,288 @@ extern "C" int am_count_by_needle(const am_needle_ids* ids, int case_mode, const
     if (rc != AM_OK) return rc;
     return out.finish(counts_out, st);
 }
+
+// ------------------------------------------------------------------ per-haystack needle counts: the term-document matrix (am_count_matrix*)
+// The fold of am_count_by_needle run once PER HAYSTACK (Automaton.hs:442-553), as a CSR matrix in HBM: row i = the (needle, count) pairs of haystack i in ascending
+// needle order.  The kernels are am_matrix.hip; the scans, the record budget and its groups of whole haystacks are fold_batch's, above.  Rows belong to
+// haystacks and a group is whole haystacks: every group leaves a part {local offsets, entries with the batch's haystack index}, and the parts are appended at the end.
+
+struct am_needle_matrix {
+    int dev = 0;
+    uint64_t n_hay = 0, n_entries = 0;
+    DevBuf offsets, data;                                 // uint64[n_hay + 1], NeedleCount[n_entries] in HBM (none when n_hay == 0)
+    std::vector<uint64_t> h_offsets; std::vector<am_needle_count> h_data;
+    bool offsets_fetched = false, data_fetched = false;
+};
+
+static_assert(sizeof(am_needle_count) == sizeof(NeedleCount) && sizeof(NeedleCount) == 16, "am_needle_count and the kernels' NeedleCount are one layout");
+static_assert(offsetof(am_needle_count, count) == 0 && offsetof(am_needle_count, needle) == 8 && offsetof(am_needle_count, haystack) == 12, "am_needle_count: offsets 0, 8, 12");
+
+namespace {
+
+struct MatrixBuild {
+    struct Part { DevBuf offsets, data; uint32_t h0 = 0, n = 0; uint64_t entries = 0; };
+    const am_needle_ids* ids;
+    std::vector<std::unique_ptr<Part>> parts;             // in haystack order: groups and segments arrive one after the other
+    explicit MatrixBuild(const am_needle_ids* i) : ids(i) {}
+
+    // the rows of haystacks [h0, h0 + n) from their records (haystack fields relative to h0)
+    int fold(const Record* recs, uint64_t n_rec, uint32_t h0, uint32_t n, int dev, hipStream_t st)
+    {
+        if (n_rec == 0 || n == 0 || ids->n_needles == 0) return AM_OK;
+        const int n_cu = g_rt.dev[dev].n_cu;
+        const uint64_t* vals_off = (const uint64_t*)ids->vals_off.p;
+        const uint32_t* vals = (const uint32_t*)ids->vals.p;
+        DevBuf ctr, row_entries, scan_tmp, keys, cnts, tmp, list, bits, pre;
+        AM_TRY(ctr.ensure(64));                             // [0] u64: values of the group; words 2, 3: rows for k_mx_rows_lds / k_mx_rows_wide
+        AM_TRY(row_entries.ensure(((size_t)n + 1) * 4));
+        HIP_TRY(hipMemsetAsync(ctr.p, 0, 64, st));
+        HIP_TRY(hipMemsetAsync(row_entries.p, 0, ((size_t)n + 1) * 4, st));
+        { Prof pr("mx_values", st);
+          HIP_TRY(launch_mx_values(recs, n_rec, vals_off, ids->n_states, ids->n_values, (uint64_t*)ctr.p, n_cu, st)); }
+        uint64_t values = 0;
+        HIP_TRY(hipMemcpyAsync(&values, ctr.p, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (values == 0) return AM_OK;
+        // distinct keys <= values, and <= rows x needles (`a, aa, aaa` over one haystack: three)
+        const uint64_t keys_max = (uint64_t)n <= values / ids->n_needles ? (uint64_t)n * ids->n_needles : values;
+        const uint64_t cap = keys_max + keys_max / 2 + 64;
+        AM_TRY(keys.ensure(cap * 8));
+        AM_TRY(cnts.ensure(cap * 8));
+        HIP_TRY(hipMemsetAsync(keys.p, 0xFF, cap * 8, st));
+        HIP_TRY(hipMemsetAsync(cnts.p, 0, cap * 8, st));
+        { Prof pr("mx_combine", st);
+          HIP_TRY(launch_mx_combine(recs, n_rec, vals_off, vals, ids->n_needles, ids->n_states, ids->n_values, n, (uint64_t*)keys.p, (uint64_t*)cnts.p, cap,
+                                    (uint32_t*)row_entries.p, n_cu, st)); }
+        std::unique_ptr<Part> part(new Part());
+        part->h0 = h0; part->n = n;
+        AM_TRY(part->offsets.ensure(((size_t)n + 1) * 8));
+        size_t tmp_bytes = 0;
+        HIP_TRY(scan_temp_bytes((uint64_t)n + 1, &tmp_bytes));
+        AM_TRY(scan_tmp.ensure(tmp_bytes));
+        HIP_TRY(launch_scan(scan_tmp.p, scan_tmp.cap, (const uint32_t*)row_entries.p, (uint64_t*)part->offsets.p, (uint64_t)n + 1, st));
+        HIP_TRY(hipMemcpyAsync(&part->entries, (const uint64_t*)part->offsets.p + n, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const uint64_t n_ent = part->entries;
+        if (n_ent == 0) return AM_OK;                       // (every handle was beyond the table)
+        if (n_ent > keys_max) return fail(AM_ERR_HIP, "am_count_matrix: more entries than the group's table was sized for");
+        AM_TRY(tmp.ensure(n_ent * sizeof(NeedleCount)));
+        AM_TRY(part->data.ensure(n_ent * sizeof(NeedleCount)));
+        AM_TRY(list.ensure((size_t)n * 4));
+        uint32_t* const rows_ctr = (uint32_t*)ctr.p + 2;
+        { Prof pr("mx_scatter", st);
+          HIP_TRY(launch_mx_scatter((const uint64_t*)keys.p, (const uint64_t*)cnts.p, cap, (const uint64_t*)part->offsets.p, (uint32_t*)row_entries.p, n, h0,
+                                    (NeedleCount*)tmp.p, n_ent, n_cu, st)); }
+        { Prof pr("mx_rows", st);
+          HIP_TRY(launch_mx_rows((const NeedleCount*)tmp.p, (const uint64_t*)part->offsets.p, n, n_ent, (NeedleCount*)part->data.p, (uint32_t*)list.p, rows_ctr, st)); }
+        if (ids->n_needles > kMxWaveRow) {                  // (a row has at most n_needles entries)
+            Prof pr("mx_rows_lds", st);
+            HIP_TRY(launch_mx_rows_lds((const NeedleCount*)tmp.p, (const uint64_t*)part->offsets.p, n, n_ent, (const uint32_t*)list.p, rows_ctr, (NeedleCount*)part->data.p, n_cu, st));
+        }
+        if (const uint32_t grid = mx_wide_grid(n, n_ent, ids->n_needles, n_cu)) {
+            const size_t words = ((size_t)ids->n_needles + 31) / 32;
+            AM_TRY(bits.ensure(words * 4 * grid));
+            AM_TRY(pre.ensure(words * 4 * grid));
+            HIP_TRY(hipMemsetAsync(bits.p, 0, words * 4 * grid, st));
+            Prof pr("mx_rows_wide", st);
+            HIP_TRY(launch_mx_rows_wide((const NeedleCount*)tmp.p, (const uint64_t*)part->offsets.p, n, n_ent, (const uint32_t*)list.p, rows_ctr, ids->n_needles,
+                                        (uint32_t*)bits.p, (uint32_t*)pre.p, grid, (NeedleCount*)part->data.p, st));
+        }
+        HIP_TRY(hipStreamSynchronize(st));                  // (the workspaces are freed, the records go back)
+        parts.push_back(std::move(part));
+        return AM_OK;
+    }
+
+    // the parts appended: offsets rebased by the entries before them, haystacks no part covers (nothing matched there) get empty rows
+    int finish(int dev, uint64_t n_hay, hipStream_t st, am_needle_matrix** out)
+    {
+        std::unique_ptr<am_needle_matrix, void (*)(am_needle_matrix*)> x(new am_needle_matrix(), am_needle_matrix_free);
+        x->dev = dev; x->n_hay = n_hay;
+        if (n_hay == 0) {                                   // offsets = [0], nothing in HBM
+            x->h_offsets.assign(1, 0); x->h_data.assign(1, am_needle_count{0, 0, 0});
+            x->offsets_fetched = x->data_fetched = true;
+            *out = x.release();
+            return AM_OK;
+        }
+        if (parts.size() == 1 && parts[0]->h0 == 0 && parts[0]->n == n_hay) {
+            Part& p = *parts[0];
+            std::swap(x->offsets.p, p.offsets.p); std::swap(x->offsets.cap, p.offsets.cap);
+            std::swap(x->data.p, p.data.p); std::swap(x->data.cap, p.data.cap);
+            x->n_entries = p.entries;
+            *out = x.release();
+            return AM_OK;
+        }
+        uint64_t total = 0;
+        for (const auto& p : parts) total += p->entries;
+        AM_TRY(x->offsets.ensure((n_hay + 1) * 8));
+        AM_TRY(x->data.ensure(total * sizeof(NeedleCount)));
+        uint64_t* const offs = (uint64_t*)x->offsets.p;
+        uint64_t h = 0, base = 0;
+        for (const auto& p : parts) {
+            if (p->h0 < h || (uint64_t)p->h0 + p->n > n_hay) return fail(AM_ERR_HIP, "am_count_matrix: the groups of haystacks are out of order");
+            HIP_TRY(launch_mx_offsets(nullptr, p->h0 - h, base, offs + h, st));
+            HIP_TRY(launch_mx_offsets((const uint64_t*)p->offsets.p, p->n, base, offs + p->h0, st));
+            HIP_TRY(hipMemcpyAsync((NeedleCount*)x->data.p + base, p->data.p, p->entries * sizeof(NeedleCount), hipMemcpyDeviceToDevice, st));
+            base += p->entries; h = (uint64_t)p->h0 + p->n;
+        }
+        HIP_TRY(launch_mx_offsets(nullptr, n_hay + 1 - h, base, offs + h, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        x->n_entries = total;
+        *out = x.release();
+        return AM_OK;
+    }
+};
+
+int matrix_case(int case_mode)
+{
+    return case_mode == AM_CASE_SENSITIVE || case_mode == AM_IGNORE_CASE ? AM_OK : fail(AM_ERR_INVALID, "case_mode must be AM_CASE_SENSITIVE or AM_IGNORE_CASE");
+}
+
+// the rows of batch `b`, whose first haystack is haystack `base` of the call, into mb
+int matrix_batch(MatrixBuild& mb, const am_needle_ids* ids, int case_mode, am_batch* b, uint64_t base)
+{
+    if (ids->n_needles == 0) return AM_OK;
+    return fold_batch(ids, case_mode, b, [&mb, base](const Record* recs, uint64_t n_rec, uint32_t h0, uint32_t n, int dev, hipStream_t st) {
+        return mb.fold(recs, n_rec, (uint32_t)(base + h0), n, dev, st);
+    });
+}
+
+}  // namespace
+
+extern "C" int am_debug_needle_matrix_limits(uint32_t* out4)
+{
+    if (!out4) return fail(AM_ERR_INVALID, "out4 is null");
+    mx_limits(out4);
+    return AM_OK;
+}
+
+extern "C" int am_count_matrix_batch(const am_needle_ids* ids, int case_mode, const am_batch* cb, am_needle_matrix** out)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    if (!ids || !cb) return fail(AM_ERR_INVALID, "null needle ids or batch");
+    AM_TRY(matrix_case(case_mode));
+    if (ids->a->dev != cb->dev) return fail(AM_ERR_INVALID, "needle ids and batch live on different devices");
+    AM_TRY(ensure_runtime());
+    am_batch* b = const_cast<am_batch*>(cb);
+    ON_DEVICE(b->dev);
+    hipStream_t st; AM_TRY(get_stream(b->dev, &st));
+    MatrixBuild mb(ids);
+    AM_TRY(matrix_batch(mb, ids, case_mode, b, 0));
+    return mb.finish(b->dev, b->n_hay, st, out);
+}
+
+extern "C" int am_matches_count_matrix(const am_matches* m, const am_needle_ids* ids, size_t n_hay, am_needle_matrix** out)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    if (!m || !ids) return fail(AM_ERR_INVALID, "null matches or values table");
+    if (n_hay >= 0xFFFFFFFFull) return fail(AM_ERR_INVALID, "too many haystacks");
+    if (m->n && !m->d_records) return fail(AM_ERR_UNSUPPORTED, "am_matches_count_matrix: the result was assembled on the host (am_run on a large host batch) and has no records in HBM");
+    AM_TRY(ensure_runtime());
+    if (m->dev != ids->a->dev) return fail(AM_ERR_INVALID, "result and values table live on different devices");
+    ON_DEVICE(m->dev);
+    hipStream_t st; AM_TRY(get_stream(m->dev, &st));
+    MatrixBuild mb(ids);
+    if (m->n) {
+        Record last;                                        // the records are sorted by haystack: the last one carries the largest index
+        HIP_TRY(hipMemcpyAsync(&last, m->d_records + m->first + m->n - 1, sizeof(Record), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (last.haystack >= n_hay) return fail(AM_ERR_INVALID, "am_matches_count_matrix: n_hay is not greater than the largest haystack index of the result");
+        AM_TRY(mb.fold(m->d_records + m->first, m->n, 0, (uint32_t)n_hay, m->dev, st));
+    }
+    return mb.finish(m->dev, n_hay, st, out);
+}
+
+extern "C" int am_count_matrix(const am_needle_ids* ids, int case_mode, const am_slice* hay, size_t n_hay, am_needle_matrix** out)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    if (!ids) return fail(AM_ERR_INVALID, "null needle ids");
+    if (n_hay && !hay) return fail(AM_ERR_INVALID, "hay is null");
+    if (n_hay >= 0xFFFFFFFFull) return fail(AM_ERR_INVALID, "too many haystacks");
+    AM_TRY(matrix_case(case_mode));
+    uint64_t total = 0;
+    for (size_t i = 0; i < n_hay; i++) { if (hay[i].len && !hay[i].ptr) return fail(AM_ERR_INVALID, "slice with null ptr"); total += hay[i].len; }
+    AM_TRY(ensure_runtime());
+    const int dev = ids->a->dev;
+    ON_DEVICE(dev);
+    hipStream_t st; AM_TRY(get_stream(dev, &st));
+    MatrixBuild mb(ids);
+    if (total == 0 || ids->n_needles == 0) return mb.finish(dev, n_hay, st, out);
+    const long forced = cfg::get(cfg::kRunSegments);       // (as am_count_by_needle: 0 = never, k > 0 = always, segments of k KiB)
+    if (n_hay < 2 || forced == 0 || (forced < 0 && total < kHistSegmentedFrom)) {
+        am_batch* b = oneshot_batch(dev);                   // this thread's batch on the automaton's device
+        int rc = upload_batch(hay, n_hay, b, true);
+        if (rc == AM_OK) rc = matrix_batch(mb, ids, case_mode, b, 0);
+        oneshot_batch_trim(dev);
+        if (rc != AM_OK) return rc;
+        return mb.finish(dev, n_hay, st, out);
+    }
+    // segments of whole haystacks, as am_count_by_needle sends them: a segment's rows are built in HBM while the next segment goes up, and appended in order
+    std::unique_ptr<am_batch, void (*)(am_batch*)> second(new am_batch(), am_batch_destroy);
+    second->dev = dev;
+    am_batch* turn[2] = {oneshot_batch(dev), second.get()};
+    const uint64_t segment = forced > 0 ? (uint64_t)forced << 10 : kHistSegment;
+    std::thread worker;
+    int rc = AM_OK, worker_rc = AM_OK; std::string worker_err;
+    auto join = [&] { if (worker.joinable()) worker.join(); if (rc == AM_OK && worker_rc != AM_OK) rc = fail(worker_rc, worker_err); };
+    size_t k = 0;
+    for (size_t i = 0; i < n_hay && rc == AM_OK; k++) {
+        size_t j = i; uint64_t bytes = 0;
+        while (j < n_hay && bytes < (i == 0 ? segment / 4 : segment)) bytes += hay[j++].len;
+        am_batch* b = turn[k & 1];
+        rc = upload_batch(hay + i, j - i, b, false);
+        join();
+        if (rc != AM_OK) break;
+        worker = std::thread([&, b, i] {
+            worker_rc = matrix_batch(mb, ids, case_mode, b, i);
+            if (worker_rc != AM_OK) worker_err = am_last_error();
+        });
+        i = j;
+    }
+    join();
+    oneshot_batch_trim(dev);
+    if (rc != AM_OK) return rc;
+    return mb.finish(dev, n_hay, st, out);
+}
+
+extern "C" uint64_t am_needle_matrix_size(const am_needle_matrix* x) { return x ? x->n_entries : 0; }
+extern "C" uint64_t am_needle_matrix_haystacks(const am_needle_matrix* x) { return x ? x->n_hay : 0; }
+extern "C" const void* am_needle_matrix_device_offsets(const am_needle_matrix* x) { return x ? x->offsets.p : nullptr; }
+extern "C" const void* am_needle_matrix_device_data(const am_needle_matrix* x) { return x ? x->data.p : nullptr; }
+
+namespace {
+template <class T>
+const T* matrix_fetch(am_needle_matrix* x, std::vector<T>& host, bool& fetched, const DevBuf& d, uint64_t n)
+{
+    if (fetched) return host.data();
+    try { host.resize((size_t)std::max<uint64_t>(n, 1)); } catch (const std::exception&) { fail(AM_ERR_OOM, "no host memory for the matrix"); return nullptr; }
+    if (n) {
+        if (ensure_runtime() != AM_OK) return nullptr;
+        OnDevice od(x->dev);
+        hipStream_t st;
+        if (od.rc != AM_OK || get_stream(x->dev, &st) != AM_OK) return nullptr;
+        if (hipMemcpyAsync(host.data(), d.p, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+            fail(AM_ERR_HIP, "copying the matrix to the host failed");
+            return nullptr;
+        }
+    }
+    fetched = true;
+    return host.data();
+}
+}  // namespace
+
+extern "C" const uint64_t* am_needle_matrix_offsets(am_needle_matrix* x)
+{
+    if (!x) { fail(AM_ERR_INVALID, "null matrix"); return nullptr; }
+    return matrix_fetch(x, x->h_offsets, x->offsets_fetched, x->offsets, x->n_hay + 1);
+}
+
+extern "C" const am_needle_count* am_needle_matrix_data(am_needle_matrix* x)
+{
+    if (!x) { fail(AM_ERR_INVALID, "null matrix"); return nullptr; }
+    return matrix_fetch(x, x->h_data, x->data_fetched, x->data, x->n_entries);
+}
+
+extern "C" void am_needle_matrix_free(am_needle_matrix* x) { delete x; }

@@ -151,6 +151,27 @@ hipError_t launch_idset_all(const uint32_t* bits, uint32_t words, uint32_t n_nee
 // [1] adds that went to HBM one by one (slot conflicts), [2] adds of the flushes
 hipError_t launch_needle_hist(const Record* recs, uint64_t n_rec, const uint64_t* vals_off, const uint32_t* vals, uint32_t n_needles, uint64_t n_states,
                               uint64_t n_values, uint64_t* counts, uint64_t* trace, uint32_t flush_tiles /* 0: the kernel's own interval */, int n_cu, hipStream_t st);
+// the term-document matrix (am_matrix.hip): per-haystack needle counts of a group of n_rows haystacks whose sorted records are recs[0, n_rec), haystack indices relative
+// to the group.  In the order of the calls: *total += lengths of the records' value lists; the (haystack, needle) keys combined into the open-addressing table keys / cnts
+// (cap slots, keys all ones and cnts zero before; cap > the group's distinct keys) with row_entries[h] = entries of row h (n_rows + 1, zero before); then, with
+// offsets = exclusive sum of row_entries and n_entries = offsets[n_rows], the live slots into tmp in arrival order (haystack = hay0 + h; row_entries ends at zero again);
+// rows of up to kMxWaveRow entries ordered by needle into `out`, the longer ones listed (list: n_rows words, ctr: two words, zero before) and ordered by launch_mx_rows_lds
+// (up to kMxLdsRow entries) and launch_mx_rows_wide (beyond: grid = mx_wide_grid(...) workgroups, each with ceil(n_needles / 32) words of `bits`, zero before, and of `pre`).
+struct alignas(16) NeedleCount { uint64_t count; uint32_t needle; uint32_t haystack; };      // = am_needle_count in include/am.h
+constexpr uint32_t kMxWaveRow = 64, kMxLdsRow = 2048;
+void mx_limits(uint32_t* out4);                             // wavefront row limit, LDS row capacity, slots of a workgroup's LDS table, records between two of its flushes
+hipError_t launch_mx_values(const Record* recs, uint64_t n_rec, const uint64_t* vals_off, uint64_t n_states, uint64_t n_values, uint64_t* total, int n_cu, hipStream_t st);
+hipError_t launch_mx_combine(const Record* recs, uint64_t n_rec, const uint64_t* vals_off, const uint32_t* vals, uint32_t n_needles, uint64_t n_states, uint64_t n_values,
+                             uint32_t n_rows, uint64_t* keys, uint64_t* cnts, uint64_t cap, uint32_t* row_entries, int n_cu, hipStream_t st);
+hipError_t launch_mx_scatter(const uint64_t* keys, const uint64_t* cnts, uint64_t cap, const uint64_t* offsets, uint32_t* row_entries, uint32_t n_rows, uint32_t hay0,
+                             NeedleCount* tmp, uint64_t n_entries, int n_cu, hipStream_t st);
+hipError_t launch_mx_rows(const NeedleCount* tmp, const uint64_t* offsets, uint32_t n_rows, uint64_t n_entries, NeedleCount* out, uint32_t* list, uint32_t* ctr, hipStream_t st);
+hipError_t launch_mx_rows_lds(const NeedleCount* tmp, const uint64_t* offsets, uint32_t n_rows, uint64_t n_entries, const uint32_t* list, const uint32_t* ctr,
+                              NeedleCount* out, int n_cu, hipStream_t st);
+uint32_t mx_wide_grid(uint32_t n_rows, uint64_t n_entries, uint32_t n_needles, int n_cu);      // 0: no row can be that long
+hipError_t launch_mx_rows_wide(const NeedleCount* tmp, const uint64_t* offsets, uint32_t n_rows, uint64_t n_entries, const uint32_t* list, const uint32_t* ctr,
+                               uint32_t n_needles, uint32_t* bits, uint32_t* pre, uint32_t grid, NeedleCount* out, hipStream_t st);
+hipError_t launch_mx_offsets(const uint64_t* local /* nullable: zeros */, uint64_t n, uint64_t base, uint64_t* out, hipStream_t st);      // out[i] = base + local[i], i < n
 // Splitter's fold over the sorted records of a one-needle automaton, and the gather of the fragments into a batch (am_split.hip)
 struct Fragment { uint64_t start, len; };                   // = am_fragment in include/am.h: code units, relative to the haystack
 struct SplitIn { const Record* recs; uint64_t n_rec; const uint8_t* text; const uint64_t* offsets; uint64_t total; uint32_t n_hay, sep_bytes, sep_cps; };

@@ -258,31 +258,70 @@ template <class A, class V, class F> A runLower(A seed, F f, const AcMachine<V>&
 // dense vector indexed by the value (V an integral handle): out[v] = how often the reference would call the fold function with `Match _ v`; the sum is countMatches
 // (benchmark/haskell/app/Main.hs:67-76).  nValues: length of the vector (values beyond it and negative values are skipped); by default 1 + the largest value.
 // The records are folded on the device (am_count_by_needle): none travels to the host.
+// machineValues in the flat form am_needle_ids_create takes; values that are negative or do not fit a handle become UINT32_MAX, which every fold skips
+struct FlatValues { std::vector<uint64_t> voff; std::vector<uint32_t> vals; size_t n = 0; };
 template <class V>
-std::vector<uint64_t> countByNeedle(CaseSensitivity cs, const AcMachine<V>& machine, const std::vector<Text>& texts, size_t nValues = SIZE_MAX)
+FlatValues flatValues(const AcMachine<V>& machine, size_t nValues, const char* who)
 {
-    std::vector<uint64_t> voff(machine.machineValues.size() + 1, 0);
-    std::vector<uint32_t> vals;
+    FlatValues fv;
+    fv.voff.assign(machine.machineValues.size() + 1, 0);
     uint64_t largest = 0; bool any = false;
     for (size_t st = 0; st < machine.machineValues.size(); st++) {
         for (const V& v : machine.machineValues[st]) {
             const bool ok = !(v < V(0)) && (uint64_t)v < UINT32_MAX;
-            vals.push_back(ok ? (uint32_t)v : UINT32_MAX);
+            fv.vals.push_back(ok ? (uint32_t)v : UINT32_MAX);
             if (ok) { any = true; if ((uint64_t)v > largest) largest = (uint64_t)v; }
         }
-        voff[st + 1] = vals.size();
+        fv.voff[st + 1] = fv.vals.size();
     }
-    const size_t n = nValues != SIZE_MAX ? nValues : (any ? (size_t)largest + 1 : 0);
-    if (n > UINT32_MAX) throw AmError(AM_ERR_INVALID, "countByNeedle: more than 2^32 - 1 values");
-    std::vector<uint64_t> out(n, 0);
-    if (n == 0) return out;
-    if (vals.empty()) vals.push_back(0);
+    fv.n = nValues != SIZE_MAX ? nValues : (any ? (size_t)largest + 1 : 0);
+    if (fv.n > UINT32_MAX) throw AmError(AM_ERR_INVALID, std::string(who) + ": more than 2^32 - 1 values");
+    if (fv.vals.empty()) fv.vals.push_back(0);
+    return fv;
+}
+
+template <class V>
+std::vector<uint64_t> countByNeedle(CaseSensitivity cs, const AcMachine<V>& machine, const std::vector<Text>& texts, size_t nValues = SIZE_MAX)
+{
+    const FlatValues fv = flatValues(machine, nValues, "countByNeedle");
+    std::vector<uint64_t> out(fv.n, 0);
+    if (fv.n == 0) return out;
     am_needle_ids* raw = nullptr;
-    amCheck(am_needle_ids_create(machine.device.get(), voff.data(), vals.data(), (uint32_t)n, &raw));
+    amCheck(am_needle_ids_create(machine.device.get(), fv.voff.data(), fv.vals.data(), (uint32_t)fv.n, &raw));
     std::unique_ptr<am_needle_ids, void (*)(am_needle_ids*)> ids(raw, am_needle_ids_destroy);
     std::vector<am_slice> slices(texts.size());
     for (size_t i = 0; i < texts.size(); i++) slices[i] = am_slice{texts[i].data, texts[i].off, texts[i].len};
     amCheck(am_count_by_needle(ids.get(), (int)cs, slices.data(), slices.size(), out.data()));
+    return out;
+}
+
+// The term-document matrix: the same fold per text.  rows[i] = Map.toAscList of  runWithCase cs Map.empty (\m (Match _ v) -> Step (Map.insertWith (+) v 1 m))
+// (Automaton.hs:442-553) over texts[i], values >= nValues (by default: none) skipped: (value, count) pairs in ascending value order, in CSR form.  Built on the device
+// (am_count_matrix): what travels to the host is the matrix.
+struct NeedleMatrix {
+    std::vector<uint64_t> offsets;                          // texts.size() + 1
+    std::vector<am_needle_count> entries;                   // row i: [offsets[i], offsets[i + 1])
+};
+template <class V>
+NeedleMatrix countMatrix(CaseSensitivity cs, const AcMachine<V>& machine, const std::vector<Text>& texts, size_t nValues = SIZE_MAX)
+{
+    const FlatValues fv = flatValues(machine, nValues, "countMatrix");
+    NeedleMatrix out;
+    out.offsets.assign(texts.size() + 1, 0);
+    if (fv.n == 0) return out;
+    am_needle_ids* raw = nullptr;
+    amCheck(am_needle_ids_create(machine.device.get(), fv.voff.data(), fv.vals.data(), (uint32_t)fv.n, &raw));
+    std::unique_ptr<am_needle_ids, void (*)(am_needle_ids*)> ids(raw, am_needle_ids_destroy);
+    std::vector<am_slice> slices(texts.size());
+    for (size_t i = 0; i < texts.size(); i++) slices[i] = am_slice{texts[i].data, texts[i].off, texts[i].len};
+    am_needle_matrix* rx = nullptr;
+    amCheck(am_count_matrix(ids.get(), (int)cs, slices.data(), slices.size(), &rx));
+    std::unique_ptr<am_needle_matrix, void (*)(am_needle_matrix*)> x(rx, am_needle_matrix_free);
+    const uint64_t* po = am_needle_matrix_offsets(x.get());
+    const am_needle_count* pd = am_needle_matrix_data(x.get());
+    if (!po || !pd) throw AmError(AM_ERR_HIP, am_last_error());
+    out.offsets.assign(po, po + texts.size() + 1);
+    out.entries.assign(pd, pd + am_needle_matrix_size(x.get()));
     return out;
 }
 

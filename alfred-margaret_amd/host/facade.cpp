@@ -95,6 +95,22 @@ int amh_count_by_needle(void* h, int case_mode, const am_slice* hay, size_t n_ha
     });
 }
 
+// the term-document matrix of a batch (countMatrix): offsets (n_hay + 1) and 2 x n_entries words per entry as the C ABI lays them out (count; needle | haystack << 32);
+// free both with amh_free_u64
+int amh_count_matrix(void* h, int case_mode, const am_slice* hay, size_t n_hay, size_t n_values, uint64_t** offs_out, uint64_t** entries_out, uint64_t* n_entries_out)
+{
+    *offs_out = nullptr; *entries_out = nullptr; *n_entries_out = 0;
+    return guarded([&] {
+        const NeedleMatrix r = countMatrix((CaseSensitivity)case_mode, static_cast<MachineBox*>(h)->m, sliceTexts(hay, n_hay), n_values);
+        const uint64_t ne = r.entries.size();
+        uint64_t* offs = (uint64_t*)malloc((n_hay + 1) * sizeof(uint64_t));
+        uint64_t* ents = (uint64_t*)malloc((ne ? ne : 1) * sizeof(am_needle_count));
+        std::memcpy(offs, r.offsets.data(), (n_hay + 1) * sizeof(uint64_t));
+        if (ne) std::memcpy(ents, r.entries.data(), ne * sizeof(am_needle_count));
+        *offs_out = offs; *entries_out = ents; *n_entries_out = ne;
+    });
+}
+
 // ---- Searcher
 int amh_searcher_build(int case_mode, const uint8_t* bytes, const uint64_t* offs, size_t n, void** out)
 {

@@ -26,8 +26,10 @@ module Data.Text.AhoCorasick.Automaton.Device
   , countMatchesDevice
   , containsAnyDevice
   , countByNeedle
+  , countMatrix
     -- * For the sibling modules
   , AmAutomaton
+  , AmNeedleCount (..)
   , AmSlice (..)
   , AmMatch (..)
   , caseFlag
@@ -59,6 +61,7 @@ import Data.Text.Utf8 (Text (..))
 data AmAutomaton
 data AmMatches
 data AmNeedleIds
+data AmNeedleMatrix
 
 -- | @am_slice@ = @U8Slice@ of benchmark/rust-ffi/app/Main.hs:34-45 (= Data.Text.Internal.Text array/offset/length).
 data AmSlice = AmSlice !(Ptr Word8) !CSize !CSize
@@ -77,6 +80,15 @@ instance Storable AmMatch where
   alignment _ = 8
   peek p = AmMatch <$> peekByteOff p 0 <*> peekByteOff p 8 <*> peekByteOff p 12
   poke p (AmMatch e h s) = pokeByteOff p 0 e >> pokeByteOff p 8 h >> pokeByteOff p 12 s
+
+-- | @am_needle_count {u64 count; u32 needle; u32 haystack}@: one entry of the term-document matrix
+data AmNeedleCount = AmNeedleCount !Word64 !Word32 !Word32
+
+instance Storable AmNeedleCount where
+  sizeOf _ = 16
+  alignment _ = 8
+  peek p = AmNeedleCount <$> peekByteOff p 0 <*> peekByteOff p 8 <*> peekByteOff p 12
+  poke p (AmNeedleCount c v h) = pokeByteOff p 0 c >> pokeByteOff p 8 v >> pokeByteOff p 12 h
 
 -- am_automaton_create_ex = am_automaton_create + the host's own lower-casing as data (see 'lowerPairs')
 -- safe: the call flattens the automaton (hundreds of milliseconds for 100k needles, a DFA table of up to 1 GiB for a dictionary): unsafe would block the capability and GC
@@ -107,6 +119,19 @@ foreign import ccall safe "am_needle_ids_destroy"
   c_am_needle_ids_destroy :: Ptr AmNeedleIds -> IO ()
 foreign import ccall safe "am_count_by_needle"
   c_am_count_by_needle :: Ptr AmNeedleIds -> CInt -> Ptr AmSlice -> CSize -> Ptr Word64 -> IO CInt
+-- the term-document matrix: scanned and folded in HBM (`safe`: blocks for the GPU call), the host copies are made on first use (`safe`: a copy over the wire)
+foreign import ccall safe "am_count_matrix"
+  c_am_count_matrix :: Ptr AmNeedleIds -> CInt -> Ptr AmSlice -> CSize -> Ptr (Ptr AmNeedleMatrix) -> IO CInt
+foreign import ccall unsafe "am_needle_matrix_size"
+  c_am_needle_matrix_size :: Ptr AmNeedleMatrix -> IO Word64
+foreign import ccall unsafe "am_needle_matrix_haystacks"
+  c_am_needle_matrix_haystacks :: Ptr AmNeedleMatrix -> IO Word64
+foreign import ccall safe "am_needle_matrix_offsets"
+  c_am_needle_matrix_offsets :: Ptr AmNeedleMatrix -> IO (Ptr Word64)
+foreign import ccall safe "am_needle_matrix_data"
+  c_am_needle_matrix_data :: Ptr AmNeedleMatrix -> IO (Ptr AmNeedleCount)
+foreign import ccall unsafe "&am_needle_matrix_free"
+  p_am_needle_matrix_free :: FunPtr (Ptr AmNeedleMatrix -> IO ())
 
 -- | An 'AcMachine' plus its flattened copy in HBM.  'machineValues' never leaves Haskell.
 data DeviceMachine v = DeviceMachine
@@ -223,6 +248,37 @@ countByNeedle cs (DeviceMachine m h) texts = do
       c_am_needle_ids_destroy ids
       checkRc rc
       UVector.fromList <$> peekArray n pCounts
+
+-- | The term-document matrix: the same fold once PER TEXT.  Element @i@ = @Map.toAscList@ of
+-- @runWithCase cs Map.empty (\m (Match _ v) -> Step (Map.insertWith (+) v 1 m))@ (Automaton.hs:442-553) over text @i@: the values that match there with how
+-- often, ascending by value; a text without a match gives @[]@, negative values are skipped.  Scanned and folded in HBM (am_count_matrix): what comes back is
+-- the matrix in CSR form, never a record.
+countMatrix :: CaseSensitivity -> DeviceMachine Int -> [Text] -> IO [[(Int, Word64)]]
+countMatrix cs (DeviceMachine m h) texts = do
+  let lists   = Vector.toList (machineValues m)
+      flat    = [ if v < 0 then maxBound else fromIntegral v :: Word32 | vs <- lists, v <- vs ]
+      offsets = scanl (+) 0 (map (fromIntegral . length) lists) :: [Word64]
+      n       = if null (filter (>= 0) (concat lists)) then 0 else 1 + maximum (concat lists)
+  if n == 0 then pure (map (const []) texts) else
+    withArray offsets $ \pOff -> withArray (if null flat then [0] else flat) $ \pVals ->
+    withPinnedTexts texts $ \pSlices nTexts ->
+    alloca $ \outIds -> alloca $ \out -> withForeignPtr h $ \ph -> do
+      c_am_needle_ids_create ph pOff pVals (fromIntegral n) outIds >>= checkRc
+      ids <- peek outIds
+      rc <- c_am_count_matrix ids (caseFlag cs) pSlices (fromIntegral nTexts) out
+      c_am_needle_ids_destroy ids
+      checkRc rc
+      fx <- peek out >>= newForeignPtr p_am_needle_matrix_free
+      withForeignPtr fx $ \x -> do
+        rows <- fromIntegral <$> c_am_needle_matrix_haystacks x
+        size <- fromIntegral <$> c_am_needle_matrix_size x
+        pO <- c_am_needle_matrix_offsets x
+        pD <- c_am_needle_matrix_data x
+        when (pO == nullPtr || pD == nullPtr || rows /= nTexts) (checkRc (-3))
+        offs <- map fromIntegral <$> peekArray (rows + 1) pO
+        ents <- peekArray size pD
+        let row a b = [ (fromIntegral v, c) | AmNeedleCount c v _ <- take (b - a) (drop a ents) ]
+        pure (zipWith row offs (drop 1 offs))
 
 -- ---- helpers -----------------------------------------------------------------------------------
 

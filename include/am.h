@@ -207,6 +207,47 @@ AM_API int am_count_by_needle_batch(const am_needle_ids* ids, int case_mode, con
 AM_API int am_count_by_needle(const am_needle_ids* ids, int case_mode, const am_slice* hay, size_t n_hay, uint64_t* counts_out /* n_needles, host */);
 AM_API int am_matches_count_by_needle(const am_matches* m, const am_needle_ids* ids, uint64_t* counts_out /* n_needles, host */);
 
+/* ---- per-haystack needle counts: the term-document matrix of a dictionary over a batch --------------
+ * The same fold,  runWithCase cs Map.empty (\m (Match _ v) -> Step (Map.insertWith (+) v 1 m))  (Automaton.hs:442-553), run once PER HAYSTACK: which needles occur in
+ * which haystack, and how often.  The result is a CSR matrix with one row per haystack: row i is [offsets[i], offsets[i + 1]) of data, and holds one entry per value
+ * v < n_needles that the reference's fold would meet at least once in haystack i; count = how often it meets it, i.e. the sum over the haystack's records r of the number
+ * of k in [values_offsets[r.state], values_offsets[r.state + 1]) with values[k] == v.  Entries are SORTED BY (haystack, needle) ASCENDING -- a row reads like Map.toAscList
+ * of the reference's fold -- and the result is bit-identical from run to run.  No entry has count 0; a haystack without a match has an empty row
+ * (offsets[i] == offsets[i + 1]).  Everything am_count_by_needle says about handles holds per row: handles >= n_needles are SKIPPED, a needle given twice with two handles
+ * counts under both, two needles under one handle add into one entry, a state reached through suffix outputs counts every value of its list, the empty needle counts once
+ * per position.  Counts are 64-bit.  Two identities follow: summing the matrix over its rows gives am_count_by_needle_batch's vector, and when every handle is
+ * < n_needles, row i sums to am_count_batch's counts_out[i].  n_needles == 0 gives n_hay empty rows; n_hay == 0 gives offsets = [0] and size 0.
+ * The records are produced and folded in HBM (csrc/am_matrix.hip) and never cross the wire; the result stays in HBM until asked for.
+ *   am_count_matrix_batch    a device-resident batch, on whatever route the automaton takes.  Record memory is bounded as in am_count_by_needle_batch (the same 1 GiB,
+ *                            the same groups of whole consecutive haystacks, a haystack that alone exceeds the bound scanned whole): a group's rows are built before the
+ *                            next group is scanned and appended, haystack index and offsets rebased.  Workspace of the fold while a group is in HBM, next to its records:
+ *                            16 bytes per slot of the group's table, which has 1.5 x min(values of the group's records, haystacks of the group x n_needles) + 64 slots
+ *                            (values = the sum of the records' value-list lengths: 24 bytes per value at most, and a few hundred bytes for `a, aa, aaa` over one
+ *                            document), 16 bytes per haystack of the group, 32 per entry of the group (its rows before and after they are ordered; 16 stay in the result,
+ *                            and 16 more per entry while the groups of a call that needed several are appended), and for rows of more than 2 048 entries up to 256 MiB of
+ *                            n_needles-bit maps.  The library's device buffers are allocated an eighth larger than asked.
+ *   am_count_matrix          the one-shot form on host slices.  A batch of 1 GiB and more goes up in segments of whole haystacks, as in am_count_by_needle; a segment's
+ *                            rows are built in HBM while the next segment is uploaded, and appended in order.
+ *   am_matches_count_matrix  the same fold over a result the caller holds (am_run_batch, am_run), for haystacks 0 .. n_hay - 1.  AM_ERR_UNSUPPORTED when the result was
+ *                            assembled on the host (no records in HBM), AM_ERR_INVALID when result and table live on different devices or when n_hay is not greater than
+ *                            the largest haystack index in the result (the records are sorted: the last one tells).
+ *   am_needle_matrix_*       size = entries of the whole matrix.  offsets (n_hay + 1) / data are host copies made on first use and owned by the result (NULL on error);
+ *                            the device_ forms are the arrays in HBM (NULL where there is nothing: no haystack, no entry).  All indices are 64-bit.
+ * Arguments are checked before any device work: AM_ERR_INVALID for null ids / batch / result / out, a case_mode that is neither AM_CASE_SENSITIVE nor AM_IGNORE_CASE,
+ * slices without memory, n_hay >= 0xFFFFFFFF.  *out is NULL after every failure. */
+typedef struct am_needle_count { uint64_t count; uint32_t needle; uint32_t haystack; } am_needle_count;   /* 16 bytes: offsets 0, 8, 12 */
+typedef struct am_needle_matrix am_needle_matrix;
+AM_API int am_count_matrix_batch(const am_needle_ids* ids, int case_mode, const am_batch* b, am_needle_matrix** out);
+AM_API int am_count_matrix(const am_needle_ids* ids, int case_mode, const am_slice* hay, size_t n_hay, am_needle_matrix** out);
+AM_API int am_matches_count_matrix(const am_matches* m, const am_needle_ids* ids, size_t n_hay, am_needle_matrix** out);
+AM_API uint64_t am_needle_matrix_size(const am_needle_matrix* x);
+AM_API uint64_t am_needle_matrix_haystacks(const am_needle_matrix* x);
+AM_API const uint64_t* am_needle_matrix_offsets(am_needle_matrix* x);
+AM_API const am_needle_count* am_needle_matrix_data(am_needle_matrix* x);
+AM_API const void* am_needle_matrix_device_offsets(const am_needle_matrix* x);
+AM_API const void* am_needle_matrix_device_data(const am_needle_matrix* x);
+AM_API void am_needle_matrix_free(am_needle_matrix* x);
+
 /* ---- Splitter: split every haystack of a batch on one separator, in HBM (src/Data/Text/AhoCorasick/Splitter.hs) ---------------
  * A Splitter is a one-needle automaton, `Aho.build [(sep, ())]` (Splitter.hs:64-67), plus the separator's length.  The scan leaves its sorted records in HBM and the
  * fold stepAccum / finalizeAccum (Splitter.hs:141-170) runs there too (csrc/am_split.hip); no record crosses the wire.  For haystack i the fragments are exactly

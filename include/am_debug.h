@@ -49,6 +49,11 @@ AM_API int am_debug_hist_adds(uint64_t* out3);
  * than the walk limit (AM_SPLIT_CHAIN_LIMIT), else about log2 of the separators kept in the longest chain.  tests/measure/splitter.py. */
 AM_API uint32_t am_debug_split_rounds(void);
 
+/* The limits the design of am_count_matrix* (csrc/am_matrix.hip) turns on: out4[0] = entries up to which a row is ordered inside one wavefront, out4[1] = entries up to which
+ * a workgroup orders it in LDS (longer rows are ranked through a bitmap of n_needles bits), out4[2] = slots of a workgroup's LDS table of (haystack, needle) keys,
+ * out4[3] = records a workgroup combines between two flushes of that table.  The tests sit on these. */
+AM_API int am_debug_needle_matrix_limits(uint32_t* out4);
+
 #ifdef __cplusplus
 }
 #endif
