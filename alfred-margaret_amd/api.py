@@ -210,6 +210,7 @@ DEBUG_ABI = {
     "am_debug_hist_adds": (C.c_int, [_vp]),
     "am_debug_split_rounds": (C.c_uint32, []),
     "am_debug_needle_matrix_limits": (C.c_int, [_vp]),
+    "am_debug_sf_unit_chunks": (C.c_uint32, [C.c_uint64, C.c_int]),
 }
 
 _libam = None
@@ -916,6 +917,14 @@ def needle_matrix_limits():
     out = (C.c_uint32 * 4)()
     check(libam().am_debug_needle_matrix_limits(out))
     return dict(zip(("wave_row", "lds_row", "lds_slots", "chunk_records"), (int(v) for v in out)))
+
+
+def sf_unit_chunks(total_bytes, n_cu=0):
+    """am_debug_sf_unit_chunks: KiB chunks per k_sf / k_dense work unit of a batch of total_bytes; n_cu = 0: the current device's compute units."""
+    uc = int(libam().am_debug_sf_unit_chunks(int(total_bytes), int(n_cu)))
+    if uc == 0:
+        raise AmError(AM_ERR_NO_DEVICE, (libam().am_last_error() or b"").decode("utf-8", "replace"))
+    return uc
 
 
 def bounds_report():

@@ -1319,6 +1319,19 @@ extern "C" int am_debug_bounds_report(uint64_t* failed_out, uint32_t* first_line
 extern "C" uint64_t am_debug_pinned_bytes(void) { return (uint64_t)g_pinned_staging_bytes.load(std::memory_order_relaxed); }
 extern "C" uint64_t am_debug_device_buffer_bytes(void) { return g_device_buffer_bytes.load(std::memory_order_relaxed); }
 
+// the unit geometry of a batch of total_bytes: sf_unit_chunks and nothing else (n_cu > 0: no device needed)
+extern "C" uint32_t am_debug_sf_unit_chunks(uint64_t total_bytes, int n_cu)
+{
+    if (n_cu <= 0) {
+        int dev = 0;
+        if (current_device(&dev) != AM_OK) return 0;
+        n_cu = g_rt.dev[dev].n_cu;
+    }
+    BatchView b{};
+    b.total = total_bytes;
+    return sf_unit_chunks(b, n_cu);
+}
+
 extern "C" int am_debug_resident_waves(float* one_ms_out, float* two_ms_out)
 {
     if (!one_ms_out || !two_ms_out) return fail(AM_ERR_INVALID, "null argument");

@@ -10,7 +10,10 @@
 // Output volume is what bounds this path: 16 bytes of records per byte of text.
 #include <hip/hip_runtime.h>
 
+#include "am_bounds.h"
 #include "am_device.h"
+
+AM_BOUNDS_TU("am_dense.hip")
 
 namespace am {
 namespace dev {
@@ -64,6 +67,7 @@ __global__ void __launch_bounds__(kDenseThreads) k_dense(AcView a, BatchView b, 
     for (uint64_t r = s0 + t; r < s1; r += kDenseThreads) {
         const Record rec = sparse[r];
         const uint32_t bit = (uint32_t)(b.offsets[rec.haystack] + rec.end_pos - 1 - unit_start);
+        AM_BOUNDS(bit < 32u * n_words);
         atomicOr(&sp_bits[bit >> 5], 1u << (bit & 31u));
     }
     __syncthreads();
@@ -133,6 +137,8 @@ __global__ void __launch_bounds__(kDenseThreads) k_dense(AcView a, BatchView b, 
         const uint32_t below = (1u << j) - 1u;
         const uint64_t at = base + un_pre[w] + __popc(un & below);
         const uint32_t sp = sp_bits[w];
+        AM_BOUNDS(at < out_offsets[u + 1]);
+        AM_BOUNDS(!((sp >> j) & 1u) || s0 + sp_pre[w] + __popc(sp & below) < s1);
         if ((sp >> j) & 1u) { out[at] = sparse[s0 + sp_pre[w] + __popc(sp & below)]; continue; }
         const uint64_t g = unit_start + p;
         const uint32_t hay = find_haystack(b, g);

@@ -54,6 +54,11 @@ AM_API uint32_t am_debug_split_rounds(void);
  * out4[3] = records a workgroup combines between two flushes of that table.  The tests sit on these. */
 AM_API int am_debug_needle_matrix_limits(uint32_t* out4);
 
+/* The work-unit geometry of the suffix-filter route (csrc/am_kernels.hip sf_unit_chunks, and nothing else): KiB chunks per k_sf / k_dense work unit of a batch of
+ * total_bytes on a device with n_cu compute units; n_cu <= 0: the current device's (0 is returned when there is none).  With n_cu > 0 the call is pure and needs no
+ * device.  The tests of the dense pass (tests/test_gpu_dense_units.py) take their batch sizes from it. */
+AM_API uint32_t am_debug_sf_unit_chunks(uint64_t total_bytes, int n_cu);
+
 #ifdef __cplusplus
 }
 #endif

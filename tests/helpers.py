@@ -396,3 +396,115 @@ def route_window_pairs(rl):
 
 def route_match_document(n):
     return "a" * (n + 7)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# Automata that contain the EMPTY needle (csrc/am_dense.hip k_dense): text whose code points are first code points of a needle about half of the time, haystack
+# cuts that put several haystacks into one 32-byte bitmap word and multi-byte code points onto word and unit boundaries, and a plain reference of what the
+# reference folds there.  tests/test_dense_units_cpu.py checks on the CPU that these are what they claim; tests/test_gpu_dense_units.py feeds them to the kernels.
+
+DENSE_WORD = 32        # bytes of text per bitmap word of k_dense
+DENSE_CHUNK = 1024     # kSfChunk: a work unit is unit_chunks of these (am.api.sf_unit_chunks)
+
+# name -> (case, needles, [(code point, weight)]): the weights of the first code points add up to about one half, a few percent of the code points complete a needle
+DENSE_SETS = {
+    "sensitive": (0, ["", "ab", "b", "éa", "日本", "𝄞"],
+                  [("a", 20), ("é", 10), ("日", 10), ("𝄞", 5), ("b", 3), ("x", 20), ("ü", 10), ("語", 10), ("💩", 7), ("本", 5), ("É", 3)]),
+    # first code points reached through lower-casings that change the byte length: U+212A (3 bytes) -> k, İ (2) -> i, U+212B (3) -> å (2), ẞ (3) -> ß (2)
+    "ignore": (1, ["", "ka", "i", "åb", "ß"],
+               [("K", 8), ("K", 8), ("k", 6), ("İ", 2), ("I", 2), ("Å", 8), ("Å", 8), ("å", 4), ("ẞ", 3),
+                ("a", 6), ("A", 4), ("b", 4), ("x", 17), ("Ж", 10), ("ж", 5), ("ü", 5)]),
+}
+DENSE_ONLY_SETS = {"empty alone": (0, [""]), "upper-case needle": (1, ["", "É"])}      # no sparse record at all; the second has sf_tiers == 0
+
+
+def dense_text(rng, n_bytes, alphabet):
+    """Valid UTF-8 of at most n_bytes (fewer by up to three): code points drawn from [(code point, weight)]."""
+    enc = [c.encode("utf-8") for c, _ in alphabet]
+    mean = sum(len(e) * w for e, (_, w) in zip(enc, alphabet)) / sum(w for _, w in alphabet)
+    out = b"".join(rng.choices(enc, weights=[w for _, w in alphabet], k=int(n_bytes / mean * 1.05) + 8))
+    assert len(out) >= n_bytes
+    cut = n_bytes
+    while (out[cut] & 0xC0) == 0x80:
+        cut -= 1
+    return out[:cut]
+
+
+def ragged_cuts(text, rng, unit_bytes=DENSE_CHUNK, big=3 << 20):
+    """Haystack offsets (np.int64, first 0, last len(text)) on code-point boundaries only, from a repeating pattern of lengths: tiny ones, 200 of 0-12 bytes, the
+    sizes around 1 KiB and 64 KiB, four haystacks that END where a multi-byte code point ends a 32-byte word, two that end so on a unit's last byte, and one of
+    `big` bytes.  A length that falls inside a code point is rounded down to its start."""
+    t = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else text
+    n = len(t)
+    multi_end = np.zeros(n + 1, dtype=bool)                      # multi_end[p]: a multi-byte code point ends with byte p - 1
+    multi_end[1:n] = ((t[:n - 1] & 0xC0) == 0x80) & ((t[1:] & 0xC0) != 0x80)
+    multi_end[n] = n > 0 and (t[n - 1] & 0xC0) == 0x80
+    at_word = np.flatnonzero(multi_end[::DENSE_WORD]) * DENSE_WORD
+    at_unit = np.flatnonzero(multi_end[::unit_bytes]) * unit_bytes
+    pattern = [0, 0, 1, 2, 3, 5, 31, 32, 33, 40] + [rng.randint(0, 12) for _ in range(200)] + [1023, 1024, 1025, 65535, 65536, 65537] + [at_word] * 4 + [at_unit] * 2 + [big]
+    cuts, at, k = [0], 0, 0
+    while at < n:
+        step = pattern[k % len(pattern)]
+        k += 1
+        if isinstance(step, np.ndarray):
+            i = int(np.searchsorted(step, at, side="right"))
+            nxt = int(step[i]) if i < len(step) else n
+        else:
+            nxt = min(n, at + step)
+            while nxt < n and (t[nxt] & 0xC0) == 0x80:
+                nxt -= 1
+        cuts.append(nxt)
+        at = nxt
+    return np.asarray(cuts, dtype=np.int64)
+
+
+def dense_reference(case, needles, text, offs):
+    """What the reference folds over a batch whose automaton holds the empty needle (Automaton.hs:373-376, 502-519), by byte comparison alone: after every
+    successful goto, i.e. wherever a non-empty PREFIX of some casing of some needle ends inside its haystack, the state's values are folded: the root's (the
+    empty needle) and one per needle that ends there.  Returns (haystack, end_pos, n_values) in batch order, end_pos relative to the haystack as in am_match."""
+    import alfred_margaret_amd as am
+    t = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else text
+    offs = np.asarray(offs, dtype=np.int64)
+    whole, prefixes = set(), set()
+    for nd in needles:
+        for c in ((am.needle_casings(nd) if case else [nd.encode("utf-8")]) if nd else []):
+            s = c.decode("utf-8")
+            whole.add(c)
+            prefixes.update(s[:k].encode("utf-8") for k in range(1, len(s) + 1))
+    folded, ends = np.zeros(len(t), dtype=bool), np.zeros(len(t), dtype=np.uint8)
+    for p in sorted(prefixes):
+        if len(p) > len(t):
+            continue
+        m = t[:len(t) - len(p) + 1] == p[0]
+        for k in range(1, len(p)):
+            m &= t[k:len(t) - len(p) + 1 + k] == p[k]
+        e = np.flatnonzero(m) + len(p) - 1                         # last byte of every occurrence
+        e = e[e - len(p) + 1 >= offs[np.searchsorted(offs, e, side="right") - 1]]      # ... that starts in the haystack it ends in
+        folded[e] = True
+        if p in whole:
+            ends[e] += 1
+    g = np.flatnonzero(folded)
+    hay = np.searchsorted(offs, g, side="right") - 1
+    n_values = ends[g].astype(np.int64) + (1 if "" in needles else 0)
+    keep = n_values > 0
+    return hay[keep], (g - offs[hay] + 1)[keep], n_values[keep]
+
+
+def dense_placements(case, needles, text, offs, unit_bytes):
+    """How often a batch holds what k_dense can get wrong: {placement: count}.  `first` = a multi-byte code point that is (a casing of) a first code point of a needle."""
+    t = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else text
+    offs = np.asarray(offs, dtype=np.int64)
+    firsts = [nd[0] for nd in needles if nd]
+    hay, end, _ = dense_reference(case, [""] + firsts, t, offs)
+    g = offs[hay] + end - 1                                        # last bytes of the first code points
+    multi = g[(t[g] & 0xC0) == 0x80]
+    hay_ends = offs[1:][np.diff(offs) > 0] - 1
+    word_of_start = offs[:-1] // DENSE_WORD
+    starts_per_word = np.bincount(word_of_start[offs[:-1] < len(t)].astype(np.int64))
+    empty_inside = (np.diff(offs) == 0) & (offs[:-1] % DENSE_WORD != 0) & (offs[:-1] < len(t))
+    n_cp = int(((t & 0xC0) != 0x80).sum())
+    return {"first ends a word": int((multi % DENSE_WORD == DENSE_WORD - 1).sum()), "first ends on the first byte of a word": int((multi % DENSE_WORD == 0).sum()),
+            "first ends a unit": int((multi % unit_bytes == unit_bytes - 1).sum()),
+            "first ends a haystack and a word": int(np.intersect1d(multi[multi % DENSE_WORD == DENSE_WORD - 1], hay_ends).size),
+            "words with three haystacks": int((starts_per_word >= 3).sum()), "empty haystacks inside a word": int(empty_inside.sum()),
+            "first share": len(g) / max(n_cp, 1)}
