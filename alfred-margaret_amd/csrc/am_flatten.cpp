@@ -947,14 +947,24 @@ int flatten(const RefArrays& ref, int case_mode, std::vector<uint8_t>& image, st
     h.n_edge_maps = 0; h.sf_row_first = row_first;
     h.sf_tiers = 0;
     size_t total_keys = 0;
-    for (int t = 0; t < 4; t++) { if (!tier_entries[t].empty()) h.sf_tiers |= 1u << t; total_keys += tier_entries[t].size(); }
     {
+        // the filter's keys: every suffix under bloom_key (am_image.h) -- IgnoreCase: modulo the ASCII case bit, so case variants that differ in bit 5 of a byte
+        // are one key.  total_keys, which sizes the filter, counts the DISTINCT keys.
+        std::vector<uint32_t> fkeys[4];
+        for (int t = 0; t < 4; t++) {
+            if (!tier_entries[t].empty()) h.sf_tiers |= 1u << t;
+            fkeys[t].reserve(tier_entries[t].size());
+            for (const TierEntry& e : tier_entries[t]) fkeys[t].push_back(bloom_tier_key(e.key, (uint32_t)t + 1, ic));
+            std::sort(fkeys[t].begin(), fkeys[t].end());
+            fkeys[t].erase(std::unique(fkeys[t].begin(), fkeys[t].end()), fkeys[t].end());
+            total_keys += fkeys[t].size();
+        }
         uint32_t lw = log2_ceil((total_keys * 16 + 31) / 32);
         lw = std::max(8u, std::min(kSfMaxBloomLog2Words, lw));
         h.sf_bloom_log2_words = lw;
         std::vector<uint32_t> bloom((size_t)1 << lw, 0);
         for (int t = 0; t < 4; t++)
-            for (const TierEntry& e : tier_entries[t]) { const uint32_t hh = bloom_hash(e.key, (uint32_t)t + 1); bloom[bloom_word(hh, lw)] |= bloom_mask(hh); }
+            for (const uint32_t key : fkeys[t]) { const uint32_t hh = bloom_hash(key, (uint32_t)t + 1); bloom[bloom_word(hh, lw)] |= bloom_mask(hh); }
         h.off_bloom = blob.put(bloom);
     }
     for (int t = 0; t < 3; t++) {       // 1..3-byte needles: plain open addressing (rare)

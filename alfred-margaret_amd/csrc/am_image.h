@@ -34,7 +34,7 @@
 namespace am {
 
 constexpr uint32_t kImageMagic = 0x31474D41u;   // "AMG1"
-constexpr uint32_t kImageVersion = 17;
+constexpr uint32_t kImageVersion = 18;
 constexpr uint32_t kUnicodeLowerVersion = 0x0E00;   // Unicode 14.0 (major << 8 | minor): the simple-lowercase table baked into IgnoreCase images (ImageHeader::flags bits 0-15)
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint64_t kWildcard = 0x200000ull;     // Automaton.hs:130-131
@@ -158,6 +158,9 @@ struct alignas(64) SfSlot {
 };
 constexpr uint32_t kSlotOccupied = 1u, kSlotChildCopy = 2u;
 
+constexpr uint32_t kBloomCaseBits = 0x20202020u;      // the ASCII case bit of four bytes (bloom_key)
+constexpr uint32_t kSfKeyFold = 0x20u;                // SfView::tiers: the filter's keys are folded (every IgnoreCase image with keys)
+
 struct SfView {
     const uint32_t* bloom;
     const u32x2* tier[3];    // exact tables for needles (variants) of exactly 1, 2, 3 bytes
@@ -170,7 +173,7 @@ struct SfView {
     const SfSlot* t4_slots;  // 2 per bucket, same index as the hot slot
     const SfNode* nodes;
     const SfEdge* edges;
-    uint32_t bloom_log2_words, tiers;
+    uint32_t bloom_log2_words, tiers;      // tiers: ImageHeader::sf_tiers | kSfKeyFold when the filter's keys are folded (bloom_key)
     uint32_t tier_log2_cap[4];
     uint32_t n_nodes;
     uint32_t t4_children;    // the table holds five-byte child entries of heavy depth-4 nodes (sf_probe_children)
@@ -242,7 +245,7 @@ inline SfView make_sf_view(const void* base, const ImageHeader& h)
     for (int t = 0; t < 4; t++) v.tier_log2_cap[t] = h.tier_log2_cap[t];
     v.nodes = (const SfNode*)(b + h.off_nodes);
     v.edges = (const SfEdge*)(b + h.off_edges);
-    v.bloom_log2_words = h.sf_bloom_log2_words; v.tiers = h.sf_tiers; v.n_nodes = h.sf_n_nodes;
+    v.bloom_log2_words = h.sf_bloom_log2_words; v.tiers = h.sf_tiers | (h.case_mode == 1 && h.sf_tiers ? kSfKeyFold : 0u); v.n_nodes = h.sf_n_nodes;
     v.t4_children = h.sf_t4_children;
     return v;
 }
@@ -297,6 +300,15 @@ AM_HD uint32_t fold_dword(uint32_t x)
 constexpr uint32_t kBloomMul = 0x9E3779B1u;
 constexpr uint32_t kBloomMaskLog2 = 9;                          // 512 masks = 2 KiB of LDS
 constexpr uint32_t kBloomMasks = 1u << kBloomMaskLog2;
+// The KEY of a window (image version 18).  CaseSensitive: the window.  IgnoreCase: the window with bit 5 of every byte set.  An IgnoreCase image holds every case
+// variant of its needles' suffixes (É next to é, А next to а, U+212A next to k), and many variant pairs differ in bit 5 of one byte only (C3 89 / C3 A9,
+// D0 90..9F / D0 B0..BF, CE 91..9F / CE B1..BF): under this key each such pair is ONE filter key, and a filter with fewer keys passes fewer false positions.
+// Exact because the filter may only pass too much: fold_dword sets bit 5 and nothing else, and only in bytes A-Z, so for a text window t and a suffix s with
+// fold(t) == s, t | 0x20202020 == fold(t) | 0x20202020 == s | 0x20202020.  The flattener inserts the key of every suffix, the scans test the key of every
+// window; what passes is probed and resolved with the exact fold as before.  (`@` and '`', `[` and `{` ... now share a key: a candidate now and then.)
+// A tier-t key (t < 4) is the top t bytes of the window's key, as it was of the window: bloom_tier_key.
+AM_HD uint32_t bloom_key(uint32_t w, bool ignore_case) { return ignore_case ? w | kBloomCaseBits : w; }
+AM_HD uint32_t bloom_tier_key(uint32_t key, uint32_t tier, bool ignore_case) { return ignore_case ? key | (kBloomCaseBits >> (8u * (4u - tier))) : key; }
 AM_HD uint32_t bloom_hash(uint32_t key, uint32_t tier) { return (key + (4u - tier) * 0x7F4A7C15u) * kBloomMul; }
 AM_HD uint32_t bloom_word(uint32_t h, uint32_t log2_words) { return h >> (32u - log2_words); }
 AM_HD uint32_t bloom_mask_index(uint32_t h) { return (h >> 2) & (kBloomMasks - 1u); }
@@ -929,9 +941,11 @@ AM_HD bool sf_verify(const SfView& s, const uint8_t* text, uint64_t gpos, uint64
 // `bloom` may point to LDS (device) or to the image (host checker); `masks` = the kernel's LDS copy of the mask table or
 // null.  The kernel's hot loop uses a batched form of the tier-4 test (all LDS reads of a lane in flight together) and
 // calls sf_filter_short only for automata that contain needles shorter than 4 bytes.
+// `tiers` = SfView::tiers: which tiers exist, and kSfKeyFold when the filter holds folded keys (bloom_key); `w` = the window, case-folded under IgnoreCase.
 AM_HD bool sf_filter_short(const uint32_t* bloom, uint32_t log2_words, uint32_t tiers, uint32_t w, const uint32_t* masks = nullptr)
 {
     bool hit = false;
+    w = bloom_key(w, (tiers & kSfKeyFold) != 0u);
     for (uint32_t t = 1; t <= 3; t++) {
         if (tiers & (1u << (t - 1))) {
             const uint32_t h = bloom_hash(w >> (8u * (4u - t)), t);
@@ -942,7 +956,7 @@ AM_HD bool sf_filter_short(const uint32_t* bloom, uint32_t log2_words, uint32_t 
 }
 AM_HD bool sf_filter_window(const uint32_t* bloom, uint32_t log2_words, uint32_t tiers, uint32_t w)
 {
-    const uint32_t h = bloom_hash(w, 4);
+    const uint32_t h = bloom_hash(bloom_key(w, (tiers & kSfKeyFold) != 0u), 4);
     bool hit = (tiers & 8u) && bloom_hit(bloom[bloom_word(h, log2_words)], h);
     if (tiers & 7u) hit = hit || sf_filter_short(bloom, log2_words, tiers, w);
     return hit;

@@ -72,8 +72,8 @@ constexpr uint32_t kSfEpochChunks = 16;          // the ring is drained every 16
 constexpr int kSfStage = 1056;                   // per-wave copy of the current chunk (folded): 8 bytes before it at offset 8, the chunk at 16, padding
 constexpr uint32_t kSfMaskBytes = kBloomMasks * 4u;      // the Bloom mask table: first thing in LDS, the filter words follow
 
-// ILP: 2 = a probe round always looks at two candidates per lane (up to 128 per round: automata with many needles, ~83 candidates per KiB on the
-// benchmark text); 1 = rounds of at most 64 candidates look at one per lane -- half the probe's instructions -- chosen for automata with a small
+// ILP: 2 = a probe round always looks at two candidates per lane (up to 128 per round: automata with many needles, ~71 candidates per KiB on the
+// benchmark text -- 83 before the filter's keys were folded, image version 18); 1 = rounds of at most 64 candidates look at one per lane -- half the probe's instructions -- chosen for automata with a small
 // 4-byte-suffix table, which leave a handful of candidates per chunk (cfg2: +4.7 %; the same branches cost cfg3 1.5 %, hence two instantiations).
 //
 // Work unit = `unit_chunks` consecutive 1-KiB chunks.  A wavefront starts with unit (workgroup, wave) and draws every further
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
     uint32_t wq_n = 0;                                     // parked walkers (uniform)
     (void)stage_all; (void)q1_all; (void)q2_all;
     const uint64_t n_waves = (uint64_t)gridDim.x * kSfWaves;
-    const uint32_t log2_words = s.bloom_log2_words, tiers = s.tiers;
+    const uint32_t log2_words = s.bloom_log2_words, tiers = s.tiers & ~kSfKeyFold;      // (the filter keys of a chunk are folded once, below: sf_filter_short need not)
     const uint32_t UC = o.unit_chunks;
     const uint64_t n_units = (n_chunks + UC - 1) / UC;
     uint64_t nval = 0;
@@ -608,7 +608,9 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
             if (IC) { d1 = fold_dword(d1); d2 = fold_dword(d2); d3 = fold_dword(d3); d4 = fold_dword(d4); }
             // the 4 bytes before the lane's 16: the lane below's last dword (wave_shr:1; lane 0 keeps `old` = the carry)
             const uint32_t d0 = (uint32_t)__builtin_amdgcn_update_dpp((int)carry4, (int)d4, 0x138, 0xf, 0xf, false);
-            const uint32_t d[5] = {d0, d1, d2, d3, d4};
+            // what the filter hashes (bloom_key): under IgnoreCase the bytes modulo the ASCII case bit, five ORs per chunk and nothing per position; the
+            // staged copy above and everything behind the filter keep the exact fold
+            const uint32_t f[5] = {bloom_key(d0, IC), bloom_key(d1, IC), bloom_key(d2, IC), bloom_key(d3, IC), bloom_key(d4, IC)};
             lds_write_u32x4(stage + 16u + lane * 16u, make_uint4(d1, d2, d3, d4));
             if (lane == 0) lds_write_u32x2(stage + 8u, make_uint2(carry3, carry4));
             if (!last_of_unit) {                                  // the next chunk follows this one: its carry is this chunk's tail
@@ -629,7 +631,7 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
 #pragma unroll
                 for (int k = 0; k < 16; k++) {
                     const int j = k >> 2, sh = k & 3;      // window = bytes k-3..k of the lane's 16, newest byte on top
-                    const uint32_t w = sh == 3 ? d[j + 1] : __builtin_amdgcn_alignbyte(d[j + 1], d[j], sh + 1);
+                    const uint32_t w = sh == 3 ? f[j + 1] : __builtin_amdgcn_alignbyte(f[j + 1], f[j], sh + 1);
                     h[k] = w * kBloomMul;
                 }
 #pragma unroll
@@ -645,7 +647,7 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
 #pragma unroll
                 for (int k = 0; k < 16; k++) {
                     const int j = k >> 2, sh = k & 3;
-                    const uint32_t w = sh == 3 ? d[j + 1] : __builtin_amdgcn_alignbyte(d[j + 1], d[j], sh + 1);
+                    const uint32_t w = sh == 3 ? f[j + 1] : __builtin_amdgcn_alignbyte(f[j + 1], f[j], sh + 1);
                     if (sf_filter_short(bloom, log2_words, tiers, w, masks)) cand |= 1u << k;
                 }
             }

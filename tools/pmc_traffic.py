@@ -49,6 +49,6 @@ lines = ["# %s -- HBM traffic of the dominant kernel per workload (k_sf; natural
 for w, e in out["workloads"].items():
     lines.append("| %s | %.2f GiB | %.0f | %.0f | %.3f |" % (w, e["launch_bytes"] / 2**30, e["fetch_size_kib"], e["write_size_kib"], e["hbm_bytes_per_scanned_byte"]))
 lines += ["", "Raw per-kernel averages: profiles/history/%s_pmc_traffic_<workload>.txt.  The correction (a 128-byte streaming request is counted as 64 bytes by FETCH_SIZE on gfx950)" % TAG,
-          "is the one /opt/skills/guides/MI355X_MICROARCH.md prescribes; `bench.py` puts `hbm_bytes_per_scanned_byte` x the bytes of its launch into `roofline.traffic`.", ""]
+          "is the one the MI355X microarchitecture guide prescribes; `bench.py` puts `hbm_bytes_per_scanned_byte` x the bytes of its launch into `roofline.traffic`.", ""]
 open(os.path.join(ROOT, "profiles", "%s_pmc_traffic.md" % TAG), "w").write("\n".join(lines))
 print(json.dumps(out["workloads"], indent=1))
