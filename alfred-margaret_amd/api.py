@@ -211,6 +211,7 @@ DEBUG_ABI = {
     "am_debug_split_rounds": (C.c_uint32, []),
     "am_debug_needle_matrix_limits": (C.c_int, [_vp]),
     "am_debug_sf_unit_chunks": (C.c_uint32, [C.c_uint64, C.c_int]),
+    "am_debug_sf_last_variant": (C.c_uint32, []),
 }
 
 _libam = None
@@ -925,6 +926,23 @@ def sf_unit_chunks(total_bytes, n_cu=0):
     if uc == 0:
         raise AmError(AM_ERR_NO_DEVICE, (libam().am_last_error() or b"").decode("utf-8", "replace"))
     return uc
+
+
+SF_MODES = ("count", "emit", "any", "ids")
+
+
+def decode_sf_variant(word):
+    """The word of am_debug_sf_last_variant (include/am_debug.h) as a dict of k_sf's template arguments; None for 0 (no k_sf launch)."""
+    word = int(word)
+    if not word & 1:
+        return None
+    return {"ic": bool(word & 2), "mode": SF_MODES[(word >> 2) & 3], "ilp": (word >> 4) & 3, "lw": (word >> 16) & 255, "short": bool(word & 64), "dbg": bool(word & 128),
+            "light": bool(word & 256), "children": bool(word & 512)}
+
+
+def sf_last_variant():
+    """am_debug_sf_last_variant: the k_sf instantiation this process launched last, as decode_sf_variant gives it; None when none ran since the last read (the read clears)."""
+    return decode_sf_variant(libam().am_debug_sf_last_variant())
 
 
 def bounds_report():

@@ -1332,6 +1332,9 @@ extern "C" uint32_t am_debug_sf_unit_chunks(uint64_t total_bytes, int n_cu)
     return sf_unit_chunks(b, n_cu);
 }
 
+// which k_sf instantiation did launch_sf_t choose?  The word launch_sf_v left at its last launch; reading clears it
+extern "C" uint32_t am_debug_sf_last_variant(void) { return take_sf_last_variant(); }
+
 extern "C" int am_debug_resident_waves(float* one_ms_out, float* two_ms_out)
 {
     if (!one_ms_out || !two_ms_out) return fail(AM_ERR_INVALID, "null argument");

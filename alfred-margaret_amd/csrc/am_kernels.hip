@@ -865,6 +865,13 @@ static uint32_t sf_wq_cap(const SfView& s, int waves)
 }
 size_t sf_lds_bytes(const SfView& s) { return sf_lds_bytes_w(s, kSfWaves); }
 
+// The template arguments of the calling process's last k_sf launch (am_debug_sf_last_variant, include/am_debug.h: the tests of launch_sf_t's choice read it);
+// 0 = none since the last read.
+constexpr uint32_t kSfVariantValid = 1u, kSfVariantIc = 2u, kSfVariantModeShift = 2, kSfVariantIlpShift = 4, kSfVariantShort = 1u << 6, kSfVariantDbg = 1u << 7,
+                   kSfVariantLight = 1u << 8, kSfVariantChildren = 1u << 9, kSfVariantLwShift = 16;
+static std::atomic<uint32_t> g_sf_last_variant{0};
+uint32_t take_sf_last_variant() { return g_sf_last_variant.exchange(0, std::memory_order_relaxed); }
+
 template <bool IC, int MODE, int ILP, int LW, bool SHORT, bool DBG = false, int NT = kSfThreads, bool CHILDREN = false>
 static hipError_t launch_sf_v(const SfView& s, const BatchView& b, const ScanOut& o, int n_cu, hipStream_t st)
 {
@@ -886,6 +893,9 @@ static hipError_t launch_sf_v(const SfView& s, const BatchView& b, const ScanOut
     const uint64_t need = (n_units + waves_per_wg - 1) / waves_per_wg;
     if (blocks > need) blocks = need;
     if (blocks == 0) return hipSuccess;
+    g_sf_last_variant.store(kSfVariantValid | (IC ? kSfVariantIc : 0u) | ((uint32_t)MODE << kSfVariantModeShift) | ((uint32_t)ILP << kSfVariantIlpShift) | (SHORT ? kSfVariantShort : 0u) |
+                            (DBG ? kSfVariantDbg : 0u) | (NT == kSfLightThreads ? kSfVariantLight : 0u) | (CHILDREN ? kSfVariantChildren : 0u) | ((uint32_t)LW << kSfVariantLwShift),
+                            std::memory_order_relaxed);
     ScanOut oo = o;
     oo.wq_cap = wq_cap;
     oo.wq_iters = kSfWqIters;

@@ -59,6 +59,13 @@ AM_API int am_debug_needle_matrix_limits(uint32_t* out4);
  * device.  The tests of the dense pass (tests/test_gpu_dense_units.py) take their batch sizes from it. */
 AM_API uint32_t am_debug_sf_unit_chunks(uint64_t total_bytes, int n_cu);
 
+/* The k_sf instantiation the calling process's last suffix-filter launch ran (csrc/am_kernels.hip launch_sf_t chooses among about thirty from the image's header, the
+ * mode and the batch size; a caller cannot see the choice).  Bit 0: valid; bit 1: IgnoreCase; bits 2-3: mode (0 count, 1 emit, 2 any, 3 ids); bits 4-5: ILP (1 or 2);
+ * bit 6: SHORT (tier probes for needles of 1-3 bytes); bit 7: DBG (AM_SF_TRACE); bit 8: the light configuration (256-thread workgroups); bit 9: CHILDREN;
+ * bits 16-23: LW (0 or 15).  Reading clears the word: 0 = no k_sf launch since the last read (another kernel took the call, or nothing was launched: an empty batch,
+ * an automaton without suffix keys).  tests/test_gpu_sf_variants.py. */
+AM_API uint32_t am_debug_sf_last_variant(void);
+
 #ifdef __cplusplus
 }
 #endif

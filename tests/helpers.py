@@ -508,3 +508,158 @@ def dense_placements(case, needles, text, offs, unit_bytes):
             "first ends a haystack and a word": int(np.intersect1d(multi[multi % DENSE_WORD == DENSE_WORD - 1], hay_ends).size),
             "words with three haystacks": int((starts_per_word >= 3).sum()), "empty haystacks inside a word": int(empty_inside.sum()),
             "first share": len(g) / max(n_cp, 1)}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# Needle families that put an automaton's image into each cell of launch_sf_t's rule (csrc/am_kernels.hip: ILP, LW, SHORT, CHILDREN), and texts that hold what a
+# k_sf instantiation can get wrong: verbatim needles, near misses that pass the 4-byte suffix filter and die later, cuts inside needles and next to KiB boundaries.
+# tests/test_sf_variants_cpu.py checks on the CPU that every family sits in the cell it claims; tests/test_gpu_sf_variants.py feeds them to the kernels.
+
+SF_FAMILIES = {"small": 2000, "mid": 34000, "large": 60000, "dict": 20000, "forked": 40000}      # name -> needles; "<name>+short" adds SF_SHORT_NEEDLES
+SF_SHORT_NEEDLES = ["~", "q7", "z9k", "ж", "語", "é5"]                          # 1, 2, 3 bytes of ASCII; 2, 3, 3 bytes with a multi-byte code point; none of their rare bytes is in SF_FILLER
+SF_SHORT_UPPER = ["~", "Q7", "Z9K", "Ж", "語", "É5"]
+SF_FILLER = "abcdefghijklmnopqrstuvwxyz" + "ABCDEFGHIJKLMNOPQRSTUVWXYZ" + " ,.0123" + "яЯåÅσΣ𝄞ß"
+SF_SWAP = {1: "xv", 2: "дю", 3: "本日", 4: "💩𝄢"}                             # a near miss replaces a code point by another of the same byte length
+_SF_NEEDLES = {}
+
+
+def sf_family_needles(family):
+    """The needles of a family, lower case, distinct, deterministic.  small / mid / large: random a-z words of 5-12 letters plus 200 lower-cased words of 2-6 code points
+    (>= 4 bytes) over the non-ASCII alphabets of ALPHABETS; dict: the first 20 000 needles of the natural-language benchmark dictionary; forked: 20 000 random 4-letter
+    stems, each behind two different letters and 0-6 random ones before those -- few suffix keys (a filter below 2^15 words), every suffix node heavy (a suffix table
+    beyond 2^15 buckets once the child entries are in it)."""
+    if family not in _SF_NEEDLES:
+        name, _, short = family.partition("+")
+        assert name in SF_FAMILIES and short in ("", "short"), family
+        if name == "dict":
+            from alfred_margaret_amd import synth
+            ns = list(synth.needles_for("natural_100k_10GiB")[:SF_FAMILIES[name]])
+        elif name == "forked":
+            rng, az, stems, seen = random.Random("sf-forked"), "abcdefghijklmnopqrstuvwxyz", set(), set()
+            while len(stems) < SF_FAMILIES[name] // 2:
+                stems.add("".join(rng.choice(az) for _ in range(4)))
+            for s in sorted(stems):
+                for f in rng.sample(az, 2):
+                    seen.add("".join(rng.choice(az) for _ in range(rng.randint(0, 6))) + f + s)
+            ns = sorted(seen)
+            rng.shuffle(ns)
+        else:
+            rng = random.Random("sf-" + name)
+            seen = set()
+            while len(seen) < 200:
+                w = oracle.lower_utf8("".join(rng.choice(rng.choice(ALPHABETS[1:3])) for _ in range(rng.randint(2, 6)))).decode("utf-8")
+                if len(w.encode("utf-8")) >= 4 and not w.isascii():
+                    seen.add(w)
+            while len(seen) < 200 + SF_FAMILIES[name]:
+                seen.add("".join(rng.choice("abcdefghijklmnopqrstuvwxyz") for _ in range(rng.randint(5, 12))))
+            ns = sorted(seen)
+            rng.shuffle(ns)
+        _SF_NEEDLES[family] = ns + (SF_SHORT_NEEDLES if short else [])
+    return _SF_NEEDLES[family]
+
+
+def _sf_upper_partners():
+    """{lower-case code point: [code points that lower to it]} over the letters of ALPHABETS (U+212A -> k, U+212B -> å, ẞ -> ß change the byte length) and A-Z."""
+    out = {}
+    for c in sorted(set("".join(ALPHABETS)) | set("ABCDEFGHIJKLMNOPQRSTUVWXYZ")):
+        low = oracle.lower_utf8(c).decode("utf-8")
+        if low != c and len(low) == 1:
+            out.setdefault(low, []).append(c)
+    return out
+
+
+def _cp_floor(t, c):
+    while 0 < c < len(t) and (t[c] & 0xC0) == 0x80:
+        c -= 1
+    return c
+
+
+def sf_near_miss(rng, needle, in_suffix):
+    """`needle` with one code point replaced by another of the same byte length (one byte, for the a-z words): inside its last four bytes, where the filter or the
+    probe refuses it, or before them, where it passes both and dies in the resolve.  A needle too short for the latter is changed in its suffix."""
+    cps = list(needle)
+    ends = np.cumsum([len(c.encode("utf-8")) for c in cps])
+    total = int(ends[-1])
+    inside = [i for i in range(len(cps)) if ends[i] > total - 4]
+    before = [i for i in range(len(cps)) if ends[i] <= total - 4]
+    i = rng.choice(inside if in_suffix or not before else before)
+    a, b = SF_SWAP[len(cps[i].encode("utf-8"))]
+    cps[i] = b if cps[i] == a else a
+    return "".join(cps)
+
+
+def sf_text(family, case, n_bytes, seed=0):
+    """(text, offsets np.int64) of exactly n_bytes of valid UTF-8 for a family: about 30 % verbatim needles (under IgnoreCase a third of them with random upper-casing
+    through every partner of _sf_upper_partners), 20 % near misses (half of them changed before the last four bytes), the rest filler over SF_FILLER; every 40th piece is
+    one of SF_SHORT_NEEDLES (or its upper case), whether or not the family holds them.  The haystacks: ragged_cuts' pattern, cuts at multiples of 1 024 +- 1, cuts in
+    the middle of forty planted needles, empty haystacks, and at the end three haystacks of filler only and three of near misses only."""
+    rng = random.Random("sf-text-%s-%d-%d-%d" % (family, case, n_bytes, seed))
+    needles = sf_family_needles(family.partition("+")[0])
+    partners = _sf_upper_partners()
+
+    def filler():
+        return "".join(rng.choice(SF_FILLER) for _ in range(rng.randint(1, 24)))
+
+    def cased(nd):
+        if not case or rng.random() < 0.67:
+            return nd
+        return "".join(rng.choice(partners[c]) if c in partners and rng.random() < 0.4 else c for c in nd)
+
+    tail = [filler().encode("utf-8") + filler().encode("utf-8") for _ in range(3)]
+    tail += ["".join(sf_near_miss(rng, rng.choice(needles), k % 2 == 0) for k in range(4)).encode("utf-8") for _ in range(3)]
+    room = n_bytes - sum(len(t) for t in tail)
+    assert room > 2048, n_bytes
+    parts, planted, at, k = [], [], 0, 0
+    while True:
+        k += 1
+        r = rng.random()
+        if k % 40 == 0:
+            i = rng.randrange(len(SF_SHORT_NEEDLES))
+            p = (SF_SHORT_UPPER[i] if case and rng.random() < 0.5 else SF_SHORT_NEEDLES[i]).encode("utf-8")
+        elif r < 0.40:
+            p = cased(rng.choice(needles)).encode("utf-8")
+            planted.append((at, len(p)))
+        elif r < 0.67:
+            p = sf_near_miss(rng, rng.choice(needles), rng.random() < 0.5).encode("utf-8")
+        else:
+            p = filler().encode("utf-8")
+        if at + len(p) > room:
+            break
+        parts.append(p)
+        at += len(p)
+    parts.append(b"X" * (room - at))
+    body = b"".join(parts)
+    t = np.frombuffer(body, dtype=np.uint8)
+    cuts = [ragged_cuts(t, rng, big=1 << 20)]
+    kib = [k * 1024 + d for k in rng.sample(range(1, room // 1024), min(12, room // 1024 - 1)) for d in (-1, 1)]
+    inside = [s + n // 2 for s, n in rng.sample(planted, min(40, len(planted)))]
+    cuts.append(np.asarray([_cp_floor(t, c) for c in kib + inside], dtype=np.int64))
+    offs = np.sort(np.concatenate(cuts))
+    offs = np.concatenate([offs, room + np.cumsum([len(x) for x in tail])]).astype(np.int64)
+    text = body + b"".join(tail)
+    assert len(text) == n_bytes and offs[0] == 0 and offs[-1] == n_bytes
+    return text, offs
+
+
+def sf_oracle_records(machine, case, text, offs):
+    """The oracle over every haystack of a batch: (haystack, matchPos, value) as arrays, in fold order."""
+    hay, pos, val = [], [], []
+    for i in range(len(offs) - 1):
+        if offs[i + 1] > offs[i]:
+            p, v = machine.run_list(case, text, int(offs[i]), int(offs[i + 1] - offs[i]))
+            if len(p):
+                hay.append(np.full(len(p), i, np.uint32)); pos.append(p); val.append(v)
+    if not hay:
+        return np.zeros(0, np.uint32), np.zeros(0, np.uint64), np.zeros(0, np.uint32)
+    return np.concatenate(hay), np.concatenate(pos), np.concatenate(val)
+
+
+def sf_expand(hay, state, end, values_off, values):
+    """Records -> (haystack, matchPos, value) arrays in fold order (expand_records, vectorised)."""
+    st = np.asarray(state, dtype=np.int64)
+    lens = (values_off[st + 1] - values_off[st]).astype(np.int64)
+    n = int(lens.sum())
+    if n == 0:
+        return np.zeros(0, np.uint32), np.zeros(0, np.uint64), np.zeros(0, np.uint32)
+    within = np.arange(n) - np.repeat(np.cumsum(lens) - lens, lens)
+    return np.repeat(np.asarray(hay, np.uint32), lens), np.repeat(np.asarray(end, np.uint64), lens), values[np.repeat(values_off[st].astype(np.int64), lens) + within]

@@ -23,7 +23,9 @@ def test_every_declared_symbol_is_exported_and_bound():
         assert hasattr(lib, n), n
     assert sorted(am.api.ABI) == names      # the Python binding table covers the header exactly
     assert sorted(am.api.DEBUG_ABI) == _declared("am_debug.h")
-    assert len(am.api.DEBUG_ABI) == 13 and "am_debug_sf_unit_chunks" in am.api.DEBUG_ABI and hasattr(lib, "am_debug_sf_unit_chunks")
+    assert len(am.api.DEBUG_ABI) == 14
+    for n in ("am_debug_sf_unit_chunks", "am_debug_sf_last_variant"):
+        assert n in am.api.DEBUG_ABI and hasattr(lib, n), n
 
 
 def test_the_library_exports_the_two_headers_and_nothing_else():
