@@ -663,3 +663,385 @@ def sf_expand(hay, state, end, values_off, values):
         return np.zeros(0, np.uint32), np.zeros(0, np.uint64), np.zeros(0, np.uint32)
     within = np.arange(n) - np.repeat(np.cumsum(lens) - lens, lens)
     return np.repeat(np.asarray(hay, np.uint32), lens), np.repeat(np.asarray(end, np.uint64), lens), values[np.repeat(values_off[st].astype(np.int64), lens) + within]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# LONG needles: 17 bytes to 66 000, on every scan and Replacer route.  What depends on the longest needle:
+#   k_sf resolve (csrc/am_image.h): the slot line settles a needle of up to 4 + 1 + 16 = 21 bytes (sf_resolve_head :727-734: the 4-byte suffix, the single
+#     edge's selector byte and a label of at most kMaxSkip = 16); every step of sf_resolve_walk consumes at most 1 + 16 = 17 bytes (:847, :856), which it reads
+#     back from global memory at gpos - depth (:809, :835), guarded at the haystack's start by depth + 1 + skip > avail (:847), avail a u32 clamp (:676).
+#   the walker queue (csrc/am_kernels.hip): count and emit park a walker that is not done after kSfWqIters = 2 steps (:70, :256-258); walk_parked (:173) takes
+#     it to the end; a parked walker that finds nothing leaves state == kNone in its slot (:302), one that finds a deeper end patches its record (:198).
+#   k_dfa / k_ac warm-up, range_window's overlap, the segments of am_run and the Replacer's reach ov (csrc/am_replacer.cpp:387, :658, :835-838).
+# So, for a needle that is the ONLY path from its 4-byte suffix (the independent random needles below): 21 | 22 bytes = the slot line settles it | the first
+# walk step, 38 | 39 = one step | two, 55 | 56 = two steps (inline) | a third (parked).  The suffixes of one base string at the same lengths are a CHAIN of
+# needle ends instead: every end splits the edge, so the walk to the 57-byte needle passes nine shallower ends, parks after the second and replaces `prior`.
+# tests/test_long_needles_cpu.py checks on the CPU that all of this is what it claims; tests/test_gpu_long_needles.py feeds it to the kernels.
+
+LONG_ALPHABETS = ("ab", "abcdefgh", "abkåßi", "ak𝄞яß")          # 1- to 4-byte code points; k å ß i have the partners U+212A, U+212B, ẞ, İ whose lower-casing changes the byte length
+LONG_SHORT_LENGTHS = (17, 20, 21, 22, 37, 38, 39, 55, 56, 57)
+LONG_POW_LENGTHS = tuple(p + d for p in (256, 1024, 2048, 4096, 8192) for d in (-1, 0, 1))
+LONG_STEP_LENGTHS = LONG_SHORT_LENGTHS + LONG_POW_LENGTHS
+LONG_SLOT_LINE = 4 + 1 + 16            # am_image.h:727-734
+LONG_STEP = 1 + 16                     # am_image.h:856, kMaxSkip
+LONG_PARK_AFTER = 2                    # am_kernels.hip:70 kSfWqIters
+LONG_BEYOND = (16500, 66000)           # more than the light configuration's 16 chunks (am_kernels.hip:64); more than 65 535 and than a 64-chunk unit (:69)
+LONG_FORK_DEPTH = 700                  # code points of the deep forks' shared suffix
+LONG_FANOUTS = (2, 4, 5, 7)            # <= 4 edges are inline in the node record, more take a displaced row (am_image.h:812-818)
+LONG_BATCH_LIMIT = 1 << 20
+LONG_MISS_DISTANCES = (1, 5, 21, 22, 38, 39, 56)
+LONG_KIB_ENDS = (-1, 0, 1, 4, 5)
+LONG_FILLER = "mnopqrstuvwxyz ,."     # one byte each, in no alphabet and nobody's case partner
+_LONG_SETS = {}
+_LONG_TEXTS = {}
+
+
+def _exact_bytes(rng, alphabet, n_bytes):
+    """Random code points of `alphabet` that add up to exactly n_bytes (every alphabet holds a one-byte code point)."""
+    out, left = [], n_bytes
+    while left:
+        c = rng.choice([c for c in alphabet if len(c.encode("utf-8")) <= left])
+        out.append(c)
+        left -= len(c.encode("utf-8"))
+    return "".join(out)
+
+
+def _chain_base(rng, alphabet, lengths):
+    """One string of max(lengths) bytes whose suffix of exactly L bytes starts on a code point, for every L of lengths."""
+    out, have = "", 0
+    for ln in sorted(lengths):
+        out = _exact_bytes(rng, alphabet, ln - have) + out
+        have = ln
+    return out
+
+
+def _suffix_bytes(s, n_bytes):
+    b = s.encode("utf-8")
+    assert n_bytes <= len(b) and (n_bytes == len(b) or (b[len(b) - n_bytes] & 0xC0) != 0x80), n_bytes
+    return b[len(b) - n_bytes:].decode("utf-8")
+
+
+def _fork_code_points(alphabet, k):
+    """k code points with k different LAST bytes (the walk goes backwards: the last byte is the edge's selector): the alphabet's, then a-h."""
+    out = []
+    for c in alphabet + "cdefgh":
+        if c.encode("utf-8")[-1] not in [d.encode("utf-8")[-1] for d in out]:
+            out.append(c)
+    assert len(out) >= k, (alphabet, k)
+    return out[:k]
+
+
+def long_needle_sets():
+    """{name: needles}, lower case (the same list serves CaseSensitive and IgnoreCase), deterministic.  No needle is ever dropped: duplicates are kept, and
+    tests/test_long_needles_cpu.py holds every list to the byte lengths it is built for.
+      steps/<alphabet>    suffixes of one base string at LONG_STEP_LENGTHS bytes, independent random needles of the same lengths, the 57- and the 1024-byte suffix twice
+      beyond/<alphabet>   16 500 and 66 000 bytes, their suffixes of 1 025 and 8 193 bytes, their 70-byte prefixes
+      forks/<alphabet>    2, 4, 5, 7 different code points in front of a shared suffix of 700 code points and of a 9-byte suffix, and continuations of 1-40 code points
+      periodic            "ab" * 4000, "ab" * 12, "ba" * 30"""
+    if _LONG_SETS:
+        return _LONG_SETS
+    for alphabet in LONG_ALPHABETS:
+        rng = random.Random("long-steps-" + alphabet)
+        base = _chain_base(rng, alphabet, LONG_STEP_LENGTHS)
+        chain = [_suffix_bytes(base, ln) for ln in LONG_STEP_LENGTHS]
+        alone = []
+        for ln in LONG_STEP_LENGTHS:
+            while True:
+                s = _exact_bytes(rng, alphabet, ln)
+                if s[-4:] != base[-4:] and all(s[-4:] != a[-4:] for a in alone):       # last four code points of its own: the only path from its suffix
+                    break
+                if len(alphabet) == 2 and s != _suffix_bytes(base, ln):               # ("ab" has 16 such endings for 25 needles: there they share them)
+                    break
+            alone.append(s)
+        _LONG_SETS["steps/" + alphabet] = chain + alone + [_suffix_bytes(base, 57), _suffix_bytes(base, 1024)]
+    for alphabet in (LONG_ALPHABETS[0], LONG_ALPHABETS[3]):
+        rng = random.Random("long-beyond-" + alphabet)
+        ns = []
+        for total in LONG_BEYOND:
+            base = _chain_base(rng, alphabet, (1025, 8193, total))
+            head = base.encode("utf-8")[:70]
+            while (base.encode("utf-8")[len(head)] & 0xC0) == 0x80:
+                head = head[:-1]
+            head = head.decode("utf-8")
+            ns += [base, _suffix_bytes(base, 1025), _suffix_bytes(base, 8193), head + "a" * (70 - len(head.encode("utf-8")))]
+        _LONG_SETS["beyond/" + alphabet] = ns
+    for alphabet in LONG_ALPHABETS[1:]:
+        rng = random.Random("long-forks-" + alphabet)
+        ns = []
+        for shared in ("".join(rng.choice(alphabet) for _ in range(LONG_FORK_DEPTH)), _exact_bytes(rng, alphabet[:2], 9)):
+            for k in LONG_FANOUTS:
+                sep = "".join(rng.choice(alphabet) for _ in range(3))                    # the forks of different fan-outs do not share their suffix
+                stem = sep + shared
+                forks = [c + stem for c in _fork_code_points(alphabet, k)]
+                ns += forks
+                ns += ["".join(rng.choice(alphabet) for _ in range(n)) + forks[i % k] for i, n in enumerate((1, 17, 40))]
+        _LONG_SETS["forks/" + alphabet] = ns
+    _LONG_SETS["periodic"] = ["ab" * 4000, "ab" * 12, "ba" * 30]
+    return _LONG_SETS
+
+
+def _long_treatment(n_bytes, alone):
+    """What the text holds for a needle of n_bytes: (near-miss distances from the end + "middle" / "first", ends relative to a multiple of 1 024, start placement,
+    cuts).  Everything up to 1 025 bytes; above, fewer near misses and placements, so that a batch stays within LONG_BATCH_LIMIT (the kinds all stay)."""
+    if n_bytes <= 1025:
+        return LONG_MISS_DISTANCES + ("middle", "first"), (0, 5) if alone else LONG_KIB_ENDS, True, ("first", "half")
+    if alone:
+        return (56,), (0,), False, ("half",)
+    if n_bytes <= 2049:
+        return (1, 56, "middle", "first"), (-1, 0), True, ("first", "half")
+    if n_bytes <= 16500:
+        return (56, "first"), (0,), True, ("half",)
+    return (56, "first"), (0,), False, ("half",)
+
+
+def long_near_miss(needle, where):
+    """`needle` with the code point that holds the byte `where` bytes before its end ("middle": its middle byte, "first": its first code point) swapped for
+    another of the same byte length (SF_SWAP); None where the needle is shorter than that."""
+    cps = list(needle)
+    ends = np.cumsum([len(c.encode("utf-8")) for c in cps])
+    total = int(ends[-1])
+    if where == "first":
+        i = 0
+    elif where == "middle":
+        i = int(np.searchsorted(ends, total // 2, side="right"))
+    elif where > total:
+        return None
+    else:
+        i = int(np.searchsorted(ends, total - where, side="right"))
+    a, b = SF_SWAP[len(cps[i].encode("utf-8"))]
+    cps[i] = b if cps[i] == a else a
+    return "".join(cps)
+
+
+class LongText:
+    """text (bytes), offs (np.int64), and what was planted: items = [(kind, needle index, haystack index, detail)] with kind in "whole", "cased", "minus first",
+    "plus one", "cut", "near miss", "ends at", "starts at", "periodic", "mixed", "empty"."""
+
+    def __init__(self, text, offs, items):
+        self.text, self.offs, self.items = text, offs, items
+
+    def hays(self):
+        return [self.text[self.offs[i]:self.offs[i + 1]] for i in range(len(self.offs) - 1)]
+
+
+def long_text_parts(name):
+    """Batches the text of a set comes in: the steps sets take two, needles of up to 2 049 bytes and the longer ones, to stay within LONG_BATCH_LIMIT."""
+    return 2 if name.startswith("steps/") else 1
+
+
+def long_needle_plan(name, case, seed=0, part=0):
+    """The LongText behind long_needle_text."""
+    key = (name, case, seed, part)
+    assert 0 <= part < long_text_parts(name)
+    if key in _LONG_TEXTS:
+        return _LONG_TEXTS[key]
+    needles = long_needle_sets()[name]
+    rng = random.Random("long-text-%s-%d-%d-%d" % key)
+    partners = _sf_upper_partners()
+    chain_len = len(LONG_STEP_LENGTHS) if name.startswith("steps/") else 0
+    hays, items = [], []
+    at = [0]
+
+    def add(kind, i, detail, *pieces):
+        for p in pieces:
+            b = p.encode("utf-8") if isinstance(p, str) else p
+            items.append((kind, i, len(hays), detail))
+            hays.append(b)
+            at[0] += len(b)
+
+    def fill(n):
+        return "".join(rng.choice(LONG_FILLER) for _ in range(n))
+
+    def cased(nd):
+        share = rng.uniform(0.3, 0.4)
+        return "".join(rng.choice(partners[c]) if c in partners and rng.random() < share else c for c in nd)
+
+    for i, nd in enumerate(needles):
+        nb = len(nd.encode("utf-8"))
+        if long_text_parts(name) == 2 and (nb > 2049) != (part == 1):
+            continue
+        alone = name.startswith("steps/") and chain_len <= i < 2 * chain_len
+        misses, kib_ends, start_at, cuts = _long_treatment(nb, alone)
+        add("whole", i, None, nd)
+        if case:
+            add("cased", i, None, cased(nd))
+        add("minus first", i, None, nd[1:])
+        add("plus one", i, None, rng.choice(LONG_FILLER + nd[0]) + nd)
+        for cut in cuts:                                            # (on a code point: a haystack is valid UTF-8) after the first code point, after the first half
+            k = 1 if cut == "first" else len(nd) // 2
+            add("cut", i, cut, nd[:k], nd[k:])
+        for where in misses:
+            nm = long_near_miss(nd, where)
+            if nm is not None:
+                add("near miss", i, where, nm)
+        for d in kib_ends:                                          # the byte behind the needle's last is byte k * 1024 + d of the batch
+            pad = (d - at[0] - nb) % 1024
+            pad += 1024 if pad < 8 else 0
+            add("ends at", i, d, fill(pad) + nd)
+            assert (at[0] - d) % 1024 == 0
+        if start_at:                                                # the needle's first byte is byte k * 1024 - 1 of the batch
+            pad = (-1 - at[0]) % 1024
+            pad += 1024 if pad < 8 else 0
+            add("starts at", i, -1, fill(pad) + nd + fill(5))
+    if name == "periodic":
+        add("periodic", 0, None, "ab" * (32 << 10))
+    for _ in range(3):
+        add("empty", -1, None, "")
+    room = min(256 << 10, LONG_BATCH_LIMIT - at[0])
+    assert room >= (96 << 10), (name, case, at[0])
+    small = [i for i, nd in enumerate(needles) if len(nd.encode("utf-8")) <= 8193]
+    parts, size = [], 0
+    while True:
+        r, i = rng.random(), rng.choice(small)
+        nd = needles[i]
+        if r < 0.45:
+            p = cased(nd) if case and rng.random() < 0.5 else nd
+        elif r < 0.75:
+            p = long_near_miss(nd, rng.choice(LONG_MISS_DISTANCES + ("middle", "first"))) or nd[1:]
+        else:
+            p = fill(rng.randint(1, 40))
+        p = p.encode("utf-8")
+        if size + len(p) > room:
+            break
+        parts.append(p)
+        size += len(p)
+    add("mixed", -1, None, b"".join(parts))
+    text = b"".join(hays)
+    offs = np.concatenate([[0], np.cumsum([len(h) for h in hays])]).astype(np.int64)
+    assert len(text) <= LONG_BATCH_LIMIT, (name, case, len(text))
+    _LONG_TEXTS[key] = LongText(text, offs, items)
+    return _LONG_TEXTS[key]
+
+
+def long_needle_text(name, case, seed=0, part=0):
+    """(text, offsets np.int64) for the set `name` (batch `part` of long_text_parts(name)), at most LONG_BATCH_LIMIT bytes, one haystack per planted piece.  For every needle: the needle alone; under
+    IgnoreCase also with 30-40 % of its code points replaced by an upper-case partner (K for k: up to three times the bytes); without its first code point; with
+    one code point in front; cut in two haystacks after its first code point and after its first half; near misses (long_near_miss) 1, 5, 21, 22, 38, 39, 56 bytes
+    from the end, in the middle and at the first code point; ending at byte k * 1024 + d of the batch for d in LONG_KIB_ENDS, and starting at k * 1024 - 1
+    (_long_treatment thins these out above 1 025 bytes).  Then 64 KiB of "ab" (periodic only), three empty haystacks and one mixed haystack of needles, near
+    misses and filler that takes the room left, 256 KiB at most."""
+    t = long_needle_plan(name, case, seed, part)
+    return t.text, t.offs
+
+
+def long_needle_unit_text(total, unit_bytes, seed=0):
+    """(needles, text, offs) for batches whose work units hold several chunks: the 1 025-, 8 193- and 16 500-byte needles of beyond/ab placed so that they end
+    1, 5, half their length and all but one byte behind a unit boundary, alone and behind a near miss; filler in between; haystacks of 0 to 3 units."""
+    rng = random.Random("long-units-%d-%d-%d" % (total, unit_bytes, seed))
+    ns = long_needle_sets()["beyond/ab"]
+    picked = [n for n in ns if len(n) in (1025, 8193, 16500)]
+    assert sorted(set(len(n) for n in picked)) == [1025, 8193, 16500]
+    buf = np.frombuffer(("".join(rng.choice(LONG_FILLER) for _ in range(4096)) * (total // 4096 + 1))[:total].encode(), dtype=np.uint8).copy()
+    n_units = total // unit_bytes
+    per = 34000 // unit_bytes + 2                                  # units between two placements: they never overlap
+    u, k, placed = per, 0, 0
+    while u < n_units - 1:
+        nd = picked[k % len(picked)]
+        behind = (1, 5, len(nd) // 2, len(nd) - 1)[(k // len(picked)) % 4]
+        end = u * unit_bytes + behind
+        piece = nd if k % 5 else long_near_miss(nd, 56) + nd
+        assert end - len(piece) >= (u - per + 1) * unit_bytes and end <= total
+        buf[end - len(piece):end] = np.frombuffer(piece.encode(), dtype=np.uint8)
+        placed += 1
+        u += per
+        k += 1
+    assert placed >= 24, (total, unit_bytes, placed)               # every needle at every distance, twice
+    cuts, c = [0], 0
+    while c < total:
+        c = min(total, c + rng.choice((0, 1, unit_bytes // 2 + 3, unit_bytes, 3 * unit_bytes + 1, 40 * unit_bytes)))
+        cuts.append(c)
+    return ns, buf.tobytes(), np.asarray(cuts, dtype=np.int64)
+
+
+# ---- Replacer: a match that a replacement COMPLETES, |L| bytes to its left and |R| to its right ------------------------------------------------------------
+# The one-kernel route takes a replacer while round_up_64(2 ov + longest replacement + 16) <= 4096 (am_replacer.cpp:837-838), ov = the longest needle in bytes
+# for CaseSensitive replacers and 4 * code points + 4 under IgnoreCase (:835-836).  The replacements here are one byte long: 2 ov + 17 <= 4096, ov <= 2039.
+LONG_RP_OV_LIMIT = (4096 - 16 - 1) // 2                       # 2039: the largest reach the one-kernel route takes with one-byte replacements
+LONG_RP_CS_LIMIT = (LONG_RP_OV_LIMIT, LONG_RP_OV_LIMIT + 1)   # needle BYTES at and above the limit (CaseSensitive): 2039, 2040
+LONG_RP_IC_LIMIT = ((LONG_RP_OV_LIMIT - 4) // 4, (LONG_RP_OV_LIMIT - 4) // 4 + 1)      # needle CODE POINTS at and above it (IgnoreCase): 508 (ov 2036), 509 (ov 2040)
+
+
+def long_route_cap(case, pairs):
+    """round_up_64(2 ov + longest replacement + 16) of am_replacer.cpp:837."""
+    return (2 * reach(case, pairs) + max(len(r.encode("utf-8")) for _, r in pairs) + 16 + 63) // 64 * 64
+
+
+class LongReplacerCase:
+    """pairs over docs (str); `expect` the final texts, `passes` the scans the longest-running document needs (Replacer.hs:219-242), `fits[i]`: document i's first
+    re-scan window (am_rplds.hip:318-322) is within LDS_WIN."""
+
+    def __init__(self, name, case, pairs, docs, expect, passes):
+        self.name, self.case, self.pairs, self.docs, self.expect, self.passes = name, case, pairs, docs, expect, passes
+        self.ov, self.cap = reach(case, pairs), long_route_cap(case, pairs)
+        self.fits = []
+        for d in docs:
+            b = d.encode("utf-8")
+            ms = b.index(b"@")
+            self.fits.append(min(ms + 1 + self.ov, len(b)) - max(ms - self.ov, 0) <= LDS_WIN)
+
+    def __repr__(self):
+        return "LongReplacerCase(%s)" % self.name
+
+
+def _long_rp_case(name, case, nl, nr, rng, alphabet="abcdefgh", upper=False):
+    """N = L + "#" + R with |L| = nl and |R| = nr code points: [("@", "#"), (N, "!"), NEVER] over L + "@" + R, bare, inside filler, and at the text's start / end."""
+    left = "".join(rng.choice(alphabet) for _ in range(nl))
+    right = "".join(rng.choice(alphabet) for _ in range(nr))
+    pairs = [("@", "#"), (left + "#" + right, "!"), NEVER]
+    if upper:
+        partners = _sf_upper_partners()
+        shown = "".join(rng.choice(partners[c]) if c in partners and rng.random() < 0.5 else c for c in left)
+        assert shown != left
+    else:
+        shown = left
+    pad = "x" * (nl + nr + 40)
+    docs = [shown + "@" + right, pad + shown + "@" + right + pad, shown + "@" + right + pad, pad + shown + "@" + right, "x" * 7 + shown + "@" + right + "x" * 9]
+    expect = [b"!", (pad + "!" + pad).encode(), ("!" + pad).encode(), (pad + "!").encode(), b"x" * 7 + b"!" + b"x" * 9]
+    return LongReplacerCase(name, case, pairs, docs, expect, 3)
+
+
+def long_needle_replacer_cases():
+    """|L| = |R| in 8, 100, 223, 224, 500, 1000, 3000 code points, both case modes; the two needle lengths on either side of the host's route limit in each mode
+    (LONG_RP_CS_LIMIT in bytes, LONG_RP_IC_LIMIT in code points); all the length in L, all of it in R; IgnoreCase with L written in K / İ / ẞ / Å; and a chain of
+    three pairs in which every replacement completes the next needle."""
+    out = []
+    for case in (0, 1):
+        tag = "IC" if case else "CS"
+        rng = random.Random("long-rp-%d" % case)
+        for n in (8, 100, 223, 224, 500, 1000, 3000):
+            out.append(_long_rp_case("%d+%d %s" % (n, n, tag), case, n, n, rng))
+        for total in (LONG_RP_IC_LIMIT if case else LONG_RP_CS_LIMIT):
+            nl = (total - 1) // 2
+            out.append(_long_rp_case("limit %d %s" % (total, tag), case, nl, total - 1 - nl, rng))
+        out.append(_long_rp_case("all left %s" % tag, case, 400, 0, rng))
+        out.append(_long_rp_case("all right %s" % tag, case, 0, 400, rng))
+        # a chain: "@" -> "#" completes N1 -> "$" completes N2 -> "%" completes N3 -> "!"
+        parts = ["".join(rng.choice("abcdefgh") for _ in range(n)) for n in (60, 60, 150, 150, 300, 300)]
+        l1, r1, l2, r2, l3, r3 = parts
+        pairs = [("@", "#"), (l1 + "#" + r1, "$"), (l2 + "$" + r2, "%"), (l3 + "%" + r3, "!"), NEVER]
+        core = l3 + l2 + l1 + "@" + r1 + r2 + r3
+        pad = "x" * 700
+        out.append(LongReplacerCase("chain %s" % tag, case, pairs, [core, pad + core + pad, core + pad], [b"!", (pad + "!" + pad).encode(), ("!" + pad).encode()], 5))
+    rng = random.Random("long-rp-upper")
+    out.append(_long_rp_case("upper 100+100 IC", 1, 100, 100, rng, alphabet="kiåßab", upper=True))
+    out.append(_long_rp_case("upper 400+8 IC", 1, 400, 8, rng, alphabet="kiåß", upper=True))
+    return out
+
+
+def replacer_passes(case, pairs, text):
+    """(final text, scans) of Replacer.run restated with the oracle's automaton (Replacer.hs:219-242): a scan per pass; the pass replaces the matches of the best
+    priority below the threshold; the loop ends with a scan that finds none, or with the lowest priority."""
+    m = oracle.Machine([oracle.lower_utf8(n) if case else n.encode("utf-8") for n, _ in pairs])
+    text = text.encode("utf-8") if isinstance(text, str) else text
+    threshold, scans = 1, 0
+    while True:
+        scans += 1
+        _, val = m.run_list(case, text)
+        below = [-int(v) for v in val if -int(v) < threshold]
+        if not below:
+            return text, scans
+        p = max(below)
+        text = oracle.Replacer(case, [pairs[-p]]).run(text)
+        if p == 1 - len(pairs):
+            return text, scans
+        threshold = p
