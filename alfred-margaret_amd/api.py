@@ -35,6 +35,9 @@ class Slice(C.Structure):          # am_slice
 MATCH_DTYPE = np.dtype([("end_pos", np.uint64), ("haystack", np.uint32), ("state", np.uint32)])   # am_match
 FRAGMENT_DTYPE = np.dtype([("start", np.uint64), ("len", np.uint64)])   # am_fragment
 NEEDLE_COUNT_DTYPE = np.dtype([("count", np.uint64), ("needle", np.uint32), ("haystack", np.uint32)])   # am_needle_count
+SPAN_DTYPE = np.dtype([("start", np.uint64), ("len", np.uint64), ("haystack", np.uint32), ("needle", np.uint32)])   # am_span
+SPANS_ALL = 0
+SPANS_LEFTMOST_LONGEST = 1
 PRIO_MATCH_DTYPE = np.dtype([("start", np.uint64), ("len", np.uint64), ("haystack", np.uint32), ("payload", np.uint32)])   # am_prio_match
 
 _u8p, _u32p, _u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
@@ -93,6 +96,18 @@ ABI = {
     "am_fragments_device_data": (_vp, [_vp]),
     "am_fragments_free": (None, [_vp]),
     "am_batch_from_fragments": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "am_span_table_create": (C.c_int, [_vp, _vp, _vp, C.POINTER(_vp)]),
+    "am_span_table_destroy": (None, [_vp]),
+    "am_spans_batch": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
+    "am_spans": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(Slice), _sz, C.POINTER(_vp)]),
+    "am_spans_size": (C.c_uint64, [_vp]),
+    "am_spans_haystacks": (C.c_uint64, [_vp]),
+    "am_spans_offsets": (_vp, [_vp]),
+    "am_spans_data": (_vp, [_vp]),
+    "am_spans_device_offsets": (_vp, [_vp]),
+    "am_spans_device_data": (_vp, [_vp]),
+    "am_spans_rounds": (C.c_uint32, [_vp]),
+    "am_spans_free": (None, [_vp]),
     "am_needle_ids_create": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(_vp)]),
     "am_needle_ids_destroy": (None, [_vp]),
     "am_contains_all": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp]),
@@ -165,6 +180,8 @@ _HOST = {
     "amh_count": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp]),
     "amh_count_by_needle": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _sz, _vp]),
     "amh_count_matrix": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _sz, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
+    "amh_spans_fold": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
+    "amh_spans": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(Slice), _sz, _vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
     "amh_searcher_build": (C.c_int, [C.c_int, C.c_char_p, _vp, _sz, C.POINTER(_vp)]),
     "amh_searcher_free": (None, [_vp]),
     "amh_searcher_set_case": (None, [_vp, C.c_int]),
@@ -480,6 +497,80 @@ class Automaton:
             libhost().amh_free_u64(pe)
         return offs, ents
 
+    def spans(self, case, texts, leftmost_longest=False):
+        """Where every match starts: (offsets np.uint64[len(texts) + 1], spans SPAN_DTYPE[offsets[-1]]); the spans of text i are spans[offsets[i]:offsets[i + 1]],
+        start and len in bytes relative to the text, needle = the value handle.  All fold steps of runWithCase (Automaton.hs:442-553) in fold order with the span
+        makeMatch gives them (Replacer.hs:264-274), or -- leftmost_longest -- the non-overlapping selection: smallest start, then longest, then smallest handle, never a
+        zero-length span.  am_spans: scanned, expanded and selected in HBM."""
+        return SpanTable(self).spans_texts(case, texts, SPANS_LEFTMOST_LONGEST if leftmost_longest else SPANS_ALL)
+
+    def spans_host_mirror(self, case, texts, leftmost_longest=False, n_values=None, lengths=None):
+        """The same through the C++ host mirror (host/spans.hpp spansFold over the fold steps of amh_run_list).  lengths: (len_bytes, len_code_points) per value handle
+        where the handles are not the needle indices."""
+        lb, lc = _handle_lengths(self.needles, n_values, lengths)
+        nv = (len(self.needles) if lengths is None else len(lengths[0])) if n_values is None else int(n_values)
+        s = _Slices(texts)
+        po, pe, ne = _vp(), _vp(), C.c_uint64(0)
+        _hcheck(libhost().amh_spans(self._h, case, SPANS_LEFTMOST_LONGEST if leftmost_longest else SPANS_ALL, s.arr, s.n, lb.ctypes.data, lc.ctypes.data, nv,
+                                    C.byref(po), C.byref(pe), C.byref(ne)))
+        return _take_spans(po, pe, s.n, int(ne.value))
+
+
+def needle_lengths(needles, n_values=None):
+    """(len_bytes, len_code_points) np.uint32 arrays of am_span_table_create for value handles 0 .. n - 1 = the needles in order (n = len(needles) unless given: fewer
+    drops the last needles, more is refused)."""
+    bs = [_as_bytes(x) for x in needles]
+    n = len(bs) if n_values is None else int(n_values)
+    if n > len(bs):
+        raise AmError(AM_ERR_INVALID, "needle_lengths: more value handles than needles")
+    lb = np.zeros(max(n, 1), np.uint32)
+    lc = np.zeros(max(n, 1), np.uint32)
+    for i in range(n):
+        lb[i] = len(bs[i])
+        lc[i] = sum(1 for c in bs[i] if (c & 0xC0) != 0x80)
+    return lb, lc
+
+
+def _handle_lengths(needles, n, lengths):
+    """needle_lengths, or the caller's (len_bytes, len_code_points) per value handle cut or checked against n."""
+    if lengths is None:
+        return needle_lengths(needles, n)
+    lb, lc = (np.ascontiguousarray(a, dtype=np.uint32) for a in lengths)
+    n = len(lb) if n is None else int(n)
+    if len(lb) != len(lc) or n > len(lb):
+        raise AmError(AM_ERR_INVALID, "lengths: two arrays of at least n entries each")
+    pad = np.zeros(1, np.uint32)
+    return np.concatenate([lb[:n], pad]), np.concatenate([lc[:n], pad])
+
+
+def _take_spans(po, pe, n_hay, k):
+    """Copies and frees the two blocks a facade spans call hands back."""
+    try:
+        offs = np.frombuffer((C.c_char * ((n_hay + 1) * 8)).from_address(po.value), dtype=np.uint64).copy()
+        spans = np.frombuffer((C.c_char * (k * SPAN_DTYPE.itemsize)).from_address(pe.value), dtype=SPAN_DTYPE).copy() if k else np.zeros(0, SPAN_DTYPE)
+    finally:
+        libhost().amh_free_u64(po)
+        libhost().amh_free_u64(pe)
+    return offs, spans
+
+
+def spans_fold_host(case, mode, triples, texts, len_bytes, len_code_points):
+    """amh_spans_fold: the sequential definition of am_spans over fold steps the caller brings -- (haystack, matchPos, value) arrays in fold order -- the texts and the
+    two length arrays.  Runs without a device."""
+    hay = np.ascontiguousarray(triples[0], dtype=np.uint32)
+    pos = np.ascontiguousarray(triples[1], dtype=np.uint64)
+    val = np.ascontiguousarray(triples[2], dtype=np.uint32)
+    lb = np.ascontiguousarray(len_bytes, dtype=np.uint32)
+    lc = np.ascontiguousarray(len_code_points, dtype=np.uint32)
+    n, nv = len(hay), len(lb)
+    pad = lambda a, t: a if a.size else np.zeros(1, t)
+    hay, pos, val, lb, lc = pad(hay, np.uint32), pad(pos, np.uint64), pad(val, np.uint32), pad(lb, np.uint32), pad(lc, np.uint32)
+    s = _Slices(texts)
+    po, pe, ne = _vp(), _vp(), C.c_uint64(0)
+    _hcheck(libhost().amh_spans_fold(case, mode, hay.ctypes.data, pos.ctypes.data, val.ctypes.data, n, s.arr, s.n, lb.ctypes.data, lc.ctypes.data, nv,
+                                     C.byref(po), C.byref(pe), C.byref(ne)))
+    return _take_spans(po, pe, s.n, int(ne.value))
+
 
 class ValuesTable:
     """machineValues of an Automaton in flat form on the device (am_needle_ids): what the fold-checksum and
@@ -556,6 +647,51 @@ class ValuesTable:
         return self._matrix(lambda out: libam().am_count_matrix(self._h, case, s.arr, s.n, out), raw)
 
 
+class SpanTable:
+    """The needles' lengths beside machineValues on the device (am_span_table): what am_spans* turns a fold step into a span with.  Lengths come from
+    automaton.needles, handle = needle index; n_needles below len(needles) skips the handles from n_needles on.  lengths: (len_bytes, len_code_points) per value handle
+    for an automaton built with handles of its own."""
+
+    def __init__(self, automaton, n_needles=None, lengths=None):
+        if n_needles is None and lengths is not None:
+            n_needles = len(lengths[0])
+        self._values = ValuesTable(automaton, n_needles)      # (the am_needle_ids must outlive the table)
+        self.n_needles = self._values.n_needles
+        self._lb, self._lc = _handle_lengths(automaton.needles, self.n_needles, lengths)
+        h = _vp()
+        check(libam().am_span_table_create(self._values.handle, self._lb.ctypes.data, self._lc.ctypes.data, C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            libam().am_span_table_destroy(self._h)
+            self._h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    def _spans(self, call, raw):
+        x = _vp()
+        check(call(C.byref(x)))
+        if raw:
+            return x
+        try:
+            return spans_to_numpy(x)
+        finally:
+            libam().am_spans_free(x)
+
+    def spans_batch(self, case, batch, mode, raw=False):
+        """am_spans_batch on a device-resident batch (an am_batch* handle: am_batch_upload / am_batch_from_device / Splitter.lines_batch): (offsets np.uint64[n_hay + 1],
+        spans SPAN_DTYPE[offsets[-1]]).  raw: the am_spans* itself, in HBM (measurements; free with am_spans_free)."""
+        return self._spans(lambda out: libam().am_spans_batch(self._h, case, mode, batch, out), raw)
+
+    def spans_texts(self, case, texts, mode):
+        """am_spans: the one-shot form on host texts."""
+        s = _Slices(texts)
+        return self._spans(lambda out: libam().am_spans(self._h, case, mode, s.arr, s.n, out), False)
+
+
 class ImageAutomaton:
     """A device automaton attached to a serialised image (am_automaton_from_host_image): no build, no
     flatten.  It serves the image's case mode and returns raw records; machineValues stay with whoever
@@ -627,6 +763,17 @@ def matrix_to_numpy(x):
     offs = np.frombuffer((C.c_char * ((n_hay + 1) * 8)).from_address(po), dtype=np.uint64).copy()
     ents = np.frombuffer((C.c_char * (n * NEEDLE_COUNT_DTYPE.itemsize)).from_address(pd), dtype=NEEDLE_COUNT_DTYPE).copy() if n else np.zeros(0, NEEDLE_COUNT_DTYPE)
     return offs, ents
+
+
+def spans_to_numpy(x):
+    """(offsets np.uint64[n_hay + 1], spans SPAN_DTYPE[n]) of an am_spans* result (host copies)."""
+    n, n_hay = int(libam().am_spans_size(x)), int(libam().am_spans_haystacks(x))
+    po, pd = libam().am_spans_offsets(x), libam().am_spans_data(x)
+    if not po or not pd:
+        raise AmError(AM_ERR_HIP, (libam().am_last_error() or b"").decode())
+    offs = np.frombuffer((C.c_char * ((n_hay + 1) * 8)).from_address(po), dtype=np.uint64).copy()
+    spans = np.frombuffer((C.c_char * (n * SPAN_DTYPE.itemsize)).from_address(pd), dtype=SPAN_DTYPE).copy() if n else np.zeros(0, SPAN_DTYPE)
+    return offs, spans
 
 
 def matches_of_haystack(m, haystack):
@@ -885,7 +1032,7 @@ class Splitter:
 
 DEBUG_SWITCHES = ("AM_SF_TRACE", "AM_SF_POOL_BLOCKS", "AM_SF_NO_CHILDREN", "AM_DFA", "AM_DFA_CHUNK", "AM_DFA_RARE_PERMILLE", "AM_DFA_MIN_KIB", "AM_DFA_TUNE", "AM_DFA_NO_CHAINS", "AM_FLATTEN_TRACE", "AM_FLATTEN_SERIAL", "AM_NO_IDS_SCAN",
                   "AM_RP_FULL_SCANS", "AM_RP_PIECES", "AM_RP_PARALLEL_FOLD", "AM_RP_GROUPS", "AM_RP_NO_FUSE", "AM_RP_NO_SPIN",
-                  "AM_RP_MAT_MAIN", "AM_RP_NO_RANGE_REUSE", "AM_RP_TRACE", "AM_RP_LDS", "AM_RP_LOOP", "AM_RUN_SEGMENTS", "AM_HIST_RECORDS_MIB", "AM_HIST_TRACE", "AM_HIST_FLUSH_TILES", "AM_SPLIT_CHAIN_LIMIT")
+                  "AM_RP_MAT_MAIN", "AM_RP_NO_RANGE_REUSE", "AM_RP_TRACE", "AM_RP_LDS", "AM_RP_LOOP", "AM_RUN_SEGMENTS", "AM_HIST_RECORDS_MIB", "AM_HIST_TRACE", "AM_HIST_FLUSH_TILES", "AM_SPLIT_CHAIN_LIMIT", "AM_SPANS_CHAIN_LIMIT")
 
 
 def debug_set(name, value):

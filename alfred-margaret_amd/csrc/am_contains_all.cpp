@@ -13,13 +13,6 @@ using namespace am::host;
 
 // ------------------------------------------------------------------ Searcher.containsAll (Searcher.hs:167-187)
 
-struct am_needle_ids {
-    const am_automaton* a = nullptr;
-    uint32_t n_needles = 0;
-    uint64_t n_states = 0, n_values = 0;     // entries of vals_off - 1 / of vals
-    DevBuf vals_off, vals;
-};
-
 extern "C" int am_needle_ids_create(const am_automaton* a, const uint64_t* values_offsets, const uint32_t* values, uint32_t n_needles, am_needle_ids** out)
 {
     if (!out) return fail(AM_ERR_INVALID, "out is null");

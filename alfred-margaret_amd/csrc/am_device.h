@@ -193,6 +193,35 @@ hipError_t launch_split_sources(const Fragment* frags, uint64_t n_frag, const ui
                                 uint64_t* lens, uint64_t* src_at, hipStream_t st);
 hipError_t launch_split_gather(const uint8_t* src, uint64_t src_total, const uint64_t* src_at, const uint64_t* dst_off, uint64_t n_frag, uint64_t total, uint8_t* dst,
                                int n_cu, hipStream_t st);
+// match spans (am_spans.hip): every fold step `Match pos v` with v < n_needles as (start, len, haystack, needle), all of them or the leftmost-longest selection
+struct Span { uint64_t start, len; uint32_t haystack, needle; };      // = am_span in include/am.h
+struct SpansIn {
+    const Record* recs; uint64_t n_rec;                     // the sorted records of the batch
+    const uint64_t* vals_off; const uint32_t* vals; uint64_t n_states, n_values;      // machineValues in flat form (am_needle_ids)
+    const uint32_t* len_bytes; const uint32_t* len_cps; uint32_t n_needles, n_hay;    // the needles' own lengths (am_span_table)
+    const uint8_t* text; const uint64_t* offsets; uint64_t total;
+};
+constexpr uint64_t kSpansMaxTile = 2048;                    // candidates per workgroup of the prefix maximum
+// cnt[i] = values < n_needles of record i (n_rec + 1 entries, the last one 0); then, with voff = exclusive sum of cnt and n_span = voff[n_rec], the spans in fold order
+hipError_t launch_spans_count(const SpansIn& in, uint32_t* cnt, hipStream_t st);
+hipError_t launch_spans_write(bool ic, const SpansIn& in, const uint64_t* voff, Span* spans, uint64_t n_span, hipStream_t st);
+// AM_SPANS_ALL: span_off[h] = voff[rec_first[h]] (n_hay + 1)
+hipError_t launch_spans_offsets(const uint64_t* rec_first, const uint64_t* voff, uint64_t n_rec, uint32_t n_hay, uint64_t* span_off, hipStream_t st);
+// AM_SPANS_LEFTMOST_LONGEST, in global byte positions g = offsets[haystack] + start.  In the order of the calls: bit g of `bits` (n_words = ceil(total / 32) words, zero
+// before) for every span with len > 0, pc[w] = popcount(bits[w]) (n_words + 1, the last one 0); with rank = exclusive sum of pc and n_cand = rank[n_words]:
+// best[rank of g] = max(len << 32 | ~needle) (zero before); cand_g[k] = the k-th set bit; head / kept (kept: n_cand + 1, the last one 0) from the exclusive prefix
+// maximum of the candidates' ends (tile_max: ceil((n_cand + 1) / kSpansMaxTile) words); the heads' lanes walk their chains (*long_chains, cleared by the caller, != 0
+// when one needed more than `limit` looks); jump[i] = next[i] for launch_split_double's rounds; with kidx = exclusive sum of kept and n_out = kidx[n_cand]: the spans
+// kept and span_off (n_hay + 1)
+hipError_t launch_spans_mark(const Span* spans, uint64_t n_span, const SpansIn& in, uint32_t* bits, uint64_t n_words, hipStream_t st);
+hipError_t launch_spans_popcount(const uint32_t* bits, uint64_t n_words, uint32_t* pc, hipStream_t st);
+hipError_t launch_spans_best(const Span* spans, uint64_t n_span, const SpansIn& in, const uint32_t* bits, const uint64_t* rank, uint64_t n_words, uint64_t* best, uint64_t n_cand, hipStream_t st);
+hipError_t launch_spans_candidates(const uint32_t* bits, const uint64_t* rank, uint64_t n_words, uint64_t* cand_g, uint64_t n_cand, hipStream_t st);
+hipError_t launch_spans_heads(const uint64_t* cand_g, const uint64_t* best, uint64_t n_cand, uint64_t* tile_max, uint8_t* head, uint32_t* kept, hipStream_t st);
+hipError_t launch_spans_walk(const uint64_t* cand_g, const uint64_t* best, uint64_t n_cand, const uint8_t* head, uint32_t* kept, uint32_t limit, uint32_t* long_chains, hipStream_t st);
+hipError_t launch_spans_next(const uint64_t* cand_g, const uint64_t* best, uint64_t n_cand, const uint8_t* head, uint64_t* jump, hipStream_t st);
+hipError_t launch_spans_emit(const uint64_t* cand_g, const uint64_t* best, const uint32_t* kept, const uint64_t* kidx, uint64_t n_cand, const SpansIn& in, Span* out, uint64_t n_out,
+                             uint64_t* span_off, hipStream_t st);
 // incremental re-scan between Replacer passes (am_replace.hip)
 struct RpWin { uint64_t src_abs; uint64_t ws; uint32_t len; uint32_t own_lo; };   // window: bytes src_abs.. of the next text; ws = its start inside the haystack; records with end > own_lo are its own
 hipError_t launch_rp_win_count(const RpHay* hs, uint32_t n_act, uint32_t* nwin, hipStream_t st);

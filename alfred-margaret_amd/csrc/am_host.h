@@ -182,6 +182,14 @@ struct am_matches {
     bool big_pinned = false;                             // DMA'd straight into it), or pageable and filled through pinned staging
 };
 
+// machineValues in flat form on the device (am_needle_ids_create, am_contains_all.cpp): what the folds over the records expand a state with
+struct am_needle_ids {
+    const am_automaton* a = nullptr;
+    uint32_t n_needles = 0;
+    uint64_t n_states = 0, n_values = 0;     // entries of vals_off - 1 / of vals
+    am::host::DevBuf vals_off, vals;
+};
+
 namespace am {
 namespace host {
 

@@ -5,6 +5,7 @@
 #include <string>
 
 #include "replacer.hpp"
+#include "spans.hpp"
 #include "splitter.hpp"
 
 using namespace alfred_margaret;
@@ -108,6 +109,53 @@ int amh_count_matrix(void* h, int case_mode, const am_slice* hay, size_t n_hay, 
         std::memcpy(offs, r.offsets.data(), (n_hay + 1) * sizeof(uint64_t));
         if (ne) std::memcpy(ents, r.entries.data(), ne * sizeof(am_needle_count));
         *offs_out = offs; *entries_out = ents; *n_entries_out = ne;
+    });
+}
+
+// ---- match spans (spans.hpp)
+namespace {
+void spansOut(const Spans& r, size_t n_hay, uint64_t** offs_out, uint64_t** spans_out, uint64_t* n_out)
+{
+    const uint64_t ns = r.spans.size();
+    uint64_t* offs = (uint64_t*)malloc((n_hay + 1) * sizeof(uint64_t));
+    uint64_t* sp = (uint64_t*)malloc((ns ? ns : 1) * sizeof(am_span));
+    std::memcpy(offs, r.offsets.data(), (n_hay + 1) * sizeof(uint64_t));
+    if (ns) std::memcpy(sp, r.spans.data(), ns * sizeof(am_span));
+    *offs_out = offs; *spans_out = sp; *n_out = ns;
+}
+}  // namespace
+// spansFold over fold steps the caller brings (n triples in fold order, haystacks ascending): no device is touched.  offsets (n_hay + 1) and the spans as the C ABI
+// lays them out (am_span, 24 bytes each); free both with amh_free_u64
+int amh_spans_fold(int case_mode, int mode, const uint32_t* hay_in, const uint64_t* pos_in, const uint32_t* val_in, uint64_t n, const am_slice* hay, size_t n_hay,
+                   const uint32_t* len_bytes, const uint32_t* len_code_points, size_t n_values, uint64_t** offs_out, uint64_t** spans_out, uint64_t* n_out)
+{
+    *offs_out = nullptr; *spans_out = nullptr; *n_out = 0;
+    return guarded([&] {
+        if ((case_mode != AM_CASE_SENSITIVE && case_mode != AM_IGNORE_CASE) || (mode != AM_SPANS_ALL && mode != AM_SPANS_LEFTMOST_LONGEST))
+            throw AmError(AM_ERR_INVALID, "amh_spans_fold: bad case_mode or mode");
+        std::vector<FoldStep> steps((size_t)n);
+        for (uint64_t i = 0; i < n; i++) steps[i] = FoldStep{hay_in[i], pos_in[i], val_in[i]};
+        const std::vector<uint32_t> lb(len_bytes, len_bytes + n_values), lc(len_code_points, len_code_points + n_values);
+        spansOut(spansFold((CaseSensitivity)case_mode, mode == AM_SPANS_LEFTMOST_LONGEST, steps, sliceTexts(hay, n_hay), lb, lc), n_hay, offs_out, spans_out, n_out);
+    });
+}
+// amh_run_list's fold (runWithCase with a list-building fold over the batch), then amh_spans_fold's
+int amh_spans(void* h, int case_mode, int mode, const am_slice* hay, size_t n_hay, const uint32_t* len_bytes, const uint32_t* len_code_points, size_t n_values,
+              uint64_t** offs_out, uint64_t** spans_out, uint64_t* n_out)
+{
+    *offs_out = nullptr; *spans_out = nullptr; *n_out = 0;
+    return guarded([&] {
+        if ((case_mode != AM_CASE_SENSITIVE && case_mode != AM_IGNORE_CASE) || (mode != AM_SPANS_ALL && mode != AM_SPANS_LEFTMOST_LONGEST))
+            throw AmError(AM_ERR_INVALID, "amh_spans: bad case_mode or mode");
+        struct Acc { std::vector<std::pair<uint64_t, uint32_t>> v; };
+        auto f = [](Acc a, const Match<uint32_t>& m) { a.v.emplace_back(m.matchPos, m.matchValue); return Next<Acc>::Step(std::move(a)); };
+        const std::vector<Text> texts = sliceTexts(hay, n_hay);
+        auto accs = runBatchWithCase((CaseSensitivity)case_mode, Acc{}, f, static_cast<MachineBox*>(h)->m, texts);
+        std::vector<FoldStep> steps;
+        for (size_t i = 0; i < accs.size(); i++)
+            for (auto& pv : accs[i].v) steps.push_back(FoldStep{(uint32_t)i, pv.first, pv.second});
+        const std::vector<uint32_t> lb(len_bytes, len_bytes + n_values), lc(len_code_points, len_code_points + n_values);
+        spansOut(spansFold((CaseSensitivity)case_mode, mode == AM_SPANS_LEFTMOST_LONGEST, steps, texts, lb, lc), n_hay, offs_out, spans_out, n_out);
     });
 }
 

@@ -1,0 +1,61 @@
+// spans.hpp -- host mirror of am_spans (include/am.h "match spans"): the sequential definition.  A fold step `Match pos v` of runWithCase (reference:
+// src/Data/Text/AhoCorasick/Automaton.hs:442-553) becomes the span makeMatch gives it (src/Data/Text/AhoCorasick/Replacer.hs:264-274) with the needle's own lengths;
+// all of them in fold order, or the leftmost-longest non-overlapping selection.  spansFold takes the fold steps as they are and touches no device.
+#pragma once
+#include <algorithm>
+
+#include "automaton.hpp"
+
+namespace alfred_margaret {
+
+struct FoldStep { uint32_t haystack; uint64_t matchPos; uint32_t value; };      // a triple of amh_run_list: fold order, haystacks ascending
+
+struct Spans {
+    std::vector<uint64_t> offsets;                          // texts.size() + 1
+    std::vector<am_span> spans;                             // haystack i: [offsets[i], offsets[i + 1])
+};
+
+// makeMatch: where the match of a needle with these lengths that ends at pos starts (clamped to 0 where the reference calls `error`)
+inline uint64_t spanStart(CaseSensitivity cs, const Text& hay, uint64_t pos, uint32_t lenBytes, uint32_t lenCodePoints)
+{
+    if (lenBytes == 0) return pos;
+    if (cs == CaseSensitivity::CaseSensitive) return pos >= lenBytes ? pos - lenBytes : 0;
+    if (pos == 0 || pos > hay.len) return 0;
+    try { return utf8::skipCodePointsBackwards(hay, (size_t)pos - 1, lenCodePoints - 1); } catch (const std::out_of_range&) { return 0; }
+}
+
+inline Spans spansFold(CaseSensitivity cs, bool leftmostLongest, const std::vector<FoldStep>& steps, const std::vector<Text>& texts,
+                       const std::vector<uint32_t>& lenBytes, const std::vector<uint32_t>& lenCodePoints)
+{
+    if (lenBytes.size() != lenCodePoints.size()) throw AmError(AM_ERR_INVALID, "spansFold: the two length arrays differ in size");
+    const size_t nValues = lenBytes.size();
+    Spans out;
+    out.offsets.assign(texts.size() + 1, 0);
+    size_t k = 0;
+    std::vector<am_span> all;
+    for (size_t h = 0; h < texts.size(); h++) {
+        out.offsets[h] = out.spans.size();
+        all.clear();
+        for (; k < steps.size() && steps[k].haystack == h; k++) {
+            const uint32_t v = steps[k].value;
+            if (v >= nValues) continue;                     // the am_needle_ids convention: skipped
+            const uint64_t start = spanStart(cs, texts[h], steps[k].matchPos, lenBytes[v], lenCodePoints[v]);
+            all.push_back(am_span{start, steps[k].matchPos - start, (uint32_t)h, v});
+        }
+        if (!leftmostLongest) { out.spans.insert(out.spans.end(), all.begin(), all.end()); continue; }
+        // smallest start >= cursor, then the largest len, then the smallest handle: in that order the first span at or after the cursor is the one to take
+        std::sort(all.begin(), all.end(), [](const am_span& a, const am_span& b) {
+            if (a.start != b.start) return a.start < b.start;
+            if (a.len != b.len) return a.len > b.len;
+            return a.needle < b.needle;
+        });
+        uint64_t cursor = 0;
+        for (const am_span& s : all)
+            if (s.len > 0 && s.start >= cursor) { out.spans.push_back(s); cursor = s.start + s.len; }
+    }
+    if (k != steps.size()) throw AmError(AM_ERR_INVALID, "spansFold: the fold steps are not grouped by ascending haystack below texts.size()");
+    out.offsets[texts.size()] = out.spans.size();
+    return out;
+}
+
+}  // namespace alfred_margaret

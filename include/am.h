@@ -287,6 +287,56 @@ AM_API const void* am_fragments_device_data(const am_fragments* f);
 AM_API void am_fragments_free(am_fragments* f);
 AM_API int am_batch_from_fragments(const am_batch* src, const am_fragments* f, am_batch** out);
 
+/* ---- match spans: where every match starts, in HBM; all of them, or the leftmost-longest non-overlapping selection ---------------
+ * A FOLD STEP is `Match pos v` of runWithCase (Automaton.hs:442-553).  Its SPAN is makeMatch (Replacer.hs:264-274) with the needle's own lengths:
+ *   AM_CASE_SENSITIVE   start = pos - len_bytes[v]
+ *   AM_IGNORE_CASE      start = skipCodePointsBackwards hay (pos - 1) (len_code_points[v] - 1)   (Utf8.hs:256-276: a k matched by U+212A is three bytes long)
+ *   len = pos - start; a needle of length 0 gives start = pos, len = 0.  The walk never leaves the haystack: one that would is clamped to 0 where the reference
+ *   calls `error`, as in am_split.  start and len are code units relative to the start of the haystack's slice.
+ * AM_SPANS_ALL: one span per fold step whose value handle is < n_needles; handles >= n_needles are SKIPPED (the convention of am_needle_ids).  ORDER: the reference's
+ *   fold order -- records ascend by (haystack, end_pos), the values of a record come in list order -- so start + len is non-decreasing per haystack, and the size
+ *   equals the sum of am_count_by_needle_batch's vector.
+ * AM_SPANS_LEFTMOST_LONGEST: per haystack, over the ALL spans with len > 0 (ZERO-LENGTH spans are never selected): cursor = 0; take the span with the smallest
+ *   start >= cursor; TIE-BREAK: among equal starts the largest len, among equal (start, len) the smallest handle; emit it, cursor = start + len, repeat.  The output
+ *   ascends by (haystack, start) and is bit-identical from run to run.  For b, abc, abcd over "abcd": ALL = (1,1,0) (0,3,1) (0,4,2), leftmost-longest = (0,4,2).
+ * The records are produced, expanded and selected in HBM (csrc/am_spans.hip: no sort -- a bitmap of the distinct starts ranks them, a 64-bit atomic maximum picks the
+ * longest span of a start, an exclusive prefix maximum finds the candidates no earlier one reaches, chains of overlapping candidates are walked or pointer-doubled);
+ * the result stays in HBM until asked for.  It is CSR like am_fragments: the spans of haystack i are [offsets[i], offsets[i + 1]) of data.
+ *   am_span_table_create     the needles' lengths beside machineValues: len_bytes / len_code_points, n_needles entries of host memory each (n_needles is ids'), copied to
+ *                            ids' device; `ids` must outlive the table.  AM_ERR_INVALID, before any device work, for null arguments (the arrays may be null when
+ *                            n_needles == 0), len_code_points[v] > len_bytes[v], exactly one of the two lengths being 0, len_code_points[v] >= 2^30 (a span length
+ *                            fits 32 bits: at most 4 bytes per code point).
+ *   am_spans_batch           a device-resident batch, on whatever route the automaton takes.  Record memory is NOT bounded here, as in am_split_batch: the whole batch
+ *                            is scanned once and all its records are in HBM while they are folded.  WORKSPACE next to the 16 bytes of a record: 12 bytes per record
+ *                            and 16 per haystack; 24 bytes per span (in AM_SPANS_ALL this is the result); in AM_SPANS_LEFTMOST_LONGEST also half a byte per byte of
+ *                            text (bitmap, word counts, ranks), 29 bytes per distinct start (45 when a chain needs the doubling rounds) and 24 per span of the result.
+ *                            The library's device buffers are allocated an eighth larger than asked.
+ *   am_spans                 the one-shot form on host slices (the calling thread's one-shot batch).  n_hay == 0 gives offsets = [0], no span and AM_OK;
+ *                            n_needles == 0 gives n_hay empty rows.
+ *   am_spans_*               size = spans of the whole batch.  offsets (n_hay + 1) / data are host copies made on first use and owned by the result (NULL on error);
+ *                            the device_ forms are the arrays in HBM (NULL where there is nothing: no haystack, no span).  am_spans_rounds = pointer-doubling rounds the
+ *                            call ran: 0 in AM_SPANS_ALL and wherever no chain of overlapping candidates was longer than AM_SPANS_CHAIN_LIMIT (csrc/am_config.h) looks.
+ * Arguments are checked before any device work: AM_ERR_INVALID for null table / batch / out, a case_mode that is neither AM_CASE_SENSITIVE nor AM_IGNORE_CASE, a mode
+ * that is neither AM_SPANS_ALL nor AM_SPANS_LEFTMOST_LONGEST, n_hay >= 0xFFFFFFFF, slices without memory, table and batch on different devices.  *out is NULL after
+ * every failure. */
+typedef struct am_span { uint64_t start; uint64_t len; uint32_t haystack; uint32_t needle; } am_span;   /* 24 bytes: offsets 0, 8, 16, 20 -- am_prio_match's shape */
+typedef struct am_span_table am_span_table;
+struct am_spans;                 /* the result.  No typedef: the one-shot entry point has the name, so the type is always written `struct am_spans` */
+#define AM_SPANS_ALL 0
+#define AM_SPANS_LEFTMOST_LONGEST 1
+AM_API int am_span_table_create(const am_needle_ids* ids, const uint32_t* len_bytes, const uint32_t* len_code_points /* n_needles each, host */, am_span_table** out);
+AM_API void am_span_table_destroy(am_span_table* t);
+AM_API int am_spans_batch(const am_span_table* t, int case_mode, int mode, const am_batch* b, struct am_spans** out);
+AM_API int am_spans(const am_span_table* t, int case_mode, int mode, const am_slice* hay, size_t n_hay, struct am_spans** out);
+AM_API uint64_t am_spans_size(const struct am_spans* s);
+AM_API uint64_t am_spans_haystacks(const struct am_spans* s);
+AM_API const uint64_t* am_spans_offsets(struct am_spans* s);
+AM_API const am_span* am_spans_data(struct am_spans* s);
+AM_API const void* am_spans_device_offsets(const struct am_spans* s);
+AM_API const void* am_spans_device_data(const struct am_spans* s);
+AM_API uint32_t am_spans_rounds(const struct am_spans* s);
+AM_API void am_spans_free(struct am_spans* s);
+
 /* Checksum of the fold sequence of a result (harness aid; SURVEY 8d "parity check at scale",
  * benchmark/benchmark.py:65-69 asserts count identity on every run).  For every haystack i < n_hay:
  *   hash_out[i]  = foldl (\h (pos, v) -> h * 0x100000001B3 + mix pos v) 0  over the matches the reference's
