@@ -623,14 +623,7 @@ class ValuesTable:
 
 
     def _matrix(self, call, raw):
-        x = _vp()
-        check(call(C.byref(x)))
-        if raw:
-            return x
-        try:
-            return matrix_to_numpy(x)
-        finally:
-            libam().am_needle_matrix_free(x)
+        return _csr_call(call, matrix_to_numpy, libam().am_needle_matrix_free, raw)
 
     def count_matrix(self, matches, n_hay, raw=False):
         """am_matches_count_matrix: the term-document matrix (offsets np.uint64[n_hay + 1], entries NEEDLE_COUNT_DTYPE) of an am_matches* result whose records are in
@@ -672,14 +665,7 @@ class SpanTable:
         return self._h
 
     def _spans(self, call, raw):
-        x = _vp()
-        check(call(C.byref(x)))
-        if raw:
-            return x
-        try:
-            return spans_to_numpy(x)
-        finally:
-            libam().am_spans_free(x)
+        return _csr_call(call, spans_to_numpy, libam().am_spans_free, raw)
 
     def spans_batch(self, case, batch, mode, raw=False):
         """am_spans_batch on a device-resident batch (an am_batch* handle: am_batch_upload / am_batch_from_device / Splitter.lines_batch): (offsets np.uint64[n_hay + 1],
@@ -743,37 +729,43 @@ def matches_to_numpy(m):
     return np.frombuffer((C.c_char * (n * MATCH_DTYPE.itemsize)).from_address(p), dtype=MATCH_DTYPE).copy()
 
 
+def _csr_to_numpy(x, prefix, dtype):
+    """(offsets np.uint64[n_hay + 1], items dtype[n]) of a CSR result handle whose accessors are am_<prefix>_size / _haystacks / _offsets / _data (host copies)."""
+    lib = libam()
+    n, n_hay = int(getattr(lib, prefix + "_size")(x)), int(getattr(lib, prefix + "_haystacks")(x))
+    po, pd = getattr(lib, prefix + "_offsets")(x), getattr(lib, prefix + "_data")(x)
+    if not po or not pd:
+        raise AmError(AM_ERR_HIP, (lib.am_last_error() or b"").decode())
+    offs = np.frombuffer((C.c_char * ((n_hay + 1) * 8)).from_address(po), dtype=np.uint64).copy()
+    items = np.frombuffer((C.c_char * (n * dtype.itemsize)).from_address(pd), dtype=dtype).copy() if n else np.zeros(0, dtype)
+    return offs, items
+
+
+def _csr_call(call, to_numpy, free, raw):
+    """call(out) makes a CSR result handle: the handle itself (raw: the caller frees it), or its host copies with the handle freed."""
+    x = _vp()
+    check(call(C.byref(x)))
+    if raw:
+        return x
+    try:
+        return to_numpy(x)
+    finally:
+        free(x)
+
+
 def fragments_to_numpy(f):
     """(offsets np.uint64[n_hay + 1], fragments FRAGMENT_DTYPE[n]) of an am_fragments* result (host copies)."""
-    n, n_hay = int(libam().am_fragments_size(f)), int(libam().am_fragments_haystacks(f))
-    po, pd = libam().am_fragments_offsets(f), libam().am_fragments_data(f)
-    if not po or not pd:
-        raise AmError(AM_ERR_HIP, (libam().am_last_error() or b"").decode())
-    offs = np.frombuffer((C.c_char * ((n_hay + 1) * 8)).from_address(po), dtype=np.uint64).copy()
-    frags = np.frombuffer((C.c_char * (n * FRAGMENT_DTYPE.itemsize)).from_address(pd), dtype=FRAGMENT_DTYPE).copy() if n else np.zeros(0, FRAGMENT_DTYPE)
-    return offs, frags
+    return _csr_to_numpy(f, "am_fragments", FRAGMENT_DTYPE)
 
 
 def matrix_to_numpy(x):
     """(offsets np.uint64[n_hay + 1], entries NEEDLE_COUNT_DTYPE[n]) of an am_needle_matrix* result (host copies)."""
-    n, n_hay = int(libam().am_needle_matrix_size(x)), int(libam().am_needle_matrix_haystacks(x))
-    po, pd = libam().am_needle_matrix_offsets(x), libam().am_needle_matrix_data(x)
-    if not po or not pd:
-        raise AmError(AM_ERR_HIP, (libam().am_last_error() or b"").decode())
-    offs = np.frombuffer((C.c_char * ((n_hay + 1) * 8)).from_address(po), dtype=np.uint64).copy()
-    ents = np.frombuffer((C.c_char * (n * NEEDLE_COUNT_DTYPE.itemsize)).from_address(pd), dtype=NEEDLE_COUNT_DTYPE).copy() if n else np.zeros(0, NEEDLE_COUNT_DTYPE)
-    return offs, ents
+    return _csr_to_numpy(x, "am_needle_matrix", NEEDLE_COUNT_DTYPE)
 
 
 def spans_to_numpy(x):
     """(offsets np.uint64[n_hay + 1], spans SPAN_DTYPE[n]) of an am_spans* result (host copies)."""
-    n, n_hay = int(libam().am_spans_size(x)), int(libam().am_spans_haystacks(x))
-    po, pd = libam().am_spans_offsets(x), libam().am_spans_data(x)
-    if not po or not pd:
-        raise AmError(AM_ERR_HIP, (libam().am_last_error() or b"").decode())
-    offs = np.frombuffer((C.c_char * ((n_hay + 1) * 8)).from_address(po), dtype=np.uint64).copy()
-    spans = np.frombuffer((C.c_char * (n * SPAN_DTYPE.itemsize)).from_address(pd), dtype=SPAN_DTYPE).copy() if n else np.zeros(0, SPAN_DTYPE)
-    return offs, spans
+    return _csr_to_numpy(x, "am_spans", SPAN_DTYPE)
 
 
 def matches_of_haystack(m, haystack):

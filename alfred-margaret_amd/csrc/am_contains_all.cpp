@@ -1,5 +1,6 @@
 // am_contains_all.cpp -- what is folded over the records with machineValues in flat form (am_needle_ids), on the device: Searcher.containsAll
-// (Searcher.hs:167-187), the fold checksum of a result, and the per-needle match counts (am_count_by_needle*).
+// (Searcher.hs:167-187), the fold checksum of a result, the per-needle match counts (am_count_by_needle*) and the per-haystack needle counts (am_count_matrix*).
+// The argument checks, the segment loop of the one-shot entry points (fold_slices) and the matrix's result handle are am_fold.h's, shared with the other folds.
 #include "am_host.h"
 
 #include <memory>
@@ -105,9 +106,8 @@ extern "C" int am_matches_fold_hash(const am_matches* m, const am_needle_ids* id
     if (n_hay && !hash_out) return fail(AM_ERR_INVALID, "hash_out is null");
     if (n_hay >= 0xFFFFFFFFull) return fail(AM_ERR_INVALID, "too many haystacks");
     if (n_hay == 0) return AM_OK;
-    if (m->n && !m->d_records) return fail(AM_ERR_UNSUPPORTED, "am_matches_fold_hash: the result was assembled on the host (am_run on a large host batch) and has no records in HBM");
+    AM_TRY(matches_in_hbm(m, ids, "am_matches_fold_hash"));
     AM_TRY(ensure_runtime());
-    if (m->dev != ids->a->dev) return fail(AM_ERR_INVALID, "result and values table live on different devices");
     ON_DEVICE(m->dev);
     hipStream_t st; AM_TRY(get_stream(m->dev, &st));
     DevBuf rec_first, out, dummy;
@@ -265,7 +265,7 @@ extern "C" int am_count_by_needle_batch(const am_needle_ids* ids, int case_mode,
 {
     if (!ids || !cb) return fail(AM_ERR_INVALID, "null needle ids or batch");
     if (ids->n_needles && !counts_out) return fail(AM_ERR_INVALID, "counts_out is null");
-    if (case_mode != AM_CASE_SENSITIVE && case_mode != AM_IGNORE_CASE) return fail(AM_ERR_INVALID, "case_mode must be AM_CASE_SENSITIVE or AM_IGNORE_CASE");
+    AM_TRY(check_case(case_mode));
     if (ids->a->dev != cb->dev) return fail(AM_ERR_INVALID, "needle ids and batch live on different devices");
     if (ids->n_needles == 0) return AM_OK;
     AM_TRY(ensure_runtime());
@@ -284,9 +284,8 @@ extern "C" int am_matches_count_by_needle(const am_matches* m, const am_needle_i
     if (!m || !ids) return fail(AM_ERR_INVALID, "null matches or values table");
     if (ids->n_needles && !counts_out) return fail(AM_ERR_INVALID, "counts_out is null");
     if (ids->n_needles == 0) return AM_OK;
-    if (m->n && !m->d_records) return fail(AM_ERR_UNSUPPORTED, "am_matches_count_by_needle: the result was assembled on the host (am_run on a large host batch) and has no records in HBM");
+    AM_TRY(matches_in_hbm(m, ids, "am_matches_count_by_needle"));
     AM_TRY(ensure_runtime());
-    if (m->dev != ids->a->dev) return fail(AM_ERR_INVALID, "result and values table live on different devices");
     if (m->n == 0) { std::memset(counts_out, 0, (size_t)ids->n_needles * 8); return AM_OK; }
     ON_DEVICE(m->dev);
     hipStream_t st; AM_TRY(get_stream(m->dev, &st));
@@ -296,60 +295,23 @@ extern "C" int am_matches_count_by_needle(const am_matches* m, const am_needle_i
     return out.finish(counts_out, st);
 }
 
-constexpr uint64_t kHistSegmentedFrom = 1ull << 30;       // as am_run: host batches from here on go up in segments of whole haystacks
-constexpr uint64_t kHistSegment = 256ull << 20;
-
 extern "C" int am_count_by_needle(const am_needle_ids* ids, int case_mode, const am_slice* hay, size_t n_hay, uint64_t* counts_out)
 {
     if (!ids) return fail(AM_ERR_INVALID, "null needle ids");
-    if (n_hay && !hay) return fail(AM_ERR_INVALID, "hay is null");
-    if (n_hay >= 0xFFFFFFFFull) return fail(AM_ERR_INVALID, "too many haystacks");
-    if (ids->n_needles && !counts_out) return fail(AM_ERR_INVALID, "counts_out is null");
-    if (case_mode != AM_CASE_SENSITIVE && case_mode != AM_IGNORE_CASE) return fail(AM_ERR_INVALID, "case_mode must be AM_CASE_SENSITIVE or AM_IGNORE_CASE");
     uint64_t total = 0;
-    for (size_t i = 0; i < n_hay; i++) { if (hay[i].len && !hay[i].ptr) return fail(AM_ERR_INVALID, "slice with null ptr"); total += hay[i].len; }
+    AM_TRY(check_slices(hay, n_hay, &total));
+    if (ids->n_needles && !counts_out) return fail(AM_ERR_INVALID, "counts_out is null");
+    AM_TRY(check_case(case_mode));
     if (ids->n_needles == 0) return AM_OK;
     AM_TRY(ensure_runtime());
     if (total == 0) { std::memset(counts_out, 0, (size_t)ids->n_needles * 8); return AM_OK; }
     const int dev = ids->a->dev;
     ON_DEVICE(dev);
-    const long forced = cfg::get(cfg::kRunSegments);       // (the switch of am_run's segments: 0 = never, k > 0 = always, segments of k KiB)
-    if (n_hay < 2 || forced == 0 || (forced < 0 && total < kHistSegmentedFrom)) {
-        am_batch* b = oneshot_batch(dev);                   // this thread's batch on the automaton's device
-        int rc = upload_batch(hay, n_hay, b, true);
-        if (rc == AM_OK) rc = am_count_by_needle_batch(ids, case_mode, b, counts_out);
-        oneshot_batch_trim(dev);
-        return rc;
-    }
-    // Segments of whole haystacks into two batches that take turns: while this thread uploads segment k + 1, a thread of its own scans segment k and folds its
-    // records in HBM.  What the wire carries is the text, once, and n_needles counts at the end.
     hipStream_t st; AM_TRY(get_stream(dev, &st));
+    // What the wire carries is the text, once (in one piece or in segments: fold_slices), and n_needles counts at the end.
     HistOut out;
     AM_TRY(out.begin(ids->n_needles, st));
-    std::unique_ptr<am_batch, void (*)(am_batch*)> second(new am_batch(), am_batch_destroy);
-    second->dev = dev;
-    am_batch* turn[2] = {oneshot_batch(dev), second.get()};
-    const uint64_t segment = forced > 0 ? (uint64_t)forced << 10 : kHistSegment;
-    std::thread worker;
-    int rc = AM_OK, worker_rc = AM_OK; std::string worker_err;
-    auto join = [&] { if (worker.joinable()) worker.join(); if (rc == AM_OK && worker_rc != AM_OK) rc = fail(worker_rc, worker_err); };
-    size_t k = 0;
-    for (size_t i = 0; i < n_hay && rc == AM_OK; k++) {
-        size_t j = i; uint64_t bytes = 0;
-        while (j < n_hay && bytes < (i == 0 ? segment / 4 : segment)) bytes += hay[j++].len;      // (the first a quarter of the others: no scan runs beside its upload)
-        am_batch* b = turn[k & 1];                          // (its last scan, segment k - 2, was joined before segment k - 1 started)
-        rc = upload_batch(hay + i, j - i, b, false);
-        join();
-        if (rc != AM_OK) break;
-        worker = std::thread([&, b] {
-            worker_rc = hist_batch(ids, case_mode, b, out.counts(), out.trace_words());
-            if (worker_rc != AM_OK) worker_err = am_last_error();
-        });
-        i = j;
-    }
-    join();
-    oneshot_batch_trim(dev);
-    if (rc != AM_OK) return rc;
+    AM_TRY(fold_slices(dev, hay, n_hay, total, [&](am_batch* b, size_t) { return hist_batch(ids, case_mode, b, out.counts(), out.trace_words()); }));
     return out.finish(counts_out, st);
 }
 
@@ -358,13 +320,7 @@ extern "C" int am_count_by_needle(const am_needle_ids* ids, int case_mode, const
 // needle order.  The kernels are am_matrix.hip; the scans, the record budget and its groups of whole haystacks are fold_batch's, above.  Rows belong to
 // haystacks and a group is whole haystacks: every group leaves a part {local offsets, entries with the batch's haystack index}, and the parts are appended at the end.
 
-struct am_needle_matrix {
-    int dev = 0;
-    uint64_t n_hay = 0, n_entries = 0;
-    DevBuf offsets, data;                                 // uint64[n_hay + 1], NeedleCount[n_entries] in HBM (none when n_hay == 0)
-    std::vector<uint64_t> h_offsets; std::vector<am_needle_count> h_data;
-    bool offsets_fetched = false, data_fetched = false;
-};
+struct am_needle_matrix : CsrResult<am_needle_count> {};
 
 static_assert(sizeof(am_needle_count) == sizeof(NeedleCount) && sizeof(NeedleCount) == 16, "am_needle_count and the kernels' NeedleCount are one layout");
 static_assert(offsetof(am_needle_count, count) == 0 && offsetof(am_needle_count, needle) == 8 && offsetof(am_needle_count, haystack) == 12, "am_needle_count: offsets 0, 8, 12");
@@ -447,19 +403,14 @@ struct MatrixBuild {
     // the parts appended: offsets rebased by the entries before them, haystacks no part covers (nothing matched there) get empty rows
     int finish(int dev, uint64_t n_hay, hipStream_t st, am_needle_matrix** out)
     {
+        if (n_hay == 0) return empty_result(dev, out);
         std::unique_ptr<am_needle_matrix, void (*)(am_needle_matrix*)> x(new am_needle_matrix(), am_needle_matrix_free);
         x->dev = dev; x->n_hay = n_hay;
-        if (n_hay == 0) {                                   // offsets = [0], nothing in HBM
-            x->h_offsets.assign(1, 0); x->h_data.assign(1, am_needle_count{0, 0, 0});
-            x->offsets_fetched = x->data_fetched = true;
-            *out = x.release();
-            return AM_OK;
-        }
         if (parts.size() == 1 && parts[0]->h0 == 0 && parts[0]->n == n_hay) {
             Part& p = *parts[0];
             std::swap(x->offsets.p, p.offsets.p); std::swap(x->offsets.cap, p.offsets.cap);
             std::swap(x->data.p, p.data.p); std::swap(x->data.cap, p.data.cap);
-            x->n_entries = p.entries;
+            x->n_items = p.entries;
             *out = x.release();
             return AM_OK;
         }
@@ -478,16 +429,11 @@ struct MatrixBuild {
         }
         HIP_TRY(launch_mx_offsets(nullptr, n_hay + 1 - h, base, offs + h, st));
         HIP_TRY(hipStreamSynchronize(st));
-        x->n_entries = total;
+        x->n_items = total;
         *out = x.release();
         return AM_OK;
     }
 };
-
-int matrix_case(int case_mode)
-{
-    return case_mode == AM_CASE_SENSITIVE || case_mode == AM_IGNORE_CASE ? AM_OK : fail(AM_ERR_INVALID, "case_mode must be AM_CASE_SENSITIVE or AM_IGNORE_CASE");
-}
 
 // the rows of batch `b`, whose first haystack is haystack `base` of the call, into mb
 int matrix_batch(MatrixBuild& mb, const am_needle_ids* ids, int case_mode, am_batch* b, uint64_t base)
@@ -512,7 +458,7 @@ extern "C" int am_count_matrix_batch(const am_needle_ids* ids, int case_mode, co
     if (!out) return fail(AM_ERR_INVALID, "out is null");
     *out = nullptr;
     if (!ids || !cb) return fail(AM_ERR_INVALID, "null needle ids or batch");
-    AM_TRY(matrix_case(case_mode));
+    AM_TRY(check_case(case_mode));
     if (ids->a->dev != cb->dev) return fail(AM_ERR_INVALID, "needle ids and batch live on different devices");
     AM_TRY(ensure_runtime());
     am_batch* b = const_cast<am_batch*>(cb);
@@ -529,9 +475,8 @@ extern "C" int am_matches_count_matrix(const am_matches* m, const am_needle_ids*
     *out = nullptr;
     if (!m || !ids) return fail(AM_ERR_INVALID, "null matches or values table");
     if (n_hay >= 0xFFFFFFFFull) return fail(AM_ERR_INVALID, "too many haystacks");
-    if (m->n && !m->d_records) return fail(AM_ERR_UNSUPPORTED, "am_matches_count_matrix: the result was assembled on the host (am_run on a large host batch) and has no records in HBM");
+    AM_TRY(matches_in_hbm(m, ids, "am_matches_count_matrix"));
     AM_TRY(ensure_runtime());
-    if (m->dev != ids->a->dev) return fail(AM_ERR_INVALID, "result and values table live on different devices");
     ON_DEVICE(m->dev);
     hipStream_t st; AM_TRY(get_stream(m->dev, &st));
     MatrixBuild mb(ids);
@@ -550,90 +495,35 @@ extern "C" int am_count_matrix(const am_needle_ids* ids, int case_mode, const am
     if (!out) return fail(AM_ERR_INVALID, "out is null");
     *out = nullptr;
     if (!ids) return fail(AM_ERR_INVALID, "null needle ids");
-    if (n_hay && !hay) return fail(AM_ERR_INVALID, "hay is null");
-    if (n_hay >= 0xFFFFFFFFull) return fail(AM_ERR_INVALID, "too many haystacks");
-    AM_TRY(matrix_case(case_mode));
     uint64_t total = 0;
-    for (size_t i = 0; i < n_hay; i++) { if (hay[i].len && !hay[i].ptr) return fail(AM_ERR_INVALID, "slice with null ptr"); total += hay[i].len; }
+    AM_TRY(check_slices(hay, n_hay, &total));
+    AM_TRY(check_case(case_mode));
     AM_TRY(ensure_runtime());
     const int dev = ids->a->dev;
     ON_DEVICE(dev);
     hipStream_t st; AM_TRY(get_stream(dev, &st));
     MatrixBuild mb(ids);
-    if (total == 0 || ids->n_needles == 0) return mb.finish(dev, n_hay, st, out);
-    const long forced = cfg::get(cfg::kRunSegments);       // (as am_count_by_needle: 0 = never, k > 0 = always, segments of k KiB)
-    if (n_hay < 2 || forced == 0 || (forced < 0 && total < kHistSegmentedFrom)) {
-        am_batch* b = oneshot_batch(dev);                   // this thread's batch on the automaton's device
-        int rc = upload_batch(hay, n_hay, b, true);
-        if (rc == AM_OK) rc = matrix_batch(mb, ids, case_mode, b, 0);
-        oneshot_batch_trim(dev);
-        if (rc != AM_OK) return rc;
-        return mb.finish(dev, n_hay, st, out);
-    }
-    // segments of whole haystacks, as am_count_by_needle sends them: a segment's rows are built in HBM while the next segment goes up, and appended in order
-    std::unique_ptr<am_batch, void (*)(am_batch*)> second(new am_batch(), am_batch_destroy);
-    second->dev = dev;
-    am_batch* turn[2] = {oneshot_batch(dev), second.get()};
-    const uint64_t segment = forced > 0 ? (uint64_t)forced << 10 : kHistSegment;
-    std::thread worker;
-    int rc = AM_OK, worker_rc = AM_OK; std::string worker_err;
-    auto join = [&] { if (worker.joinable()) worker.join(); if (rc == AM_OK && worker_rc != AM_OK) rc = fail(worker_rc, worker_err); };
-    size_t k = 0;
-    for (size_t i = 0; i < n_hay && rc == AM_OK; k++) {
-        size_t j = i; uint64_t bytes = 0;
-        while (j < n_hay && bytes < (i == 0 ? segment / 4 : segment)) bytes += hay[j++].len;
-        am_batch* b = turn[k & 1];
-        rc = upload_batch(hay + i, j - i, b, false);
-        join();
-        if (rc != AM_OK) break;
-        worker = std::thread([&, b, i] {
-            worker_rc = matrix_batch(mb, ids, case_mode, b, i);
-            if (worker_rc != AM_OK) worker_err = am_last_error();
-        });
-        i = j;
-    }
-    join();
-    oneshot_batch_trim(dev);
-    if (rc != AM_OK) return rc;
+    // a segment's rows are built in HBM while the next segment goes up (fold_slices), and appended in order
+    if (total != 0 && ids->n_needles != 0)
+        AM_TRY(fold_slices(dev, hay, n_hay, total, [&](am_batch* b, size_t first) { return matrix_batch(mb, ids, case_mode, b, first); }));
     return mb.finish(dev, n_hay, st, out);
 }
 
-extern "C" uint64_t am_needle_matrix_size(const am_needle_matrix* x) { return x ? x->n_entries : 0; }
+extern "C" uint64_t am_needle_matrix_size(const am_needle_matrix* x) { return x ? x->n_items : 0; }
 extern "C" uint64_t am_needle_matrix_haystacks(const am_needle_matrix* x) { return x ? x->n_hay : 0; }
 extern "C" const void* am_needle_matrix_device_offsets(const am_needle_matrix* x) { return x ? x->offsets.p : nullptr; }
 extern "C" const void* am_needle_matrix_device_data(const am_needle_matrix* x) { return x ? x->data.p : nullptr; }
 
-namespace {
-template <class T>
-const T* matrix_fetch(am_needle_matrix* x, std::vector<T>& host, bool& fetched, const DevBuf& d, uint64_t n)
-{
-    if (fetched) return host.data();
-    try { host.resize((size_t)std::max<uint64_t>(n, 1)); } catch (const std::exception&) { fail(AM_ERR_OOM, "no host memory for the matrix"); return nullptr; }
-    if (n) {
-        if (ensure_runtime() != AM_OK) return nullptr;
-        OnDevice od(x->dev);
-        hipStream_t st;
-        if (od.rc != AM_OK || get_stream(x->dev, &st) != AM_OK) return nullptr;
-        if (hipMemcpyAsync(host.data(), d.p, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-            fail(AM_ERR_HIP, "copying the matrix to the host failed");
-            return nullptr;
-        }
-    }
-    fetched = true;
-    return host.data();
-}
-}  // namespace
-
 extern "C" const uint64_t* am_needle_matrix_offsets(am_needle_matrix* x)
 {
     if (!x) { fail(AM_ERR_INVALID, "null matrix"); return nullptr; }
-    return matrix_fetch(x, x->h_offsets, x->offsets_fetched, x->offsets, x->n_hay + 1);
+    return x->fetch_offsets("the matrix");
 }
 
 extern "C" const am_needle_count* am_needle_matrix_data(am_needle_matrix* x)
 {
     if (!x) { fail(AM_ERR_INVALID, "null matrix"); return nullptr; }
-    return matrix_fetch(x, x->h_data, x->data_fetched, x->data, x->n_entries);
+    return x->fetch_data("the matrix");
 }
 
 extern "C" void am_needle_matrix_free(am_needle_matrix* x) { delete x; }

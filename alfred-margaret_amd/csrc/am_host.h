@@ -1,6 +1,8 @@
 // am_host.h -- what the host-side translation units of libam share (am_abi.cpp: runtime and thread state, automata, batches, one-shot entry points, results;
-// am_run.cpp: routes and scans; am_replacer.cpp: the Replacer; am_contains_all.cpp: containsAll and the fold checksum; am_splitter.cpp: the Splitter): error handling, the per-device runtime,
-// device buffers, the handle structs of include/am.h and the few scan entry points the Replacer drives.  Internal: nothing here is part of the C ABI.
+// am_run.cpp: routes and scans; am_replacer.cpp: the Replacer; am_contains_all.cpp: containsAll, the fold checksum, the per-needle counts and the needle matrix;
+// am_splitter.cpp: the Splitter; am_spans.cpp: match spans): error handling, the per-device runtime, device buffers, the handle structs of include/am.h and the few
+// scan entry points the Replacer drives.  am_fold.h, included at the end, holds what the folds over a scan's records share: argument checks, the CSR result handle,
+// the chain finisher and the segment loop.  Internal: nothing here is part of the C ABI.
 #pragma once
 #include "../../include/am.h"
 #include "../../include/am_debug.h"
@@ -248,3 +250,5 @@ inline constexpr RpRoute kNoRoute{nullptr, nullptr, nullptr, nullptr, nullptr};
 
 }  // namespace host
 }  // namespace am
+
+#include "am_fold.h"

@@ -1,6 +1,7 @@
 // am_spans.cpp -- match spans on the device (include/am.h "match spans"): one scan of the batch, then the records a scan leaves in HBM are expanded through the value
 // lists and the needles' own lengths into (start, len, haystack, needle), all of them in fold order or the leftmost-longest non-overlapping selection
-// (am_spans.hip).  The result is CSR like am_fragments and stays in HBM until asked for.
+// (am_spans.hip).  The result is CSR like am_fragments and stays in HBM until asked for: its handle, the finisher of long chains and the argument checks are
+// am_fold.h's, shared with the other folds.
 #include "am_host.h"
 
 #include <cstddef>
@@ -14,13 +15,8 @@ struct am_span_table {
     DevBuf len_bytes, len_cps;                              // uint32[n_needles] each, on the automaton's device
 };
 
-struct am_spans {
-    int dev = 0;
-    uint64_t n_span = 0, n_hay = 0;
+struct am_spans : CsrResult<am_span> {
     uint32_t rounds = 0;                                    // pointer-doubling rounds of the call
-    DevBuf data, offsets;                                   // Span[n_span], uint64[n_hay + 1] in HBM (none when n_hay == 0)
-    std::vector<am_span> h_data; std::vector<uint64_t> h_offsets;
-    bool data_fetched = false, offsets_fetched = false;
 };
 
 using SpansResult = struct am_spans;                     // (am_spans alone names the one-shot entry point)
@@ -32,37 +28,19 @@ namespace {
 
 constexpr uint32_t kSpansChainLimit = 32;                   // candidates the lane of a chain's head looks at before the chain goes to the doubling rounds
 
-int read_u64(const void* d_src, uint64_t* out, hipStream_t st)
-{
-    HIP_TRY(hipMemcpyAsync(out, d_src, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return AM_OK;
-}
-
 int check_modes(int case_mode, int mode)
 {
-    if (case_mode != AM_CASE_SENSITIVE && case_mode != AM_IGNORE_CASE) return fail(AM_ERR_INVALID, "case_mode must be AM_CASE_SENSITIVE or AM_IGNORE_CASE");
+    AM_TRY(check_case(case_mode));
     if (mode != AM_SPANS_ALL && mode != AM_SPANS_LEFTMOST_LONGEST) return fail(AM_ERR_INVALID, "mode must be AM_SPANS_ALL or AM_SPANS_LEFTMOST_LONGEST");
     return AM_OK;
 }
 
-// no haystacks: zero spans, offsets = [0], nothing in HBM
-int no_spans(int dev, SpansResult** out)
-{
-    SpansResult* s = new SpansResult();
-    s->dev = dev;
-    s->h_offsets.assign(1, 0); s->h_data.assign(1, am_span{0, 0, 0, 0});
-    s->offsets_fetched = s->data_fetched = true;
-    *out = s;
-    return AM_OK;
-}
-
-// the leftmost-longest selection over the spans in HBM: s->data, s->n_span, s->rounds and span_off
+// the leftmost-longest selection over the spans in HBM: s->data, s->n_items, s->rounds and span_off
 int select_leftmost_longest(const SpansIn& in, const Span* spans, uint64_t n_span, SpansResult* s, hipStream_t st)
 {
     uint64_t* const span_off = (uint64_t*)s->offsets.p;
     const uint64_t n_words = (in.total + 31) / 32;
-    DevBuf bits, pc, rank, scan_tmp, best, cand, tile_max, head, kept, kidx, flag, jump0, jump1;
+    DevBuf bits, pc, rank, scan_tmp, best, cand, tile_max, head, kept, kidx, flag;
     uint64_t n_cand = 0;
     if (n_span != 0 && n_words != 0) {
         AM_TRY(bits.ensure((n_words + 1) * 4));
@@ -81,7 +59,7 @@ int select_leftmost_longest(const SpansIn& in, const Span* spans, uint64_t n_spa
     }
     if (n_cand == 0) {                                      // nothing but zero-length spans, or nothing at all: empty rows
         HIP_TRY(hipMemsetAsync(span_off, 0, ((uint64_t)in.n_hay + 1) * 8, st));
-        s->n_span = 0;
+        s->n_items = 0;
         return AM_OK;
     }
     AM_TRY(best.ensure(n_cand * 8));
@@ -109,32 +87,13 @@ int select_leftmost_longest(const SpansIn& in, const Span* spans, uint64_t n_spa
     const long lim = cfg::get(cfg::kSpansChainLimit);
     { Prof pr("spans_walk", st);
       HIP_TRY(launch_spans_walk(cg, bs, n_cand, (const uint8_t*)head.p, kp, lim > 0 ? (uint32_t)std::min<long>(lim, 1L << 30) : kSpansChainLimit, fl, st)); }
-    uint32_t long_chains = 0;
-    if (n_cand > 1) {
-        HIP_TRY(hipMemcpyAsync(&long_chains, fl, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    if (long_chains) {
-        AM_TRY(jump0.ensure(n_cand * 8));
-        AM_TRY(jump1.ensure(n_cand * 8));
-        uint64_t* jump[2] = {(uint64_t*)jump0.p, (uint64_t*)jump1.p};
-        { Prof pr("spans_next", st);
-          HIP_TRY(launch_spans_next(cg, bs, n_cand, (const uint8_t*)head.p, jump[0], st)); }
-        uint32_t rounds = 0;
-        for (uint32_t marked = 1; marked != 0 && rounds < 64; rounds++) {      // (a path of k candidates is marked after log2(k) + 1 rounds: 64 is no limit for 64-bit indices)
-            HIP_TRY(hipMemsetAsync(fl + 1, 0, 4, st));
-            { Prof pr("spans_double", st);
-              HIP_TRY(launch_split_double(jump[rounds & 1], jump[(rounds & 1) ^ 1], n_cand, kp, fl + 1, st)); }
-            HIP_TRY(hipMemcpyAsync(&marked, fl + 1, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        }
-        s->rounds = rounds;
-    }
+    AM_TRY(finish_long_chains(n_cand, kp, fl, [&](uint64_t* jump) { return launch_spans_next(cg, bs, n_cand, (const uint8_t*)head.p, jump, st); },
+                              "spans_next", "spans_double", &s->rounds, st));
     HIP_TRY(launch_scan(scan_tmp.p, scan_tmp.cap, kp, (uint64_t*)kidx.p, n_cand + 1, st));
     uint64_t n_out = 0;
     AM_TRY(read_u64((const uint64_t*)kidx.p + n_cand, &n_out, st));
     AM_TRY(s->data.ensure(n_out * sizeof(Span)));
-    s->n_span = n_out;
+    s->n_items = n_out;
     { Prof pr("spans_emit", st);
       HIP_TRY(launch_spans_emit(cg, bs, kp, (const uint64_t*)kidx.p, n_cand, in, (Span*)s->data.p, n_out, span_off, st)); }
     HIP_TRY(hipStreamSynchronize(st));                      // (the workspaces are freed)
@@ -181,7 +140,7 @@ extern "C" int am_spans_batch(const am_span_table* t, int case_mode, int mode, c
     if (ids->a->dev != cb->dev) return fail(AM_ERR_INVALID, "span table and batch live on different devices");
     AM_TRY(ensure_runtime());
     am_batch* b = const_cast<am_batch*>(cb);
-    if (b->n_hay == 0) return no_spans(b->dev, out);
+    if (b->n_hay == 0) return empty_result(b->dev, out);
     std::unique_ptr<SpansResult, void (*)(SpansResult*)> s(new SpansResult(), am_spans_free);
     s->dev = b->dev; s->n_hay = b->n_hay;
     ON_DEVICE(b->dev);
@@ -214,7 +173,7 @@ extern "C" int am_spans_batch(const am_span_table* t, int case_mode, int mode, c
     if (mode == AM_SPANS_ALL) {
         HIP_TRY(launch_rp_ranges(in.recs, n_rec, (uint64_t*)rec_first.p, kNoRoute, b->n_hay, st));
         HIP_TRY(launch_spans_offsets((const uint64_t*)rec_first.p, (const uint64_t*)voff.p, n_rec, b->n_hay, (uint64_t*)s->offsets.p, st));
-        s->n_span = n_span;
+        s->n_items = n_span;
     } else {
         AM_TRY(select_leftmost_longest(in, (const Span*)spans.p, n_span, s.get(), st));
     }
@@ -227,14 +186,12 @@ extern "C" int am_spans(const am_span_table* t, int case_mode, int mode, const a
 {
     if (!out) return fail(AM_ERR_INVALID, "out is null");
     *out = nullptr;
-    if (n_hay && !hay) return fail(AM_ERR_INVALID, "hay is null");
-    if (n_hay >= 0xFFFFFFFFull) return fail(AM_ERR_INVALID, "too many haystacks");
+    AM_TRY(check_slices(hay, n_hay));
     AM_TRY(check_modes(case_mode, mode));
-    for (size_t i = 0; i < n_hay; i++) if (hay[i].len && !hay[i].ptr) return fail(AM_ERR_INVALID, "slice with null ptr");
     if (!t) return fail(AM_ERR_INVALID, "null span table");      // (last: a caller without a device can see every other check)
     AM_TRY(ensure_runtime());
     const int dev = t->ids->a->dev;
-    if (n_hay == 0) return no_spans(dev, out);
+    if (n_hay == 0) return empty_result(dev, out);
     ON_DEVICE(dev);
     am_batch* b = oneshot_batch(dev);                       // this thread's batch on the automaton's device
     int rc = upload_batch(hay, n_hay, b, true);
@@ -243,43 +200,22 @@ extern "C" int am_spans(const am_span_table* t, int case_mode, int mode, const a
     return rc;
 }
 
-extern "C" uint64_t am_spans_size(const SpansResult* s) { return s ? s->n_span : 0; }
+extern "C" uint64_t am_spans_size(const SpansResult* s) { return s ? s->n_items : 0; }
 extern "C" uint64_t am_spans_haystacks(const SpansResult* s) { return s ? s->n_hay : 0; }
 extern "C" uint32_t am_spans_rounds(const SpansResult* s) { return s ? s->rounds : 0; }
 extern "C" const void* am_spans_device_offsets(const SpansResult* s) { return s ? s->offsets.p : nullptr; }
-extern "C" const void* am_spans_device_data(const SpansResult* s) { return s && s->n_span ? s->data.p : nullptr; }
-
-namespace {
-template <class T>
-const T* fetch(SpansResult* s, std::vector<T>& host, bool& fetched, const DevBuf& d, uint64_t n)
-{
-    if (fetched) return host.data();
-    try { host.resize((size_t)std::max<uint64_t>(n, 1)); } catch (const std::exception&) { fail(AM_ERR_OOM, "no host memory for the spans"); return nullptr; }
-    if (n) {
-        if (ensure_runtime() != AM_OK) return nullptr;
-        OnDevice od(s->dev);
-        hipStream_t st;
-        if (od.rc != AM_OK || get_stream(s->dev, &st) != AM_OK) return nullptr;
-        if (hipMemcpyAsync(host.data(), d.p, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-            fail(AM_ERR_HIP, "copying the spans to the host failed");
-            return nullptr;
-        }
-    }
-    fetched = true;
-    return host.data();
-}
-}  // namespace
+extern "C" const void* am_spans_device_data(const SpansResult* s) { return s && s->n_items ? s->data.p : nullptr; }
 
 extern "C" const uint64_t* am_spans_offsets(SpansResult* s)
 {
     if (!s) { fail(AM_ERR_INVALID, "null spans"); return nullptr; }
-    return fetch(s, s->h_offsets, s->offsets_fetched, s->offsets, s->n_hay + 1);
+    return s->fetch_offsets("the spans");
 }
 
 extern "C" const am_span* am_spans_data(SpansResult* s)
 {
     if (!s) { fail(AM_ERR_INVALID, "null spans"); return nullptr; }
-    return fetch(s, s->h_data, s->data_fetched, s->data, s->n_span);
+    return s->fetch_data("the spans");
 }
 
 extern "C" void am_spans_free(SpansResult* s) { delete s; }

@@ -28,6 +28,7 @@
 
 #include "am_bounds.h"
 #include "am_device.h"
+#include "am_wave.h"
 
 AM_BOUNDS_TU("am_spans.hip")
 
@@ -67,14 +68,7 @@ __device__ __forceinline__ uint64_t span_start(const SpansIn& in, const Record& 
     AM_BOUNDS(base + r.end_pos <= in.total);
     if (base + r.end_pos > in.total) return 0;
     const uint8_t* hay = in.text + base;
-    int64_t index = (int64_t)r.end_pos - 1;                            // Utf8.hs:256-276 skipCodePointsBackwards hay (end - 1) (cps - 1)
-    uint32_t n = in.len_cps[v] - 1;                                    // (nb != 0: the table has at least one code point for it)
-    for (;;) {
-        if (index >= 0 && (hay[index] & 0xC0) == 0x80) { index--; continue; }
-        if (index < 0) return 0;                                       // (the reference calls `error`: not reachable for a match the automaton reported)
-        if (n == 0) return (uint64_t)index;
-        index--; n--;
-    }
+    return skip_code_points_backwards(hay, r.end_pos, in.len_cps[v] - 1);      // (nb != 0: the table has at least one code point for it)
 }
 
 // one lane per record (+ one for the trailing zero of the scan's input): its values < n_needles

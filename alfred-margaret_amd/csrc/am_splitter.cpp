@@ -1,6 +1,7 @@
 // am_splitter.cpp -- Data.Text.AhoCorasick.Splitter on the device (reference: src/Data/Text/AhoCorasick/Splitter.hs): one scan of the batch with the one-needle
 // automaton, then stepAccum / finalizeAccum (:141-170) over the sorted records in HBM (am_split.hip).  What comes back is a list of (start, length) per haystack that
 // stays in HBM until asked for, and am_batch_from_fragments turns it into a batch of its own: document -> lines -> any *_batch entry point, without the host.
+// The result handle, the chain finisher and the argument checks are am_fold.h's, shared with the other folds.
 #include "am_host.h"
 
 using namespace am;
@@ -12,12 +13,8 @@ struct am_splitter {
     uint32_t sep_bytes = 0, sep_cps = 0;
 };
 
-struct am_fragments {
-    int dev = 0;
-    uint64_t n_frag = 0, n_hay = 0, src_total = 0;        // src_total: bytes of the batch they were cut from (am_batch_from_fragments checks it)
-    DevBuf data, offsets;                                 // Fragment[n_frag], uint64[n_hay + 1] in HBM (none when n_hay == 0)
-    std::vector<am_fragment> h_data; std::vector<uint64_t> h_offsets;
-    bool data_fetched = false, offsets_fetched = false;
+struct am_fragments : CsrResult<am_fragment> {
+    uint64_t src_total = 0;                               // bytes of the batch they were cut from (am_batch_from_fragments checks it)
 };
 
 static_assert(sizeof(am_fragment) == sizeof(Fragment), "am_fragment and the kernels' Fragment are one layout");
@@ -28,31 +25,8 @@ constexpr uint32_t kSplitChainLimit = 32;                 // records the lane of
 std::atomic<uint32_t> g_split_rounds{0};                  // doubling rounds of the last am_split_batch (am_debug_split_rounds)
 
 struct Bufs {
-    DevBuf start, head, kept, kidx, scan_tmp, rec_first, flag, jump0, jump1;
+    DevBuf start, head, kept, kidx, scan_tmp, rec_first, flag;
 };
-
-int read_u64(const void* d_src, uint64_t* out, hipStream_t st)
-{
-    HIP_TRY(hipMemcpyAsync(out, d_src, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return AM_OK;
-}
-
-int check_case(int case_mode)
-{
-    return case_mode == AM_CASE_SENSITIVE || case_mode == AM_IGNORE_CASE ? AM_OK : fail(AM_ERR_INVALID, "case_mode must be AM_CASE_SENSITIVE or AM_IGNORE_CASE");
-}
-
-// no haystacks: zero fragments, offsets = [0], nothing in HBM
-int no_fragments(int dev, am_fragments** out)
-{
-    am_fragments* f = new am_fragments();
-    f->dev = dev;
-    f->h_offsets.assign(1, 0); f->h_data.assign(1, am_fragment{0, 0});
-    f->offsets_fetched = f->data_fetched = true;
-    *out = f;
-    return AM_OK;
-}
 
 }  // namespace
 
@@ -90,7 +64,7 @@ extern "C" int am_split_batch(const am_splitter* s, int case_mode, const am_batc
     std::unique_ptr<am_fragments, void (*)(am_fragments*)> f(new am_fragments(), am_fragments_free);
     f->dev = b->dev; f->n_hay = b->n_hay; f->src_total = b->total;
     g_split_rounds.store(0, std::memory_order_relaxed);
-    if (b->n_hay == 0) return no_fragments(b->dev, out);
+    if (b->n_hay == 0) return empty_result(b->dev, out);
     ON_DEVICE(b->dev);
     hipStream_t st; AM_TRY(get_stream(b->dev, &st));
     RecordArray ra(b->dev);
@@ -116,36 +90,20 @@ extern "C" int am_split_batch(const am_splitter* s, int case_mode, const am_batc
     const long lim = cfg::get(cfg::kSplitChainLimit);
     { Prof pr("split_walk", st);
       HIP_TRY(launch_split_walk(in.recs, n_rec, (const uint64_t*)w.start.p, (const uint8_t*)w.head.p, kept, lim > 0 ? (uint32_t)std::min<long>(lim, 1L << 30) : kSplitChainLimit, flag, st)); }
-    uint32_t long_chains = 0;
-    if (n_rec > 1) {
-        HIP_TRY(hipMemcpyAsync(&long_chains, flag, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    if (long_chains) {
-        AM_TRY(w.jump0.ensure(n_rec * 8));
-        AM_TRY(w.jump1.ensure(n_rec * 8));
-        uint64_t* jump[2] = {(uint64_t*)w.jump0.p, (uint64_t*)w.jump1.p};
-        { Prof pr("split_next", st);
-          HIP_TRY(launch_split_next(in.recs, n_rec, (const uint64_t*)w.start.p, (const uint8_t*)w.head.p, jump[0], st)); }
-        uint32_t rounds = 0;
-        for (uint32_t marked = 1; marked != 0 && rounds < 64; rounds++) {      // (a path of k records is marked after log2(k) + 1 rounds: 64 is no limit for 64-bit indices)
-            HIP_TRY(hipMemsetAsync(flag + 1, 0, 4, st));
-            { Prof pr("split_double", st);
-              HIP_TRY(launch_split_double(jump[rounds & 1], jump[(rounds & 1) ^ 1], n_rec, kept, flag + 1, st)); }
-            HIP_TRY(hipMemcpyAsync(&marked, flag + 1, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        }
-        g_split_rounds.store(rounds, std::memory_order_relaxed);
-    }
+    uint32_t rounds = 0;
+    AM_TRY(finish_long_chains(n_rec, kept, flag, [&](uint64_t* jump) {
+        return launch_split_next(in.recs, n_rec, (const uint64_t*)w.start.p, (const uint8_t*)w.head.p, jump, st);
+    }, "split_next", "split_double", &rounds, st));
+    g_split_rounds.store(rounds, std::memory_order_relaxed);
     HIP_TRY(launch_scan(w.scan_tmp.p, w.scan_tmp.cap, kept, (uint64_t*)w.kidx.p, n_rec + 1, st));
     uint64_t n_kept = 0;
     AM_TRY(read_u64((const uint64_t*)w.kidx.p + n_rec, &n_kept, st));
-    f->n_frag = n_kept + b->n_hay;
-    AM_TRY(f->data.ensure(f->n_frag * sizeof(Fragment)));
+    f->n_items = n_kept + b->n_hay;
+    AM_TRY(f->data.ensure(f->n_items * sizeof(Fragment)));
     AM_TRY(f->offsets.ensure(((uint64_t)b->n_hay + 1) * 8));
     { Prof pr("split_emit", st);
       HIP_TRY(launch_split_emit(in, (const uint64_t*)w.start.p, kept, (const uint64_t*)w.kidx.p, (const uint64_t*)w.rec_first.p, (uint64_t*)f->offsets.p,
-                                (Fragment*)f->data.p, f->n_frag, st)); }
+                                (Fragment*)f->data.p, f->n_items, st)); }
     HIP_TRY(hipStreamSynchronize(st));                      // (the record array goes back to the cache, the workspaces are freed)
     *out = f.release();
     return AM_OK;
@@ -156,13 +114,11 @@ extern "C" int am_split(const am_splitter* s, int case_mode, const am_slice* hay
     if (!out) return fail(AM_ERR_INVALID, "out is null");
     *out = nullptr;
     if (!s) return fail(AM_ERR_INVALID, "null splitter");
-    if (n_hay && !hay) return fail(AM_ERR_INVALID, "hay is null");
-    if (n_hay >= 0xFFFFFFFFull) return fail(AM_ERR_INVALID, "too many haystacks");
+    AM_TRY(check_slices(hay, n_hay));
     AM_TRY(check_case(case_mode));
-    for (size_t i = 0; i < n_hay; i++) if (hay[i].len && !hay[i].ptr) return fail(AM_ERR_INVALID, "slice with null ptr");
     AM_TRY(ensure_runtime());
     const int dev = s->a->dev;
-    if (n_hay == 0) return no_fragments(dev, out);
+    if (n_hay == 0) return empty_result(dev, out);
     ON_DEVICE(dev);
     am_batch* b = oneshot_batch(dev);                       // this thread's batch on the automaton's device
     int rc = upload_batch(hay, n_hay, b, true);
@@ -171,42 +127,21 @@ extern "C" int am_split(const am_splitter* s, int case_mode, const am_slice* hay
     return rc;
 }
 
-extern "C" uint64_t am_fragments_size(const am_fragments* f) { return f ? f->n_frag : 0; }
+extern "C" uint64_t am_fragments_size(const am_fragments* f) { return f ? f->n_items : 0; }
 extern "C" uint64_t am_fragments_haystacks(const am_fragments* f) { return f ? f->n_hay : 0; }
 extern "C" const void* am_fragments_device_offsets(const am_fragments* f) { return f ? f->offsets.p : nullptr; }
 extern "C" const void* am_fragments_device_data(const am_fragments* f) { return f ? f->data.p : nullptr; }
 
-namespace {
-template <class T>
-const T* fetch(am_fragments* f, std::vector<T>& host, bool& fetched, const DevBuf& d, uint64_t n)
-{
-    if (fetched) return host.data();
-    try { host.resize((size_t)std::max<uint64_t>(n, 1)); } catch (const std::exception&) { fail(AM_ERR_OOM, "no host memory for the fragments"); return nullptr; }
-    if (n) {
-        if (ensure_runtime() != AM_OK) return nullptr;
-        OnDevice od(f->dev);
-        hipStream_t st;
-        if (od.rc != AM_OK || get_stream(f->dev, &st) != AM_OK) return nullptr;
-        if (hipMemcpyAsync(host.data(), d.p, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-            fail(AM_ERR_HIP, "copying the fragments to the host failed");
-            return nullptr;
-        }
-    }
-    fetched = true;
-    return host.data();
-}
-}  // namespace
-
 extern "C" const uint64_t* am_fragments_offsets(am_fragments* f)
 {
     if (!f) { fail(AM_ERR_INVALID, "null fragments"); return nullptr; }
-    return fetch(f, f->h_offsets, f->offsets_fetched, f->offsets, f->n_hay + 1);
+    return f->fetch_offsets("the fragments");
 }
 
 extern "C" const am_fragment* am_fragments_data(am_fragments* f)
 {
     if (!f) { fail(AM_ERR_INVALID, "null fragments"); return nullptr; }
-    return fetch(f, f->h_data, f->data_fetched, f->data, f->n_frag);
+    return f->fetch_data("the fragments");
 }
 
 extern "C" void am_fragments_free(am_fragments* f) { delete f; }
@@ -218,13 +153,13 @@ extern "C" int am_batch_from_fragments(const am_batch* src, const am_fragments* 
     if (!src || !f) return fail(AM_ERR_INVALID, "null batch or fragments");
     if (f->n_hay != src->n_hay || f->src_total != src->total || f->dev != src->dev)
         return fail(AM_ERR_INVALID, "the fragments were not produced from a batch with this haystack count and size");
-    if (f->n_frag >= 0xFFFFFFFFull) return fail(AM_ERR_UNSUPPORTED, "am_batch_from_fragments: 2^32 - 1 fragments and more do not fit a batch");
+    if (f->n_items >= 0xFFFFFFFFull) return fail(AM_ERR_UNSUPPORTED, "am_batch_from_fragments: 2^32 - 1 fragments and more do not fit a batch");
     AM_TRY(ensure_runtime());
     ON_DEVICE(src->dev);
     hipStream_t st; AM_TRY(get_stream(src->dev, &st));
     std::unique_ptr<am_batch, void (*)(am_batch*)> nb(new am_batch(), am_batch_destroy);
     nb->dev = src->dev; nb->owns = true;
-    const uint64_t n = f->n_frag;
+    const uint64_t n = f->n_items;
     DevBuf lens, src_at, scan_tmp;
     AM_TRY(lens.ensure((n + 1) * 8));
     AM_TRY(src_at.ensure((n + 1) * 8));

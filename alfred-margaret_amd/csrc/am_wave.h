@@ -1,4 +1,5 @@
-// am_wave.h -- wave64 helpers shared by the HIP kernels of libam (gfx950): lane id, DPP prefix sum, uniform values, LDS by absolute address
+// am_wave.h -- device helpers shared by the HIP kernels of libam (gfx950): lane id, DPP prefix sum, uniform values, LDS by absolute address (wave64), and the
+// backward code-point walk of the IgnoreCase folds
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -62,6 +63,20 @@ __device__ __forceinline__ void lds_write_u16(uint32_t byte_addr, uint32_t v) { 
 __device__ __forceinline__ void lds_write_u32x2(uint32_t byte_addr, uint2 v) { u32x2_n t; t.x = v.x; t.y = v.y; *reinterpret_cast<lds_u32x2_t*>((uintptr_t)byte_addr) = t; }
 __device__ __forceinline__ void lds_write_u32x4(uint32_t byte_addr, uint4 v) { u32x4_n t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w; *reinterpret_cast<lds_u32x4_t*>((uintptr_t)byte_addr) = t; }
 
+// ------------------------------------------------------------------ UTF-8
+// Utf8.hs:256-276 skipCodePointsBackwards hay (end_pos - 1) n: the index of the first byte of the code point n code points before the one whose last byte is
+// hay[end_pos - 1].  The start of an IgnoreCase match of cps code points that ends at end_pos is n = cps - 1 (Splitter.hs:117-121, Replacer.hs:268-274).  Reads at
+// most 4 bytes per code point, all of them in hay[0, end_pos): the caller has checked that these lie in its text.  A walk that would leave the haystack answers 0.
+__device__ __forceinline__ uint64_t skip_code_points_backwards(const uint8_t* hay, uint64_t end_pos, uint32_t n)
+{
+    int64_t index = (int64_t)end_pos - 1;
+    for (;;) {
+        if (index >= 0 && (hay[index] & 0xC0) == 0x80) { index--; continue; }
+        if (index < 0) return 0;                                       // (the reference calls `error`: not reachable for a match the automaton reported)
+        if (n == 0) return (uint64_t)index;
+        index--; n--;
+    }
+}
 
 }  // namespace dev
 }  // namespace am
