@@ -1,6 +1,7 @@
 // am_replacer.cpp -- Replacer (Replacer.hs:97-274) behind include/am.h: every pass on the device.  Three loops: all passes of a haystack in one
 // kernel (replacer_run_loop, csrc/am_rploop.hip), pass by pass with the texts kept as piece tables (replacer_run_pt) or spliced (replacer_run,
-// csrc/am_replace.hip).
+// csrc/am_replace.hip).  The two pass-by-pass loops are lists of the same named steps (size_pass, rp_fold, bookkeeping_scans, window_geometry, route_next,
+// merge_records) around what is their own: piece lists or the splice, and how finished haystacks travel home.
 #include "am_host.h"
 
 using namespace am;
@@ -14,6 +15,14 @@ static_assert(sizeof(am_payload) == sizeof(RpPayload) && offsetof(am_payload, re
               "am_payload must mirror the device payload");
 
 namespace {
+
+// A device array of T: a DevBuf whose element type is stated once, where it is declared.  room(count) is ensure(count * sizeof(T)), so the growth rule sees
+// the bytes it always saw; get() is the only place the pointer takes its type.
+template <class T>
+struct DevArr : DevBuf {
+    int room(size_t count) { return ensure(count * sizeof(T)); }
+    T* get() const { return static_cast<T*>(p); }
+};
 
 // growing page-locked host memory.  DevBuf's rule (am_host.h) holds here too: never static or thread storage -- the destructor calls into HIP.
 struct PinBuf {
@@ -36,33 +45,42 @@ struct PinBuf {
 
 // The workspace of one run: device buffers, pinned scratch, copy stream.  A replacer keeps the sessions of finished runs for the next ones (SessionLease).
 struct RpSession {
-    DevBuf text[2], offs[2], orig[2], thr[2];
-    DevBuf totals; uint64_t* tot_host = nullptr; uint64_t tot_seq = 0;       // the per-pass totals, read back through pinned memory (tot_host[15]: sequence number of the last pass written)
+    DevArr<uint8_t> text[2]; DevArr<uint64_t> offs[2]; DevArr<uint32_t> orig[2]; DevArr<int64_t> thr[2];
+    DevArr<uint64_t> totals; uint64_t* tot_host = nullptr; uint64_t tot_seq = 0;       // the per-pass totals, read back through pinned memory (tot_host[15]: sequence number of the last pass written)
     hipStream_t copy_stream = nullptr; hipEvent_t ev_spliced = nullptr;     // finished texts travel home next to the window scans
     PinBuf fin_host;                     // RpFin[] of the haystacks a pass finished
-    DevBuf recbuf[2];                    // sorted records of the current pass / of the next one (incremental re-scan)
-    DevBuf nwin, win_off, wins, wlen, woffs, wtext, wrec, wrec_first, mcount, moff, tile_hay;
+    DevArr<Record> recbuf[2];            // sorted records of the current pass / of the next one (incremental re-scan)
+    DevArr<uint32_t> nwin, wlen, mcount, tile_hay; DevArr<uint64_t> win_off, woffs, wrec_first, moff; DevArr<RpWin> wins; DevArr<uint8_t> wtext; DevArr<Record> wrec;
     am_batch ws2;                        // workspace of the window scans
-    DevBuf rec_first, rec_first2, kept, hs, len_next, len_fin, tiles, act, fin, off_next, off_fin, tile_off, act_idx, fin_idx, scan_tmp, fin_text, fin_meta;      // (rec_first2: the piece-table loop's second ranges buffer -- a pass's merge writes the next pass's ranges)
+    DevArr<uint64_t> rec_first[2];       // record ranges of the haystacks ([1]: the piece-table loop's second ranges buffer -- a pass's merge writes the next pass's ranges)
+    DevArr<RpKept> kept; DevArr<RpHay> hs;
+    DevArr<uint64_t> len_next, len_fin; DevArr<uint32_t> tiles, act, fin;                      // RpRoute: per haystack, written by the fold
+    DevArr<uint64_t> off_next, off_fin, tile_off, act_idx, fin_idx;                           // RpRouted: their exclusive sums
+    DevArr<uint8_t> scan_tmp, fin_text; DevArr<RpFin> fin_meta;
     am_batch ws;                         // workspace holder for the scans; never owns its text
-    DevBuf first_orig, first_thr;
-    DevBuf pt_pieces[2], pt_start[2], pt_cnt[2], pt_need, pt_need_off, pt_fin_start, pt_fin_cnt;      // piece-table path
-    DevBuf lp_rec, lp_pc, lp_kept, lp_wtext, lp_out, lp_ctrl, lp_cap_r, lp_cap_p, lp_rec_base, lp_pc_base, lp_fin, lp_fin_start, lp_fin_cnt, lp_redo;      // one-kernel loops (am_rplds.hip, am_rploop.hip)
-    DevBuf lp_stage[8];                  // device staging of the haystack groups' finished texts on their way to the host
+    DevArr<uint32_t> first_orig; DevArr<int64_t> first_thr;
+    DevArr<RpPiece> pt_pieces[2]; DevArr<uint64_t> pt_start[2], pt_need_off, pt_fin_start; DevArr<uint32_t> pt_cnt[2], pt_need, pt_fin_cnt;      // piece-table path
+    // one-kernel loops (am_rplds.hip, am_rploop.hip)
+    DevArr<Record> lp_rec; DevArr<RpPiece> lp_pc; DevArr<RpKept> lp_kept; DevArr<uint8_t> lp_wtext; DevArr<RpLoopOut> lp_out; DevArr<RpFin> lp_fin;
+    DevArr<uint32_t> lp_ctrl, lp_cap_r, lp_cap_p, lp_fin_cnt, lp_redo; DevArr<uint64_t> lp_rec_base, lp_pc_base, lp_fin_start;
+    DevArr<uint8_t> lp_stage[8];         // device staging of the haystack groups' finished texts on their way to the host
     PinBuf lp_host;                      // the loop's per-haystack results, then the materialise tables
-    DevBuf pf_best, pf_delta, pf_payload, pf_selflag, pf_sidx, pf_cand, pf_sel, pf_keep, pf_kflag, pf_kdelta, pf_kidx, pf_kdpre, pf_tmp;   // record-parallel fold
+    // record-parallel fold
+    DevArr<int64_t> pf_best, pf_delta; DevArr<uint32_t> pf_payload, pf_selflag, pf_keep, pf_kflag; DevArr<uint64_t> pf_sidx, pf_kdelta, pf_kidx, pf_kdpre; DevArr<RpSel> pf_cand, pf_sel;
+    DevArr<uint8_t> pf_tmp;
     // what counts against the limits of the session cache: the buffers that grow with the texts and the records
     size_t device_bytes() const
     {
         size_t n = 0;
-        for (const DevBuf* d : {&text[0], &text[1], &recbuf[0], &recbuf[1], &kept, &wins, &wtext, &wrec, &fin_text, &ws.pool, &ws2.pool, &ws.hidx, &ws2.hidx, &pf_cand, &pf_sel, &pf_sidx,
-                                &lp_rec, &lp_pc, &lp_kept, &lp_wtext, &lp_stage[0], &lp_stage[1], &lp_stage[2], &lp_stage[3], &lp_stage[4], &lp_stage[5], &lp_stage[6], &lp_stage[7]}) n += d->cap;
+        for (const DevBuf* d : std::initializer_list<const DevBuf*>{&text[0], &text[1], &recbuf[0], &recbuf[1], &kept, &wins, &wtext, &wrec, &fin_text, &ws.pool, &ws2.pool, &ws.hidx, &ws2.hidx,
+                                &pf_cand, &pf_sel, &pf_sidx, &lp_rec, &lp_pc, &lp_kept, &lp_wtext, &lp_stage[0], &lp_stage[1], &lp_stage[2], &lp_stage[3], &lp_stage[4],
+                                &lp_stage[5], &lp_stage[6], &lp_stage[7]}) n += d->cap;
         return n;
     }
     // the block the totals of a pass come home in
     int pinned_totals()
     {
-        AM_TRY(totals.ensure(128));
+        AM_TRY(totals.room(16));
         if (tot_host) return AM_OK;
         if (hipHostMalloc((void**)&tot_host, 128, hipHostMallocPortable | hipHostMallocCoherent) != hipSuccess) { tot_host = nullptr; return fail(AM_ERR_OOM, "hipHostMalloc failed"); }
         std::memset(tot_host, 0, 128);                    // (fine-grained: a device store is visible to the host while the kernel is still running)
@@ -79,12 +97,16 @@ struct RpSession {
     {
         std::vector<uint32_t> o(n_hay); std::vector<int64_t> t(n_hay, 1);
         for (uint32_t i = 0; i < n_hay; i++) o[i] = i;
-        AM_TRY(first_orig.ensure(n_hay * sizeof(uint32_t))); AM_TRY(first_thr.ensure(n_hay * sizeof(int64_t)));
-        HIP_TRY(hipMemcpyAsync(first_orig.p, o.data(), n_hay * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(first_thr.p, t.data(), n_hay * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        AM_TRY(first_orig.room(n_hay)); AM_TRY(first_thr.room(n_hay));
+        HIP_TRY(hipMemcpyAsync(first_orig.get(), o.data(), n_hay * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(first_thr.get(), t.data(), n_hay * sizeof(int64_t), hipMemcpyHostToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));
         return AM_OK;
     }
+    // what the fold writes per haystack, and the sums of it (valid until the arrays are sized again: size_pass)
+    RpRoute route() const { return RpRoute{len_next.get(), len_fin.get(), tiles.get(), act.get(), fin.get()}; }
+    RpRouted routed() const { return RpRouted{off_next.get(), off_fin.get(), tile_off.get(), act_idx.get(), fin_idx.get()}; }
+    size_t scan_room() const { return scan_tmp.cap - 16; }      // bytes of scan_tmp a scan may use
     ~RpSession()      // (the device buffers free themselves afterwards: nothing is in flight on the copy stream by then)
     {
         if (tot_host) (void)hipHostFree(tot_host);
@@ -98,7 +120,7 @@ struct RpSession {
 struct am_replacer {
     const am_automaton* a = nullptr;
     int case_mode = 0;
-    DevBuf vals_off, vals, payloads, repl, one;
+    DevArr<uint64_t> vals_off; DevArr<uint32_t> vals; DevArr<RpPayload> payloads; DevArr<uint8_t> repl; DevArr<RpStateOne> one;
     RpTables t{};
     uint32_t max_repl_len = 0;                        // longest replacement (bounds the re-scan window of the one-kernel loop)
     uint64_t n_repl_bytes = 0;                        // size of the replacement blob
@@ -252,7 +274,7 @@ extern "C" int am_replacer_create(const am_automaton* a, int case_mode, const ui
         rc = up(r->one, one.data(), one.size() * sizeof(RpStateOne));
     }
     if (rc != AM_OK) { am_replacer_destroy(r); return rc; }
-    r->t = RpTables{(const uint64_t*)r->vals_off.p, (const uint32_t*)r->vals.p, (const RpPayload*)r->payloads.p, (const uint8_t*)r->repl.p, min_priority, (const RpStateOne*)r->one.p};
+    r->t = RpTables{r->vals_off.get(), r->vals.get(), r->payloads.get(), r->repl.get(), min_priority, r->one.get()};
     *out = r;
     return AM_OK;
 }
@@ -296,10 +318,37 @@ int bind_workspace(am_batch& w, int dev, const void* text, const uint64_t* offse
     return finish_batch(&w);
 }
 
+// ------------------------------------------------------------------ the pass-by-pass loops: what moves from pass to pass, and the steps both loops share
+
+// What moves from pass to pass in both loops: the active haystacks' offsets, original indices and thresholds (the caller's batch and first_pass_arrays in the first
+// pass, afterwards what the previous pass's route wrote), how many there are, and which halves of the session's [2] arrays are this pass's.
+struct RpPass {
+    const uint64_t* offs; const uint32_t* orig; const int64_t* thr;
+    uint32_t n_act;
+    int nxt = 0;      // offs / orig / thr / text [nxt]: what this pass's route and splice write for the next pass
+    int cur = 0;      // recbuf / pt_* / (piece tables) rec_first [cur]: what this pass reads; [cur ^ 1] is written for the next pass
+    uint64_t n1() const { return (uint64_t)n_act + 1; }
+    void advance(const RpSession& s, uint64_t n_next)      // onto what this pass's route wrote
+    {
+        offs = s.offs[nxt].get(); orig = s.orig[nxt].get(); thr = s.thr[nxt].get();
+        n_act = (uint32_t)n_next; nxt ^= 1; cur ^= 1;
+    }
+};
+
+// AM_RP_TRACE: where the host's wall clock goes in a pass-by-pass loop, in four phases that each loop names (development aid)
+struct PhaseClock {
+    double t[4] = {0, 0, 0, 0}, t0 = 0;
+    static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    void start() { t0 = now(); }
+    void lap(int phase) { const double t1 = now(); t[phase] += t1 - t0; t0 = t1; }      // the time since start() or the last lap goes to `phase`
+    void print(const char* fmt) const { std::fprintf(stderr, fmt, t[0] * 1e3, t[1] * 1e3, t[2] * 1e3, t[3] * 1e3); }
+};
+
 // The prefix sums of a pass over n1 elements: up to 2^18 in one launch (k_scan_jobs) instead of a launch or two per sum, else one scan per job in the list's order.
+constexpr uint64_t kOneLaunchSums = 1u << 18;
 int scan_pass(const ScanJobs& jobs, uint64_t n1, void* tmp, size_t tmp_bytes, hipStream_t st)
 {
-    if (n1 <= (1u << 18)) { HIP_TRY(launch_scan_jobs(jobs, st)); return AM_OK; }
+    if (n1 <= kOneLaunchSums) { HIP_TRY(launch_scan_jobs(jobs, st)); return AM_OK; }
     for (uint32_t i = 0; i < jobs.n_jobs; i++) {
         const ScanJob& j = jobs.j[i];
         if (j.in64) HIP_TRY(launch_scan64(tmp, tmp_bytes, j.in64, j.out, j.n, st));
@@ -308,51 +357,156 @@ int scan_pass(const ScanJobs& jobs, uint64_t n1, void* tmp, size_t tmp_bytes, hi
     return AM_OK;
 }
 
-// prependMatch + makeMatch + removeOverlap of one pass (Replacer.hs:252-274,191-198): one wavefront per haystack, or -- few
-// haystacks with very many matches each -- parallel over the records.  Writes kept[], hs[] and the route arrays.
-static int rp_fold(RpSession& s, const am_replacer* r, bool ic, const uint8_t* text, const uint64_t* offs, const Record* recs, uint64_t n_rec, const int64_t* thr,
-                   uint64_t max_length, const RpRoute& route, uint32_t n_act, hipStream_t st, const uint64_t* rec_first)
+// Which fold a pass takes: one wavefront per haystack, or -- few haystacks with very many matches each -- parallel over the records (AM_RP_PARALLEL_FOLD forces
+// either: tests).
+bool parallel_fold_wanted(uint32_t n_act, uint64_t n_rec)
 {
-    const uint64_t n1 = (uint64_t)n_act + 1;
-    // one wavefront per haystack, or -- few haystacks with very many matches each -- parallel over the records
-        bool par_fold = n_rec > 2048ull * n_act;
-        if (cfg::get(cfg::kRpParallelFold) != cfg::kUnset) par_fold = cfg::get(cfg::kRpParallelFold) != 0;        // tests force either path
-        if (!par_fold) {
-            Prof pr("rp_pass", st);
-            HIP_TRY(launch_rp_pass(ic, r->t, text, offs, recs, rec_first, thr,
-                                   max_length, (RpKept*)s.kept.p, (RpHay*)s.hs.p, route, n_act, 0u, st));
-        } else {
-            Prof pr("rp_pass", st);
-            const uint64_t nb = n_rec + 2;
-            AM_TRY(s.pf_best.ensure(n1 * 8)); AM_TRY(s.pf_delta.ensure(n1 * 8)); AM_TRY(s.pf_payload.ensure(n1 * 4));
-            AM_TRY(s.pf_selflag.ensure(nb * 4)); AM_TRY(s.pf_sidx.ensure(nb * 8)); AM_TRY(s.pf_cand.ensure(nb * sizeof(RpSel))); AM_TRY(s.pf_sel.ensure(nb * sizeof(RpSel)));
-            AM_TRY(s.pf_keep.ensure(nb * 4)); AM_TRY(s.pf_kflag.ensure(nb * 4)); AM_TRY(s.pf_kdelta.ensure(nb * 8)); AM_TRY(s.pf_kidx.ensure(nb * 8)); AM_TRY(s.pf_kdpre.ensure(nb * 8));
-            size_t t32b = 0, t64b = 0;
-            if (scan_temp_bytes(nb, &t32b) != hipSuccess || scan64_temp_bytes(nb, &t64b) != hipSuccess) return fail(AM_ERR_HIP, "scan sizing failed");
-            AM_TRY(s.pf_tmp.ensure(std::max(t32b, t64b) + 16));
-            const size_t ptmp = s.pf_tmp.cap - 16;
-            HIP_TRY(hipMemsetAsync(s.pf_delta.p, 0, n1 * 8, st)); HIP_TRY(hipMemsetAsync(s.pf_payload.p, 0, n1 * 4, st));
-            HIP_TRY(hipMemsetAsync(s.pf_kflag.p, 0, nb * 4, st)); HIP_TRY(hipMemsetAsync(s.pf_kdelta.p, 0, nb * 8, st)); HIP_TRY(hipMemsetAsync(s.pf_keep.p, 0, nb * 4, st));
-            HIP_TRY(launch_rpp_best(r->t, recs, n_rec, thr, (int64_t*)s.pf_best.p, n_act, st));
-            HIP_TRY(launch_rpp_select(ic, r->t, text, offs, recs, n_rec, (const int64_t*)s.pf_best.p,
-                                      (uint32_t*)s.pf_selflag.p, (RpSel*)s.pf_cand.p, (int64_t*)s.pf_delta.p, (uint32_t*)s.pf_payload.p, st));
-            HIP_TRY(launch_scan(s.pf_tmp.p, ptmp, (const uint32_t*)s.pf_selflag.p, (uint64_t*)s.pf_sidx.p, n_rec + 1, st));
-            const uint64_t* n_sel_dev = (const uint64_t*)s.pf_sidx.p + n_rec;
-            HIP_TRY(launch_rpp_compact((const uint32_t*)s.pf_selflag.p, (const uint64_t*)s.pf_sidx.p, (const RpSel*)s.pf_cand.p, n_rec, (RpSel*)s.pf_sel.p, st));
-            HIP_TRY(launch_rpp_overlaps((const RpSel*)s.pf_sel.p, n_sel_dev, n_rec, (uint32_t*)s.pf_keep.p, st));
-            HIP_TRY(launch_rpp_kflags((const RpSel*)s.pf_sel.p, n_sel_dev, n_rec, (const uint32_t*)s.pf_keep.p, r->t, (const uint32_t*)s.pf_payload.p,
-                                      (uint32_t*)s.pf_kflag.p, (uint64_t*)s.pf_kdelta.p, st));
-            HIP_TRY(launch_scan(s.pf_tmp.p, ptmp, (const uint32_t*)s.pf_kflag.p, (uint64_t*)s.pf_kidx.p, n_rec + 2, st));
-            HIP_TRY(launch_scan64(s.pf_tmp.p, ptmp, (const uint64_t*)s.pf_kdelta.p, (uint64_t*)s.pf_kdpre.p, n_rec + 2, st));
-            HIP_TRY(launch_rpp_finish(r->t, (const RpSel*)s.pf_sel.p, n_sel_dev, n_rec, (const uint32_t*)s.pf_kflag.p, (const uint64_t*)s.pf_kidx.p,
-                                      (const uint64_t*)s.pf_kdpre.p, (const uint64_t*)s.pf_sidx.p, offs, rec_first, (const int64_t*)s.pf_best.p,
-                                      (const int64_t*)s.pf_delta.p, (const uint32_t*)s.pf_payload.p, max_length, (RpKept*)s.kept.p, (RpHay*)s.hs.p, route, n_act, st));
-        }
+    const long forced = cfg::get(cfg::kRpParallelFold);
+    return forced != cfg::kUnset ? forced != 0 : n_rec > 2048ull * n_act;
+}
+
+// The record-parallel fold needs the exact count on the host: a count that is still on the device (*n_rec_dev; *n_rec bounds it) is fetched when that regime is
+// possible -- the bound asks for it, or the switch is set.  Otherwise the bound stays, and parallel_fold_wanted says no to it as it would to the count.
+int exact_count_for_fold(RpSession& s, uint32_t n_act, uint64_t* n_rec, const uint64_t** n_rec_dev, hipStream_t st)
+{
+    if (!*n_rec_dev || (cfg::get(cfg::kRpParallelFold) == cfg::kUnset && !parallel_fold_wanted(n_act, *n_rec))) return AM_OK;
+    HIP_TRY(hipMemcpyAsync(&s.tot_host[9], *n_rec_dev, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *n_rec = s.tot_host[9]; *n_rec_dev = nullptr;
+    return AM_OK;
+}
+
+// Room for a pass over p.n_act haystacks and n_rec records: the record ranges, what the fold writes (kept, hs, the route arrays), the sums of the route arrays,
+// with `windows` the geometry of the re-scan windows (at most one per record), and the scan temporary for the longest sum among them; a valid records pointer
+// even when nothing matched.  (The sum of the window lengths has n_rec + 1 elements; the temporary is sized for n_rec + 2 in both loops.)
+int size_pass(RpSession& s, const RpPass& p, DevArr<uint64_t>& ranges, uint64_t n_rec, bool windows)
+{
+    const uint64_t n1 = p.n1();
+    AM_TRY(ranges.room(n1)); AM_TRY(s.kept.room(n_rec + 1)); AM_TRY(s.hs.room(n1));
+    AM_TRY(s.len_next.room(n1)); AM_TRY(s.len_fin.room(n1)); AM_TRY(s.tiles.room(n1)); AM_TRY(s.act.room(n1)); AM_TRY(s.fin.room(n1));
+    AM_TRY(s.off_next.room(n1)); AM_TRY(s.off_fin.room(n1)); AM_TRY(s.tile_off.room(n1)); AM_TRY(s.act_idx.room(n1)); AM_TRY(s.fin_idx.room(n1));
+    size_t t32 = 0, t64 = 0, tw = 0;
+    if (scan_temp_bytes(n1, &t32) != hipSuccess || scan64_temp_bytes(n1, &t64) != hipSuccess) return fail(AM_ERR_HIP, "scan sizing failed");
+    if (windows) {
+        AM_TRY(s.nwin.room(n1)); AM_TRY(s.win_off.room(n1));
+        AM_TRY(s.wins.room(n_rec + 1)); AM_TRY(s.wlen.room(n_rec + 2)); AM_TRY(s.woffs.room(n_rec + 2));
+        if (scan_temp_bytes(n_rec + 2, &tw) != hipSuccess) return fail(AM_ERR_HIP, "scan sizing failed");
+    }
+    AM_TRY(s.scan_tmp.room(std::max(std::max(t32, t64), tw) + 16));
+    return s.recbuf[p.cur].room(1);
+}
+
+// prependMatch + makeMatch + removeOverlap of one pass (Replacer.hs:252-274,191-198): one wavefront per haystack, or (`par`, parallel_fold_wanted) parallel over
+// the records.  Writes kept[], hs[] and the route arrays.
+int rp_fold(RpSession& s, const am_replacer* r, bool ic, bool par, const uint8_t* text, const RpPass& p, const Record* recs, uint64_t n_rec, uint64_t max_length,
+            const uint64_t* rec_first, hipStream_t st)
+{
+    Prof pr("rp_pass", st);
+    const RpRoute route = s.route();
+    if (!par) {
+        HIP_TRY(launch_rp_pass(ic, r->t, text, p.offs, recs, rec_first, p.thr, max_length, s.kept.get(), s.hs.get(), route, p.n_act, 0u, st));
+        return AM_OK;
+    }
+    const uint64_t n1 = p.n1(), nb = n_rec + 2;
+    AM_TRY(s.pf_best.room(n1)); AM_TRY(s.pf_delta.room(n1)); AM_TRY(s.pf_payload.room(n1));
+    AM_TRY(s.pf_selflag.room(nb)); AM_TRY(s.pf_sidx.room(nb)); AM_TRY(s.pf_cand.room(nb)); AM_TRY(s.pf_sel.room(nb));
+    AM_TRY(s.pf_keep.room(nb)); AM_TRY(s.pf_kflag.room(nb)); AM_TRY(s.pf_kdelta.room(nb)); AM_TRY(s.pf_kidx.room(nb)); AM_TRY(s.pf_kdpre.room(nb));
+    size_t t32b = 0, t64b = 0;
+    if (scan_temp_bytes(nb, &t32b) != hipSuccess || scan64_temp_bytes(nb, &t64b) != hipSuccess) return fail(AM_ERR_HIP, "scan sizing failed");
+    AM_TRY(s.pf_tmp.room(std::max(t32b, t64b) + 16));
+    const size_t ptmp = s.pf_tmp.cap - 16;
+    HIP_TRY(hipMemsetAsync(s.pf_delta.get(), 0, n1 * 8, st)); HIP_TRY(hipMemsetAsync(s.pf_payload.get(), 0, n1 * 4, st));
+    HIP_TRY(hipMemsetAsync(s.pf_kflag.get(), 0, nb * 4, st)); HIP_TRY(hipMemsetAsync(s.pf_kdelta.get(), 0, nb * 8, st)); HIP_TRY(hipMemsetAsync(s.pf_keep.get(), 0, nb * 4, st));
+    HIP_TRY(launch_rpp_best(r->t, recs, n_rec, p.thr, s.pf_best.get(), p.n_act, st));
+    HIP_TRY(launch_rpp_select(ic, r->t, text, p.offs, recs, n_rec, s.pf_best.get(), s.pf_selflag.get(), s.pf_cand.get(), s.pf_delta.get(), s.pf_payload.get(), st));
+    HIP_TRY(launch_scan(s.pf_tmp.get(), ptmp, s.pf_selflag.get(), s.pf_sidx.get(), n_rec + 1, st));
+    const uint64_t* n_sel_dev = s.pf_sidx.get() + n_rec;
+    HIP_TRY(launch_rpp_compact(s.pf_selflag.get(), s.pf_sidx.get(), s.pf_cand.get(), n_rec, s.pf_sel.get(), st));
+    HIP_TRY(launch_rpp_overlaps(s.pf_sel.get(), n_sel_dev, n_rec, s.pf_keep.get(), st));
+    HIP_TRY(launch_rpp_kflags(s.pf_sel.get(), n_sel_dev, n_rec, s.pf_keep.get(), r->t, s.pf_payload.get(), s.pf_kflag.get(), s.pf_kdelta.get(), st));
+    HIP_TRY(launch_scan(s.pf_tmp.get(), ptmp, s.pf_kflag.get(), s.pf_kidx.get(), n_rec + 2, st));
+    HIP_TRY(launch_scan64(s.pf_tmp.get(), ptmp, s.pf_kdelta.get(), s.pf_kdpre.get(), n_rec + 2, st));
+    HIP_TRY(launch_rpp_finish(r->t, s.pf_sel.get(), n_sel_dev, n_rec, s.pf_kflag.get(), s.pf_kidx.get(), s.pf_kdpre.get(), s.pf_sidx.get(), p.offs, rec_first, s.pf_best.get(),
+                              s.pf_delta.get(), s.pf_payload.get(), max_length, s.kept.get(), s.hs.get(), route, p.n_act, st));
+    return AM_OK;
+}
+
+// The bookkeeping sums of a pass over the route arrays: bytes of next and finished text, the loop's own third sum (the splice's tiles, or the piece entries the next
+// lists need), the indices among the active and the finished haystacks and, with `windows`, the windows per haystack.
+int bookkeeping_scans(RpSession& s, const RpPass& p, const uint32_t* third_in, uint64_t* third_out, bool windows, hipStream_t st)
+{
+    const uint64_t n1 = p.n1();
+    ScanJobs jobs{};
+    jobs.j[0] = ScanJob{nullptr, s.len_next.get(), s.off_next.get(), n1, nullptr};
+    jobs.j[1] = ScanJob{nullptr, s.len_fin.get(), s.off_fin.get(), n1, nullptr};
+    jobs.j[2] = ScanJob{third_in, nullptr, third_out, n1, nullptr};
+    jobs.j[3] = ScanJob{s.act.get(), nullptr, s.act_idx.get(), n1, nullptr};
+    jobs.j[4] = ScanJob{s.fin.get(), nullptr, s.fin_idx.get(), n1, nullptr};
+    jobs.n_jobs = 5;
+    if (windows) { jobs.j[5] = ScanJob{s.nwin.get(), nullptr, s.win_off.get(), n1, nullptr}; jobs.n_jobs = 6; }
+    return scan_pass(jobs, n1, s.scan_tmp.get(), s.scan_room(), st);
+}
+
+// The re-scan windows of a pass (their geometry follows from the kept matches alone; the text is copied once the next texts exist) and the sum of their lengths.
+// *woffs_last tells launch_rp_totals where the total is: ~0 = the count of windows is read on the device (the sum had exactly n_win + 1 elements), else n_rec.
+int window_geometry(RpSession& s, const am_replacer* r, const RpPass& p, const uint64_t* rec_first, uint64_t n_rec, uint32_t ov, bool pieces, hipStream_t st, uint64_t* woffs_last)
+{
+    Prof pr("rp_windows", st);
+    const bool small = p.n1() <= kOneLaunchSums;
+    if (!small) HIP_TRY(hipMemsetAsync(s.wlen.get(), 0, (n_rec + 2) * 4, st));     // at most one window per record; unused entries scan as zeros
+    HIP_TRY(launch_rp_win_meta(r->t, s.routed(), s.hs.get(), rec_first, s.kept.get(), s.win_off.get(), ov, s.wins.get(), s.wlen.get(), p.n_act, st, pieces));
+    if (small) {
+        ScanJobs jobs{};
+        jobs.j[0] = ScanJob{s.wlen.get(), nullptr, s.woffs.get(), 1, s.win_off.get() + p.n_act};
+        jobs.n_jobs = 1;
+        HIP_TRY(launch_scan_jobs(jobs, st));
+        *woffs_last = ~0ull;
+    } else {
+        HIP_TRY(launch_scan(s.scan_tmp.get(), s.scan_room(), s.wlen.get(), s.woffs.get(), n_rec + 1, st));
+        *woffs_last = n_rec;
+    }
+    return AM_OK;
+}
+
+// The surviving haystacks' offsets, original indices and thresholds into the [nxt] arrays, the finished ones' metadata into fin_meta (their text goes to fin_text).
+int route_next(RpSession& s, const RpPass& p, uint64_t n_next, uint64_t n_fin, uint64_t total_fin, hipStream_t st)
+{
+    AM_TRY(s.offs[p.nxt].room(n_next + 1)); AM_TRY(s.orig[p.nxt].room(n_next + 1)); AM_TRY(s.thr[p.nxt].room(n_next + 1));
+    AM_TRY(s.fin_text.room(total_fin + 16)); AM_TRY(s.fin_meta.room(n_fin + 1));
+    Prof pr("rp_route", st);
+    HIP_TRY(launch_rp_route(s.hs.get(), s.routed(), p.orig, p.n_act, s.offs[p.nxt].get(), s.orig[p.nxt].get(), s.thr[p.nxt].get(), s.fin_meta.get(), st));
+    return AM_OK;
+}
+
+// The next pass's records without a full scan: per surviving haystack the old records, shifted with the text, and the window scan's own (s.wrec: n_wrec of them, or,
+// n_wrec_dev given, a count still on the device that n_wrec bounds) -- count, prefix sum, write into recbuf[cur ^ 1].  The sum lands in `ranges_next`: the records'
+// ranges per haystack of the next pass, their exact number in ranges_next[n_next].  (k_rp_ranges writes n_win + 1 ranges of the window records and k_rp_merge reads
+// no further; both loops size wrec_first for n_win + 2.)
+int merge_records(RpSession& s, const RpPass& p, const uint64_t* rec_first, uint64_t n_rec, uint64_t n_next, uint64_t n_win, uint64_t n_wrec, const uint64_t* n_wrec_dev,
+                  uint32_t ov, bool clear_last_count, DevArr<uint64_t>& ranges_next, hipStream_t st)
+{
+    DevArr<Record>& next_records = s.recbuf[p.cur ^ 1];
+    AM_TRY(s.wrec_first.room(n_win + 2)); AM_TRY(s.mcount.room(n_next + 1)); AM_TRY(ranges_next.room(n_next + 1));
+    AM_TRY(next_records.room(n_rec + n_wrec + 1));          // an upper bound; the exact count comes with the sum
+    const Record* records = s.recbuf[p.cur].get();
+    const RpRouted rt = s.routed();
+    Prof pr("rp_merge", st);
+    if (n_wrec_dev) HIP_TRY(launch_rp_ranges_dev(s.wrec.get(), n_wrec_dev, s.wrec_first.get(), kNoRoute, (uint32_t)n_win, st));
+    else HIP_TRY(launch_rp_ranges(s.wrec.get(), n_wrec, s.wrec_first.get(), kNoRoute, (uint32_t)n_win, st));
+    if (clear_last_count) HIP_TRY(hipMemsetAsync(s.mcount.get() + n_next, 0, 4, st));
+    HIP_TRY(launch_rp_merge(false, records, rec_first, s.kept.get(), s.hs.get(), p.offs, rt, s.win_off.get(), s.wins.get(), s.wrec.get(), s.wrec_first.get(), ov, p.n_act,
+                            s.mcount.get(), nullptr, nullptr, st));
+    { ScanJobs jobs{};
+      jobs.j[0] = ScanJob{s.mcount.get(), nullptr, ranges_next.get(), n_next + 1, nullptr};
+      jobs.n_jobs = 1;
+      AM_TRY(scan_pass(jobs, n_next + 1, s.scan_tmp.get(), s.scan_room(), st)); }
+    HIP_TRY(launch_rp_merge(true, records, rec_first, s.kept.get(), s.hs.get(), p.offs, rt, s.win_off.get(), s.wins.get(), s.wrec.get(), s.wrec_first.get(), ov, p.n_act,
+                            s.mcount.get(), ranges_next.get(), next_records.get(), st));
     return AM_OK;
 }
 
 // The haystacks a pass finished, once their bytes (at `home`) and metadata have arrived on the copy stream: into the result.
-static int scatter_finished(RpSession& s, uint64_t n_fin, uint64_t total_fin, uint8_t* home, uint32_t n_hay, am_replaced* res)
+int scatter_finished(RpSession& s, uint64_t n_fin, uint64_t total_fin, uint8_t* home, uint32_t n_hay, am_replaced* res)
 {
     HIP_TRY(hipStreamSynchronize(s.copy_stream));
     const RpFin* fin = (const RpFin*)s.fin_host.p;
@@ -378,30 +532,24 @@ int replacer_run_pt(const am_replacer* r, const am_batch* in, uint64_t max_lengt
     AM_TRY(s.pinned_totals());
     AM_TRY(s.copy_lane());
     const uint8_t* base_text = (const uint8_t*)in->d_text;               // never modified: every text piece points into it
-    const uint64_t* cur_offs = in->d_offsets;                            // logical offsets of the active haystacks (lengths only after pass 0)
-    uint32_t n_act = n_hay;
-    int nxt = 0;
     AM_TRY(s.first_pass_arrays(n_hay, st));
-    const uint32_t* cur_orig = (const uint32_t*)s.first_orig.p;
-    const int64_t* cur_thr = (const int64_t*)s.first_thr.p;
+    RpPass p{in->d_offsets, s.first_orig.get(), s.first_thr.get(), n_hay};      // (offs: logical offsets of the active haystacks, lengths only after pass 0)
     const uint32_t ov = 4u * (flavor->h.max_needle_cps ? flavor->h.max_needle_cps : 1u) + 4u;
     // piece lists of pass 0: one piece per haystack
-    int cur_pt = 0;
-    AM_TRY(s.pt_pieces[0].ensure(((size_t)n_hay * 2 + 2) * sizeof(RpPiece)));
-    AM_TRY(s.pt_start[0].ensure(((size_t)n_hay + 1) * 8)); AM_TRY(s.pt_cnt[0].ensure(((size_t)n_hay + 1) * 4));
-    HIP_TRY(launch_pt_init(in->d_offsets, n_hay, (RpPiece*)s.pt_pieces[0].p, (uint64_t*)s.pt_start[0].p, (uint32_t*)s.pt_cnt[0].p, st));
+    AM_TRY(s.pt_pieces[0].room((size_t)n_hay * 2 + 2));
+    AM_TRY(s.pt_start[0].room((size_t)n_hay + 1)); AM_TRY(s.pt_cnt[0].room((size_t)n_hay + 1));
+    HIP_TRY(launch_pt_init(in->d_offsets, n_hay, s.pt_pieces[0].get(), s.pt_start[0].get(), s.pt_cnt[0].get(), st));
     // pass 0 scans the caller's batch; afterwards the records come from the window scans + the shifted old records
     uint64_t n_rec = 0;                                   // records of the current pass: exact when n_rec_dev == nullptr, else an upper bound ...
     const uint64_t* n_rec_dev = nullptr;                  // ... and the exact count is still on the device
-    int cur_rec = 0;
     {
         res->scanned += in->total;
         AM_TRY(bind_workspace(s.ws, in->dev, in->d_text, in->d_offsets, in->total, n_hay));
         AM_TRY(run_records(r->a, r->case_mode, &s.ws, records_into(s.recbuf[0]), &n_rec));
     }
     const bool trace = cfg::on(cfg::kRpTrace);
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t_a = 0, t_b = 0, t_c = 0, t_sync = 0;
+    PhaseClock clk;
+    enum { kFold, kWaiting, kPieces, kWindows };          // (kWaiting is part of kFold)
     // finished haystacks of the previous pass: their bytes are on their way home on the copy stream; the host looks at the list after
     // the next pass's (only) synchronisation
     uint64_t prev_n_fin = 0, prev_total_fin = 0; uint8_t* prev_home = nullptr;
@@ -416,73 +564,38 @@ int replacer_run_pt(const am_replacer* r, const am_batch* in, uint64_t max_lengt
         return scatter_finished(s, prev_n_fin, prev_total_fin, prev_home, n_hay, res);
     };
 
-    int cur_rf = 0; bool have_ranges = false;           // (see the ranges buffers below)
-    while (n_act > 0) {
-        double t0 = now();
+    bool have_ranges = false;           // the previous pass's merge left this pass's record ranges behind
+    while (p.n_act > 0) {
+        clk.start();
         res->passes++;
-        DevBuf& records = s.recbuf[cur_rec];
-        const uint64_t n1 = (uint64_t)n_act + 1;
-        // the record-parallel fold needs the exact count on the host: fetch it when that regime is possible
-        if (n_rec_dev && (n_rec > 2048ull * n_act || cfg::get(cfg::kRpParallelFold) != cfg::kUnset)) {
-            HIP_TRY(hipMemcpyAsync(&s.tot_host[9], n_rec_dev, 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            n_rec = s.tot_host[9]; n_rec_dev = nullptr;
-        }
+        AM_TRY(exact_count_for_fold(s, p.n_act, &n_rec, &n_rec_dev, st));
+        const bool par_fold = parallel_fold_wanted(p.n_act, n_rec);
         // record ranges of the haystacks: two buffers that take turns -- the merge at the end of a pass leaves the offsets of the records it
         // writes (per haystack of the next pass) in the other one, which ARE the next pass's ranges: no search then
-        DevBuf& rfb = cur_rf ? s.rec_first2 : s.rec_first; DevBuf& rfb_next = cur_rf ? s.rec_first : s.rec_first2;
-        AM_TRY(rfb.ensure(n1 * 8)); AM_TRY(s.kept.ensure((n_rec + 1) * sizeof(RpKept))); AM_TRY(s.hs.ensure(n1 * sizeof(RpHay)));
-        AM_TRY(s.len_next.ensure(n1 * 8)); AM_TRY(s.len_fin.ensure(n1 * 8)); AM_TRY(s.tiles.ensure(n1 * 4)); AM_TRY(s.act.ensure(n1 * 4)); AM_TRY(s.fin.ensure(n1 * 4));
-        AM_TRY(s.off_next.ensure(n1 * 8)); AM_TRY(s.off_fin.ensure(n1 * 8)); AM_TRY(s.tile_off.ensure(n1 * 8)); AM_TRY(s.act_idx.ensure(n1 * 8)); AM_TRY(s.fin_idx.ensure(n1 * 8));
-        AM_TRY(s.nwin.ensure(n1 * 4)); AM_TRY(s.win_off.ensure(n1 * 8)); AM_TRY(s.pt_need.ensure(n1 * 4)); AM_TRY(s.pt_need_off.ensure(n1 * 8));
-        AM_TRY(s.wins.ensure((n_rec + 1) * sizeof(RpWin))); AM_TRY(s.wlen.ensure((n_rec + 2) * 4)); AM_TRY(s.woffs.ensure((n_rec + 2) * 8));
-        size_t t32 = 0, t64 = 0, tw = 0;
-        if (scan_temp_bytes(n1, &t32) != hipSuccess || scan64_temp_bytes(n1, &t64) != hipSuccess || scan_temp_bytes(n_rec + 2, &tw) != hipSuccess) return fail(AM_ERR_HIP, "scan sizing failed");
-        AM_TRY(s.scan_tmp.ensure(std::max(std::max(t32, t64), tw) + 16));
-        const size_t tmp2 = s.scan_tmp.cap - 16;
-        AM_TRY(records.ensure(sizeof(Record)));
-        RpRoute route{(uint64_t*)s.len_next.p, (uint64_t*)s.len_fin.p, (uint32_t*)s.tiles.p, (uint32_t*)s.act.p, (uint32_t*)s.fin.p};
-        RpRouted rt{(const uint64_t*)s.off_next.p, (const uint64_t*)s.off_fin.p, (const uint64_t*)s.tile_off.p, (const uint64_t*)s.act_idx.p, (const uint64_t*)s.fin_idx.p};
+        DevArr<uint64_t>& ranges = s.rec_first[p.cur]; DevArr<uint64_t>& ranges_next = s.rec_first[p.cur ^ 1];
+        AM_TRY(size_pass(s, p, ranges, n_rec, true));
+        AM_TRY(s.pt_need.room(p.n1())); AM_TRY(s.pt_need_off.room(p.n1()));
+        const Record* records = s.recbuf[p.cur].get();
+        const RpPiece* pieces = s.pt_pieces[p.cur].get(); const uint64_t* pc_start = s.pt_start[p.cur].get(); const uint32_t* pc_cnt = s.pt_cnt[p.cur].get();
+        const RpRouted rt = s.routed();
         // the per-haystack fold also finds its record range and writes the piece / window counts (one dispatch instead of three in the pass's
         // chain); the record-parallel fold keeps the separate launches
-        bool par_fold = (n_rec_dev ? 0 : n_rec) > 2048ull * n_act;
-        if (cfg::get(cfg::kRpParallelFold) != cfg::kUnset) par_fold = cfg::get(cfg::kRpParallelFold) != 0;
-        const bool no_fuse = cfg::on(cfg::kRpNoFuse);                                             // A/B
-        const bool fused = !par_fold && !no_fuse;
+        const bool fused = !par_fold && !cfg::on(cfg::kRpNoFuse);                                 // A/B
         if (fused) {
             Prof pr("rp_pass", st);
-            const RpFused fu{have_ranges ? nullptr : (uint64_t*)rfb.p, n_rec_dev ? 0 : n_rec, n_rec_dev, (const uint32_t*)s.pt_cnt[cur_pt].p, (uint32_t*)s.pt_need.p, (uint32_t*)s.nwin.p};
-            HIP_TRY(launch_rp_pass(false, r->t, base_text, cur_offs, (const Record*)records.p, (const uint64_t*)rfb.p, cur_thr, max_length, (RpKept*)s.kept.p, (RpHay*)s.hs.p, route, n_act, 0u, st, &fu));
+            const RpFused fu{have_ranges ? nullptr : ranges.get(), n_rec_dev ? 0 : n_rec, n_rec_dev, pc_cnt, s.pt_need.get(), s.nwin.get()};
+            HIP_TRY(launch_rp_pass(false, r->t, base_text, p.offs, records, ranges.get(), p.thr, max_length, s.kept.get(), s.hs.get(), s.route(), p.n_act, 0u, st, &fu));
         } else {
             { Prof pr("rp_ranges", st);
-              if (n_rec_dev) HIP_TRY(launch_rp_ranges_dev((const Record*)records.p, n_rec_dev, (uint64_t*)rfb.p, route, n_act, st));
-              else HIP_TRY(launch_rp_ranges((const Record*)records.p, n_rec, (uint64_t*)rfb.p, route, n_act, st)); }
-            AM_TRY(rp_fold(s, r, false, base_text, cur_offs, (const Record*)records.p, n_rec_dev ? 0 : n_rec, cur_thr, max_length, route, n_act, st, (const uint64_t*)rfb.p));
+              if (n_rec_dev) HIP_TRY(launch_rp_ranges_dev(records, n_rec_dev, ranges.get(), s.route(), p.n_act, st));
+              else HIP_TRY(launch_rp_ranges(records, n_rec, ranges.get(), s.route(), p.n_act, st)); }
+            AM_TRY(rp_fold(s, r, false, par_fold, base_text, p, records, n_rec_dev ? 0 : n_rec, max_length, ranges.get(), st));
         }
-        const bool small = n1 <= (1u << 18);
         { Prof pr("rp_scans", st);
-          if (!fused) HIP_TRY(launch_pt_count((const RpHay*)s.hs.p, (const uint32_t*)s.pt_cnt[cur_pt].p, n_act, (uint32_t*)s.pt_need.p, (uint32_t*)s.nwin.p, st));
-          ScanJobs jobs{};
-          jobs.j[0] = ScanJob{nullptr, route.len_next, (uint64_t*)s.off_next.p, n1, nullptr};
-          jobs.j[1] = ScanJob{nullptr, route.len_fin, (uint64_t*)s.off_fin.p, n1, nullptr};
-          jobs.j[2] = ScanJob{(const uint32_t*)s.pt_need.p, nullptr, (uint64_t*)s.pt_need_off.p, n1, nullptr};
-          jobs.j[3] = ScanJob{route.act, nullptr, (uint64_t*)s.act_idx.p, n1, nullptr};
-          jobs.j[4] = ScanJob{route.fin, nullptr, (uint64_t*)s.fin_idx.p, n1, nullptr};
-          jobs.j[5] = ScanJob{(const uint32_t*)s.nwin.p, nullptr, (uint64_t*)s.win_off.p, n1, nullptr};
-          jobs.n_jobs = 6;
-          AM_TRY(scan_pass(jobs, n1, s.scan_tmp.p, tmp2, st)); }
+          if (!fused) HIP_TRY(launch_pt_count(s.hs.get(), pc_cnt, p.n_act, s.pt_need.get(), s.nwin.get(), st));
+          AM_TRY(bookkeeping_scans(s, p, s.pt_need.get(), s.pt_need_off.get(), true, st)); }
         uint64_t woffs_last = n_rec;
-        { Prof pr("rp_windows", st);
-          if (!small) HIP_TRY(hipMemsetAsync(s.wlen.p, 0, (n_rec + 2) * 4, st));
-          HIP_TRY(launch_rp_win_meta(r->t, rt, (const RpHay*)s.hs.p, (const uint64_t*)rfb.p, (const RpKept*)s.kept.p,
-                                     (const uint64_t*)s.win_off.p, ov, (RpWin*)s.wins.p, (uint32_t*)s.wlen.p, n_act, st, true));
-          if (small) {
-              ScanJobs jobs{};
-              jobs.j[0] = ScanJob{(const uint32_t*)s.wlen.p, nullptr, (uint64_t*)s.woffs.p, 1, (const uint64_t*)s.win_off.p + n_act};
-              jobs.n_jobs = 1;
-              HIP_TRY(launch_scan_jobs(jobs, st));
-              woffs_last = ~0ull;
-          } else HIP_TRY(launch_scan(s.scan_tmp.p, tmp2, (const uint32_t*)s.wlen.p, (uint64_t*)s.woffs.p, n_rec + 1, st)); }
+        AM_TRY(window_geometry(s, r, p, ranges.get(), n_rec, ov, true, st, &woffs_last));
         // the pass's ONE synchronisation: bytes of next text, bytes of finished text, -, haystacks still active, haystacks finished,
         // windows, window bytes, piece entries, and the exact record count of this pass when it was still on the device
         // (k_rp_totals writes straight into the pinned host block -- 80 bytes of posted PCIe writes -- instead of into device memory that a
@@ -490,9 +603,8 @@ int replacer_run_pt(const am_replacer* r, const am_batch* in, uint64_t max_lengt
         // ... and the host waits for the LAST word of that block (a sequence number the kernel stores after a system-scope fence) by spinning on
         // it for a while before it falls back to hipStreamSynchronize: the blocking wait's wake-up cost 20-30 us of every pass's ~250
         const uint64_t seq = ++s.tot_seq;
-        HIP_TRY(launch_rp_totals(rt, n_act, (const uint64_t*)s.win_off.p, (const uint64_t*)s.woffs.p, woffs_last, s.tot_host, st,
-                                 (const uint64_t*)s.pt_need_off.p + n_act, n_rec_dev, seq));
-        const double t_s0 = now();
+        HIP_TRY(launch_rp_totals(rt, p.n_act, s.win_off.get(), s.woffs.get(), woffs_last, s.tot_host, st, s.pt_need_off.get() + p.n_act, n_rec_dev, seq));
+        const double t_s0 = PhaseClock::now();
         {
             const bool no_spin = cfg::on(cfg::kRpNoSpin);                                 // A/B
             bool seen = false;
@@ -500,32 +612,27 @@ int replacer_run_pt(const am_replacer* r, const am_batch* in, uint64_t max_lengt
                 const double give_up = t_s0 + 2e-3;
                 for (uint32_t it = 0; !seen; it++) {
                     seen = __atomic_load_n(&s.tot_host[15], __ATOMIC_ACQUIRE) == seq;
-                    if (!seen && (it & 1023u) == 1023u && now() > give_up) break;
+                    if (!seen && (it & 1023u) == 1023u && PhaseClock::now() > give_up) break;
                 }
             }
             if (!seen) HIP_TRY(hipStreamSynchronize(st));
         }
-        if (trace) t_sync += now() - t_s0;
+        if (trace) clk.t[kWaiting] += PhaseClock::now() - t_s0;
         const uint64_t* tot = s.tot_host;
         const uint64_t total_next = tot[0], total_fin = tot[1], n_next = tot[3], n_fin = tot[4], n_win = tot[5], total_w = tot[6], n_pieces = tot[8];
         if (n_rec_dev) { n_rec = tot[9]; n_rec_dev = nullptr; }
         AM_TRY(finished_home());                              // the previous pass's finished haystacks (their copies have had a whole pass)
-        t_a += now() - t0; t0 = now();
+        clk.lap(kFold);
         if (n_win >= 0xFFFFFFF0ull) return fail(AM_ERR_UNSUPPORTED, "too many replacements in one pass; split the batch");
         // ---- the next pass's piece lists; finished haystacks are materialised and go home
-        AM_TRY(s.offs[nxt].ensure((n_next + 1) * 8)); AM_TRY(s.orig[nxt].ensure((n_next + 1) * 4)); AM_TRY(s.thr[nxt].ensure((n_next + 1) * 8));
-        AM_TRY(s.fin_text.ensure(total_fin + 16)); AM_TRY(s.fin_meta.ensure((n_fin + 1) * sizeof(RpFin)));
-        AM_TRY(s.pt_pieces[cur_pt ^ 1].ensure((n_pieces + 2) * sizeof(RpPiece)));
-        AM_TRY(s.pt_start[cur_pt ^ 1].ensure((n_next + 1) * 8)); AM_TRY(s.pt_cnt[cur_pt ^ 1].ensure((n_next + 1) * 4));
-        AM_TRY(s.pt_fin_start.ensure((n_fin + 1) * 8)); AM_TRY(s.pt_fin_cnt.ensure((n_fin + 1) * 4));
+        DevArr<RpPiece>& next_pieces = s.pt_pieces[p.cur ^ 1]; DevArr<uint64_t>& next_start = s.pt_start[p.cur ^ 1]; DevArr<uint32_t>& next_cnt = s.pt_cnt[p.cur ^ 1];
+        AM_TRY(next_pieces.room(n_pieces + 2)); AM_TRY(next_start.room(n_next + 1)); AM_TRY(next_cnt.room(n_next + 1));
+        AM_TRY(s.pt_fin_start.room(n_fin + 1)); AM_TRY(s.pt_fin_cnt.room(n_fin + 1));
         if (ev_copied_used) HIP_TRY(hipStreamWaitEvent(st, ev_copied, 0));      // the previous pass's finished texts are written and their metadata has left fin_meta
-        { Prof pr("rp_route", st);
-          HIP_TRY(launch_rp_route((const RpHay*)s.hs.p, rt, cur_orig, n_act, (uint64_t*)s.offs[nxt].p, (uint32_t*)s.orig[nxt].p, (int64_t*)s.thr[nxt].p, (RpFin*)s.fin_meta.p, st)); }
+        AM_TRY(route_next(s, p, n_next, n_fin, total_fin, st));
         { Prof pr("pt_build", st);
-          HIP_TRY(launch_pt_build(r->t, (const RpHay*)s.hs.p, (const uint64_t*)rfb.p, (const RpKept*)s.kept.p, (const RpPiece*)s.pt_pieces[cur_pt].p,
-                                  (const uint64_t*)s.pt_start[cur_pt].p, (const uint32_t*)s.pt_cnt[cur_pt].p, (const uint64_t*)s.pt_need_off.p, rt, n_act,
-                                  (RpPiece*)s.pt_pieces[cur_pt ^ 1].p, (uint64_t*)s.pt_start[cur_pt ^ 1].p, (uint32_t*)s.pt_cnt[cur_pt ^ 1].p,
-                                  (uint64_t*)s.pt_fin_start.p, (uint32_t*)s.pt_fin_cnt.p, st)); }
+          HIP_TRY(launch_pt_build(r->t, s.hs.get(), ranges.get(), s.kept.get(), pieces, pc_start, pc_cnt, s.pt_need_off.get(), rt, p.n_act,
+                                  next_pieces.get(), next_start.get(), next_cnt.get(), s.pt_fin_start.get(), s.pt_fin_cnt.get(), st)); }
         res->spliced += total_fin;
         if (n_fin) {
             uint8_t* home = nullptr;
@@ -538,79 +645,61 @@ int replacer_run_pt(const am_replacer* r, const am_batch* in, uint64_t max_lengt
             hipStream_t mst = mat_main ? st : s.copy_stream;
             if (!mat_main) { HIP_TRY(hipEventRecord(s.ev_spliced, st)); HIP_TRY(hipStreamWaitEvent(s.copy_stream, s.ev_spliced, 0)); }
             { Prof pr("pt_materialise", mst);
-              HIP_TRY(launch_pt_materialise((const RpPiece*)s.pt_pieces[cur_pt ^ 1].p, (const uint64_t*)s.pt_fin_start.p, (const uint32_t*)s.pt_fin_cnt.p, (const RpFin*)s.fin_meta.p,
-                                            (uint32_t)n_fin, base_text, r->t.repl, res->dev >= 0 && total_fin ? home : (uint8_t*)s.fin_text.p, mst)); }
+              HIP_TRY(launch_pt_materialise(next_pieces.get(), s.pt_fin_start.get(), s.pt_fin_cnt.get(), s.fin_meta.get(), (uint32_t)n_fin, base_text, r->t.repl,
+                                            res->dev >= 0 && total_fin ? home : s.fin_text.get(), mst)); }
             if (mat_main) { HIP_TRY(hipEventRecord(s.ev_spliced, st)); HIP_TRY(hipStreamWaitEvent(s.copy_stream, s.ev_spliced, 0)); }
-            if (total_fin && res->dev < 0) HIP_TRY(hipMemcpyAsync(home, s.fin_text.p, total_fin, hipMemcpyDeviceToHost, s.copy_stream));
-            HIP_TRY(hipMemcpyAsync(s.fin_host.p, s.fin_meta.p, n_fin * sizeof(RpFin), hipMemcpyDeviceToHost, s.copy_stream));
+            if (total_fin && res->dev < 0) HIP_TRY(hipMemcpyAsync(home, s.fin_text.get(), total_fin, hipMemcpyDeviceToHost, s.copy_stream));
+            HIP_TRY(hipMemcpyAsync(s.fin_host.p, s.fin_meta.get(), n_fin * sizeof(RpFin), hipMemcpyDeviceToHost, s.copy_stream));
             HIP_TRY(hipEventRecord(ev_copied, s.copy_stream));
             ev_copied_used = true;
             prev_n_fin = n_fin; prev_total_fin = total_fin; prev_home = home; copies_pending = true;
         }
-        t_b += now() - t0; t0 = now();
+        clk.lap(kPieces);
         // ---- the next pass's records
         uint64_t next_n_rec = 0; const uint64_t* next_n_rec_dev = nullptr; bool next_have_ranges = false;
         if (n_next > 0) {
-            DevBuf& next_records = s.recbuf[cur_rec ^ 1];
             if (total_w > total_next) {
                 // tiny texts: the windows would be larger than the texts themselves -- materialise the next texts and scan them whole
-                AM_TRY(s.text[0].ensure(padded_text(total_next)));
-                HIP_TRY(launch_pt_materialise_next((const RpPiece*)s.pt_pieces[cur_pt ^ 1].p, (const uint64_t*)s.pt_start[cur_pt ^ 1].p, (const uint32_t*)s.pt_cnt[cur_pt ^ 1].p,
-                                                   (const uint64_t*)s.offs[nxt].p, (uint32_t)n_next, base_text, r->t.repl, (uint8_t*)s.text[0].p, st));
-                HIP_TRY(hipMemsetAsync((uint8_t*)s.text[0].p + total_next, 0, padded_text(total_next) - (size_t)total_next, st));
-                AM_TRY(bind_workspace(s.ws, in->dev, s.text[0].p, (const uint64_t*)s.offs[nxt].p, total_next, (uint32_t)n_next));
-                AM_TRY(run_records(r->a, r->case_mode, &s.ws, records_into(next_records), &next_n_rec));
+                AM_TRY(s.text[0].room(padded_text(total_next)));
+                HIP_TRY(launch_pt_materialise_next(next_pieces.get(), next_start.get(), next_cnt.get(), s.offs[p.nxt].get(), (uint32_t)n_next, base_text, r->t.repl, s.text[0].get(), st));
+                HIP_TRY(hipMemsetAsync(s.text[0].get() + total_next, 0, padded_text(total_next) - (size_t)total_next, st));
+                AM_TRY(bind_workspace(s.ws, in->dev, s.text[0].get(), s.offs[p.nxt].get(), total_next, (uint32_t)n_next));
+                AM_TRY(run_records(r->a, r->case_mode, &s.ws, records_into(s.recbuf[p.cur ^ 1]), &next_n_rec));
                 res->scanned += total_next;
             } else {
                 // windows around the replacements (gathered from the new piece lists) + the shifted old records; no host round trip when the
                 // worst-case record pool of the window scan stays small
                 const bool lean = total_w <= (64ull << 20);
                 uint64_t n_wrec = 0; const uint64_t* n_wrec_dev = nullptr;
-                AM_TRY(s.wtext.ensure(padded_text(total_w)));
-                AM_TRY(s.wrec.ensure(((lean ? total_w : 0) + 1) * sizeof(Record)));
+                AM_TRY(s.wtext.room(padded_text(total_w)));
+                AM_TRY(s.wrec.room((lean ? total_w : 0) + 1));
                 if (n_win > 0 && total_w > 0) {
                     { Prof pr("rp_windows", st);
-                      HIP_TRY(launch_pt_win_copy((const RpWin*)s.wins.p, (const uint64_t*)s.woffs.p, (const RpPiece*)s.pt_pieces[cur_pt ^ 1].p, (const uint64_t*)s.pt_start[cur_pt ^ 1].p,
-                                                 (const uint32_t*)s.pt_cnt[cur_pt ^ 1].p, base_text, r->t.repl, (uint8_t*)s.wtext.p, n_win, total_w, padded_text(total_w), st)); }
-                    AM_TRY(bind_workspace(s.ws2, in->dev, s.wtext.p, (const uint64_t*)s.woffs.p, total_w, (uint32_t)n_win));
-                    if (lean) AM_TRY(run_records_async(r->a, r->case_mode, &s.ws2, (Record*)s.wrec.p, &n_wrec_dev, st));
+                      HIP_TRY(launch_pt_win_copy(s.wins.get(), s.woffs.get(), next_pieces.get(), next_start.get(), next_cnt.get(), base_text, r->t.repl, s.wtext.get(), n_win, total_w,
+                                                 padded_text(total_w), st)); }
+                    AM_TRY(bind_workspace(s.ws2, in->dev, s.wtext.get(), s.woffs.get(), total_w, (uint32_t)n_win));
+                    if (lean) AM_TRY(run_records_async(r->a, r->case_mode, &s.ws2, s.wrec.get(), &n_wrec_dev, st));
                     else AM_TRY(run_records(r->a, r->case_mode, &s.ws2, records_into(s.wrec), &n_wrec));
                     res->scanned += total_w;
                 }
                 const uint64_t wrec_bound = n_wrec_dev ? total_w : n_wrec;
-                AM_TRY(s.wrec_first.ensure((n_win + 2) * 8)); AM_TRY(s.mcount.ensure((n_next + 1) * 4)); AM_TRY(rfb_next.ensure((n_next + 1) * 8));
-                AM_TRY(next_records.ensure((n_rec + wrec_bound + 1) * sizeof(Record)));
-                Prof pr("rp_merge", st);
-                if (n_wrec_dev) HIP_TRY(launch_rp_ranges_dev((const Record*)s.wrec.p, n_wrec_dev, (uint64_t*)s.wrec_first.p, kNoRoute, (uint32_t)n_win, st));
-                else HIP_TRY(launch_rp_ranges((const Record*)s.wrec.p, n_wrec, (uint64_t*)s.wrec_first.p, kNoRoute, (uint32_t)n_win, st));
-                HIP_TRY(launch_rp_merge(false, (const Record*)records.p, (const uint64_t*)rfb.p, (const RpKept*)s.kept.p, (const RpHay*)s.hs.p, cur_offs, rt,
-                                        (const uint64_t*)s.win_off.p, (const RpWin*)s.wins.p, (const Record*)s.wrec.p, (const uint64_t*)s.wrec_first.p, ov, n_act,
-                                        (uint32_t*)s.mcount.p, nullptr, nullptr, st));
-                { ScanJobs jobs{};
-                  jobs.j[0] = ScanJob{(const uint32_t*)s.mcount.p, nullptr, (uint64_t*)rfb_next.p, n_next + 1, nullptr};
-                  jobs.n_jobs = 1;
-                  AM_TRY(scan_pass(jobs, n_next + 1, s.scan_tmp.p, tmp2, st)); }
-                HIP_TRY(launch_rp_merge(true, (const Record*)records.p, (const uint64_t*)rfb.p, (const RpKept*)s.kept.p, (const RpHay*)s.hs.p, cur_offs, rt,
-                                        (const uint64_t*)s.win_off.p, (const RpWin*)s.wins.p, (const Record*)s.wrec.p, (const uint64_t*)s.wrec_first.p, ov, n_act,
-                                        (uint32_t*)s.mcount.p, (const uint64_t*)rfb_next.p, (Record*)next_records.p, st));
+                AM_TRY(merge_records(s, p, ranges.get(), n_rec, n_next, n_win, wrec_bound, n_wrec_dev, ov, false, ranges_next, st));
                 next_n_rec = n_rec + wrec_bound;                 // an upper bound; the exact count is read with the next pass's totals
-                next_n_rec_dev = (const uint64_t*)rfb_next.p + n_next;
+                next_n_rec_dev = ranges_next.get() + n_next;
                 next_have_ranges = true;
             }
         }
-        t_c += now() - t0;
+        clk.lap(kWindows);
         if (trace && cfg::get(cfg::kRpTrace) == 2)
-            std::fprintf(stderr, "[am_replacer pt pass %u] active %u -> %llu, finished %llu, records <= %llu, windows %llu (%llu B), next text %llu B\n", (unsigned)res->passes, n_act,
+            std::fprintf(stderr, "[am_replacer pt pass %u] active %u -> %llu, finished %llu, records <= %llu, windows %llu (%llu B), next text %llu B\n", (unsigned)res->passes, p.n_act,
                          (unsigned long long)n_next, (unsigned long long)n_fin, (unsigned long long)n_rec, (unsigned long long)n_win, (unsigned long long)total_w, (unsigned long long)total_next);
-        cur_rec ^= 1; cur_pt ^= 1; n_rec = next_n_rec; n_rec_dev = next_n_rec_dev;
-        const bool no_reuse = cfg::on(cfg::kRpNoRangeReuse);                              // A/B
-        have_ranges = next_have_ranges && !no_reuse; cur_rf ^= 1;
-        cur_offs = (const uint64_t*)s.offs[nxt].p; cur_orig = (const uint32_t*)s.orig[nxt].p; cur_thr = (const int64_t*)s.thr[nxt].p;
-        n_act = (uint32_t)n_next; nxt ^= 1;
+        n_rec = next_n_rec; n_rec_dev = next_n_rec_dev;
+        have_ranges = next_have_ranges && !cfg::on(cfg::kRpNoRangeReuse);                         // A/B
+        p.advance(s, n_next);
     }
     HIP_TRY(hipStreamSynchronize(st));
     AM_TRY(finished_home());
-    if (trace) std::fprintf(stderr, "[am_replacer pt] fold+scans %.1f ms (of which waiting for the device %.1f), pieces+materialise %.1f ms, windows+merge %.1f ms\n", t_a * 1e3, t_sync * 1e3, t_b * 1e3, t_c * 1e3);
+    if (trace) clk.print("[am_replacer pt] fold+scans %.1f ms (of which waiting for the device %.1f), pieces+materialise %.1f ms, windows+merge %.1f ms\n");
     return AM_OK;
 }
 
@@ -642,165 +731,98 @@ int replacer_run(const am_replacer* r, const am_batch* in, uint64_t max_length, 
     AM_TRY(s.pinned_totals());
     // pass 0 reads the caller's batch in place; afterwards the text ping-pongs between s.text[0] and s.text[1]
     const uint8_t* cur_text = (const uint8_t*)in->d_text;
-    const uint64_t* cur_offs = in->d_offsets;
     uint64_t total = in->total;
-    uint32_t n_act = n_hay;
-    int nxt = 0;
     AM_TRY(s.first_pass_arrays(n_hay, st));
-    const uint32_t* cur_orig = (const uint32_t*)s.first_orig.p;
-    const int64_t* cur_thr = (const int64_t*)s.first_thr.p;
+    RpPass p{in->d_offsets, s.first_orig.get(), s.first_thr.get(), n_hay};
     AM_TRY(s.copy_lane());
     // Incremental re-scan (am_replace.hip): after the first pass only windows around the replacements are scanned and
     // merged with the shifted records of the previous pass.  Needs the suffix-filter kernel's position-local semantics
     // (automata with the empty needle re-scan everything); AM_RP_FULL_SCANS=1 turns it off (A/B, tests).
     const Flavor* flavor = nullptr;
     AM_TRY(prepare(r->a, r->case_mode, &flavor));
+    const bool ic = r->case_mode == AM_IGNORE_CASE;
     const uint32_t ov = 4u * (flavor->h.max_needle_cps ? flavor->h.max_needle_cps : 1u) + 4u;
     const bool inc_enabled = flavor->h.sf_enabled && flavor->h.root_vlen == 0 && r->a->kernel_pref != 1 && !cfg::on(cfg::kRpFullScans);
     bool have_inc = false;
     uint64_t inc_n_rec = 0;
-    int cur_rec = 0;
+    DevArr<uint64_t>& ranges = s.rec_first[0];
     // AM_RP_TRACE=1: wall-clock split of the loop on stderr (development aid)
-    const bool trace = cfg::on(cfg::kRpTrace);
-    double t_scan = 0, t_fold = 0, t_splice = 0, t_home = 0;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    struct Report { bool on; double &a, &b, &c, &d; ~Report() { if (on) std::fprintf(stderr, "[am_replacer] scan %.1f ms, fold+scans %.1f ms, splice+D2H %.1f ms, scatter %.1f ms\n", a * 1e3, b * 1e3, c * 1e3, d * 1e3); } } report{trace, t_scan, t_fold, t_splice, t_home};
+    PhaseClock clk;
+    enum { kScan, kFold, kSplice, kHome };
+    struct Report { bool on; const PhaseClock& c; ~Report() { if (on) c.print("[am_replacer] scan %.1f ms, fold+scans %.1f ms, splice+D2H %.1f ms, scatter %.1f ms\n"); } } report{cfg::on(cfg::kRpTrace), clk};
 
-    while (n_act > 0) {
-        double t0 = now();
+    while (p.n_act > 0) {
+        clk.start();
         res->passes++;
         // ---- the scan (Replacer.hs:223-225): everything, unless the previous pass already derived this pass's records
         uint64_t n_rec = 0;
-        DevBuf& records = s.recbuf[cur_rec];
         if (have_inc) { n_rec = inc_n_rec; have_inc = false; }
         else {
             res->scanned += total;
-            AM_TRY(bind_workspace(s.ws, in->dev, cur_text, cur_offs, total, n_act));
-            AM_TRY(run_records(r->a, r->case_mode, &s.ws, records_into(records), &n_rec));
+            AM_TRY(bind_workspace(s.ws, in->dev, cur_text, p.offs, total, p.n_act));
+            AM_TRY(run_records(r->a, r->case_mode, &s.ws, records_into(s.recbuf[p.cur]), &n_rec));
         }
-        t_scan += now() - t0; t0 = now();
-        // ---- per-haystack fold of the records
-        const uint64_t n1 = (uint64_t)n_act + 1;
-        AM_TRY(s.rec_first.ensure(n1 * 8)); AM_TRY(s.kept.ensure((n_rec + 1) * sizeof(RpKept))); AM_TRY(s.hs.ensure(n1 * sizeof(RpHay)));
-        AM_TRY(s.len_next.ensure(n1 * 8)); AM_TRY(s.len_fin.ensure(n1 * 8)); AM_TRY(s.tiles.ensure(n1 * 4)); AM_TRY(s.act.ensure(n1 * 4)); AM_TRY(s.fin.ensure(n1 * 4));
-        AM_TRY(s.off_next.ensure(n1 * 8)); AM_TRY(s.off_fin.ensure(n1 * 8)); AM_TRY(s.tile_off.ensure(n1 * 8)); AM_TRY(s.act_idx.ensure(n1 * 8)); AM_TRY(s.fin_idx.ensure(n1 * 8));
-        size_t t32 = 0, t64 = 0;
-        if (scan_temp_bytes(n1, &t32) != hipSuccess || scan64_temp_bytes(n1, &t64) != hipSuccess) return fail(AM_ERR_HIP, "scan sizing failed");
-        const size_t tmp_bytes = t32 > t64 ? t32 : t64;
-        AM_TRY(s.scan_tmp.ensure(tmp_bytes + 16));
-        AM_TRY(records.ensure(sizeof(Record)));            // a valid pointer even when nothing matched
-        RpRoute route{(uint64_t*)s.len_next.p, (uint64_t*)s.len_fin.p, (uint32_t*)s.tiles.p, (uint32_t*)s.act.p, (uint32_t*)s.fin.p};
-        { Prof pr("rp_ranges", st); HIP_TRY(launch_rp_ranges((const Record*)records.p, n_rec, (uint64_t*)s.rec_first.p, route, n_act, st)); }
-        AM_TRY(rp_fold(s, r, r->case_mode == AM_IGNORE_CASE, cur_text, cur_offs, (const Record*)records.p, n_rec, cur_thr, max_length, route, n_act, st, (const uint64_t*)s.rec_first.p));
-        RpRouted rt{(const uint64_t*)s.off_next.p, (const uint64_t*)s.off_fin.p, (const uint64_t*)s.tile_off.p, (const uint64_t*)s.act_idx.p, (const uint64_t*)s.fin_idx.p};
-        // windows of the incremental re-scan (their geometry follows from the kept matches alone, the text is copied after the splice)
+        clk.lap(kScan);
+        // ---- per-haystack fold of the records; windows of the incremental re-scan
         const bool try_inc = inc_enabled && n_rec > 0;
-        const bool small = n1 <= (1u << 18);          // bookkeeping sums in one launch (k_scan_jobs) instead of a dozen scan launches
-        size_t tmp2 = tmp_bytes;
-        uint64_t woffs_last = n_rec;
-        if (try_inc) {
-            AM_TRY(s.nwin.ensure(n1 * 4)); AM_TRY(s.win_off.ensure(n1 * 8));
-            AM_TRY(s.wins.ensure((n_rec + 1) * sizeof(RpWin))); AM_TRY(s.wlen.ensure((n_rec + 2) * 4)); AM_TRY(s.woffs.ensure((n_rec + 2) * 8));
-            size_t tw = 0;
-            if (scan_temp_bytes(n_rec + 1, &tw) != hipSuccess) return fail(AM_ERR_HIP, "scan sizing failed");
-            AM_TRY(s.scan_tmp.ensure(std::max(tw, tmp_bytes) + 16));
-            tmp2 = s.scan_tmp.cap - 16;
-            HIP_TRY(launch_rp_win_count((const RpHay*)s.hs.p, n_act, (uint32_t*)s.nwin.p, st));
-        }
+        const bool par_fold = parallel_fold_wanted(p.n_act, n_rec);
+        AM_TRY(size_pass(s, p, ranges, n_rec, try_inc));
+        const Record* records = s.recbuf[p.cur].get();
+        const RpRouted rt = s.routed();
+        { Prof pr("rp_ranges", st); HIP_TRY(launch_rp_ranges(records, n_rec, ranges.get(), s.route(), p.n_act, st)); }
+        AM_TRY(rp_fold(s, r, ic, par_fold, cur_text, p, records, n_rec, max_length, ranges.get(), st));
+        if (try_inc) HIP_TRY(launch_rp_win_count(s.hs.get(), p.n_act, s.nwin.get(), st));
         { Prof pr("rp_scans", st);
-          ScanJobs jobs{};
-          jobs.j[0] = ScanJob{nullptr, route.len_next, (uint64_t*)s.off_next.p, n1, nullptr};
-          jobs.j[1] = ScanJob{nullptr, route.len_fin, (uint64_t*)s.off_fin.p, n1, nullptr};
-          jobs.j[2] = ScanJob{route.tiles, nullptr, (uint64_t*)s.tile_off.p, n1, nullptr};
-          jobs.j[3] = ScanJob{route.act, nullptr, (uint64_t*)s.act_idx.p, n1, nullptr};
-          jobs.j[4] = ScanJob{route.fin, nullptr, (uint64_t*)s.fin_idx.p, n1, nullptr};
-          jobs.n_jobs = 5;
-          if (try_inc) { jobs.j[5] = ScanJob{(const uint32_t*)s.nwin.p, nullptr, (uint64_t*)s.win_off.p, n1, nullptr}; jobs.n_jobs = 6; }
-          AM_TRY(scan_pass(jobs, n1, s.scan_tmp.p, tmp2, st)); }
-        if (try_inc) {
-            Prof pr("rp_windows", st);
-            if (!small) HIP_TRY(hipMemsetAsync(s.wlen.p, 0, (n_rec + 2) * 4, st));     // at most one window per record; unused entries scan as zeros
-            HIP_TRY(launch_rp_win_meta(r->t, rt, (const RpHay*)s.hs.p, (const uint64_t*)s.rec_first.p, (const RpKept*)s.kept.p,
-                                       (const uint64_t*)s.win_off.p, ov, (RpWin*)s.wins.p, (uint32_t*)s.wlen.p, n_act, st));
-            if (small) {          // exactly n_win + 1 elements: the count is read on the device
-                ScanJobs jobs{};
-                jobs.j[0] = ScanJob{(const uint32_t*)s.wlen.p, nullptr, (uint64_t*)s.woffs.p, 1, (const uint64_t*)s.win_off.p + n_act};
-                jobs.n_jobs = 1;
-                HIP_TRY(launch_scan_jobs(jobs, st));
-                woffs_last = ~0ull;
-            } else HIP_TRY(launch_scan(s.scan_tmp.p, tmp2, (const uint32_t*)s.wlen.p, (uint64_t*)s.woffs.p, n_rec + 1, st));
-        }
+          AM_TRY(bookkeeping_scans(s, p, s.tiles.get(), s.tile_off.get(), try_inc, st)); }
+        uint64_t woffs_last = n_rec;
+        if (try_inc) AM_TRY(window_geometry(s, r, p, ranges.get(), n_rec, ov, false, st, &woffs_last));
         // bytes of next text, bytes of finished text, tiles, haystacks still active, haystacks finished, windows, window bytes
-        HIP_TRY(launch_rp_totals(rt, n_act, try_inc ? (const uint64_t*)s.win_off.p : nullptr, try_inc ? (const uint64_t*)s.woffs.p : nullptr, woffs_last,
-                                 (uint64_t*)s.totals.p, st));
-        HIP_TRY(hipMemcpyAsync(s.tot_host, s.totals.p, 56, hipMemcpyDeviceToHost, st));
+        HIP_TRY(launch_rp_totals(rt, p.n_act, try_inc ? s.win_off.get() : nullptr, try_inc ? s.woffs.get() : nullptr, woffs_last, s.totals.get(), st));
+        HIP_TRY(hipMemcpyAsync(s.tot_host, s.totals.get(), 56, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         const uint64_t* tot = s.tot_host;
         const uint64_t total_next = tot[0], total_fin = tot[1], n_tiles = tot[2], n_next = tot[3], n_fin = tot[4], n_win = tot[5], total_w = tot[6];
-        t_fold += now() - t0; t0 = now();
+        clk.lap(kFold);
         res->spliced += total_next + total_fin;
         if (n_tiles >= 0x7FFFFFF0ull) return fail(AM_ERR_UNSUPPORTED, "replacement output too large for one launch; split the batch");
         // ---- replace (Replacer.hs:163-180) into the next batch / the finished buffer
-        AM_TRY(s.text[nxt].ensure(padded_text(total_next))); AM_TRY(s.offs[nxt].ensure((n_next + 1) * 8));
-        AM_TRY(s.orig[nxt].ensure((n_next + 1) * 4)); AM_TRY(s.thr[nxt].ensure((n_next + 1) * 8));
-        AM_TRY(s.fin_text.ensure(total_fin + 16)); AM_TRY(s.fin_meta.ensure((n_fin + 1) * sizeof(RpFin))); AM_TRY(s.tile_hay.ensure((n_tiles + 1) * 4));
-        { Prof pr("rp_route", st);
-          HIP_TRY(launch_rp_route((const RpHay*)s.hs.p, rt, cur_orig, n_act, (uint64_t*)s.offs[nxt].p, (uint32_t*)s.orig[nxt].p, (int64_t*)s.thr[nxt].p, (RpFin*)s.fin_meta.p, st)); }
+        DevArr<uint8_t>& text_next = s.text[p.nxt];
+        AM_TRY(text_next.room(padded_text(total_next))); AM_TRY(s.tile_hay.room(n_tiles + 1));
+        AM_TRY(route_next(s, p, n_next, n_fin, total_fin, st));
         { Prof pr("rp_splice", st);
-          HIP_TRY(launch_rp_splice(r->t, cur_text, cur_offs, (const uint64_t*)s.rec_first.p, (const RpKept*)s.kept.p, (const RpHay*)s.hs.p, rt, n_act, n_tiles,
-                                   (uint32_t*)s.tile_hay.p, (uint8_t*)s.text[nxt].p, (uint8_t*)s.fin_text.p, st)); }
-        HIP_TRY(hipMemsetAsync((uint8_t*)s.text[nxt].p + total_next, 0, padded_text(total_next) - (size_t)total_next, st));
+          HIP_TRY(launch_rp_splice(r->t, cur_text, p.offs, ranges.get(), s.kept.get(), s.hs.get(), rt, p.n_act, n_tiles, s.tile_hay.get(), text_next.get(), s.fin_text.get(), st)); }
+        HIP_TRY(hipMemsetAsync(text_next.get() + total_next, 0, padded_text(total_next) - (size_t)total_next, st));
         // ---- finished haystacks go home: the copy runs on its own stream, next to the window scans below
         uint8_t* home = nullptr;
         if (total_fin) AM_TRY(res->room((size_t)total_fin, &home));
         AM_TRY(s.fin_host.ensure((n_fin + 1) * sizeof(RpFin)));
         HIP_TRY(hipEventRecord(s.ev_spliced, st));
         HIP_TRY(hipStreamWaitEvent(s.copy_stream, s.ev_spliced, 0));
-        if (total_fin) HIP_TRY(hipMemcpyAsync(home, s.fin_text.p, total_fin, hipMemcpyDefault, s.copy_stream));      // the slab is pinned host memory, or device memory for results that stay there
-        if (n_fin) HIP_TRY(hipMemcpyAsync(s.fin_host.p, s.fin_meta.p, n_fin * sizeof(RpFin), hipMemcpyDeviceToHost, s.copy_stream));
-        t_splice += now() - t0; t0 = now();
-        t_home += now() - t0; t0 = now();
+        if (total_fin) HIP_TRY(hipMemcpyAsync(home, s.fin_text.get(), total_fin, hipMemcpyDefault, s.copy_stream));      // the slab is pinned host memory, or device memory for results that stay there
+        if (n_fin) HIP_TRY(hipMemcpyAsync(s.fin_host.p, s.fin_meta.get(), n_fin * sizeof(RpFin), hipMemcpyDeviceToHost, s.copy_stream));
+        clk.lap(kSplice);
         // ---- next pass's records without a full scan: windows around the replacements + the shifted old records
         if (try_inc && n_next > 0 && n_win > 0 && n_win < 0xFFFFFFF0ull && total_w <= total_next / 2) {
-            const uint8_t* text_next = (const uint8_t*)s.text[nxt].p;
-            AM_TRY(s.wtext.ensure(padded_text(total_w)));
+            AM_TRY(s.wtext.room(padded_text(total_w)));
             { Prof pr("rp_windows", st);
-              HIP_TRY(launch_rp_win_copy((const RpWin*)s.wins.p, (const uint64_t*)s.woffs.p, text_next, (uint8_t*)s.wtext.p, n_win, st));
-              HIP_TRY(hipMemsetAsync((uint8_t*)s.wtext.p + total_w, 0, padded_text(total_w) - (size_t)total_w, st)); }
-            AM_TRY(bind_workspace(s.ws2, in->dev, s.wtext.p, (const uint64_t*)s.woffs.p, total_w, (uint32_t)n_win));
+              HIP_TRY(launch_rp_win_copy(s.wins.get(), s.woffs.get(), text_next.get(), s.wtext.get(), n_win, st));
+              HIP_TRY(hipMemsetAsync(s.wtext.get() + total_w, 0, padded_text(total_w) - (size_t)total_w, st)); }
+            AM_TRY(bind_workspace(s.ws2, in->dev, s.wtext.get(), s.woffs.get(), total_w, (uint32_t)n_win));
             uint64_t n_wrec = 0;
             AM_TRY(run_records(r->a, r->case_mode, &s.ws2, records_into(s.wrec), &n_wrec));
             res->scanned += total_w;
-            AM_TRY(s.wrec.ensure(sizeof(Record)));
-            AM_TRY(s.wrec_first.ensure((n_win + 1) * 8)); AM_TRY(s.mcount.ensure((n_next + 1) * 4)); AM_TRY(s.moff.ensure((n_next + 1) * 8));
-            DevBuf& next_records = s.recbuf[cur_rec ^ 1];
-            AM_TRY(next_records.ensure((n_rec + n_wrec + 1) * sizeof(Record)));          // upper bound; the exact count arrives with the end-of-pass sync
-            Prof pr("rp_merge", st);
-            HIP_TRY(launch_rp_ranges((const Record*)s.wrec.p, n_wrec, (uint64_t*)s.wrec_first.p, kNoRoute, (uint32_t)n_win, st));
-            HIP_TRY(hipMemsetAsync((uint32_t*)s.mcount.p + n_next, 0, 4, st));
-            HIP_TRY(launch_rp_merge(false, (const Record*)records.p, (const uint64_t*)s.rec_first.p, (const RpKept*)s.kept.p, (const RpHay*)s.hs.p, cur_offs, rt,
-                                    (const uint64_t*)s.win_off.p, (const RpWin*)s.wins.p, (const Record*)s.wrec.p, (const uint64_t*)s.wrec_first.p, ov, n_act,
-                                    (uint32_t*)s.mcount.p, nullptr, nullptr, st));
-            { ScanJobs jobs{};
-              jobs.j[0] = ScanJob{(const uint32_t*)s.mcount.p, nullptr, (uint64_t*)s.moff.p, n_next + 1, nullptr};
-              jobs.n_jobs = 1;
-              AM_TRY(scan_pass(jobs, n_next + 1, s.scan_tmp.p, tmp2, st)); }
-            HIP_TRY(launch_rp_merge(true, (const Record*)records.p, (const uint64_t*)s.rec_first.p, (const RpKept*)s.kept.p, (const RpHay*)s.hs.p, cur_offs, rt,
-                                    (const uint64_t*)s.win_off.p, (const RpWin*)s.wins.p, (const Record*)s.wrec.p, (const uint64_t*)s.wrec_first.p, ov, n_act,
-                                    (uint32_t*)s.mcount.p, (const uint64_t*)s.moff.p, (Record*)next_records.p, st));
-            HIP_TRY(hipMemcpyAsync(&s.tot_host[7], (uint64_t*)s.moff.p + n_next, 8, hipMemcpyDeviceToHost, st));
+            AM_TRY(s.wrec.room(1));
+            AM_TRY(merge_records(s, p, ranges.get(), n_rec, n_next, n_win, n_wrec, nullptr, ov, true, s.moff, st));
+            HIP_TRY(hipMemcpyAsync(&s.tot_host[7], s.moff.get() + n_next, 8, hipMemcpyDeviceToHost, st));      // the exact count arrives with the end-of-pass sync
             have_inc = true;
         }
         HIP_TRY(hipStreamSynchronize(st));            // end of pass: the merged record count (if any) is on the host now
         if (have_inc) inc_n_rec = s.tot_host[7];
-        t_scan += now() - t0; t0 = now();
+        clk.lap(kScan);
         AM_TRY(scatter_finished(s, n_fin, total_fin, home, n_hay, res));
-        t_home += now() - t0; t0 = now();
-        cur_rec ^= 1;
-        cur_text = (const uint8_t*)s.text[nxt].p; cur_offs = (const uint64_t*)s.offs[nxt].p;
-        cur_orig = (const uint32_t*)s.orig[nxt].p; cur_thr = (const int64_t*)s.thr[nxt].p;
-        total = total_next; n_act = (uint32_t)n_next; nxt ^= 1;
-        t_scan += now() - t0;
+        clk.lap(kHome);
+        cur_text = text_next.get(); total = total_next;
+        p.advance(s, n_next);
     }
     return AM_OK;
 }
@@ -850,40 +872,41 @@ static int replacer_run_loop(const am_replacer* r, const am_batch* in, uint64_t 
     if (n_rec >= (1ull << 26)) return AM_OK;                 // (the regions below would not fit: the pass-by-pass loop scans again)
     const uint64_t n1 = (uint64_t)n_hay + 1;
     const uint64_t rec_total = 4 * n_rec + 128ull * n_hay, pc_total = 8 * n_rec + 128ull * n_hay;      // = the sums of k_rp_loop_caps' region sizes
-    AM_TRY(s.recbuf[0].ensure(sizeof(Record)));
-    AM_TRY(s.rec_first.ensure(n1 * 8));
-    AM_TRY(s.lp_cap_r.ensure(n1 * 4)); AM_TRY(s.lp_cap_p.ensure(n1 * 4)); AM_TRY(s.lp_rec_base.ensure(n1 * 8)); AM_TRY(s.lp_pc_base.ensure(n1 * 8));
-    AM_TRY(s.lp_rec.ensure((rec_total + 1) * sizeof(Record))); AM_TRY(s.lp_pc.ensure((pc_total + 1) * sizeof(RpPiece)));
-    AM_TRY(s.lp_kept.ensure((rec_total / 2 + 1) * sizeof(RpKept)));
-    AM_TRY(s.lp_wtext.ensure(wcap64 * n_hay + 64)); AM_TRY(s.lp_out.ensure(n1 * sizeof(RpLoopOut))); AM_TRY(s.lp_ctrl.ensure(128));
+    DevArr<uint64_t>& ranges = s.rec_first[0];
+    AM_TRY(s.recbuf[0].room(1));
+    AM_TRY(ranges.room(n1));
+    AM_TRY(s.lp_cap_r.room(n1)); AM_TRY(s.lp_cap_p.room(n1)); AM_TRY(s.lp_rec_base.room(n1)); AM_TRY(s.lp_pc_base.room(n1));
+    AM_TRY(s.lp_rec.room(rec_total + 1)); AM_TRY(s.lp_pc.room(pc_total + 1));
+    AM_TRY(s.lp_kept.room(rec_total / 2 + 1));
+    AM_TRY(s.lp_wtext.room(wcap64 * n_hay + 64)); AM_TRY(s.lp_out.room(n1)); AM_TRY(s.lp_ctrl.room(32));
     size_t t32 = 0;
     if (scan_temp_bytes(n1, &t32) != hipSuccess) return fail(AM_ERR_HIP, "scan sizing failed");
-    AM_TRY(s.scan_tmp.ensure(t32 + 16));
+    AM_TRY(s.scan_tmp.room(t32 + 16));
     { Prof pr("rp_ranges", st);
-      HIP_TRY(launch_rp_ranges((const Record*)s.recbuf[0].p, n_rec, (uint64_t*)s.rec_first.p, kNoRoute, n_hay, st)); }
-    HIP_TRY(hipMemsetAsync(s.lp_ctrl.p, 0, 128, st));
+      HIP_TRY(launch_rp_ranges(s.recbuf[0].get(), n_rec, ranges.get(), kNoRoute, n_hay, st)); }
+    HIP_TRY(hipMemsetAsync(s.lp_ctrl.get(), 0, 128, st));
     { Prof pr("rp_scans", st);
-      HIP_TRY(launch_rp_loop_caps((const uint64_t*)s.rec_first.p, n_hay, (uint32_t*)s.lp_cap_r.p, (uint32_t*)s.lp_cap_p.p, (uint32_t*)s.lp_ctrl.p + 6, st));
-      HIP_TRY(launch_scan(s.scan_tmp.p, t32, (const uint32_t*)s.lp_cap_r.p, (uint64_t*)s.lp_rec_base.p, n1, st));
-      HIP_TRY(launch_scan(s.scan_tmp.p, t32, (const uint32_t*)s.lp_cap_p.p, (uint64_t*)s.lp_pc_base.p, n1, st)); }
+      HIP_TRY(launch_rp_loop_caps(ranges.get(), n_hay, s.lp_cap_r.get(), s.lp_cap_p.get(), s.lp_ctrl.get() + 6, st));
+      HIP_TRY(launch_scan(s.scan_tmp.get(), t32, s.lp_cap_r.get(), s.lp_rec_base.get(), n1, st));
+      HIP_TRY(launch_scan(s.scan_tmp.get(), t32, s.lp_cap_p.get(), s.lp_pc_base.get(), n1, st)); }
     say("ranges + region sizes");
     if (sw != 1) {
         // a wavefront walks its haystack's whole record list in every pass: one document with very many matches would be the tail of the launch
         // (the pass-by-pass loop folds such lists in parallel over the records)
         AM_TRY(s.lp_host.ensure(64));
         uint32_t* c = (uint32_t*)s.lp_host.p;
-        HIP_TRY(hipMemcpyAsync(c, s.lp_ctrl.p, 64, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(c, s.lp_ctrl.get(), 64, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (c[6] > 4096u) return AM_OK;
     }
     RpLoop a{};
     a.t = r->t; a.s = make_sf_view(fl->d_image, fl->h);
     a.text = (const uint8_t*)in->d_text; a.offsets = in->d_offsets; a.n_hay = n_hay; a.ov = ov;
-    a.recs0 = (const Record*)s.recbuf[0].p; a.rec_first0 = (const uint64_t*)s.rec_first.p;
-    a.rec_buf = (Record*)s.lp_rec.p; a.rec_base = (const uint64_t*)s.lp_rec_base.p;
-    a.pc_buf = (RpPiece*)s.lp_pc.p; a.pc_base = (const uint64_t*)s.lp_pc_base.p;
-    a.kept_buf = (RpKept*)s.lp_kept.p; a.wtext = (uint8_t*)s.lp_wtext.p; a.wcap = (uint32_t)wcap64;
-    a.max_len = max_length; a.out = (RpLoopOut*)s.lp_out.p; a.ctrl = (uint32_t*)s.lp_ctrl.p;
+    a.recs0 = s.recbuf[0].get(); a.rec_first0 = ranges.get();
+    a.rec_buf = s.lp_rec.get(); a.rec_base = s.lp_rec_base.get();
+    a.pc_buf = s.lp_pc.get(); a.pc_base = s.lp_pc_base.get();
+    a.kept_buf = s.lp_kept.get(); a.wtext = s.lp_wtext.get(); a.wcap = (uint32_t)wcap64;
+    a.max_len = max_length; a.out = s.lp_out.get(); a.ctrl = s.lp_ctrl.get();
     a.pad = cfg::get(cfg::kRpTrace) >= 3 ? 1u : 0u;
     // k_rp_lds first: a haystack's lists in LDS for all its passes (am_rplds.hip); what does not fit there raises its redo flag and k_rp_loop, launched
     // right behind, runs exactly those haystacks (lists in global memory).  AM_RP_LDS=0 (A/B, tests), the instrumented instantiation and replacement
@@ -891,9 +914,9 @@ static int replacer_run_loop(const am_replacer* r, const am_batch* in, uint64_t 
     const bool use_lds = cfg::get(cfg::kRpLds) != 0 && r->n_repl_bytes < (1ull << 31);
     a.redo = nullptr; a.h_first = 0; a.pl_implicit = r->pl_implicit ? 1u : 0u;
     if (use_lds) {
-        AM_TRY(s.lp_redo.ensure((size_t)n_hay * 4 + 64));
-        HIP_TRY(hipMemsetAsync(s.lp_redo.p, 0, (size_t)n_hay * 4, st));
-        a.redo = (uint32_t*)s.lp_redo.p;
+        AM_TRY(s.lp_redo.room((size_t)n_hay + 16));
+        HIP_TRY(hipMemsetAsync(s.lp_redo.get(), 0, (size_t)n_hay * 4, st));
+        a.redo = s.lp_redo.get();
     }
     // Haystack GROUPS.  Results that stay on the device: one group, one launch.  Results that go to the host (Replacer.run :: Text -> Text returns host text;
     // a gibibyte takes 20 ms over PCIe, four times what the passes take): the batch is cut into up to eight groups of >= 2048 haystacks, every group's
@@ -911,7 +934,7 @@ static int replacer_run_loop(const am_replacer* r, const am_batch* in, uint64_t 
     RpFin* fin_h = (RpFin*)((uint8_t*)s.lp_host.p + 64 + out_bytes);
     uint64_t* fstart_h = (uint64_t*)(fin_h + n_hay);
     uint32_t* fcnt_h = (uint32_t*)(fstart_h + n_hay);
-    AM_TRY(s.lp_fin.ensure((size_t)n_hay * sizeof(RpFin))); AM_TRY(s.lp_fin_start.ensure((size_t)n_hay * 8)); AM_TRY(s.lp_fin_cnt.ensure((size_t)n_hay * 4));
+    AM_TRY(s.lp_fin.room(n_hay)); AM_TRY(s.lp_fin_start.room(n_hay)); AM_TRY(s.lp_fin_cnt.room(n_hay));
     struct Events {
         std::vector<hipEvent_t> ev;
         ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
@@ -924,8 +947,8 @@ static int replacer_run_loop(const am_replacer* r, const am_batch* in, uint64_t 
         a.h_first = h0;
         if (use_lds) { Prof pr("rp_lds", st); HIP_TRY(launch_rp_lds(r->case_mode == AM_IGNORE_CASE, a, h1 - h0, st)); }
         { Prof pr("rp_loop", st); HIP_TRY(launch_rp_loop(r->case_mode == AM_IGNORE_CASE, a, h1 - h0, st)); }
-        HIP_TRY(hipMemcpyAsync(out_h + h0, (const RpLoopOut*)s.lp_out.p + h0, (size_t)(h1 - h0) * sizeof(RpLoopOut), hipMemcpyDeviceToHost, st));
-        if (g + 1 == n_groups) HIP_TRY(hipMemcpyAsync(ctrl_h, s.lp_ctrl.p, 64, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out_h + h0, s.lp_out.get() + h0, (size_t)(h1 - h0) * sizeof(RpLoopOut), hipMemcpyDeviceToHost, st));
+        if (g + 1 == n_groups) HIP_TRY(hipMemcpyAsync(ctrl_h, s.lp_ctrl.get(), 64, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipEventCreateWithFlags(&done.ev[g], hipEventDisableTiming));
         HIP_TRY(hipEventRecord(done.ev[g], st));
     }
@@ -950,20 +973,20 @@ static int replacer_run_loop(const am_replacer* r, const am_batch* in, uint64_t 
         if (gave_up) break;
         hipStream_t ms = n_groups > 1 ? s.copy_stream : st;
         if (n_groups > 1) HIP_TRY(hipStreamWaitEvent(ms, done.ev[g], 0));
-        HIP_TRY(hipMemcpyAsync((RpFin*)s.lp_fin.p + h0, fin_h + h0, (size_t)(h1 - h0) * sizeof(RpFin), hipMemcpyHostToDevice, ms));
-        HIP_TRY(hipMemcpyAsync((uint64_t*)s.lp_fin_start.p + h0, fstart_h + h0, (size_t)(h1 - h0) * 8, hipMemcpyHostToDevice, ms));
-        HIP_TRY(hipMemcpyAsync((uint32_t*)s.lp_fin_cnt.p + h0, fcnt_h + h0, (size_t)(h1 - h0) * 4, hipMemcpyHostToDevice, ms));
+        HIP_TRY(hipMemcpyAsync(s.lp_fin.get() + h0, fin_h + h0, (size_t)(h1 - h0) * sizeof(RpFin), hipMemcpyHostToDevice, ms));
+        HIP_TRY(hipMemcpyAsync(s.lp_fin_start.get() + h0, fstart_h + h0, (size_t)(h1 - h0) * 8, hipMemcpyHostToDevice, ms));
+        HIP_TRY(hipMemcpyAsync(s.lp_fin_cnt.get() + h0, fcnt_h + h0, (size_t)(h1 - h0) * 4, hipMemcpyHostToDevice, ms));
         uint8_t* home = nullptr;
         if (total_fin) AM_TRY(res->room((size_t)total_fin, &home));
         home_of[g] = home;
         uint8_t* d_fin = home;
         if (res->dev < 0) {
-            DevBuf& sb = n_groups > 1 ? s.lp_stage[g] : s.fin_text;      // (the session keeps them: no allocation in the steady state)
-            AM_TRY(sb.ensure(total_fin + 16));
-            d_fin = (uint8_t*)sb.p;
+            DevArr<uint8_t>& sb = n_groups > 1 ? s.lp_stage[g] : s.fin_text;      // (the session keeps them: no allocation in the steady state)
+            AM_TRY(sb.room(total_fin + 16));
+            d_fin = sb.get();
         }
         { Prof pr("pt_materialise", ms);
-          HIP_TRY(launch_pt_materialise((const RpPiece*)s.lp_pc.p, (const uint64_t*)s.lp_fin_start.p + h0, (const uint32_t*)s.lp_fin_cnt.p + h0, (const RpFin*)s.lp_fin.p + h0, h1 - h0,
+          HIP_TRY(launch_pt_materialise(s.lp_pc.get(), s.lp_fin_start.get() + h0, s.lp_fin_cnt.get() + h0, s.lp_fin.get() + h0, h1 - h0,
                                         (const uint8_t*)in->d_text, r->t.repl, d_fin, ms)); }      // (an output-centred variant -- aligned 16-byte chunks, chunk -> piece map in LDS -- was measured in round 5: the same 0.98 ms per GiB)
         if (res->dev < 0 && total_fin) {
             // home in requests of 256 MiB (one huge request keeps the copy engine from overlapping with anything else queued behind it)
@@ -979,14 +1002,14 @@ static int replacer_run_loop(const am_replacer* r, const am_batch* in, uint64_t 
     if (n_groups > 1) HIP_TRY(hipStreamSynchronize(s.copy_stream));
     if (a.pad && use_lds) {
         uint64_t ph[10];
-        HIP_TRY(hipMemcpy(ph, (const uint8_t*)s.lp_ctrl.p + 32, 80, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ph, s.lp_ctrl.get() + 8, 80, hipMemcpyDeviceToHost));
         static const char* const names[9] = {"records in + fold", "select + payload", "overlap removal", "counts + dead slots", "piece list", "gather", "window scan", "inserts", "whole run"};
         for (int i = 0; i < 9; i++) std::fprintf(stderr, "[am_replacer lds] %-22s %14llu cycles = %5.1f %% of the wavefronts' time, %8.0f per pass\n", names[i], (unsigned long long)ph[i],
                                                  100.0 * (double)ph[i] / (double)(ph[8] ? ph[8] : 1), (double)ph[i] / (double)(ph[9] ? ph[9] : 1));
         std::fprintf(stderr, "[am_replacer lds] passes of all haystacks: %llu\n", (unsigned long long)ph[9]);
     } else if (a.pad) {
         uint64_t ph[8];
-        HIP_TRY(hipMemcpy(ph, (const uint8_t*)s.lp_ctrl.p + 32, 64, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ph, s.lp_ctrl.get() + 8, 64, hipMemcpyDeviceToHost));
         static const char* const names[7] = {"fold 1 (best priority)", "fold 2 (select, overlaps)", "pieces", "record copies + searches", "gather", "window scan", "whole run"};
         for (int i = 0; i < 7; i++) std::fprintf(stderr, "[am_replacer loop] %-26s %14llu cycles = %5.1f %% of the wavefronts' time, %8.0f per pass\n", names[i], (unsigned long long)ph[i],
                                                  100.0 * (double)ph[i] / (double)(ph[6] ? ph[6] : 1), (double)ph[i] / (double)(ph[7] ? ph[7] : 1));
@@ -1148,31 +1171,32 @@ extern "C" int am_run_priority(const am_replacer* r, const am_slice* hay, size_t
     hipStream_t st; AM_TRY(get_stream(b->dev, &st));
     const uint32_t n = (uint32_t)n_hay;
     const uint64_t n1 = (uint64_t)n + 1;
-    DevBuf records, rec_first, kept, hs, nk, off, thr, best, out, tmp;
+    DevArr<Record> records; DevArr<uint64_t> rec_first, off; DevArr<RpKept> kept; DevArr<RpHay> hs; DevArr<uint32_t> nk; DevArr<int64_t> thr, best; DevArr<RpSelected> out;
+    DevArr<uint8_t> tmp;
     uint64_t n_rec = 0;
     AM_TRY(run_records(r->a, r->case_mode, b, records_into(records), &n_rec));
-    AM_TRY(records.ensure(sizeof(Record)));
-    AM_TRY(rec_first.ensure(n1 * 8)); AM_TRY(kept.ensure((n_rec + 1) * sizeof(RpKept))); AM_TRY(hs.ensure(n1 * sizeof(RpHay)));
-    AM_TRY(nk.ensure(n1 * 4)); AM_TRY(off.ensure(n1 * 8)); AM_TRY(thr.ensure(n1 * 8)); AM_TRY(best.ensure(n1 * 8));
+    AM_TRY(records.room(1));
+    AM_TRY(rec_first.room(n1)); AM_TRY(kept.room(n_rec + 1)); AM_TRY(hs.room(n1));
+    AM_TRY(nk.room(n1)); AM_TRY(off.room(n1)); AM_TRY(thr.room(n1)); AM_TRY(best.room(n1));
     size_t tmp_bytes = 0;
     if (scan_temp_bytes(n1, &tmp_bytes) != hipSuccess) return fail(AM_ERR_HIP, "scan sizing failed");
-    AM_TRY(tmp.ensure(tmp_bytes + 16));
-    HIP_TRY(hipMemcpyAsync(thr.p, thresholds, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync((uint32_t*)nk.p + n, 0, 4, st));
-    RpRoute route{nullptr, nullptr, (uint32_t*)nk.p, nullptr, nullptr};
-    HIP_TRY(launch_rp_ranges((const Record*)records.p, n_rec, (uint64_t*)rec_first.p, kNoRoute, n, st));
-    HIP_TRY(launch_rp_pass(r->case_mode == AM_IGNORE_CASE, r->t, (const uint8_t*)b->d_text, b->d_offsets, (const Record*)records.p, (const uint64_t*)rec_first.p,
-                           (const int64_t*)thr.p, UINT64_MAX, (RpKept*)kept.p, (RpHay*)hs.p, route, n, 1u, st));
-    HIP_TRY(launch_scan(tmp.p, tmp_bytes, (const uint32_t*)nk.p, (uint64_t*)off.p, n1, st));
+    AM_TRY(tmp.room(tmp_bytes + 16));
+    HIP_TRY(hipMemcpyAsync(thr.get(), thresholds, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(nk.get() + n, 0, 4, st));
+    RpRoute route{nullptr, nullptr, nk.get(), nullptr, nullptr};
+    HIP_TRY(launch_rp_ranges(records.get(), n_rec, rec_first.get(), kNoRoute, n, st));
+    HIP_TRY(launch_rp_pass(r->case_mode == AM_IGNORE_CASE, r->t, (const uint8_t*)b->d_text, b->d_offsets, records.get(), rec_first.get(), thr.get(), UINT64_MAX, kept.get(), hs.get(),
+                           route, n, 1u, st));
+    HIP_TRY(launch_scan(tmp.get(), tmp_bytes, nk.get(), off.get(), n1, st));
     uint64_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, (uint64_t*)off.p + n, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&total, off.get() + n, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    AM_TRY(out.ensure((total + 1) * sizeof(RpSelected)));
-    HIP_TRY(launch_rp_gather((const RpHay*)hs.p, (const uint64_t*)rec_first.p, (const RpKept*)kept.p, (const uint64_t*)off.p, (RpSelected*)out.p, (int64_t*)best.p, n, st));
+    AM_TRY(out.room(total + 1));
+    HIP_TRY(launch_rp_gather(hs.get(), rec_first.get(), kept.get(), off.get(), out.get(), best.get(), n, st));
     am_prio_match* host = (am_prio_match*)std::malloc((total ? total : 1) * sizeof(am_prio_match));
     if (!host) return fail(AM_ERR_OOM, "malloc(matches) failed");
-    hipError_t e = hipMemcpyAsync(best_out, best.p, (size_t)n * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && total) e = hipMemcpyAsync(host, out.p, total * sizeof(am_prio_match), hipMemcpyDeviceToHost, st);
+    hipError_t e = hipMemcpyAsync(best_out, best.get(), (size_t)n * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && total) e = hipMemcpyAsync(host, out.get(), total * sizeof(am_prio_match), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { std::free(host); return fail(AM_ERR_HIP, hipGetErrorString(e)); }
     *matches_out = host; *n_matches_out = (size_t)total;
