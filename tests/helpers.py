@@ -1045,3 +1045,234 @@ def replacer_passes(case, pairs, text):
         if p == 1 - len(pairs):
             return text, scans
         threshold = p
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# The table walk's storage tiers (csrc/am_dfa.hip dfa_step): a mid-size automaton whose DFA section leaves LDS in every direction -- rows beyond the LDS rows, columns
+# beyond the LDS and the hot columns, records of both kinds beyond their LDS share, more than 16 384 states (k_dfa_place's 4-byte entries carry a tag), states with
+# 14, 15, 16 and more values (kDfaEndLookUp) -- and a plain walk of the section that says which tier answered every step.  tests/test_dfa_tiers_cpu.py holds the walk
+# to the oracle and the counts to floors; tests/test_gpu_dfa_tiers.py feeds the same automaton and text to k_dfa under every launch shape.
+
+DFA_TIER_ALPHABET = "abcdefghijklmnopqrstuvwxyz" + "ABCDEFGHIJKLMNOPQRSTUVWXYZ" + "0123456789" + " ,.-" + "яжщåßσ語💩"
+DFA_TIER_FILLER = "_\n"                # in no needle: class 0, the root from everywhere without a load
+DFA_TIER_RUN = "Qz" * 9                # its suffixes are needles: k code points into a run, k - 1 of them end (and "zQz" three times more)
+DFA_LDS_TWO_PER_CU = (512, 640, 640)   # (rows, single-entry records, two-entry records) a workgroup keeps in LDS, two workgroups per CU (am_dfa.hip:535-538 dfa_launch_shape)
+DFA_LDS_ONE_PER_CU = (1008, 2048, 1024)    # one workgroup per CU with all of its LDS (am_dfa.hip:535-538)
+DFA_LDS_COLS = 32                      # kLdsLog2Cols (am_dfa.hip:57): LDS holds columns 1 .. 32 of its rows
+DFA_END_LOOK_UP = 15                   # kDfaEndLookUp (am_image.h:197): end bits of a list of 15 values and more; the count then reads out[]
+DFA_PLACE_SLOTS = 8192                 # k_dfa_place's 4-byte entries (am_dfa.hip:465: slot = st & 8191, the rest is the tag)
+DFA_PLACE_MUL, DFA_PLACE_SHIFT = 0x9E3779B1, 20      # ... and its 8-byte entries (am_dfa.hip:469: 4 096 slots under a hash)
+DFA_SUPER_ROOM = 4096 - 1024           # kDfaSuper - kDfaSuperReserve (am_dfa.hip:52-53): tokens a superblock takes before its wavefront draws the next one
+DFA_TIERS = ("lds_rows", "lds_row_col_above_32", "hot", "cold", "single_lds", "single_global", "single_ahead", "two_lds", "two_global", "two_first", "two_second", "two_leans")
+
+
+def dfa_tier_needles(seed=0):
+    """6 000 random needles of 2-9 code points over DFA_TIER_ALPHABET (one to four bytes a code point, both cases of a-z), the 17 suffixes of DFA_TIER_RUN from 18 code
+    points down to 2, and "zQz" three times more: k code points into a run of QzQz..., k - 1 suffixes end (k <= 18) and from k = 3 on the three "zQz" too, so that a run
+    entered at Q reports 1, 6, 8, ... 14, 16, 18, 20 values and a run entered at z (a haystack cut after an odd number of its code points) 5, 7, ... 15, 17, 19:
+    14, 15 and 16 lie on both sides of kDfaEndLookUp.  CaseSensitive as they are; an IgnoreCase test lower-cases them as the other tests do."""
+    rng = random.Random("dfa-tiers-%d" % seed)
+    out = ["".join(rng.choice(DFA_TIER_ALPHABET) for _ in range(rng.randint(2, 9))) for _ in range(6000)]
+    return out + [DFA_TIER_RUN[i:] for i in range(17)] + ["zQz"] * 3
+
+
+def _dfa_upper(rng, s):
+    return "".join(c.upper() if (rng.random() < 0.25 and len(c.upper()) == 1) else c for c in s)
+
+
+def dfa_tier_text(needles, case, seed=0, n_bytes=256 << 10, runs_only=False):
+    """Ragged haystacks (bytes) of n_bytes in all.  A tile: every needle once -- whole (6 in 10), its last code point changed (2), cut in half (2) --, up to 6 code
+    points of filler (the alphabet and DFA_TIER_FILLER) after every other one, 16 runs of DFA_TIER_RUN of which 8 carry a haystack cut after their first 1, 2, 3 or 4 code points; all of it shuffled; under
+    IgnoreCase a code point in four upper-cased.  Tiles with fresh shuffles follow each other up to n_bytes.  The text is cut on code-point boundaries into haystacks
+    of (0, 0, 1, 5, 40, 300, 3 000, 20 000) bytes at most, and at every cut a run carries.  runs_only: a run (half of them cut) between any two other pieces, and
+    an eighth of the needles: a batch that consists mostly of runs split over haystack seams."""
+    rng = random.Random("dfa-tier-text-%d-%d-%d-%d" % (case, seed, n_bytes, runs_only))
+    alphabet = DFA_TIER_ALPHABET.lower() if case else DFA_TIER_ALPHABET
+    blob, forced = bytearray(), []
+    while len(blob) < n_bytes:
+        tile = []
+        for n in (needles[::8] if runs_only else needles):
+            r = rng.random()
+            s = n if r < 0.6 else n[:-1] + rng.choice(alphabet) if r < 0.8 else n[:len(n) // 2]
+            if rng.random() < 0.5:
+                s += "".join(rng.choice(alphabet + DFA_TIER_FILLER) for _ in range(rng.randint(0, 6)))
+            tile.append((s, None))
+        n_runs = len(tile) if runs_only else 16
+        tile += [(DFA_TIER_RUN, (1 + i // 2 % 4) if i % 2 else None) for i in range(n_runs)]
+        rng.shuffle(tile)
+        for s, cut in tile:
+            if case:
+                s = _dfa_upper(rng, s)
+            if cut is not None:
+                forced.append(len(blob) + len(s[:cut].encode("utf-8")))
+            blob += s.encode("utf-8")
+    end = n_bytes
+    while end > 0 and (blob[end] & 0xC0) == 0x80:
+        end -= 1
+    blob = bytes(blob[:end])
+    forced = [f for f in forced if f < end]
+    hays, p, k = [], 0, 0
+    while p < end:
+        size = rng.choice((0, 0, 1, 5, 40, 300, 3000, 20000))
+        q = min(p + size, end)
+        while q < end and q > p and (blob[q] & 0xC0) == 0x80:
+            q -= 1
+        if size and q == p:                                   # the code point at p is longer than the size drawn: all of it
+            q = p + 1
+            while q < end and (blob[q] & 0xC0) == 0x80:
+                q += 1
+        while k < len(forced) and forced[k] <= p:
+            k += 1
+        if k < len(forced) and forced[k] < q:
+            q = forced[k]
+        hays.append(blob[p:q])
+        p = q
+    return hays + [b"", b""]
+
+
+def dfa_tables(img):
+    """The DFA section of an image as arrays (layouts: am_image.h:84-94): next u32[n_rows << log2_classes], hot u32[n_rows << hot_log2], cls u8[256],
+    chain u32[n_single + 1][2], chain2 u32[n_states - n_rows - n_single][4], out u32[n_states][2]; "header" = ImgCheck.dfa_header."""
+    img = np.frombuffer(bytes(img), dtype=np.uint8)
+    h = ImgCheck.dfa_header(img)
+    n_two = h["n_states"] - h["n_rows"] - h["n_single"]
+    assert h["n_states"] >= 1 and n_two >= 0, h
+
+    def arr(off, count, dtype=np.uint32):
+        assert off % 4 == 0 and off + count * np.dtype(dtype).itemsize <= len(img), (off, count, len(img))
+        return np.frombuffer(img, dtype=dtype, count=count, offset=off)
+    return {"header": h, "next": arr(h["off_next"], h["n_rows"] << h["log2_classes"]), "hot": arr(h["off_hot"], h["n_rows"] << h["hot_log2"]),
+            "cls": arr(h["off_cls"], 256, np.uint8), "chain": arr(h["off_chain"], 2 * (h["n_single"] + 1)).reshape(-1, 2),
+            "chain2": arr(h["off_chain2"], 4 * n_two).reshape(-1, 4), "out": arr(h["off_out"], 2 * h["n_states"]).reshape(-1, 2)}
+
+
+def _alias_pairs(keys):
+    """pairs of distinct states that share a key"""
+    _, n = np.unique(np.asarray(keys, dtype=np.int64), return_counts=True)
+    return int((n * (n - 1) // 2).sum())
+
+
+def dfa_tier_census(img, batch, hot_rows, lds_n1, lds_n2, chunk):
+    """A plain walk of the DFA section over `batch` (a list of haystacks), haystack by haystack from the root, that follows dfa_common_step (am_image.h:1109-1126) for
+    the answer and dfa_step (am_dfa.hip:123-153) for the place the answer comes from, given what a workgroup keeps in LDS.  Returns
+      "tiers"        steps per tier (DFA_TIERS), and "class0", "single_answers", "single_leans" beside them
+      "ends"         [(haystack, end_pos)] of every step that ends something, in walk order;  "end_values": the length of each one's list
+      "seam_ends"    the ends of 14, 15 or 16 values that lie in another haystack than the one their unit (of `chunk` bytes) starts in
+      "groups"       per group of 64 units: {"records", "alias_low" (pairs of distinct end states equal modulo 8 192), "alias_hash" (equal under k_dfa_place's hash)}
+    Look-ahead: a single-entry record beyond lds_n1 is answered without a load exactly when the last record load from global memory was of the state before it,
+    single-entry as well, and nothing has used what it brought along since.  An image with rare bytes (a class of 0xFF) is refused: this walk has no dfa_rare_step."""
+    t = dfa_tables(img)
+    h = t["header"]
+    cls = t["cls"].tolist()
+    if 0xFF in cls:
+        raise ValueError("the image has bytes without a column (kDfaRare): dfa_tier_census does not walk them")
+    nxt, hot, out_y = t["next"].tolist(), t["hot"].tolist(), t["out"][:, 1].tolist()
+    chain, chain2 = t["chain"].tolist(), t["chain2"].tolist()
+    n_rows, n_single, l2c, hot_l2 = h["n_rows"], h["n_single"], h["log2_classes"], h["hot_log2"]
+    hot_cols = 1 << hot_l2
+    c = dict.fromkeys(DFA_TIERS + ("class0", "single_answers", "single_leans"), 0)
+    ends, end_values, end_states, end_global, seam_ends = [], [], [], [], []
+    starts = np.concatenate([[0], np.cumsum([len(x) for x in batch])]).astype(np.int64)
+    ahead = -1
+    for hi, hay in enumerate(batch):
+        state, base = 0, int(starts[hi])
+        for pos, byte in enumerate(bytes(hay)):
+            cl = cls[byte]
+            if cl == 0:
+                c["class0"] += 1
+                state = 0
+                continue
+            e = None
+            if state >= n_rows:
+                if state < n_rows + n_single:
+                    idx = state - n_rows
+                    if idx < lds_n1:
+                        c["single_lds"] += 1
+                    elif state == ahead:
+                        c["single_ahead"] += 1
+                        ahead = -1
+                    else:
+                        c["single_global"] += 1
+                        ahead = state + 1
+                    x, y = chain[idx]
+                    if (y >> 24) == cl:
+                        e = x
+                        c["single_answers"] += 1
+                    else:
+                        c["single_leans"] += 1
+                else:
+                    idx = state - n_rows - n_single
+                    c["two_lds" if idx < lds_n2 else "two_global"] += 1
+                    x, y, z, w = chain2[idx]
+                    if (y >> 24) == cl:
+                        e = x
+                        c["two_first"] += 1
+                    elif (w >> 24) == cl:
+                        e = z
+                        c["two_second"] += 1
+                    else:
+                        c["two_leans"] += 1
+                if e is None:
+                    state = y & 0xFFFFFF
+                    assert state < n_rows
+            if e is None:
+                if state < hot_rows and cl <= DFA_LDS_COLS:
+                    c["lds_rows"] += 1
+                elif cl <= hot_cols:
+                    c["hot"] += 1
+                else:
+                    c["cold"] += 1
+                    if state < hot_rows:
+                        c["lds_row_col_above_32"] += 1
+                e = hot[(state << hot_l2) + cl - 1] if cl <= hot_cols else nxt[(state << l2c) + cl]
+                if cl <= hot_cols:
+                    assert e == nxt[(state << l2c) + cl]
+            state = e & 0x0FFFFFFF
+            if e >> 28:
+                bits = e >> 28
+                vl = bits if bits < DFA_END_LOOK_UP else out_y[state]
+                assert vl >= bits
+                ends.append((hi, pos + 1)); end_values.append(vl); end_states.append(state); end_global.append(base + pos)
+                if 14 <= vl <= 16:
+                    unit_start = (base + pos) // chunk * chunk
+                    if int(np.searchsorted(starts, unit_start, side="right")) - 1 != hi and unit_start < base:
+                        seam_ends.append((hi, pos + 1, vl))
+    groups = []
+    g_of = np.asarray(end_global, dtype=np.int64) // (64 * chunk)
+    st = np.asarray(end_states, dtype=np.int64)
+    for g in range(int((starts[-1] + 64 * chunk - 1) // (64 * chunk))):
+        s = np.unique(st[g_of == g])
+        groups.append({"records": int((g_of == g).sum()), "alias_low": _alias_pairs(s % DFA_PLACE_SLOTS),
+                       "alias_hash": _alias_pairs(((s * DFA_PLACE_MUL) & 0xFFFFFFFF) >> DFA_PLACE_SHIFT)})
+    return {"tiers": c, "ends": ends, "end_values": end_values, "seam_ends": seam_ends, "groups": groups}
+
+
+def dfa_header_preconditions(img):
+    """What the image must be for the tier tests to say anything (asserted, never skipped): rows, records of both kinds and columns beyond every LDS share of both launch
+    shapes, more states than k_dfa_place's 4-byte entries tell apart by their slot, a state with 16 values or more.  Returns the figures."""
+    t = dfa_tables(img)
+    h = t["header"]
+    f = {"n_states": h["n_states"], "n_rows": h["n_rows"], "n_single": h["n_single"], "n_two": h["n_states"] - h["n_rows"] - h["n_single"],
+         "log2_classes": h["log2_classes"], "hot_log2": h["hot_log2"], "rare_bytes": int((t["cls"] == 0xFF).sum()), "max_values": int(t["out"][:, 1].max())}
+    assert f["n_rows"] >= 1100 and f["n_single"] >= 2200 and f["n_two"] >= 1100 and f["log2_classes"] >= 6 and f["n_states"] > 16384 and f["max_values"] >= 16, f
+    return f
+
+
+def dfa_census_floors(census):
+    """The floors of tests/test_dfa_tiers_cpu.py on one census: every tier at least 200 steps, ends of 14, 15 and 16 values at least 4 times each, at least 2 of them past a
+    haystack seam inside their unit."""
+    for tier in DFA_TIERS:
+        assert census["tiers"][tier] >= 200, (tier, census["tiers"])
+    for vl in (14, 15, 16):
+        assert census["end_values"].count(vl) >= 4, (vl, census["end_values"].count(vl))
+    assert len(census["seam_ends"]) >= 2, census["seam_ends"]
+
+
+def dfa_alias_groups(census):
+    """The groups of at most DFA_SUPER_ROOM records (their tokens fit one superblock).  Each must alias at least 10 pairs of distinct end states in either cache form, and
+    there must be 4 of them."""
+    small = [g for g in census["groups"] if g["records"] <= DFA_SUPER_ROOM]
+    assert len(small) >= 4, [g["records"] for g in census["groups"]]
+    for g in small:
+        assert g["alias_low"] >= 10 and g["alias_hash"] >= 10, census["groups"]
+    return small

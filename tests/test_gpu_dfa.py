@@ -95,10 +95,11 @@ def test_the_walks_variants_report_the_same_records(dfa_everywhere, tune):
         am.debug_set("AM_DFA_TUNE", -1)
 
 
-@pytest.mark.parametrize("chunk", [64, 256, 131072])
+@pytest.mark.parametrize("chunk", [64, 256, 8192, 8208, 131072])
 def test_unit_boundaries_inside_matches_and_code_points(dfa_everywhere, chunk):
     """Small units: every haystack is cut many times, inside needles, inside code points, inside the warm-up of the next unit; haystack boundaries
-    and empty haystacks fall inside units.  Units beyond 65 536 bytes (a token's fields are 16 bits): records by count -> scan -> emit, two walks."""
+    and empty haystacks fall inside units.  Units beyond 8 192 bytes (a token's fields are 13 bits, kTokMaxChunk): records by count -> scan -> emit, two walks;
+    8 192 is the last unit size that takes tokens, 8 208 the first that does not."""
     am.debug_set("AM_DFA_CHUNK", chunk)
     rng = random.Random(77 + chunk)
     for _ in range(6):
@@ -109,6 +110,45 @@ def test_unit_boundaries_inside_matches_and_code_points(dfa_everywhere, chunk):
         for case in (0, 1):
             ns = [oracle.lower_utf8(n).decode() for n in needles] if case else needles
             check_dfa_route(ns, hays, case)
+
+
+@pytest.mark.parametrize("chunk", [8192, 8208])
+def test_a_tokens_fields_at_their_last_value(dfa_everywhere, chunk):
+    """a, aa, aaa over 1 MiB of a: a record per byte, so the last token of a unit of 8 192 bytes carries offset 8 191 and seq 8 191, all 13 bits of both fields
+    (am_dfa.hip kTokPosBits); a unit of 8 208 bytes is beyond them and takes count -> scan -> emit.  Records: the oracle's on the first and the last 4 096 positions,
+    the suffix filter's everywhere.  One walk and k_dfa_place at 8 192 (the pool of the first attempt sized for a token per byte: the guess for a batch this small is a
+    token per 6 bytes, AM_SF_POOL_BLOCKS), two walks and no k_dfa_place at 8 208."""
+    am.debug_set("AM_DFA_CHUNK", chunk)
+    am.debug_set("AM_SF_POOL_BLOCKS", 1024)                  # 4 Mi tokens; every wavefront's superblocks and the 1 Mi tokens fit
+    n = 1 << 20
+    hays = [b"a" * n]
+    a, o = am.Automaton(["a", "aa", "aaa"]), oracle.Machine(["a", "aa", "aaa"])
+    lib = am.api.libam()
+    try:
+        a.set_kernel(3)
+        am.api.check(lib.am_profile_reset()); am.api.check(lib.am_profile_enable(1))
+        recs = a.run_records(0, hays)
+        am.api.check(lib.am_profile_enable(0))
+        ms, k = C.c_double(0), C.c_uint64(0)
+        am.api.check(lib.am_profile_read(b"dfa", C.byref(ms), C.byref(k)))
+        walks = k.value
+        am.api.check(lib.am_profile_read(b"dfa_place", C.byref(ms), C.byref(k)))
+        assert (walks, k.value) == ((1, 1) if chunk == 8192 else (2, 0))
+        a.set_kernel(2)
+        sf = a.run_records(0, hays)
+    finally:
+        am.debug_set("AM_SF_POOL_BLOCKS", -1)
+    assert len(recs) == n and np.array_equal(recs, sf)
+    assert np.array_equal(recs["end_pos"], np.arange(1, n + 1, dtype=np.uint64))
+    pos, val = o.run_list(0, hays[0][:4096])
+    exp = [(0, int(p), int(v)) for p, v in zip(pos, val)]
+    head = recs[:4096]
+    assert expand_records(o.values_off(), o.values(), head["haystack"], head["state"], head["end_pos"]) == exp
+    # (the text is one letter: what ends at position p >= 3 of the first 4 096 ends at every later one)
+    tail = recs[n - 4096:]
+    shifted = [(0, p + n - 4096, v) for _, p, v in exp if p >= 3]
+    assert expand_records(o.values_off(), o.values(), tail["haystack"], tail["state"], tail["end_pos"])[-len(shifted):] == shifted
+    assert len(set(tail["state"].tolist())) == 1
 
 
 def test_no_dfa_section_is_an_error_only_when_forced():
