@@ -962,10 +962,15 @@ int flatten(const RefArrays& ref, int case_mode, std::vector<uint8_t>& image, st
         uint32_t lw = log2_ceil((total_keys * 16 + 31) / 32);
         lw = std::max(8u, std::min(kSfMaxBloomLog2Words, lw));
         h.sf_bloom_log2_words = lw;
-        std::vector<uint32_t> bloom((size_t)1 << lw, 0);
+        // two filters of the same size over the same keys: off_bloom under the table masks, the scan filter (k_sf's LDS copy) under the rotated ones (scan_mask)
+        std::vector<uint32_t> bloom((size_t)1 << lw, 0), scan((size_t)1 << lw, 0);
         for (int t = 0; t < 4; t++)
-            for (const uint32_t key : fkeys[t]) { const uint32_t hh = bloom_hash(key, (uint32_t)t + 1); bloom[bloom_word(hh, lw)] |= bloom_mask(hh); }
+            for (const uint32_t key : fkeys[t]) {
+                const uint32_t hh = bloom_hash(key, (uint32_t)t + 1), m = bloom_mask(hh);
+                bloom[bloom_word(hh, lw)] |= m; scan[bloom_word(hh, lw)] |= rotr32(m, scan_rot(hh));
+            }
         h.off_bloom = blob.put(bloom);
+        h.off_scan_bloom = blob.put(scan);
     }
     for (int t = 0; t < 3; t++) {       // 1..3-byte needles: plain open addressing (rare)
         const uint32_t lc = std::max(4u, log2_ceil(tier_entries[t].size() * 2 + 1));
@@ -1433,7 +1438,7 @@ bool image_sections_in_bounds(const ImageHeader& h)
                 h.ac_goto_log2_cap >= 4 && h.ac_goto_log2_cap <= 31 && ok(h.off_goto, 1ull << h.ac_goto_log2_cap, 16) && ok(h.off_fail, h.n_states, 4);
     if (h.sf_enabled) {
         if (h.sf_bloom_log2_words > 20) return false;
-        good = good && ok(h.off_bloom, 1ull << h.sf_bloom_log2_words, 4) && ok(h.off_nodes, h.sf_n_nodes, 32) && ok(h.off_edges, h.n_edges, 64) && h.n_edge_maps == 0;
+        good = good && ok(h.off_bloom, 1ull << h.sf_bloom_log2_words, 4) && ok(h.off_scan_bloom, 1ull << h.sf_bloom_log2_words, 4) && (h.off_scan_bloom & 3u) == 0 && ok(h.off_nodes, h.sf_n_nodes, 32) && ok(h.off_edges, h.n_edges, 64) && h.n_edge_maps == 0;
         for (int t = 0; t < 4; t++) {
             if (!(h.sf_tiers & (1u << t))) continue;
             if (h.tier_log2_cap[t] > 30) return false;

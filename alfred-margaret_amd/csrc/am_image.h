@@ -34,7 +34,7 @@
 namespace am {
 
 constexpr uint32_t kImageMagic = 0x31474D41u;   // "AMG1"
-constexpr uint32_t kImageVersion = 18;
+constexpr uint32_t kImageVersion = 19;
 constexpr uint32_t kUnicodeLowerVersion = 0x0E00;   // Unicode 14.0 (major << 8 | minor): the simple-lowercase table baked into IgnoreCase images (ImageHeader::flags bits 0-15)
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint64_t kWildcard = 0x200000ull;     // Automaton.hs:130-131
@@ -92,6 +92,9 @@ struct ImageHeader {
     // (version 17) states [dfa_n_rows, dfa_n_rows + dfa_n_single) have a single-child record (off_dfa_chain), the rest a two-children record:
     uint32_t dfa_n_single;
     uint64_t off_dfa_chain2;    // u32x4[dfa_n_states - dfa_n_rows - dfa_n_single]: {target a | its end bits, class a << 24 | the row state R this one leans on, target b | its end bits, class b << 24}
+    // (version 19) the SCAN filter: the keys of off_bloom once more, each with its mask rotated by hash bits (scan_mask).  k_sf alone reads it; off_bloom keeps the
+    // unrotated rule for everything that tests a window against the filter in global memory (sf_filter_window)
+    uint64_t off_scan_bloom;    // u32[1 << sf_bloom_log2_words]
 };
 
 // Resolved pointers, passed to kernels by value (SGPRs).
@@ -163,6 +166,7 @@ constexpr uint32_t kSfKeyFold = 0x20u;                // SfView::tiers: the filt
 
 struct SfView {
     const uint32_t* bloom;
+    const uint32_t* scan_bloom;   // the same keys under the rotated masks (scan_mask): what k_sf copies into LDS
     const u32x2* tier[3];    // exact tables for needles (variants) of exactly 1, 2, 3 bytes
     // 4-byte suffixes: (2,2) cuckoo table.  A key lives in one of the 2 slots of bucket_a(key) or
     // bucket_b(key).  HOT side (what the probe reads, 8 B per bucket, ~1 MiB for 100k needles, so
@@ -239,6 +243,7 @@ inline SfView make_sf_view(const void* base, const ImageHeader& h)
     const uint8_t* b = (const uint8_t*)base;
     SfView v;
     v.bloom = (const uint32_t*)(b + h.off_bloom);
+    v.scan_bloom = (const uint32_t*)(b + h.off_scan_bloom);
     for (int t = 0; t < 3; t++) v.tier[t] = (const u32x2*)(b + h.off_tier[t]);
     v.t4_hot = (const u32x2*)(b + h.off_tier[3]);
     v.t4_slots = (const SfSlot*)(b + h.off_t4_slots);
@@ -329,6 +334,17 @@ AM_HD uint32_t bloom_mask_entry(uint32_t i)
 AM_HD uint32_t bloom_mask(uint32_t h, const uint32_t* tab = nullptr) { return tab ? tab[bloom_mask_index(h)] : bloom_mask_entry(bloom_mask_index(h)); }
 // true iff all mask bits of h are set in the filter word v
 AM_HD bool bloom_hit(uint32_t v, uint32_t h, const uint32_t* tab = nullptr) { const uint32_t m = bloom_mask(h, tab); return (v & m) == m; }
+// The SCAN filter's rule (image version 19, ImageHeader::off_scan_bloom): the table mask ROTATED RIGHT by product bits 11..15, which neither the word index
+// (the top log2_words <= 15 bits) nor the mask index (bits 2..10) uses -- 512 x 32 masks out of the same 2-KiB table.  With 512 masks a text window that
+// lands in the word of a key with the same mask passes outright, and at 3.4 keys per word that term is a large share of the false positives; mask index
+// bits 2..10 of a product depend on the window's oldest 11 bits alone, bits 11..15 bring five more in.  Counted on the CPU
+// (tools/experiments/filter_rotated_masks.py): 70.7 -> 62.5 positions pass per KiB of the 100k-needle workload's text, the bound of any 4-of-32 mask choice.
+// In the kernel: one shift and one v_alignbit_b32 per window (the instruction reads the low five bits of its shift operand), no LDS, no memory request.
+constexpr uint32_t kScanRotShift = 11;
+AM_HD uint32_t rotr32(uint32_t m, uint32_t r) { return (m >> r) | (m << ((32u - r) & 31u)); }      // r in 0..31; one v_alignbit_b32 on the device
+AM_HD uint32_t scan_rot(uint32_t h) { return (h >> kScanRotShift) & 31u; }
+AM_HD uint32_t scan_mask(uint32_t h, const uint32_t* tab = nullptr) { return rotr32(bloom_mask(h, tab), scan_rot(h)); }
+AM_HD bool scan_hit(uint32_t v, uint32_t h, const uint32_t* tab = nullptr) { const uint32_t m = scan_mask(h, tab); return (v & m) == m; }
 
 AM_HD uint32_t tier_slot(uint32_t key, uint32_t log2_cap) { return (key * 0x85EBCA6Bu) >> (32u - log2_cap); }
 
@@ -942,6 +958,8 @@ AM_HD bool sf_verify(const SfView& s, const uint8_t* text, uint64_t gpos, uint64
 // null.  The kernel's hot loop uses a batched form of the tier-4 test (all LDS reads of a lane in flight together) and
 // calls sf_filter_short only for automata that contain needles shorter than 4 bytes.
 // `tiers` = SfView::tiers: which tiers exist, and kSfKeyFold when the filter holds folded keys (bloom_key); `w` = the window, case-folded under IgnoreCase.
+// SCAN: `bloom` is the scan filter (rotated masks, scan_mask): k_sf's LDS copy; everything else tests off_bloom with the unrotated rule.
+template <bool SCAN = false>
 AM_HD bool sf_filter_short(const uint32_t* bloom, uint32_t log2_words, uint32_t tiers, uint32_t w, const uint32_t* masks = nullptr)
 {
     bool hit = false;
@@ -949,7 +967,8 @@ AM_HD bool sf_filter_short(const uint32_t* bloom, uint32_t log2_words, uint32_t 
     for (uint32_t t = 1; t <= 3; t++) {
         if (tiers & (1u << (t - 1))) {
             const uint32_t h = bloom_hash(w >> (8u * (4u - t)), t);
-            hit = hit || bloom_hit(bloom[bloom_word(h, log2_words)], h, masks);
+            const uint32_t v = bloom[bloom_word(h, log2_words)];
+            hit = hit || (SCAN ? scan_hit(v, h, masks) : bloom_hit(v, h, masks));
         }
     }
     return hit;

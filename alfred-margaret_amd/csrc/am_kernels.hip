@@ -72,8 +72,8 @@ constexpr uint32_t kSfEpochChunks = 16;          // the ring is drained every 16
 constexpr int kSfStage = 1056;                   // per-wave copy of the current chunk (folded): 8 bytes before it at offset 8, the chunk at 16, padding
 constexpr uint32_t kSfMaskBytes = kBloomMasks * 4u;      // the Bloom mask table: first thing in LDS, the filter words follow
 
-// ILP: 2 = a probe round always looks at two candidates per lane (up to 128 per round: automata with many needles, ~71 candidates per KiB on the
-// benchmark text -- 83 before the filter's keys were folded, image version 18); 1 = rounds of at most 64 candidates look at one per lane -- half the probe's instructions -- chosen for automata with a small
+// ILP: 2 = a probe round always looks at two candidates per lane (up to 128 per round: automata with many needles, ~62 candidates per KiB on the
+// benchmark text -- 71 before the masks were rotated, image version 19, 83 before the filter's keys were folded, image version 18); 1 = rounds of at most 64 candidates look at one per lane -- half the probe's instructions -- chosen for automata with a small
 // 4-byte-suffix table, which leave a handful of candidates per chunk (cfg2: +4.7 %; the same branches cost cfg3 1.5 %, hence two instantiations).
 //
 // Work unit = `unit_chunks` consecutive 1-KiB chunks.  A wavefront starts with unit (workgroup, wave) and draws every further
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
     uint16_t* q2_all = q1_all + kSfWaves * kSfQ1;
 
     for (uint32_t i = threadIdx.x; i < kBloomMasks; i += kSfThreads) masks[i] = bloom_mask_entry(i);
-    for (uint32_t i = threadIdx.x; i < words; i += kSfThreads) bloom[i] = s.bloom[i];
+    for (uint32_t i = threadIdx.x; i < words; i += kSfThreads) bloom[i] = s.scan_bloom[i];      // the scan filter: rotated masks (scan_mask, am_image.h)
     __syncthreads();
 
     const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // uniform: unit / chunk arithmetic stays scalar
@@ -641,14 +641,17 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
                     m[k] = lds_read_u32(h[k] & ((kBloomMasks - 1u) << 2));
                 }
 #pragma unroll
-                for (int k = 15; k >= 0; k--) cand = (cand << 1) | (uint32_t)((v[k] & m[k]) == m[k]);      // bit k of cand = position k
+                for (int k = 15; k >= 0; k--) {      // bit k of cand = position k; the table mask rotated by product bits 11..15 (scan_mask)
+                    const uint32_t mr = rotr32(m[k], scan_rot(h[k]));
+                    cand = (cand << 1) | (uint32_t)((v[k] & mr) == mr);
+                }
             }
             if (SHORT && (!kFlagMode || !skip)) {    // automata with 1..3-byte needles: extra probes per position
 #pragma unroll
                 for (int k = 0; k < 16; k++) {
                     const int j = k >> 2, sh = k & 3;
                     const uint32_t w = sh == 3 ? f[j + 1] : __builtin_amdgcn_alignbyte(f[j + 1], f[j], sh + 1);
-                    if (sf_filter_short(bloom, log2_words, tiers, w, masks)) cand |= 1u << k;
+                    if (sf_filter_short<true>(bloom, log2_words, tiers, w, masks)) cand |= 1u << k;
                 }
             }
             __builtin_amdgcn_s_setprio(2);
