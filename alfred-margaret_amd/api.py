@@ -108,6 +108,17 @@ ABI = {
     "am_spans_device_data": (_vp, [_vp]),
     "am_spans_rounds": (C.c_uint32, [_vp]),
     "am_spans_free": (None, [_vp]),
+    "am_subst_table_create": (C.c_int, [_vp, _vp, _vp, C.POINTER(_vp)]),
+    "am_subst_table_destroy": (None, [_vp]),
+    "am_batch_substitute": (C.c_int, [_vp, _vp, _vp, C.POINTER(_vp)]),
+    "am_substitute_batch": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "am_substitute": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, C.POINTER(_vp)]),
+    "am_substitute_geometry": (None, [_u32p, _u32p]),
+    "am_batch_haystacks": (C.c_uint64, [_vp]),
+    "am_batch_device_text": (_vp, [_vp]),
+    "am_batch_device_offsets": (_vp, [_vp]),
+    "am_batch_read_offsets": (C.c_int, [_vp, _vp]),
+    "am_batch_read_text": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp]),
     "am_needle_ids_create": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(_vp)]),
     "am_needle_ids_destroy": (None, [_vp]),
     "am_contains_all": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp]),
@@ -182,6 +193,8 @@ _HOST = {
     "amh_count_matrix": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _sz, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
     "amh_spans_fold": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
     "amh_spans": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(Slice), _sz, _vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
+    "amh_substitute_fold": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, C.POINTER(_vp), _vp]),
+    "amh_substitute": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, C.POINTER(_vp), _vp]),
     "amh_searcher_build": (C.c_int, [C.c_int, C.c_char_p, _vp, _sz, C.POINTER(_vp)]),
     "amh_searcher_free": (None, [_vp]),
     "amh_searcher_set_case": (None, [_vp, C.c_int]),
@@ -515,6 +528,57 @@ class Automaton:
                                     C.byref(po), C.byref(pe), C.byref(ne)))
         return _take_spans(po, pe, s.n, int(ne.value))
 
+    def substitute(self, case, texts, replacements):
+        """Every leftmost-longest match replaced once, replacements[v] for needle v, never scanned again (include/am.h "substitute"): a list of bytes, one per text.
+        am_substitute: scanned, selected and spliced in HBM."""
+        return SubstTable(SpanTable(self), replacements).substitute_texts(case, texts)
+
+    def substitute_host_mirror(self, case, texts, replacements, n_values=None, lengths=None):
+        """The same through the C++ host mirror (host/spans.hpp substitute over spansFold over the fold steps of amh_run_list)."""
+        lb, lc = _handle_lengths(self.needles, n_values, lengths)
+        nv = (len(self.needles) if lengths is None else len(lengths[0])) if n_values is None else int(n_values)
+        pool, offs = _pack_replacements(replacements, nv)
+        s = _Slices(texts)
+        blob, out_offs = _vp(), np.zeros(s.n + 1, np.uint64)
+        _hcheck(libhost().amh_substitute(self._h, case, s.arr, s.n, lb.ctypes.data, lc.ctypes.data, nv, pool, offs.ctypes.data, C.byref(blob), out_offs.ctypes.data))
+        return _take_texts(blob, out_offs)
+
+
+def _pack_replacements(replacements, n):
+    """(pool bytes, repl_off np.uint64[n + 1]) of am_subst_table_create for value handles 0 .. n - 1."""
+    bs = [_as_bytes(x) for x in replacements]
+    if len(bs) != n:
+        raise AmError(AM_ERR_INVALID, "replacements: one per value handle (%d given, %d handles)" % (len(bs), n))
+    pool, offs = pack_texts(bs)
+    return pool, offs
+
+
+def _take_texts(blob, offs):
+    """Copies and frees the blob a facade call hands back: a list of bytes per offsets row."""
+    try:
+        whole = C.string_at(blob.value, int(offs[-1])) if int(offs[-1]) else b""
+    finally:
+        libhost().amh_free_blob(blob)
+    return [whole[int(offs[i]):int(offs[i + 1])] for i in range(len(offs) - 1)]
+
+
+def substitute_fold_host(case, triples, texts, len_bytes, len_code_points, replacements):
+    """amh_substitute_fold: the sequential definition of am_substitute over fold steps the caller brings (as spans_fold_host).  Runs without a device."""
+    hay = np.ascontiguousarray(triples[0], dtype=np.uint32)
+    pos = np.ascontiguousarray(triples[1], dtype=np.uint64)
+    val = np.ascontiguousarray(triples[2], dtype=np.uint32)
+    lb = np.ascontiguousarray(len_bytes, dtype=np.uint32)
+    lc = np.ascontiguousarray(len_code_points, dtype=np.uint32)
+    n, nv = len(hay), len(lb)
+    pad = lambda a, t: a if a.size else np.zeros(1, t)
+    hay, pos, val, lb, lc = pad(hay, np.uint32), pad(pos, np.uint64), pad(val, np.uint32), pad(lb, np.uint32), pad(lc, np.uint32)
+    pool, offs = _pack_replacements(replacements, nv)
+    s = _Slices(texts)
+    blob, out_offs = _vp(), np.zeros(s.n + 1, np.uint64)
+    _hcheck(libhost().amh_substitute_fold(case, hay.ctypes.data, pos.ctypes.data, val.ctypes.data, n, s.arr, s.n, lb.ctypes.data, lc.ctypes.data, nv, pool,
+                                          offs.ctypes.data, C.byref(blob), out_offs.ctypes.data))
+    return _take_texts(blob, out_offs)
+
 
 def needle_lengths(needles, n_values=None):
     """(len_bytes, len_code_points) np.uint32 arrays of am_span_table_create for value handles 0 .. n - 1 = the needles in order (n = len(needles) unless given: fewer
@@ -676,6 +740,80 @@ class SpanTable:
         """am_spans: the one-shot form on host texts."""
         s = _Slices(texts)
         return self._spans(lambda out: libam().am_spans(self._h, case, mode, s.arr, s.n, out), False)
+
+
+def substitute_geometry():
+    """(group_bytes, tile_bytes) of the splice's gather (am_substitute_geometry)."""
+    g, t = C.c_uint32(0), C.c_uint32(0)
+    libam().am_substitute_geometry(C.byref(g), C.byref(t))
+    return int(g.value), int(t.value)
+
+
+def batch_offsets(batch):
+    """The n_hay + 1 byte offsets of an am_batch* handle (am_batch_read_offsets)."""
+    n = int(libam().am_batch_haystacks(batch))
+    offs = np.zeros(n + 1, np.uint64)
+    check(libam().am_batch_read_offsets(batch, offs.ctypes.data))
+    return offs
+
+
+def batch_read_text(batch, first, n):
+    """Bytes [first, first + n) of the concatenated text of an am_batch* handle (am_batch_read_text)."""
+    buf = C.create_string_buffer(max(int(n), 1))
+    check(libam().am_batch_read_text(batch, int(first), int(n), buf))
+    return buf.raw[:int(n)]
+
+
+def batch_to_bytes(batch):
+    """(offsets np.uint64[n_hay + 1], [bytes per haystack]) of an am_batch* handle, through the batch accessors."""
+    offs = batch_offsets(batch)
+    whole = batch_read_text(batch, 0, int(offs[-1]))
+    return offs, [whole[int(offs[i]):int(offs[i + 1])] for i in range(len(offs) - 1)]
+
+
+class SubstTable:
+    """The replacements beside a SpanTable on the device (am_subst_table): replacements[v] = the bytes that replace a match of value handle v."""
+
+    def __init__(self, span_table, replacements):
+        self._t = span_table                                 # (the am_span_table must outlive the table)
+        self.n_needles = span_table.n_needles
+        self._pool, self._off = _pack_replacements(replacements, self.n_needles)
+        h = _vp()
+        check(libam().am_subst_table_create(span_table.handle, self._off.ctypes.data, self._pool or None, C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            libam().am_subst_table_destroy(self._h)
+            self._h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    def _texts(self, call, raw):
+        b = _vp()
+        check(call(C.byref(b)))
+        if raw:
+            return b
+        try:
+            return batch_to_bytes(b)[1]
+        finally:
+            libam().am_batch_destroy(b)
+
+    def substitute_batch(self, case, batch, raw=False):
+        """am_substitute_batch on a device-resident batch (an am_batch* handle): the rewritten texts as a list of bytes.  raw: the new am_batch* itself, in HBM
+        (the next device stage takes it; free with am_batch_destroy)."""
+        return self._texts(lambda out: libam().am_substitute_batch(self._h, case, batch, out, None), raw)
+
+    def substitute_texts(self, case, texts):
+        """am_substitute: the one-shot form on host texts, a list of bytes."""
+        s = _Slices(texts)
+        return self._texts(lambda out: libam().am_substitute(self._h, case, s.arr, s.n, out), False)
+
+    def splice(self, batch, spans_raw, raw=False):
+        """am_batch_substitute: the splice alone over an am_spans* the caller holds (SpanTable.spans_batch(..., SPANS_LEFTMOST_LONGEST, raw=True) on `batch`)."""
+        return self._texts(lambda out: libam().am_batch_substitute(batch, spans_raw, self._h, out), raw)
 
 
 class ImageAutomaton:

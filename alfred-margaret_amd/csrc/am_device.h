@@ -222,6 +222,23 @@ hipError_t launch_spans_walk(const uint64_t* cand_g, const uint64_t* best, uint6
 hipError_t launch_spans_next(const uint64_t* cand_g, const uint64_t* best, uint64_t n_cand, const uint8_t* head, uint64_t* jump, hipStream_t st);
 hipError_t launch_spans_emit(const uint64_t* cand_g, const uint64_t* best, const uint32_t* kept, const uint64_t* kidx, uint64_t n_cand, const SpansIn& in, Span* out, uint64_t n_out,
                              uint64_t* span_off, hipStream_t st);
+// substitute (am_subst.hip): the leftmost-longest spans of a batch spliced into a new text.  P = 2 * n_span + n_hay pieces: span j of haystack h owns 2j + h (the gap
+// before it) and 2j + h + 1 (its replacement), 2 * span_off[h + 1] + h is the tail of h
+constexpr uint64_t kSubstRepl = 1ull << 63;                 // a piece's source: offset into the replacement pool instead of the batch text
+struct SubstIn {
+    const Span* spans; uint64_t n_span; const uint64_t* span_off;       // an AM_SPANS_LEFTMOST_LONGEST result of the batch below
+    const uint64_t* src_off; uint64_t src_total; uint32_t n_hay, n_needles;
+    const uint64_t* repl_off; uint64_t pool_bytes;           // replacement of handle v: pool[repl_off[v], repl_off[v + 1])
+};
+void subst_geometry(uint32_t* group_bytes, uint32_t* tile_bytes);      // k_subst_gather's store group and tile
+// lens / src_at / live: P + 1 entries each, zero before (the last ones stay 0: the scans' trailing element); then, with dst_at = exclusive sum of lens (total = dst_at[P])
+// and cidx = exclusive sum of live (n_live = cidx[P]): the live pieces as cdst / csrc (n_live + 1 entries, the last one the sentinel `total`) and out_off (n_hay + 1);
+// then the bytes (dst: readable and writable to round_up(total, 16))
+hipError_t launch_subst_pieces(const SubstIn& in, uint64_t* lens, uint64_t* src_at, uint32_t* live, hipStream_t st);
+hipError_t launch_subst_compact(const uint64_t* src_at, const uint32_t* live, const uint64_t* dst_at, const uint64_t* cidx, uint64_t n_pieces, uint64_t* cdst, uint64_t* csrc,
+                                uint64_t n_live, const uint64_t* span_off, uint64_t n_span, uint64_t n_hay, uint64_t* out_off, hipStream_t st);
+hipError_t launch_subst_gather(const uint8_t* text, uint64_t src_total, const uint8_t* pool, uint64_t pool_bytes, const uint64_t* cdst, const uint64_t* csrc, uint64_t n_live,
+                               uint64_t total, uint8_t* dst, int n_cu, hipStream_t st);
 // incremental re-scan between Replacer passes (am_replace.hip)
 struct RpWin { uint64_t src_abs; uint64_t ws; uint32_t len; uint32_t own_lo; };   // window: bytes src_abs.. of the next text; ws = its start inside the haystack; records with end > own_lo are its own
 hipError_t launch_rp_win_count(const RpHay* hs, uint32_t n_act, uint32_t* nwin, hipStream_t st);

@@ -2,22 +2,13 @@
 // lists and the needles' own lengths into (start, len, haystack, needle), all of them in fold order or the leftmost-longest non-overlapping selection
 // (am_spans.hip).  The result is CSR like am_fragments and stays in HBM until asked for: its handle, the finisher of long chains and the argument checks are
 // am_fold.h's, shared with the other folds.
-#include "am_host.h"
+#include "am_spans.h"
 
 #include <cstddef>
 
 using namespace am;
 using namespace am::dev;
 using namespace am::host;
-
-struct am_span_table {
-    const am_needle_ids* ids = nullptr;
-    DevBuf len_bytes, len_cps;                              // uint32[n_needles] each, on the automaton's device
-};
-
-struct am_spans : CsrResult<am_span> {
-    uint32_t rounds = 0;                                    // pointer-doubling rounds of the call
-};
 
 using SpansResult = struct am_spans;                     // (am_spans alone names the one-shot entry point)
 
@@ -32,6 +23,14 @@ int check_modes(int case_mode, int mode)
 {
     AM_TRY(check_case(case_mode));
     if (mode != AM_SPANS_ALL && mode != AM_SPANS_LEFTMOST_LONGEST) return fail(AM_ERR_INVALID, "mode must be AM_SPANS_ALL or AM_SPANS_LEFTMOST_LONGEST");
+    return AM_OK;
+}
+
+// the result of a call without haystacks
+int empty_spans(int dev, int mode, uint32_t n_needles, SpansResult** out)
+{
+    AM_TRY(empty_result(dev, out));
+    (*out)->mode = mode; (*out)->n_needles = n_needles;
     return AM_OK;
 }
 
@@ -140,9 +139,10 @@ extern "C" int am_spans_batch(const am_span_table* t, int case_mode, int mode, c
     if (ids->a->dev != cb->dev) return fail(AM_ERR_INVALID, "span table and batch live on different devices");
     AM_TRY(ensure_runtime());
     am_batch* b = const_cast<am_batch*>(cb);
-    if (b->n_hay == 0) return empty_result(b->dev, out);
+    if (b->n_hay == 0) return empty_spans(b->dev, mode, ids->n_needles, out);
     std::unique_ptr<SpansResult, void (*)(SpansResult*)> s(new SpansResult(), am_spans_free);
     s->dev = b->dev; s->n_hay = b->n_hay;
+    s->mode = mode; s->n_needles = ids->n_needles; s->src_total = b->total;
     ON_DEVICE(b->dev);
     hipStream_t st; AM_TRY(get_stream(b->dev, &st));
     RecordArray ra(b->dev);
@@ -191,7 +191,7 @@ extern "C" int am_spans(const am_span_table* t, int case_mode, int mode, const a
     if (!t) return fail(AM_ERR_INVALID, "null span table");      // (last: a caller without a device can see every other check)
     AM_TRY(ensure_runtime());
     const int dev = t->ids->a->dev;
-    if (n_hay == 0) return empty_result(dev, out);
+    if (n_hay == 0) return empty_spans(dev, mode, t->ids->n_needles, out);
     ON_DEVICE(dev);
     am_batch* b = oneshot_batch(dev);                       // this thread's batch on the automaton's device
     int rc = upload_batch(hay, n_hay, b, true);

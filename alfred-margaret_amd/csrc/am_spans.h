@@ -1,0 +1,16 @@
+// am_spans.h -- the two handles of include/am.h "match spans" that am_spans.cpp makes and am_subst.cpp reads: the needles' lengths beside machineValues, and the
+// CSR result of a spans call with what the splice checks it against.  Internal: nothing here is part of the C ABI.
+#pragma once
+#include "am_host.h"
+
+struct am_span_table {
+    const am_needle_ids* ids = nullptr;
+    am::host::DevBuf len_bytes, len_cps;                    // uint32[n_needles] each, on the automaton's device
+};
+
+struct am_spans : am::host::CsrResult<am_span> {
+    uint32_t rounds = 0;                                    // pointer-doubling rounds of the call
+    int mode = AM_SPANS_ALL;                                // what am_batch_substitute holds a result to: the selection, the table's handles and the batch it was made from
+    uint32_t n_needles = 0;
+    uint64_t src_total = 0;
+};

@@ -1,0 +1,225 @@
+// am_subst.cpp -- substitute on the device (include/am.h "substitute"): the leftmost-longest spans of a batch (am_spans.cpp) spliced with the replacements of their
+// needles into a NEW batch in HBM (am_subst.hip), `replace :: [Match] -> Text -> Text` of the reference (src/Data/Text/AhoCorasick/Replacer.hs:163-180) over matches
+// that are never scanned again.  am_batch_substitute is the splice alone -- to am_spans what am_batch_from_fragments is to am_fragments -- and am_substitute_batch /
+// am_substitute put the spans call in front of it.  Every argument is checked before any device work.
+#include "am_spans.h"
+
+using namespace am;
+using namespace am::dev;
+using namespace am::host;
+
+struct am_subst_table {
+    const am_span_table* t = nullptr;
+    int dev = 0;
+    uint32_t n_needles = 0;
+    uint64_t pool_bytes = 0;
+    DevBuf off, pool;                                       // uint64[n_needles + 1]; the replacements' bytes, padded: a 16-byte group read from any offset stays inside
+};
+
+namespace {
+
+constexpr size_t kPoolPad = 32;
+
+using BatchPtr = std::unique_ptr<am_batch, void (*)(am_batch*)>;
+
+// a batch of the library's own without haystacks: offsets = [0], one group of zeros
+int empty_batch(int dev, am_batch** out)
+{
+    ON_DEVICE(dev);
+    hipStream_t st; AM_TRY(get_stream(dev, &st));
+    BatchPtr nb(new am_batch(), am_batch_destroy);
+    nb->dev = dev; nb->owns = true;
+    AM_TRY(nb->offs_buf.ensure(8));
+    AM_TRY(nb->text_buf.ensure(padded_text(0)));
+    HIP_TRY(hipMemsetAsync(nb->offs_buf.p, 0, 8, st));
+    HIP_TRY(hipMemsetAsync(nb->text_buf.p, 0, padded_text(0), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    nb->d_text = nb->text_buf.p; nb->d_offsets = (uint64_t*)nb->offs_buf.p;
+    AM_TRY(finish_batch(nb.get()));
+    *out = nb.release();
+    return AM_OK;
+}
+
+int check_splice(const am_batch* src, const struct am_spans* s, const am_subst_table* r)
+{
+    if (!src || !s || !r) return fail(AM_ERR_INVALID, "null batch, spans or substitution table");
+    if (s->mode != AM_SPANS_LEFTMOST_LONGEST) return fail(AM_ERR_INVALID, "am_batch_substitute: the spans are not an AM_SPANS_LEFTMOST_LONGEST result (overlapping spans cannot be spliced)");
+    if (s->n_hay != src->n_hay || s->src_total != src->total) return fail(AM_ERR_INVALID, "the spans were not produced from a batch with this haystack count and size");
+    if (s->dev != src->dev || r->dev != src->dev) return fail(AM_ERR_INVALID, "batch, spans and substitution table live on different devices");
+    if (r->n_needles != s->n_needles) return fail(AM_ERR_INVALID, "the substitution table's n_needles differs from that of the span table the spans were made with");
+    return AM_OK;
+}
+
+// the splice; every argument has been checked
+int splice(const am_batch* src, const struct am_spans* s, const am_subst_table* r, am_batch** out)
+{
+    AM_TRY(ensure_runtime());
+    if (src->n_hay == 0) return empty_batch(src->dev, out);
+    ON_DEVICE(src->dev);
+    hipStream_t st; AM_TRY(get_stream(src->dev, &st));
+    BatchPtr nb(new am_batch(), am_batch_destroy);
+    nb->dev = src->dev; nb->owns = true;
+    const uint64_t n_span = s->n_items, n_hay = src->n_hay, n_pieces = 2 * n_span + n_hay;
+    SubstIn in;
+    in.spans = (const Span*)s->data.p; in.n_span = n_span; in.span_off = (const uint64_t*)s->offsets.p;
+    in.src_off = src->d_offsets; in.src_total = src->total; in.n_hay = src->n_hay; in.n_needles = r->n_needles;
+    in.repl_off = (const uint64_t*)r->off.p; in.pool_bytes = r->pool_bytes;
+    DevBuf lens, src_at, live, dst_at, cidx, cdst, csrc, scan_tmp;
+    AM_TRY(lens.ensure((n_pieces + 1) * 8));
+    AM_TRY(src_at.ensure((n_pieces + 1) * 8));
+    AM_TRY(live.ensure((n_pieces + 1) * 4));
+    AM_TRY(dst_at.ensure((n_pieces + 1) * 8));
+    AM_TRY(cidx.ensure((n_pieces + 1) * 8));
+    AM_TRY(nb->offs_buf.ensure((n_hay + 1) * 8));
+    size_t tmp_bytes = 0;
+    HIP_TRY(scan64_temp_bytes(n_pieces + 1, &tmp_bytes));
+    AM_TRY(scan_tmp.ensure(tmp_bytes));
+    HIP_TRY(hipMemsetAsync(lens.p, 0, (n_pieces + 1) * 8, st));
+    HIP_TRY(hipMemsetAsync(live.p, 0, (n_pieces + 1) * 4, st));
+    { Prof pr("subst_pieces", st);
+      HIP_TRY(launch_subst_pieces(in, (uint64_t*)lens.p, (uint64_t*)src_at.p, (uint32_t*)live.p, st)); }
+    { Prof pr("subst_scan", st);
+      HIP_TRY(launch_scan64(scan_tmp.p, scan_tmp.cap, (const uint64_t*)lens.p, (uint64_t*)dst_at.p, n_pieces + 1, st));
+      HIP_TRY(launch_scan(scan_tmp.p, scan_tmp.cap, (const uint32_t*)live.p, (uint64_t*)cidx.p, n_pieces + 1, st)); }
+    uint64_t total = 0, n_live = 0;
+    HIP_TRY(hipMemcpyAsync(&total, (const uint64_t*)dst_at.p + n_pieces, 8, hipMemcpyDeviceToHost, st));
+    AM_TRY(read_u64((const uint64_t*)cidx.p + n_pieces, &n_live, st));
+    AM_TRY(cdst.ensure((n_live + 1) * 8));
+    AM_TRY(csrc.ensure((n_live + 1) * 8));
+    const size_t padded = padded_text(total);
+    AM_TRY(nb->text_buf.ensure(padded));
+    { Prof pr("subst_compact", st);
+      HIP_TRY(launch_subst_compact((const uint64_t*)src_at.p, (const uint32_t*)live.p, (const uint64_t*)dst_at.p, (const uint64_t*)cidx.p, n_pieces, (uint64_t*)cdst.p,
+                                   (uint64_t*)csrc.p, n_live, in.span_off, n_span, n_hay, (uint64_t*)nb->offs_buf.p, st)); }
+    const uint64_t whole = total & ~15ull;
+    HIP_TRY(hipMemsetAsync((uint8_t*)nb->text_buf.p + whole, 0, padded - whole, st));            // zero tail: kernels read whole 16-byte groups
+    { Prof pr("subst_gather", st);
+      HIP_TRY(launch_subst_gather((const uint8_t*)src->d_text, src->total, (const uint8_t*)r->pool.p, r->pool_bytes, (const uint64_t*)cdst.p, (const uint64_t*)csrc.p, n_live,
+                                  total, (uint8_t*)nb->text_buf.p, g_rt.dev[src->dev].n_cu, st)); }
+    HIP_TRY(hipStreamSynchronize(st));                      // a batch object may be used from any thread and stream afterwards; the workspaces are freed
+    nb->d_text = nb->text_buf.p; nb->d_offsets = (uint64_t*)nb->offs_buf.p;
+    nb->total = total; nb->n_hay = src->n_hay;
+    AM_TRY(finish_batch(nb.get()));
+    *out = nb.release();
+    return AM_OK;
+}
+
+}  // namespace
+
+extern "C" int am_subst_table_create(const am_span_table* t, const uint64_t* repl_off, const uint8_t* repl_bytes, am_subst_table** out)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    if (!t || !repl_off) return fail(AM_ERR_INVALID, "null span table or repl_off");
+    const uint32_t n = t->ids->n_needles;
+    if (repl_off[0] != 0) return fail(AM_ERR_INVALID, "am_subst_table_create: repl_off[0] must be 0");
+    for (uint32_t v = 0; v < n; v++) {
+        if (repl_off[v + 1] < repl_off[v]) return fail(AM_ERR_INVALID, "am_subst_table_create: repl_off descends at needle " + std::to_string(v));
+        if (repl_off[v + 1] - repl_off[v] >= (1ull << 32)) return fail(AM_ERR_INVALID, "am_subst_table_create: a replacement of 2^32 bytes and more (needle " + std::to_string(v) + ")");
+    }
+    const uint64_t pool_bytes = repl_off[n];
+    if (pool_bytes && !repl_bytes) return fail(AM_ERR_INVALID, "repl_bytes is null");
+    AM_TRY(ensure_runtime());
+    const int dev = t->ids->a->dev;
+    ON_DEVICE(dev);
+    std::unique_ptr<am_subst_table> r(new am_subst_table());
+    r->t = t; r->dev = dev; r->n_needles = n; r->pool_bytes = pool_bytes;
+    const size_t padded = (size_t)((pool_bytes + 15) & ~15ull) + kPoolPad;
+    AM_TRY(r->off.ensure(((size_t)n + 1) * 8));
+    AM_TRY(r->pool.ensure(padded));
+    HIP_TRY(hipMemset(r->pool.p, 0, padded));
+    HIP_TRY(hipMemcpy(r->off.p, repl_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
+    if (pool_bytes) HIP_TRY(hipMemcpy(r->pool.p, repl_bytes, (size_t)pool_bytes, hipMemcpyHostToDevice));
+    *out = r.release();
+    return AM_OK;
+}
+
+extern "C" void am_subst_table_destroy(am_subst_table* r)
+{
+    if (!r) return;
+    OnDevice od(r->dev);
+    delete r;
+}
+
+extern "C" int am_batch_substitute(const am_batch* src, const struct am_spans* s, const am_subst_table* r, am_batch** out)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    AM_TRY(check_splice(src, s, r));
+    return splice(src, s, r, out);
+}
+
+extern "C" int am_substitute_batch(const am_subst_table* r, int case_mode, const am_batch* b, am_batch** out, struct am_spans** spans_out)
+{
+    if (spans_out) *spans_out = nullptr;
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    AM_TRY(check_case(case_mode));
+    if (!r || !b) return fail(AM_ERR_INVALID, "null substitution table or batch");
+    if (r->dev != b->dev) return fail(AM_ERR_INVALID, "substitution table and batch live on different devices");
+    struct am_spans* raw = nullptr;
+    AM_TRY(am_spans_batch(r->t, case_mode, AM_SPANS_LEFTMOST_LONGEST, b, &raw));
+    std::unique_ptr<struct am_spans, void (*)(struct am_spans*)> s(raw, am_spans_free);
+    AM_TRY(check_splice(b, s.get(), r));
+    AM_TRY(splice(b, s.get(), r, out));
+    if (spans_out) *spans_out = s.release();
+    return AM_OK;
+}
+
+extern "C" int am_substitute(const am_subst_table* r, int case_mode, const am_slice* hay, size_t n_hay, am_batch** out)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    AM_TRY(check_slices(hay, n_hay));
+    AM_TRY(check_case(case_mode));
+    if (!r) return fail(AM_ERR_INVALID, "null substitution table");      // (last: a caller without a device can see every other check)
+    AM_TRY(ensure_runtime());
+    if (n_hay == 0) return empty_batch(r->dev, out);
+    ON_DEVICE(r->dev);
+    am_batch* b = oneshot_batch(r->dev);                    // this thread's batch on the table's device; the result is a batch of its own
+    int rc = upload_batch(hay, n_hay, b, true);
+    if (rc == AM_OK) rc = am_substitute_batch(r, case_mode, b, out, nullptr);
+    oneshot_batch_trim(r->dev);
+    return rc;
+}
+
+extern "C" void am_substitute_geometry(uint32_t* group_bytes, uint32_t* tile_bytes)
+{
+    uint32_t g = 0, t = 0;
+    subst_geometry(&g, &t);
+    if (group_bytes) *group_bytes = g;
+    if (tile_bytes) *tile_bytes = t;
+}
+
+// ---- batch accessors: what a device stage that PRODUCES text hands back
+
+extern "C" uint64_t am_batch_haystacks(const am_batch* b) { return b ? b->n_hay : 0; }
+extern "C" const void* am_batch_device_text(const am_batch* b) { return b ? b->d_text : nullptr; }
+extern "C" const void* am_batch_device_offsets(const am_batch* b) { return b ? b->d_offsets : nullptr; }
+
+namespace {
+int read_back(const am_batch* b, void* dst, const void* d_src, size_t n)
+{
+    AM_TRY(ensure_runtime());
+    ON_DEVICE(b->dev);
+    hipStream_t st; AM_TRY(get_stream(b->dev, &st));        // (a one-shot upload of this thread may still be on its way on that stream)
+    HIP_TRY(hipMemcpyAsync(dst, d_src, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return AM_OK;
+}
+}  // namespace
+
+extern "C" int am_batch_read_offsets(const am_batch* b, uint64_t* out)
+{
+    if (!b || !out) return fail(AM_ERR_INVALID, "null batch or out");
+    return read_back(b, out, b->d_offsets, ((size_t)b->n_hay + 1) * 8);
+}
+
+extern "C" int am_batch_read_text(const am_batch* b, uint64_t first_byte, uint64_t n_bytes, uint8_t* dst)
+{
+    if (!b) return fail(AM_ERR_INVALID, "null batch");
+    if (first_byte > b->total || n_bytes > b->total - first_byte) return fail(AM_ERR_INVALID, "am_batch_read_text: the range ends beyond the batch's total bytes");
+    if (n_bytes == 0) return AM_OK;
+    if (!dst) return fail(AM_ERR_INVALID, "dst is null");
+    return read_back(b, dst, (const uint8_t*)b->d_text + first_byte, (size_t)n_bytes);
+}

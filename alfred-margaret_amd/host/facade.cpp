@@ -159,6 +159,56 @@ int amh_spans(void* h, int case_mode, int mode, const am_slice* hay, size_t n_ha
     });
 }
 
+// ---- substitute (spans.hpp): the leftmost-longest spans spliced with replacement v = repl_bytes[repl_off[v], repl_off[v + 1]); the texts come back as one malloc'd blob
+// (amh_free_blob) + offsets (n_hay + 1, the caller's)
+namespace {
+void substituteOut(const Spans& sp, const std::vector<Text>& texts, const uint8_t* repl_bytes, const uint64_t* repl_off, size_t n_values, uint8_t** blob_out, uint64_t* offs_out)
+{
+    std::vector<std::string> repl(n_values);
+    for (size_t v = 0; v < n_values; v++) if (repl_off[v + 1] > repl_off[v]) repl[v].assign((const char*)repl_bytes + repl_off[v], (size_t)(repl_off[v + 1] - repl_off[v]));
+    const std::vector<std::string> res = substitute(sp, texts, repl);
+    uint64_t total = 0;
+    for (size_t i = 0; i < res.size(); i++) { offs_out[i] = total; total += res[i].size(); }
+    offs_out[res.size()] = total;
+    uint8_t* blob = (uint8_t*)malloc(total ? total : 1);
+    for (size_t i = 0; i < res.size(); i++) if (!res[i].empty()) std::memcpy(blob + offs_out[i], res[i].data(), res[i].size());
+    *blob_out = blob;
+}
+}  // namespace
+// over fold steps the caller brings (as amh_spans_fold): no device is touched
+int amh_substitute_fold(int case_mode, const uint32_t* hay_in, const uint64_t* pos_in, const uint32_t* val_in, uint64_t n, const am_slice* hay, size_t n_hay,
+                        const uint32_t* len_bytes, const uint32_t* len_code_points, size_t n_values, const uint8_t* repl_bytes, const uint64_t* repl_off,
+                        uint8_t** blob_out, uint64_t* offs_out)
+{
+    *blob_out = nullptr;
+    return guarded([&] {
+        if (case_mode != AM_CASE_SENSITIVE && case_mode != AM_IGNORE_CASE) throw AmError(AM_ERR_INVALID, "amh_substitute_fold: bad case_mode");
+        std::vector<FoldStep> steps((size_t)n);
+        for (uint64_t i = 0; i < n; i++) steps[i] = FoldStep{hay_in[i], pos_in[i], val_in[i]};
+        const std::vector<uint32_t> lb(len_bytes, len_bytes + n_values), lc(len_code_points, len_code_points + n_values);
+        const std::vector<Text> texts = sliceTexts(hay, n_hay);
+        substituteOut(spansFold((CaseSensitivity)case_mode, true, steps, texts, lb, lc), texts, repl_bytes, repl_off, n_values, blob_out, offs_out);
+    });
+}
+// amh_run_list's fold (the scan on the device, the fold on the host), then spansFold and substitute
+int amh_substitute(void* h, int case_mode, const am_slice* hay, size_t n_hay, const uint32_t* len_bytes, const uint32_t* len_code_points, size_t n_values,
+                   const uint8_t* repl_bytes, const uint64_t* repl_off, uint8_t** blob_out, uint64_t* offs_out)
+{
+    *blob_out = nullptr;
+    return guarded([&] {
+        if (case_mode != AM_CASE_SENSITIVE && case_mode != AM_IGNORE_CASE) throw AmError(AM_ERR_INVALID, "amh_substitute: bad case_mode");
+        struct Acc { std::vector<std::pair<uint64_t, uint32_t>> v; };
+        auto f = [](Acc a, const Match<uint32_t>& m) { a.v.emplace_back(m.matchPos, m.matchValue); return Next<Acc>::Step(std::move(a)); };
+        const std::vector<Text> texts = sliceTexts(hay, n_hay);
+        auto accs = runBatchWithCase((CaseSensitivity)case_mode, Acc{}, f, static_cast<MachineBox*>(h)->m, texts);
+        std::vector<FoldStep> steps;
+        for (size_t i = 0; i < accs.size(); i++)
+            for (auto& pv : accs[i].v) steps.push_back(FoldStep{(uint32_t)i, pv.first, pv.second});
+        const std::vector<uint32_t> lb(len_bytes, len_bytes + n_values), lc(len_code_points, len_code_points + n_values);
+        substituteOut(spansFold((CaseSensitivity)case_mode, true, steps, texts, lb, lc), texts, repl_bytes, repl_off, n_values, blob_out, offs_out);
+    });
+}
+
 // ---- Searcher
 int amh_searcher_build(int case_mode, const uint8_t* bytes, const uint64_t* offs, size_t n, void** out)
 {

@@ -3,6 +3,7 @@
 // all of them in fold order, or the leftmost-longest non-overlapping selection.  spansFold takes the fold steps as they are and touches no device.
 #pragma once
 #include <algorithm>
+#include <string>
 
 #include "automaton.hpp"
 
@@ -55,6 +56,29 @@ inline Spans spansFold(CaseSensitivity cs, bool leftmostLongest, const std::vect
     }
     if (k != steps.size()) throw AmError(AM_ERR_INVALID, "spansFold: the fold steps are not grouped by ascending haystack below texts.size()");
     out.offsets[texts.size()] = out.spans.size();
+    return out;
+}
+
+// substitute (include/am.h "substitute"): `replace` (src/Data/Text/AhoCorasick/Replacer.hs:163-180) applied to the leftmost-longest spans of spansFold, sequentially:
+// out_i = hay[0, s_1) ++ repl[v_1] ++ hay[s_1 + l_1, s_2) ++ ... ++ repl[v_k] ++ hay[s_k + l_k, len_i).  Replacements are bytes and are never scanned.
+inline std::vector<std::string> substitute(const Spans& spans, const std::vector<Text>& texts, const std::vector<std::string>& replacements)
+{
+    if (spans.offsets.size() != texts.size() + 1) throw AmError(AM_ERR_INVALID, "substitute: the spans are not those of these texts");
+    std::vector<std::string> out(texts.size());
+    for (size_t h = 0; h < texts.size(); h++) {
+        const Text& hay = texts[h];
+        std::string& o = out[h];
+        uint64_t cursor = 0;
+        for (uint64_t k = spans.offsets[h]; k < spans.offsets[h + 1]; k++) {
+            const am_span& s = spans.spans.at((size_t)k);
+            if (s.start < cursor || s.start + s.len > hay.len || s.needle >= replacements.size())
+                throw AmError(AM_ERR_INVALID, "substitute: a span overlaps the one before it, leaves its haystack or has no replacement");
+            if (s.start > cursor) o.append(reinterpret_cast<const char*>(hay.begin()) + cursor, (size_t)(s.start - cursor));
+            o.append(replacements[s.needle]);
+            cursor = s.start + s.len;
+        }
+        if (hay.len > cursor) o.append(reinterpret_cast<const char*>(hay.begin()) + cursor, (size_t)(hay.len - cursor));
+    }
     return out;
 }
 

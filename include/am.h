@@ -337,6 +337,51 @@ AM_API const void* am_spans_device_data(const struct am_spans* s);
 AM_API uint32_t am_spans_rounds(const struct am_spans* s);
 AM_API void am_spans_free(struct am_spans* s);
 
+/* ---- substitute: every leftmost-longest match replaced once, in HBM; the rewritten texts are a batch of their own ---------------
+ * For haystack i of the batch, with the rows (s_1, l_1, v_1) ... (s_k, l_k, v_k) of am_spans* in AM_SPANS_LEFTMOST_LONGEST mode:
+ *   out_i = hay[0, s_1) ++ repl[v_1] ++ hay[s_1 + l_1, s_2) ++ repl[v_2] ++ ... ++ repl[v_k] ++ hay[s_k + l_k, len_i)
+ * which is `replace` (Replacer.hs:163-180) applied to those matches: what Rust's aho-corasick calls replace_all under LeftmostLongest.  It is NOT Replacer.run
+ * (am_replacer_*: priorities, repeated passes).  Replacements are bytes and are NEVER SCANNED.  ZERO-LENGTH spans are never selected, so an empty needle inserts
+ * nothing.  Handles >= n_needles are SKIPPED (the convention of am_needle_ids).  Under AM_IGNORE_CASE the bytes removed are the SPAN'S OWN len: a k matched by
+ * U+212A removes three bytes.  A haystack without a match comes back BYTE FOR BYTE, an empty haystack stays empty, and the output batch has as many haystacks as the
+ * input, IN ORDER.  Every index and total is 64-bit: the output may exceed 4 GiB while the input does not.  The bytes do not depend on the order of any atomic: two
+ * runs give identical batches.  For b -> X, abc -> Y, abcd -> Z over "abcd b": "Z X"; for a -> "" over "banana": "bnn".
+ * The splice runs in HBM (csrc/am_subst.hip): a haystack with k spans is 2k + 1 pieces (gaps of the text, replacements from the pool); an exclusive sum of their
+ * lengths places them, the pieces of length 0 are dropped, and a gather over tiles of the new text keeps the tile's slice of the piece table in LDS and writes aligned
+ * 16-byte groups.  WORKSPACE of the splice, freed when it returns: 36 bytes per piece (2 x spans + haystacks pieces) and 16 per piece of non-zero length; the result
+ * holds its text and 8 bytes per haystack.  The library's device buffers are allocated an eighth larger than asked.
+ *   am_subst_table_create   the replacements beside a span table: replacement of handle v = repl_bytes[repl_off[v], repl_off[v + 1]), repl_off has n_needles + 1 entries
+ *                           of host memory (n_needles is the span table's); the pool is copied to the table's device, padded so that a 16-byte group read from any
+ *                           offset stays inside.  `t` must outlive the table.  AM_ERR_INVALID, before any device work, for null arguments (repl_bytes may be null
+ *                           when the pool is empty), repl_off[0] != 0, descending offsets, one replacement of 2^32 bytes and more.
+ *   am_batch_substitute     the splice alone: to am_spans what am_batch_from_fragments is to am_fragments.  `s` must be an AM_SPANS_LEFTMOST_LONGEST result of `src`:
+ *                           AM_ERR_INVALID for an AM_SPANS_ALL result, for a batch whose haystack count or total bytes differ, for batch, spans and table on different
+ *                           devices and for a table whose n_needles differs from that of the span table the spans were made with.  The new batch is owned by the
+ *                           library (am_batch_destroy); its text is 16-byte aligned, zero-filled and readable to round_up(total, 16): usable by every *_batch
+ *                           entry point.
+ *   am_substitute_batch     am_spans_batch in AM_SPANS_LEFTMOST_LONGEST mode followed by the splice.  spans_out (nullable): the spans, in SOURCE coordinates
+ *                           (am_spans_free).  Record memory is NOT bounded here, as in am_spans_batch.
+ *   am_substitute           the one-shot form on host slices (the calling thread's one-shot batch).  The result is a batch of its own and stays valid after the
+ *                           one-shot batch is reused.  n_hay == 0 gives a batch without haystacks and AM_OK.
+ *   am_substitute_geometry  the gather's store group and tile in bytes (tests place piece ends on the real seams).
+ * Batch accessors -- what a device stage that produces text hands back: am_batch_haystacks; am_batch_device_text / am_batch_device_offsets (the arrays in HBM, owned by
+ * the batch or borrowed by it); am_batch_read_offsets copies the n_hay + 1 offsets, am_batch_read_text any byte range [first_byte, first_byte + n_bytes) of the
+ * concatenated text to host memory (AM_ERR_INVALID beyond total; a range of 0 bytes is AM_OK).
+ * Arguments are checked before any device work: AM_ERR_INVALID for null table / batch / spans / out, a case_mode that is neither AM_CASE_SENSITIVE nor
+ * AM_IGNORE_CASE, n_hay >= 0xFFFFFFFF, slices without memory.  *out (and *spans_out) is NULL after every failure. */
+typedef struct am_subst_table am_subst_table;
+AM_API int am_subst_table_create(const am_span_table* t, const uint64_t* repl_off /* n_needles + 1, host */, const uint8_t* repl_bytes, am_subst_table** out);
+AM_API void am_subst_table_destroy(am_subst_table* r);
+AM_API int am_batch_substitute(const am_batch* src, const struct am_spans* s, const am_subst_table* r, am_batch** out);
+AM_API int am_substitute_batch(const am_subst_table* r, int case_mode, const am_batch* b, am_batch** out, struct am_spans** spans_out /* nullable */);
+AM_API int am_substitute(const am_subst_table* r, int case_mode, const am_slice* hay, size_t n_hay, am_batch** out);
+AM_API void am_substitute_geometry(uint32_t* group_bytes, uint32_t* tile_bytes);
+AM_API uint64_t am_batch_haystacks(const am_batch* b);
+AM_API const void* am_batch_device_text(const am_batch* b);
+AM_API const void* am_batch_device_offsets(const am_batch* b);
+AM_API int am_batch_read_offsets(const am_batch* b, uint64_t* out /* n_hay + 1, host */);
+AM_API int am_batch_read_text(const am_batch* b, uint64_t first_byte, uint64_t n_bytes, uint8_t* dst);
+
 /* Checksum of the fold sequence of a result (harness aid; SURVEY 8d "parity check at scale",
  * benchmark/benchmark.py:65-69 asserts count identity on every run).  For every haystack i < n_hay:
  *   hash_out[i]  = foldl (\h (pos, v) -> h * 0x100000001B3 + mix pos v) 0  over the matches the reference's
