@@ -98,6 +98,11 @@ ABI = {
     "am_batch_from_fragments": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "am_span_table_create": (C.c_int, [_vp, _vp, _vp, C.POINTER(_vp)]),
     "am_span_table_destroy": (None, [_vp]),
+    "am_word_bytes_default": (None, [_vp]),
+    "am_span_table_create_words": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "am_span_table_word_bytes": (C.c_int, [_vp, _vp]),
+    "am_count_spans_by_needle_batch": (C.c_int, [_vp, C.c_int, _vp, _vp]),
+    "am_count_spans_by_needle": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp]),
     "am_spans_batch": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
     "am_spans": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(Slice), _sz, C.POINTER(_vp)]),
     "am_spans_size": (C.c_uint64, [_vp]),
@@ -192,8 +197,10 @@ _HOST = {
     "amh_count_by_needle": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _sz, _vp]),
     "amh_count_matrix": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _sz, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
     "amh_spans_fold": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
+    "amh_spans_fold_words": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
     "amh_spans": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(Slice), _sz, _vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
     "amh_substitute_fold": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, C.POINTER(_vp), _vp]),
+    "amh_substitute_fold_words": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, _vp, C.POINTER(_vp), _vp]),
     "amh_substitute": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, C.POINTER(_vp), _vp]),
     "amh_searcher_build": (C.c_int, [C.c_int, C.c_char_p, _vp, _sz, C.POINTER(_vp)]),
     "amh_searcher_free": (None, [_vp]),
@@ -510,12 +517,13 @@ class Automaton:
             libhost().amh_free_u64(pe)
         return offs, ents
 
-    def spans(self, case, texts, leftmost_longest=False):
+    def spans(self, case, texts, leftmost_longest=False, whole_words=False):
         """Where every match starts: (offsets np.uint64[len(texts) + 1], spans SPAN_DTYPE[offsets[-1]]); the spans of text i are spans[offsets[i]:offsets[i + 1]],
         start and len in bytes relative to the text, needle = the value handle.  All fold steps of runWithCase (Automaton.hs:442-553) in fold order with the span
         makeMatch gives them (Replacer.hs:264-274), or -- leftmost_longest -- the non-overlapping selection: smallest start, then longest, then smallest handle, never a
-        zero-length span.  am_spans: scanned, expanded and selected in HBM."""
-        return SpanTable(self).spans_texts(case, texts, SPANS_LEFTMOST_LONGEST if leftmost_longest else SPANS_ALL)
+        zero-length span.  am_spans: scanned, expanded and selected in HBM.  whole_words: True (the default word class) or a class as SpanTable takes it -- only the
+        spans whose neighbours inside the text are no word bytes, filtered BEFORE the selection (include/am.h "whole words")."""
+        return SpanTable(self, word_bytes=whole_words).spans_texts(case, texts, SPANS_LEFTMOST_LONGEST if leftmost_longest else SPANS_ALL)
 
     def spans_host_mirror(self, case, texts, leftmost_longest=False, n_values=None, lengths=None):
         """The same through the C++ host mirror (host/spans.hpp spansFold over the fold steps of amh_run_list).  lengths: (len_bytes, len_code_points) per value handle
@@ -528,10 +536,17 @@ class Automaton:
                                     C.byref(po), C.byref(pe), C.byref(ne)))
         return _take_spans(po, pe, s.n, int(ne.value))
 
-    def substitute(self, case, texts, replacements):
+    def substitute(self, case, texts, replacements, whole_words=False):
         """Every leftmost-longest match replaced once, replacements[v] for needle v, never scanned again (include/am.h "substitute"): a list of bytes, one per text.
-        am_substitute: scanned, selected and spliced in HBM."""
-        return SubstTable(SpanTable(self), replacements).substitute_texts(case, texts)
+        am_substitute: scanned, selected and spliced in HBM.  whole_words: as in spans -- the leftmost-longest WHOLE-WORD matches."""
+        return SubstTable(SpanTable(self, word_bytes=whole_words), replacements).substitute_texts(case, texts)
+
+    def count_whole_words(self, case, texts, word_bytes=True):
+        """How often every needle occurs as a whole word over all the texts: np.uint64[len(needles)], the bincount of the whole-word spans(..., whole_words=word_bytes)
+        rows.  am_count_spans_by_needle: scanned, filtered and folded in HBM, the counts come back."""
+        if not self.needles:
+            return np.zeros(0, np.uint64)
+        return SpanTable(self, word_bytes=word_bytes).count_by_needle_texts(case, texts)
 
     def substitute_host_mirror(self, case, texts, replacements, n_values=None, lengths=None):
         """The same through the C++ host mirror (host/spans.hpp substitute over spansFold over the fold steps of amh_run_list)."""
@@ -562,8 +577,32 @@ def _take_texts(blob, offs):
     return [whole[int(offs[i]):int(offs[i + 1])] for i in range(len(offs) - 1)]
 
 
-def substitute_fold_host(case, triples, texts, len_bytes, len_code_points, replacements):
-    """amh_substitute_fold: the sequential definition of am_substitute over fold steps the caller brings (as spans_fold_host).  Runs without a device."""
+def default_word_bytes():
+    """am_word_bytes_default: the default word class as 256 flags (bytes of 0 / 1): 0-9 A-Z a-z _ and every byte 0x80-0xFF.  Runs without a device."""
+    out = (C.c_uint8 * 256)()
+    libam().am_word_bytes_default(out)
+    return bytes(out)
+
+
+def _word_flags(word_bytes):
+    """None / False: no class (None).  True: the default class.  bytes or an iterable of byte values: the class of exactly those values (empty: the empty class).
+    Returns np.uint8[256] flags or None."""
+    if word_bytes is None or word_bytes is False:
+        return None
+    if word_bytes is True:
+        return np.frombuffer(default_word_bytes(), dtype=np.uint8).copy()
+    flags = np.zeros(256, np.uint8)
+    for b in (word_bytes.encode("utf-8") if isinstance(word_bytes, str) else word_bytes):
+        b = int(b)
+        if not 0 <= b <= 255:
+            raise AmError(AM_ERR_INVALID, "word_bytes: byte values 0 .. 255")
+        flags[b] = 1
+    return flags
+
+
+def substitute_fold_host(case, triples, texts, len_bytes, len_code_points, replacements, word_bytes=None):
+    """amh_substitute_fold: the sequential definition of am_substitute over fold steps the caller brings (as spans_fold_host).  Runs without a device.  word_bytes: a
+    word class as SpanTable takes it (amh_substitute_fold_words)."""
     hay = np.ascontiguousarray(triples[0], dtype=np.uint32)
     pos = np.ascontiguousarray(triples[1], dtype=np.uint64)
     val = np.ascontiguousarray(triples[2], dtype=np.uint32)
@@ -575,8 +614,9 @@ def substitute_fold_host(case, triples, texts, len_bytes, len_code_points, repla
     pool, offs = _pack_replacements(replacements, nv)
     s = _Slices(texts)
     blob, out_offs = _vp(), np.zeros(s.n + 1, np.uint64)
-    _hcheck(libhost().amh_substitute_fold(case, hay.ctypes.data, pos.ctypes.data, val.ctypes.data, n, s.arr, s.n, lb.ctypes.data, lc.ctypes.data, nv, pool,
-                                          offs.ctypes.data, C.byref(blob), out_offs.ctypes.data))
+    flags = _word_flags(word_bytes)
+    _hcheck(libhost().amh_substitute_fold_words(case, hay.ctypes.data, pos.ctypes.data, val.ctypes.data, n, s.arr, s.n, lb.ctypes.data, lc.ctypes.data, nv, pool,
+                                                offs.ctypes.data, None if flags is None else flags.ctypes.data, C.byref(blob), out_offs.ctypes.data))
     return _take_texts(blob, out_offs)
 
 
@@ -618,9 +658,9 @@ def _take_spans(po, pe, n_hay, k):
     return offs, spans
 
 
-def spans_fold_host(case, mode, triples, texts, len_bytes, len_code_points):
+def spans_fold_host(case, mode, triples, texts, len_bytes, len_code_points, word_bytes=None):
     """amh_spans_fold: the sequential definition of am_spans over fold steps the caller brings -- (haystack, matchPos, value) arrays in fold order -- the texts and the
-    two length arrays.  Runs without a device."""
+    two length arrays.  Runs without a device.  word_bytes: a word class as SpanTable takes it (amh_spans_fold_words)."""
     hay = np.ascontiguousarray(triples[0], dtype=np.uint32)
     pos = np.ascontiguousarray(triples[1], dtype=np.uint64)
     val = np.ascontiguousarray(triples[2], dtype=np.uint32)
@@ -631,8 +671,9 @@ def spans_fold_host(case, mode, triples, texts, len_bytes, len_code_points):
     hay, pos, val, lb, lc = pad(hay, np.uint32), pad(pos, np.uint64), pad(val, np.uint32), pad(lb, np.uint32), pad(lc, np.uint32)
     s = _Slices(texts)
     po, pe, ne = _vp(), _vp(), C.c_uint64(0)
-    _hcheck(libhost().amh_spans_fold(case, mode, hay.ctypes.data, pos.ctypes.data, val.ctypes.data, n, s.arr, s.n, lb.ctypes.data, lc.ctypes.data, nv,
-                                     C.byref(po), C.byref(pe), C.byref(ne)))
+    flags = _word_flags(word_bytes)
+    _hcheck(libhost().amh_spans_fold_words(case, mode, hay.ctypes.data, pos.ctypes.data, val.ctypes.data, n, s.arr, s.n, lb.ctypes.data, lc.ctypes.data, nv,
+                                           None if flags is None else flags.ctypes.data, C.byref(po), C.byref(pe), C.byref(ne)))
     return _take_spans(po, pe, s.n, int(ne.value))
 
 
@@ -707,16 +748,21 @@ class ValuesTable:
 class SpanTable:
     """The needles' lengths beside machineValues on the device (am_span_table): what am_spans* turns a fold step into a span with.  Lengths come from
     automaton.needles, handle = needle index; n_needles below len(needles) skips the handles from n_needles on.  lengths: (len_bytes, len_code_points) per value handle
-    for an automaton built with handles of its own."""
+    for an automaton built with handles of its own.  word_bytes: None -- no word class, every span is a row; True -- the default class; bytes or an iterable of byte
+    values -- the class of those values (am_span_table_create_words): every consumer of the table then sees the whole-word spans only."""
 
-    def __init__(self, automaton, n_needles=None, lengths=None):
+    def __init__(self, automaton, n_needles=None, lengths=None, word_bytes=None):
         if n_needles is None and lengths is not None:
             n_needles = len(lengths[0])
         self._values = ValuesTable(automaton, n_needles)      # (the am_needle_ids must outlive the table)
         self.n_needles = self._values.n_needles
         self._lb, self._lc = _handle_lengths(automaton.needles, self.n_needles, lengths)
+        self._words = _word_flags(word_bytes)
         h = _vp()
-        check(libam().am_span_table_create(self._values.handle, self._lb.ctypes.data, self._lc.ctypes.data, C.byref(h)))
+        if self._words is None:
+            check(libam().am_span_table_create(self._values.handle, self._lb.ctypes.data, self._lc.ctypes.data, C.byref(h)))
+        else:
+            check(libam().am_span_table_create_words(self._values.handle, self._lb.ctypes.data, self._lc.ctypes.data, self._words.ctypes.data, C.byref(h)))
         self._h = h
 
     def __del__(self):
@@ -728,8 +774,29 @@ class SpanTable:
     def handle(self):
         return self._h
 
+    @property
+    def word_bytes(self):
+        """am_span_table_word_bytes: the table's class as 256 flags (bytes of 0 / 1), None for a table without one."""
+        out = (C.c_uint8 * 256)()
+        return bytes(out) if libam().am_span_table_word_bytes(self._h, out) else None
+
     def _spans(self, call, raw):
         return _csr_call(call, spans_to_numpy, libam().am_spans_free, raw)
+
+    def _counts(self, call):
+        out = np.zeros(max(self.n_needles, 1), np.uint64)
+        check(call(out.ctypes.data))
+        return out[:self.n_needles]
+
+    def count_by_needle_batch(self, case, batch):
+        """am_count_spans_by_needle_batch on a device-resident batch: np.uint64[n_needles], counts[v] = the AM_SPANS_ALL rows of this table with needle v (with a word
+        class: the whole-word occurrences; without one: ValuesTable.count_by_needle_batch's vector)."""
+        return self._counts(lambda out: libam().am_count_spans_by_needle_batch(self._h, case, batch, out))
+
+    def count_by_needle_texts(self, case, texts):
+        """am_count_spans_by_needle: the one-shot form on host texts."""
+        s = _Slices(texts)
+        return self._counts(lambda out: libam().am_count_spans_by_needle(self._h, case, s.arr, s.n, out))
 
     def spans_batch(self, case, batch, mode, raw=False):
         """am_spans_batch on a device-resident batch (an am_batch* handle: am_batch_upload / am_batch_from_device / Splitter.lines_batch): (offsets np.uint64[n_hay + 1],

@@ -2,6 +2,7 @@
 // (Searcher.hs:167-187), the fold checksum of a result, the per-needle match counts (am_count_by_needle*) and the per-haystack needle counts (am_count_matrix*).
 // The argument checks, the segment loop of the one-shot entry points (fold_slices) and the matrix's result handle are am_fold.h's, shared with the other folds.
 #include "am_host.h"
+#include "am_spans.h"
 
 #include <memory>
 #include <string>
@@ -158,8 +159,9 @@ int hist_launch(const am_needle_ids* ids, const Record* recs, uint64_t n_rec, ui
 }
 
 // what is done with the sorted records of a scan while they are in HBM: records [0, n_rec) belong to haystacks [h0, h0 + n_hay) of the batch the caller handed to
-// fold_batch, their haystack fields count from h0.  Returns when the device has finished with the records.
-using RecordFold = std::function<int(const Record* recs, uint64_t n_rec, uint32_t h0, uint32_t n_hay, int dev, hipStream_t st)>;
+// fold_batch, their haystack fields count from h0.  `scanned` is the batch the records index: the caller's, or the group's sub-batch with a text and offsets of its
+// own -- a fold that reads text (the whole-word counts) reads that one.  Returns when the device has finished with the records.
+using RecordFold = std::function<int(const Record* recs, uint64_t n_rec, uint32_t h0, uint32_t n_hay, const am_batch* scanned, int dev, hipStream_t st)>;
 
 // one scan of `b` (haystacks h0 ... of the caller's batch), its records handed to `fold`; returns when the fold has finished (the record array is free again)
 int fold_scan(const am_needle_ids* ids, int case_mode, am_batch* b, RecordArray& ra, uint32_t h0, const RecordFold& fold)
@@ -169,7 +171,7 @@ int fold_scan(const am_needle_ids* ids, int case_mode, am_batch* b, RecordArray&
     if (n_rec == 0) return AM_OK;
     ON_DEVICE(b->dev);
     hipStream_t st; AM_TRY(get_stream(b->dev, &st));
-    AM_TRY(fold((const Record*)ra.p, n_rec, h0, b->n_hay, b->dev, st));
+    AM_TRY(fold((const Record*)ra.p, n_rec, h0, b->n_hay, b, b->dev, st));
     HIP_TRY(hipStreamSynchronize(st));
     return AM_OK;
 }
@@ -224,8 +226,27 @@ int fold_batch(const am_needle_ids* ids, int case_mode, am_batch* b, const Recor
 // the counts of a device-resident batch into d_counts (accumulating)
 int hist_batch(const am_needle_ids* ids, int case_mode, am_batch* b, uint64_t* d_counts, uint64_t* d_trace)
 {
-    return fold_batch(ids, case_mode, b, [&](const Record* recs, uint64_t n_rec, uint32_t, uint32_t, int dev, hipStream_t st) {
+    return fold_batch(ids, case_mode, b, [&](const Record* recs, uint64_t n_rec, uint32_t, uint32_t, const am_batch*, int dev, hipStream_t st) {
         return hist_launch(ids, recs, n_rec, d_counts, d_trace, dev, st);
+    });
+}
+
+// the same over the whole-word spans of a table with a word class (am_count_spans_by_needle*): the predicate reads the text and the offsets of the batch the records
+// index, which is the group's sub-batch where fold_batch made groups
+int hist_words_batch(const am_span_table* t, int case_mode, am_batch* b, uint64_t* d_counts, uint64_t* d_trace)
+{
+    const am_needle_ids* ids = t->ids;
+    return fold_batch(ids, case_mode, b, [&](const Record* recs, uint64_t n_rec, uint32_t, uint32_t n_hay, const am_batch* scanned, int dev, hipStream_t st) {
+        SpansIn in;
+        in.recs = recs; in.n_rec = n_rec;
+        in.vals_off = (const uint64_t*)ids->vals_off.p; in.vals = (const uint32_t*)ids->vals.p; in.n_states = ids->n_states; in.n_values = ids->n_values;
+        in.len_bytes = (const uint32_t*)t->len_bytes.p; in.len_cps = (const uint32_t*)t->len_cps.p; in.n_needles = ids->n_needles; in.n_hay = n_hay;
+        in.text = (const uint8_t*)scanned->d_text; in.offsets = scanned->d_offsets; in.total = scanned->total;
+        in.words = t->d_words();
+        Prof pr("needle_hist_words", st);
+        HIP_TRY(launch_needle_hist_words(case_mode == AM_IGNORE_CASE, in, d_counts, d_trace,
+                                         cfg::get(cfg::kHistFlushTiles) > 0 ? (uint32_t)std::min<long>(cfg::get(cfg::kHistFlushTiles), 1L << 30) : 0u, g_rt.dev[dev].n_cu, st));
+        return AM_OK;
     });
 }
 
@@ -277,6 +298,47 @@ extern "C" int am_count_by_needle_batch(const am_needle_ids* ids, int case_mode,
     AM_TRY(out.begin(ids->n_needles, st));
     AM_TRY(hist_batch(ids, case_mode, b, out.counts(), out.trace_words()));
     return out.finish(counts_out, st);
+}
+
+extern "C" int am_count_spans_by_needle_batch(const am_span_table* t, int case_mode, const am_batch* cb, uint64_t* counts_out)
+{
+    if (!t || !cb) return fail(AM_ERR_INVALID, "null span table or batch");
+    const am_needle_ids* ids = t->ids;
+    if (!t->has_words) return am_count_by_needle_batch(ids, case_mode, cb, counts_out);      // no class: every span is a row, the rows are the values
+    if (ids->n_needles && !counts_out) return fail(AM_ERR_INVALID, "counts_out is null");
+    AM_TRY(check_case(case_mode));
+    if (ids->a->dev != cb->dev) return fail(AM_ERR_INVALID, "span table and batch live on different devices");
+    if (ids->n_needles == 0) return AM_OK;
+    AM_TRY(ensure_runtime());
+    am_batch* b = const_cast<am_batch*>(cb);
+    if (b->n_hay == 0 || b->total == 0) { std::memset(counts_out, 0, (size_t)ids->n_needles * 8); return AM_OK; }
+    ON_DEVICE(b->dev);
+    hipStream_t st; AM_TRY(get_stream(b->dev, &st));
+    HistOut out;
+    AM_TRY(out.begin(ids->n_needles, st));
+    AM_TRY(hist_words_batch(t, case_mode, b, out.counts(), out.trace_words()));
+    return out.finish(counts_out, st);
+}
+
+extern "C" int am_count_spans_by_needle(const am_span_table* t, int case_mode, const am_slice* hay, size_t n_hay, uint64_t* counts_out)
+{
+    uint64_t total = 0;
+    AM_TRY(check_slices(hay, n_hay, &total));
+    AM_TRY(check_case(case_mode));
+    if (!t) return fail(AM_ERR_INVALID, "null span table");      // (last of the checks a caller without a device can see; n_needles is the table's)
+    const am_needle_ids* ids = t->ids;
+    if (ids->n_needles && !counts_out) return fail(AM_ERR_INVALID, "counts_out is null");
+    if (!t->has_words) return am_count_by_needle(ids, case_mode, hay, n_hay, counts_out);
+    if (ids->n_needles == 0) return AM_OK;
+    AM_TRY(ensure_runtime());
+    if (total == 0) { std::memset(counts_out, 0, (size_t)ids->n_needles * 8); return AM_OK; }
+    const int dev = ids->a->dev;
+    ON_DEVICE(dev);
+    am_batch* b = oneshot_batch(dev);                       // this thread's batch on the automaton's device: upload plus the batch form, as am_spans does it
+    int rc = upload_batch(hay, n_hay, b, true);
+    if (rc == AM_OK) rc = am_count_spans_by_needle_batch(t, case_mode, b, counts_out);
+    oneshot_batch_trim(dev);
+    return rc;
 }
 
 extern "C" int am_matches_count_by_needle(const am_matches* m, const am_needle_ids* ids, uint64_t* counts_out)
@@ -439,7 +501,7 @@ struct MatrixBuild {
 int matrix_batch(MatrixBuild& mb, const am_needle_ids* ids, int case_mode, am_batch* b, uint64_t base)
 {
     if (ids->n_needles == 0) return AM_OK;
-    return fold_batch(ids, case_mode, b, [&mb, base](const Record* recs, uint64_t n_rec, uint32_t h0, uint32_t n, int dev, hipStream_t st) {
+    return fold_batch(ids, case_mode, b, [&mb, base](const Record* recs, uint64_t n_rec, uint32_t h0, uint32_t n, const am_batch*, int dev, hipStream_t st) {
         return mb.fold(recs, n_rec, (uint32_t)(base + h0), n, dev, st);
     });
 }

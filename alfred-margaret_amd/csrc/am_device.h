@@ -195,15 +195,18 @@ hipError_t launch_split_gather(const uint8_t* src, uint64_t src_total, const uin
                                int n_cu, hipStream_t st);
 // match spans (am_spans.hip): every fold step `Match pos v` with v < n_needles as (start, len, haystack, needle), all of them or the leftmost-longest selection
 struct Span { uint64_t start, len; uint32_t haystack, needle; };      // = am_span in include/am.h
+constexpr uint32_t kWordClassWords = 8;                     // a word class: 256 flags, bit b & 31 of word b >> 5
 struct SpansIn {
     const Record* recs; uint64_t n_rec;                     // the sorted records of the batch
     const uint64_t* vals_off; const uint32_t* vals; uint64_t n_states, n_values;      // machineValues in flat form (am_needle_ids)
     const uint32_t* len_bytes; const uint32_t* len_cps; uint32_t n_needles, n_hay;    // the needles' own lengths (am_span_table)
     const uint8_t* text; const uint64_t* offsets; uint64_t total;
+    const uint32_t* words;                                  // the table's word class: 256 flags in 8 dwords (am_words.h); null: no class, every span is kept
 };
 constexpr uint64_t kSpansMaxTile = 2048;                    // candidates per workgroup of the prefix maximum
-// cnt[i] = values < n_needles of record i (n_rec + 1 entries, the last one 0); then, with voff = exclusive sum of cnt and n_span = voff[n_rec], the spans in fold order
-hipError_t launch_spans_count(const SpansIn& in, uint32_t* cnt, hipStream_t st);
+// cnt[i] = values < n_needles of record i (n_rec + 1 entries, the last one 0); then, with voff = exclusive sum of cnt and n_span = voff[n_rec], the spans in fold order.
+// With in.words both passes keep the whole-word spans only (ic decides the starts, so the count pass needs it as well)
+hipError_t launch_spans_count(bool ic, const SpansIn& in, uint32_t* cnt, hipStream_t st);
 hipError_t launch_spans_write(bool ic, const SpansIn& in, const uint64_t* voff, Span* spans, uint64_t n_span, hipStream_t st);
 // AM_SPANS_ALL: span_off[h] = voff[rec_first[h]] (n_hay + 1)
 hipError_t launch_spans_offsets(const uint64_t* rec_first, const uint64_t* voff, uint64_t n_rec, uint32_t n_hay, uint64_t* span_off, hipStream_t st);
@@ -222,6 +225,9 @@ hipError_t launch_spans_walk(const uint64_t* cand_g, const uint64_t* best, uint6
 hipError_t launch_spans_next(const uint64_t* cand_g, const uint64_t* best, uint64_t n_cand, const uint8_t* head, uint64_t* jump, hipStream_t st);
 hipError_t launch_spans_emit(const uint64_t* cand_g, const uint64_t* best, const uint32_t* kept, const uint64_t* kidx, uint64_t n_cand, const SpansIn& in, Span* out, uint64_t n_out,
                              uint64_t* span_off, hipStream_t st);
+// per-needle counts over the whole-word spans only (am_hist.hip, am_count_spans_by_needle*): counts[id] += the values id < in.n_needles of in.recs whose span the class
+// in.words (not null) keeps: the bincount of the AM_SPANS_ALL rows of that table.  trace / flush_tiles / n_cu as launch_needle_hist
+hipError_t launch_needle_hist_words(bool ic, const SpansIn& in, uint64_t* counts, uint64_t* trace, uint32_t flush_tiles, int n_cu, hipStream_t st);
 // substitute (am_subst.hip): the leftmost-longest spans of a batch spliced into a new text.  P = 2 * n_span + n_hay pieces: span j of haystack h owns 2j + h (the gap
 // before it) and 2j + h + 1 (its replacement), 2 * span_off[h + 1] + h is the tail of h
 constexpr uint64_t kSubstRepl = 1ull << 63;                 // a piece's source: offset into the replacement pool instead of the batch text

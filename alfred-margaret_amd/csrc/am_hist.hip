@@ -16,12 +16,15 @@
 // all of them to one slot in the worst case, below 2^32.
 // Lane per RECORD, the value list of a record looped by its lane: the states of a dictionary carry one value almost everywhere (a suffix chain like
 // tshirt / shirt / hirt a few), so a wave-wide prefix sum to spread values over lanes would be paid by every record for the sake of few.
+// k_needle_hist_words is the same walk over the WHOLE-WORD spans of a table with a word class (am_count_spans_by_needle*): a value is added only where span_of
+// (am_words.h) keeps the span it gives with its record -- the bincount of the AM_SPANS_ALL rows of that table.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "am_bounds.h"
 #include "am_device.h"
+#include "am_words.h"
 
 AM_BOUNDS_TU("am_hist.hip")
 
@@ -45,13 +48,13 @@ static_assert((uint64_t)kHistTile * kHistLdsPerRecord * kHistTilesPerFlush < (1u
 // ids are handles in the caller's order (alphabetical, by frequency, ...): a multiplicative hash spreads neighbours over the table
 __device__ __forceinline__ uint32_t hist_slot(uint32_t id) { return (id * 0x9E3779B1u) >> (32 - kHistSlotBits); }
 
-template <bool kTrace>
-__global__ void __launch_bounds__(kHistThreads) k_needle_hist(const Record* __restrict__ recs, uint64_t n_rec, const uint64_t* __restrict__ vals_off,
-                                                              const uint32_t* __restrict__ vals, uint32_t n_needles, uint64_t n_states, uint64_t n_values,
-                                                              unsigned long long* __restrict__ counts, unsigned long long* __restrict__ trace, uint32_t tiles_per_flush)
+// The walk over the tiles with the workgroup's LDS table (tag / cnt: kHistSlots words each, declared by the kernel).  WORDS: a value is added only where the span it
+// gives with its record is a whole word -- span_of (am_words.h), the function the span expansion decides its rows with -- against the class in `words` (LDS).
+template <bool kTrace, bool WORDS, bool IC>
+__device__ __forceinline__ void hist_body(uint32_t* tag, uint32_t* cnt, const uint32_t* words, const SpansIn& in, const Record* __restrict__ recs, uint64_t n_rec,
+                                          const uint64_t* __restrict__ vals_off, const uint32_t* __restrict__ vals, uint32_t n_needles, uint64_t n_states, uint64_t n_values,
+                                          unsigned long long* __restrict__ counts, unsigned long long* __restrict__ trace, uint32_t tiles_per_flush)
 {
-    __shared__ uint32_t tag[kHistSlots];
-    __shared__ uint32_t cnt[kHistSlots];
     for (uint32_t i = threadIdx.x; i < kHistSlots; i += kHistThreads) { tag[i] = kHistEmpty; cnt[i] = 0; }
     __syncthreads();
     // every live slot to HBM with one add; `clear`: the counts start again (the tags stay: the hot ids keep their slots)
@@ -73,12 +76,14 @@ __global__ void __launch_bounds__(kHistThreads) k_needle_hist(const Record* __re
     uint32_t since_flush = 0;
     for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {            // (the same tiles for every lane of the workgroup: the barriers below are uniform)
         uint64_t k[kHistPerThread], ke[kHistPerThread];
+        Record rec[kHistPerThread];                                          // (WORDS only: the predicate needs the record's haystack and end)
 #pragma unroll
         for (uint32_t u = 0; u < kHistPerThread; u++) {
             const uint64_t r = t * kHistTile + u * kHistThreads + threadIdx.x;
             k[u] = ke[u] = 0;
             if (r < n_rec) {
-                const uint32_t state = recs[r].state;
+                if (WORDS) rec[u] = recs[r];
+                const uint32_t state = WORDS ? rec[u].state : recs[r].state;
                 AM_BOUNDS(state < n_states);
                 if (state < n_states) { k[u] = vals_off[state]; ke[u] = vals_off[state + 1]; }
                 AM_BOUNDS(k[u] <= ke[u] && ke[u] <= n_values);
@@ -90,6 +95,10 @@ __global__ void __launch_bounds__(kHistThreads) k_needle_hist(const Record* __re
             for (uint64_t j = 0; k[u] + j < ke[u]; j++) {
                 const uint32_t id = vals[k[u] + j];
                 if (id >= n_needles) continue;                               // a handle beyond the table: skipped, as containsAll skips it (k_idset)
+                if (WORDS) {
+                    uint64_t ss, sn;
+                    if (!span_of<IC, true>(in, rec[u], id, words, ss, sn)) continue;      // no whole word: no row of the span table, no count
+                }
                 uint32_t s = 0;
                 bool hit = false;
                 if (j < kHistLdsPerRecord) {
@@ -120,6 +129,29 @@ __global__ void __launch_bounds__(kHistThreads) k_needle_hist(const Record* __re
     }
 }
 
+template <bool kTrace>
+__global__ void __launch_bounds__(kHistThreads) k_needle_hist(const Record* __restrict__ recs, uint64_t n_rec, const uint64_t* __restrict__ vals_off,
+                                                              const uint32_t* __restrict__ vals, uint32_t n_needles, uint64_t n_states, uint64_t n_values,
+                                                              unsigned long long* __restrict__ counts, unsigned long long* __restrict__ trace, uint32_t tiles_per_flush)
+{
+    __shared__ uint32_t tag[kHistSlots];
+    __shared__ uint32_t cnt[kHistSlots];
+    hist_body<kTrace, false, false>(tag, cnt, nullptr, SpansIn{}, recs, n_rec, vals_off, vals, n_needles, n_states, n_values, counts, trace, tiles_per_flush);
+}
+
+// the whole-word form: the workgroup stages the table's 32-byte class in LDS beside its tables; the LDS-counter wrap argument is the plain kernel's (a record adds
+// at most as often as there)
+template <bool kTrace, bool IC>
+__global__ void __launch_bounds__(kHistThreads) k_needle_hist_words(SpansIn in, unsigned long long* __restrict__ counts, unsigned long long* __restrict__ trace,
+                                                                    uint32_t tiles_per_flush)
+{
+    __shared__ uint32_t tag[kHistSlots];
+    __shared__ uint32_t cnt[kHistSlots];
+    __shared__ uint32_t words[kWordClassWords];
+    if (threadIdx.x < kWordClassWords) words[threadIdx.x] = in.words[threadIdx.x];      // (hist_body's first barrier comes before any read)
+    hist_body<kTrace, true, IC>(tag, cnt, words, in, in.recs, in.n_rec, in.vals_off, in.vals, in.n_needles, in.n_states, in.n_values, counts, trace, tiles_per_flush);
+}
+
 }  // namespace
 
 hipError_t launch_needle_hist(const Record* recs, uint64_t n_rec, const uint64_t* vals_off, const uint32_t* vals, uint32_t n_needles, uint64_t n_states,
@@ -133,6 +165,25 @@ hipError_t launch_needle_hist(const Record* recs, uint64_t n_rec, const uint64_t
                                   (unsigned long long*)counts, (unsigned long long*)trace, tiles_per_flush);
     else hipLaunchKernelGGL(k_needle_hist<false>, dim3(grid), dim3(kHistThreads), 0, st, recs, n_rec, vals_off, vals, n_needles, n_states, n_values,
                             (unsigned long long*)counts, (unsigned long long*)nullptr, tiles_per_flush);
+    return hipGetLastError();
+}
+
+hipError_t launch_needle_hist_words(bool ic, const SpansIn& in, uint64_t* counts, uint64_t* trace, uint32_t flush_tiles, int n_cu, hipStream_t st)
+{
+    if (in.n_rec == 0 || in.n_needles == 0) return hipSuccess;
+    if (!in.words) return hipErrorInvalidValue;
+    const uint64_t n_tiles = (in.n_rec + kHistTile - 1) / kHistTile;
+    const dim3 grid((uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)(n_cu > 0 ? n_cu : 1) * kHistGroupsPerCu)), block(kHistThreads);
+    const uint32_t tiles_per_flush = flush_tiles != 0 && flush_tiles < kHistTilesPerFlush ? flush_tiles : kHistTilesPerFlush;
+    unsigned long long* const c = (unsigned long long*)counts;
+    unsigned long long* const tr = (unsigned long long*)trace;
+    if (trace) {
+        if (ic) hipLaunchKernelGGL((k_needle_hist_words<true, true>), grid, block, 0, st, in, c, tr, tiles_per_flush);
+        else hipLaunchKernelGGL((k_needle_hist_words<true, false>), grid, block, 0, st, in, c, tr, tiles_per_flush);
+    } else {
+        if (ic) hipLaunchKernelGGL((k_needle_hist_words<false, true>), grid, block, 0, st, in, c, tr, tiles_per_flush);
+        else hipLaunchKernelGGL((k_needle_hist_words<false, false>), grid, block, 0, st, in, c, tr, tiles_per_flush);
+    }
     return hipGetLastError();
 }
 

@@ -2,9 +2,11 @@
 // lists and the needles' own lengths into (start, len, haystack, needle), all of them in fold order or the leftmost-longest non-overlapping selection
 // (am_spans.hip).  The result is CSR like am_fragments and stays in HBM until asked for: its handle, the finisher of long chains and the argument checks are
 // am_fold.h's, shared with the other folds.
+// A span table may carry a word class (am_span_table_create_words, include/am.h "whole words"): 8 dwords beside the lengths that the expansion filters with.
 #include "am_spans.h"
 
 #include <cstddef>
+#include <cstring>
 
 using namespace am;
 using namespace am::dev;
@@ -101,7 +103,10 @@ int select_leftmost_longest(const SpansIn& in, const Span* spans, uint64_t n_spa
 
 }  // namespace
 
-extern "C" int am_span_table_create(const am_needle_ids* ids, const uint32_t* len_bytes, const uint32_t* len_code_points, am_span_table** out)
+namespace {
+
+// am_span_table_create and am_span_table_create_words: one set of checks, one set of messages; word_bytes (256 flags, not null) only where has_words
+int create_table(const am_needle_ids* ids, const uint32_t* len_bytes, const uint32_t* len_code_points, bool has_words, const uint8_t* word_bytes, am_span_table** out)
 {
     if (!out) return fail(AM_ERR_INVALID, "out is null");
     *out = nullptr;
@@ -123,8 +128,47 @@ extern "C" int am_span_table_create(const am_needle_ids* ids, const uint32_t* le
         HIP_TRY(hipMemcpy(t->len_bytes.p, len_bytes, (size_t)n * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(t->len_cps.p, len_code_points, (size_t)n * 4, hipMemcpyHostToDevice));
     }
+    if (has_words) {
+        uint32_t packed[kWordClassWords] = {};
+        for (uint32_t b = 0; b < 256; b++) {
+            t->word_bytes[b] = word_bytes[b] ? 1 : 0;
+            if (word_bytes[b]) packed[b >> 5] |= 1u << (b & 31u);
+        }
+        AM_TRY(t->words.ensure(sizeof(packed)));
+        HIP_TRY(hipMemcpy(t->words.p, packed, sizeof(packed), hipMemcpyHostToDevice));
+        t->has_words = true;
+    }
     *out = t.release();
     return AM_OK;
+}
+
+}  // namespace
+
+extern "C" int am_span_table_create(const am_needle_ids* ids, const uint32_t* len_bytes, const uint32_t* len_code_points, am_span_table** out)
+{
+    return create_table(ids, len_bytes, len_code_points, false, nullptr, out);
+}
+
+// the default class: 0-9 A-Z a-z _ and every byte of a multi-byte UTF-8 sequence (any code point beyond ASCII is a word character)
+extern "C" void am_word_bytes_default(uint8_t out[256])
+{
+    if (!out) return;
+    for (uint32_t b = 0; b < 256; b++)
+        out[b] = ((b >= '0' && b <= '9') || (b >= 'A' && b <= 'Z') || (b >= 'a' && b <= 'z') || b == '_' || b >= 0x80) ? 1 : 0;
+}
+
+extern "C" int am_span_table_create_words(const am_needle_ids* ids, const uint32_t* len_bytes, const uint32_t* len_code_points, const uint8_t* word_bytes, am_span_table** out)
+{
+    uint8_t dflt[256];
+    if (!word_bytes) am_word_bytes_default(dflt);
+    return create_table(ids, len_bytes, len_code_points, true, word_bytes ? word_bytes : dflt, out);
+}
+
+extern "C" int am_span_table_word_bytes(const am_span_table* t, uint8_t* out256)
+{
+    if (!t || !t->has_words) return 0;
+    if (out256) std::memcpy(out256, t->word_bytes, 256);
+    return 1;
 }
 
 extern "C" void am_span_table_destroy(am_span_table* t) { delete t; }
@@ -153,6 +197,7 @@ extern "C" int am_spans_batch(const am_span_table* t, int case_mode, int mode, c
     in.vals_off = (const uint64_t*)ids->vals_off.p; in.vals = (const uint32_t*)ids->vals.p; in.n_states = ids->n_states; in.n_values = ids->n_values;
     in.len_bytes = (const uint32_t*)t->len_bytes.p; in.len_cps = (const uint32_t*)t->len_cps.p; in.n_needles = ids->n_needles; in.n_hay = b->n_hay;
     in.text = (const uint8_t*)b->d_text; in.offsets = b->d_offsets; in.total = b->total;
+    in.words = t->d_words();
     DevBuf cnt, voff, scan_tmp, rec_first, all_spans;
     AM_TRY(cnt.ensure((n_rec + 1) * 4));
     AM_TRY(voff.ensure((n_rec + 1) * 8));
@@ -162,7 +207,7 @@ extern "C" int am_spans_batch(const am_span_table* t, int case_mode, int mode, c
     HIP_TRY(scan_temp_bytes(n_rec + 1, &tmp_bytes));
     AM_TRY(scan_tmp.ensure(tmp_bytes));
     { Prof pr("spans_count", st);
-      HIP_TRY(launch_spans_count(in, (uint32_t*)cnt.p, st));
+      HIP_TRY(launch_spans_count(case_mode == AM_IGNORE_CASE, in, (uint32_t*)cnt.p, st));
       HIP_TRY(launch_scan(scan_tmp.p, scan_tmp.cap, (const uint32_t*)cnt.p, (uint64_t*)voff.p, n_rec + 1, st)); }
     uint64_t n_span = 0;
     AM_TRY(read_u64((const uint64_t*)voff.p + n_rec, &n_span, st));

@@ -6,6 +6,10 @@
 struct am_span_table {
     const am_needle_ids* ids = nullptr;
     am::host::DevBuf len_bytes, len_cps;                    // uint32[n_needles] each, on the automaton's device
+    bool has_words = false;                                 // am_span_table_create_words: every consumer of the table sees the whole-word spans only
+    uint8_t word_bytes[256] = {};                           // the class as the caller gave it, 0 / 1
+    am::host::DevBuf words;                                 // ... and as the kernels read it: 8 dwords beside the lengths (am_words.h)
+    const uint32_t* d_words() const { return has_words ? (const uint32_t*)words.p : nullptr; }
 };
 
 struct am_spans : am::host::CsrResult<am_span> {

@@ -5,6 +5,8 @@
 // (records ascend by (haystack, end), the values of a record come in list order).  Natural text carries 1.25 values per record: a lane per record is the right shape.
 // IgnoreCase walks len_code_points - 1 code points backwards from the last byte of the match (src/Data/Text/Utf8.hs:256-276), per value; the walk never leaves the
 // haystack (clamped to 0 where the reference calls `error`).
+// A table with a WORD CLASS (am_span_table_create_words) keeps the whole-word spans only: both passes decide that with span_of (am_words.h), the count pass counts
+// kept rows, and everything below runs on a compact span array as if the other spans had never matched.
 //
 // LEFTMOST-LONGEST without a sort, in global byte positions g = offsets[haystack] + start.  Haystacks are contiguous and len > 0 implies g < total, so ascending g is
 // ascending (haystack, start), and a span of an earlier haystack ends at or before every g of a later one: nothing below needs a haystack comparison.
@@ -29,6 +31,7 @@
 #include "am_bounds.h"
 #include "am_device.h"
 #include "am_wave.h"
+#include "am_words.h"
 
 AM_BOUNDS_TU("am_spans.hip")
 
@@ -54,24 +57,9 @@ __device__ __forceinline__ void value_range(const SpansIn& in, const Record& r, 
     if (v0 > v1) v0 = v1;
 }
 
-// start of the match of needle v that ends at r.end_pos, relative to the haystack (Replacer.hs:264-274 makeMatch; a needle of length 0 starts where it ends)
-template <bool IC>
-__device__ __forceinline__ uint64_t span_start(const SpansIn& in, const Record& r, uint32_t v)
-{
-    AM_BOUNDS(v < in.n_needles);
-    const uint32_t nb = in.len_bytes[v];
-    if (nb == 0) return r.end_pos;
-    if (!IC) return r.end_pos >= nb ? r.end_pos - nb : 0;
-    AM_BOUNDS(r.haystack < in.n_hay);
-    if (r.haystack >= in.n_hay || r.end_pos == 0) return 0;
-    const uint64_t base = in.offsets[r.haystack];
-    AM_BOUNDS(base + r.end_pos <= in.total);
-    if (base + r.end_pos > in.total) return 0;
-    const uint8_t* hay = in.text + base;
-    return skip_code_points_backwards(hay, r.end_pos, in.len_cps[v] - 1);      // (nb != 0: the table has at least one code point for it)
-}
-
-// one lane per record (+ one for the trailing zero of the scan's input): its values < n_needles
+// one lane per record (+ one for the trailing zero of the scan's input): its values < n_needles; WORDS: those the word class keeps (span_of, am_words.h -- under
+// IC the backwards walk runs here and again in k_spans_write: no span that is dropped is ever written)
+template <bool IC, bool WORDS>
 __global__ void __launch_bounds__(kSpThreads) k_spans_count(SpansIn in, uint32_t* __restrict__ cnt)
 {
     const uint64_t i = global_lane();
@@ -81,12 +69,18 @@ __global__ void __launch_bounds__(kSpThreads) k_spans_count(SpansIn in, uint32_t
     uint64_t v0, v1;
     value_range(in, r, v0, v1);
     uint32_t c = 0;
-    for (uint64_t k = v0; k < v1; k++) c += in.vals[k] < in.n_needles ? 1u : 0u;
+    for (uint64_t k = v0; k < v1; k++) {
+        const uint32_t v = in.vals[k];
+        if (!WORDS) { c += v < in.n_needles ? 1u : 0u; continue; }
+        if (v >= in.n_needles) continue;
+        uint64_t s, n;
+        c += span_of<IC, true>(in, r, v, in.words, s, n) ? 1u : 0u;
+    }
     cnt[i] = c;
 }
 
 // one lane per record: its spans, in list order, at voff[i]
-template <bool IC>
+template <bool IC, bool WORDS>
 __global__ void __launch_bounds__(kSpThreads) k_spans_write(SpansIn in, const uint64_t* __restrict__ voff, Span* __restrict__ spans, uint64_t n_span)
 {
     const uint64_t i = global_lane();
@@ -102,11 +96,12 @@ __global__ void __launch_bounds__(kSpThreads) k_spans_write(SpansIn in, const ui
     for (uint64_t k = v0; k < v1; k++) {
         const uint32_t v = in.vals[k];
         if (v >= in.n_needles) continue;                               // the am_needle_ids convention: skipped
-        const uint64_t s = span_start<IC>(in, r, v);
+        uint64_t s, n;
+        if (!span_of<IC, WORDS>(in, r, v, in.words, s, n)) continue;   // (WORDS only: no whole word, no row -- voff counted the kept ones)
         AM_BOUNDS(o < n_span && o < voff[i + 1] && s <= r.end_pos);
         if (o >= n_span) return;
         Span x;
-        x.start = s; x.len = r.end_pos >= s ? r.end_pos - s : 0; x.haystack = r.haystack; x.needle = v;
+        x.start = s; x.len = n; x.haystack = r.haystack; x.needle = v;
         spans[o++] = x;
     }
 }
@@ -332,17 +327,26 @@ __global__ void __launch_bounds__(kSpThreads) k_spans_ll_offsets(const uint64_t*
 
 }  // namespace
 
-hipError_t launch_spans_count(const SpansIn& in, uint32_t* cnt, hipStream_t st)
+hipError_t launch_spans_count(bool ic, const SpansIn& in, uint32_t* cnt, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_spans_count, dim3(blocks_for(in.n_rec + 1)), dim3(kSpThreads), 0, st, in, cnt);
+    const dim3 grid(blocks_for(in.n_rec + 1)), block(kSpThreads);
+    if (!in.words) hipLaunchKernelGGL((k_spans_count<false, false>), grid, block, 0, st, in, cnt);      // (no class: the count needs no start, so no case mode)
+    else if (ic) hipLaunchKernelGGL((k_spans_count<true, true>), grid, block, 0, st, in, cnt);
+    else hipLaunchKernelGGL((k_spans_count<false, true>), grid, block, 0, st, in, cnt);
     return hipGetLastError();
 }
 
 hipError_t launch_spans_write(bool ic, const SpansIn& in, const uint64_t* voff, Span* spans, uint64_t n_span, hipStream_t st)
 {
     if (in.n_rec == 0 || n_span == 0) return hipSuccess;
-    if (ic) hipLaunchKernelGGL(k_spans_write<true>, dim3(blocks_for(in.n_rec)), dim3(kSpThreads), 0, st, in, voff, spans, n_span);
-    else hipLaunchKernelGGL(k_spans_write<false>, dim3(blocks_for(in.n_rec)), dim3(kSpThreads), 0, st, in, voff, spans, n_span);
+    const dim3 grid(blocks_for(in.n_rec)), block(kSpThreads);
+    if (in.words) {
+        if (ic) hipLaunchKernelGGL((k_spans_write<true, true>), grid, block, 0, st, in, voff, spans, n_span);
+        else hipLaunchKernelGGL((k_spans_write<false, true>), grid, block, 0, st, in, voff, spans, n_span);
+    } else {
+        if (ic) hipLaunchKernelGGL((k_spans_write<true, false>), grid, block, 0, st, in, voff, spans, n_span);
+        else hipLaunchKernelGGL((k_spans_write<false, false>), grid, block, 0, st, in, voff, spans, n_span);
+    }
     return hipGetLastError();
 }
 

@@ -126,8 +126,10 @@ void spansOut(const Spans& r, size_t n_hay, uint64_t** offs_out, uint64_t** span
 }  // namespace
 // spansFold over fold steps the caller brings (n triples in fold order, haystacks ascending): no device is touched.  offsets (n_hay + 1) and the spans as the C ABI
 // lays them out (am_span, 24 bytes each); free both with amh_free_u64
-int amh_spans_fold(int case_mode, int mode, const uint32_t* hay_in, const uint64_t* pos_in, const uint32_t* val_in, uint64_t n, const am_slice* hay, size_t n_hay,
-                   const uint32_t* len_bytes, const uint32_t* len_code_points, size_t n_values, uint64_t** offs_out, uint64_t** spans_out, uint64_t* n_out)
+// amh_spans_fold_words: the same with a word class (256 flags, nullable: none) -- only the whole-word spans are rows, filter before select
+int amh_spans_fold_words(int case_mode, int mode, const uint32_t* hay_in, const uint64_t* pos_in, const uint32_t* val_in, uint64_t n, const am_slice* hay, size_t n_hay,
+                         const uint32_t* len_bytes, const uint32_t* len_code_points, size_t n_values, const uint8_t* word_bytes, uint64_t** offs_out, uint64_t** spans_out,
+                         uint64_t* n_out)
 {
     *offs_out = nullptr; *spans_out = nullptr; *n_out = 0;
     return guarded([&] {
@@ -136,8 +138,13 @@ int amh_spans_fold(int case_mode, int mode, const uint32_t* hay_in, const uint64
         std::vector<FoldStep> steps((size_t)n);
         for (uint64_t i = 0; i < n; i++) steps[i] = FoldStep{hay_in[i], pos_in[i], val_in[i]};
         const std::vector<uint32_t> lb(len_bytes, len_bytes + n_values), lc(len_code_points, len_code_points + n_values);
-        spansOut(spansFold((CaseSensitivity)case_mode, mode == AM_SPANS_LEFTMOST_LONGEST, steps, sliceTexts(hay, n_hay), lb, lc), n_hay, offs_out, spans_out, n_out);
+        spansOut(spansFold((CaseSensitivity)case_mode, mode == AM_SPANS_LEFTMOST_LONGEST, steps, sliceTexts(hay, n_hay), lb, lc, word_bytes), n_hay, offs_out, spans_out, n_out);
     });
+}
+int amh_spans_fold(int case_mode, int mode, const uint32_t* hay_in, const uint64_t* pos_in, const uint32_t* val_in, uint64_t n, const am_slice* hay, size_t n_hay,
+                   const uint32_t* len_bytes, const uint32_t* len_code_points, size_t n_values, uint64_t** offs_out, uint64_t** spans_out, uint64_t* n_out)
+{
+    return amh_spans_fold_words(case_mode, mode, hay_in, pos_in, val_in, n, hay, n_hay, len_bytes, len_code_points, n_values, nullptr, offs_out, spans_out, n_out);
 }
 // amh_run_list's fold (runWithCase with a list-building fold over the batch), then amh_spans_fold's
 int amh_spans(void* h, int case_mode, int mode, const am_slice* hay, size_t n_hay, const uint32_t* len_bytes, const uint32_t* len_code_points, size_t n_values,
@@ -176,9 +183,10 @@ void substituteOut(const Spans& sp, const std::vector<Text>& texts, const uint8_
 }
 }  // namespace
 // over fold steps the caller brings (as amh_spans_fold): no device is touched
-int amh_substitute_fold(int case_mode, const uint32_t* hay_in, const uint64_t* pos_in, const uint32_t* val_in, uint64_t n, const am_slice* hay, size_t n_hay,
-                        const uint32_t* len_bytes, const uint32_t* len_code_points, size_t n_values, const uint8_t* repl_bytes, const uint64_t* repl_off,
-                        uint8_t** blob_out, uint64_t* offs_out)
+// amh_substitute_fold_words: the same with a word class (256 flags, nullable: none)
+int amh_substitute_fold_words(int case_mode, const uint32_t* hay_in, const uint64_t* pos_in, const uint32_t* val_in, uint64_t n, const am_slice* hay, size_t n_hay,
+                              const uint32_t* len_bytes, const uint32_t* len_code_points, size_t n_values, const uint8_t* repl_bytes, const uint64_t* repl_off,
+                              const uint8_t* word_bytes, uint8_t** blob_out, uint64_t* offs_out)
 {
     *blob_out = nullptr;
     return guarded([&] {
@@ -187,8 +195,14 @@ int amh_substitute_fold(int case_mode, const uint32_t* hay_in, const uint64_t* p
         for (uint64_t i = 0; i < n; i++) steps[i] = FoldStep{hay_in[i], pos_in[i], val_in[i]};
         const std::vector<uint32_t> lb(len_bytes, len_bytes + n_values), lc(len_code_points, len_code_points + n_values);
         const std::vector<Text> texts = sliceTexts(hay, n_hay);
-        substituteOut(spansFold((CaseSensitivity)case_mode, true, steps, texts, lb, lc), texts, repl_bytes, repl_off, n_values, blob_out, offs_out);
+        substituteOut(spansFold((CaseSensitivity)case_mode, true, steps, texts, lb, lc, word_bytes), texts, repl_bytes, repl_off, n_values, blob_out, offs_out);
     });
+}
+int amh_substitute_fold(int case_mode, const uint32_t* hay_in, const uint64_t* pos_in, const uint32_t* val_in, uint64_t n, const am_slice* hay, size_t n_hay,
+                        const uint32_t* len_bytes, const uint32_t* len_code_points, size_t n_values, const uint8_t* repl_bytes, const uint64_t* repl_off,
+                        uint8_t** blob_out, uint64_t* offs_out)
+{
+    return amh_substitute_fold_words(case_mode, hay_in, pos_in, val_in, n, hay, n_hay, len_bytes, len_code_points, n_values, repl_bytes, repl_off, nullptr, blob_out, offs_out);
 }
 // amh_run_list's fold (the scan on the device, the fold on the host), then spansFold and substitute
 int amh_substitute(void* h, int case_mode, const am_slice* hay, size_t n_hay, const uint32_t* len_bytes, const uint32_t* len_code_points, size_t n_values,

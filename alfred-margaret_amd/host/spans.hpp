@@ -25,8 +25,25 @@ inline uint64_t spanStart(CaseSensitivity cs, const Text& hay, uint64_t pos, uin
     try { return utf8::skipCodePointsBackwards(hay, (size_t)pos - 1, lenCodePoints - 1); } catch (const std::out_of_range&) { return 0; }
 }
 
+// the whole-word rule of include/am.h "whole words": both neighbours of [start, start + len) inside THIS haystack are no word bytes (or do not exist); it does not
+// look at the span's own bytes.  wordBytes: 256 flags, non-zero = word byte
+inline bool wholeWord(const Text& hay, uint64_t start, uint64_t len, const uint8_t* wordBytes)
+{
+    if (start > hay.len || len > hay.len - start) return false;
+    if (start > 0 && wordBytes[hay.begin()[start - 1]]) return false;
+    if (start + len < hay.len && wordBytes[hay.begin()[start + len]]) return false;
+    return true;
+}
+
+// the default class: 0-9 A-Z a-z _ and every byte from 0x80 on (am_word_bytes_default)
+inline void defaultWordBytes(uint8_t out[256])
+{
+    for (unsigned b = 0; b < 256; b++) out[b] = ((b >= '0' && b <= '9') || (b >= 'A' && b <= 'Z') || (b >= 'a' && b <= 'z') || b == '_' || b >= 0x80) ? 1 : 0;
+}
+
+// wordBytes (nullable: no class): only the whole-word spans are rows, and the leftmost-longest selection runs over those -- filter, then select
 inline Spans spansFold(CaseSensitivity cs, bool leftmostLongest, const std::vector<FoldStep>& steps, const std::vector<Text>& texts,
-                       const std::vector<uint32_t>& lenBytes, const std::vector<uint32_t>& lenCodePoints)
+                       const std::vector<uint32_t>& lenBytes, const std::vector<uint32_t>& lenCodePoints, const uint8_t* wordBytes = nullptr)
 {
     if (lenBytes.size() != lenCodePoints.size()) throw AmError(AM_ERR_INVALID, "spansFold: the two length arrays differ in size");
     const size_t nValues = lenBytes.size();
@@ -41,7 +58,9 @@ inline Spans spansFold(CaseSensitivity cs, bool leftmostLongest, const std::vect
             const uint32_t v = steps[k].value;
             if (v >= nValues) continue;                     // the am_needle_ids convention: skipped
             const uint64_t start = spanStart(cs, texts[h], steps[k].matchPos, lenBytes[v], lenCodePoints[v]);
-            all.push_back(am_span{start, steps[k].matchPos - start, (uint32_t)h, v});
+            const uint64_t len = steps[k].matchPos >= start ? steps[k].matchPos - start : 0;
+            if (wordBytes && !wholeWord(texts[h], start, len, wordBytes)) continue;
+            all.push_back(am_span{start, len, (uint32_t)h, v});
         }
         if (!leftmostLongest) { out.spans.insert(out.spans.end(), all.begin(), all.end()); continue; }
         // smallest start >= cursor, then the largest len, then the smallest handle: in that order the first span at or after the cursor is the one to take
@@ -80,6 +99,13 @@ inline std::vector<std::string> substitute(const Spans& spans, const std::vector
         if (hay.len > cursor) o.append(reinterpret_cast<const char*>(hay.begin()) + cursor, (size_t)(hay.len - cursor));
     }
     return out;
+}
+
+// ... straight from the fold steps, with an optional word class: substitute over spansFold(cs, leftmost-longest, ..., wordBytes)
+inline std::vector<std::string> substitute(CaseSensitivity cs, const std::vector<FoldStep>& steps, const std::vector<Text>& texts, const std::vector<uint32_t>& lenBytes,
+                                           const std::vector<uint32_t>& lenCodePoints, const std::vector<std::string>& replacements, const uint8_t* wordBytes = nullptr)
+{
+    return substitute(spansFold(cs, true, steps, texts, lenBytes, lenCodePoints, wordBytes), texts, replacements);
 }
 
 }  // namespace alfred_margaret

@@ -382,6 +382,42 @@ AM_API const void* am_batch_device_offsets(const am_batch* b);
 AM_API int am_batch_read_offsets(const am_batch* b, uint64_t* out /* n_hay + 1, host */);
 AM_API int am_batch_read_text(const am_batch* b, uint64_t first_byte, uint64_t n_bytes, uint8_t* dst);
 
+/* ---- whole words: a span table with a word class -- spans, substitute and term counts over the whole-word matches only, in HBM ---------------
+ * A WORD CLASS W is a set of byte values, given as 256 flags (non-zero = word byte).  A span (start, len) of a haystack of L bytes is a WHOLE WORD iff both hold:
+ *   start == 0        or  hay[start - 1]    is not in W
+ *   start + len == L  or  hay[start + len]  is not in W
+ * This is the look-around form (?<!\w)needle(?!\w), not \b: it does not look at the needle's own bytes, so c++ is a whole word in "c++ is".  The neighbours are bytes
+ * of the SAME haystack only: a batch stores its haystacks back to back, and the last byte of haystack h - 1, the first byte of haystack h + 1 and the zero padding
+ * behind the text are never neighbours.  Under AM_IGNORE_CASE `start` is the span's own start from the backwards walk: a k matched by U+212A has its left neighbour
+ * three bytes before its end.  A zero-length span follows the same rule with len = 0.  The DEFAULT class (word_bytes == NULL) is 0-9 A-Z a-z _ and every byte
+ * 0x80-0xFF, so any non-ASCII code point is a word character; a caller who wants something else passes a table of their own.
+ * A span table made with a word class changes what EVERY consumer of that table sees:
+ *   AM_SPANS_ALL                       the whole-word rows only, in fold order.  For he, the over "the he she": (0,3,the) (4,2,he) -- not the he inside the and she.
+ *   AM_SPANS_LEFTMOST_LONGEST          the same selection rule, over the whole-word rows with len > 0: FILTER, THEN SELECT.  For ab, `ab c` over "ab cd" the plain table
+ *                                      selects (0,4,`ab c`), which is followed by d and is no whole word -- filtering afterwards would leave nothing; the table with a
+ *                                      class gives (0,2,ab).
+ *   am_substitute*, am_batch_substitute  the splice over that selection (the splice reads spans: it needs no class of its own).
+ *   am_count_spans_by_needle*          counts[v] = the number of AM_SPANS_ALL rows with needle v: the term frequencies of whole words.
+ * A table made by am_span_table_create has no class and behaves byte for byte as before.
+ * The predicate sits between the expansion and the selection (csrc/am_words.h, one device function for the expansion and the histogram): the records, the needles'
+ * lengths and the text are in HBM already, the class is 32 bytes beside the lengths, no span that is dropped is ever written, and everything after the expansion runs
+ * on a compact span array.  Nothing about the scans, the record format or the image changes.
+ *   am_word_bytes_default            the default class as 256 flags of 0 / 1.  Needs no device.
+ *   am_span_table_create_words       am_span_table_create (the same checks, the same messages) with a class: word_bytes = 256 flags of host memory, NULL for the default.
+ *   am_span_table_word_bytes         1 and the class as 256 flags of 0 / 1 in out256 (nullable) for a table with a class, 0 for one without (or a null table).
+ *   am_count_spans_by_needle_batch   a device-resident batch; counts_out = n_needles counts of host memory.  Record memory is BOUNDED as in am_count_by_needle_batch
+ *                                    (groups of whole haystacks, each scanned and folded before the next; the predicate reads the group's own text).  For a table
+ *                                    without a class it is am_count_by_needle_batch's vector.  Integer adds commute: two runs give identical counts.
+ *   am_count_spans_by_needle         the one-shot form on host slices (the calling thread's one-shot batch).
+ * Arguments are checked before any device work: AM_ERR_INVALID for null table / batch / counts_out (with n_needles > 0), a case_mode that is neither AM_CASE_SENSITIVE
+ * nor AM_IGNORE_CASE, n_hay >= 0xFFFFFFFF, slices without memory, table and batch on different devices. */
+AM_API void am_word_bytes_default(uint8_t out[256]);
+AM_API int am_span_table_create_words(const am_needle_ids* ids, const uint32_t* len_bytes, const uint32_t* len_code_points,
+                                      const uint8_t* word_bytes /* 256 flags, host, non-zero = word byte; NULL: the default class */, am_span_table** out);
+AM_API int am_span_table_word_bytes(const am_span_table* t, uint8_t* out256 /* nullable */);   /* 1: has a class (copied to out256), 0: none */
+AM_API int am_count_spans_by_needle_batch(const am_span_table* t, int case_mode, const am_batch* b, uint64_t* counts_out /* n_needles, host */);
+AM_API int am_count_spans_by_needle(const am_span_table* t, int case_mode, const am_slice* hay, size_t n_hay, uint64_t* counts_out /* n_needles, host */);
+
 /* Checksum of the fold sequence of a result (harness aid; SURVEY 8d "parity check at scale",
  * benchmark/benchmark.py:65-69 asserts count identity on every run).  For every haystack i < n_hay:
  *   hash_out[i]  = foldl (\h (pos, v) -> h * 0x100000001B3 + mix pos v) 0  over the matches the reference's
