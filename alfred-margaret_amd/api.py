@@ -124,6 +124,20 @@ ABI = {
     "am_batch_device_offsets": (_vp, [_vp]),
     "am_batch_read_offsets": (C.c_int, [_vp, _vp]),
     "am_batch_read_text": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp]),
+    "am_select_any_batch": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
+    "am_select_all_batch": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
+    "am_select_spans_batch": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
+    "am_select_flags": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(_vp)]),
+    "am_select_any": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(Slice), _sz, C.POINTER(_vp)]),
+    "am_select_all": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(Slice), _sz, C.POINTER(_vp)]),
+    "am_selection_size": (C.c_uint64, [_vp]),
+    "am_selection_source_haystacks": (C.c_uint64, [_vp]),
+    "am_selection_total_bytes": (C.c_uint64, [_vp]),
+    "am_selection_indices": (_vp, [_vp]),
+    "am_selection_device_indices": (_vp, [_vp]),
+    "am_selection_free": (None, [_vp]),
+    "am_batch_from_selection": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "am_select_geometry": (None, [_u32p, _u32p]),
     "am_needle_ids_create": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(_vp)]),
     "am_needle_ids_destroy": (None, [_vp]),
     "am_contains_all": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp]),
@@ -548,6 +562,20 @@ class Automaton:
             return np.zeros(0, np.uint64)
         return SpanTable(self, word_bytes=word_bytes).count_by_needle_texts(case, texts)
 
+    def grep(self, case, texts, invert=False, whole_words=False):
+        """The texts that contain a needle -- `grep -F -f needles`; invert: `grep -v`; whole_words (True or a class as SpanTable takes it): `grep -w` -- as
+        (indices np.uint32, [bytes]): the kept texts' indices, ascending, and the kept texts.  Decided and compacted in HBM (include/am.h "select")."""
+        s = _Slices(texts)
+        if not whole_words:
+            return _grep_texts(texts, _select(lambda out: libam().am_select_any(self.device, case, int(bool(invert)), s.arr, s.n, out)))
+        t = SpanTable(self, word_bytes=whole_words)
+        b = _vp()
+        check(libam().am_batch_upload(s.arr, s.n, C.byref(b)))
+        try:
+            return _grep_texts(texts, t.select_batch(case, b, invert))
+        finally:
+            libam().am_batch_destroy(b)
+
     def substitute_host_mirror(self, case, texts, replacements, n_values=None, lengths=None):
         """The same through the C++ host mirror (host/spans.hpp substitute over spansFold over the fold steps of amh_run_list)."""
         lb, lc = _handle_lengths(self.needles, n_values, lengths)
@@ -744,6 +772,15 @@ class ValuesTable:
         s = _Slices(texts)
         return self._matrix(lambda out: libam().am_count_matrix(self._h, case, s.arr, s.n, out), raw)
 
+    def select_all_batch(self, case, batch, invert=False):
+        """am_select_all_batch on a device-resident batch (an am_batch* handle): the Selection of the haystacks that contain every needle id (Searcher.containsAll)."""
+        return _select(lambda out: libam().am_select_all_batch(self._h, case, int(bool(invert)), batch, out))
+
+    def select_all_texts(self, case, texts, invert=False):
+        """am_select_all: the one-shot form on host texts."""
+        s = _Slices(texts)
+        return _select(lambda out: libam().am_select_all(self._h, case, int(bool(invert)), s.arr, s.n, out))
+
 
 class SpanTable:
     """The needles' lengths beside machineValues on the device (am_span_table): what am_spans* turns a fold step into a span with.  Lengths come from
@@ -807,6 +844,85 @@ class SpanTable:
         """am_spans: the one-shot form on host texts."""
         s = _Slices(texts)
         return self._spans(lambda out: libam().am_spans(self._h, case, mode, s.arr, s.n, out), False)
+
+    def select_batch(self, case, batch, invert=False):
+        """am_select_spans_batch on a device-resident batch: the Selection of the haystacks whose SPANS_ALL row under this table is not empty (with a word class:
+        the haystacks that hold a needle as a whole word)."""
+        return _select(lambda out: libam().am_select_spans_batch(self._h, case, int(bool(invert)), batch, out))
+
+
+class Selection:
+    """Which haystacks of a batch a select kept (am_selection): ascending source indices in HBM, copied to the host on first use."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            libam().am_selection_free(self._h)
+            self._h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def size(self):
+        return int(libam().am_selection_size(self._h))
+
+    @property
+    def source_haystacks(self):
+        return int(libam().am_selection_source_haystacks(self._h))
+
+    @property
+    def total_bytes(self):
+        return int(libam().am_selection_total_bytes(self._h))
+
+    @property
+    def indices(self):
+        """np.uint32[size]: the kept haystacks' indices in the source batch, ascending."""
+        p = libam().am_selection_indices(self._h)
+        if not p:
+            check(AM_ERR_HIP)
+        n = self.size
+        return np.ctypeslib.as_array(C.cast(p, _u32p), shape=(max(n, 1),))[:n].copy()
+
+    def batch(self, src):
+        """am_batch_from_selection: the kept haystacks of `src` (the am_batch* the selection was made from) as a new am_batch* in HBM; free with am_batch_destroy."""
+        nb = _vp()
+        check(libam().am_batch_from_selection(src, self._h, C.byref(nb)))
+        return nb
+
+
+def _select(call):
+    h = _vp()
+    check(call(C.byref(h)))
+    return Selection(h)
+
+
+def select_flags(batch, flags, invert=False):
+    """am_select_flags: the caller's own predicate over an am_batch* handle, one flag per haystack (non-zero = true)."""
+    f = np.ascontiguousarray(np.asarray(flags) != 0, dtype=np.uint8)
+    return _select(lambda out: libam().am_select_flags(batch, f.ctypes.data if f.size else None, int(bool(invert)), out))
+
+
+def select_geometry():
+    """(tile_bytes, scan_block_items) of the select's gather and of the compaction's exclusive sums (am_select_geometry)."""
+    t, s = C.c_uint32(0), C.c_uint32(0)
+    libam().am_select_geometry(C.byref(t), C.byref(s))
+    return int(t.value), int(s.value)
+
+
+def _grep_texts(texts, sel):
+    """(indices, [bytes]) of a selection over host texts: the texts are the caller's already, only the indices come back."""
+    def text(t):
+        if isinstance(t, tuple):
+            t, off, ln = t
+            t = bytes(t)
+            return t[off:] if ln is None else t[off:off + ln]
+        return bytes(t) if isinstance(t, np.ndarray) else _as_bytes(t)
+    idx = sel.indices
+    return idx, [text(texts[int(i)]) for i in idx]
 
 
 def substitute_geometry():
@@ -990,6 +1106,8 @@ class Searcher:
         _hcheck(libhost().amh_searcher_build(case, blob, offs.ctypes.data, len(needles), C.byref(h)))
         self._h = h
         self.case = case
+        self._needles = [_as_bytes(n) for n in needles]
+        self._ids = None                                     # the needle-id table of the selects, made on first use
 
     build = classmethod(lambda cls, case, needles: cls(case, needles))
 
@@ -1021,6 +1139,29 @@ class Searcher:
 
     def contains_all(self, text):
         return bool(self.contains_all_batch([text])[0])
+
+    def _id_table(self):
+        """buildNeedleIdSearcher (Searcher.hs:167-169) as the C ABI takes it: the needles with their indices as values, and machineValues in flat form beside them."""
+        if self._ids is None:
+            self._ids = ValuesTable(Automaton(self._needles))
+        return self._ids
+
+    def select_batch(self, batch, all=False, invert=False):
+        """am_select_any_batch / am_select_all_batch (all=True) on a device-resident batch (an am_batch* handle) in this searcher's case mode: the Selection of the
+        haystacks for which containsAny / containsAll holds (invert: does not hold)."""
+        t = self._id_table()
+        if all:
+            return t.select_all_batch(self.case, batch, invert)
+        return _select(lambda out: libam().am_select_any_batch(t._a.device, self.case, int(bool(invert)), batch, out))
+
+    def grep_batch(self, texts, all=False, invert=False):
+        """The texts that contain any needle (all=True: every needle), or -- invert -- those that do not, as (indices np.uint32, [bytes]).  The one-shot forms
+        am_select_any / am_select_all: decided and compacted in HBM, the indices come back."""
+        t = self._id_table()
+        s = _Slices(texts)
+        if all:
+            return _grep_texts(texts, t.select_all_texts(self.case, texts, invert))
+        return _grep_texts(texts, _select(lambda out: libam().am_select_any(t._a.device, self.case, int(bool(invert)), s.arr, s.n, out)))
 
 
 class Replacer:

@@ -49,13 +49,12 @@ extern "C" int am_needle_ids_create(const am_automaton* a, const uint64_t* value
 
 extern "C" void am_needle_ids_destroy(am_needle_ids* ids) { delete ids; }
 
-extern "C" int am_contains_all_batch(const am_needle_ids* ids, int case_mode, const am_batch* cb, uint8_t* flags_out)
+// containsAll with the flags left in HBM: the sink decides what becomes of them (am_contains_all_batch: the copy to the caller; a select: the compaction)
+int am::host::contains_all_flags(const am_needle_ids* ids, int case_mode, am_batch* b, FlagSink& sink)
 {
-    if (!ids || !cb) return fail(AM_ERR_INVALID, "null needle ids or batch");
-    am_batch* b = const_cast<am_batch*>(cb);
     const uint32_t n_hay = b->n_hay;
-    if (n_hay && !flags_out) return fail(AM_ERR_INVALID, "flags_out is null");
-    if (ids->n_needles == 0) { if (n_hay) std::memset(flags_out, 1, n_hay); return AM_OK; }     // IS.null of the empty set (Searcher.hs:176,184)
+    AM_TRY(sink.begin(b));
+    if (ids->n_needles == 0) return n_hay ? sink.constant(1) : AM_OK;      // IS.null of the empty set (Searcher.hs:176,184)
     if (n_hay == 0) return AM_OK;
     ON_DEVICE(b->dev);
     hipStream_t st; AM_TRY(get_stream(b->dev, &st));
@@ -69,12 +68,12 @@ extern "C" int am_contains_all_batch(const am_needle_ids* ids, int case_mode, co
         AM_TRY(flags.ensure((size_t)n_hay * 4 + 64));                  // (here: the haystacks' missing-id counters)
         bool taken = false;
         AM_TRY(scan_needle_ids(ids->a, case_mode, b, (const uint64_t*)ids->vals_off.p, (const uint32_t*)ids->vals.p, ids->n_needles, (uint32_t*)bits.p, words,
-                               (uint32_t*)flags.p, flags_out, &taken));
+                               (uint32_t*)flags.p, sink, &taken));
         if (taken) return AM_OK;
     }
     uint64_t n_rec = 0;
     AM_TRY(run_records(ids->a, case_mode, b, records_into(records), &n_rec));
-    if (n_rec == 0) { std::memset(flags_out, 0, n_hay); return AM_OK; }
+    if (n_rec == 0) return sink.constant(0);
     // one bitmap row per haystack; very wide batches go through in groups of haystacks (records are sorted by haystack)
     const uint64_t budget = 1ull << 30;
     const uint32_t group = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_hay, budget / ((uint64_t)words * 4)));
@@ -96,9 +95,14 @@ extern "C" int am_contains_all_batch(const am_needle_ids* ids, int case_mode, co
           HIP_TRY(launch_idset((const Record*)records.p, r0, r1, (const uint64_t*)ids->vals_off.p, (const uint32_t*)ids->vals.p, ids->n_needles, h0, words, (uint32_t*)bits.p, st));
           HIP_TRY(launch_idset_all((const uint32_t*)bits.p, words, ids->n_needles, h1 - h0, (uint8_t*)flags.p + h0, st)); }
     }
-    HIP_TRY(hipMemcpyAsync(flags_out, flags.p, n_hay, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return AM_OK;
+    return sink.device((const uint8_t*)flags.p, st);       // (returns when the copy or the compaction has finished: the workspaces are freed)
+}
+
+extern "C" int am_contains_all_batch(const am_needle_ids* ids, int case_mode, const am_batch* cb, uint8_t* flags_out)
+{
+    if (!ids || !cb) return fail(AM_ERR_INVALID, "null needle ids or batch");
+    HostFlagSink sink(flags_out, false);
+    return contains_all_flags(ids, case_mode, const_cast<am_batch*>(cb), sink);
 }
 
 extern "C" int am_matches_fold_hash(const am_matches* m, const am_needle_ids* ids, size_t n_hay, uint64_t* hash_out, uint64_t* count_out)
@@ -275,6 +279,33 @@ struct HistOut {
 };
 
 }  // namespace
+
+// am_select_spans_batch's predicate (am_select.cpp): d_flags[h] = 1 for every haystack whose AM_SPANS_ALL row under table t is not empty; d_flags = b->n_hay bytes in
+// HBM that this call clears.  Scanned and folded in bounded record memory like the whole-word counts above: k_hay_flags_spans reads the text and the offsets of the
+// batch the records index, which is the group's sub-batch where fold_batch made groups, and flags the group's haystacks at d_flags + h0.
+int am::host::spans_flags(const am_span_table* t, int case_mode, am_batch* b, uint8_t* d_flags)
+{
+    const am_needle_ids* ids = t->ids;
+    if (b->n_hay == 0) return AM_OK;
+    {
+        ON_DEVICE(b->dev);
+        hipStream_t st; AM_TRY(get_stream(b->dev, &st));
+        HIP_TRY(hipMemsetAsync(d_flags, 0, b->n_hay, st));
+        HIP_TRY(hipStreamSynchronize(st));                  // (as HistOut::begin: the folds follow on this thread's stream, the scans synchronise in between)
+    }
+    if (ids->n_needles == 0) return AM_OK;
+    return fold_batch(ids, case_mode, b, [&](const Record* recs, uint64_t n_rec, uint32_t h0, uint32_t n_hay, const am_batch* scanned, int, hipStream_t st) {
+        SpansIn in;
+        in.recs = recs; in.n_rec = n_rec;
+        in.vals_off = (const uint64_t*)ids->vals_off.p; in.vals = (const uint32_t*)ids->vals.p; in.n_states = ids->n_states; in.n_values = ids->n_values;
+        in.len_bytes = (const uint32_t*)t->len_bytes.p; in.len_cps = (const uint32_t*)t->len_cps.p; in.n_needles = ids->n_needles; in.n_hay = n_hay;
+        in.text = (const uint8_t*)scanned->d_text; in.offsets = scanned->d_offsets; in.total = scanned->total;
+        in.words = t->d_words();
+        Prof pr("hay_flags_spans", st);
+        HIP_TRY(launch_hay_flags_spans(case_mode == AM_IGNORE_CASE, in, d_flags + h0, st));
+        return AM_OK;
+    });
+}
 
 extern "C" int am_debug_hist_adds(uint64_t* out3)
 {

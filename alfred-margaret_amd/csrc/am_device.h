@@ -245,6 +245,22 @@ hipError_t launch_subst_compact(const uint64_t* src_at, const uint32_t* live, co
                                 uint64_t n_live, const uint64_t* span_off, uint64_t n_span, uint64_t n_hay, uint64_t* out_off, hipStream_t st);
 hipError_t launch_subst_gather(const uint8_t* text, uint64_t src_total, const uint8_t* pool, uint64_t pool_bytes, const uint64_t* cdst, const uint64_t* csrc, uint64_t n_live,
                                uint64_t total, uint8_t* dst, int n_cu, hipStream_t st);
+// select (am_select.hip): the haystacks of a batch that a predicate keeps, compacted by RUNS (maximal sequences of consecutive kept haystacks: contiguous in the source)
+// flags[h] = 1 for every haystack that owns a (record, value < n_needles) pair whose span the table keeps (span_of, am_words.h): row h of AM_SPANS_ALL is not empty.
+// flags: in.n_hay bytes, zero before; in.words null: no class, IC is not looked at
+hipError_t launch_hay_flags_spans(bool ic, const SpansIn& in, uint8_t* flags, hipStream_t st);
+// n + 1 entries each, the last ones 0 (the scans' trailing element): keep[i] = (flags[i] != 0) != (invert != 0) (flags null: every flag is `constant`),
+// run_head[i] = keep[i] && !(i > 0 && keep[i - 1]), klen[i] = keep[i] ? length of haystack i : 0
+hipError_t launch_select_plan(const uint8_t* flags, uint32_t constant, uint32_t invert, const uint64_t* src_offsets, uint64_t n, uint64_t src_total, uint32_t* keep,
+                              uint32_t* run_head, uint64_t* klen, hipStream_t st);
+// with rank / run_rank / koff = the exclusive sums of keep / run_head / klen (n_kept = rank[n], n_runs = run_rank[n], total = koff[n]): indices[rank] = i and
+// new_off[rank] = koff[i] for every kept haystack (new_off[n_kept] = total); per run its source position run_src = src_offsets[first] and its destination run_dst =
+// koff[first] (run_dst[n_runs] = total: the closing entry launch_split_gather wants)
+hipError_t launch_select_emit(const uint32_t* keep, const uint32_t* run_head, const uint64_t* rank, const uint64_t* run_rank, const uint64_t* koff, const uint64_t* src_offsets,
+                              uint64_t n, uint64_t n_kept, uint64_t n_runs, uint32_t* indices, uint64_t* new_off, uint64_t* run_src, uint64_t* run_dst, hipStream_t st);
+// am_select_geometry: bytes of new text per workgroup of launch_split_gather (am_split.hip), elements per workgroup of launch_scan / a sweep of launch_scan_jobs (am_scan.hip)
+uint32_t split_gather_tile_bytes();
+uint32_t scan_tile_items();
 // incremental re-scan between Replacer passes (am_replace.hip)
 struct RpWin { uint64_t src_abs; uint64_t ws; uint32_t len; uint32_t own_lo; };   // window: bytes src_abs.. of the next text; ws = its start inside the haystack; records with end > own_lo are its own
 hipError_t launch_rp_win_count(const RpHay* hs, uint32_t n_act, uint32_t* nwin, hipStream_t st);

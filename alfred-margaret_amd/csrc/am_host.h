@@ -210,11 +210,43 @@ int prepare(const am_automaton* ca, int case_mode, const Flavor** out);         
 int finish_batch(am_batch* b);                                                               // workspaces of a batch whose text and offsets are in place
 // am_run.cpp, the scans.  am_run_batch (allow_small: the one-document path may take the call); am_run_range and the segmented am_run ask for the general path
 int run_batch_impl(const am_automaton* a, int case_mode, const am_batch* cb, am_matches** out, bool allow_small);
+// Where the per-haystack flags of a containsAny / containsAll scan go.  The scans leave them in HBM; the public entry points copy them to the caller (HostFlagSink), a
+// select compacts them where they are (am_select.cpp).
+struct FlagSink {
+    virtual ~FlagSink() = default;
+    virtual int begin(const am_batch* b) = 0;               // once, after the entry point's own checks and before any scan
+    // the flags of the batch: n_hay bytes in HBM, the work that writes them enqueued on st.  Called with b->mu held where they are the batch's scratch (b->flags): the sink
+    // has taken what it needs when it returns
+    virtual int device(const uint8_t* d_flags, hipStream_t st) = 0;
+    virtual int constant(uint8_t v) = 0;                    // nothing was scanned: every flag is v
+};
+// ... into n_hay bytes of host memory, as am_contains_any_batch (clear_first: zeroed in begin) and am_contains_all_batch hand them out
+struct HostFlagSink : FlagSink {
+    uint8_t* out; bool clear_first; uint32_t n = 0;
+    HostFlagSink(uint8_t* flags_out, bool clear) : out(flags_out), clear_first(clear) {}
+    int begin(const am_batch* b) override
+    {
+        n = b->n_hay;
+        if (n && !out) return fail(AM_ERR_INVALID, "flags_out is null");
+        if (n && clear_first) std::memset(out, 0, n);
+        return AM_OK;
+    }
+    int device(const uint8_t* d_flags, hipStream_t st) override
+    {
+        ResultCopies rc;
+        AM_TRY(rc.add(out, d_flags, n, st));
+        return rc.finish(st);
+    }
+    int constant(uint8_t v) override { if (n) std::memset(out, v, n); return AM_OK; }
+};
+// am_contains_any_batch / am_contains_all_batch with the flags handed to a sink (am_run.cpp, am_contains_all.cpp)
+int contains_any_flags(const am_automaton* a, int case_mode, am_batch* b, FlagSink& sink);
+int contains_all_flags(const am_needle_ids* ids, int case_mode, am_batch* b, FlagSink& sink);
 // Searcher.containsAll without records (k_sf's ids mode): every reported needle id into the haystack's row of d_bits (n_hay x words, cleared here),
-// flags_out[h] = 1 iff all n_needles ids were seen; *taken = false when the automaton does not go this way (general kernel forced, the empty needle's
+// flag h = 1 iff all n_needles ids were seen, handed to the sink; *taken = false when the automaton does not go this way (general kernel forced, the empty needle's
 // dense pass, nothing to scan) and the caller folds the records instead.
 int scan_needle_ids(const am_automaton* a, int case_mode, am_batch* b, const uint64_t* d_vals_off, const uint32_t* d_vals, uint32_t n_needles,
-                    uint32_t* d_bits, uint32_t words, uint32_t* d_missing, uint8_t* flags_out, bool* taken);
+                    uint32_t* d_bits, uint32_t words, uint32_t* d_missing, FlagSink& sink, bool* taken);
 // sorted records of a batch: sink_final(n, &ptr) names the destination once the count is known
 int run_records(const am_automaton* a, int case_mode, am_batch* b, const std::function<int(uint64_t, Record**)>& sink_final, uint64_t* n_out, bool have_lock = false);
 // the same without a host round trip (suffix-filter route, worst-case pool): the count stays on the device

@@ -232,7 +232,7 @@ struct SfEmit {
 
 // count / containsAny of an automaton with the empty needle on the suffix-filter route: a record at almost every position, so
 // the records are made (k_sf + dense pass) and reduced
-static int reduce_dense(const am_automaton* a, int case_mode, am_batch* b, uint64_t* counts_out, uint64_t* total_out, uint8_t* flags_out)
+static int reduce_dense(const am_automaton* a, int case_mode, am_batch* b, uint64_t* counts_out, uint64_t* total_out, FlagSink* flag_sink)
 {
     uint64_t n_rec = 0;
     auto sink = [&](uint64_t n, Record** ptr) -> int { AM_TRY(b->dense_out.ensure(n * sizeof(Record))); *ptr = (Record*)b->dense_out.p; return AM_OK; };
@@ -240,20 +240,20 @@ static int reduce_dense(const am_automaton* a, int case_mode, am_batch* b, uint6
     AM_TRY(prepare(a, case_mode, &f));
     std::lock_guard<std::mutex> lk(b->mu);          // ONE lock over the scan and the reduction: b->dense_out must not be refilled by another thread in between
     AM_TRY(run_records(a, case_mode, b, sink, &n_rec, true));
-    if (n_rec == 0) return AM_OK;
+    if (n_rec == 0) return flag_sink ? flag_sink->constant(0) : AM_OK;
     ON_DEVICE(b->dev);
     hipStream_t st; AM_TRY(get_stream(b->dev, &st));
     AM_TRY(b->small.ensure(64));
     HIP_TRY(hipMemsetAsync(b->small.p, 0, 64, st));
     if (counts_out) { AM_TRY(b->hay_counts.ensure((size_t)b->n_hay * 8)); HIP_TRY(hipMemsetAsync(b->hay_counts.p, 0, (size_t)b->n_hay * 8, st)); }
-    if (flags_out) { AM_TRY(b->flags.ensure(b->n_hay)); HIP_TRY(hipMemsetAsync(b->flags.p, 0, b->n_hay, st)); }
+    if (flag_sink) { AM_TRY(b->flags.ensure(b->n_hay)); HIP_TRY(hipMemsetAsync(b->flags.p, 0, b->n_hay, st)); }
     const AcView ac = make_ac_view(f->d_image, f->h);
     HIP_TRY(launch_records_reduce((const Record*)b->dense_out.p, n_rec, ac.vlen, counts_out ? (uint64_t*)b->hay_counts.p : nullptr, (uint64_t*)b->small.p,
-                                  flags_out ? (uint8_t*)b->flags.p : nullptr, st));
+                                  flag_sink ? (uint8_t*)b->flags.p : nullptr, st));
     uint64_t total = 0;
     HIP_TRY(hipMemcpyAsync(&total, b->small.p, 8, hipMemcpyDeviceToHost, st));
     if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, b->hay_counts.p, (size_t)b->n_hay * 8, hipMemcpyDeviceToHost, st));
-    if (flags_out) HIP_TRY(hipMemcpyAsync(flags_out, b->flags.p, b->n_hay, hipMemcpyDeviceToHost, st));
+    if (flag_sink) AM_TRY(flag_sink->device((const uint8_t*)b->flags.p, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (total_out) *total_out = total;
     return AM_OK;
@@ -292,14 +292,13 @@ extern "C" int am_count_batch(const am_automaton* a, int case_mode, const am_bat
     return AM_OK;
 }
 
-extern "C" int am_contains_any_batch(const am_automaton* a, int case_mode, const am_batch* cb, uint8_t* flags_out)
+// containsAny with the flags left in HBM: the sink decides what becomes of them (am_contains_any_batch: the copy to the caller; a select: the compaction)
+int am::host::contains_any_flags(const am_automaton* a, int case_mode, am_batch* b, FlagSink& sink)
 {
-    am_batch* b = const_cast<am_batch*>(cb);
     Plan p; AM_TRY(make_plan(a, case_mode, b, p, true));
-    if (!flags_out && b->n_hay) return fail(AM_ERR_INVALID, "flags_out is null");
-    if (b->n_hay) std::memset(flags_out, 0, b->n_hay);
-    if (p.nothing) return AM_OK;
-    if (p.dense) return reduce_dense(a, case_mode, b, nullptr, nullptr, flags_out);
+    AM_TRY(sink.begin(b));
+    if (p.nothing) return sink.constant(0);
+    if (p.dense) return reduce_dense(a, case_mode, b, nullptr, nullptr, &sink);
     std::lock_guard<std::mutex> lk(b->mu);
     ON_DEVICE(b->dev);
     hipStream_t st; AM_TRY(get_stream(b->dev, &st));
@@ -310,14 +309,17 @@ extern "C" int am_contains_any_batch(const am_automaton* a, int case_mode, const
     o.flags = (uint8_t*)b->flags.p;
     AM_TRY(build_hidx_and_clear(p, b, st, b->flags.p, ((size_t)b->n_hay + 3) & ~(size_t)3, b->small.p, 64));      // (the counter block: k_sf's unit ticket)
     AM_TRY(launch_scan_kernel(p, kModeAny, o, st));
-    ResultCopies rc;
-    AM_TRY(rc.add(flags_out, b->flags.p, b->n_hay, st));
-    AM_TRY(rc.finish(st));
-    return AM_OK;
+    return sink.device((const uint8_t*)b->flags.p, st);
+}
+
+extern "C" int am_contains_any_batch(const am_automaton* a, int case_mode, const am_batch* cb, uint8_t* flags_out)
+{
+    HostFlagSink sink(flags_out, true);
+    return contains_any_flags(a, case_mode, const_cast<am_batch*>(cb), sink);
 }
 
 int am::host::scan_needle_ids(const am_automaton* a, int case_mode, am_batch* b, const uint64_t* d_vals_off, const uint32_t* d_vals, uint32_t n_needles,
-                              uint32_t* d_bits, uint32_t words, uint32_t* d_missing, uint8_t* flags_out, bool* taken)
+                              uint32_t* d_bits, uint32_t words, uint32_t* d_missing, FlagSink& sink, bool* taken)
 {
     *taken = false;
     Plan p; AM_TRY(make_plan(a, case_mode, b, p));
@@ -335,9 +337,7 @@ int am::host::scan_needle_ids(const am_automaton* a, int case_mode, am_batch* b,
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_missing, (int)n_needles, b->n_hay, st));
     AM_TRY(build_hidx_and_clear(p, b, st, b->flags.p, ((size_t)b->n_hay + 3) & ~(size_t)3, b->small.p, 64));      // (the counter block: k_sf's unit ticket)
     AM_TRY(launch_scan_kernel(p, kModeIds, o, st));
-    ResultCopies rc;
-    AM_TRY(rc.add(flags_out, b->flags.p, b->n_hay, st));
-    AM_TRY(rc.finish(st));
+    AM_TRY(sink.device((const uint8_t*)b->flags.p, st));
     *taken = true;
     return AM_OK;
 }

@@ -89,6 +89,8 @@ hipError_t scan_any(void* temp, size_t temp_bytes, const T* in, uint64_t* out, u
 }
 }  // namespace
 
+uint32_t scan_tile_items() { return (uint32_t)kScanTile; }
+
 // bytes of temporary storage for a scan of n elements (either element type)
 hipError_t scan_temp_bytes(uint64_t n, size_t* bytes) { *bytes = ((n + kScanTile - 1) / kScanTile + 1) * sizeof(uint64_t); return hipSuccess; }
 hipError_t scan64_temp_bytes(uint64_t n, size_t* bytes) { return scan_temp_bytes(n, bytes); }

@@ -1,0 +1,294 @@
+// am_select.cpp -- select on the device (include/am.h "select"): keep the haystacks of a batch that a predicate holds for, drop the rest, and hand the kept ones on
+// as a batch of their own -- `grep -F -f needles`, `grep -v`, `grep -w` and "the lines that mention all of these terms" between two stages of a pipeline in HBM.
+// The predicates are the library's own: the flags of the containsAny / containsAll scans, taken where the scans leave them (FlagSink, am_host.h), and the non-empty
+// rows of AM_SPANS_ALL (spans_flags, am_contains_all.cpp).  The compaction by runs is am_select.hip's; the bytes move with am_split.hip's gather.  What crosses to the
+// host during a *_batch select: the kept count, the run count and the kept bytes (one copy of three words), and whatever the scans read back themselves.
+// Every argument is checked before any device work.
+#include "am_spans.h"
+
+using namespace am;
+using namespace am::dev;
+using namespace am::host;
+
+// which haystacks of a batch were kept: ascending source indices, their new offsets, and the runs the gather copies.  (Holds DevBufs: on the heap only.)
+struct am_selection {
+    int dev = 0;
+    uint64_t n_src = 0, src_total = 0;                      // the batch it was made from (am_batch_from_selection checks both)
+    uint64_t n_kept = 0, n_runs = 0, total = 0;
+    DevBuf indices, new_off, run_src, run_dst;              // uint32[n_kept], uint64[n_kept + 1], uint64[n_runs + 1] each (none when n_src == 0)
+    std::vector<uint32_t> h_indices; bool fetched = false;
+};
+
+namespace {
+
+using SelectionPtr = std::unique_ptr<am_selection, void (*)(am_selection*)>;
+using BatchPtr = std::unique_ptr<am_batch, void (*)(am_batch*)>;
+
+constexpr uint64_t kOneLaunchSums = 1ull << 16;             // up to here the three exclusive sums take one launch (launch_scan_jobs), beyond it three launches each
+
+// the compaction of n = b->n_hay > 0 flags in HBM (d_flags null: every flag is `constant`) into s; returns when the device has finished with the flags
+int compact(const am_batch* b, const uint8_t* d_flags, uint8_t constant, int invert, hipStream_t st, am_selection* s)
+{
+    const uint64_t n = b->n_hay;
+    DevBuf keep, run_head, klen, rank, run_rank, koff, scan_tmp;
+    AM_TRY(keep.ensure((n + 1) * 4));
+    AM_TRY(run_head.ensure((n + 1) * 4));
+    AM_TRY(klen.ensure((n + 1) * 8));
+    AM_TRY(rank.ensure((n + 1) * 8));
+    AM_TRY(run_rank.ensure((n + 1) * 8));
+    AM_TRY(koff.ensure((n + 1) * 8));
+    { Prof pr("select_plan", st);
+      HIP_TRY(launch_select_plan(d_flags, constant, invert ? 1u : 0u, b->d_offsets, n, b->total, (uint32_t*)keep.p, (uint32_t*)run_head.p, (uint64_t*)klen.p, st)); }
+    if (n + 1 <= kOneLaunchSums) {
+        ScanJobs jobs{}; jobs.n_jobs = 3;
+        jobs.j[0] = ScanJob{(const uint32_t*)keep.p, nullptr, (uint64_t*)rank.p, n + 1, nullptr};
+        jobs.j[1] = ScanJob{(const uint32_t*)run_head.p, nullptr, (uint64_t*)run_rank.p, n + 1, nullptr};
+        jobs.j[2] = ScanJob{nullptr, (const uint64_t*)klen.p, (uint64_t*)koff.p, n + 1, nullptr};
+        HIP_TRY(launch_scan_jobs(jobs, st));
+    } else {
+        size_t tmp_bytes = 0;
+        HIP_TRY(scan64_temp_bytes(n + 1, &tmp_bytes));
+        AM_TRY(scan_tmp.ensure(tmp_bytes));
+        HIP_TRY(launch_scan(scan_tmp.p, scan_tmp.cap, (const uint32_t*)keep.p, (uint64_t*)rank.p, n + 1, st));
+        HIP_TRY(launch_scan(scan_tmp.p, scan_tmp.cap, (const uint32_t*)run_head.p, (uint64_t*)run_rank.p, n + 1, st));
+        HIP_TRY(launch_scan64(scan_tmp.p, scan_tmp.cap, (const uint64_t*)klen.p, (uint64_t*)koff.p, n + 1, st));
+    }
+    uint64_t tail[3] = {0, 0, 0};                           // the three scalars that cross
+    HIP_TRY(hipMemcpyAsync(&tail[0], (const uint64_t*)rank.p + n, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&tail[1], (const uint64_t*)run_rank.p + n, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&tail[2], (const uint64_t*)koff.p + n, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));                      // (the flags have been read: the batch's scratch is free again)
+    s->n_kept = tail[0]; s->n_runs = tail[1]; s->total = tail[2];
+    if (s->n_kept > n || s->n_runs > s->n_kept || s->total > b->total) return fail(AM_ERR_HIP, "select: the compaction's sums are out of range");
+    AM_TRY(s->indices.ensure(s->n_kept * 4));
+    AM_TRY(s->new_off.ensure((s->n_kept + 1) * 8));
+    AM_TRY(s->run_src.ensure((s->n_runs + 1) * 8));
+    AM_TRY(s->run_dst.ensure((s->n_runs + 1) * 8));
+    { Prof pr("select_emit", st);
+      HIP_TRY(launch_select_emit((const uint32_t*)keep.p, (const uint32_t*)run_head.p, (const uint64_t*)rank.p, (const uint64_t*)run_rank.p, (const uint64_t*)koff.p,
+                                 b->d_offsets, n, s->n_kept, s->n_runs, (uint32_t*)s->indices.p, (uint64_t*)s->new_off.p, (uint64_t*)s->run_src.p, (uint64_t*)s->run_dst.p, st)); }
+    HIP_TRY(hipStreamSynchronize(st));                      // (the workspaces are freed; a selection may be used from any thread and stream afterwards)
+    return AM_OK;
+}
+
+// the sink of a containsAny / containsAll scan that compacts the flags where the scan left them
+struct SelectSink : FlagSink {
+    const am_batch* b; int invert; am_selection* s;
+    SelectSink(const am_batch* batch, int inv, am_selection* sel) : b(batch), invert(inv), s(sel) {}
+    int begin(const am_batch*) override { return AM_OK; }
+    int device(const uint8_t* d_flags, hipStream_t st) override { return compact(b, d_flags, 0, invert, st, s); }
+    int constant(uint8_t v) override
+    {
+        ON_DEVICE(b->dev);
+        hipStream_t st; AM_TRY(get_stream(b->dev, &st));
+        return compact(b, nullptr, v, invert, st, s);
+    }
+};
+
+SelectionPtr new_selection(const am_batch* b)
+{
+    SelectionPtr s(new am_selection(), am_selection_free);
+    s->dev = b->dev; s->n_src = b->n_hay; s->src_total = b->total;
+    if (b->n_hay == 0) { s->h_indices.assign(1, 0); s->fetched = true; }      // nothing to select from: nothing in HBM
+    return s;
+}
+
+// a batch of the library's own without haystacks: offsets = [0], one group of zeros
+int empty_batch(int dev, am_batch** out)
+{
+    ON_DEVICE(dev);
+    hipStream_t st; AM_TRY(get_stream(dev, &st));
+    BatchPtr nb(new am_batch(), am_batch_destroy);
+    nb->dev = dev; nb->owns = true;
+    AM_TRY(nb->offs_buf.ensure(8));
+    AM_TRY(nb->text_buf.ensure(padded_text(0)));
+    HIP_TRY(hipMemsetAsync(nb->offs_buf.p, 0, 8, st));
+    HIP_TRY(hipMemsetAsync(nb->text_buf.p, 0, padded_text(0), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    nb->d_text = nb->text_buf.p; nb->d_offsets = (uint64_t*)nb->offs_buf.p;
+    AM_TRY(finish_batch(nb.get()));
+    *out = nb.release();
+    return AM_OK;
+}
+
+// the one-shot forms: the slices into the calling thread's batch on `dev`, then the batch form
+template <class BatchForm>
+int select_slices(int dev, const am_slice* hay, size_t n_hay, BatchForm&& batch_form)
+{
+    ON_DEVICE(dev);
+    am_batch* b = oneshot_batch(dev);
+    int rc = upload_batch(hay, n_hay, b, true);
+    if (rc == AM_OK) rc = batch_form(b);
+    oneshot_batch_trim(dev);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int am_select_any_batch(const am_automaton* a, int case_mode, int invert, const am_batch* cb, am_selection** out)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    AM_TRY(check_case(case_mode));
+    if (!a || !cb) return fail(AM_ERR_INVALID, "null automaton or batch");
+    if (a->dev != cb->dev) return fail(AM_ERR_INVALID, "automaton and batch live on different devices");
+    AM_TRY(ensure_runtime());
+    am_batch* b = const_cast<am_batch*>(cb);
+    SelectionPtr s = new_selection(b);
+    if (b->n_hay != 0) {
+        SelectSink sink(b, invert, s.get());
+        AM_TRY(contains_any_flags(a, case_mode, b, sink));
+    }
+    *out = s.release();
+    return AM_OK;
+}
+
+extern "C" int am_select_all_batch(const am_needle_ids* ids, int case_mode, int invert, const am_batch* cb, am_selection** out)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    AM_TRY(check_case(case_mode));
+    if (!ids || !cb) return fail(AM_ERR_INVALID, "null needle ids or batch");
+    if (ids->a->dev != cb->dev) return fail(AM_ERR_INVALID, "needle ids and batch live on different devices");
+    AM_TRY(ensure_runtime());
+    am_batch* b = const_cast<am_batch*>(cb);
+    SelectionPtr s = new_selection(b);
+    if (b->n_hay != 0) {
+        SelectSink sink(b, invert, s.get());
+        AM_TRY(contains_all_flags(ids, case_mode, b, sink));
+    }
+    *out = s.release();
+    return AM_OK;
+}
+
+extern "C" int am_select_spans_batch(const am_span_table* t, int case_mode, int invert, const am_batch* cb, am_selection** out)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    AM_TRY(check_case(case_mode));
+    if (!t || !cb) return fail(AM_ERR_INVALID, "null span table or batch");
+    if (t->ids->a->dev != cb->dev) return fail(AM_ERR_INVALID, "span table and batch live on different devices");
+    AM_TRY(ensure_runtime());
+    am_batch* b = const_cast<am_batch*>(cb);
+    SelectionPtr s = new_selection(b);
+    if (b->n_hay != 0) {
+        ON_DEVICE(b->dev);
+        hipStream_t st; AM_TRY(get_stream(b->dev, &st));
+        DevBuf flags;                                       // the call's own: the scans of the groups use the batch's scratch
+        AM_TRY(flags.ensure(b->n_hay));
+        AM_TRY(spans_flags(t, case_mode, b, (uint8_t*)flags.p));
+        AM_TRY(compact(b, (const uint8_t*)flags.p, 0, invert, st, s.get()));
+    }
+    *out = s.release();
+    return AM_OK;
+}
+
+extern "C" int am_select_flags(const am_batch* b, const uint8_t* host_flags, int invert, am_selection** out)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    if (!b) return fail(AM_ERR_INVALID, "null batch");
+    if (b->n_hay && !host_flags) return fail(AM_ERR_INVALID, "flags is null");
+    AM_TRY(ensure_runtime());
+    SelectionPtr s = new_selection(b);
+    if (b->n_hay != 0) {
+        ON_DEVICE(b->dev);
+        hipStream_t st; AM_TRY(get_stream(b->dev, &st));
+        DevBuf flags;
+        AM_TRY(flags.ensure(b->n_hay));
+        HIP_TRY(hipMemcpyAsync(flags.p, host_flags, b->n_hay, hipMemcpyHostToDevice, st));
+        AM_TRY(compact(b, (const uint8_t*)flags.p, 0, invert, st, s.get()));
+    }
+    *out = s.release();
+    return AM_OK;
+}
+
+extern "C" int am_select_any(const am_automaton* a, int case_mode, int invert, const am_slice* hay, size_t n_hay, am_selection** out)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    AM_TRY(check_slices(hay, n_hay));
+    AM_TRY(check_case(case_mode));
+    if (!a) return fail(AM_ERR_INVALID, "null automaton");      // (last: a caller without a device can see every other check)
+    AM_TRY(ensure_runtime());                               // (the last of what a caller without a device can see; the handle is not looked at before)
+    return select_slices(a->dev, hay, n_hay, [&](am_batch* b) { return am_select_any_batch(a, case_mode, invert, b, out); });
+}
+
+extern "C" int am_select_all(const am_needle_ids* ids, int case_mode, int invert, const am_slice* hay, size_t n_hay, am_selection** out)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    AM_TRY(check_slices(hay, n_hay));
+    AM_TRY(check_case(case_mode));
+    if (!ids) return fail(AM_ERR_INVALID, "null needle ids");
+    AM_TRY(ensure_runtime());
+    return select_slices(ids->a->dev, hay, n_hay, [&](am_batch* b) { return am_select_all_batch(ids, case_mode, invert, b, out); });
+}
+
+extern "C" uint64_t am_selection_size(const am_selection* s) { return s ? s->n_kept : 0; }
+extern "C" uint64_t am_selection_source_haystacks(const am_selection* s) { return s ? s->n_src : 0; }
+extern "C" uint64_t am_selection_total_bytes(const am_selection* s) { return s ? s->total : 0; }
+extern "C" const void* am_selection_device_indices(const am_selection* s) { return s && s->n_kept ? s->indices.p : nullptr; }
+
+extern "C" const uint32_t* am_selection_indices(am_selection* s)
+{
+    if (!s) { fail(AM_ERR_INVALID, "null selection"); return nullptr; }
+    if (s->fetched) return s->h_indices.data();
+    try { s->h_indices.resize((size_t)std::max<uint64_t>(s->n_kept, 1)); } catch (const std::exception&) { fail(AM_ERR_OOM, "no host memory for the selection's indices"); return nullptr; }
+    if (s->n_kept) {
+        if (ensure_runtime() != AM_OK) return nullptr;
+        OnDevice od(s->dev);
+        hipStream_t st;
+        if (od.rc != AM_OK || get_stream(s->dev, &st) != AM_OK) return nullptr;
+        if (hipMemcpyAsync(s->h_indices.data(), s->indices.p, (size_t)s->n_kept * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+            fail(AM_ERR_HIP, "copying the selection's indices to the host failed");
+            return nullptr;
+        }
+    }
+    s->fetched = true;
+    return s->h_indices.data();
+}
+
+extern "C" void am_selection_free(am_selection* s)
+{
+    if (!s) return;
+    OnDevice od(s->dev);
+    delete s;
+}
+
+extern "C" int am_batch_from_selection(const am_batch* src, const am_selection* s, am_batch** out)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    if (!src || !s) return fail(AM_ERR_INVALID, "null batch or selection");
+    if (s->n_src != src->n_hay || s->src_total != src->total || s->dev != src->dev)
+        return fail(AM_ERR_INVALID, "the selection was not made from a batch with this haystack count and size");
+    AM_TRY(ensure_runtime());
+    if (s->n_kept == 0) return empty_batch(src->dev, out);
+    ON_DEVICE(src->dev);
+    hipStream_t st; AM_TRY(get_stream(src->dev, &st));
+    BatchPtr nb(new am_batch(), am_batch_destroy);
+    nb->dev = src->dev; nb->owns = true;
+    const uint64_t total = s->total;
+    const size_t padded = padded_text(total);
+    AM_TRY(nb->offs_buf.ensure((s->n_kept + 1) * 8));
+    AM_TRY(nb->text_buf.ensure(padded));
+    HIP_TRY(hipMemcpyAsync(nb->offs_buf.p, s->new_off.p, (s->n_kept + 1) * 8, hipMemcpyDeviceToDevice, st));
+    const uint64_t whole = total & ~15ull;
+    HIP_TRY(hipMemsetAsync((uint8_t*)nb->text_buf.p + whole, 0, padded - whole, st));            // zero tail: kernels read whole 16-byte groups
+    { Prof pr("select_gather", st);
+      HIP_TRY(launch_split_gather((const uint8_t*)src->d_text, src->total, (const uint64_t*)s->run_src.p, (const uint64_t*)s->run_dst.p, s->n_runs, total,
+                                  (uint8_t*)nb->text_buf.p, g_rt.dev[src->dev].n_cu, st)); }
+    HIP_TRY(hipStreamSynchronize(st));                      // a batch object may be used from any thread and stream afterwards
+    nb->d_text = nb->text_buf.p; nb->d_offsets = (uint64_t*)nb->offs_buf.p;
+    nb->total = total; nb->n_hay = (uint32_t)s->n_kept;
+    AM_TRY(finish_batch(nb.get()));
+    *out = nb.release();
+    return AM_OK;
+}
+
+extern "C" void am_select_geometry(uint32_t* tile_bytes, uint32_t* scan_block_items)
+{
+    if (tile_bytes) *tile_bytes = split_gather_tile_bytes();
+    if (scan_block_items) *scan_block_items = scan_tile_items();
+}

@@ -1,0 +1,131 @@
+// am_select.hip -- select on the device (include/am.h "select"): the haystacks of a batch that a predicate keeps, as ascending indices and as a batch of their own.
+//
+// The predicate arrives as one byte per haystack in HBM: the flags of the containsAny / containsAll scans, or k_hay_flags_spans over the sorted records of a scan --
+// haystack h is flagged when one of its (record, value) pairs is a span the table keeps (span_of, am_words.h: the function the span expansion and the whole-word
+// histogram decide with), i.e. when row h of AM_SPANS_ALL is not empty.
+//
+// The compaction works on RUNS.  A batch stores its haystacks back to back, so a maximal sequence of consecutive kept haystacks is ONE contiguous piece of the source
+// text.  k_select_plan turns the flags into keep / run_head / the kept lengths, three exclusive sums (am_scan.hip) give every kept haystack its rank and its new offset
+// and every run its rank, and k_select_emit writes the indices, the new offsets and per run (source position, destination position).  The bytes then move with
+// launch_split_gather (am_split.hip) with the runs as its fragments: keeping everything is one run and a straight copy, keeping alternate haystacks gives `kept` runs.
+// All positions and totals are 64-bit; the only 32-bit quantities are haystack indices (n_hay < 2^32 - 1 for every batch).  Plain C++ and vector stores only.
+#include <hip/hip_runtime.h>
+
+#include "am_bounds.h"
+#include "am_device.h"
+#include "am_wave.h"
+#include "am_words.h"
+
+AM_BOUNDS_TU("am_select.hip")
+
+namespace am {
+namespace dev {
+
+namespace {
+
+constexpr uint32_t kSelThreads = 256;
+
+inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kSelThreads - 1) / kSelThreads); }
+__device__ __forceinline__ uint64_t global_lane() { return (uint64_t)blockIdx.x * kSelThreads + threadIdx.x; }
+
+// one lane per record: the first of its values whose span the table keeps flags the record's haystack, the remaining values are skipped (several lanes may store the
+// same 1 into the same byte)
+template <bool IC, bool WORDS>
+__global__ void __launch_bounds__(kSelThreads) k_hay_flags_spans(SpansIn in, uint8_t* __restrict__ flags)
+{
+    const uint64_t i = global_lane();
+    if (i >= in.n_rec) return;
+    const Record r = in.recs[i];
+    AM_BOUNDS(r.haystack < in.n_hay && r.state < in.n_states);
+    if (r.haystack >= in.n_hay || r.state >= in.n_states) return;
+    uint64_t v0 = in.vals_off[r.state], v1 = in.vals_off[r.state + 1];
+    AM_BOUNDS(v0 <= v1 && v1 <= in.n_values);
+    if (v1 > in.n_values) v1 = in.n_values;
+    for (uint64_t k = v0; k < v1; k++) {
+        const uint32_t v = in.vals[k];
+        if (v >= in.n_needles) continue;                               // the am_needle_ids convention: skipped
+        uint64_t s, n;
+        if (!span_of<IC, WORDS>(in, r, v, in.words, s, n)) continue;
+        flags[r.haystack] = 1;
+        return;
+    }
+}
+
+// one lane per haystack (+ one for the trailing zero of the scans' inputs)
+__global__ void __launch_bounds__(kSelThreads) k_select_plan(const uint8_t* __restrict__ flags, uint32_t constant, uint32_t invert, const uint64_t* __restrict__ src_offsets,
+                                                             uint64_t n, uint64_t src_total, uint32_t* __restrict__ keep, uint32_t* __restrict__ run_head,
+                                                             uint64_t* __restrict__ klen)
+{
+    const uint64_t i = global_lane();
+    if (i > n) return;
+    if (i == n) { keep[i] = 0; run_head[i] = 0; klen[i] = 0; return; }
+    const bool inv = invert != 0;
+    const bool k = ((flags ? flags[i] : constant) != 0) != inv;
+    const bool before = i > 0 && ((flags ? flags[i - 1] : constant) != 0) != inv;
+    const uint64_t o0 = src_offsets[i], o1 = src_offsets[i + 1];
+    AM_BOUNDS(o0 <= o1 && o1 <= src_total);
+    const uint64_t len = o0 <= o1 && o1 <= src_total ? o1 - o0 : 0;
+    keep[i] = k ? 1u : 0u;
+    run_head[i] = k && !before ? 1u : 0u;
+    klen[i] = k ? len : 0;
+}
+
+// one lane per haystack (+ one for the closing entries)
+__global__ void __launch_bounds__(kSelThreads) k_select_emit(const uint32_t* __restrict__ keep, const uint32_t* __restrict__ run_head, const uint64_t* __restrict__ rank,
+                                                             const uint64_t* __restrict__ run_rank, const uint64_t* __restrict__ koff,
+                                                             const uint64_t* __restrict__ src_offsets, uint64_t n, uint64_t n_kept, uint64_t n_runs,
+                                                             uint32_t* __restrict__ indices, uint64_t* __restrict__ new_off, uint64_t* __restrict__ run_src,
+                                                             uint64_t* __restrict__ run_dst)
+{
+    const uint64_t i = global_lane();
+    if (i > n) return;
+    if (i == n) {
+        AM_BOUNDS(rank[n] == n_kept && run_rank[n] == n_runs);
+        new_off[n_kept] = koff[n];
+        run_dst[n_runs] = koff[n];
+        run_src[n_runs] = 0;
+        return;
+    }
+    if (!keep[i]) return;
+    const uint64_t r = rank[i];
+    AM_BOUNDS(r < n_kept);
+    if (r >= n_kept) return;
+    indices[r] = (uint32_t)i;
+    new_off[r] = koff[i];
+    if (!run_head[i]) return;
+    const uint64_t q = run_rank[i];
+    AM_BOUNDS(q < n_runs);
+    if (q >= n_runs) return;
+    run_src[q] = src_offsets[i];
+    run_dst[q] = koff[i];
+}
+
+}  // namespace
+
+hipError_t launch_hay_flags_spans(bool ic, const SpansIn& in, uint8_t* flags, hipStream_t st)
+{
+    if (in.n_rec == 0) return hipSuccess;
+    const dim3 grid(blocks_for(in.n_rec)), block(kSelThreads);
+    if (!in.words) hipLaunchKernelGGL((k_hay_flags_spans<false, false>), grid, block, 0, st, in, flags);      // (no class: every span is kept, no start is needed, so no case mode)
+    else if (ic) hipLaunchKernelGGL((k_hay_flags_spans<true, true>), grid, block, 0, st, in, flags);
+    else hipLaunchKernelGGL((k_hay_flags_spans<false, true>), grid, block, 0, st, in, flags);
+    return hipGetLastError();
+}
+
+hipError_t launch_select_plan(const uint8_t* flags, uint32_t constant, uint32_t invert, const uint64_t* src_offsets, uint64_t n, uint64_t src_total, uint32_t* keep,
+                              uint32_t* run_head, uint64_t* klen, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_select_plan, dim3(blocks_for(n + 1)), dim3(kSelThreads), 0, st, flags, constant, invert, src_offsets, n, src_total, keep, run_head, klen);
+    return hipGetLastError();
+}
+
+hipError_t launch_select_emit(const uint32_t* keep, const uint32_t* run_head, const uint64_t* rank, const uint64_t* run_rank, const uint64_t* koff, const uint64_t* src_offsets,
+                              uint64_t n, uint64_t n_kept, uint64_t n_runs, uint32_t* indices, uint64_t* new_off, uint64_t* run_src, uint64_t* run_dst, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_select_emit, dim3(blocks_for(n + 1)), dim3(kSelThreads), 0, st, keep, run_head, rank, run_rank, koff, src_offsets, n, n_kept, n_runs, indices, new_off,
+                       run_src, run_dst);
+    return hipGetLastError();
+}
+
+}  // namespace dev
+}  // namespace am

@@ -12,6 +12,13 @@ struct am_span_table {
     const uint32_t* d_words() const { return has_words ? (const uint32_t*)words.p : nullptr; }
 };
 
+namespace am {
+namespace host {
+// d_flags[h] = 1 iff row h of am_spans_batch(t, case_mode, AM_SPANS_ALL, b) is not empty, in bounded record memory (am_contains_all.cpp, beside the whole-word counts)
+int spans_flags(const am_span_table* t, int case_mode, am_batch* b, uint8_t* d_flags);
+}  // namespace host
+}  // namespace am
+
 struct am_spans : am::host::CsrResult<am_span> {
     uint32_t rounds = 0;                                    // pointer-doubling rounds of the call
     int mode = AM_SPANS_ALL;                                // what am_batch_substitute holds a result to: the selection, the table's handles and the batch it was made from

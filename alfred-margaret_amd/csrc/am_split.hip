@@ -247,6 +247,8 @@ __global__ void __launch_bounds__(kSplitThreads) k_split_gather(const uint8_t* _
 
 }  // namespace
 
+uint32_t split_gather_tile_bytes() { return (uint32_t)kGatherTile; }
+
 hipError_t launch_split_start(bool ic, const SplitIn& in, uint64_t* start, uint8_t* head, uint32_t* kept, hipStream_t st)
 {
     if (ic) hipLaunchKernelGGL(k_split_start<true>, dim3(blocks_for(in.n_rec + 1)), dim3(kSplitThreads), 0, st, in, start, head, kept);

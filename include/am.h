@@ -418,6 +418,45 @@ AM_API int am_span_table_word_bytes(const am_span_table* t, uint8_t* out256 /* n
 AM_API int am_count_spans_by_needle_batch(const am_span_table* t, int case_mode, const am_batch* b, uint64_t* counts_out /* n_needles, host */);
 AM_API int am_count_spans_by_needle(const am_span_table* t, int case_mode, const am_slice* hay, size_t n_hay, uint64_t* counts_out /* n_needles, host */);
 
+/* ---- select: keep the haystacks that match and drop the rest, in HBM; the kept haystacks are a batch of their own ---------------
+ * `grep -F -f needles` (am_select_any*), `grep -v` (invert), `grep -w` (am_select_spans_batch with a table that carries a word class) and "the lines that mention all of
+ * these terms" (am_select_all*) over a batch, without the flags, the texts or the kept texts crossing the wire.  A SELECTION says which haystacks of a batch were kept:
+ * ascending uint32 source indices in HBM, copied to the host on first use.  keep[i] = predicate(haystack i) != (invert != 0):
+ *   am_select_any_batch     the predicate is byte for byte what am_contains_any_batch reports (Searcher.containsAny).
+ *   am_select_all_batch     ... what am_contains_all_batch reports (Searcher.containsAll), with the reference's quirks: [""] is never contained, zero needles is true.
+ *   am_select_spans_batch   row i of am_spans_batch(t, case_mode, AM_SPANS_ALL, b) is not empty.  With a table made by am_span_table_create_words that is
+ *                           (?<!\w)(n1|n2|...)(?!\w) per haystack, filter then select as above; a zero-length span is a span.  Record memory is BOUNDED as in
+ *                           am_count_spans_by_needle_batch (groups of whole haystacks).
+ *   am_select_flags         the caller's own predicate: n_hay flags of host memory, non-zero = true.
+ *   am_select_any, am_select_all   the one-shot forms on host slices: the indices only (the texts are the caller's already).
+ * An empty haystack contains nothing: it is kept under `invert`.  During a *_batch select only scalars cross to the host (the kept count, the kept bytes, the run count
+ * and what the scans read back anyway); the bounded-memory grouping of am_select_spans_batch, where it runs, reads what am_count_spans_by_needle_batch reads.
+ *   am_batch_from_selection  a NEW batch that the library owns, on src's device: one haystack per kept index, in order, offsets = the running sum of their lengths, the
+ *                           text 16-byte aligned, readable to round_up(total, 16) and zero beyond total.  Every *_batch entry point takes it, another select too: a
+ *                           selection of a selection composes through the two index arrays.  Consecutive kept haystacks are contiguous in the source, so the bytes
+ *                           move in RUNS (maximal sequences of consecutive kept haystacks): keeping everything is one straight copy.  src must be the batch the
+ *                           selection was made from: AM_ERR_INVALID when the haystack count, the total bytes or the device differ.  A selection that keeps nothing
+ *                           gives a valid batch of 0 haystacks and 0 bytes.
+ *   am_selection_indices    host, ascending, never NULL on success (a placeholder element for an empty selection); am_selection_device_indices: the same in HBM.
+ *   am_select_geometry      for tests: the gather's tile in bytes, and the haystacks one workgroup of the compaction's exclusive sums handles.
+ * Arguments are checked before any device work: AM_ERR_INVALID for null handles or a null out, a case_mode that is neither of the two, null flags with n_hay > 0, slices
+ * without memory, handles on different devices.  *out is NULL after every failure. */
+typedef struct am_selection am_selection;
+AM_API int am_select_any_batch(const am_automaton* a, int case_mode, int invert, const am_batch* b, am_selection** out);
+AM_API int am_select_all_batch(const am_needle_ids* ids, int case_mode, int invert, const am_batch* b, am_selection** out);
+AM_API int am_select_spans_batch(const am_span_table* t, int case_mode, int invert, const am_batch* b, am_selection** out);
+AM_API int am_select_flags(const am_batch* b, const uint8_t* flags /* n_hay, host; nonzero = true */, int invert, am_selection** out);
+AM_API int am_select_any(const am_automaton* a, int case_mode, int invert, const am_slice* hay, size_t n_hay, am_selection** out);
+AM_API int am_select_all(const am_needle_ids* ids, int case_mode, int invert, const am_slice* hay, size_t n_hay, am_selection** out);
+AM_API uint64_t am_selection_size(const am_selection* s);                 /* haystacks kept */
+AM_API uint64_t am_selection_source_haystacks(const am_selection* s);
+AM_API uint64_t am_selection_total_bytes(const am_selection* s);          /* bytes of the kept haystacks */
+AM_API const uint32_t* am_selection_indices(am_selection* s);
+AM_API const void* am_selection_device_indices(const am_selection* s);
+AM_API void am_selection_free(am_selection* s);
+AM_API int am_batch_from_selection(const am_batch* src, const am_selection* s, am_batch** out);
+AM_API void am_select_geometry(uint32_t* tile_bytes, uint32_t* scan_block_items);
+
 /* Checksum of the fold sequence of a result (harness aid; SURVEY 8d "parity check at scale",
  * benchmark/benchmark.py:65-69 asserts count identity on every run).  For every haystack i < n_hay:
  *   hash_out[i]  = foldl (\h (pos, v) -> h * 0x100000001B3 + mix pos v) 0  over the matches the reference's
