@@ -625,7 +625,10 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
             uint32_t cand = 0;
             if (!kFlagMode || !skip) {
                 // tier 4 (needles of >= 4 bytes): straight-line code, the lane's 32 LDS reads (filter word + mask per
-                // position) are all in flight before the first one is tested
+                // position) are all in flight before the first one is tested.  They go out in the order the tests consume them, 15 .. 0 (DS
+                // operations return in order: the first test waits with lgkmcnt(14) -- for its own two reads and 16 more; the counter's field ends at 15 -- where it waited
+                // for 30 of the 32 reads), and the scheduling barrier keeps the compiler from spreading the reads among the tests (measured both ways, LABNOTES
+                // "k_sf chunk loop").
                 uint32_t h[16], v[16], m[16];
                 const uint32_t sh_word = 32u - log2_words;
 #pragma unroll
@@ -635,15 +638,16 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
                     h[k] = w * kBloomMul;
                 }
 #pragma unroll
-                for (int k = 0; k < 16; k++) {
+                for (int k = 15; k >= 0; k--) {
                     if (LW) v[k] = lds_read_u32(kSfMaskBytes + ((h[k] >> (30 - LW)) & (((1u << LW) - 1u) << 2)));
                     else v[k] = lds_read_u32(kSfMaskBytes + ((h[k] >> sh_word) << 2));
                     m[k] = lds_read_u32(h[k] & ((kBloomMasks - 1u) << 2));
                 }
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int k = 15; k >= 0; k--) {      // bit k of cand = position k; the table mask rotated by product bits 11..15 (scan_mask)
+                for (int k = 15; k >= 0; k--) {      // bit k of cand = position k (the first one shifted in ends up on top); the table mask rotated by product bits 11..15 (scan_mask)
                     const uint32_t mr = rotr32(m[k], scan_rot(h[k]));
-                    cand = (cand << 1) | (uint32_t)((v[k] & mr) == mr);
+                    cand = shift_in_eq(cand, v[k] & mr, mr);      // (cand << 1) | ((v[k] & mr) == mr)
                 }
             }
             if (SHORT && (!kFlagMode || !skip)) {    // automata with 1..3-byte needles: extra probes per position
@@ -665,7 +669,7 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
                 // compact (up to kSfQ1) candidate positions into the wave's LDS queue, in position order
                 const uint32_t n = __popc(cand);
                 const uint32_t incl = wave_inclusive_sum(n, lane);
-                const uint32_t total = __shfl(incl, 63, 64);
+                const uint32_t total = wave_last_lane(incl);      // in an SGPR: n_q1, the loop's exits and every `if` on the round's size are scalar branches
                 if (total == 0 && !(first && pending)) break;
                 uint32_t idx = incl - n;
                 // the loop runs as long as the busiest lane has candidates, so it only queues positions; the probe

@@ -24,6 +24,20 @@ __device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t x, uint32_t /*la
     return x;
 }
 
+// the wave's total of an inclusive prefix sum = lane 63's value, as a scalar (v_readlane_b32): whatever is computed or decided from it stays on the scalar
+// side -- an `if` on it is a scalar branch.  (__shfl(x, 63) is a ds_bpermute: an LDS round trip, and a result in a VGPR that turns every `if` on it into an
+// exec-masked region.)
+__device__ __forceinline__ uint32_t wave_last_lane(uint32_t x) { return (uint32_t)__builtin_amdgcn_readlane((int)x, 63); }
+
+// (acc << 1) | (a == b) in two VOP2/VOPC instructions: the comparison's result goes in as the carry of acc + acc.  The compiler's own code for the C
+// expression is v_cmp + v_cndmask (VOP3) + half a v_lshlrev / v_or3 per step, and no C form of the addition makes it use the carry (tried: acc + (acc +
+// (a == b)) and __builtin_addc both come out as the above).
+__device__ __forceinline__ uint32_t shift_in_eq(uint32_t acc, uint32_t a, uint32_t b)
+{
+    asm("v_cmp_eq_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(acc) : "v"(a), "v"(b) : "vcc");
+    return acc;
+}
+
 // a value that is the same in every lane, moved to scalar registers (the two v_readfirstlane also force any load that
 // produces it to be waited for right here)
 __device__ __forceinline__ uint64_t uniform_u64(uint64_t x)
