@@ -489,7 +489,7 @@ int am::host::finish_batch(am_batch* b)
 }
 
 // Uploads the slices into `b` (re-using its device buffers when they are large enough).
-static int upload_slices(const am_slice* hay, size_t n_hay, am_batch* b, bool oneshot = false)
+int am::host::upload_batch(const am_slice* hay, size_t n_hay, am_batch* b, bool oneshot)
 {
     if (n_hay && !hay) return fail(AM_ERR_INVALID, "hay is null");
     if (n_hay >= 0xFFFFFFFFull) return fail(AM_ERR_INVALID, "too many haystacks");
@@ -623,7 +623,7 @@ extern "C" int am_batch_upload(const am_slice* hay, size_t n_hay, am_batch** out
     *out = nullptr;
     am_batch* b = new am_batch();
     int rc = current_device(&b->dev);
-    if (rc == AM_OK) rc = upload_slices(hay, n_hay, b);
+    if (rc == AM_OK) rc = upload_batch(hay, n_hay, b, false);
     if (rc != AM_OK) { am_batch_destroy(b); return rc; }
     *out = b;
     return AM_OK;
@@ -632,15 +632,14 @@ extern "C" int am_batch_upload(const am_slice* hay, size_t n_hay, am_batch** out
 // One-shot entry points keep one batch object (device text + workspaces) per calling thread and device between calls, so
 // that a caller that scans one document per call does not pay a dozen hipMalloc/hipFree each time -- and calls from
 // different threads share nothing.  Anything larger than 256 MiB is let go.
-namespace {
-am_batch* oneshot_get(int dev)
+am_batch* am::host::oneshot_batch(int dev)
 {
     am_batch*& b = tl_state.oneshot[dev];
     if (!b) b = adopt_batch(dev);
     if (!b) { b = new am_batch(); b->dev = dev; }
     return b;
 }
-void oneshot_trim(int dev)
+void am::host::oneshot_batch_trim(int dev)
 {
     am_batch*& b = tl_state.oneshot[dev];
     if (!b) return;
@@ -659,11 +658,7 @@ void oneshot_trim(int dev)
     }
     if (held > limit) { am_batch_destroy(b); b = nullptr; }
 }
-}  // namespace
 
-int am::host::upload_batch(const am_slice* hay, size_t n_hay, am_batch* b, bool oneshot) { return upload_slices(hay, n_hay, b, oneshot); }
-am_batch* am::host::oneshot_batch(int dev) { return oneshot_get(dev); }
-void am::host::oneshot_batch_trim(int dev) { oneshot_trim(dev); }
 int am::host::record_array_get(int dev, size_t need, void** p, size_t* cap)
 {
     *p = g_record_cache[dev].take(need, cap);
@@ -714,21 +709,13 @@ extern "C" int am_count(const am_automaton* a, int case_mode, const am_slice* ha
 {
     if (n_hay && !counts_out) return fail(AM_ERR_INVALID, "counts_out is null");
     if (!a) return fail(AM_ERR_INVALID, "null automaton");
-    am_batch* b = oneshot_get(a->dev);                    // this thread's batch on the automaton's device
-    int rc = upload_slices(hay, n_hay, b, true);
-    if (rc == AM_OK) rc = am_count_batch(a, case_mode, b, counts_out, nullptr);
-    oneshot_trim(a->dev);
-    return rc;
+    return with_oneshot_batch(a->dev, hay, n_hay, [&](am_batch* b) { return am_count_batch(a, case_mode, b, counts_out, nullptr); });
 }
 
 extern "C" int am_contains_any(const am_automaton* a, int case_mode, const am_slice* hay, size_t n_hay, uint8_t* flags_out)
 {
     if (!a) return fail(AM_ERR_INVALID, "null automaton");
-    am_batch* b = oneshot_get(a->dev);                    // this thread's batch on the automaton's device
-    int rc = upload_slices(hay, n_hay, b, true);
-    if (rc == AM_OK) rc = am_contains_any_batch(a, case_mode, b, flags_out);
-    oneshot_trim(a->dev);
-    return rc;
+    return with_oneshot_batch(a->dev, hay, n_hay, [&](am_batch* b) { return am_contains_any_batch(a, case_mode, b, flags_out); });
 }
 
 static int run_segmented(const am_automaton* a, int case_mode, const am_slice* hay, size_t n_hay, uint64_t total, am_matches** out);
@@ -748,11 +735,7 @@ extern "C" int am_run(const am_automaton* a, int case_mode, const am_slice* hay,
         if (sound && n_hay < 0xFFFFFFFFull && (cfg::get(cfg::kRunSegments) > 0 || (total >= kRunSegmentedFrom && prepare(a, case_mode, &f) == AM_OK && f->h.dfa_n_states != 0)))
             return run_segmented(a, case_mode, hay, n_hay, total, out);
     }
-    am_batch* b = oneshot_get(a->dev);                    // this thread's batch on the automaton's device
-    int rc = upload_slices(hay, n_hay, b, true);
-    if (rc == AM_OK) rc = am_run_batch(a, case_mode, b, out);
-    oneshot_trim(a->dev);
-    return rc;
+    return with_oneshot_batch(a->dev, hay, n_hay, [&](am_batch* b) { return am_run_batch(a, case_mode, b, out); });
 }
 
 // ---- ONE haystack in ranges ("a single huge haystack splits into G ranges with maxNeedleCodePoints overlap" -- the same rule as the
@@ -785,11 +768,8 @@ extern "C" int am_run_range(const am_automaton* a, int case_mode, const am_slice
     AM_TRY(range_window(a, case_mode, hay, lo, hi, &start, &scan_hi));
     if (hi == lo) { am_matches* m = new am_matches(); m->dev = a->dev; m->fetched = true; *out = m; return AM_OK; }
     const am_slice win{hay->ptr, hay->off + start, scan_hi - start};
-    am_batch* b = oneshot_get(a->dev);
-    int rc = upload_slices(&win, 1, b, true);
-    am_matches* m = nullptr;
-    if (rc == AM_OK) rc = run_batch_impl(a, case_mode, b, &m, false);          // (the general path: the records stay on the device, unfetched)
-    oneshot_trim(a->dev);
+    am_matches* m = nullptr;                                // (the general path: the records stay on the device, unfetched)
+    int rc = with_oneshot_batch(a->dev, &win, 1, [&](am_batch* b) { return run_batch_impl(a, case_mode, b, &m, false); });
     if (rc != AM_OK) return rc;
     if (m->n) {
         OnDevice od(m->dev);
@@ -1017,7 +997,7 @@ static int run_segmented(const am_automaton* a, int case_mode, const am_slice* h
     const int dev = a->dev;
     AM_TRY(ensure_runtime());
     ON_DEVICE(dev);
-    am_batch* b = oneshot_get(dev);
+    am_batch* b = oneshot_batch(dev);
     struct Job { am_matches* m; uint64_t at; };
     static const bool trace = std::getenv("AM_RUN_TRACE") != nullptr;      // (measurements: when each segment's steps begin and end, ms since the call began, on stderr)
     const auto t_begin = std::chrono::steady_clock::now();
@@ -1054,7 +1034,7 @@ static int run_segmented(const am_automaton* a, int case_mode, const am_slice* h
         // (the first segment a quarter of the others: its upload and scan are the only ones no download runs beside)
         while (j < n_hay && (rest_at_once || bytes < (i == 0 ? segment / 4 : segment))) bytes += hay[j++].len;
         const double t_up = now_ms();
-        rc = upload_slices(hay + i, j - i, b, true);
+        rc = upload_batch(hay + i, j - i, b, true);
         const double t_scan = now_ms();
         am_matches* m = nullptr;
         { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return jobs.size() < 2; }); }      // at most three record arrays alive: one on its way, one waiting, this one
@@ -1086,7 +1066,7 @@ static int run_segmented(const am_automaton* a, int case_mode, const am_slice* h
     { std::lock_guard<std::mutex> lk(mu); closing = true; }
     cv.notify_all();
     downloader.join();
-    oneshot_trim(dev);
+    oneshot_batch_trim(dev);
     if (rc == AM_OK && dl_rc != AM_OK) rc = fail(dl_rc, dl_err);
     if (rc != AM_OK) { if (block) g_host_cache.give(block, block_cap); return rc; }
     am_matches* res = new am_matches();

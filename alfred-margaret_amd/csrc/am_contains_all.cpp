@@ -201,26 +201,23 @@ int fold_batch(const am_needle_ids* ids, int case_mode, am_batch* b, const Recor
     std::vector<uint64_t> offs((size_t)b->n_hay + 1), sub_offs;
     HIP_TRY(hipMemcpyAsync(offs.data(), b->d_offsets, offs.size() * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    std::unique_ptr<am_batch, void (*)(am_batch*)> sub(new am_batch(), am_batch_destroy);
-    sub->dev = b->dev;
+    DerivedBatch sub;                                       // ONE batch: its buffers serve group after group
+    sub.begin(b->dev);
     for (uint32_t h0 = 0; h0 < b->n_hay;) {
         uint32_t h1 = h0; uint64_t values = 0;
         while (h1 < b->n_hay && (h1 == h0 || (values + per[h1]) * sizeof(Record) <= budget)) values += per[h1++];      // (a haystack beyond the budget by itself: a group of one)
         const uint64_t bytes = offs[h1] - offs[h0];
         if (values != 0 && bytes != 0) {
-            const size_t padded = padded_text(bytes);
-            AM_TRY(sub->text_buf.ensure(padded));
-            AM_TRY(sub->offs_buf.ensure((size_t)(h1 - h0 + 1) * 8));
+            uint64_t* sub_off; uint8_t* sub_text;
+            AM_TRY(sub.text(bytes, st, &sub_text));
+            AM_TRY(sub.offsets(h1 - h0, &sub_off));
             sub_offs.resize((size_t)(h1 - h0) + 1);
             for (uint32_t h = h0; h <= h1; h++) sub_offs[h - h0] = offs[h] - offs[h0];
-            HIP_TRY(hipMemcpyAsync(sub->text_buf.p, (const uint8_t*)b->d_text + offs[h0], bytes, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipMemsetAsync((uint8_t*)sub->text_buf.p + bytes, 0, padded - bytes, st));                        // zero tail: kernels read whole 16-byte groups
-            HIP_TRY(hipMemcpyAsync(sub->offs_buf.p, sub_offs.data(), sub_offs.size() * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(sub_text, (const uint8_t*)b->d_text + offs[h0], bytes, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(sub_off, sub_offs.data(), sub_offs.size() * 8, hipMemcpyHostToDevice, st));
             HIP_TRY(hipStreamSynchronize(st));
-            sub->owns = true; sub->d_text = sub->text_buf.p; sub->d_offsets = (uint64_t*)sub->offs_buf.p;
-            sub->total = bytes; sub->n_hay = h1 - h0;
-            AM_TRY(finish_batch(sub.get()));
-            AM_TRY(fold_scan(ids, case_mode, sub.get(), ra, h0, fold));
+            AM_TRY(sub.ready(bytes, h1 - h0));
+            AM_TRY(fold_scan(ids, case_mode, sub.b.get(), ra, h0, fold));
         }
         h0 = h1;
     }
@@ -239,16 +236,9 @@ int hist_batch(const am_needle_ids* ids, int case_mode, am_batch* b, uint64_t* d
 // index, which is the group's sub-batch where fold_batch made groups
 int hist_words_batch(const am_span_table* t, int case_mode, am_batch* b, uint64_t* d_counts, uint64_t* d_trace)
 {
-    const am_needle_ids* ids = t->ids;
-    return fold_batch(ids, case_mode, b, [&](const Record* recs, uint64_t n_rec, uint32_t, uint32_t n_hay, const am_batch* scanned, int dev, hipStream_t st) {
-        SpansIn in;
-        in.recs = recs; in.n_rec = n_rec;
-        in.vals_off = (const uint64_t*)ids->vals_off.p; in.vals = (const uint32_t*)ids->vals.p; in.n_states = ids->n_states; in.n_values = ids->n_values;
-        in.len_bytes = (const uint32_t*)t->len_bytes.p; in.len_cps = (const uint32_t*)t->len_cps.p; in.n_needles = ids->n_needles; in.n_hay = n_hay;
-        in.text = (const uint8_t*)scanned->d_text; in.offsets = scanned->d_offsets; in.total = scanned->total;
-        in.words = t->d_words();
+    return fold_batch(t->ids, case_mode, b, [&](const Record* recs, uint64_t n_rec, uint32_t, uint32_t n_hay, const am_batch* scanned, int dev, hipStream_t st) {
         Prof pr("needle_hist_words", st);
-        HIP_TRY(launch_needle_hist_words(case_mode == AM_IGNORE_CASE, in, d_counts, d_trace,
+        HIP_TRY(launch_needle_hist_words(case_mode == AM_IGNORE_CASE, spans_in(t, recs, n_rec, scanned, n_hay), d_counts, d_trace,
                                          cfg::get(cfg::kHistFlushTiles) > 0 ? (uint32_t)std::min<long>(cfg::get(cfg::kHistFlushTiles), 1L << 30) : 0u, g_rt.dev[dev].n_cu, st));
         return AM_OK;
     });
@@ -295,14 +285,8 @@ int am::host::spans_flags(const am_span_table* t, int case_mode, am_batch* b, ui
     }
     if (ids->n_needles == 0) return AM_OK;
     return fold_batch(ids, case_mode, b, [&](const Record* recs, uint64_t n_rec, uint32_t h0, uint32_t n_hay, const am_batch* scanned, int, hipStream_t st) {
-        SpansIn in;
-        in.recs = recs; in.n_rec = n_rec;
-        in.vals_off = (const uint64_t*)ids->vals_off.p; in.vals = (const uint32_t*)ids->vals.p; in.n_states = ids->n_states; in.n_values = ids->n_values;
-        in.len_bytes = (const uint32_t*)t->len_bytes.p; in.len_cps = (const uint32_t*)t->len_cps.p; in.n_needles = ids->n_needles; in.n_hay = n_hay;
-        in.text = (const uint8_t*)scanned->d_text; in.offsets = scanned->d_offsets; in.total = scanned->total;
-        in.words = t->d_words();
         Prof pr("hay_flags_spans", st);
-        HIP_TRY(launch_hay_flags_spans(case_mode == AM_IGNORE_CASE, in, d_flags + h0, st));
+        HIP_TRY(launch_hay_flags_spans(case_mode == AM_IGNORE_CASE, spans_in(t, recs, n_rec, scanned, n_hay), d_flags + h0, st));
         return AM_OK;
     });
 }
@@ -313,12 +297,14 @@ extern "C" int am_debug_hist_adds(uint64_t* out3)
     return AM_OK;
 }
 
-extern "C" int am_count_by_needle_batch(const am_needle_ids* ids, int case_mode, const am_batch* cb, uint64_t* counts_out)
+// the counts of a device-resident batch to the caller, behind the checks both *_batch entry points make once their handles are known not to be null; handle: what the
+// entry point's message calls its own ("needle ids"); fold(b, d_counts, d_trace): hist_batch or hist_words_batch
+template <class Fold>
+static int count_batch(const am_needle_ids* ids, const char* handle, int case_mode, const am_batch* cb, uint64_t* counts_out, Fold&& fold)
 {
-    if (!ids || !cb) return fail(AM_ERR_INVALID, "null needle ids or batch");
     if (ids->n_needles && !counts_out) return fail(AM_ERR_INVALID, "counts_out is null");
     AM_TRY(check_case(case_mode));
-    if (ids->a->dev != cb->dev) return fail(AM_ERR_INVALID, "needle ids and batch live on different devices");
+    if (ids->a->dev != cb->dev) return fail(AM_ERR_INVALID, std::string(handle) + " and batch live on different devices");
     if (ids->n_needles == 0) return AM_OK;
     AM_TRY(ensure_runtime());
     am_batch* b = const_cast<am_batch*>(cb);
@@ -327,28 +313,21 @@ extern "C" int am_count_by_needle_batch(const am_needle_ids* ids, int case_mode,
     hipStream_t st; AM_TRY(get_stream(b->dev, &st));
     HistOut out;
     AM_TRY(out.begin(ids->n_needles, st));
-    AM_TRY(hist_batch(ids, case_mode, b, out.counts(), out.trace_words()));
+    AM_TRY(fold(b, out.counts(), out.trace_words()));
     return out.finish(counts_out, st);
+}
+
+extern "C" int am_count_by_needle_batch(const am_needle_ids* ids, int case_mode, const am_batch* cb, uint64_t* counts_out)
+{
+    if (!ids || !cb) return fail(AM_ERR_INVALID, "null needle ids or batch");
+    return count_batch(ids, "needle ids", case_mode, cb, counts_out, [&](am_batch* b, uint64_t* d_counts, uint64_t* d_trace) { return hist_batch(ids, case_mode, b, d_counts, d_trace); });
 }
 
 extern "C" int am_count_spans_by_needle_batch(const am_span_table* t, int case_mode, const am_batch* cb, uint64_t* counts_out)
 {
     if (!t || !cb) return fail(AM_ERR_INVALID, "null span table or batch");
-    const am_needle_ids* ids = t->ids;
-    if (!t->has_words) return am_count_by_needle_batch(ids, case_mode, cb, counts_out);      // no class: every span is a row, the rows are the values
-    if (ids->n_needles && !counts_out) return fail(AM_ERR_INVALID, "counts_out is null");
-    AM_TRY(check_case(case_mode));
-    if (ids->a->dev != cb->dev) return fail(AM_ERR_INVALID, "span table and batch live on different devices");
-    if (ids->n_needles == 0) return AM_OK;
-    AM_TRY(ensure_runtime());
-    am_batch* b = const_cast<am_batch*>(cb);
-    if (b->n_hay == 0 || b->total == 0) { std::memset(counts_out, 0, (size_t)ids->n_needles * 8); return AM_OK; }
-    ON_DEVICE(b->dev);
-    hipStream_t st; AM_TRY(get_stream(b->dev, &st));
-    HistOut out;
-    AM_TRY(out.begin(ids->n_needles, st));
-    AM_TRY(hist_words_batch(t, case_mode, b, out.counts(), out.trace_words()));
-    return out.finish(counts_out, st);
+    if (!t->has_words) return am_count_by_needle_batch(t->ids, case_mode, cb, counts_out);      // no class: every span is a row, the rows are the values
+    return count_batch(t->ids, "span table", case_mode, cb, counts_out, [&](am_batch* b, uint64_t* d_counts, uint64_t* d_trace) { return hist_words_batch(t, case_mode, b, d_counts, d_trace); });
 }
 
 extern "C" int am_count_spans_by_needle(const am_span_table* t, int case_mode, const am_slice* hay, size_t n_hay, uint64_t* counts_out)
@@ -363,13 +342,7 @@ extern "C" int am_count_spans_by_needle(const am_span_table* t, int case_mode, c
     if (ids->n_needles == 0) return AM_OK;
     AM_TRY(ensure_runtime());
     if (total == 0) { std::memset(counts_out, 0, (size_t)ids->n_needles * 8); return AM_OK; }
-    const int dev = ids->a->dev;
-    ON_DEVICE(dev);
-    am_batch* b = oneshot_batch(dev);                       // this thread's batch on the automaton's device: upload plus the batch form, as am_spans does it
-    int rc = upload_batch(hay, n_hay, b, true);
-    if (rc == AM_OK) rc = am_count_spans_by_needle_batch(t, case_mode, b, counts_out);
-    oneshot_batch_trim(dev);
-    return rc;
+    return with_oneshot_batch(ids->a->dev, hay, n_hay, [&](am_batch* b) { return am_count_spans_by_needle_batch(t, case_mode, b, counts_out); });
 }
 
 extern "C" int am_matches_count_by_needle(const am_matches* m, const am_needle_ids* ids, uint64_t* counts_out)

@@ -1,6 +1,7 @@
-// am_fold.h -- the host-side scaffolding the device folds over a scan's records share (am_splitter.cpp, am_spans.cpp, am_contains_all.cpp): the argument checks of
-// their entry points, the CSR result handle (am_fragments, am_needle_matrix, am_spans), the finisher of long chains (pointer doubling) and the loop that sends host
-// slices up in segments and folds each in HBM.  The kernels differ from fold to fold; what is here does not.  Included at the end of am_host.h; internal.
+// am_fold.h -- the host-side scaffolding the device stages share (am_splitter.cpp, am_spans.cpp, am_subst.cpp, am_select.cpp, am_contains_all.cpp and the one-shot
+// entry points of am_abi.cpp): the argument checks of their entry points, the CSR result handle (am_fragments, am_needle_matrix, am_spans), the finisher of long chains
+// (pointer doubling), the one-shot form of an entry point, the loop that sends host slices up in segments and folds each in HBM, and the builder of the batches the
+// library derives in HBM.  The kernels differ from stage to stage; what is here does not.  Included at the end of am_host.h; internal.
 #pragma once
 
 namespace am {
@@ -31,6 +32,27 @@ inline int matches_in_hbm(const am_matches* m, const am_needle_ids* ids, const c
     return AM_OK;
 }
 
+// ---- the host copy of n elements a result keeps in HBM, made once, on first use (the CSR results below, am_selection).  noun: what the error text calls them.  A fetch
+// of zero elements answers with a pointer to one placeholder element, never NULL.
+template <class T>
+const T* fetch_once(std::vector<T>& host, bool& fetched, int dev, const DevBuf& d, uint64_t n, const char* noun)
+{
+    if (fetched) return host.data();
+    try { host.resize((size_t)std::max<uint64_t>(n, 1)); } catch (const std::exception&) { fail(AM_ERR_OOM, std::string("no host memory for ") + noun); return nullptr; }
+    if (n) {
+        if (ensure_runtime() != AM_OK) return nullptr;
+        OnDevice od(dev);
+        hipStream_t st;
+        if (od.rc != AM_OK || get_stream(dev, &st) != AM_OK) return nullptr;
+        if (hipMemcpyAsync(host.data(), d.p, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+            fail(AM_ERR_HIP, std::string("copying ") + noun + " to the host failed");
+            return nullptr;
+        }
+    }
+    fetched = true;
+    return host.data();
+}
+
 // ---- the CSR result of a fold: Item[n_items] and uint64[n_hay + 1] row offsets that stay in HBM until asked for; the host copies are made once, on first use.
 // (Holds DevBufs: on the heap only, see THE RULE above DevBuf.)
 template <class Item>
@@ -48,29 +70,9 @@ struct CsrResult {
         h_offsets.assign(1, 0); h_data.assign(1, Item{});
         offsets_fetched = data_fetched = true;
     }
-    // noun: what the error text calls the result ("the fragments").  A fetch of zero items answers with a pointer to one placeholder element, never NULL.
-    const uint64_t* fetch_offsets(const char* noun) { return fetch(h_offsets, offsets_fetched, offsets, n_hay + 1, noun); }
-    const Item* fetch_data(const char* noun) { return fetch(h_data, data_fetched, data, n_items, noun); }
-
-private:
-    template <class T>
-    const T* fetch(std::vector<T>& host, bool& fetched, const DevBuf& d, uint64_t n, const char* noun)
-    {
-        if (fetched) return host.data();
-        try { host.resize((size_t)std::max<uint64_t>(n, 1)); } catch (const std::exception&) { fail(AM_ERR_OOM, std::string("no host memory for ") + noun); return nullptr; }
-        if (n) {
-            if (ensure_runtime() != AM_OK) return nullptr;
-            OnDevice od(dev);
-            hipStream_t st;
-            if (od.rc != AM_OK || get_stream(dev, &st) != AM_OK) return nullptr;
-            if (hipMemcpyAsync(host.data(), d.p, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-                fail(AM_ERR_HIP, std::string("copying ") + noun + " to the host failed");
-                return nullptr;
-            }
-        }
-        fetched = true;
-        return host.data();
-    }
+    // noun: what the error text calls the result ("the fragments")
+    const uint64_t* fetch_offsets(const char* noun) { return fetch_once(h_offsets, offsets_fetched, dev, offsets, n_hay + 1, noun); }
+    const Item* fetch_data(const char* noun) { return fetch_once(h_data, data_fetched, dev, data, n_items, noun); }
 };
 
 // the result of a call without haystacks
@@ -122,6 +124,19 @@ int finish_long_chains(uint64_t n, uint32_t* kept, uint32_t* flag, Next&& launch
     return AM_OK;
 }
 
+// ---- the one-shot form of an entry point: the slices into the calling thread's batch on `dev`, form(b) -- the *_batch form -- if they went up, and the batch trimmed
+// whatever came of either.  The entry point has made its own checks and early returns; upload_batch's (hay, the haystack count, then the runtime, then every slice's
+// pointer) are the first thing that happens here, so this does not make the device current: upload_batch and the batch forms do that themselves.
+template <class Form>
+int with_oneshot_batch(int dev, const am_slice* hay, size_t n_hay, Form&& form)
+{
+    am_batch* b = oneshot_batch(dev);
+    int rc = upload_batch(hay, n_hay, b, true);
+    if (rc == AM_OK) rc = form(b);
+    oneshot_batch_trim(dev);
+    return rc;
+}
+
 // ---- host slices -> batches -> a fold per batch.  fold(b, first) folds batch b, whose haystack 0 is haystack `first` of the call, and returns when the device has
 // finished with b.  The caller has made `dev` current.
 constexpr uint64_t kFoldSegmentedFrom = 1ull << 30;         // as am_run: host batches from here on go up in segments of whole haystacks
@@ -131,16 +146,11 @@ template <class Fold>
 int fold_slices(int dev, const am_slice* hay, size_t n_hay, uint64_t total, Fold&& fold)
 {
     const long forced = cfg::get(cfg::kRunSegments);       // (the switch of am_run's segments: 0 = never, k > 0 = always, segments of k KiB)
-    if (n_hay < 2 || forced == 0 || (forced < 0 && total < kFoldSegmentedFrom)) {
-        am_batch* b = oneshot_batch(dev);                   // this thread's batch on the device
-        int rc = upload_batch(hay, n_hay, b, true);
-        if (rc == AM_OK) rc = fold(b, (size_t)0);
-        oneshot_batch_trim(dev);
-        return rc;
-    }
+    if (n_hay < 2 || forced == 0 || (forced < 0 && total < kFoldSegmentedFrom))
+        return with_oneshot_batch(dev, hay, n_hay, [&](am_batch* b) { return fold(b, (size_t)0); });
     // Segments of whole haystacks into two batches that take turns: while this thread uploads segment k + 1, a thread of its own scans segment k and folds its
     // records in HBM.  The worker is joined before the next one starts: folds see the segments one after the other, in order.
-    std::unique_ptr<am_batch, void (*)(am_batch*)> second(new am_batch(), am_batch_destroy);
+    BatchPtr second(new am_batch(), am_batch_destroy);
     second->dev = dev;
     am_batch* turn[2] = {oneshot_batch(dev), second.get()};
     const uint64_t segment = forced > 0 ? (uint64_t)forced << 10 : kFoldSegment;
@@ -165,6 +175,55 @@ int fold_slices(int dev, const am_slice* hay, size_t n_hay, uint64_t total, Fold
     oneshot_batch_trim(dev);
     return rc;
 }
+
+// ---- batches the library derives in HBM (the fragments, a selection, a splice, the groups of a fold): a batch of the library's own that owns its offsets and its
+// text.  Kernels read whole 16-byte groups, so text() zeroes from the last whole group of the text to the padded end, on the stream and ahead of whatever the producer
+// enqueues to write the bytes.  The producer waits for the device itself before ready() / publish(): it knows why.
+struct DerivedBatch {
+    BatchPtr b{nullptr, am_batch_destroy};
+    void begin(int dev) { b.reset(new am_batch()); b->dev = dev; b->owns = true; }
+    int offsets(uint64_t n_hay, uint64_t** p)               // room for n_hay + 1 offsets, which the producer writes
+    {
+        AM_TRY(b->offs_buf.ensure((n_hay + 1) * 8));
+        *p = (uint64_t*)b->offs_buf.p;
+        return AM_OK;
+    }
+    int text(uint64_t total, hipStream_t st, uint8_t** p)   // room for the padded text, its zero tail enqueued
+    {
+        const size_t padded = padded_text(total);
+        const uint64_t whole = total & ~15ull;
+        AM_TRY(b->text_buf.ensure(padded));
+        *p = (uint8_t*)b->text_buf.p;
+        HIP_TRY(hipMemsetAsync(*p + whole, 0, padded - whole, st));
+        return AM_OK;
+    }
+    int ready(uint64_t total, uint64_t n_hay)               // offsets and text are in place: a batch like any other (again: the buffers serve the next fill)
+    {
+        b->d_text = b->text_buf.p; b->d_offsets = (uint64_t*)b->offs_buf.p;
+        b->total = total; b->n_hay = (uint32_t)n_hay;
+        return finish_batch(b.get());
+    }
+    int publish(uint64_t total, uint64_t n_hay, am_batch** out)
+    {
+        AM_TRY(ready(total, n_hay));
+        *out = b.release();
+        return AM_OK;
+    }
+    // a batch without haystacks: offsets = [0], one group of zeros
+    static int empty(int dev, am_batch** out)
+    {
+        ON_DEVICE(dev);
+        hipStream_t st; AM_TRY(get_stream(dev, &st));
+        DerivedBatch nb;
+        nb.begin(dev);
+        uint64_t* off; uint8_t* text;
+        AM_TRY(nb.offsets(0, &off));
+        HIP_TRY(hipMemsetAsync(off, 0, 8, st));
+        AM_TRY(nb.text(0, st, &text));
+        HIP_TRY(hipStreamSynchronize(st));
+        return nb.publish(0, 0, out);
+    }
+};
 
 }  // namespace host
 }  // namespace am

@@ -1,8 +1,9 @@
 // am_host.h -- what the host-side translation units of libam share (am_abi.cpp: runtime and thread state, automata, batches, one-shot entry points, results;
 // am_run.cpp: routes and scans; am_replacer.cpp: the Replacer; am_contains_all.cpp: containsAll, the fold checksum, the per-needle counts and the needle matrix;
-// am_splitter.cpp: the Splitter; am_spans.cpp: match spans): error handling, the per-device runtime, device buffers, the handle structs of include/am.h and the few
-// scan entry points the Replacer drives.  am_fold.h, included at the end, holds what the folds over a scan's records share: argument checks, the CSR result handle,
-// the chain finisher and the segment loop.  Internal: nothing here is part of the C ABI.
+// am_splitter.cpp: the Splitter; am_spans.cpp: match spans; am_subst.cpp: substitute; am_select.cpp: select -- the last two through am_spans.h, which adds the span
+// table and the spans result): error handling, the per-device runtime, device buffers, the handle structs of include/am.h and the few scan entry points the Replacer
+// drives.  am_fold.h, included at the end, holds the scaffolding of the device stages: argument checks, the CSR result handle, the chain finisher, the one-shot
+// wrapper, the segment loop and the builder of derived batches.  Internal: nothing here is part of the C ABI.
 #pragma once
 #include "../../include/am.h"
 #include "../../include/am_debug.h"
@@ -251,8 +252,9 @@ int scan_needle_ids(const am_automaton* a, int case_mode, am_batch* b, const uin
 int run_records(const am_automaton* a, int case_mode, am_batch* b, const std::function<int(uint64_t, Record**)>& sink_final, uint64_t* n_out, bool have_lock = false);
 // the same without a host round trip (suffix-filter route, worst-case pool): the count stays on the device
 int run_records_async(const am_automaton* a, int case_mode, am_batch* b, Record* d_out, const uint64_t** n_dev, hipStream_t st);
-// am_abi.cpp: what am_count_by_needle* (am_contains_all.cpp) shares with the run entry points: the slices of a call into a batch (oneshot: small uploads stay enqueued on the calling
-// thread's stream), the calling thread's one-shot batch on a device, and the device arrays of freed results (kept for the next records: taken from there or allocated, given back)
+// am_abi.cpp: what the one-shot entry points of every stage share (through with_oneshot_batch and fold_slices, am_fold.h): the slices of a call into a batch, re-using its
+// device buffers (oneshot: small uploads stay enqueued on the calling thread's stream), the calling thread's one-shot batch on a device and its trim after the call; and the
+// device arrays of freed results (kept for the next records: taken from there or allocated, given back)
 int upload_batch(const am_slice* hay, size_t n_hay, am_batch* b, bool oneshot);
 am_batch* oneshot_batch(int dev);
 void oneshot_batch_trim(int dev);
@@ -270,6 +272,7 @@ struct RecordArray {
     }
     ~RecordArray() { record_array_put(dev, p, cap); }
 };
+using BatchPtr = std::unique_ptr<am_batch, void (*)(am_batch*)>;
 inline size_t padded_text(uint64_t total) { return (size_t)((total + 15) & ~15ull) + 16; }
 // the sink of run_records that puts the records into `d` (a DevBuf or a RecordArray), with room for `spare` more
 template <class Buf>

@@ -1074,8 +1074,7 @@ static int replacer_run_groups(const am_replacer* r, const am_batch* in, uint64_
         for (uint32_t i = 0; i <= h1 - h0; i++) sub[i] = offs[h0 + i] - offs[h0];
         AM_TRY(gp->offs.ensure(sub.size() * 8));
         HIP_TRY(hipMemcpy(gp->offs.p, sub.data(), sub.size() * 8, hipMemcpyHostToDevice));
-        gp->b.dev = in->dev; gp->b.owns = false; gp->b.d_text = (uint8_t*)in->d_text + offs[h0]; gp->b.d_offsets = (uint64_t*)gp->offs.p;
-        gp->b.total = sub.back(); gp->b.n_hay = h1 - h0;
+        AM_TRY(bind_workspace(gp->b, in->dev, (const uint8_t*)in->d_text + offs[h0], (const uint64_t*)gp->offs.p, sub.back(), h1 - h0));
         gs.push_back(std::move(gp));
     }
     std::vector<std::thread> pool;
@@ -1092,7 +1091,6 @@ static int replacer_run_groups(const am_replacer* r, const am_batch* in, uint64_
         Group& x = *gs[g];
         OnDevice od(in->dev);                                   // a fresh thread's current device is 0: the group's buffers and launches belong to the batch's device
         x.rc = od.rc;
-        if (x.rc == AM_OK) x.rc = finish_batch(&x.b);
         if (x.rc == AM_OK) {
             hipStream_t st;
             x.rc = get_stream(in->dev, &st);

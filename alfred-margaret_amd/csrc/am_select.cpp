@@ -22,7 +22,6 @@ struct am_selection {
 namespace {
 
 using SelectionPtr = std::unique_ptr<am_selection, void (*)(am_selection*)>;
-using BatchPtr = std::unique_ptr<am_batch, void (*)(am_batch*)>;
 
 constexpr uint64_t kOneLaunchSums = 1ull << 16;             // up to here the three exclusive sums take one launch (launch_scan_jobs), beyond it three launches each
 
@@ -93,114 +92,72 @@ SelectionPtr new_selection(const am_batch* b)
     return s;
 }
 
-// a batch of the library's own without haystacks: offsets = [0], one group of zeros
-int empty_batch(int dev, am_batch** out)
+// the frame of the four *_batch selects: the checks in the order every one of them makes them, the selection, and fill(b, s) where there is a haystack to select from.
+// handle: the entry point's own, looked at -- handle_dev() -- only once it and the batch are known not to be null; case_mode: null where the entry point takes none
+// (am_select_flags)
+template <class DevOf, class Fill>
+int select_with(const void* handle, DevOf&& handle_dev, const int* case_mode, const am_batch* cb, am_selection** out, const char* null_msg, const char* dev_msg, Fill&& fill)
 {
-    ON_DEVICE(dev);
-    hipStream_t st; AM_TRY(get_stream(dev, &st));
-    BatchPtr nb(new am_batch(), am_batch_destroy);
-    nb->dev = dev; nb->owns = true;
-    AM_TRY(nb->offs_buf.ensure(8));
-    AM_TRY(nb->text_buf.ensure(padded_text(0)));
-    HIP_TRY(hipMemsetAsync(nb->offs_buf.p, 0, 8, st));
-    HIP_TRY(hipMemsetAsync(nb->text_buf.p, 0, padded_text(0), st));
-    HIP_TRY(hipStreamSynchronize(st));
-    nb->d_text = nb->text_buf.p; nb->d_offsets = (uint64_t*)nb->offs_buf.p;
-    AM_TRY(finish_batch(nb.get()));
-    *out = nb.release();
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    if (case_mode) AM_TRY(check_case(*case_mode));
+    if (!handle || !cb) return fail(AM_ERR_INVALID, null_msg);
+    if (handle_dev() != cb->dev) return fail(AM_ERR_INVALID, dev_msg);
+    AM_TRY(ensure_runtime());
+    am_batch* b = const_cast<am_batch*>(cb);
+    SelectionPtr s = new_selection(b);
+    if (b->n_hay != 0) AM_TRY(fill(b, s.get()));
+    *out = s.release();
     return AM_OK;
 }
 
-// the one-shot forms: the slices into the calling thread's batch on `dev`, then the batch form
-template <class BatchForm>
-int select_slices(int dev, const am_slice* hay, size_t n_hay, BatchForm&& batch_form)
+// a fill: the flags that write(d_flags, st) puts into n_hay bytes of the call's own (the scans of the groups use the batch's scratch), compacted
+template <class Write>
+int compact_written(const am_batch* b, int invert, am_selection* s, Write&& write)
 {
-    ON_DEVICE(dev);
-    am_batch* b = oneshot_batch(dev);
-    int rc = upload_batch(hay, n_hay, b, true);
-    if (rc == AM_OK) rc = batch_form(b);
-    oneshot_batch_trim(dev);
-    return rc;
+    ON_DEVICE(b->dev);
+    hipStream_t st; AM_TRY(get_stream(b->dev, &st));
+    DevBuf flags;
+    AM_TRY(flags.ensure(b->n_hay));
+    AM_TRY(write((uint8_t*)flags.p, st));
+    return compact(b, (const uint8_t*)flags.p, 0, invert, st, s);
 }
 
 }  // namespace
 
 extern "C" int am_select_any_batch(const am_automaton* a, int case_mode, int invert, const am_batch* cb, am_selection** out)
 {
-    if (!out) return fail(AM_ERR_INVALID, "out is null");
-    *out = nullptr;
-    AM_TRY(check_case(case_mode));
-    if (!a || !cb) return fail(AM_ERR_INVALID, "null automaton or batch");
-    if (a->dev != cb->dev) return fail(AM_ERR_INVALID, "automaton and batch live on different devices");
-    AM_TRY(ensure_runtime());
-    am_batch* b = const_cast<am_batch*>(cb);
-    SelectionPtr s = new_selection(b);
-    if (b->n_hay != 0) {
-        SelectSink sink(b, invert, s.get());
-        AM_TRY(contains_any_flags(a, case_mode, b, sink));
-    }
-    *out = s.release();
-    return AM_OK;
+    return select_with(a, [&] { return a->dev; }, &case_mode, cb, out, "null automaton or batch", "automaton and batch live on different devices", [&](am_batch* b, am_selection* s) {
+        SelectSink sink(b, invert, s);
+        return contains_any_flags(a, case_mode, b, sink);
+    });
 }
 
 extern "C" int am_select_all_batch(const am_needle_ids* ids, int case_mode, int invert, const am_batch* cb, am_selection** out)
 {
-    if (!out) return fail(AM_ERR_INVALID, "out is null");
-    *out = nullptr;
-    AM_TRY(check_case(case_mode));
-    if (!ids || !cb) return fail(AM_ERR_INVALID, "null needle ids or batch");
-    if (ids->a->dev != cb->dev) return fail(AM_ERR_INVALID, "needle ids and batch live on different devices");
-    AM_TRY(ensure_runtime());
-    am_batch* b = const_cast<am_batch*>(cb);
-    SelectionPtr s = new_selection(b);
-    if (b->n_hay != 0) {
-        SelectSink sink(b, invert, s.get());
-        AM_TRY(contains_all_flags(ids, case_mode, b, sink));
-    }
-    *out = s.release();
-    return AM_OK;
+    return select_with(ids, [&] { return ids->a->dev; }, &case_mode, cb, out, "null needle ids or batch", "needle ids and batch live on different devices", [&](am_batch* b, am_selection* s) {
+        SelectSink sink(b, invert, s);
+        return contains_all_flags(ids, case_mode, b, sink);
+    });
 }
 
 extern "C" int am_select_spans_batch(const am_span_table* t, int case_mode, int invert, const am_batch* cb, am_selection** out)
 {
-    if (!out) return fail(AM_ERR_INVALID, "out is null");
-    *out = nullptr;
-    AM_TRY(check_case(case_mode));
-    if (!t || !cb) return fail(AM_ERR_INVALID, "null span table or batch");
-    if (t->ids->a->dev != cb->dev) return fail(AM_ERR_INVALID, "span table and batch live on different devices");
-    AM_TRY(ensure_runtime());
-    am_batch* b = const_cast<am_batch*>(cb);
-    SelectionPtr s = new_selection(b);
-    if (b->n_hay != 0) {
-        ON_DEVICE(b->dev);
-        hipStream_t st; AM_TRY(get_stream(b->dev, &st));
-        DevBuf flags;                                       // the call's own: the scans of the groups use the batch's scratch
-        AM_TRY(flags.ensure(b->n_hay));
-        AM_TRY(spans_flags(t, case_mode, b, (uint8_t*)flags.p));
-        AM_TRY(compact(b, (const uint8_t*)flags.p, 0, invert, st, s.get()));
-    }
-    *out = s.release();
-    return AM_OK;
+    return select_with(t, [&] { return t->ids->a->dev; }, &case_mode, cb, out, "null span table or batch", "span table and batch live on different devices", [&](am_batch* b, am_selection* s) {
+        return compact_written(b, invert, s, [&](uint8_t* d_flags, hipStream_t) { return spans_flags(t, case_mode, b, d_flags); });
+    });
 }
 
-extern "C" int am_select_flags(const am_batch* b, const uint8_t* host_flags, int invert, am_selection** out)
+extern "C" int am_select_flags(const am_batch* cb, const uint8_t* host_flags, int invert, am_selection** out)
 {
-    if (!out) return fail(AM_ERR_INVALID, "out is null");
-    *out = nullptr;
-    if (!b) return fail(AM_ERR_INVALID, "null batch");
-    if (b->n_hay && !host_flags) return fail(AM_ERR_INVALID, "flags is null");
-    AM_TRY(ensure_runtime());
-    SelectionPtr s = new_selection(b);
-    if (b->n_hay != 0) {
-        ON_DEVICE(b->dev);
-        hipStream_t st; AM_TRY(get_stream(b->dev, &st));
-        DevBuf flags;
-        AM_TRY(flags.ensure(b->n_hay));
-        HIP_TRY(hipMemcpyAsync(flags.p, host_flags, b->n_hay, hipMemcpyHostToDevice, st));
-        AM_TRY(compact(b, (const uint8_t*)flags.p, 0, invert, st, s.get()));
-    }
-    *out = s.release();
-    return AM_OK;
+    // (the batch is its own handle; a batch with haystacks was made on a device, so the flags' check, made where there is a haystack, is behind no other failure)
+    return select_with(cb, [&] { return cb->dev; }, nullptr, cb, out, "null batch", "", [&](am_batch* b, am_selection* s) -> int {
+        if (!host_flags) return fail(AM_ERR_INVALID, "flags is null");
+        return compact_written(b, invert, s, [&](uint8_t* d_flags, hipStream_t st) -> int {
+            HIP_TRY(hipMemcpyAsync(d_flags, host_flags, b->n_hay, hipMemcpyHostToDevice, st));
+            return AM_OK;
+        });
+    });
 }
 
 extern "C" int am_select_any(const am_automaton* a, int case_mode, int invert, const am_slice* hay, size_t n_hay, am_selection** out)
@@ -211,7 +168,7 @@ extern "C" int am_select_any(const am_automaton* a, int case_mode, int invert, c
     AM_TRY(check_case(case_mode));
     if (!a) return fail(AM_ERR_INVALID, "null automaton");      // (last: a caller without a device can see every other check)
     AM_TRY(ensure_runtime());                               // (the last of what a caller without a device can see; the handle is not looked at before)
-    return select_slices(a->dev, hay, n_hay, [&](am_batch* b) { return am_select_any_batch(a, case_mode, invert, b, out); });
+    return with_oneshot_batch(a->dev, hay, n_hay, [&](am_batch* b) { return am_select_any_batch(a, case_mode, invert, b, out); });
 }
 
 extern "C" int am_select_all(const am_needle_ids* ids, int case_mode, int invert, const am_slice* hay, size_t n_hay, am_selection** out)
@@ -222,7 +179,7 @@ extern "C" int am_select_all(const am_needle_ids* ids, int case_mode, int invert
     AM_TRY(check_case(case_mode));
     if (!ids) return fail(AM_ERR_INVALID, "null needle ids");
     AM_TRY(ensure_runtime());
-    return select_slices(ids->a->dev, hay, n_hay, [&](am_batch* b) { return am_select_all_batch(ids, case_mode, invert, b, out); });
+    return with_oneshot_batch(ids->a->dev, hay, n_hay, [&](am_batch* b) { return am_select_all_batch(ids, case_mode, invert, b, out); });
 }
 
 extern "C" uint64_t am_selection_size(const am_selection* s) { return s ? s->n_kept : 0; }
@@ -233,20 +190,7 @@ extern "C" const void* am_selection_device_indices(const am_selection* s) { retu
 extern "C" const uint32_t* am_selection_indices(am_selection* s)
 {
     if (!s) { fail(AM_ERR_INVALID, "null selection"); return nullptr; }
-    if (s->fetched) return s->h_indices.data();
-    try { s->h_indices.resize((size_t)std::max<uint64_t>(s->n_kept, 1)); } catch (const std::exception&) { fail(AM_ERR_OOM, "no host memory for the selection's indices"); return nullptr; }
-    if (s->n_kept) {
-        if (ensure_runtime() != AM_OK) return nullptr;
-        OnDevice od(s->dev);
-        hipStream_t st;
-        if (od.rc != AM_OK || get_stream(s->dev, &st) != AM_OK) return nullptr;
-        if (hipMemcpyAsync(s->h_indices.data(), s->indices.p, (size_t)s->n_kept * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-            fail(AM_ERR_HIP, "copying the selection's indices to the host failed");
-            return nullptr;
-        }
-    }
-    s->fetched = true;
-    return s->h_indices.data();
+    return fetch_once(s->h_indices, s->fetched, s->dev, s->indices, s->n_kept, "the selection's indices");
 }
 
 extern "C" void am_selection_free(am_selection* s)
@@ -264,27 +208,20 @@ extern "C" int am_batch_from_selection(const am_batch* src, const am_selection* 
     if (s->n_src != src->n_hay || s->src_total != src->total || s->dev != src->dev)
         return fail(AM_ERR_INVALID, "the selection was not made from a batch with this haystack count and size");
     AM_TRY(ensure_runtime());
-    if (s->n_kept == 0) return empty_batch(src->dev, out);
+    if (s->n_kept == 0) return DerivedBatch::empty(src->dev, out);
     ON_DEVICE(src->dev);
     hipStream_t st; AM_TRY(get_stream(src->dev, &st));
-    BatchPtr nb(new am_batch(), am_batch_destroy);
-    nb->dev = src->dev; nb->owns = true;
-    const uint64_t total = s->total;
-    const size_t padded = padded_text(total);
-    AM_TRY(nb->offs_buf.ensure((s->n_kept + 1) * 8));
-    AM_TRY(nb->text_buf.ensure(padded));
-    HIP_TRY(hipMemcpyAsync(nb->offs_buf.p, s->new_off.p, (s->n_kept + 1) * 8, hipMemcpyDeviceToDevice, st));
-    const uint64_t whole = total & ~15ull;
-    HIP_TRY(hipMemsetAsync((uint8_t*)nb->text_buf.p + whole, 0, padded - whole, st));            // zero tail: kernels read whole 16-byte groups
+    DerivedBatch nb;
+    nb.begin(src->dev);
+    uint64_t* new_off; uint8_t* new_text;
+    AM_TRY(nb.offsets(s->n_kept, &new_off));
+    HIP_TRY(hipMemcpyAsync(new_off, s->new_off.p, (s->n_kept + 1) * 8, hipMemcpyDeviceToDevice, st));
+    AM_TRY(nb.text(s->total, st, &new_text));
     { Prof pr("select_gather", st);
-      HIP_TRY(launch_split_gather((const uint8_t*)src->d_text, src->total, (const uint64_t*)s->run_src.p, (const uint64_t*)s->run_dst.p, s->n_runs, total,
-                                  (uint8_t*)nb->text_buf.p, g_rt.dev[src->dev].n_cu, st)); }
+      HIP_TRY(launch_split_gather((const uint8_t*)src->d_text, src->total, (const uint64_t*)s->run_src.p, (const uint64_t*)s->run_dst.p, s->n_runs, s->total, new_text,
+                                  g_rt.dev[src->dev].n_cu, st)); }
     HIP_TRY(hipStreamSynchronize(st));                      // a batch object may be used from any thread and stream afterwards
-    nb->d_text = nb->text_buf.p; nb->d_offsets = (uint64_t*)nb->offs_buf.p;
-    nb->total = total; nb->n_hay = (uint32_t)s->n_kept;
-    AM_TRY(finish_batch(nb.get()));
-    *out = nb.release();
-    return AM_OK;
+    return nb.publish(s->total, s->n_kept, out);
 }
 
 extern "C" void am_select_geometry(uint32_t* tile_bytes, uint32_t* scan_block_items)

@@ -192,12 +192,7 @@ extern "C" int am_spans_batch(const am_span_table* t, int case_mode, int mode, c
     RecordArray ra(b->dev);
     uint64_t n_rec = 0;
     if (b->total != 0) AM_TRY(run_records(ids->a, case_mode, b, records_into(ra), &n_rec));
-    SpansIn in;
-    in.recs = (const Record*)ra.p; in.n_rec = n_rec;
-    in.vals_off = (const uint64_t*)ids->vals_off.p; in.vals = (const uint32_t*)ids->vals.p; in.n_states = ids->n_states; in.n_values = ids->n_values;
-    in.len_bytes = (const uint32_t*)t->len_bytes.p; in.len_cps = (const uint32_t*)t->len_cps.p; in.n_needles = ids->n_needles; in.n_hay = b->n_hay;
-    in.text = (const uint8_t*)b->d_text; in.offsets = b->d_offsets; in.total = b->total;
-    in.words = t->d_words();
+    const SpansIn in = spans_in(t, (const Record*)ra.p, n_rec, b, b->n_hay);
     DevBuf cnt, voff, scan_tmp, rec_first, all_spans;
     AM_TRY(cnt.ensure((n_rec + 1) * 4));
     AM_TRY(voff.ensure((n_rec + 1) * 8));
@@ -237,12 +232,7 @@ extern "C" int am_spans(const am_span_table* t, int case_mode, int mode, const a
     AM_TRY(ensure_runtime());
     const int dev = t->ids->a->dev;
     if (n_hay == 0) return empty_spans(dev, mode, t->ids->n_needles, out);
-    ON_DEVICE(dev);
-    am_batch* b = oneshot_batch(dev);                       // this thread's batch on the automaton's device
-    int rc = upload_batch(hay, n_hay, b, true);
-    if (rc == AM_OK) rc = am_spans_batch(t, case_mode, mode, b, out);
-    oneshot_batch_trim(dev);
-    return rc;
+    return with_oneshot_batch(dev, hay, n_hay, [&](am_batch* b) { return am_spans_batch(t, case_mode, mode, b, out); });
 }
 
 extern "C" uint64_t am_spans_size(const SpansResult* s) { return s ? s->n_items : 0; }

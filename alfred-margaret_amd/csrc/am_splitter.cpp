@@ -119,12 +119,7 @@ extern "C" int am_split(const am_splitter* s, int case_mode, const am_slice* hay
     AM_TRY(ensure_runtime());
     const int dev = s->a->dev;
     if (n_hay == 0) return empty_result(dev, out);
-    ON_DEVICE(dev);
-    am_batch* b = oneshot_batch(dev);                       // this thread's batch on the automaton's device
-    int rc = upload_batch(hay, n_hay, b, true);
-    if (rc == AM_OK) rc = am_split_batch(s, case_mode, b, out);
-    oneshot_batch_trim(dev);
-    return rc;
+    return with_oneshot_batch(dev, hay, n_hay, [&](am_batch* b) { return am_split_batch(s, case_mode, b, out); });
 }
 
 extern "C" uint64_t am_fragments_size(const am_fragments* f) { return f ? f->n_items : 0; }
@@ -157,31 +152,24 @@ extern "C" int am_batch_from_fragments(const am_batch* src, const am_fragments* 
     AM_TRY(ensure_runtime());
     ON_DEVICE(src->dev);
     hipStream_t st; AM_TRY(get_stream(src->dev, &st));
-    std::unique_ptr<am_batch, void (*)(am_batch*)> nb(new am_batch(), am_batch_destroy);
-    nb->dev = src->dev; nb->owns = true;
+    DerivedBatch nb;
+    nb.begin(src->dev);
     const uint64_t n = f->n_items;
     DevBuf lens, src_at, scan_tmp;
     AM_TRY(lens.ensure((n + 1) * 8));
     AM_TRY(src_at.ensure((n + 1) * 8));
-    AM_TRY(nb->offs_buf.ensure((n + 1) * 8));
+    uint64_t* new_off; uint8_t* new_text;
+    AM_TRY(nb.offsets(n, &new_off));
     size_t tmp_bytes = 0;
     HIP_TRY(scan64_temp_bytes(n + 1, &tmp_bytes));
     AM_TRY(scan_tmp.ensure(tmp_bytes));
     HIP_TRY(launch_split_sources((const Fragment*)f->data.p, n, (const uint64_t*)f->offsets.p, src->d_offsets, src->n_hay, src->total, (uint64_t*)lens.p, (uint64_t*)src_at.p, st));
-    HIP_TRY(launch_scan64(scan_tmp.p, scan_tmp.cap, (const uint64_t*)lens.p, (uint64_t*)nb->offs_buf.p, n + 1, st));
+    HIP_TRY(launch_scan64(scan_tmp.p, scan_tmp.cap, (const uint64_t*)lens.p, new_off, n + 1, st));
     uint64_t total = 0;
-    AM_TRY(read_u64((const uint64_t*)nb->offs_buf.p + n, &total, st));
-    const size_t padded = padded_text(total);
-    AM_TRY(nb->text_buf.ensure(padded));
-    const uint64_t whole = total & ~15ull;
-    HIP_TRY(hipMemsetAsync((uint8_t*)nb->text_buf.p + whole, 0, padded - whole, st));            // zero tail: kernels read whole 16-byte groups
+    AM_TRY(read_u64(new_off + n, &total, st));
+    AM_TRY(nb.text(total, st, &new_text));
     { Prof pr("split_gather", st);
-      HIP_TRY(launch_split_gather((const uint8_t*)src->d_text, src->total, (const uint64_t*)src_at.p, (const uint64_t*)nb->offs_buf.p, n, total, (uint8_t*)nb->text_buf.p,
-                                  g_rt.dev[src->dev].n_cu, st)); }
+      HIP_TRY(launch_split_gather((const uint8_t*)src->d_text, src->total, (const uint64_t*)src_at.p, new_off, n, total, new_text, g_rt.dev[src->dev].n_cu, st)); }
     HIP_TRY(hipStreamSynchronize(st));                      // a batch object may be used from any thread and stream afterwards
-    nb->d_text = nb->text_buf.p; nb->d_offsets = (uint64_t*)nb->offs_buf.p;
-    nb->total = total; nb->n_hay = (uint32_t)n;
-    AM_TRY(finish_batch(nb.get()));
-    *out = nb.release();
-    return AM_OK;
+    return nb.publish(total, n, out);
 }

@@ -20,26 +20,6 @@ namespace {
 
 constexpr size_t kPoolPad = 32;
 
-using BatchPtr = std::unique_ptr<am_batch, void (*)(am_batch*)>;
-
-// a batch of the library's own without haystacks: offsets = [0], one group of zeros
-int empty_batch(int dev, am_batch** out)
-{
-    ON_DEVICE(dev);
-    hipStream_t st; AM_TRY(get_stream(dev, &st));
-    BatchPtr nb(new am_batch(), am_batch_destroy);
-    nb->dev = dev; nb->owns = true;
-    AM_TRY(nb->offs_buf.ensure(8));
-    AM_TRY(nb->text_buf.ensure(padded_text(0)));
-    HIP_TRY(hipMemsetAsync(nb->offs_buf.p, 0, 8, st));
-    HIP_TRY(hipMemsetAsync(nb->text_buf.p, 0, padded_text(0), st));
-    HIP_TRY(hipStreamSynchronize(st));
-    nb->d_text = nb->text_buf.p; nb->d_offsets = (uint64_t*)nb->offs_buf.p;
-    AM_TRY(finish_batch(nb.get()));
-    *out = nb.release();
-    return AM_OK;
-}
-
 int check_splice(const am_batch* src, const struct am_spans* s, const am_subst_table* r)
 {
     if (!src || !s || !r) return fail(AM_ERR_INVALID, "null batch, spans or substitution table");
@@ -54,11 +34,11 @@ int check_splice(const am_batch* src, const struct am_spans* s, const am_subst_t
 int splice(const am_batch* src, const struct am_spans* s, const am_subst_table* r, am_batch** out)
 {
     AM_TRY(ensure_runtime());
-    if (src->n_hay == 0) return empty_batch(src->dev, out);
+    if (src->n_hay == 0) return DerivedBatch::empty(src->dev, out);
     ON_DEVICE(src->dev);
     hipStream_t st; AM_TRY(get_stream(src->dev, &st));
-    BatchPtr nb(new am_batch(), am_batch_destroy);
-    nb->dev = src->dev; nb->owns = true;
+    DerivedBatch nb;
+    nb.begin(src->dev);
     const uint64_t n_span = s->n_items, n_hay = src->n_hay, n_pieces = 2 * n_span + n_hay;
     SubstIn in;
     in.spans = (const Span*)s->data.p; in.n_span = n_span; in.span_off = (const uint64_t*)s->offsets.p;
@@ -70,7 +50,8 @@ int splice(const am_batch* src, const struct am_spans* s, const am_subst_table* 
     AM_TRY(live.ensure((n_pieces + 1) * 4));
     AM_TRY(dst_at.ensure((n_pieces + 1) * 8));
     AM_TRY(cidx.ensure((n_pieces + 1) * 8));
-    AM_TRY(nb->offs_buf.ensure((n_hay + 1) * 8));
+    uint64_t* new_off; uint8_t* new_text;
+    AM_TRY(nb.offsets(n_hay, &new_off));
     size_t tmp_bytes = 0;
     HIP_TRY(scan64_temp_bytes(n_pieces + 1, &tmp_bytes));
     AM_TRY(scan_tmp.ensure(tmp_bytes));
@@ -86,22 +67,15 @@ int splice(const am_batch* src, const struct am_spans* s, const am_subst_table* 
     AM_TRY(read_u64((const uint64_t*)cidx.p + n_pieces, &n_live, st));
     AM_TRY(cdst.ensure((n_live + 1) * 8));
     AM_TRY(csrc.ensure((n_live + 1) * 8));
-    const size_t padded = padded_text(total);
-    AM_TRY(nb->text_buf.ensure(padded));
     { Prof pr("subst_compact", st);
       HIP_TRY(launch_subst_compact((const uint64_t*)src_at.p, (const uint32_t*)live.p, (const uint64_t*)dst_at.p, (const uint64_t*)cidx.p, n_pieces, (uint64_t*)cdst.p,
-                                   (uint64_t*)csrc.p, n_live, in.span_off, n_span, n_hay, (uint64_t*)nb->offs_buf.p, st)); }
-    const uint64_t whole = total & ~15ull;
-    HIP_TRY(hipMemsetAsync((uint8_t*)nb->text_buf.p + whole, 0, padded - whole, st));            // zero tail: kernels read whole 16-byte groups
+                                   (uint64_t*)csrc.p, n_live, in.span_off, n_span, n_hay, new_off, st)); }
+    AM_TRY(nb.text(total, st, &new_text));
     { Prof pr("subst_gather", st);
       HIP_TRY(launch_subst_gather((const uint8_t*)src->d_text, src->total, (const uint8_t*)r->pool.p, r->pool_bytes, (const uint64_t*)cdst.p, (const uint64_t*)csrc.p, n_live,
-                                  total, (uint8_t*)nb->text_buf.p, g_rt.dev[src->dev].n_cu, st)); }
+                                  total, new_text, g_rt.dev[src->dev].n_cu, st)); }
     HIP_TRY(hipStreamSynchronize(st));                      // a batch object may be used from any thread and stream afterwards; the workspaces are freed
-    nb->d_text = nb->text_buf.p; nb->d_offsets = (uint64_t*)nb->offs_buf.p;
-    nb->total = total; nb->n_hay = src->n_hay;
-    AM_TRY(finish_batch(nb.get()));
-    *out = nb.release();
-    return AM_OK;
+    return nb.publish(total, n_hay, out);
 }
 
 }  // namespace
@@ -174,13 +148,8 @@ extern "C" int am_substitute(const am_subst_table* r, int case_mode, const am_sl
     AM_TRY(check_case(case_mode));
     if (!r) return fail(AM_ERR_INVALID, "null substitution table");      // (last: a caller without a device can see every other check)
     AM_TRY(ensure_runtime());
-    if (n_hay == 0) return empty_batch(r->dev, out);
-    ON_DEVICE(r->dev);
-    am_batch* b = oneshot_batch(r->dev);                    // this thread's batch on the table's device; the result is a batch of its own
-    int rc = upload_batch(hay, n_hay, b, true);
-    if (rc == AM_OK) rc = am_substitute_batch(r, case_mode, b, out, nullptr);
-    oneshot_batch_trim(r->dev);
-    return rc;
+    if (n_hay == 0) return DerivedBatch::empty(r->dev, out);
+    return with_oneshot_batch(r->dev, hay, n_hay, [&](am_batch* b) { return am_substitute_batch(r, case_mode, b, out, nullptr); });      // (the result is a batch of its own)
 }
 
 extern "C" void am_substitute_geometry(uint32_t* group_bytes, uint32_t* tile_bytes)
