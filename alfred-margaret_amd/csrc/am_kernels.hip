@@ -169,8 +169,15 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
             cnt_val += sum;
         } else if (found) atomicAdd(reinterpret_cast<unsigned long long*>(o.hay_counts + hay), (unsigned long long)vlen);
     };
+    // The resolve's view of the automaton and of the output is read from the kernel's argument segment where a resolve begins (s_load: a few hundred
+    // cycles, once per epoch), so that the fields only the resolve and the walk use -- most of SfView's pointers -- hold no scalar registers across the
+    // chunk loop, whose uniform state otherwise lives in the lanes of a VGPR (14 v_readlane / v_writelane on every chunk's straight path before, 4 now).
+    // The argument segment is laid out as this struct: three by-value structs of 8-byte alignment and a u64.
+    struct KArgs { SfView s; BatchView b; ScanOut o; uint64_t n_chunks; };
     // ---- the parked walkers: the newest <= 64 of them, walked to the end in lock step (all lanes busy; see resolve_batch)
     auto walk_parked = [&]() {
+        const SfView s = kernarg_reload<SfView>(offsetof(KArgs, s));          // (shadow the kernel's arguments: see KArgs)
+        const ScanOut o = kernarg_reload<ScanOut>(offsetof(KArgs, o));
         const uint32_t n = wq_n < 64u ? wq_n : 64u, base = wq_n - n;
         wq_n = base;
         const bool valid = lane < n;
@@ -215,6 +222,8 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
     constexpr int RN = 1;
     // nb == 0 && drain: only walk what is parked (end of a unit).  walk_parked has ONE call site here (it contains a whole trie walk).
     auto resolve_batch = [&](uint32_t nb, bool drain) {
+        const SfView s = kernarg_reload<SfView>(offsetof(KArgs, s));          // (shadow the kernel's arguments: see KArgs)
+        const ScanOut o = kernarg_reload<ScanOut>(offsetof(KArgs, o));
         __builtin_amdgcn_s_setprio(3);                       // (wave priorities: see the filter below)
         if (timing) { const uint64_t now = __builtin_amdgcn_s_memtime(); t_r0 += now - t_mark; t_mark = now; n_batches++; }
         uint64_t gpos[RN];
@@ -494,6 +503,12 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
             v = make_uint4(t.x, t.y, t.z, t.w);
         }
     };
+    // a chunk known to lie wholly inside the batch (every chunk but the batch's last one): no test, no zero-fill, the load in the straight path
+    auto fetch_whole = [&](uint64_t cc, uint4& v) {
+        typedef uint32_t u32x4_native __attribute__((ext_vector_type(4)));
+        const u32x4_native t = *reinterpret_cast<const u32x4_native*>(b.text + cc * kSfChunk + lane * 16u);
+        v = make_uint4(t.x, t.y, t.z, t.w);
+    };
     auto fetch_before = [&](uint64_t cc, uint32_t& c3, uint32_t& c4) {          // uniform: one request for the wave
         uint2 t = make_uint2(0, 0);
         if (cc < n_chunks && cc > 0) {
@@ -518,6 +533,19 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
     // if it is set.  A 1-GiB document that matches in its first KiB costs a few chunks per wavefront, not the scan.
     uint32_t any_word = 0, any_hay = kNone, flagged_hay = kNone;      // the flag word requested last, whose it is; the haystack known to be flagged
 
+    // The chunk loop's tests against the end of the batch and against the cached bracket, as 32-bit compares of chunk numbers within the unit (all
+    // uniform: s_cmp + scalar branches; the 64-bit forms, which the scalar unit cannot order, are evaluated once per unit and per haystack lookup):
+    //   chunk ci starts inside haystack hay0 while ci < he_ci, and ends inside it -- or hay0 is the batch's last haystack -- while ci < single_ci;
+    //   the chunk AFTER chunk ci lies wholly inside the batch while ci < n_whole; chunk tail_ci is the batch's last (kNone: not in this unit).
+    uint32_t he_ci = 0, single_ci = 0, n_whole = 0, tail_ci = kNone;
+    auto bracket_ci = [&](uint64_t at) {                  // at: the first byte of the chunk at hand (a chunk of the current unit)
+        he_ci = 0; single_ci = 0;                         // outside the cached bracket: the chunk looks its haystack up
+        if (at >= hs0 && at < he0) {
+            const uint64_t d = he0 - unit_base_chunk * kSfChunk, up = (d + kSfChunk - 1) / kSfChunk, down = d / kSfChunk;
+            he_ci = up < kNone ? (uint32_t)up : kNone;
+            single_ci = he0 >= b.total || down >= kNone ? kNone : (uint32_t)down;
+        }
+    };
     uint64_t u_next = u;
     for (; u < n_units; u = u_next) {
         // the unit after this one (its first chunk is prefetched while this unit's last chunk is processed)
@@ -543,6 +571,10 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
                 continue;
             }
         }
+        tail_ci = unit_base_chunk + n_in_unit >= n_chunks ? n_in_unit - 1u : kNone;
+        n_whole = n_in_unit - 1u;                             // (n_in_unit >= 1: u < n_units)
+        if (tail_ci != kNone && n_whole) n_whole--;           // the batch's last chunk may be a partial one: fetched and masked lane by lane
+        bracket_ci(unit_base_chunk * kSfChunk);
         bool jumped = false;                                  // flag mode: the loop went from a skipped chunk to the unit's last one
         for (uint32_t ci = 0; ci < n_in_unit; ci++) {
             const uint64_t c = unit_base_chunk + ci;
@@ -570,8 +602,12 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
             }
             const bool next_skipped = kFlagMode && !last_of_unit && flagged_hay != kNone && flagged_hay == hay0 &&
                                       (c + 1) * kSfChunk >= hs0 && (c + 2) * kSfChunk <= he0;
-            if (!next_skipped)
-            fetch(!last_of_unit ? c + 1 : u_next * UC, next_v);
+            // (the chunk after this one of the same unit, anywhere but at the batch's end: requested without a test; the next unit's first chunk and
+            // the batch's last chunk take the tested form behind a scalar branch)
+            if (!next_skipped) {
+                if (ci < n_whole) fetch_whole(c + 1, next_v);
+                else fetch(!last_of_unit ? c + 1 : u_next * UC, next_v);
+            }
             if (last_of_unit) fetch_before(u_next * UC, next_c3, next_c4);
 
             const uint64_t c0 = c * kSfChunk;
@@ -582,11 +618,13 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
             // (The bracket goes through readfirstlane so that its loads are waited for INSIDE this rarely taken branch: a load
             // left pending at the join would make the compiler wait with vmcnt(0) on every chunk -- and vmcnt counts in order,
             // so that wait would also cover the prefetch issued just above and expose a full HBM latency per chunk.)
-            if (c0 >= he0 || c0 < hs0) {
+            // (he_ci: chunks only move forward inside a unit, so a chunk that starts before the bracket's end starts inside the bracket)
+            if (ci >= he_ci) {
                 hay0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)b.hidx[c0 >> kHidxShift]);      // c0 is a multiple of 1 KiB: the index names its haystack (one load instead of a binary search)
                 hs0 = uniform_u64(b.offsets[hay0]); he0 = uniform_u64(b.offsets[hay0 + 1]);
+                bracket_ci(c0);
             }
-            const bool single = (c0 + kSfChunk < b.total ? c0 + kSfChunk : b.total) <= he0;
+            const bool single = ci < single_ci;      // min(c0 + 1 KiB, the batch's end) <= he0
             bool skip = false;
             if (kFlagMode) {
                 skip = single && flagged_hay == hay0;
@@ -659,6 +697,7 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
                 }
             }
             __builtin_amdgcn_s_setprio(2);
+            if (ci == tail_ci)                       // only the batch's last chunk can reach past the batch's end (a scalar branch)
             if (p0 + 16 > b.total) cand &= p0 < b.total ? (1u << (uint32_t)(b.total - p0)) - 1u : 0u;
             if (timing) { asm volatile("" :: "v"(cand)); tick(t_filter); }
 
@@ -674,6 +713,18 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
                 uint32_t idx = incl - n;
                 // the loop runs as long as the busiest lane has candidates, so it only queues positions; the probe
                 // (dense, one candidate per lane) picks the window and the two bytes before it out of the staged chunk
+                // (the queue's bound can only bind when the wave has more candidates than the queue takes -- a scalar test on `total`, false in
+                // almost every chunk of every workload: the usual loop carries neither the bound's compare nor a copy of idx for it.  In the ILP = 2
+                // instantiations only, whose lanes queue four or five positions per chunk: with the handful of candidates the ILP = 1 ones are chosen
+                // for, the loop runs once or twice and the extra branch costs more than it saves -- cfg2 0.765 -> 0.774 ms per launch)
+                if (ILP == 2 && total <= (uint32_t)kSfQ1) {
+                    while (cand) {
+                        const uint32_t k = __builtin_ctz(cand);
+                        cand &= cand - 1u;
+                        AM_BOUNDS(idx < (uint32_t)kSfQ1);
+                        lds_write_u16(q1 + 2u * idx++, lane * 16u + k);
+                    }
+                } else
                 while (cand && idx < (uint32_t)kSfQ1) {
                     const uint32_t k = __builtin_ctz(cand);
                     cand &= cand - 1u;

@@ -46,6 +46,21 @@ __device__ __forceinline__ uint64_t uniform_u64(uint64_t x)
     return ((uint64_t)hi << 32) | lo;
 }
 
+// A by-value kernel argument (a struct `offset` bytes into the kernel's argument segment) read again where the call stands: the segment is in the constant
+// address space, so the fields the caller goes on to use arrive by s_load, and the empty asm hides the segment's address from the compiler at this point --
+// it cannot take the loads back to the kernel's entry, where their results would occupy scalar registers for the whole kernel.
+template <class T>
+__device__ __forceinline__ T kernarg_reload(uint32_t offset)
+{
+    typedef const __attribute__((address_space(4))) char* kernarg_bytes;
+    kernarg_bytes p = (kernarg_bytes)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    typedef const __attribute__((address_space(4))) T* kernarg_t;      // (typed: a copy of unknown alignment is made with vector loads, not with s_load)
+    T out;
+    __builtin_memcpy(&out, (kernarg_t)(p + offset), sizeof(T));
+    return out;
+}
+
 __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t x)
 {
 #pragma unroll
