@@ -38,6 +38,8 @@ NEEDLE_COUNT_DTYPE = np.dtype([("count", np.uint64), ("needle", np.uint32), ("ha
 SPAN_DTYPE = np.dtype([("start", np.uint64), ("len", np.uint64), ("haystack", np.uint32), ("needle", np.uint32)])   # am_span
 SPANS_ALL = 0
 SPANS_LEFTMOST_LONGEST = 1
+EXTRACT_EACH = 0
+EXTRACT_MERGED = 1
 PRIO_MATCH_DTYPE = np.dtype([("start", np.uint64), ("len", np.uint64), ("haystack", np.uint32), ("payload", np.uint32)])   # am_prio_match
 
 _u8p, _u32p, _u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
@@ -138,6 +140,9 @@ ABI = {
     "am_selection_free": (None, [_vp]),
     "am_batch_from_selection": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "am_select_geometry": (None, [_u32p, _u32p]),
+    "am_fragments_from_spans": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_vp)]),
+    "am_extract_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "am_extract": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(Slice), _sz, C.POINTER(_vp), C.POINTER(_vp)]),
     "am_needle_ids_create": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(_vp)]),
     "am_needle_ids_destroy": (None, [_vp]),
     "am_contains_all": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp]),
@@ -213,6 +218,7 @@ _HOST = {
     "amh_spans_fold": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
     "amh_spans_fold_words": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
     "amh_spans": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(Slice), _sz, _vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
+    "amh_extract_fold": (C.c_int, [_vp, _vp, C.POINTER(Slice), _sz, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
     "amh_substitute_fold": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, C.POINTER(_vp), _vp]),
     "amh_substitute_fold_words": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, _vp, C.POINTER(_vp), _vp]),
     "amh_substitute": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, C.POINTER(_vp), _vp]),
@@ -576,6 +582,23 @@ class Automaton:
         finally:
             libam().am_batch_destroy(b)
 
+    def extract(self, case, texts, before=0, after=0, merged=False, leftmost_longest=True, whole_words=False):
+        """The matched text with up to `before` / `after` code points of its own text around it (include/am.h "extract"): a list of lists of bytes, one list per
+        text -- a snippet per match (`grep -o` with context), or -- merged -- the union of overlapping and touching windows per text, as `grep -C` prints them
+        (leftmost-longest matches only).  am_extract: scanned, selected, windowed and gathered in HBM.  whole_words: as in spans."""
+        s = _Slices(texts)
+        t = SpanTable(self, word_bytes=whole_words)
+        nb, fr = _vp(), _vp()
+        check(libam().am_extract(t.handle, case, SPANS_LEFTMOST_LONGEST if leftmost_longest else SPANS_ALL, int(before), int(after),
+                                 EXTRACT_MERGED if merged else EXTRACT_EACH, s.arr, s.n, C.byref(nb), C.byref(fr)))
+        try:
+            offs = fragments_to_numpy(fr)[0]
+            snippets = batch_to_bytes(nb)[1]
+        finally:
+            libam().am_fragments_free(fr)
+            libam().am_batch_destroy(nb)
+        return [snippets[int(offs[i]):int(offs[i + 1])] for i in range(len(offs) - 1)]
+
     def substitute_host_mirror(self, case, texts, replacements, n_values=None, lengths=None):
         """The same through the C++ host mirror (host/spans.hpp substitute over spansFold over the fold steps of amh_run_list)."""
         lb, lc = _handle_lengths(self.needles, n_values, lengths)
@@ -703,6 +726,28 @@ def spans_fold_host(case, mode, triples, texts, len_bytes, len_code_points, word
     _hcheck(libhost().amh_spans_fold_words(case, mode, hay.ctypes.data, pos.ctypes.data, val.ctypes.data, n, s.arr, s.n, lb.ctypes.data, lc.ctypes.data, nv,
                                            None if flags is None else flags.ctypes.data, C.byref(po), C.byref(pe), C.byref(ne)))
     return _take_spans(po, pe, s.n, int(ne.value))
+
+
+def extract_fold_host(spans_offsets, spans, texts, before, after, merged=False):
+    """amh_extract_fold: the sequential definition of am_fragments_from_spans (host/spans.hpp extractFold, a byte at a time) over spans the caller brings -- CSR offsets
+    and SPAN_DTYPE rows as spans_fold_host returns them -- and the texts: (offsets np.uint64[len(texts) + 1], fragments FRAGMENT_DTYPE).  Runs without a device."""
+    so = np.ascontiguousarray(spans_offsets, dtype=np.uint64)
+    sp = np.ascontiguousarray(spans, dtype=SPAN_DTYPE)
+    s = _Slices(texts)
+    if len(so) != s.n + 1 or int(so[-1]) != len(sp):
+        raise AmError(AM_ERR_INVALID, "extract_fold_host: the spans are not those of these texts")
+    if not sp.size:
+        sp = np.zeros(1, SPAN_DTYPE)
+    po, pf, nf = _vp(), _vp(), C.c_uint64(0)
+    _hcheck(libhost().amh_extract_fold(so.ctypes.data, sp.ctypes.data, s.arr, s.n, int(before), int(after), int(bool(merged)), C.byref(po), C.byref(pf), C.byref(nf)))
+    k = int(nf.value)
+    try:
+        offs = np.frombuffer((C.c_char * ((s.n + 1) * 8)).from_address(po.value), dtype=np.uint64).copy()
+        frags = np.frombuffer((C.c_char * (k * FRAGMENT_DTYPE.itemsize)).from_address(pf.value), dtype=FRAGMENT_DTYPE).copy() if k else np.zeros(0, FRAGMENT_DTYPE)
+    finally:
+        libhost().amh_free_u64(po)
+        libhost().amh_free_u64(pf)
+    return offs, frags
 
 
 class ValuesTable:
@@ -849,6 +894,27 @@ class SpanTable:
         """am_select_spans_batch on a device-resident batch: the Selection of the haystacks whose SPANS_ALL row under this table is not empty (with a word class:
         the haystacks that hold a needle as a whole word)."""
         return _select(lambda out: libam().am_select_spans_batch(self._h, case, int(bool(invert)), batch, out))
+
+    def fragments_from_spans(self, batch, spans_raw, before, after, merged, raw=False):
+        """am_fragments_from_spans: the windows of an am_spans* the caller holds (spans_batch(..., raw=True) on `batch`) as (offsets np.uint64[n_hay + 1], fragments
+        FRAGMENT_DTYPE), relative to their haystacks.  raw: the am_fragments* itself, in HBM (am_batch_from_fragments takes it; free with am_fragments_free)."""
+        return _csr_call(lambda out: libam().am_fragments_from_spans(batch, spans_raw, int(before), int(after), EXTRACT_MERGED if merged else EXTRACT_EACH, out),
+                         fragments_to_numpy, libam().am_fragments_free, raw)
+
+    def extract_batch(self, case, batch, before=0, after=0, merged=False, leftmost_longest=True):
+        """am_extract_batch on a device-resident batch: (the new am_batch* handle with one haystack per fragment -- free with am_batch_destroy --, offsets
+        np.uint64[n_hay + 1], fragments FRAGMENT_DTYPE in SOURCE coordinates: the snippets of haystack i are haystacks offsets[i] .. offsets[i + 1] of the new batch)."""
+        nb, fr = _vp(), _vp()
+        check(libam().am_extract_batch(self._h, case, SPANS_LEFTMOST_LONGEST if leftmost_longest else SPANS_ALL, int(before), int(after),
+                                       EXTRACT_MERGED if merged else EXTRACT_EACH, batch, C.byref(nb), C.byref(fr)))
+        try:
+            offs, frags = fragments_to_numpy(fr)
+        except Exception:
+            libam().am_batch_destroy(nb)
+            raise
+        finally:
+            libam().am_fragments_free(fr)
+        return nb, offs, frags
 
 
 class Selection:

@@ -258,6 +258,15 @@ hipError_t launch_select_plan(const uint8_t* flags, uint32_t constant, uint32_t 
 // koff[first] (run_dst[n_runs] = total: the closing entry launch_split_gather wants)
 hipError_t launch_select_emit(const uint32_t* keep, const uint32_t* run_head, const uint64_t* rank, const uint64_t* run_rank, const uint64_t* koff, const uint64_t* src_offsets,
                               uint64_t n, uint64_t n_kept, uint64_t n_runs, uint32_t* indices, uint64_t* new_off, uint64_t* run_src, uint64_t* run_dst, hipStream_t st);
+// extract (am_extract.hip): the window of every span -- the span with up to `before` / `after` code points of its own haystack around it -- relative to the haystack.
+// frags given: AM_EXTRACT_EACH, frags[i] = the window of span i (ws / we unused).  frags null: ws[i] / we[i] for the two kernels below.
+hipError_t launch_extract_windows(const Span* spans, uint64_t n_span, const uint8_t* text, const uint64_t* src_offsets, uint32_t n_hay, uint64_t total, uint32_t before,
+                                  uint32_t after, Fragment* frags, uint64_t* ws, uint64_t* we, hipStream_t st);
+// head[i] = span i opens a piece (the first of its haystack, or ws[i] > we[i - 1]); head has n_span + 1 entries (the last one 0: the sum's trailing element)
+hipError_t launch_extract_heads(const Span* spans, uint64_t n_span, const uint64_t* ws, const uint64_t* we, uint32_t* head, hipStream_t st);
+// with rank = the exclusive sum of head (n_pieces = rank[n_span]): frags[p] = [ws of the head of piece p, we of its last span), out_off[h] = rank[span_off[h]]
+hipError_t launch_extract_emit(const uint32_t* head, const uint64_t* rank, const uint64_t* ws, const uint64_t* we, uint64_t n_span, uint64_t n_pieces, const uint64_t* span_off,
+                               uint64_t n_hay, Fragment* frags, uint64_t* out_off, hipStream_t st);
 // am_select_geometry: bytes of new text per workgroup of launch_split_gather (am_split.hip), elements per workgroup of launch_scan / a sweep of launch_scan_jobs (am_scan.hip)
 uint32_t split_gather_tile_bytes();
 uint32_t scan_tile_items();

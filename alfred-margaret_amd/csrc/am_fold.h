@@ -1,4 +1,4 @@
-// am_fold.h -- the host-side scaffolding the device stages share (am_splitter.cpp, am_spans.cpp, am_subst.cpp, am_select.cpp, am_contains_all.cpp and the one-shot
+// am_fold.h -- the host-side scaffolding the device stages share (am_splitter.cpp, am_spans.cpp, am_subst.cpp, am_select.cpp, am_extract.cpp, am_contains_all.cpp and the one-shot
 // entry points of am_abi.cpp): the argument checks of their entry points, the CSR result handle (am_fragments, am_needle_matrix, am_spans), the finisher of long chains
 // (pointer doubling), the one-shot form of an entry point, the loop that sends host slices up in segments and folds each in HBM, and the builder of the batches the
 // library derives in HBM.  The kernels differ from stage to stage; what is here does not.  Included at the end of am_host.h; internal.
@@ -227,3 +227,9 @@ struct DerivedBatch {
 
 }  // namespace host
 }  // namespace am
+
+// the result of am_split* (am_splitter.cpp) and of am_fragments_from_spans (am_extract.cpp): what am_batch_from_fragments turns into a batch
+struct am_fragments : am::host::CsrResult<am_fragment> {
+    uint64_t src_total = 0;                               // bytes of the batch they were cut from (am_batch_from_fragments checks it)
+};
+static_assert(sizeof(am_fragment) == sizeof(am::dev::Fragment), "am_fragment and the kernels' Fragment are one layout");

@@ -13,12 +13,6 @@ struct am_splitter {
     uint32_t sep_bytes = 0, sep_cps = 0;
 };
 
-struct am_fragments : CsrResult<am_fragment> {
-    uint64_t src_total = 0;                               // bytes of the batch they were cut from (am_batch_from_fragments checks it)
-};
-
-static_assert(sizeof(am_fragment) == sizeof(Fragment), "am_fragment and the kernels' Fragment are one layout");
-
 namespace {
 
 constexpr uint32_t kSplitChainLimit = 32;                 // records the lane of a chain's head looks at before the chain goes to the doubling rounds

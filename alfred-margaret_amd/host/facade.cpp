@@ -166,6 +166,30 @@ int amh_spans(void* h, int case_mode, int mode, const am_slice* hay, size_t n_ha
     });
 }
 
+// ---- extract (spans.hpp): extractFold over spans the caller brings (CSR: span_offs has n_hay + 1 entries, spans_in span_offs[n_hay] rows of am_span): no device is
+// touched.  offsets (n_hay + 1) and the fragments as the C ABI lays them out (am_fragment, 16 bytes each); free both with amh_free_u64
+int amh_extract_fold(const uint64_t* span_offs, const am_span* spans_in, const am_slice* hay, size_t n_hay, uint32_t before, uint32_t after, int merged,
+                     uint64_t** offs_out, uint64_t** frags_out, uint64_t* n_out)
+{
+    *offs_out = nullptr; *frags_out = nullptr; *n_out = 0;
+    return guarded([&] {
+        if (merged != 0 && merged != 1) throw AmError(AM_ERR_INVALID, "amh_extract_fold: bad mode");
+        if (!span_offs || span_offs[0] != 0) throw AmError(AM_ERR_INVALID, "amh_extract_fold: span_offs is null or does not begin with 0");
+        for (size_t h = 0; h < n_hay; h++)
+            if (span_offs[h + 1] < span_offs[h]) throw AmError(AM_ERR_INVALID, "amh_extract_fold: span_offs descends");
+        Spans sp;
+        sp.offsets.assign(span_offs, span_offs + n_hay + 1);
+        if (span_offs[n_hay]) sp.spans.assign(spans_in, spans_in + span_offs[n_hay]);
+        const Extracted r = extractFold(sp, sliceTexts(hay, n_hay), before, after, merged != 0);
+        const uint64_t nf = r.fragments.size();
+        uint64_t* offs = (uint64_t*)malloc((n_hay + 1) * sizeof(uint64_t));
+        uint64_t* fr = (uint64_t*)malloc((nf ? nf : 1) * sizeof(am_fragment));
+        std::memcpy(offs, r.offsets.data(), (n_hay + 1) * sizeof(uint64_t));
+        if (nf) std::memcpy(fr, r.fragments.data(), nf * sizeof(am_fragment));
+        *offs_out = offs; *frags_out = fr; *n_out = nf;
+    });
+}
+
 // ---- substitute (spans.hpp): the leftmost-longest spans spliced with replacement v = repl_bytes[repl_off[v], repl_off[v + 1]); the texts come back as one malloc'd blob
 // (amh_free_blob) + offsets (n_hay + 1, the caller's)
 namespace {

@@ -108,4 +108,63 @@ inline std::vector<std::string> substitute(CaseSensitivity cs, const std::vector
     return substitute(spansFold(cs, true, steps, texts, lenBytes, lenCodePoints, wordBytes), texts, replacements);
 }
 
+// extract (include/am.h "extract"): every span with up to `before` code points of its haystack in front of it and up to `after` behind it, as fragments of the
+// haystack; one per span, or -- merged -- the union of the windows per haystack as disjoint ascending pieces.  The sequential definition, a byte at a time.
+struct Extracted {
+    std::vector<uint64_t> offsets;                          // texts.size() + 1
+    std::vector<am_fragment> fragments;                     // haystack i: [offsets[i], offsets[i + 1])
+};
+
+inline bool isStartByte(uint8_t b) { return (b & 0xC0) != 0x80; }
+
+// the window [ws, we) of the span (s, l) of hay: ws = the before-th START byte among the indices < s, counted leftwards (fewer: 0; before == 0: s), we = the
+// after-th START byte among the indices > s + l, counted rightwards (fewer: hay.len; after == 0: s + l)
+inline am_fragment extractWindow(const Text& hay, uint64_t s, uint64_t l, uint32_t before, uint32_t after)
+{
+    if (s > hay.len || l > hay.len - s) throw AmError(AM_ERR_INVALID, "extractFold: a span leaves its haystack");
+    const uint8_t* p = hay.begin();
+    const uint64_t e = s + l;
+    uint64_t ws = s, we = e;
+    if (before > 0) {
+        ws = 0;
+        uint32_t seen = 0;
+        for (uint64_t i = s; i-- > 0;)
+            if (isStartByte(p[i]) && ++seen == before) { ws = i; break; }
+    }
+    if (after > 0) {
+        we = hay.len;
+        uint32_t seen = 0;
+        for (uint64_t i = e + 1; i < hay.len; i++)
+            if (isStartByte(p[i]) && ++seen == after) { we = i; break; }
+    }
+    return am_fragment{ws, we - ws};
+}
+
+// merged: the rows of a haystack must ascend by start and must not overlap (an AM_SPANS_LEFTMOST_LONGEST result); window i joins the piece of window i - 1 of the
+// same haystack iff ws_i <= we_{i-1}
+inline Extracted extractFold(const Spans& spans, const std::vector<Text>& texts, uint32_t before, uint32_t after, bool merged)
+{
+    if (spans.offsets.size() != texts.size() + 1) throw AmError(AM_ERR_INVALID, "extractFold: the spans are not those of these texts");
+    Extracted out;
+    out.offsets.assign(texts.size() + 1, 0);
+    for (size_t h = 0; h < texts.size(); h++) {
+        out.offsets[h] = out.fragments.size();
+        uint64_t cursor = 0;
+        bool open = false;                                  // a piece of THIS haystack is open: the first span of a haystack always opens one
+        for (uint64_t k = spans.offsets[h]; k < spans.offsets[h + 1]; k++) {
+            const am_span& s = spans.spans.at((size_t)k);
+            const am_fragment w = extractWindow(texts[h], s.start, s.len, before, after);
+            if (!merged) { out.fragments.push_back(w); continue; }
+            if (s.start < cursor) throw AmError(AM_ERR_INVALID, "extractFold: merged windows need spans that ascend and do not overlap");
+            cursor = s.start + s.len;
+            am_fragment* last = open ? &out.fragments.back() : nullptr;
+            if (last && w.start <= last->start + last->len) last->len = w.start + w.len - last->start;      // (we is non-decreasing over such rows)
+            else out.fragments.push_back(w);
+            open = true;
+        }
+    }
+    out.offsets[texts.size()] = out.fragments.size();
+    return out;
+}
+
 }  // namespace alfred_margaret

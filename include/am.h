@@ -457,6 +457,50 @@ AM_API void am_selection_free(am_selection* s);
 AM_API int am_batch_from_selection(const am_batch* src, const am_selection* s, am_batch** out);
 AM_API void am_select_geometry(uint32_t* tile_bytes, uint32_t* scan_block_items);
 
+/* ---- extract: the matched text with some characters around it, in HBM; the snippets are a batch of their own ---------------
+ * `grep -o`, `grep -o -E '.{0,40}needle.{0,40}'`, a keyword-in-context concordance, the snippets of a search front end, the windows an entity-extraction pipeline gives
+ * to its next model -- over a batch, without the spans (24 bytes each) or the snippets crossing the wire.
+ * A byte b is a START byte iff (b & 0xC0) != 0x80.  The definition is on bytes, so it holds for text that is not valid UTF-8.  For a span (s, l) of haystack h with L
+ * bytes, e = s + l, before = B and after = A (code points):
+ *   ws = the index of the B-th START byte of h among the indices < s, counted leftwards from s; 0 if there are fewer than B; s if B == 0
+ *   we = the index of the A-th START byte of h among the indices > e, counted rightwards; L if there are fewer than A; e if A == 0
+ *   the WINDOW is [ws, we), i.e. am_fragment {ws, we - ws}, relative to the haystack like every fragment.
+ * On valid UTF-8, where spans lie on code point boundaries, the window is the span plus at most B whole code points before it and at most A after it.  The walks NEVER
+ * LEAVE THE HAYSTACK: bytes of the neighbouring haystacks are never counted or included, and neither is the padding behind the text (in a borrowed batch the padding
+ * need not be zero).
+ *   AM_EXTRACT_EACH    one fragment per span, in the spans' order, with the spans' own CSR offsets: fragment k belongs to span k.  Overlapping windows repeat text;
+ *                      ZERO-LENGTH fragments are kept.  Takes an AM_SPANS_ALL or an AM_SPANS_LEFTMOST_LONGEST result.
+ *   AM_EXTRACT_MERGED  per haystack, the union of the windows as disjoint ascending pieces, as `grep -C` prints them: window i joins the piece of window i - 1 of the SAME
+ *                      haystack iff ws_i <= we_{i-1} -- TOUCHING windows join, a gap of one byte separates; a piece is [ws of its first window, we of its last).  The
+ *                      first span of a haystack always opens a piece, whatever the last window of the haystack before it was.  Takes an AM_SPANS_LEFTMOST_LONGEST
+ *                      result only (those rows ascend by start and do not overlap, so ws and we are both non-decreasing and a comparison with the neighbour decides);
+ *                      AM_ERR_INVALID for an AM_SPANS_ALL result, as in am_batch_substitute.
+ * The stage runs in HBM (csrc/am_extract.hip): one lane per span walks aligned 16-byte groups of the text -- one load, the 16-bit mask of the group's START bytes cut to
+ * the haystack and to the walk's side of the span, a popcount, a select in the group that holds the wanted byte; MERGED flags the spans that open a piece, ranks them
+ * with one exclusive sum, and only the piece count crosses to the host.  WORKSPACE of AM_EXTRACT_MERGED, freed when the call returns: 28 bytes per span (none in
+ * AM_EXTRACT_EACH); the result holds 16 bytes per fragment and 8 per haystack.  The library's device buffers are allocated an eighth larger than asked.
+ *   am_fragments_from_spans  the stage alone: to am_spans what am_batch_substitute is, with am_fragments as the result.  src must be the batch the spans were made from:
+ *                            AM_ERR_INVALID when the haystack count, the total bytes or the device differ.  The result carries src's size, so
+ *                            am_batch_from_fragments(src, result, ...) accepts it, and am_fragments_offsets maps a fragment back to its haystack.  No haystacks gives
+ *                            offsets = [0] and AM_OK; no spans gives n_hay empty rows.
+ *   am_extract_batch         am_spans_batch(t, case_mode, spans_mode, b), the stage and am_batch_from_fragments in one call: the new batch has ONE HAYSTACK PER FRAGMENT
+ *                            (a zero-length fragment is an empty haystack), owned by the library (am_batch_destroy), usable by every *_batch entry point.  frags_out
+ *                            (nullable): the fragments in SOURCE coordinates (am_fragments_free); their offsets map a snippet back to its document.  A span table with
+ *                            a word class extracts whole words only (the stage reads spans).  AM_ERR_UNSUPPORTED where am_batch_from_fragments returns it (2^32 - 1
+ *                            fragments and more).  Record memory is NOT bounded here, as in am_spans_batch.
+ *   am_extract               the one-shot form on host slices (the calling thread's one-shot batch).  The result is a batch of its own and stays valid after the
+ *                            one-shot batch is reused.  n_hay == 0 gives a batch without haystacks and AM_OK.
+ * Arguments are checked before any device work: AM_ERR_INVALID for null table / batch / spans / out, a case_mode that is neither AM_CASE_SENSITIVE nor AM_IGNORE_CASE, a
+ * spans_mode that is neither AM_SPANS_ALL nor AM_SPANS_LEFTMOST_LONGEST, a mode that is neither AM_EXTRACT_EACH nor AM_EXTRACT_MERGED, AM_EXTRACT_MERGED with
+ * AM_SPANS_ALL, n_hay >= 0xFFFFFFFF, slices without memory, handles on different devices.  *out (and *frags_out) is NULL after every failure. */
+#define AM_EXTRACT_EACH 0
+#define AM_EXTRACT_MERGED 1
+AM_API int am_fragments_from_spans(const am_batch* src, const struct am_spans* s, uint32_t before, uint32_t after, int mode, am_fragments** out);
+AM_API int am_extract_batch(const am_span_table* t, int case_mode, int spans_mode, uint32_t before, uint32_t after, int mode,
+                            const am_batch* b, am_batch** out, am_fragments** frags_out /* nullable */);
+AM_API int am_extract(const am_span_table* t, int case_mode, int spans_mode, uint32_t before, uint32_t after, int mode,
+                      const am_slice* hay, size_t n_hay, am_batch** out, am_fragments** frags_out /* nullable */);
+
 /* Checksum of the fold sequence of a result (harness aid; SURVEY 8d "parity check at scale",
  * benchmark/benchmark.py:65-69 asserts count identity on every run).  For every haystack i < n_hay:
  *   hash_out[i]  = foldl (\h (pos, v) -> h * 0x100000001B3 + mix pos v) 0  over the matches the reference's
