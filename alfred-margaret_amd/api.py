@@ -36,6 +36,9 @@ MATCH_DTYPE = np.dtype([("end_pos", np.uint64), ("haystack", np.uint32), ("state
 FRAGMENT_DTYPE = np.dtype([("start", np.uint64), ("len", np.uint64)])   # am_fragment
 NEEDLE_COUNT_DTYPE = np.dtype([("count", np.uint64), ("needle", np.uint32), ("haystack", np.uint32)])   # am_needle_count
 SPAN_DTYPE = np.dtype([("start", np.uint64), ("len", np.uint64), ("haystack", np.uint32), ("needle", np.uint32)])   # am_span
+RULE_NEGATE = 0x80000000
+RULE_NONE = 0xFFFFFFFF               # the label of a haystack on which no rule fires
+RULE_FIRED, RULE_FIRST = 0, 1
 SPANS_ALL = 0
 SPANS_LEFTMOST_LONGEST = 1
 EXTRACT_EACH = 0
@@ -140,6 +143,22 @@ ABI = {
     "am_selection_free": (None, [_vp]),
     "am_batch_from_selection": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "am_select_geometry": (None, [_u32p, _u32p]),
+    "am_rules_create": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.POINTER(_vp)]),
+    "am_rules_destroy": (None, [_vp]),
+    "am_rules_eval_batch": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_vp)]),
+    "am_rules_eval": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, C.POINTER(_vp)]),
+    "am_rule_hits_haystacks": (C.c_uint64, [_vp]),
+    "am_rule_hits_rules": (C.c_uint64, [_vp]),
+    "am_rule_hits_hay_words": (C.c_uint64, [_vp]),
+    "am_rule_hits_fired": (_vp, [_vp]),
+    "am_rule_hits_labels": (_vp, [_vp]),
+    "am_rule_hits_counts": (_vp, [_vp]),
+    "am_rule_hits_device_fired": (_vp, [_vp]),
+    "am_rule_hits_device_labels": (_vp, [_vp]),
+    "am_rule_hits_device_counts": (_vp, [_vp]),
+    "am_rule_hits_free": (None, [_vp]),
+    "am_select_rule": (C.c_int, [_vp, C.c_uint32, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
+    "am_rules_geometry": (None, [_u32p, _u32p, _u32p]),
     "am_fragments_from_spans": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_vp)]),
     "am_extract_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "am_extract": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(Slice), _sz, C.POINTER(_vp), C.POINTER(_vp)]),
@@ -219,6 +238,7 @@ _HOST = {
     "amh_spans_fold_words": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
     "amh_spans": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(Slice), _sz, _vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
     "amh_extract_fold": (C.c_int, [_vp, _vp, C.POINTER(Slice), _sz, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
+    "amh_rules_fold": (C.c_int, [_vp, _vp, C.c_uint64, _sz, _sz, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "amh_substitute_fold": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, C.POINTER(_vp), _vp]),
     "amh_substitute_fold_words": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, _vp, C.POINTER(_vp), _vp]),
     "amh_substitute": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, C.POINTER(_vp), _vp]),
@@ -979,6 +999,215 @@ def select_geometry():
     return int(t.value), int(s.value)
 
 
+def rules_geometry():
+    """(tile_haystacks, lds_slot_words, lds_rules) of the rule evaluation (am_rules_geometry): every internal limit a test must cross."""
+    t, w, r = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    libam().am_rules_geometry(C.byref(t), C.byref(w), C.byref(r))
+    return int(t.value), int(w.value), int(r.value)
+
+
+class Not:
+    """A negated needle inside Rule.cnf: the literal is true where the needle does NOT occur."""
+
+    def __init__(self, needle):
+        self.needle = needle
+
+
+class Rule:
+    """One rule of a RuleSet, in conjunctive normal form over needles: every needle of all_of occurs, AND some needle of any_of occurs, AND no needle of none_of
+    occurs.  An absent any_of adds no clause; an explicit empty any_of=[] adds an empty clause, which is false.  A rule without a clause is true.  Rule.cnf takes the
+    clauses themselves: a list of lists of needles, a needle wrapped in Not negated."""
+
+    def __init__(self, all_of=(), any_of=None, none_of=()):
+        self.clauses = [[(n, False)] for n in all_of]
+        if any_of is not None:
+            self.clauses.append([(n, False) for n in any_of])
+        self.clauses += [[(n, True)] for n in none_of]
+
+    @classmethod
+    def cnf(cls, clauses):
+        r = cls()
+        r.clauses = [[(x.needle, True) if isinstance(x, Not) else (x, False) for x in c] for c in clauses]
+        return r
+
+
+def compile_rules(case, rules):
+    """Needles to slots, on the host: (needles [bytes], slots [int per needle], n_slots, rule_off, clause_off, literals) as am_rules_create takes them.
+    IgnoreCase needles are lower-cased the way Searcher does; needles are deduplicated by text.  A slot's bit says "one of my needles occurred", so needles that occur in
+    exactly the same clauses, all of them positively, share ONE slot -- a 5 000-word any_of used by one rule costs one bit per haystack.  A needle with a negated
+    membership keeps a slot of its own: NOT a OR NOT b is not NOT (a OR b)."""
+    texts, members = {}, []                                # needle text -> index; per needle the set of (clause, negated)
+    clauses, rule_off = [], [0]
+    for rule in rules:
+        for clause in rule.clauses:
+            ids = []
+            for needle, neg in clause:
+                t = _as_bytes(needle)
+                if case == IGNORE_CASE:
+                    t = lower_utf8(t)
+                k = texts.setdefault(t, len(texts))
+                if k == len(members):
+                    members.append(set())
+                members[k].add((len(clauses), bool(neg)))
+                ids.append((k, bool(neg)))
+            clauses.append(ids)
+        rule_off.append(len(clauses))
+    groups, slots = {}, []
+    for k, m in enumerate(members):
+        key = frozenset(m) if not any(neg for _, neg in m) else ("own", k)
+        slots.append(groups.setdefault(key, len(groups)))
+    clause_off, literals = [0], []
+    for ids in clauses:
+        seen = set()
+        for k, neg in ids:
+            lit = slots[k] | (RULE_NEGATE if neg else 0)
+            if lit not in seen:
+                seen.add(lit)
+                literals.append(lit)
+        clause_off.append(len(literals))
+    return (list(texts), slots, len(groups), np.asarray(rule_off, np.uint64), np.asarray(clause_off, np.uint64), np.asarray(literals, np.uint32))
+
+
+def _fired_bits(words, n_rules, n_hay):
+    """bool[n_rules, n_hay] of uint64[n_rules, hay_words] (bit h % 64 of word h / 64)."""
+    if n_rules == 0 or n_hay == 0:
+        return np.zeros((n_rules, n_hay), bool)
+    bits = np.unpackbits(np.ascontiguousarray(words).view(np.uint8).reshape(n_rules, -1), axis=1, bitorder="little")
+    return bits[:, :n_hay].astype(bool)
+
+
+def rules_fold_host(hay, val, n_hay, n_slots, rule_off, clause_off, literals):
+    """amh_rules_fold: the sequential definition of am_rules_eval (host/rules.hpp rulesFold) over fold steps the caller brings -- (haystack, value) arrays in fold order
+    -- and a program as am_rules_create takes it.  Runs without a device.  (fired_words uint64[n_rules, hay_words], labels, counts)."""
+    hay, val = np.ascontiguousarray(hay, np.uint32), np.ascontiguousarray(val, np.uint32)
+    ro, co, li = np.ascontiguousarray(rule_off, np.uint64), np.ascontiguousarray(clause_off, np.uint64), np.ascontiguousarray(literals, np.uint32)
+    n_rules, hw = len(ro) - 1, (n_hay + 63) // 64
+    fired, labels, counts = np.zeros(max(n_rules * hw, 1), np.uint64), np.zeros(max(n_hay, 1), np.uint32), np.zeros(max(n_rules, 1), np.uint64)
+    _hcheck(libhost().amh_rules_fold(hay.ctypes.data if hay.size else None, val.ctypes.data if val.size else None, hay.size, n_hay, n_slots, ro.ctypes.data, co.ctypes.data,
+                                     li.ctypes.data if li.size else None, n_rules, fired.ctypes.data, labels.ctypes.data, counts.ctypes.data))
+    return fired[:n_rules * hw].reshape(n_rules, hw), labels[:n_hay], counts[:n_rules]
+
+
+class RuleHits:
+    """What a RuleSet found in a batch (am_rule_hits): rule-major bitmaps, first-rule-wins labels and per-rule counts in HBM, copied to the host on first use."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            libam().am_rule_hits_free(self._h)
+            self._h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def n_hay(self):
+        return int(libam().am_rule_hits_haystacks(self._h))
+
+    @property
+    def n_rules(self):
+        return int(libam().am_rule_hits_rules(self._h))
+
+    @property
+    def hay_words(self):
+        return int(libam().am_rule_hits_hay_words(self._h))
+
+    def _host(self, fn, n, ctype):
+        p = fn(self._h)
+        if not p:
+            check(AM_ERR_HIP)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=(max(n, 1),))[:n].copy()
+
+    @property
+    def fired_words(self):
+        """np.uint64[n_rules, hay_words]: bit h % 64 of word h // 64 of row r is set iff rule r fires on haystack h; the bits beyond n_hay are zero."""
+        return self._host(libam().am_rule_hits_fired, self.n_rules * self.hay_words, C.c_uint64).reshape(self.n_rules, self.hay_words)
+
+    @property
+    def fired(self):
+        """bool[n_rules, n_hay]."""
+        return _fired_bits(self.fired_words, self.n_rules, self.n_hay)
+
+    @property
+    def labels(self):
+        """np.uint32[n_hay]: the smallest rule that fires, RULE_NONE where none does."""
+        return self._host(libam().am_rule_hits_labels, self.n_hay, C.c_uint32)
+
+    @property
+    def counts(self):
+        """np.uint64[n_rules]: the haystacks on which each rule fires."""
+        return self._host(libam().am_rule_hits_counts, self.n_rules, C.c_uint64)
+
+    def select(self, rule, first=False, invert=False, batch=None):
+        """am_select_rule: the Selection of the haystacks of `batch` (the am_batch* the hits were made from) on which `rule` fires -- first=True: for which it is the
+        FIRST rule that fires (label == rule); invert: the others."""
+        return _select(lambda out: libam().am_select_rule(self._h, int(rule), RULE_FIRST if first else RULE_FIRED, int(bool(invert)), batch, out))
+
+
+class RuleSet:
+    """Many boolean rules over needles, evaluated from ONE scan (am_rules): rs = RuleSet(IGNORE_CASE, [Rule(all_of=["nike", "shoe"], none_of=["kids"]), ...]);
+    rs.eval(texts) / rs.eval_batch(batch) give a RuleHits.  The needles are compiled to slots on the host (compile_rules); n_slots is the width of a haystack's row."""
+
+    def __init__(self, case, rules):
+        self.case = case
+        self.rules = list(rules)
+        self.needles, self.slots, self.n_slots, self.rule_off, self.clause_off, self.literals = compile_rules(case, self.rules)
+        self._a = self._t = self._h = None                  # the automaton, its slot table and the program on the device, made on first use
+
+    @classmethod
+    def from_program(cls, case, needles, slots, n_slots, rule_off, clause_off, literals):
+        """A rule set from a program the caller compiled: needles[i] carries slot slots[i] (a needle may appear several times, a value >= n_slots is skipped), the
+        three arrays as am_rules_create takes them.  The needles are taken as they are (under IGNORE_CASE: lower-cased already)."""
+        rs = cls(case, [])
+        rs.needles, rs.slots, rs.n_slots = [_as_bytes(n) for n in needles], [int(v) for v in slots], int(n_slots)
+        rs.rule_off, rs.clause_off, rs.literals = np.asarray(rule_off, np.uint64), np.asarray(clause_off, np.uint64), np.asarray(literals, np.uint32)
+        rs.rules = [None] * (len(rs.rule_off) - 1)
+        return rs
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            libam().am_rules_destroy(self._h)
+            self._h = None
+
+    @property
+    def automaton(self):
+        if self._a is None:
+            self._a = Automaton(self.needles, values=self.slots)
+        return self._a
+
+    @property
+    def handle(self):
+        if self._h is None:
+            self._t = ValuesTable(self.automaton, n_needles=self.n_slots)
+            h = _vp()
+            check(libam().am_rules_create(self._t.handle, self.rule_off.ctypes.data, self.clause_off.ctypes.data, self.literals.ctypes.data if self.literals.size else None,
+                                          len(self.rules), C.byref(h)))
+            self._h = h
+        return self._h
+
+    def eval_batch(self, batch):
+        """am_rules_eval_batch on a device-resident batch (an am_batch* handle)."""
+        h = _vp()
+        check(libam().am_rules_eval_batch(self.handle, self.case, batch, C.byref(h)))
+        return RuleHits(h)
+
+    def eval(self, texts):
+        """am_rules_eval: the one-shot form on host texts."""
+        s = _Slices(texts)
+        h = _vp()
+        check(libam().am_rules_eval(self.handle, self.case, s.arr, s.n, C.byref(h)))
+        return RuleHits(h)
+
+    def eval_host_mirror(self, texts):
+        """The same through the C++ host mirror (host/rules.hpp rulesFold over the fold steps of amh_run_list): (fired bool[n_rules, n_hay], labels, counts)."""
+        hay, _, val = self.automaton.run_batch_with_case(self.case, texts)
+        words, labels, counts = rules_fold_host(hay, val, len(texts), self.n_slots, self.rule_off, self.clause_off, self.literals)
+        return _fired_bits(words, len(self.rules), len(texts)), labels, counts
+
+
 def _grep_texts(texts, sel):
     """(indices, [bytes]) of a selection over host texts: the texts are the caller's already, only the indices come back."""
     def text(t):
@@ -1436,7 +1665,7 @@ class Splitter:
 
 DEBUG_SWITCHES = ("AM_SF_TRACE", "AM_SF_POOL_BLOCKS", "AM_SF_NO_CHILDREN", "AM_DFA", "AM_DFA_CHUNK", "AM_DFA_RARE_PERMILLE", "AM_DFA_MIN_KIB", "AM_DFA_TUNE", "AM_DFA_NO_CHAINS", "AM_FLATTEN_TRACE", "AM_FLATTEN_SERIAL", "AM_NO_IDS_SCAN",
                   "AM_RP_FULL_SCANS", "AM_RP_PIECES", "AM_RP_PARALLEL_FOLD", "AM_RP_GROUPS", "AM_RP_NO_FUSE", "AM_RP_NO_SPIN",
-                  "AM_RP_MAT_MAIN", "AM_RP_NO_RANGE_REUSE", "AM_RP_TRACE", "AM_RP_LDS", "AM_RP_LOOP", "AM_RUN_SEGMENTS", "AM_HIST_RECORDS_MIB", "AM_HIST_TRACE", "AM_HIST_FLUSH_TILES", "AM_SPLIT_CHAIN_LIMIT", "AM_SPANS_CHAIN_LIMIT")
+                  "AM_RP_MAT_MAIN", "AM_RP_NO_RANGE_REUSE", "AM_RP_TRACE", "AM_RP_LDS", "AM_RP_LOOP", "AM_RUN_SEGMENTS", "AM_HIST_RECORDS_MIB", "AM_HIST_TRACE", "AM_HIST_FLUSH_TILES", "AM_SPLIT_CHAIN_LIMIT", "AM_SPANS_CHAIN_LIMIT", "AM_RULES_ROWS_MIB")
 
 
 def debug_set(name, value):

@@ -34,6 +34,7 @@ enum Key {
     kHistFlushTiles,      // AM_HIST_FLUSH_TILES: tiles after which a workgroup of k_needle_hist flushes and clears its LDS counts (tests: 1 = after every tile); unset: 2048, the most that cannot wrap a counter
     kSplitChainLimit,     // AM_SPLIT_CHAIN_LIMIT: records the lane of a chain's head looks at in k_split_walk before the chain is left to the pointer-doubling rounds (tests: 1 = the head looks at one record: chains of three records and more go to the rounds); unset: 32
     kSpansChainLimit,     // AM_SPANS_CHAIN_LIMIT: the same for the candidates of am_spans* in leftmost-longest mode (k_spans_walk); unset: 32
+    kRulesRowsMiB,        // AM_RULES_ROWS_MIB: MiB of slot rows am_rules_eval_batch keeps in HBM at a time (tests: 0 = the smallest group, 64 haystacks); unset: 1024
     kCount
 };
 
@@ -46,7 +47,7 @@ inline const char* name_of(int k)
 {
     static const char* const names[kCount] = {"AM_SF_TRACE", "AM_SF_POOL_BLOCKS", "AM_SF_NO_CHILDREN", "AM_DFA", "AM_DFA_CHUNK", "AM_DFA_RARE_PERMILLE", "AM_DFA_MIN_KIB", "AM_DFA_TUNE", "AM_DFA_NO_CHAINS", "AM_FLATTEN_TRACE", "AM_FLATTEN_SERIAL", "AM_NO_IDS_SCAN",
                                               "AM_RP_FULL_SCANS", "AM_RP_PIECES", "AM_RP_PARALLEL_FOLD", "AM_RP_GROUPS", "AM_RP_NO_FUSE", "AM_RP_NO_SPIN",
-                                              "AM_RP_MAT_MAIN", "AM_RP_NO_RANGE_REUSE", "AM_RP_TRACE", "AM_RP_LDS", "AM_RP_LOOP", "AM_RUN_SEGMENTS", "AM_HIST_RECORDS_MIB", "AM_HIST_TRACE", "AM_HIST_FLUSH_TILES", "AM_SPLIT_CHAIN_LIMIT", "AM_SPANS_CHAIN_LIMIT"};
+                                              "AM_RP_MAT_MAIN", "AM_RP_NO_RANGE_REUSE", "AM_RP_TRACE", "AM_RP_LDS", "AM_RP_LOOP", "AM_RUN_SEGMENTS", "AM_HIST_RECORDS_MIB", "AM_HIST_TRACE", "AM_HIST_FLUSH_TILES", "AM_SPLIT_CHAIN_LIMIT", "AM_SPANS_CHAIN_LIMIT", "AM_RULES_ROWS_MIB"};
     return names[k];
 }
 constexpr long kUnset = -1;

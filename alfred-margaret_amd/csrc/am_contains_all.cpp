@@ -49,6 +49,15 @@ extern "C" int am_needle_ids_create(const am_automaton* a, const uint64_t* value
 
 extern "C" void am_needle_ids_destroy(am_needle_ids* ids) { delete ids; }
 
+// The slot rows of a batch by the direct route (round 5): the scan itself sets the bit of every needle id it reports -- no record is written -- and a haystack whose
+// row is full is not looked at any further (`Done`, Searcher.hs:181; a full row cannot grow).  The per-haystack "row is full" flags go to the sink.  *taken = false:
+// the call did not go this way (the general kernel, the empty needle's dense pass, nothing to scan) and the caller folds the records instead.
+static int direct_rows(const am_needle_ids* ids, int case_mode, am_batch* b, uint32_t* d_bits, uint32_t words, uint32_t* d_missing, FlagSink& sink, bool* taken)
+{
+    *taken = false;
+    return scan_needle_ids(ids->a, case_mode, b, (const uint64_t*)ids->vals_off.p, (const uint32_t*)ids->vals.p, ids->n_needles, d_bits, words, d_missing, sink, taken);
+}
+
 // containsAll with the flags left in HBM: the sink decides what becomes of them (am_contains_all_batch: the copy to the caller; a select: the compaction)
 int am::host::contains_all_flags(const am_needle_ids* ids, int case_mode, am_batch* b, FlagSink& sink)
 {
@@ -60,15 +69,13 @@ int am::host::contains_all_flags(const am_needle_ids* ids, int case_mode, am_bat
     hipStream_t st; AM_TRY(get_stream(b->dev, &st));
     DevBuf records, rec_first, bits, flags;
     const uint32_t words = (ids->n_needles + 31) / 32;
-    // The direct route (round 5): the scan itself sets the bit of every needle id it reports -- no record is written -- and a haystack whose set is
-    // complete is not looked at any further (`Done`, Searcher.hs:181), like containsAny's first match.  One bitmap row per haystack, up to 8 GiB of them;
-    // wider batches, the general kernel and automata with the empty needle fold the records (below).
+    // The direct route (direct_rows): one bitmap row per haystack, up to 8 GiB of them; wider batches, the general kernel and automata with the empty needle fold
+    // the records (below).
     if ((uint64_t)n_hay * words * 4 <= (8ull << 30) && !cfg::on(cfg::kNoIdsScan)) {
         AM_TRY(bits.ensure((uint64_t)n_hay * words * 4 + 64));
         AM_TRY(flags.ensure((size_t)n_hay * 4 + 64));                  // (here: the haystacks' missing-id counters)
         bool taken = false;
-        AM_TRY(scan_needle_ids(ids->a, case_mode, b, (const uint64_t*)ids->vals_off.p, (const uint32_t*)ids->vals.p, ids->n_needles, (uint32_t*)bits.p, words,
-                               (uint32_t*)flags.p, sink, &taken));
+        AM_TRY(direct_rows(ids, case_mode, b, (uint32_t*)bits.p, words, (uint32_t*)flags.p, sink, &taken));
         if (taken) return AM_OK;
     }
     uint64_t n_rec = 0;
@@ -196,9 +203,9 @@ int fold_batch(const am_needle_ids* ids, int case_mode, am_batch* b, const Recor
     AM_TRY(am_count_batch(ids->a, case_mode, b, per.data(), &total_values));
     if (total_values == 0) return AM_OK;
     if (total_values * sizeof(Record) <= budget) return fold_scan(ids, case_mode, b, ra, 0, fold);
-    // groups of whole consecutive haystacks, each a batch of its own: its text copied (device to device) to a 16-byte aligned start, its offsets rebased
+    // groups of whole consecutive haystacks, each a batch of its own (sub_batch, am_fold.h)
     hipStream_t st; AM_TRY(get_stream(b->dev, &st));
-    std::vector<uint64_t> offs((size_t)b->n_hay + 1), sub_offs;
+    std::vector<uint64_t> offs((size_t)b->n_hay + 1);
     HIP_TRY(hipMemcpyAsync(offs.data(), b->d_offsets, offs.size() * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     DerivedBatch sub;                                       // ONE batch: its buffers serve group after group
@@ -208,15 +215,7 @@ int fold_batch(const am_needle_ids* ids, int case_mode, am_batch* b, const Recor
         while (h1 < b->n_hay && (h1 == h0 || (values + per[h1]) * sizeof(Record) <= budget)) values += per[h1++];      // (a haystack beyond the budget by itself: a group of one)
         const uint64_t bytes = offs[h1] - offs[h0];
         if (values != 0 && bytes != 0) {
-            uint64_t* sub_off; uint8_t* sub_text;
-            AM_TRY(sub.text(bytes, st, &sub_text));
-            AM_TRY(sub.offsets(h1 - h0, &sub_off));
-            sub_offs.resize((size_t)(h1 - h0) + 1);
-            for (uint32_t h = h0; h <= h1; h++) sub_offs[h - h0] = offs[h] - offs[h0];
-            HIP_TRY(hipMemcpyAsync(sub_text, (const uint8_t*)b->d_text + offs[h0], bytes, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipMemcpyAsync(sub_off, sub_offs.data(), sub_offs.size() * 8, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            AM_TRY(sub.ready(bytes, h1 - h0));
+            AM_TRY(sub_batch(b, h0, h1, offs[h0], offs[h1], sub, st));
             AM_TRY(fold_scan(ids, case_mode, sub.b.get(), ra, h0, fold));
         }
         h0 = h1;
@@ -269,6 +268,34 @@ struct HistOut {
 };
 
 }  // namespace
+
+// the slot rows of a batch (am_host.h): what am_rules_eval_batch evaluates.  The direct route keeps its flags to itself here; the record route is k_idset under
+// fold_batch, a group's records into the rows of the group's haystacks
+int am::host::slot_rows(const am_needle_ids* ids, int case_mode, am_batch* b, uint32_t* d_bits, uint32_t words, uint32_t* d_missing)
+{
+    if (b->n_hay == 0 || words == 0) return AM_OK;
+    struct NoSink : FlagSink {
+        int begin(const am_batch*) override { return AM_OK; }
+        // called with b->mu held: the scan writes the batch's scratch (its flags, its unit ticket), so it has finished before the lock goes -- another thread's
+        // call on the same batch clears that scratch on a stream of its own
+        int device(const uint8_t*, hipStream_t st) override { HIP_TRY(hipStreamSynchronize(st)); return AM_OK; }
+        int constant(uint8_t) override { return AM_OK; }
+    } none;
+    bool taken = false;
+    if (!cfg::on(cfg::kNoIdsScan)) AM_TRY(direct_rows(ids, case_mode, b, d_bits, words, d_missing, none, &taken));
+    if (taken) return AM_OK;
+    {
+        ON_DEVICE(b->dev);
+        hipStream_t st; AM_TRY(get_stream(b->dev, &st));
+        HIP_TRY(hipMemsetAsync(d_bits, 0, (uint64_t)b->n_hay * words * 4, st));
+        HIP_TRY(hipStreamSynchronize(st));                  // (as HistOut::begin: the folds follow on this thread's stream, the scans synchronise in between)
+    }
+    return fold_batch(ids, case_mode, b, [&](const Record* recs, uint64_t n_rec, uint32_t h0, uint32_t, const am_batch*, int, hipStream_t st) {
+        Prof pr("idset", st);
+        HIP_TRY(launch_idset(recs, 0, n_rec, (const uint64_t*)ids->vals_off.p, (const uint32_t*)ids->vals.p, ids->n_needles, 0, words, d_bits + (uint64_t)h0 * words, st));
+        return AM_OK;
+    });
+}
 
 // am_select_spans_batch's predicate (am_select.cpp): d_flags[h] = 1 for every haystack whose AM_SPANS_ALL row under table t is not empty; d_flags = b->n_hay bytes in
 // HBM that this call clears.  Scanned and folded in bounded record memory like the whole-word counts above: k_hay_flags_spans reads the text and the offsets of the

@@ -270,6 +270,15 @@ hipError_t launch_extract_emit(const uint32_t* head, const uint64_t* rank, const
 // am_select_geometry: bytes of new text per workgroup of launch_split_gather (am_split.hip), elements per workgroup of launch_scan / a sweep of launch_scan_jobs (am_scan.hip)
 uint32_t split_gather_tile_bytes();
 uint32_t scan_tile_items();
+// rule sets (am_rules.hip; the program view, the launch struct and the evaluator of one (row, program) pair: am_rules.h).  k_rules_eval: the slot rows of in.n_hay
+// consecutive haystacks against the program, into their words of in.fired, their labels and in.counts (accumulating: cleared by the caller).  in.n_hay is a whole batch
+// or a group that begins at a multiple of 64 haystacks (in.word0), so no word of `fired` is written twice.  A persistent grid sized from n_cu.
+struct RulesEvalIn;
+hipError_t launch_rules_eval(const RulesEvalIn& in, int n_cu, hipStream_t st);
+// flags[h] = bit h of fired_row (one rule's row of `fired`), or -- fired_row null -- labels[h] == rule: the n_hay byte flags launch_select_plan takes
+hipError_t launch_rule_flags(const uint64_t* fired_row, const uint32_t* labels, uint32_t rule, uint64_t n_hay, uint64_t hay_words, uint8_t* flags, hipStream_t st);
+// am_rules_geometry: haystacks per workgroup step of k_rules_eval, the widest slot row (32-bit words) it stages in LDS, the rules whose counts it keeps in LDS
+void rules_geometry(uint32_t* tile_haystacks, uint32_t* lds_slot_words, uint32_t* lds_rules);
 // incremental re-scan between Replacer passes (am_replace.hip)
 struct RpWin { uint64_t src_abs; uint64_t ws; uint32_t len; uint32_t own_lo; };   // window: bytes src_abs.. of the next text; ws = its start inside the haystack; records with end > own_lo are its own
 hipError_t launch_rp_win_count(const RpHay* hs, uint32_t n_act, uint32_t* nwin, hipStream_t st);

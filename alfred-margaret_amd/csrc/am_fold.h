@@ -225,6 +225,21 @@ struct DerivedBatch {
     }
 };
 
+// haystacks [h0, h1) of b as a batch of its own in `sub` (ONE DerivedBatch serves group after group: the groups of fold_batch, am_contains_all.cpp, and of
+// am_rules_eval_batch, am_rules.cpp): the text copied device to device to a 16-byte aligned start, the offsets rebased on the device.  o0 / o1: b's offsets at h0 /
+// h1, which the caller has on the host.  Returns when the copies have finished: a batch like any other.
+inline int sub_batch(const am_batch* b, uint64_t h0, uint64_t h1, uint64_t o0, uint64_t o1, DerivedBatch& sub, hipStream_t st)
+{
+    const uint64_t bytes = o1 - o0;
+    uint64_t* sub_off; uint8_t* sub_text;
+    AM_TRY(sub.text(bytes, st, &sub_text));
+    AM_TRY(sub.offsets(h1 - h0, &sub_off));
+    if (bytes) HIP_TRY(hipMemcpyAsync(sub_text, (const uint8_t*)b->d_text + o0, bytes, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(launch_mx_offsets(b->d_offsets + h0, h1 - h0 + 1, 0 - o0, sub_off, st));      // (base + local[i] in 64-bit arithmetic: local[i] - o0)
+    HIP_TRY(hipStreamSynchronize(st));
+    return sub.ready(bytes, h1 - h0);
+}
+
 }  // namespace host
 }  // namespace am
 

@@ -1,7 +1,7 @@
 // am_host.h -- what the host-side translation units of libam share (am_abi.cpp: runtime and thread state, automata, batches, one-shot entry points, results;
 // am_run.cpp: routes and scans; am_replacer.cpp: the Replacer; am_contains_all.cpp: containsAll, the fold checksum, the per-needle counts and the needle matrix;
-// am_splitter.cpp: the Splitter; am_spans.cpp: match spans; am_subst.cpp: substitute; am_select.cpp: select -- the last two through am_spans.h, which adds the span
-// table and the spans result): error handling, the per-device runtime, device buffers, the handle structs of include/am.h and the few scan entry points the Replacer
+// am_splitter.cpp: the Splitter; am_spans.cpp: match spans; am_subst.cpp: substitute; am_select.cpp: select; am_rules.cpp: rule sets -- substitute and select through
+// am_spans.h, which adds the span table and the spans result): error handling, the per-device runtime, device buffers, the handle structs of include/am.h and the few scan entry points the Replacer
 // drives.  am_fold.h, included at the end, holds the scaffolding of the device stages: argument checks, the CSR result handle, the chain finisher, the one-shot
 // wrapper, the segment loop and the builder of derived batches.  Internal: nothing here is part of the C ABI.
 #pragma once
@@ -193,6 +193,16 @@ struct am_needle_ids {
     am::host::DevBuf vals_off, vals;
 };
 
+// what am_rules_eval* leaves in HBM (am_rules.cpp; am_select_rule, am_select.cpp, reads it): rule-major bitmaps, first-rule-wins labels, per-rule counts; the host
+// copies are made once, on first use.  Remembers the batch it was made from as am_selection does.  (Holds DevBufs: on the heap only.)
+struct am_rule_hits {
+    int dev = 0;
+    uint64_t n_hay = 0, src_total = 0, n_rules = 0, hay_words = 0;
+    am::host::DevBuf fired, labels, counts;                 // uint64[n_rules][hay_words], uint32[n_hay], uint64[n_rules]
+    std::vector<uint64_t> h_fired, h_counts; std::vector<uint32_t> h_labels;
+    bool fired_fetched = false, labels_fetched = false, counts_fetched = false;
+};
+
 namespace am {
 namespace host {
 
@@ -248,6 +258,10 @@ int contains_all_flags(const am_needle_ids* ids, int case_mode, am_batch* b, Fla
 // dense pass, nothing to scan) and the caller folds the records instead.
 int scan_needle_ids(const am_automaton* a, int case_mode, am_batch* b, const uint64_t* d_vals_off, const uint32_t* d_vals, uint32_t n_needles,
                     uint32_t* d_bits, uint32_t words, uint32_t* d_missing, FlagSink& sink, bool* taken);
+// The slot rows of a batch (am_contains_all.cpp): d_bits[h * words + v / 32] bit v % 32 set iff the fold over haystack h meets value v < ids->n_needles; n_hay x words
+// words that this call clears, d_missing: n_hay words of scratch.  The ids-mode scan where scan_needle_ids takes the call (no record is written), k_idset over the
+// records elsewhere, in bounded record memory (fold_batch).  The work is enqueued on the calling thread's stream; what the scans read back they have read back.
+int slot_rows(const am_needle_ids* ids, int case_mode, am_batch* b, uint32_t* d_bits, uint32_t words, uint32_t* d_missing);
 // sorted records of a batch: sink_final(n, &ptr) names the destination once the count is known
 int run_records(const am_automaton* a, int case_mode, am_batch* b, const std::function<int(uint64_t, Record**)>& sink_final, uint64_t* n_out, bool have_lock = false);
 // the same without a host round trip (suffix-filter route, worst-case pool): the count stays on the device

@@ -1,8 +1,9 @@
 // am_select.cpp -- select on the device (include/am.h "select"): keep the haystacks of a batch that a predicate holds for, drop the rest, and hand the kept ones on
 // as a batch of their own -- `grep -F -f needles`, `grep -v`, `grep -w` and "the lines that mention all of these terms" between two stages of a pipeline in HBM.
 // The predicates are the library's own: the flags of the containsAny / containsAll scans, taken where the scans leave them (FlagSink, am_host.h), and the non-empty
-// rows of AM_SPANS_ALL (spans_flags, am_contains_all.cpp).  The compaction by runs is am_select.hip's; the bytes move with am_split.hip's gather.  What crosses to the
-// host during a *_batch select: the kept count, the run count and the kept bytes (one copy of three words), and whatever the scans read back themselves.
+// rows of AM_SPANS_ALL (spans_flags, am_contains_all.cpp), and one rule of a rule-set result (am_select_rule over am_rules.cpp's am_rule_hits).  The compaction by
+// runs is am_select.hip's; the bytes move with am_split.hip's gather.  What crosses to the host during a *_batch select: the kept count, the run count and the kept
+// bytes (one copy of three words), and whatever the scans read back themselves.
 // Every argument is checked before any device work.
 #include "am_spans.h"
 
@@ -158,6 +159,30 @@ extern "C" int am_select_flags(const am_batch* cb, const uint8_t* host_flags, in
             return AM_OK;
         });
     });
+}
+
+// the haystacks of one rule of a rule-set result (am_rules.cpp): its row of `fired`, or labels == rule, as byte flags (k_rule_flags), then the compaction every select
+// shares.  src must be the batch the hits were made from: the hits remember haystack count, total bytes and device, as a selection does.
+extern "C" int am_select_rule(const am_rule_hits* x, uint32_t rule, int which, int invert, const am_batch* src, am_selection** out)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    if (which != AM_RULE_FIRED && which != AM_RULE_FIRST) return fail(AM_ERR_INVALID, "which must be AM_RULE_FIRED or AM_RULE_FIRST");
+    if (!x || !src) return fail(AM_ERR_INVALID, "null rule hits or batch");
+    if (rule >= x->n_rules) return fail(AM_ERR_INVALID, "rule is not below the number of rules");
+    if (x->n_hay != src->n_hay || x->src_total != src->total || x->dev != src->dev)
+        return fail(AM_ERR_INVALID, "the rule hits were not made from a batch with this haystack count and size");
+    AM_TRY(ensure_runtime());
+    SelectionPtr s = new_selection(src);
+    if (src->n_hay != 0)
+        AM_TRY(compact_written(src, invert, s.get(), [&](uint8_t* d_flags, hipStream_t st) -> int {
+            Prof pr("rule_flags", st);
+            HIP_TRY(launch_rule_flags(which == AM_RULE_FIRED ? (const uint64_t*)x->fired.p + (uint64_t)rule * x->hay_words : nullptr, (const uint32_t*)x->labels.p, rule,
+                                      x->n_hay, x->hay_words, d_flags, st));
+            return AM_OK;
+        }));
+    *out = s.release();
+    return AM_OK;
 }
 
 extern "C" int am_select_any(const am_automaton* a, int case_mode, int invert, const am_slice* hay, size_t n_hay, am_selection** out)

@@ -5,6 +5,7 @@
 #include <string>
 
 #include "replacer.hpp"
+#include "rules.hpp"
 #include "spans.hpp"
 #include "splitter.hpp"
 
@@ -163,6 +164,27 @@ int amh_spans(void* h, int case_mode, int mode, const am_slice* hay, size_t n_ha
             for (auto& pv : accs[i].v) steps.push_back(FoldStep{(uint32_t)i, pv.first, pv.second});
         const std::vector<uint32_t> lb(len_bytes, len_bytes + n_values), lc(len_code_points, len_code_points + n_values);
         spansOut(spansFold((CaseSensitivity)case_mode, mode == AM_SPANS_LEFTMOST_LONGEST, steps, texts, lb, lc), n_hay, offs_out, spans_out, n_out);
+    });
+}
+
+// ---- rule sets (rules.hpp): rulesFold over fold steps the caller brings (n (haystack, value) pairs in fold order, haystacks ascending) and a program in the C ABI's
+// form (rule_off: n_rules + 1, clause_off: rule_off[n_rules] + 1, literals: clause_off[last]): no device is touched.  fired_out: n_rules x ceil(n_hay / 64) words,
+// labels_out: n_hay, counts_out: n_rules, all the caller's
+int amh_rules_fold(const uint32_t* hay_in, const uint32_t* val_in, uint64_t n, size_t n_hay, size_t n_slots, const uint64_t* rule_off, const uint64_t* clause_off,
+                   const uint32_t* literals, uint32_t n_rules, uint64_t* fired_out, uint32_t* labels_out, uint64_t* counts_out)
+{
+    return guarded([&] {
+        if (!rule_off || !clause_off) throw AmError(AM_ERR_INVALID, "amh_rules_fold: null offsets");
+        RuleProgram p;
+        p.ruleOff.assign(rule_off, rule_off + (size_t)n_rules + 1);
+        p.clauseOff.assign(clause_off, clause_off + (size_t)p.ruleOff.back() + 1);
+        if (p.clauseOff.back()) p.literals.assign(literals, literals + (size_t)p.clauseOff.back());
+        std::vector<FoldStep> steps((size_t)n);
+        for (uint64_t i = 0; i < n; i++) steps[i] = FoldStep{hay_in[i], 0, val_in[i]};
+        const RuleHits r = rulesFold(steps, n_hay, n_slots, p);
+        if (!r.fired.empty()) std::memcpy(fired_out, r.fired.data(), r.fired.size() * 8);
+        if (!r.labels.empty()) std::memcpy(labels_out, r.labels.data(), r.labels.size() * 4);
+        if (!r.counts.empty()) std::memcpy(counts_out, r.counts.data(), r.counts.size() * 8);
     });
 }
 

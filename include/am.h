@@ -457,6 +457,60 @@ AM_API void am_selection_free(am_selection* s);
 AM_API int am_batch_from_selection(const am_batch* src, const am_selection* s, am_batch** out);
 AM_API void am_select_geometry(uint32_t* tile_bytes, uint32_t* scan_block_items);
 
+/* ---- rule sets: many boolean rules over needle groups, evaluated from ONE scan of a batch, in HBM ---------------
+ * A rule is "the title mentions nike and shoe, any word of this 5 000-word list, and none of these three".  Categorising a product feed, multi-label tagging and
+ * first-rule-wins routing evaluate hundreds of such rules over the same lines; all a rule needs to know is, per haystack, WHICH needles occurred at all -- the set
+ * the containsAll scan computes without writing a record.  So one scan with the union dictionary answers every rule of a rule set; Searcher.containsAny (one clause),
+ * Searcher.containsAll (unit clauses) and `grep -v` (a negated literal) are special cases of the one operator.
+ * SLOTS.  `slots` is an am_needle_ids whose values are slot numbers 0 .. n_slots-1 (its n_needles argument is n_slots).  Several needles may carry the same slot; a
+ * needle may appear several times with different slots.  P(h) = { v < n_slots : the fold of runWithCase (Automaton.hs:442-553) over haystack h meets Match _ v } --
+ * the complement of containsAll's final IntSet (Searcher.hs:173-187).  Values >= n_slots are SKIPPED (the convention of am_needle_ids).  The empty needle does here
+ * what it does in the reference's fold.
+ * PROGRAM, in conjunctive normal form over slot literals:
+ *   rule_off    uint64[n_rules + 1]    offsets into the clauses; n_clauses = rule_off[n_rules]
+ *   clause_off  uint64[n_clauses + 1]  offsets into the literals; n_literals = clause_off[n_clauses]
+ *   literals    uint32[n_literals]     bits 0..30: the slot; bit 31 (AM_RULE_NEGATE) set: negated
+ * A literal is true iff (slot in P(h)) != negated.  A clause is the OR of its literals; an EMPTY CLAUSE IS FALSE.  A rule is the AND of its clauses; A RULE WITH NO
+ * CLAUSE IS TRUE.  So a rule of negative literals only fires on the empty haystack, `x AND NOT x` never fires, `x OR NOT x` always fires.  Duplicate literals are
+ * allowed.  The arrays are copied: the caller's may go after am_rules_create; `slots` (and its automaton) must outlive the rules.
+ * RESULT (am_rule_hits) for a batch of n_hay haystacks, in HBM until asked for (the accessors make host copies on first use; never NULL on success):
+ *   fired   uint64[n_rules][hay_words], hay_words = ceil(n_hay / 64): bit h % 64 of word h / 64 of row r is set iff rule r fires on haystack h; bits beyond n_hay are ZERO
+ *   labels  uint32[n_hay]: the smallest rule that fires (first rule wins), 0xFFFFFFFF when none fires
+ *   counts  uint64[n_rules]: the haystacks on which the rule fires = the popcount of its row
+ * Everything is bit-identical from run to run.  n_rules == 0 is valid (empty rows, every label 0xFFFFFFFF); n_hay == 0 gives an empty result.
+ *   am_rules_eval_batch  on a device-resident batch.  The slot rows are bounded workspace (1 GiB): a batch whose rows exceed it is scanned and evaluated in groups of
+ *                        whole consecutive haystacks, each a multiple of 64.  Only what the scans read back themselves crosses to the host (with groups: one offset a group).
+ *   am_rules_eval        the one-shot form on host slices: the slices go up as ONE batch -- no segments of the upload, unlike am_count_by_needle.
+ *   am_select_rule       the haystacks of rule `rule` as a selection of `src` (am_batch_from_selection makes them a batch): which = AM_RULE_FIRED, the rule's bit;
+ *                        AM_RULE_FIRST, label == rule -- over all rules these and "no rule" (the inverted union) are a partition of the batch.  src must be the batch
+ *                        the hits were made from: AM_ERR_INVALID when the haystack count, the total bytes or the device differ.
+ *   am_rules_geometry    for tests: the haystacks one workgroup step of the evaluation handles, the widest slot row (in 32-slot words) it keeps in LDS (wider rows are
+ *                        read in HBM), and the rules whose counts a workgroup keeps in LDS (the counts of the rules beyond go to HBM per wavefront).
+ * Arguments are checked before any device work: AM_ERR_INVALID for null handles or a null out, offsets that do not start at 0 or that decrease, a literal whose slot is
+ * >= n_slots, n_rules == 0xFFFFFFFF, a case_mode or `which` that is neither of the two, rule >= n_rules, handles on different devices, slices without memory,
+ * n_hay >= 0xFFFFFFFF.  *out is NULL after every failure. */
+#define AM_RULE_NEGATE 0x80000000u
+#define AM_RULE_FIRED 0   /* the rule's bit */
+#define AM_RULE_FIRST 1   /* label == rule */
+typedef struct am_rules am_rules;
+typedef struct am_rule_hits am_rule_hits;
+AM_API int am_rules_create(const am_needle_ids* slots, const uint64_t* rule_off, const uint64_t* clause_off, const uint32_t* literals, uint32_t n_rules, am_rules** out);
+AM_API void am_rules_destroy(am_rules* r);
+AM_API int am_rules_eval_batch(const am_rules* r, int case_mode, const am_batch* b, am_rule_hits** out);
+AM_API int am_rules_eval(const am_rules* r, int case_mode, const am_slice* hay, size_t n_hay, am_rule_hits** out);
+AM_API uint64_t am_rule_hits_haystacks(const am_rule_hits* x);
+AM_API uint64_t am_rule_hits_rules(const am_rule_hits* x);
+AM_API uint64_t am_rule_hits_hay_words(const am_rule_hits* x);
+AM_API const uint64_t* am_rule_hits_fired(am_rule_hits* x);
+AM_API const uint32_t* am_rule_hits_labels(am_rule_hits* x);
+AM_API const uint64_t* am_rule_hits_counts(am_rule_hits* x);
+AM_API const void* am_rule_hits_device_fired(const am_rule_hits* x);
+AM_API const void* am_rule_hits_device_labels(const am_rule_hits* x);
+AM_API const void* am_rule_hits_device_counts(const am_rule_hits* x);
+AM_API void am_rule_hits_free(am_rule_hits* x);
+AM_API int am_select_rule(const am_rule_hits* x, uint32_t rule, int which, int invert, const am_batch* src, am_selection** out);
+AM_API void am_rules_geometry(uint32_t* tile_haystacks, uint32_t* lds_slot_words, uint32_t* lds_rules);
+
 /* ---- extract: the matched text with some characters around it, in HBM; the snippets are a batch of their own ---------------
  * `grep -o`, `grep -o -E '.{0,40}needle.{0,40}'`, a keyword-in-context concordance, the snippets of a search front end, the windows an entity-extraction pipeline gives
  * to its next model -- over a batch, without the spans (24 bytes each) or the snippets crossing the wire.
