@@ -39,6 +39,8 @@ SPAN_DTYPE = np.dtype([("start", np.uint64), ("len", np.uint64), ("haystack", np
 RULE_NEGATE = 0x80000000
 RULE_NONE = 0xFFFFFFFF               # the label of a haystack on which no rule fires
 RULE_FIRED, RULE_FIRST = 0, 1
+SCORED_DTYPE = np.dtype([("score", np.int64), ("haystack", np.uint32), ("reserved", np.uint32)])   # am_scored
+SCORE_MAX_COLUMNS = 8                # AM_SCORE_MAX_COLUMNS
 SPANS_ALL = 0
 SPANS_LEFTMOST_LONGEST = 1
 EXTRACT_EACH = 0
@@ -159,6 +161,21 @@ ABI = {
     "am_rule_hits_free": (None, [_vp]),
     "am_select_rule": (C.c_int, [_vp, C.c_uint32, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
     "am_rules_geometry": (None, [_u32p, _u32p, _u32p]),
+    "am_weights_create": (C.c_int, [_vp, _vp, C.c_uint32, C.POINTER(_vp)]),
+    "am_weights_destroy": (None, [_vp]),
+    "am_score_batch": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_vp)]),
+    "am_score": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, C.POINTER(_vp)]),
+    "am_score_spans_batch": (C.c_int, [_vp, _vp, C.c_int, _vp, C.POINTER(_vp)]),
+    "am_matches_score": (C.c_int, [_vp, _vp, _sz, C.POINTER(_vp)]),
+    "am_scores_haystacks": (C.c_uint64, [_vp]),
+    "am_scores_columns": (C.c_uint64, [_vp]),
+    "am_scores_data": (_vp, [_vp]),
+    "am_scores_device_data": (_vp, [_vp]),
+    "am_scores_free": (None, [_vp]),
+    "am_scores_top_k": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_int, _vp, _u64p]),
+    "am_select_top_k": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_int, _vp, C.POINTER(_vp)]),
+    "am_select_score": (C.c_int, [_vp, C.c_uint32, C.c_int64, C.c_int64, C.c_int, _vp, C.POINTER(_vp)]),
+    "am_score_geometry": (None, [_u32p, _u32p]),
     "am_fragments_from_spans": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_vp)]),
     "am_extract_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "am_extract": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(Slice), _sz, C.POINTER(_vp), C.POINTER(_vp)]),
@@ -239,6 +256,7 @@ _HOST = {
     "amh_spans": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(Slice), _sz, _vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
     "amh_extract_fold": (C.c_int, [_vp, _vp, C.POINTER(Slice), _sz, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
     "amh_rules_fold": (C.c_int, [_vp, _vp, C.c_uint64, _sz, _sz, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "amh_score": (C.c_int, [_vp, _vp, C.c_uint64, _sz, _sz, _vp, C.c_uint32, _vp]),
     "amh_substitute_fold": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, C.POINTER(_vp), _vp]),
     "amh_substitute_fold_words": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, _vp, C.POINTER(_vp), _vp]),
     "amh_substitute": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, C.POINTER(_vp), _vp]),
@@ -556,6 +574,30 @@ class Automaton:
             libhost().amh_free_u64(po)
             libhost().amh_free_u64(pe)
         return offs, ents
+
+    def score(self, case, texts, weights, whole_words=False, n_values=None):
+        """A number per match, added up per text: np.int64[n_cols, len(texts)], scores[c, i] = the sum of weights[c][v] over every fold step `Match _ v` of
+        runWithCase (Automaton.hs:442-553) over texts[i], modulo 2^64 -- the fold `acc + weight v`.  weights: one column (a flat list, one weight per value handle) or
+        up to SCORE_MAX_COLUMNS of them.  am_score: scanned and summed in HBM, the scores come back.  whole_words: True (the default word class) or a class as
+        SpanTable takes it -- only the whole-word occurrences add (include/am.h "whole words")."""
+        n = len(self.needles) if n_values is None else int(n_values)
+        if not whole_words:
+            return Weights(ValuesTable(self, n), weights).score_texts(case, texts).scores
+        t = SpanTable(self, n_needles=n, word_bytes=whole_words)
+        w = Weights(t.values, weights)
+        s = _Slices(texts)
+        b = _vp()
+        check(libam().am_batch_upload(s.arr, s.n, C.byref(b)))
+        try:
+            return t.score_batch(case, b, w).scores
+        finally:
+            libam().am_batch_destroy(b)
+
+    def score_host_mirror(self, case, texts, weights, n_values=None):
+        """The same through the C++ host mirror (host/automaton.hpp scoreByHaystack over the fold steps of amh_run_list)."""
+        n = len(self.needles) if n_values is None else int(n_values)
+        hay, _, val = self.run_batch_with_case(case, texts)
+        return score_host(hay, val, len(texts), n, weights)
 
     def spans(self, case, texts, leftmost_longest=False, whole_words=False):
         """Where every match starts: (offsets np.uint64[len(texts) + 1], spans SPAN_DTYPE[offsets[-1]]); the spans of text i are spans[offsets[i]:offsets[i + 1]],
@@ -915,6 +957,16 @@ class SpanTable:
         the haystacks that hold a needle as a whole word)."""
         return _select(lambda out: libam().am_select_spans_batch(self._h, case, int(bool(invert)), batch, out))
 
+    @property
+    def values(self):
+        """The ValuesTable the table was made over: what a Weights for score_batch is made over."""
+        return self._values
+
+    def score_batch(self, case, batch, weights):
+        """am_score_spans_batch on a device-resident batch: the Scores of its haystacks over the AM_SPANS_ALL rows of this table (with a word class: the whole-word
+        occurrences only).  weights: a Weights made over this table's `values`."""
+        return _scores(lambda out: libam().am_score_spans_batch(self._h, weights.handle, case, batch, out))
+
     def fragments_from_spans(self, batch, spans_raw, before, after, merged, raw=False):
         """am_fragments_from_spans: the windows of an am_spans* the caller holds (spans_batch(..., raw=True) on `batch`) as (offsets np.uint64[n_hay + 1], fragments
         FRAGMENT_DTYPE), relative to their haystacks.  raw: the am_fragments* itself, in HBM (am_batch_from_fragments takes it; free with am_fragments_free)."""
@@ -1004,6 +1056,127 @@ def rules_geometry():
     t, w, r = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
     libam().am_rules_geometry(C.byref(t), C.byref(w), C.byref(r))
     return int(t.value), int(w.value), int(r.value)
+
+
+def score_geometry():
+    """(tile_records, topk_block_items) of the scoring fold and of the top-k histogram (am_score_geometry): known without a device."""
+    t, b = C.c_uint32(0), C.c_uint32(0)
+    libam().am_score_geometry(C.byref(t), C.byref(b))
+    return int(t.value), int(b.value)
+
+
+def _weight_columns(columns, n_needles):
+    """np.int64[n_cols, n_needles], C-contiguous, of one column or a list of columns."""
+    w = np.asarray(columns, dtype=np.int64)
+    if w.ndim == 1:
+        w = w.reshape(1, -1)
+    if w.ndim != 2 or w.shape[1] != n_needles:
+        raise AmError(AM_ERR_INVALID, "weights: columns of one weight per value handle (%s given, %d handles)" % (w.shape, n_needles))
+    return np.ascontiguousarray(w)
+
+
+def score_host(hay, val, n_hay, n_values, columns):
+    """amh_score: the sequential definition of am_score (host/automaton.hpp scoreByHaystack) over fold steps the caller brings -- (haystack, value) arrays in fold
+    order -- and weight columns.  Runs without a device.  np.int64[n_cols, n_hay]."""
+    hay, val = np.ascontiguousarray(hay, np.uint32), np.ascontiguousarray(val, np.uint32)
+    w = _weight_columns(columns, n_values)
+    out = np.zeros(max(w.shape[0] * n_hay, 1), np.int64)
+    _hcheck(libhost().amh_score(hay.ctypes.data if hay.size else None, val.ctypes.data if val.size else None, hay.size, n_hay, n_values,
+                                w.ctypes.data if w.size else None, w.shape[0], out.ctypes.data))
+    return out[:w.shape[0] * n_hay].reshape(w.shape[0], n_hay)
+
+
+class Weights:
+    """Weight columns over the value handles of a ValuesTable, on the device (am_weights): Weights(table, [[w of handle 0, w of handle 1, ...], ...]), one to
+    SCORE_MAX_COLUMNS columns of int64 (one flat list: one column)."""
+
+    def __init__(self, values_table, columns):
+        self._t = values_table                   # the am_needle_ids must outlive the weights
+        self.columns = _weight_columns(columns, values_table.n_needles)
+        h = _vp()
+        check(libam().am_weights_create(values_table.handle, self.columns.ctypes.data if self.columns.size else None, self.columns.shape[0], C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            libam().am_weights_destroy(self._h)
+            self._h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def n_cols(self):
+        return int(self.columns.shape[0])
+
+    def score_batch(self, case, batch):
+        """am_score_batch on a device-resident batch (an am_batch* handle): the Scores of its haystacks."""
+        return _scores(lambda out: libam().am_score_batch(self._h, case, batch, out))
+
+    def score_texts(self, case, texts):
+        """am_score: the one-shot form on host texts."""
+        s = _Slices(texts)
+        return _scores(lambda out: libam().am_score(self._h, case, s.arr, s.n, out))
+
+    def score_matches(self, matches, n_hay):
+        """am_matches_score: the same fold over an am_matches* result whose records are in HBM."""
+        return _scores(lambda out: libam().am_matches_score(matches, self._h, n_hay, out))
+
+
+class Scores:
+    """What a scoring call left in HBM (am_scores): int64[n_cols, n_hay], copied to the host on first use."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            libam().am_scores_free(self._h)
+            self._h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def n_hay(self):
+        return int(libam().am_scores_haystacks(self._h))
+
+    @property
+    def n_cols(self):
+        return int(libam().am_scores_columns(self._h))
+
+    @property
+    def scores(self):
+        """np.int64[n_cols, n_hay]: scores[c, i] = the sum of column c's weights over the fold steps of haystack i, modulo 2^64."""
+        p = libam().am_scores_data(self._h)
+        if not p:
+            check(AM_ERR_HIP)
+        n = self.n_cols * self.n_hay
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int64)), shape=(max(n, 1),))[:n].copy().reshape(self.n_cols, self.n_hay)
+
+    def top_k(self, k, column=0, largest=True):
+        """am_scores_top_k: the min(k, n_hay) best haystacks of a column as SCORED_DTYPE[...] in order -- (score descending, haystack ascending), or with
+        largest=False (score ascending, haystack ascending).  The cut is found on the device; the winners cross."""
+        out = np.zeros(max(min(int(k), self.n_hay), 1), SCORED_DTYPE)
+        n = C.c_uint64(0)
+        check(libam().am_scores_top_k(self._h, int(column), int(k), int(bool(largest)), out.ctypes.data, C.byref(n)))
+        return out[:int(n.value)]
+
+    def select_top_k(self, k, column=0, largest=True, batch=None):
+        """am_select_top_k: the same haystacks as a Selection of `batch` (the am_batch* the scores were made from), ascending indices."""
+        return _select(lambda out: libam().am_select_top_k(self._h, int(column), int(k), int(bool(largest)), batch, out))
+
+    def select(self, lo, hi, column=0, invert=False, batch=None):
+        """am_select_score: the Selection of the haystacks of `batch` with lo <= score <= hi (lo > hi: none); invert: the others."""
+        return _select(lambda out: libam().am_select_score(self._h, int(column), int(lo), int(hi), int(bool(invert)), batch, out))
+
+
+def _scores(call):
+    h = _vp()
+    check(call(C.byref(h)))
+    return Scores(h)
 
 
 class Not:

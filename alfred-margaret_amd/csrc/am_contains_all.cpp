@@ -169,11 +169,6 @@ int hist_launch(const am_needle_ids* ids, const Record* recs, uint64_t n_rec, ui
     return AM_OK;
 }
 
-// what is done with the sorted records of a scan while they are in HBM: records [0, n_rec) belong to haystacks [h0, h0 + n_hay) of the batch the caller handed to
-// fold_batch, their haystack fields count from h0.  `scanned` is the batch the records index: the caller's, or the group's sub-batch with a text and offsets of its
-// own -- a fold that reads text (the whole-word counts) reads that one.  Returns when the device has finished with the records.
-using RecordFold = std::function<int(const Record* recs, uint64_t n_rec, uint32_t h0, uint32_t n_hay, const am_batch* scanned, int dev, hipStream_t st)>;
-
 // one scan of `b` (haystacks h0 ... of the caller's batch), its records handed to `fold`; returns when the fold has finished (the record array is free again)
 int fold_scan(const am_needle_ids* ids, int case_mode, am_batch* b, RecordArray& ra, uint32_t h0, const RecordFold& fold)
 {
@@ -187,9 +182,11 @@ int fold_scan(const am_needle_ids* ids, int case_mode, am_batch* b, RecordArray&
     return AM_OK;
 }
 
-// a device-resident batch scanned and folded in bounded record memory: in one piece, or in groups of whole consecutive haystacks (am_count_by_needle* and
-// am_count_matrix* share this loop)
-int fold_batch(const am_needle_ids* ids, int case_mode, am_batch* b, const RecordFold& fold)
+}  // namespace
+
+// a device-resident batch scanned and folded in bounded record memory (am_host.h): in one piece, or in groups of whole consecutive haystacks (am_count_by_needle*,
+// am_count_matrix*, the slot rows, the whole-word flags and am_score* share this loop)
+int am::host::fold_batch(const am_needle_ids* ids, int case_mode, am_batch* b, const RecordFold& fold)
 {
     if (b->n_hay == 0 || b->total == 0) return AM_OK;
     ON_DEVICE(b->dev);                                     // (segments are folded on threads of their own)
@@ -222,6 +219,8 @@ int fold_batch(const am_needle_ids* ids, int case_mode, am_batch* b, const Recor
     }
     return AM_OK;
 }
+
+namespace {
 
 // the counts of a device-resident batch into d_counts (accumulating)
 int hist_batch(const am_needle_ids* ids, int case_mode, am_batch* b, uint64_t* d_counts, uint64_t* d_trace)

@@ -279,6 +279,24 @@ hipError_t launch_rules_eval(const RulesEvalIn& in, int n_cu, hipStream_t st);
 hipError_t launch_rule_flags(const uint64_t* fired_row, const uint32_t* labels, uint32_t rule, uint64_t n_hay, uint64_t hay_words, uint8_t* flags, hipStream_t st);
 // am_rules_geometry: haystacks per workgroup step of k_rules_eval, the widest slot row (32-bit words) it stages in LDS, the rules whose counts it keeps in LDS
 void rules_geometry(uint32_t* tile_haystacks, uint32_t* lds_slot_words, uint32_t* lds_rules);
+// scores (am_score.hip; score_key / topk_pick, the select's state and k_score's output struct: am_score.h).  k_score: score[c][h] += the weights of column c of the
+// values id < in.n_needles of in.recs, per haystack h of the records -- a segmented sum over the sorted records, at most one 64-bit add per column and run of equal
+// haystacks a wavefront holds; out.scores is accumulating (cleared by the caller) and out.stride >= in.n_hay.  in.words given: only the values whose span the class
+// keeps (ic decides the starts), otherwise the lengths, the text and the offsets of `in` are not looked at.  A persistent grid sized from n_cu.
+struct ScoreOut;
+struct TopkState;
+struct alignas(8) Scored { int64_t score; uint32_t haystack; uint32_t reserved; };      // = am_scored in include/am.h
+hipError_t launch_score(bool ic, const SpansIn& in, const ScoreOut& out, int n_cu, hipStream_t st);
+// the workspace of a top-k selection over n keys: the select's state, 256 words of histogram, tie / tie_rank of n + 1 entries each, and the exclusive sum's temporary
+struct TopkWork { TopkState* state; uint64_t* hist; uint32_t* tie; uint64_t* tie_rank; void* scan_tmp; size_t scan_tmp_bytes; };
+// the min(k, n) best scores of col[0, n) -- largest: (score descending, index ascending), else (score ascending, index ascending) -- for 1 <= k <= n: flags[i] (n
+// bytes, nullable) and keep[i] (n + 1 words, the last one 0, nullable) = 1 for the winners.  Eight histogram passes and their picks, all on the device
+hipError_t launch_topk_flags(const int64_t* col, uint64_t n, uint64_t k, bool largest, const TopkWork& w, uint8_t* flags, uint32_t* keep, hipStream_t st);
+hipError_t launch_score_range(const int64_t* col, uint64_t n, int64_t lo, int64_t hi, uint8_t* flags, hipStream_t st);      // flags[i] = lo <= col[i] <= hi
+// with pos = the exclusive sum of keep (n + 1): out[pos[i]] = {col[i], i} for every kept i; n_out = pos[n]
+hipError_t launch_topk_gather(const int64_t* col, uint64_t n, const uint32_t* keep, const uint64_t* pos, Scored* out, uint64_t n_out, hipStream_t st);
+// am_score_geometry: records per workgroup step of k_score (a wavefront owns a quarter of them, consecutive), keys per workgroup of the top-k histogram
+void score_geometry(uint32_t* tile_records, uint32_t* topk_block_items);
 // incremental re-scan between Replacer passes (am_replace.hip)
 struct RpWin { uint64_t src_abs; uint64_t ws; uint32_t len; uint32_t own_lo; };   // window: bytes src_abs.. of the next text; ws = its start inside the haystack; records with end > own_lo are its own
 hipError_t launch_rp_win_count(const RpHay* hs, uint32_t n_act, uint32_t* nwin, hipStream_t st);

@@ -1,6 +1,6 @@
 // am_host.h -- what the host-side translation units of libam share (am_abi.cpp: runtime and thread state, automata, batches, one-shot entry points, results;
 // am_run.cpp: routes and scans; am_replacer.cpp: the Replacer; am_contains_all.cpp: containsAll, the fold checksum, the per-needle counts and the needle matrix;
-// am_splitter.cpp: the Splitter; am_spans.cpp: match spans; am_subst.cpp: substitute; am_select.cpp: select; am_rules.cpp: rule sets -- substitute and select through
+// am_splitter.cpp: the Splitter; am_spans.cpp: match spans; am_subst.cpp: substitute; am_select.cpp: select; am_rules.cpp: rule sets; am_score.cpp: scores -- substitute, select and scores through
 // am_spans.h, which adds the span table and the spans result): error handling, the per-device runtime, device buffers, the handle structs of include/am.h and the few scan entry points the Replacer
 // drives.  am_fold.h, included at the end, holds the scaffolding of the device stages: argument checks, the CSR result handle, the chain finisher, the one-shot
 // wrapper, the segment loop and the builder of derived batches.  Internal: nothing here is part of the C ABI.
@@ -203,6 +203,26 @@ struct am_rule_hits {
     bool fired_fetched = false, labels_fetched = false, counts_fetched = false;
 };
 
+// the weight columns of a scoring call in HBM beside the values table they are indexed by (am_score.cpp).  (Holds a DevBuf: on the heap only.)
+struct am_weights {
+    const am_needle_ids* ids = nullptr;                     // must outlive the weights
+    int dev = 0;
+    uint32_t n_cols = 0, n_needles = 0;
+    am::host::DevBuf w;                                     // int64[n_cols][n_needles]
+};
+
+// what am_score* leaves in HBM (am_score.cpp; am_select_top_k / am_select_score, am_select.cpp, read it): int64[n_cols][n_hay], column after column; the host copy is
+// made once, on first use.  Remembers the batch it was made from as am_selection does.  (Holds a DevBuf: on the heap only.)
+struct am_scores {
+    int dev = 0;
+    uint64_t n_hay = 0, src_total = 0;
+    bool src_total_known = true;                            // false: made from a held result (am_matches_score), which does not know the bytes of its batch
+    uint32_t n_cols = 0;
+    am::host::DevBuf scores;
+    std::vector<int64_t> h_scores; bool fetched = false;
+    const int64_t* column(uint32_t c) const { return (const int64_t*)scores.p + (uint64_t)c * n_hay; }
+};
+
 namespace am {
 namespace host {
 
@@ -262,6 +282,18 @@ int scan_needle_ids(const am_automaton* a, int case_mode, am_batch* b, const uin
 // words that this call clears, d_missing: n_hay words of scratch.  The ids-mode scan where scan_needle_ids takes the call (no record is written), k_idset over the
 // records elsewhere, in bounded record memory (fold_batch).  The work is enqueued on the calling thread's stream; what the scans read back they have read back.
 int slot_rows(const am_needle_ids* ids, int case_mode, am_batch* b, uint32_t* d_bits, uint32_t words, uint32_t* d_missing);
+// What is done with the sorted records of a scan while they are in HBM: records [0, n_rec) belong to haystacks [h0, h0 + n_hay) of the batch the caller handed to
+// fold_batch, their haystack fields count from h0.  `scanned` is the batch the records index: the caller's, or the group's sub-batch with a text and offsets of its
+// own -- a fold that reads text (the whole-word counts and scores) reads that one.  Returns when the device has finished with the records.
+using RecordFold = std::function<int(const Record* recs, uint64_t n_rec, uint32_t h0, uint32_t n_hay, const am_batch* scanned, int dev, hipStream_t st)>;
+// A device-resident batch scanned and folded in bounded record memory (am_contains_all.cpp): in one piece, or -- where the records would exceed the budget (1 GiB;
+// AM_HIST_RECORDS_MIB) -- counted first and then scanned in groups of whole consecutive haystacks, each group folded before the next is scanned.  `fold` is not called
+// for a scan without records.
+int fold_batch(const am_needle_ids* ids, int case_mode, am_batch* b, const RecordFold& fold);
+// The top-k flags of one column of a scores result (am_score.cpp; am_select_top_k and am_scores_top_k share it), 1 <= k < x->n_hay: d_flags (n_hay bytes, nullable) and
+// d_keep (n_hay + 1 words, nullable) as launch_topk_flags writes them, enqueued on st.  The workspace lives in `work`, which the caller keeps until st has finished.
+struct TopkBuffers { DevBuf state, tie, tie_rank, scan_tmp; };
+int topk_flags(const am_scores* x, uint32_t column, uint64_t k, int largest, TopkBuffers& work, uint8_t* d_flags, uint32_t* d_keep, hipStream_t st);
 // sorted records of a batch: sink_final(n, &ptr) names the destination once the count is known
 int run_records(const am_automaton* a, int case_mode, am_batch* b, const std::function<int(uint64_t, Record**)>& sink_final, uint64_t* n_out, bool have_lock = false);
 // the same without a host round trip (suffix-filter route, worst-case pool): the count stays on the device

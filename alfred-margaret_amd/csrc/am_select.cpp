@@ -1,7 +1,8 @@
 // am_select.cpp -- select on the device (include/am.h "select"): keep the haystacks of a batch that a predicate holds for, drop the rest, and hand the kept ones on
 // as a batch of their own -- `grep -F -f needles`, `grep -v`, `grep -w` and "the lines that mention all of these terms" between two stages of a pipeline in HBM.
 // The predicates are the library's own: the flags of the containsAny / containsAll scans, taken where the scans leave them (FlagSink, am_host.h), and the non-empty
-// rows of AM_SPANS_ALL (spans_flags, am_contains_all.cpp), and one rule of a rule-set result (am_select_rule over am_rules.cpp's am_rule_hits).  The compaction by
+// rows of AM_SPANS_ALL (spans_flags, am_contains_all.cpp), one rule of a rule-set result (am_select_rule over am_rules.cpp's am_rule_hits), and the best k or a range
+// of one column of a scores result (am_select_top_k / am_select_score over am_score.cpp's am_scores; the flags are am_score.hip's).  The compaction by
 // runs is am_select.hip's; the bytes move with am_split.hip's gather.  What crosses to the host during a *_batch select: the kept count, the run count and the kept
 // bytes (one copy of three words), and whatever the scans read back themselves.
 // Every argument is checked before any device work.
@@ -183,6 +184,54 @@ extern "C" int am_select_rule(const am_rule_hits* x, uint32_t rule, int which, i
         }));
     *out = s.release();
     return AM_OK;
+}
+
+// the two selects over one column of a scores result (am_score.cpp): the checks both make, the selection, and -- where there is a haystack -- fill(s).  src must be
+// the batch the scores were made from: the scores remember haystack count, total bytes and device, as a selection does.
+template <class Fill>
+static int select_scores(const am_scores* x, uint32_t column, const am_batch* src, am_selection** out, Fill&& fill)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    if (!x || !src) return fail(AM_ERR_INVALID, "null scores or batch");
+    if (column >= x->n_cols) return fail(AM_ERR_INVALID, "column is not below the number of columns");
+    if (x->n_hay != src->n_hay || (x->src_total_known && x->src_total != src->total) || x->dev != src->dev)
+        return fail(AM_ERR_INVALID, "the scores were not made from a batch with this haystack count and size");
+    AM_TRY(ensure_runtime());
+    SelectionPtr s = new_selection(src);
+    if (src->n_hay != 0) AM_TRY(fill(s.get()));
+    *out = s.release();
+    return AM_OK;
+}
+
+// every flag of the selection is `v`
+static int compact_constant(const am_batch* b, uint8_t v, am_selection* s)
+{
+    ON_DEVICE(b->dev);
+    hipStream_t st; AM_TRY(get_stream(b->dev, &st));
+    return compact(b, nullptr, v, 0, st, s);
+}
+
+// the min(k, n_hay) best haystacks of a column: the radix select's flags (topk_flags, am_score.cpp: key > T, or key == T and among the first q ties), compacted
+extern "C" int am_select_top_k(const am_scores* x, uint32_t column, uint64_t k, int largest, const am_batch* src, am_selection** out)
+{
+    return select_scores(x, column, src, out, [&](am_selection* s) -> int {
+        if (k == 0 || k >= x->n_hay) return compact_constant(src, k == 0 ? 0 : 1, s);      // nothing, or everything: no key is looked at
+        TopkBuffers work;                                   // (lives until the compaction has waited for the stream)
+        return compact_written(src, 0, s, [&](uint8_t* d_flags, hipStream_t st) { return topk_flags(x, column, k, largest, work, d_flags, nullptr, st); });
+    });
+}
+
+// lo <= score <= hi (lo > hi keeps nothing), or -- invert -- the others
+extern "C" int am_select_score(const am_scores* x, uint32_t column, int64_t lo, int64_t hi, int invert, const am_batch* src, am_selection** out)
+{
+    return select_scores(x, column, src, out, [&](am_selection* s) -> int {
+        return compact_written(src, invert, s, [&](uint8_t* d_flags, hipStream_t st) -> int {
+            Prof pr("score_range", st);
+            HIP_TRY(launch_score_range(x->column(column), x->n_hay, lo, hi, d_flags, st));
+            return AM_OK;
+        });
+    });
 }
 
 extern "C" int am_select_any(const am_automaton* a, int case_mode, int invert, const am_slice* hay, size_t n_hay, am_selection** out)

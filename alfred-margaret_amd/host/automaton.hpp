@@ -10,6 +10,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -295,7 +296,25 @@ std::vector<uint64_t> countByNeedle(CaseSensitivity cs, const AcMachine<V>& mach
     return out;
 }
 
-// The term-document matrix: the same fold per text.  rows[i] = Map.toAscList of  runWithCase cs Map.empty (\m (Match _ v) -> Step (Map.insertWith (+) v 1 m))
+// Scores: the fold  runWithCase cs 0 (\acc (Match _ v) -> Step (acc + weight v))  (Automaton.hs:442-553) per haystack and weight column -- the sequential definition
+// of am_score (include/am.h "scores").  steps: the (haystack, value) pairs of the fold in fold order (amh_run_list's); weights: int64[nCols][nValues], column after
+// column; out[c * nHay + h], summed modulo 2^64 as the reference's Int does.  Values >= nValues are skipped.  Touches no device.
+inline std::vector<int64_t> scoreByHaystack(const uint32_t* stepHaystack, const uint32_t* stepValue, uint64_t nSteps, size_t nHay, size_t nValues, const int64_t* weights,
+                                            size_t nCols)
+{
+    if (nCols == 0 || nCols > AM_SCORE_MAX_COLUMNS) throw AmError(AM_ERR_INVALID, "scoreByHaystack: n_cols must be 1 .. AM_SCORE_MAX_COLUMNS");
+    std::vector<uint64_t> acc(nCols * nHay, 0);             // (unsigned: the wrap is defined)
+    for (uint64_t i = 0; i < nSteps; i++) {
+        if (stepHaystack[i] >= nHay) throw AmError(AM_ERR_INVALID, "scoreByHaystack: a fold step beyond the haystacks");
+        if (stepValue[i] >= nValues) continue;
+        for (size_t c = 0; c < nCols; c++) acc[c * nHay + stepHaystack[i]] += (uint64_t)weights[c * nValues + stepValue[i]];
+    }
+    std::vector<int64_t> out(acc.size());
+    if (!acc.empty()) std::memcpy(out.data(), acc.data(), acc.size() * 8);
+    return out;
+}
+
+// The term-document matrix: the same fold per text. rows[i] = Map.toAscList of  runWithCase cs Map.empty (\m (Match _ v) -> Step (Map.insertWith (+) v 1 m))
 // (Automaton.hs:442-553) over texts[i], values >= nValues (by default: none) skipped: (value, count) pairs in ascending value order, in CSR form.  Built on the device
 // (am_count_matrix): what travels to the host is the matrix.
 struct NeedleMatrix {

@@ -188,6 +188,18 @@ int amh_rules_fold(const uint32_t* hay_in, const uint32_t* val_in, uint64_t n, s
     });
 }
 
+// ---- scores (automaton.hpp scoreByHaystack) over fold steps the caller brings (n (haystack, value) pairs in fold order): no device is touched.  weights: n_cols x
+// n_values, scores_out: n_cols x n_hay, both column after column, the caller's
+int amh_score(const uint32_t* hay_in, const uint32_t* val_in, uint64_t n, size_t n_hay, size_t n_values, const int64_t* weights, uint32_t n_cols, int64_t* scores_out)
+{
+    return guarded([&] {
+        if (n && (!hay_in || !val_in)) throw AmError(AM_ERR_INVALID, "amh_score: null fold steps");
+        if (n_values && !weights) throw AmError(AM_ERR_INVALID, "amh_score: null weights");
+        const std::vector<int64_t> r = scoreByHaystack(hay_in, val_in, n, n_hay, n_values, weights, n_cols);
+        if (!r.empty()) std::memcpy(scores_out, r.data(), r.size() * 8);
+    });
+}
+
 // ---- extract (spans.hpp): extractFold over spans the caller brings (CSR: span_offs has n_hay + 1 entries, spans_in span_offs[n_hay] rows of am_span): no device is
 // touched.  offsets (n_hay + 1) and the fragments as the C ABI lays them out (am_fragment, 16 bytes each); free both with amh_free_u64
 int amh_extract_fold(const uint64_t* span_offs, const am_span* spans_in, const am_slice* hay, size_t n_hay, uint32_t before, uint32_t after, int merged,

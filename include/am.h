@@ -511,6 +511,65 @@ AM_API void am_rule_hits_free(am_rule_hits* x);
 AM_API int am_select_rule(const am_rule_hits* x, uint32_t rule, int which, int invert, const am_batch* src, am_selection** out);
 AM_API void am_rules_geometry(uint32_t* tile_haystacks, uint32_t* lds_slot_words, uint32_t* lds_rules);
 
+/* ---- scores: a number per match, added up per haystack, in HBM; top-k and range select over the result ---------------
+ * The most common fold after counting:  runText 0 (\acc (Match _ v) -> Step (acc + weight v))  -- sentiment and spam lexicons, keyword relevance, "rank these product
+ * titles against this weighted dictionary" -- for every haystack of a batch and up to AM_SCORE_MAX_COLUMNS weight columns from ONE scan.
+ * WEIGHTS.  int64 W[n_cols][n_needles], column after column, over the value handles of an am_needle_ids; 1 <= n_cols <= AM_SCORE_MAX_COLUMNS.  The array is copied:
+ * the caller's may go after am_weights_create; `ids` (and its automaton) must outlive the weights.
+ * SCORE.  For haystack i and column c, score[c][i] = the sum of W[c][v] over every fold step `Match _ v` that runWithCase (Automaton.hs:442-553) makes on haystack i
+ * with v < n_needles, i.e. over the haystack's records r and the k in [values_offsets[r.state], values_offsets[r.state + 1]) with values[k] < n_needles.  The sum is
+ * taken MODULO 2^64 -- two's complement, what the reference's Int does.  Everything am_count_by_needle says about handles holds per haystack: overlapping occurrences
+ * count, handles >= n_needles are SKIPPED, a needle given twice with two handles adds under both, two needles under one handle both add its weight, a state reached
+ * through suffix outputs adds every value of its list, the empty needle adds once per position.  Three identities follow, all modulo 2^64:
+ *   score[c][i] = sum over v of matrix[i][v] * W[c][v]                      (am_count_matrix's row i)
+ *   a column of ones, with every handle < n_needles, is am_count_batch's counts_out
+ *   sum over i of score[c][i] = sum over v of count_by_needle[v] * W[c][v]   (am_count_by_needle_batch's vector)
+ * WHOLE WORDS.  am_score_spans_batch over a span table with a word class adds only those (record, value) pairs whose span the class keeps -- exactly the rows
+ * am_count_spans_by_needle* counts; a table without a class is the plain form.
+ * RESULT (am_scores): int64[n_cols][n_hay] in HBM, COLUMN-MAJOR as the weights are, so that a column is contiguous; the host copy is made on first use and owned by
+ * the result (never NULL on success: a placeholder element for an empty result).  Integer adds commute: the scores are bit-identical from run to run and whether or
+ * not the batch went through in groups or segments.  n_needles == 0 gives all-zero scores; n_hay == 0 gives an empty result.
+ *   am_score_batch        a device-resident batch, on whatever route the automaton takes.  The records are produced and summed in HBM (csrc/am_score.hip: a segmented
+ *                         sum over the sorted records, no atomic per value or record) and never cross the wire.  Record memory is bounded exactly as in
+ *                         am_count_by_needle_batch: the same 1 GiB, the same groups of whole consecutive haystacks.
+ *   am_score              the one-shot form on host slices; a batch of 1 GiB and more goes up in segments of whole haystacks, as in am_count_by_needle.
+ *   am_score_spans_batch  the whole-word form; t and w must have been made over the same am_needle_ids.
+ *   am_matches_score      the same fold over a result the caller holds (am_run_batch, am_run), for haystacks 0 .. n_hay - 1.  AM_ERR_UNSUPPORTED when the result was
+ *                         assembled on the host (no records in HBM), AM_ERR_INVALID when n_hay is not greater than the largest haystack index in the result.  Such
+ *                         scores do not know the bytes of their batch: the selects below hold them to the haystack count and the device only.
+ * TOP-K of a column.  Largest: order the haystacks by (score descending, haystack ascending) and take the first min(k, n_hay); smallest: by (score ascending, haystack
+ * ascending).  Ties at the cut go to the lower haystack index; k == 0 gives nothing.  The cut is found on the device (eight passes of an 8-bit radix select over
+ * order-preserving keys); nothing of size n_hay crosses to the host.
+ *   am_scores_top_k       the winners as {score, haystack} in that order, in host memory: out has room for min(k, n_hay) entries, *n_out = how many were written.
+ *   am_select_top_k       the winners as a selection of `src` -- ascending haystack indices, as every selection -- so that am_batch_from_selection makes them a batch.
+ *   am_select_score       the haystacks with lo <= score <= hi (lo > hi keeps nothing), or -- invert -- the others.
+ * For both selects src must be the batch the scores were made from: AM_ERR_INVALID when the haystack count, the total bytes or the device differ.  Selections compose
+ * with am_batch_from_selection and with each other.
+ *   am_score_geometry     for tests, known without a device: the records one workgroup step of the fold handles (a wavefront owns a quarter of them, consecutive, 64
+ *                         at a time), and the keys one workgroup of the top-k histogram handles.
+ * Arguments are checked before any device work: AM_ERR_INVALID for null handles or null outputs, n_cols of 0 or above the maximum, column >= n_cols, a case_mode that
+ * is neither of the two, a span table whose ids is not the weights' ids, handles on different devices, slices without memory, n_hay >= 0xFFFFFFFF.  *out is NULL
+ * after every failure. */
+#define AM_SCORE_MAX_COLUMNS 8
+typedef struct am_weights am_weights;
+typedef struct am_scores am_scores;
+typedef struct am_scored { int64_t score; uint32_t haystack; uint32_t reserved; } am_scored;   /* 16 bytes: offsets 0, 8, 12 */
+AM_API int am_weights_create(const am_needle_ids* ids, const int64_t* weights /* n_cols * n_needles, host */, uint32_t n_cols, am_weights** out);
+AM_API void am_weights_destroy(am_weights* w);
+AM_API int am_score_batch(const am_weights* w, int case_mode, const am_batch* b, am_scores** out);
+AM_API int am_score(const am_weights* w, int case_mode, const am_slice* hay, size_t n_hay, am_scores** out);
+AM_API int am_score_spans_batch(const am_span_table* t, const am_weights* w, int case_mode, const am_batch* b, am_scores** out);
+AM_API int am_matches_score(const am_matches* m, const am_weights* w, size_t n_hay, am_scores** out);
+AM_API uint64_t am_scores_haystacks(const am_scores* x);
+AM_API uint64_t am_scores_columns(const am_scores* x);
+AM_API const int64_t* am_scores_data(am_scores* x);            /* host copy on first use: [n_cols][n_hay] */
+AM_API const void* am_scores_device_data(const am_scores* x);  /* the same in HBM */
+AM_API void am_scores_free(am_scores* x);
+AM_API int am_scores_top_k(am_scores* x, uint32_t column, uint64_t k, int largest, am_scored* out /* min(k, n_hay), host */, uint64_t* n_out);
+AM_API int am_select_top_k(const am_scores* x, uint32_t column, uint64_t k, int largest, const am_batch* src, am_selection** out);
+AM_API int am_select_score(const am_scores* x, uint32_t column, int64_t lo, int64_t hi, int invert, const am_batch* src, am_selection** out);
+AM_API void am_score_geometry(uint32_t* tile_records, uint32_t* topk_block_items);
+
 /* ---- extract: the matched text with some characters around it, in HBM; the snippets are a batch of their own ---------------
  * `grep -o`, `grep -o -E '.{0,40}needle.{0,40}'`, a keyword-in-context concordance, the snippets of a search front end, the windows an entity-extraction pipeline gives
  * to its next model -- over a batch, without the spans (24 bytes each) or the snippets crossing the wire.
