@@ -99,7 +99,7 @@ int am::host::contains_all_flags(const am_needle_ids* ids, int case_mode, am_bat
         const uint64_t r0 = first.empty() ? 0 : first[h0], r1 = first.empty() ? n_rec : first[h1];
         HIP_TRY(hipMemsetAsync(bits.p, 0, (uint64_t)(h1 - h0) * words * 4, st));
         { Prof pr("idset", st);
-          HIP_TRY(launch_idset((const Record*)records.p, r0, r1, (const uint64_t*)ids->vals_off.p, (const uint32_t*)ids->vals.p, ids->n_needles, h0, words, (uint32_t*)bits.p, st));
+          HIP_TRY(launch_idset(records_in(ids, (const Record*)records.p + r0, r1 - r0, h1 - h0), h0, words, (uint32_t*)bits.p, st));
           HIP_TRY(launch_idset_all((const uint32_t*)bits.p, words, ids->n_needles, h1 - h0, (uint8_t*)flags.p + h0, st)); }
     }
     return sink.device((const uint8_t*)flags.p, st);       // (returns when the copy or the compaction has finished: the workspaces are freed)
@@ -129,8 +129,7 @@ extern "C" int am_matches_fold_hash(const am_matches* m, const am_needle_ids* id
     const Record* recs = m->n ? m->d_records + m->first : (const Record*)dummy.p;
     HIP_TRY(launch_rp_ranges(recs, m->n, (uint64_t*)rec_first.p, kNoRoute, (uint32_t)n_hay, st));
     { Prof pr("fold_hash", st);
-      HIP_TRY(launch_fold_hash(recs, (const uint64_t*)rec_first.p, (const uint64_t*)ids->vals_off.p, (const uint32_t*)ids->vals.p, (uint32_t)n_hay,
-                               (uint64_t*)out.p, (uint64_t*)out.p + n_hay, st)); }
+      HIP_TRY(launch_fold_hash(records_in(ids, recs, m->n, (uint32_t)n_hay), (const uint64_t*)rec_first.p, (uint64_t*)out.p, (uint64_t*)out.p + n_hay, st)); }
     HIP_TRY(hipMemcpyAsync(hash_out, out.p, n_hay * 8, hipMemcpyDeviceToHost, st));
     if (count_out) HIP_TRY(hipMemcpyAsync(count_out, (uint64_t*)out.p + n_hay, n_hay * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -160,12 +159,12 @@ constexpr uint64_t kHistRecordBudget = 1ull << 30;       // bytes of records in 
 uint64_t hist_budget() { const long v = cfg::get(cfg::kHistRecordsMiB); return v > 0 ? (uint64_t)v << 20 : kHistRecordBudget; }
 
 std::atomic<uint64_t> g_hist_trace[3];                   // AM_HIST_TRACE: sums of the launches' trace words (am_debug_hist_adds)
+uint32_t hist_flush_tiles() { const long v = cfg::get(cfg::kHistFlushTiles); return v > 0 ? (uint32_t)std::min<long>(v, 1L << 30) : 0u; }      // (0: the kernels' own interval)
 
-int hist_launch(const am_needle_ids* ids, const Record* recs, uint64_t n_rec, uint64_t* d_counts, uint64_t* d_trace, int dev, hipStream_t st)
+int needle_hist(const RecordsIn& in, uint64_t* d_counts, uint64_t* d_trace, int dev, hipStream_t st)
 {
     Prof pr("needle_hist", st);
-    HIP_TRY(launch_needle_hist(recs, n_rec, (const uint64_t*)ids->vals_off.p, (const uint32_t*)ids->vals.p, ids->n_needles, ids->n_states, ids->n_values,
-                               d_counts, d_trace, cfg::get(cfg::kHistFlushTiles) > 0 ? (uint32_t)std::min<long>(cfg::get(cfg::kHistFlushTiles), 1L << 30) : 0u, g_rt.dev[dev].n_cu, st));
+    HIP_TRY(launch_needle_hist(in, d_counts, d_trace, hist_flush_tiles(), g_rt.dev[dev].n_cu, st));
     return AM_OK;
 }
 
@@ -225,8 +224,8 @@ namespace {
 // the counts of a device-resident batch into d_counts (accumulating)
 int hist_batch(const am_needle_ids* ids, int case_mode, am_batch* b, uint64_t* d_counts, uint64_t* d_trace)
 {
-    return fold_batch(ids, case_mode, b, [&](const Record* recs, uint64_t n_rec, uint32_t, uint32_t, const am_batch*, int dev, hipStream_t st) {
-        return hist_launch(ids, recs, n_rec, d_counts, d_trace, dev, st);
+    return fold_batch(ids, case_mode, b, [&](const Record* recs, uint64_t n_rec, uint32_t, uint32_t n_hay, const am_batch*, int dev, hipStream_t st) {
+        return needle_hist(records_in(ids, recs, n_rec, n_hay), d_counts, d_trace, dev, st);
     });
 }
 
@@ -236,8 +235,7 @@ int hist_words_batch(const am_span_table* t, int case_mode, am_batch* b, uint64_
 {
     return fold_batch(t->ids, case_mode, b, [&](const Record* recs, uint64_t n_rec, uint32_t, uint32_t n_hay, const am_batch* scanned, int dev, hipStream_t st) {
         Prof pr("needle_hist_words", st);
-        HIP_TRY(launch_needle_hist_words(case_mode == AM_IGNORE_CASE, spans_in(t, recs, n_rec, scanned, n_hay), d_counts, d_trace,
-                                         cfg::get(cfg::kHistFlushTiles) > 0 ? (uint32_t)std::min<long>(cfg::get(cfg::kHistFlushTiles), 1L << 30) : 0u, g_rt.dev[dev].n_cu, st));
+        HIP_TRY(launch_needle_hist_words(case_mode == AM_IGNORE_CASE, spans_in(t, recs, n_rec, scanned, n_hay), d_counts, d_trace, hist_flush_tiles(), g_rt.dev[dev].n_cu, st));
         return AM_OK;
     });
 }
@@ -289,9 +287,9 @@ int am::host::slot_rows(const am_needle_ids* ids, int case_mode, am_batch* b, ui
         HIP_TRY(hipMemsetAsync(d_bits, 0, (uint64_t)b->n_hay * words * 4, st));
         HIP_TRY(hipStreamSynchronize(st));                  // (as HistOut::begin: the folds follow on this thread's stream, the scans synchronise in between)
     }
-    return fold_batch(ids, case_mode, b, [&](const Record* recs, uint64_t n_rec, uint32_t h0, uint32_t, const am_batch*, int, hipStream_t st) {
+    return fold_batch(ids, case_mode, b, [&](const Record* recs, uint64_t n_rec, uint32_t h0, uint32_t n_hay, const am_batch*, int, hipStream_t st) {
         Prof pr("idset", st);
-        HIP_TRY(launch_idset(recs, 0, n_rec, (const uint64_t*)ids->vals_off.p, (const uint32_t*)ids->vals.p, ids->n_needles, 0, words, d_bits + (uint64_t)h0 * words, st));
+        HIP_TRY(launch_idset(records_in(ids, recs, n_rec, n_hay), 0, words, d_bits + (uint64_t)h0 * words, st));
         return AM_OK;
     });
 }
@@ -383,7 +381,8 @@ extern "C" int am_matches_count_by_needle(const am_matches* m, const am_needle_i
     hipStream_t st; AM_TRY(get_stream(m->dev, &st));
     HistOut out;
     AM_TRY(out.begin(ids->n_needles, st));
-    AM_TRY(hist_launch(ids, m->d_records + m->first, m->n, out.counts(), out.trace_words(), m->dev, st));
+    // (a held result does not know how many haystacks its batch had: no bound on the haystack fields, which the histogram does not look at)
+    AM_TRY(needle_hist(records_in(ids, m->d_records + m->first, m->n, UINT32_MAX), out.counts(), out.trace_words(), m->dev, st));
     return out.finish(counts_out, st);
 }
 
@@ -430,15 +429,14 @@ struct MatrixBuild {
     {
         if (n_rec == 0 || n == 0 || ids->n_needles == 0) return AM_OK;
         const int n_cu = g_rt.dev[dev].n_cu;
-        const uint64_t* vals_off = (const uint64_t*)ids->vals_off.p;
-        const uint32_t* vals = (const uint32_t*)ids->vals.p;
+        const RecordsIn in = records_in(ids, recs, n_rec, n);
         DevBuf ctr, row_entries, scan_tmp, keys, cnts, tmp, list, bits, pre;
         AM_TRY(ctr.ensure(64));                             // [0] u64: values of the group; words 2, 3: rows for k_mx_rows_lds / k_mx_rows_wide
         AM_TRY(row_entries.ensure(((size_t)n + 1) * 4));
         HIP_TRY(hipMemsetAsync(ctr.p, 0, 64, st));
         HIP_TRY(hipMemsetAsync(row_entries.p, 0, ((size_t)n + 1) * 4, st));
         { Prof pr("mx_values", st);
-          HIP_TRY(launch_mx_values(recs, n_rec, vals_off, ids->n_states, ids->n_values, (uint64_t*)ctr.p, n_cu, st)); }
+          HIP_TRY(launch_mx_values(in, (uint64_t*)ctr.p, n_cu, st)); }
         uint64_t values = 0;
         HIP_TRY(hipMemcpyAsync(&values, ctr.p, 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -451,8 +449,7 @@ struct MatrixBuild {
         HIP_TRY(hipMemsetAsync(keys.p, 0xFF, cap * 8, st));
         HIP_TRY(hipMemsetAsync(cnts.p, 0, cap * 8, st));
         { Prof pr("mx_combine", st);
-          HIP_TRY(launch_mx_combine(recs, n_rec, vals_off, vals, ids->n_needles, ids->n_states, ids->n_values, n, (uint64_t*)keys.p, (uint64_t*)cnts.p, cap,
-                                    (uint32_t*)row_entries.p, n_cu, st)); }
+          HIP_TRY(launch_mx_combine(in, (uint64_t*)keys.p, (uint64_t*)cnts.p, cap, (uint32_t*)row_entries.p, n_cu, st)); }
         std::unique_ptr<Part> part(new Part());
         part->h0 = h0; part->n = n;
         AM_TRY(part->offsets.ensure(((size_t)n + 1) * 8));
@@ -514,12 +511,12 @@ struct MatrixBuild {
         uint64_t h = 0, base = 0;
         for (const auto& p : parts) {
             if (p->h0 < h || (uint64_t)p->h0 + p->n > n_hay) return fail(AM_ERR_HIP, "am_count_matrix: the groups of haystacks are out of order");
-            HIP_TRY(launch_mx_offsets(nullptr, p->h0 - h, base, offs + h, st));
-            HIP_TRY(launch_mx_offsets((const uint64_t*)p->offsets.p, p->n, base, offs + p->h0, st));
+            HIP_TRY(launch_offsets_rebase(nullptr, p->h0 - h, base, offs + h, st));
+            HIP_TRY(launch_offsets_rebase((const uint64_t*)p->offsets.p, p->n, base, offs + p->h0, st));
             HIP_TRY(hipMemcpyAsync((NeedleCount*)x->data.p + base, p->data.p, p->entries * sizeof(NeedleCount), hipMemcpyDeviceToDevice, st));
             base += p->entries; h = (uint64_t)p->h0 + p->n;
         }
-        HIP_TRY(launch_mx_offsets(nullptr, n_hay + 1 - h, base, offs + h, st));
+        HIP_TRY(launch_offsets_rebase(nullptr, n_hay + 1 - h, base, offs + h, st));
         HIP_TRY(hipStreamSynchronize(st));
         x->n_items = total;
         *out = x.release();
@@ -572,13 +569,8 @@ extern "C" int am_matches_count_matrix(const am_matches* m, const am_needle_ids*
     ON_DEVICE(m->dev);
     hipStream_t st; AM_TRY(get_stream(m->dev, &st));
     MatrixBuild mb(ids);
-    if (m->n) {
-        Record last;                                        // the records are sorted by haystack: the last one carries the largest index
-        HIP_TRY(hipMemcpyAsync(&last, m->d_records + m->first + m->n - 1, sizeof(Record), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (last.haystack >= n_hay) return fail(AM_ERR_INVALID, "am_matches_count_matrix: n_hay is not greater than the largest haystack index of the result");
-        AM_TRY(mb.fold(m->d_records + m->first, m->n, 0, (uint32_t)n_hay, m->dev, st));
-    }
+    AM_TRY(matches_below(m, n_hay, "am_matches_count_matrix", st));
+    if (m->n) AM_TRY(mb.fold(m->d_records + m->first, m->n, 0, (uint32_t)n_hay, m->dev, st));
     return mb.finish(m->dev, n_hay, st, out);
 }
 

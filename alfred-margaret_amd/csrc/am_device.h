@@ -1,4 +1,4 @@
-// am_device.h -- interface between the C-ABI layer (am_abi.cpp, am_run.cpp) and the kernels (am_kernels.hip)
+// am_device.h -- interface between the host-side translation units (am_host.h) and the kernels: the launchers of every .hip file and the structs they take
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -94,7 +94,7 @@ hipError_t read_sf_phase_cycles(uint64_t* out5);
 hipError_t read_sf_wave_records(uint64_t* out, size_t n_waves);
 hipError_t scan_temp_bytes(uint64_t n, size_t* bytes);
 hipError_t launch_scan(void* temp, size_t temp_bytes, const uint32_t* counts, uint64_t* offsets, uint64_t n, hipStream_t st);
-
+hipError_t launch_offsets_rebase(const uint64_t* local /* nullable: zeros */, uint64_t n, uint64_t base, uint64_t* out, hipStream_t st);      // out[i] = base + local[i], i < n (am_scan.hip)
 
 // ---- automata with the empty needle: dense pass over the suffix-filter kernel's records (am_dense.hip)
 hipError_t launch_dense(bool ic, bool write, const AcView& a, const BatchView& b, const Record* sparse, const uint64_t* sparse_offsets, uint32_t unit_chunks,
@@ -142,18 +142,23 @@ hipError_t launch_rp_route(const RpHay* hs, const RpRouted& rt, const uint32_t* 
 hipError_t launch_rp_splice(const RpTables& t, const uint8_t* text, const uint64_t* offsets, const uint64_t* rec_first, const RpKept* kept,
                             const RpHay* hs, const RpRouted& rt, uint32_t n_act, uint64_t n_tiles, uint32_t* tile_hay /* n_tiles entries, scratch */,
                             uint8_t* text_next, uint8_t* text_fin, hipStream_t st);
-hipError_t launch_idset(const Record* recs, uint64_t r0, uint64_t r1, const uint64_t* vals_off, const uint32_t* vals, uint32_t n_needles,
-                        uint32_t hay0, uint32_t words, uint32_t* bits, hipStream_t st);
-hipError_t launch_fold_hash(const Record* recs, const uint64_t* rec_first, const uint64_t* vals_off, const uint32_t* vals, uint32_t n_hay,
-                            uint64_t* hash_out, uint64_t* count_out, hipStream_t st);
+// ---- folds over the records of a scan.  What every one of them reads: the sorted records and machineValues in flat form (am_needle_ids; host: records_in, am_host.h);
+// the value list of a record is read through value_range / load_records (am_records.h), by k_mx_values (am_matrix.hip) alone with a loop of its own.
+struct RecordsIn {
+    const Record* recs; uint64_t n_rec;                     // the sorted records
+    const uint64_t* vals_off; const uint32_t* vals; uint64_t n_states, n_values;      // entries of vals_off - 1 / of vals (index checks)
+    uint32_t n_needles, n_hay;                              // handles >= n_needles are skipped by the folds that keep a table; n_hay bounds the records' haystack fields
+};
+// Searcher.containsAll on the records and the fold checksum (am_records.hip).  launch_idset: bit id of row (haystack - hay0) of `bits` (in.n_hay rows of `words` words)
+// for every value id < in.n_needles of in.recs.  launch_fold_hash: per haystack h < in.n_hay the checksum and the count of EVERY value of records [rec_first[h], rec_first[h + 1])
+hipError_t launch_idset(const RecordsIn& in, uint32_t hay0, uint32_t words, uint32_t* bits, hipStream_t st);
+hipError_t launch_fold_hash(const RecordsIn& in, const uint64_t* rec_first, uint64_t* hash_out, uint64_t* count_out, hipStream_t st);
 hipError_t launch_idset_all(const uint32_t* bits, uint32_t words, uint32_t n_needles, uint32_t n_hay, uint8_t* flags, hipStream_t st);
-// per-needle match counts (am_hist.hip): counts[id] += occurrences of id < n_needles in the value lists of records [0, n_rec); a persistent grid sized from n_cu.
-// n_states / n_values: entries of vals_off - 1 / of vals (index checks).  trace (nullable; the instrumented instantiation): [0] adds the workgroups' LDS tables absorbed,
-// [1] adds that went to HBM one by one (slot conflicts), [2] adds of the flushes
-hipError_t launch_needle_hist(const Record* recs, uint64_t n_rec, const uint64_t* vals_off, const uint32_t* vals, uint32_t n_needles, uint64_t n_states,
-                              uint64_t n_values, uint64_t* counts, uint64_t* trace, uint32_t flush_tiles /* 0: the kernel's own interval */, int n_cu, hipStream_t st);
-// the term-document matrix (am_matrix.hip): per-haystack needle counts of a group of n_rows haystacks whose sorted records are recs[0, n_rec), haystack indices relative
-// to the group.  In the order of the calls: *total += lengths of the records' value lists; the (haystack, needle) keys combined into the open-addressing table keys / cnts
+// per-needle match counts (am_hist.hip): counts[id] += occurrences of id < in.n_needles in the value lists of in.recs; a persistent grid sized from n_cu.
+// trace (nullable; the instrumented instantiation): [0] adds the workgroups' LDS tables absorbed, [1] adds that went to HBM one by one (slot conflicts), [2] the flushes' adds
+hipError_t launch_needle_hist(const RecordsIn& in, uint64_t* counts, uint64_t* trace, uint32_t flush_tiles /* 0: the kernel's own interval */, int n_cu, hipStream_t st);
+// the term-document matrix (am_matrix.hip): per-haystack needle counts of a group of n_rows = in.n_hay haystacks whose sorted records are in.recs, haystack indices
+// relative to the group.  In the order of the calls: *total += lengths of the records' value lists; the (haystack, needle) keys combined into the open-addressing table keys / cnts
 // (cap slots, keys all ones and cnts zero before; cap > the group's distinct keys) with row_entries[h] = entries of row h (n_rows + 1, zero before); then, with
 // offsets = exclusive sum of row_entries and n_entries = offsets[n_rows], the live slots into tmp in arrival order (haystack = hay0 + h; row_entries ends at zero again);
 // rows of up to kMxWaveRow entries ordered by needle into `out`, the longer ones listed (list: n_rows words, ctr: two words, zero before) and ordered by launch_mx_rows_lds
@@ -161,9 +166,8 @@ hipError_t launch_needle_hist(const Record* recs, uint64_t n_rec, const uint64_t
 struct alignas(16) NeedleCount { uint64_t count; uint32_t needle; uint32_t haystack; };      // = am_needle_count in include/am.h
 constexpr uint32_t kMxWaveRow = 64, kMxLdsRow = 2048;
 void mx_limits(uint32_t* out4);                             // wavefront row limit, LDS row capacity, slots of a workgroup's LDS table, records between two of its flushes
-hipError_t launch_mx_values(const Record* recs, uint64_t n_rec, const uint64_t* vals_off, uint64_t n_states, uint64_t n_values, uint64_t* total, int n_cu, hipStream_t st);
-hipError_t launch_mx_combine(const Record* recs, uint64_t n_rec, const uint64_t* vals_off, const uint32_t* vals, uint32_t n_needles, uint64_t n_states, uint64_t n_values,
-                             uint32_t n_rows, uint64_t* keys, uint64_t* cnts, uint64_t cap, uint32_t* row_entries, int n_cu, hipStream_t st);
+hipError_t launch_mx_values(const RecordsIn& in, uint64_t* total, int n_cu, hipStream_t st);
+hipError_t launch_mx_combine(const RecordsIn& in, uint64_t* keys, uint64_t* cnts, uint64_t cap, uint32_t* row_entries, int n_cu, hipStream_t st);
 hipError_t launch_mx_scatter(const uint64_t* keys, const uint64_t* cnts, uint64_t cap, const uint64_t* offsets, uint32_t* row_entries, uint32_t n_rows, uint32_t hay0,
                              NeedleCount* tmp, uint64_t n_entries, int n_cu, hipStream_t st);
 hipError_t launch_mx_rows(const NeedleCount* tmp, const uint64_t* offsets, uint32_t n_rows, uint64_t n_entries, NeedleCount* out, uint32_t* list, uint32_t* ctr, hipStream_t st);
@@ -172,7 +176,6 @@ hipError_t launch_mx_rows_lds(const NeedleCount* tmp, const uint64_t* offsets, u
 uint32_t mx_wide_grid(uint32_t n_rows, uint64_t n_entries, uint32_t n_needles, int n_cu);      // 0: no row can be that long
 hipError_t launch_mx_rows_wide(const NeedleCount* tmp, const uint64_t* offsets, uint32_t n_rows, uint64_t n_entries, const uint32_t* list, const uint32_t* ctr,
                                uint32_t n_needles, uint32_t* bits, uint32_t* pre, uint32_t grid, NeedleCount* out, hipStream_t st);
-hipError_t launch_mx_offsets(const uint64_t* local /* nullable: zeros */, uint64_t n, uint64_t base, uint64_t* out, hipStream_t st);      // out[i] = base + local[i], i < n
 // Splitter's fold over the sorted records of a one-needle automaton, and the gather of the fragments into a batch (am_split.hip)
 struct Fragment { uint64_t start, len; };                   // = am_fragment in include/am.h: code units, relative to the haystack
 struct SplitIn { const Record* recs; uint64_t n_rec; const uint8_t* text; const uint64_t* offsets; uint64_t total; uint32_t n_hay, sep_bytes, sep_cps; };
@@ -196,10 +199,8 @@ hipError_t launch_split_gather(const uint8_t* src, uint64_t src_total, const uin
 // match spans (am_spans.hip): every fold step `Match pos v` with v < n_needles as (start, len, haystack, needle), all of them or the leftmost-longest selection
 struct Span { uint64_t start, len; uint32_t haystack, needle; };      // = am_span in include/am.h
 constexpr uint32_t kWordClassWords = 8;                     // a word class: 256 flags, bit b & 31 of word b >> 5
-struct SpansIn {
-    const Record* recs; uint64_t n_rec;                     // the sorted records of the batch
-    const uint64_t* vals_off; const uint32_t* vals; uint64_t n_states, n_values;      // machineValues in flat form (am_needle_ids)
-    const uint32_t* len_bytes; const uint32_t* len_cps; uint32_t n_needles, n_hay;    // the needles' own lengths (am_span_table)
+struct SpansIn : RecordsIn {                                // the sorted records of the batch and machineValues, and what only spans need:
+    const uint32_t* len_bytes; const uint32_t* len_cps;     // the needles' own lengths (am_span_table)
     const uint8_t* text; const uint64_t* offsets; uint64_t total;
     const uint32_t* words;                                  // the table's word class: 256 flags in 8 dwords (am_words.h); null: no class, every span is kept
 };
@@ -245,10 +246,10 @@ hipError_t launch_subst_compact(const uint64_t* src_at, const uint32_t* live, co
                                 uint64_t n_live, const uint64_t* span_off, uint64_t n_span, uint64_t n_hay, uint64_t* out_off, hipStream_t st);
 hipError_t launch_subst_gather(const uint8_t* text, uint64_t src_total, const uint8_t* pool, uint64_t pool_bytes, const uint64_t* cdst, const uint64_t* csrc, uint64_t n_live,
                                uint64_t total, uint8_t* dst, int n_cu, hipStream_t st);
-// select (am_select.hip): the haystacks of a batch that a predicate keeps, compacted by RUNS (maximal sequences of consecutive kept haystacks: contiguous in the source)
-// flags[h] = 1 for every haystack that owns a (record, value < n_needles) pair whose span the table keeps (span_of, am_words.h): row h of AM_SPANS_ALL is not empty.
-// flags: in.n_hay bytes, zero before; in.words null: no class, IC is not looked at
+// a select's predicate over the records (am_records.hip): flags[h] = 1 for every haystack that owns a (record, value < n_needles) pair whose span the table keeps
+// (span_of, am_words.h): row h of AM_SPANS_ALL is not empty.  flags: in.n_hay bytes, zero before; in.words null: no class, IC is not looked at
 hipError_t launch_hay_flags_spans(bool ic, const SpansIn& in, uint8_t* flags, hipStream_t st);
+// select (am_select.hip): the haystacks of a batch that a predicate keeps, compacted by RUNS (maximal sequences of consecutive kept haystacks: contiguous in the source)
 // n + 1 entries each, the last ones 0 (the scans' trailing element): keep[i] = (flags[i] != 0) != (invert != 0) (flags null: every flag is `constant`),
 // run_head[i] = keep[i] && !(i > 0 && keep[i - 1]), klen[i] = keep[i] ? length of haystack i : 0
 hipError_t launch_select_plan(const uint8_t* flags, uint32_t constant, uint32_t invert, const uint64_t* src_offsets, uint64_t n, uint64_t src_total, uint32_t* keep,
@@ -282,7 +283,7 @@ void rules_geometry(uint32_t* tile_haystacks, uint32_t* lds_slot_words, uint32_t
 // scores (am_score.hip; score_key / topk_pick, the select's state and k_score's output struct: am_score.h).  k_score: score[c][h] += the weights of column c of the
 // values id < in.n_needles of in.recs, per haystack h of the records -- a segmented sum over the sorted records, at most one 64-bit add per column and run of equal
 // haystacks a wavefront holds; out.scores is accumulating (cleared by the caller) and out.stride >= in.n_hay.  in.words given: only the values whose span the class
-// keeps (ic decides the starts), otherwise the lengths, the text and the offsets of `in` are not looked at.  A persistent grid sized from n_cu.
+// keeps (ic decides the starts), otherwise only the RecordsIn part of `in` is looked at (and handed to the kernel).  A persistent grid sized from n_cu.
 struct ScoreOut;
 struct TopkState;
 struct alignas(8) Scored { int64_t score; uint32_t haystack; uint32_t reserved; };      // = am_scored in include/am.h
@@ -353,7 +354,7 @@ hipError_t launch_rpp_finish(const RpTables& t, const RpSel* sel, const uint64_t
                              const uint64_t* kdpre, const uint64_t* sidx, const uint64_t* offsets, const uint64_t* rec_first, const int64_t* best,
                              const int64_t* delta_all, const uint32_t* payload_of, uint64_t max_len, RpKept* kept, RpHay* hs, const RpRoute& route, uint32_t n_act,
                              hipStream_t st);
-// several small exclusive sums in one launch: out[i] = sum of in[0..i), for i < n (+ *n_dev when given)
+// several small exclusive sums in one launch (am_scan.hip): out[i] = sum of in[0..i), for i < n (+ *n_dev when given)
 struct ScanJob { const uint32_t* in32; const uint64_t* in64; uint64_t* out; uint64_t n; const uint64_t* n_dev; };
 struct ScanJobs { ScanJob j[6]; uint32_t n_jobs; };
 hipError_t launch_scan_jobs(const ScanJobs& jobs, hipStream_t st);

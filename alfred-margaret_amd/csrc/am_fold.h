@@ -1,5 +1,5 @@
-// am_fold.h -- the host-side scaffolding the device stages share (am_splitter.cpp, am_spans.cpp, am_subst.cpp, am_select.cpp, am_extract.cpp, am_contains_all.cpp and the one-shot
-// entry points of am_abi.cpp): the argument checks of their entry points, the CSR result handle (am_fragments, am_needle_matrix, am_spans), the finisher of long chains
+// am_fold.h -- the host-side scaffolding the device stages share (am_splitter.cpp, am_spans.cpp, am_subst.cpp, am_select.cpp, am_extract.cpp, am_contains_all.cpp, am_score.cpp and the
+// one-shot entry points of am_abi.cpp): the argument checks of their entry points (a held result's among them: matches_in_hbm, matches_below), the CSR result handle (am_fragments, am_needle_matrix, am_spans), the finisher of long chains
 // (pointer doubling), the one-shot form of an entry point, the loop that sends host slices up in segments and folds each in HBM, and the builder of the batches the
 // library derives in HBM.  The kernels differ from stage to stage; what is here does not.  Included at the end of am_host.h; internal.
 #pragma once
@@ -29,6 +29,17 @@ inline int matches_in_hbm(const am_matches* m, const am_needle_ids* ids, const c
 {
     if (m->n && !m->d_records) return fail(AM_ERR_UNSUPPORTED, std::string(entry) + ": the result was assembled on the host (am_run on a large host batch) and has no records in HBM");
     if (m->dev != ids->a->dev) return fail(AM_ERR_INVALID, "result and values table live on different devices");
+    return AM_OK;
+}
+
+// ... and whose haystack fields all lie below n_hay: the records are sorted by haystack, so the last one, read back here, carries the largest index
+inline int matches_below(const am_matches* m, size_t n_hay, const char* entry, hipStream_t st)
+{
+    if (m->n == 0) return AM_OK;
+    Record last;
+    HIP_TRY(hipMemcpyAsync(&last, m->d_records + m->first + m->n - 1, sizeof(Record), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (last.haystack >= n_hay) return fail(AM_ERR_INVALID, std::string(entry) + ": n_hay is not greater than the largest haystack index of the result");
     return AM_OK;
 }
 
@@ -235,7 +246,7 @@ inline int sub_batch(const am_batch* b, uint64_t h0, uint64_t h1, uint64_t o0, u
     AM_TRY(sub.text(bytes, st, &sub_text));
     AM_TRY(sub.offsets(h1 - h0, &sub_off));
     if (bytes) HIP_TRY(hipMemcpyAsync(sub_text, (const uint8_t*)b->d_text + o0, bytes, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(launch_mx_offsets(b->d_offsets + h0, h1 - h0 + 1, 0 - o0, sub_off, st));      // (base + local[i] in 64-bit arithmetic: local[i] - o0)
+    HIP_TRY(launch_offsets_rebase(b->d_offsets + h0, h1 - h0 + 1, 0 - o0, sub_off, st));      // (base + local[i] in 64-bit arithmetic: local[i] - o0)
     HIP_TRY(hipStreamSynchronize(st));
     return sub.ready(bytes, h1 - h0);
 }

@@ -1,7 +1,7 @@
 // am_hist.hip -- per-needle match counts: the fold `Map.insertWith (+) v 1` over every (record, value of machineValues ! record.state)
 // (reference: src/Data/Text/AhoCorasick/Automaton.hs:442-553 runWithCase and the folds over it; the count identity sum(counts) == countMatches is
-// benchmark/haskell/app/Main.hs:67-76), on the records a scan has left in HBM.  A sibling of k_idset / k_fold_hash (am_replace.hip): the same
-// expansion of a record through the flat value lists of am_needle_ids, into a histogram uint64[n_needles] instead of a bitmap or a checksum.
+// benchmark/haskell/app/Main.hs:67-76), on the records a scan has left in HBM.  A sibling of k_idset / k_fold_hash (am_records.hip): the same
+// expansion of a record through the flat value lists of am_needle_ids (am_records.h), into a histogram uint64[n_needles] instead of a bitmap or a checksum.
 //
 // Natural text is Zipf-distributed: one global atomic per value would send a large share of all adds to a few dozen addresses, and adders that meet on
 // one row run an order of magnitude below adders that are spread.  So the adds of a workgroup to the same id are combined ON CHIP:
@@ -11,9 +11,8 @@
 //     as a 64-bit global atomic (tags never change once claimed: no eviction, nothing to re-validate);
 //   * at the end the workgroup adds every live slot to HBM with one 64-bit global atomic.
 // No LDS counter can wrap: a record adds at most kHistLdsPerRecord times to LDS (the values of a list beyond that go to HBM directly), a tile has kHistTile
-// records, and the workgroup flushes (and clears) its counts after at most kHistTilesPerFlush tiles
-// (AM_HIST_FLUSH_TILES lets a test ask for fewer, never more): at most 1024 * 1024 * 2048 = 2^31 adds between two flushes,
-// all of them to one slot in the worst case, below 2^32.
+// records, and the workgroup flushes (and clears) its counts after at most kHistTilesPerFlush tiles (AM_HIST_FLUSH_TILES lets a test ask for fewer, never more):
+// at most 1024 * 1024 * 2048 = 2^31 adds between two flushes, all of them to one slot in the worst case, below 2^32.
 // Lane per RECORD, the value list of a record looped by its lane: the states of a dictionary carry one value almost everywhere (a suffix chain like
 // tshirt / shirt / hirt a few), so a wave-wide prefix sum to spread values over lanes would be paid by every record for the sake of few.
 // k_needle_hist_words is the same walk over the WHOLE-WORD spans of a table with a word class (am_count_spans_by_needle*): a value is added only where span_of
@@ -24,6 +23,7 @@
 
 #include "am_bounds.h"
 #include "am_device.h"
+#include "am_records.h"
 #include "am_words.h"
 
 AM_BOUNDS_TU("am_hist.hip")
@@ -48,13 +48,15 @@ static_assert((uint64_t)kHistTile * kHistLdsPerRecord * kHistTilesPerFlush < (1u
 // ids are handles in the caller's order (alphabetical, by frequency, ...): a multiplicative hash spreads neighbours over the table
 __device__ __forceinline__ uint32_t hist_slot(uint32_t id) { return (id * 0x9E3779B1u) >> (32 - kHistSlotBits); }
 
-// The walk over the tiles with the workgroup's LDS table (tag / cnt: kHistSlots words each, declared by the kernel).  WORDS: a value is added only where the span it
-// gives with its record is a whole word -- span_of (am_words.h), the function the span expansion decides its rows with -- against the class in `words` (LDS).
-template <bool kTrace, bool WORDS, bool IC>
-__device__ __forceinline__ void hist_body(uint32_t* tag, uint32_t* cnt, const uint32_t* words, const SpansIn& in, const Record* __restrict__ recs, uint64_t n_rec,
-                                          const uint64_t* __restrict__ vals_off, const uint32_t* __restrict__ vals, uint32_t n_needles, uint64_t n_states, uint64_t n_values,
-                                          unsigned long long* __restrict__ counts, unsigned long long* __restrict__ trace, uint32_t tiles_per_flush)
+// The walk over the tiles with the workgroup's LDS table (tag / cnt: kHistSlots words each, declared by the kernel).  WORDS (View = SpansIn, otherwise RecordsIn): a
+// value is added only where the span it gives with its record is a whole word -- span_of (am_words.h), the function the span expansion decides its rows with --
+// against the class in `words` (LDS).
+template <bool kTrace, bool WORDS, bool IC, class View>
+__device__ __forceinline__ void hist_body(const View& in, uint32_t* tag, uint32_t* cnt, const uint32_t* words, unsigned long long* __restrict__ counts,
+                                          unsigned long long* __restrict__ trace, uint32_t tiles_per_flush)
 {
+    const uint32_t* __restrict__ vals = in.vals;
+    const uint32_t n_needles = in.n_needles;
     for (uint32_t i = threadIdx.x; i < kHistSlots; i += kHistThreads) { tag[i] = kHistEmpty; cnt[i] = 0; }
     __syncthreads();
     // every live slot to HBM with one add; `clear`: the counts start again (the tags stay: the hot ids keep their slots)
@@ -72,30 +74,18 @@ __device__ __forceinline__ void hist_body(uint32_t* tag, uint32_t* cnt, const ui
         return adds;
     };
     uint64_t in_lds = 0, in_hbm = 0, in_flush = 0;        // (kTrace only)
-    const uint64_t n_tiles = (n_rec + kHistTile - 1) / kHistTile;
+    const uint64_t n_tiles = (in.n_rec + kHistTile - 1) / kHistTile;
     uint32_t since_flush = 0;
     for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {            // (the same tiles for every lane of the workgroup: the barriers below are uniform)
         uint64_t k[kHistPerThread], ke[kHistPerThread];
-        Record rec[kHistPerThread];                                          // (WORDS only: the predicate needs the record's haystack and end)
-#pragma unroll
-        for (uint32_t u = 0; u < kHistPerThread; u++) {
-            const uint64_t r = t * kHistTile + u * kHistThreads + threadIdx.x;
-            k[u] = ke[u] = 0;
-            if (r < n_rec) {
-                if (WORDS) rec[u] = recs[r];
-                const uint32_t state = WORDS ? rec[u].state : recs[r].state;
-                AM_BOUNDS(state < n_states);
-                if (state < n_states) { k[u] = vals_off[state]; ke[u] = vals_off[state + 1]; }
-                AM_BOUNDS(k[u] <= ke[u] && ke[u] <= n_values);
-                if (ke[u] > n_values) ke[u] = n_values;
-            }
-        }
+        Record rec[kHistPerThread];                                          // (beyond the state, WORDS only: the predicate needs the record's haystack and end)
+        load_records<kHistPerThread, false>(in, t * kHistTile + threadIdx.x, kHistThreads, rec, k, ke);
 #pragma unroll
         for (uint32_t u = 0; u < kHistPerThread; u++) {
             for (uint64_t j = 0; k[u] + j < ke[u]; j++) {
                 const uint32_t id = vals[k[u] + j];
                 if (id >= n_needles) continue;                               // a handle beyond the table: skipped, as containsAll skips it (k_idset)
-                if (WORDS) {
+                if constexpr (WORDS) {
                     uint64_t ss, sn;
                     if (!span_of<IC, true>(in, rec[u], id, words, ss, sn)) continue;      // no whole word: no row of the span table, no count
                 }
@@ -130,13 +120,12 @@ __device__ __forceinline__ void hist_body(uint32_t* tag, uint32_t* cnt, const ui
 }
 
 template <bool kTrace>
-__global__ void __launch_bounds__(kHistThreads) k_needle_hist(const Record* __restrict__ recs, uint64_t n_rec, const uint64_t* __restrict__ vals_off,
-                                                              const uint32_t* __restrict__ vals, uint32_t n_needles, uint64_t n_states, uint64_t n_values,
-                                                              unsigned long long* __restrict__ counts, unsigned long long* __restrict__ trace, uint32_t tiles_per_flush)
+__global__ void __launch_bounds__(kHistThreads) k_needle_hist(RecordsIn in, unsigned long long* __restrict__ counts, unsigned long long* __restrict__ trace,
+                                                              uint32_t tiles_per_flush)
 {
     __shared__ uint32_t tag[kHistSlots];
     __shared__ uint32_t cnt[kHistSlots];
-    hist_body<kTrace, false, false>(tag, cnt, nullptr, SpansIn{}, recs, n_rec, vals_off, vals, n_needles, n_states, n_values, counts, trace, tiles_per_flush);
+    hist_body<kTrace, false, false>(in, tag, cnt, nullptr, counts, trace, tiles_per_flush);
 }
 
 // the whole-word form: the workgroup stages the table's 32-byte class in LDS beside its tables; the LDS-counter wrap argument is the plain kernel's (a record adds
@@ -149,42 +138,33 @@ __global__ void __launch_bounds__(kHistThreads) k_needle_hist_words(SpansIn in, 
     __shared__ uint32_t cnt[kHistSlots];
     __shared__ uint32_t words[kWordClassWords];
     if (threadIdx.x < kWordClassWords) words[threadIdx.x] = in.words[threadIdx.x];      // (hist_body's first barrier comes before any read)
-    hist_body<kTrace, true, IC>(tag, cnt, words, in, in.recs, in.n_rec, in.vals_off, in.vals, in.n_needles, in.n_states, in.n_values, counts, trace, tiles_per_flush);
+    hist_body<kTrace, true, IC>(in, tag, cnt, words, counts, trace, tiles_per_flush);
+}
+
+// what both launchers decide the same way: the persistent grid, and the flush interval (never more than the bound the wrap argument rests on)
+template <class Kernel, class View>
+hipError_t hist_run(Kernel kernel, const View& in, uint64_t* counts, uint64_t* trace, uint32_t flush_tiles, int n_cu, hipStream_t st)
+{
+    const dim3 grid((uint32_t)std::min<uint64_t>((in.n_rec + kHistTile - 1) / kHistTile, (uint64_t)(n_cu > 0 ? n_cu : 1) * kHistGroupsPerCu));
+    const uint32_t tiles_per_flush = flush_tiles != 0 && flush_tiles < kHistTilesPerFlush ? flush_tiles : kHistTilesPerFlush;
+    hipLaunchKernelGGL(kernel, grid, dim3(kHistThreads), 0, st, in, (unsigned long long*)counts, (unsigned long long*)trace, tiles_per_flush);
+    return hipGetLastError();
 }
 
 }  // namespace
 
-hipError_t launch_needle_hist(const Record* recs, uint64_t n_rec, const uint64_t* vals_off, const uint32_t* vals, uint32_t n_needles, uint64_t n_states,
-                              uint64_t n_values, uint64_t* counts, uint64_t* trace, uint32_t flush_tiles, int n_cu, hipStream_t st)
+hipError_t launch_needle_hist(const RecordsIn& in, uint64_t* counts, uint64_t* trace, uint32_t flush_tiles, int n_cu, hipStream_t st)
 {
-    if (n_rec == 0 || n_needles == 0) return hipSuccess;
-    const uint64_t n_tiles = (n_rec + kHistTile - 1) / kHistTile;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)(n_cu > 0 ? n_cu : 1) * kHistGroupsPerCu);
-    const uint32_t tiles_per_flush = flush_tiles != 0 && flush_tiles < kHistTilesPerFlush ? flush_tiles : kHistTilesPerFlush;      // (never more than the bound the wrap argument rests on)
-    if (trace) hipLaunchKernelGGL(k_needle_hist<true>, dim3(grid), dim3(kHistThreads), 0, st, recs, n_rec, vals_off, vals, n_needles, n_states, n_values,
-                                  (unsigned long long*)counts, (unsigned long long*)trace, tiles_per_flush);
-    else hipLaunchKernelGGL(k_needle_hist<false>, dim3(grid), dim3(kHistThreads), 0, st, recs, n_rec, vals_off, vals, n_needles, n_states, n_values,
-                            (unsigned long long*)counts, (unsigned long long*)nullptr, tiles_per_flush);
-    return hipGetLastError();
+    if (in.n_rec == 0 || in.n_needles == 0) return hipSuccess;
+    return hist_run(trace ? k_needle_hist<true> : k_needle_hist<false>, in, counts, trace, flush_tiles, n_cu, st);
 }
 
 hipError_t launch_needle_hist_words(bool ic, const SpansIn& in, uint64_t* counts, uint64_t* trace, uint32_t flush_tiles, int n_cu, hipStream_t st)
 {
     if (in.n_rec == 0 || in.n_needles == 0) return hipSuccess;
     if (!in.words) return hipErrorInvalidValue;
-    const uint64_t n_tiles = (in.n_rec + kHistTile - 1) / kHistTile;
-    const dim3 grid((uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)(n_cu > 0 ? n_cu : 1) * kHistGroupsPerCu)), block(kHistThreads);
-    const uint32_t tiles_per_flush = flush_tiles != 0 && flush_tiles < kHistTilesPerFlush ? flush_tiles : kHistTilesPerFlush;
-    unsigned long long* const c = (unsigned long long*)counts;
-    unsigned long long* const tr = (unsigned long long*)trace;
-    if (trace) {
-        if (ic) hipLaunchKernelGGL((k_needle_hist_words<true, true>), grid, block, 0, st, in, c, tr, tiles_per_flush);
-        else hipLaunchKernelGGL((k_needle_hist_words<true, false>), grid, block, 0, st, in, c, tr, tiles_per_flush);
-    } else {
-        if (ic) hipLaunchKernelGGL((k_needle_hist_words<false, true>), grid, block, 0, st, in, c, tr, tiles_per_flush);
-        else hipLaunchKernelGGL((k_needle_hist_words<false, false>), grid, block, 0, st, in, c, tr, tiles_per_flush);
-    }
-    return hipGetLastError();
+    const auto kernel = trace ? (ic ? k_needle_hist_words<true, true> : k_needle_hist_words<true, false>) : (ic ? k_needle_hist_words<false, true> : k_needle_hist_words<false, false>);
+    return hist_run(kernel, in, counts, trace, flush_tiles, n_cu, st);
 }
 
 }  // namespace dev

@@ -1,5 +1,5 @@
 // am_host.h -- what the host-side translation units of libam share (am_abi.cpp: runtime and thread state, automata, batches, one-shot entry points, results;
-// am_run.cpp: routes and scans; am_replacer.cpp: the Replacer; am_contains_all.cpp: containsAll, the fold checksum, the per-needle counts and the needle matrix;
+// am_run.cpp: routes and scans; am_replacer.cpp: the Replacer; am_contains_all.cpp: the values table (am_needle_ids, which records_in below turns into the kernels' view), containsAll, the fold checksum, the per-needle counts and the needle matrix;
 // am_splitter.cpp: the Splitter; am_spans.cpp: match spans; am_subst.cpp: substitute; am_select.cpp: select; am_rules.cpp: rule sets; am_score.cpp: scores -- substitute, select and scores through
 // am_spans.h, which adds the span table and the spans result): error handling, the per-device runtime, device buffers, the handle structs of include/am.h and the few scan entry points the Replacer
 // drives.  am_fold.h, included at the end, holds the scaffolding of the device stages: argument checks, the CSR result handle, the chain finisher, the one-shot
@@ -192,6 +192,11 @@ struct am_needle_ids {
     uint64_t n_states = 0, n_values = 0;     // entries of vals_off - 1 / of vals
     am::host::DevBuf vals_off, vals;
 };
+// what a fold's kernels read (am_device.h): records [0, n_rec) of a scan, whose haystack fields are below n_hay, with the table
+inline am::dev::RecordsIn records_in(const am_needle_ids* ids, const am::dev::Record* recs, uint64_t n_rec, uint32_t n_hay)
+{
+    return {recs, n_rec, (const uint64_t*)ids->vals_off.p, (const uint32_t*)ids->vals.p, ids->n_states, ids->n_values, ids->n_needles, n_hay};
+}
 
 // what am_rules_eval* leaves in HBM (am_rules.cpp; am_select_rule, am_select.cpp, reads it): rule-major bitmaps, first-rule-wins labels, per-rule counts; the host
 // copies are made once, on first use.  Remembers the batch it was made from as am_selection does.  (Holds DevBufs: on the heap only.)

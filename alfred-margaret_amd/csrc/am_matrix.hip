@@ -1,6 +1,6 @@
 // am_matrix.hip -- the term-document matrix: the fold `Map.insertWith (+) v 1` of runWithCase (reference: src/Data/Text/AhoCorasick/Automaton.hs:442-553) run once PER
 // HAYSTACK, as a CSR matrix {count, needle, haystack} with one row per haystack, rows sorted by needle, built in HBM from the sorted records a scan has left there.
-// A sibling of k_needle_hist (am_hist.hip): the same expansion of a record through the flat value lists of am_needle_ids, keyed by (haystack, needle) instead of needle.
+// A sibling of k_needle_hist (am_hist.hip): the same expansion of a record through the value lists of am_needle_ids (am_records.h), keyed by (haystack, needle).
 //
 // The two shapes it has to serve pull apart: lines of natural text are millions of rows of a handful of entries (a tile of records spans dozens of rows), and
 // `a, aa, aaa` over 16 MiB of `a` is one row of three entries that 48 M adds meet.  One global atomic per value onto a hot key is an order of magnitude too slow, and
@@ -27,6 +27,7 @@
 
 #include "am_bounds.h"
 #include "am_device.h"
+#include "am_records.h"
 
 AM_BOUNDS_TU("am_matrix.hip")
 
@@ -74,55 +75,43 @@ __device__ __forceinline__ void mx_insert(uint64_t key, uint64_t c, unsigned lon
     AM_BOUNDS(false);                                     // the table is larger than the keys it can meet
 }
 
-__global__ void __launch_bounds__(kMxThreads) k_mx_values(const Record* __restrict__ recs, uint64_t n_rec, const uint64_t* __restrict__ vals_off, uint64_t n_states,
-                                                          uint64_t n_values, unsigned long long* __restrict__ total)
+// (every value: the table is sized for the handles beyond n_needles too.  The one fold that reads vals_off itself: through value_range this loop measured 17 % slower
+// in two sessions, for no reason the ISA shows -- profiles/r25_record_folds.md -- so it keeps the tests it had: a list that is out of range adds nothing)
+__global__ void __launch_bounds__(kMxThreads) k_mx_values(RecordsIn in, unsigned long long* __restrict__ total)
 {
     uint64_t v = 0;
-    for (uint64_t r = (uint64_t)blockIdx.x * kMxThreads + threadIdx.x; r < n_rec; r += (uint64_t)gridDim.x * kMxThreads) {
-        const uint32_t state = recs[r].state;
-        AM_BOUNDS(state < n_states);
-        if (state >= n_states) continue;
-        const uint64_t k = vals_off[state], ke = vals_off[state + 1];
-        AM_BOUNDS(k <= ke && ke <= n_values);
-        if (k <= ke && ke <= n_values) v += ke - k;
+    for (uint64_t r = (uint64_t)blockIdx.x * kMxThreads + threadIdx.x; r < in.n_rec; r += (uint64_t)gridDim.x * kMxThreads) {
+        const uint32_t state = in.recs[r].state;
+        AM_BOUNDS(state < in.n_states);
+        if (state >= in.n_states) continue;
+        const uint64_t k = in.vals_off[state], ke = in.vals_off[state + 1];
+        AM_BOUNDS(k <= ke && ke <= in.n_values);
+        if (k <= ke && ke <= in.n_values) v += ke - k;
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
     if ((threadIdx.x & (kWave - 1)) == 0 && v) atomicAdd(total, (unsigned long long)v);
 }
 
-__global__ void __launch_bounds__(kMxThreads) k_mx_combine(const Record* __restrict__ recs, uint64_t n_rec, const uint64_t* __restrict__ vals_off,
-                                                           const uint32_t* __restrict__ vals, uint32_t n_needles, uint64_t n_states, uint64_t n_values, uint32_t n_rows,
-                                                           unsigned long long* __restrict__ keys, unsigned long long* __restrict__ cnts, uint64_t cap,
+__global__ void __launch_bounds__(kMxThreads) k_mx_combine(RecordsIn in, unsigned long long* __restrict__ keys, unsigned long long* __restrict__ cnts, uint64_t cap,
                                                            uint32_t* __restrict__ row_entries)
 {
     __shared__ unsigned long long tag[kMxSlots];
     __shared__ uint32_t cnt[kMxSlots];
     for (uint32_t i = threadIdx.x; i < kMxSlots; i += kMxThreads) { tag[i] = kMxEmpty; cnt[i] = 0; }
     __syncthreads();
-    const uint64_t n_chunks = (n_rec + kMxChunk - 1) / kMxChunk;
+    const uint64_t n_chunks = (in.n_rec + kMxChunk - 1) / kMxChunk;
     for (uint64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {            // (the same chunks for every lane of the workgroup: the barriers below are uniform)
         for (uint32_t t = 0; t < kMxTilesPerChunk; t++) {
             uint64_t k[kMxPerThread], ke[kMxPerThread];
-            uint32_t hay[kMxPerThread];
-#pragma unroll
-            for (uint32_t u = 0; u < kMxPerThread; u++) {
-                const uint64_t r = c * kMxChunk + t * kMxTile + u * kMxThreads + threadIdx.x;
-                k[u] = ke[u] = 0; hay[u] = 0;
-                if (r < n_rec) {
-                    const Record rec = recs[r];
-                    AM_BOUNDS(rec.state < n_states && rec.haystack < n_rows);
-                    if (rec.state < n_states && rec.haystack < n_rows) { k[u] = vals_off[rec.state]; ke[u] = vals_off[rec.state + 1]; hay[u] = rec.haystack; }
-                    AM_BOUNDS(k[u] <= ke[u] && ke[u] <= n_values);
-                    if (ke[u] > n_values) ke[u] = n_values;
-                }
-            }
+            Record rec[kMxPerThread];
+            load_records<kMxPerThread, true>(in, c * kMxChunk + t * kMxTile + threadIdx.x, kMxThreads, rec, k, ke);      // (a record of a haystack beyond the group: emptied)
 #pragma unroll
             for (uint32_t u = 0; u < kMxPerThread; u++) {
                 uint32_t budget = kMxLdsPerRecord;                          // what this record may still add to LDS counters
                 // `n` occurrences of `id` in this record's list: to the workgroup's table, or (slot taken by another key, budget spent) to HBM
                 auto emit = [&](uint32_t id, uint64_t n) {
-                    const uint64_t key = (uint64_t)hay[u] << 32 | id;
+                    const uint64_t key = (uint64_t)rec[u].haystack << 32 | id;
                     if (n <= budget) {
                         const uint32_t s = (uint32_t)(mx_mix(key) >> (64 - kMxSlotBits));
                         AM_BOUNDS(s < kMxSlots);
@@ -130,12 +119,12 @@ __global__ void __launch_bounds__(kMxThreads) k_mx_combine(const Record* __restr
                         if (tg == kMxEmpty) { tg = atomicCAS(&tag[s], (unsigned long long)kMxEmpty, (unsigned long long)key); if (tg == kMxEmpty) tg = key; }
                         if (tg == key) { budget -= (uint32_t)n; atomicAdd(&cnt[s], (uint32_t)n); return; }
                     }
-                    mx_insert(key, n, keys, cnts, cap, row_entries, n_rows);
+                    mx_insert(key, n, keys, cnts, cap, row_entries, in.n_hay);
                 };
                 uint32_t pend = kMxNoId; uint64_t run = 0;                  // equal neighbours of a list (one needle given many times under one handle) are one add
                 for (uint64_t j = k[u]; j < ke[u]; j++) {
-                    const uint32_t id = vals[j];
-                    if (id >= n_needles) continue;                          // a handle beyond the table: skipped, as am_count_by_needle skips it
+                    const uint32_t id = in.vals[j];
+                    if (id >= in.n_needles) continue;                       // a handle beyond the table: skipped, as am_count_by_needle skips it
                     if (id == pend) { run++; continue; }
                     if (run) emit(pend, run);
                     pend = id; run = 1;
@@ -146,7 +135,7 @@ __global__ void __launch_bounds__(kMxThreads) k_mx_combine(const Record* __restr
         __syncthreads();
         for (uint32_t i = threadIdx.x; i < kMxSlots; i += kMxThreads) {
             const uint32_t n = cnt[i];
-            if (n != 0) { mx_insert(tag[i], n, keys, cnts, cap, row_entries, n_rows); cnt[i] = 0; }
+            if (n != 0) { mx_insert(tag[i], n, keys, cnts, cap, row_entries, in.n_hay); cnt[i] = 0; }
             tag[i] = kMxEmpty;
         }
         __syncthreads();
@@ -293,12 +282,6 @@ __global__ void __launch_bounds__(kMxThreads) k_mx_rows_wide(const NeedleCount* 
     }
 }
 
-__global__ void __launch_bounds__(kMxThreads) k_mx_offsets(const uint64_t* __restrict__ local, uint64_t n, uint64_t base, uint64_t* __restrict__ out)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * kMxThreads + threadIdx.x;
-    if (i < n) out[i] = base + (local ? local[i] : 0);
-}
-
 uint32_t mx_grid(uint64_t items, int n_cu, uint32_t per_cu)
 {
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + kMxThreads - 1) / kMxThreads, (uint64_t)(n_cu > 0 ? n_cu : 1) * per_cu));
@@ -308,21 +291,19 @@ uint32_t mx_grid(uint64_t items, int n_cu, uint32_t per_cu)
 
 void mx_limits(uint32_t* out4) { out4[0] = kMxWaveRow; out4[1] = kMxLdsRow; out4[2] = kMxSlots; out4[3] = kMxChunk; }
 
-hipError_t launch_mx_values(const Record* recs, uint64_t n_rec, const uint64_t* vals_off, uint64_t n_states, uint64_t n_values, uint64_t* total, int n_cu, hipStream_t st)
+hipError_t launch_mx_values(const RecordsIn& in, uint64_t* total, int n_cu, hipStream_t st)
 {
-    if (n_rec == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_mx_values, dim3(mx_grid(n_rec, n_cu, 16)), dim3(kMxThreads), 0, st, recs, n_rec, vals_off, n_states, n_values, (unsigned long long*)total);
+    if (in.n_rec == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_mx_values, dim3(mx_grid(in.n_rec, n_cu, 16)), dim3(kMxThreads), 0, st, in, (unsigned long long*)total);
     return hipGetLastError();
 }
 
-hipError_t launch_mx_combine(const Record* recs, uint64_t n_rec, const uint64_t* vals_off, const uint32_t* vals, uint32_t n_needles, uint64_t n_states, uint64_t n_values,
-                             uint32_t n_rows, uint64_t* keys, uint64_t* cnts, uint64_t cap, uint32_t* row_entries, int n_cu, hipStream_t st)
+hipError_t launch_mx_combine(const RecordsIn& in, uint64_t* keys, uint64_t* cnts, uint64_t cap, uint32_t* row_entries, int n_cu, hipStream_t st)
 {
-    if (n_rec == 0 || n_needles == 0 || n_rows == 0 || cap == 0) return hipSuccess;
-    const uint64_t n_chunks = (n_rec + kMxChunk - 1) / kMxChunk;
+    if (in.n_rec == 0 || in.n_needles == 0 || in.n_hay == 0 || cap == 0) return hipSuccess;
+    const uint64_t n_chunks = (in.n_rec + kMxChunk - 1) / kMxChunk;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(n_chunks, (uint64_t)(n_cu > 0 ? n_cu : 1) * kMxGroupsPerCu);
-    hipLaunchKernelGGL(k_mx_combine, dim3(grid), dim3(kMxThreads), 0, st, recs, n_rec, vals_off, vals, n_needles, n_states, n_values, n_rows, (unsigned long long*)keys,
-                       (unsigned long long*)cnts, cap, row_entries);
+    hipLaunchKernelGGL(k_mx_combine, dim3(grid), dim3(kMxThreads), 0, st, in, (unsigned long long*)keys, (unsigned long long*)cnts, cap, row_entries);
     return hipGetLastError();
 }
 
@@ -365,13 +346,6 @@ hipError_t launch_mx_rows_wide(const NeedleCount* tmp, const uint64_t* offsets, 
     if (grid == 0) return hipSuccess;
     const uint32_t words = (uint32_t)(((uint64_t)n_needles + 31) / 32);
     hipLaunchKernelGGL(k_mx_rows_wide, dim3(grid), dim3(kMxThreads), 0, st, tmp, offsets, n_rows, n_entries, list, ctr, n_needles, words, bits, pre, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_mx_offsets(const uint64_t* local, uint64_t n, uint64_t base, uint64_t* out, hipStream_t st)
-{
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_mx_offsets, dim3((uint32_t)((n + kMxThreads - 1) / kMxThreads)), dim3(kMxThreads), 0, st, local, n, base, out);
     return hipGetLastError();
 }
 

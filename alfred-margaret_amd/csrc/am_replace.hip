@@ -15,8 +15,6 @@
 // their start positions are ordered like their end positions and the derived-Ord sort (:159, :241) is the
 // identity on the record order.  am_replacer_create rejects payload tables with duplicate priorities.
 #include <hip/hip_runtime.h>
-#include <atomic>
-#include <cstdlib>
 
 #include "am_device.h"
 
@@ -993,161 +991,6 @@ hipError_t launch_pt_win_copy(const RpWin* wins, const uint64_t* woffs, const Rp
 {
     if (n_win == 0) return hipSuccess;
     hipLaunchKernelGGL(k_pt_win_copy, dim3((uint32_t)((n_win + 1 + 3) / 4)), dim3(256), 0, st, wins, woffs, pieces, next_start, next_cnt, text, repl, wtext, n_win, total_w, padded);
-    return hipGetLastError();
-}
-
-// ---- Searcher.containsAll (Searcher.hs:173-187) on the records: the IntSet of needle ids still missing, as one
-// bitmap of `words` 32-bit words per haystack.  k_idset sets the bit of every reported id, k_idset_all tests
-// whether all n_needles bits of a haystack are set (IS.null of the final accumulator).
-__global__ void __launch_bounds__(256) k_idset(const Record* __restrict__ recs, uint64_t r0, uint64_t r1, const uint64_t* __restrict__ vals_off,
-                                               const uint32_t* __restrict__ vals, uint32_t n_needles, uint32_t hay0, uint32_t words, uint32_t* __restrict__ bits)
-{
-    const uint64_t r = r0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= r1) return;
-    const Record rec = recs[r];
-    uint32_t* row = bits + (uint64_t)(rec.haystack - hay0) * words;
-    for (uint64_t k = vals_off[rec.state], ke = vals_off[rec.state + 1]; k < ke; k++) {
-        const uint32_t id = vals[k];
-        if (id >= n_needles) continue;                           // IS.delete of an absent key
-        const uint32_t m = 1u << (id & 31);
-        if (!(row[id >> 5] & m)) atomicOr(row + (id >> 5), m);      // a stale read only costs an extra atomic
-    }
-}
-
-__global__ void __launch_bounds__(256) k_idset_all(const uint32_t* __restrict__ bits, uint32_t words, uint32_t n_needles, uint32_t n_hay, uint8_t* __restrict__ flags)
-{
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint32_t h = blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
-    if (h >= n_hay) return;
-    const uint32_t* row = bits + (uint64_t)h * words;
-    int64_t c = 0;
-    for (uint32_t w = lane; w < words; w += kWave) c += __popc(row[w]);
-    c = wave_sum_i64(c);
-    if (lane == 0) flags[h] = c == (int64_t)n_needles ? 1 : 0;
-}
-
-hipError_t launch_idset(const Record* recs, uint64_t r0, uint64_t r1, const uint64_t* vals_off, const uint32_t* vals, uint32_t n_needles,
-                        uint32_t hay0, uint32_t words, uint32_t* bits, hipStream_t st)
-{
-    if (r1 <= r0) return hipSuccess;
-    hipLaunchKernelGGL(k_idset, dim3((uint32_t)((r1 - r0 + 255) / 256)), dim3(256), 0, st, recs, r0, r1, vals_off, vals, n_needles, hay0, words, bits);
-    return hipGetLastError();
-}
-
-hipError_t launch_idset_all(const uint32_t* bits, uint32_t words, uint32_t n_needles, uint32_t n_hay, uint8_t* flags, hipStream_t st)
-{
-    if (n_hay == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_idset_all, dim3((n_hay + 3) / 4), dim3(256), 0, st, bits, words, n_needles, n_hay, flags);
-    return hipGetLastError();
-}
-
-// ---- checksum of the fold sequence (SURVEY 8d "parity check at scale"): per haystack, the left fold
-//   h' = h * P + mix(matchPos, value)      over every (record, value of machineValues ! record.state) in order
-// i.e. exactly what the reference's runWithCase would hand to a fold function, reduced to 64 bits.  One wavefront per
-// haystack: every lane folds a contiguous block of the haystack's records, the (hash, count) pairs are combined with
-// the associative rule (h1, c1) . (h2, c2) = (h1 * P^c2 + h2, c1 + c2).
-constexpr uint64_t kFoldP = 0x100000001B3ull;
-__device__ __forceinline__ uint64_t fold_mix(uint64_t pos, uint32_t v)
-{
-    uint64_t x = (pos * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)v + 0x632BE59BD9B4E019ull);
-    x ^= x >> 32; x *= 0xD6E8FEB86659FD93ull; x ^= x >> 32;
-    return x;
-}
-__device__ __forceinline__ uint64_t fold_pow(uint64_t e)
-{
-    uint64_t r = 1, b = kFoldP;
-    while (e) { if (e & 1) r *= b; b *= b; e >>= 1; }
-    return r;
-}
-__global__ void __launch_bounds__(256) k_fold_hash(const Record* __restrict__ recs, const uint64_t* __restrict__ rec_first, const uint64_t* __restrict__ vals_off,
-                                                   const uint32_t* __restrict__ vals, uint32_t n_hay, uint64_t* __restrict__ hash_out, uint64_t* __restrict__ count_out)
-{
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint32_t h = blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
-    if (h >= n_hay) return;
-    const uint64_t r0 = rec_first[h], r1 = rec_first[h + 1];
-    const uint64_t per = (r1 - r0 + kWave - 1) / kWave;
-    uint64_t a = r0 + per * lane, z = a + per;
-    if (a > r1) a = r1;
-    if (z > r1) z = r1;
-    uint64_t hh = 0, cnt = 0;
-    for (uint64_t r = a; r < z; r++) {
-        const Record rec = recs[r];
-        for (uint64_t k = vals_off[rec.state], ke = vals_off[rec.state + 1]; k < ke; k++) { hh = hh * kFoldP + fold_mix(rec.end_pos, vals[k]); cnt++; }
-    }
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {            // lanes whose index is a multiple of 2d absorb their right neighbour's block
-        const uint64_t oh = __shfl_down(hh, d, kWave), oc = __shfl_down(cnt, d, kWave);
-        hh = hh * fold_pow(oc) + oh; cnt += oc;
-    }
-    if (lane == 0) { hash_out[h] = hh; if (count_out) count_out[h] = cnt; }
-}
-
-hipError_t launch_fold_hash(const Record* recs, const uint64_t* rec_first, const uint64_t* vals_off, const uint32_t* vals, uint32_t n_hay,
-                            uint64_t* hash_out, uint64_t* count_out, hipStream_t st)
-{
-    if (n_hay == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_fold_hash, dim3((n_hay + 3) / 4), dim3(256), 0, st, recs, rec_first, vals_off, vals, n_hay, hash_out, count_out);
-    return hipGetLastError();
-}
-
-// ---- several small exclusive sums in ONE launch (the Replacer's per-pass bookkeeping: a dozen scan launches otherwise).
-// One 1024-thread workgroup per job walks its array in tiles of 4096 elements: 4 elements per thread, wave scan with
-// shuffles, wave totals through LDS, running carry.  Meant for arrays up to a few hundred thousand elements.
-__global__ void __launch_bounds__(1024) k_scan_jobs(ScanJobs jobs)
-{
-    // exclusive sums by ONE workgroup per job, 4 096 elements per sweep.  What a sweep costs is the latency of its loads (9.3 us for the five
-    // sweeps of 16 385 elements, whatever the barriers cost): the loads of FOUR sweeps are issued together (index clamped, value masked: no
-    // branch between them), then the four sweeps run.  Per sweep: a wavefront scan, the 16 wavefront totals through LDS (two buffers that take
-    // turns: one barrier per sweep) and a second wavefront scan over those 16 in every wavefront, which gives the wavefront's offset and the
-    // sweep's total -- the running carry stays in registers.
-    constexpr int kBatch = 4;
-    __shared__ uint64_t wave_tot[2][16];
-    const ScanJob j = jobs.j[blockIdx.x];
-    const uint64_t n = j.n_dev ? *j.n_dev + j.n : j.n;
-    if (n == 0) return;
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    uint64_t carry = 0;
-    int turn = 0;
-    for (uint64_t base0 = 0; base0 < n; base0 += 4096 * kBatch) {
-        uint64_t v[kBatch][4];
-        if (j.in64) {
-#pragma unroll
-            for (int bb = 0; bb < kBatch; bb++)
-#pragma unroll
-                for (int k = 0; k < 4; k++) { const uint64_t i = base0 + 4096u * bb + (uint64_t)threadIdx.x * 4 + k; const uint64_t x = j.in64[i < n ? i : n - 1]; v[bb][k] = i < n ? x : 0ull; }
-        } else {
-#pragma unroll
-            for (int bb = 0; bb < kBatch; bb++)
-#pragma unroll
-                for (int k = 0; k < 4; k++) { const uint64_t i = base0 + 4096u * bb + (uint64_t)threadIdx.x * 4 + k; const uint32_t x = j.in32[i < n ? i : n - 1]; v[bb][k] = i < n ? (uint64_t)x : 0ull; }
-        }
-#pragma unroll
-        for (int bb = 0; bb < kBatch; bb++) {
-            const uint64_t base = base0 + 4096u * bb;
-            if (base >= n) break;                         // (uniform)
-            const uint64_t i0 = base + (uint64_t)threadIdx.x * 4;
-            const uint64_t mine = v[bb][0] + v[bb][1] + v[bb][2] + v[bb][3];
-            const int64_t incl = wave_inclusive_sum_i64((int64_t)mine, lane);
-            if (lane == kWave - 1) wave_tot[turn][wave] = (uint64_t)incl;
-            __syncthreads();
-            const uint64_t wt = lane < 16 ? wave_tot[turn][lane] : 0ull;
-            const int64_t wincl = wave_inclusive_sum_i64((int64_t)wt, lane);               // lanes 0..15: totals of the wavefronts up to and including `lane`
-            const uint64_t before_waves = (uint64_t)__shfl(wincl, wave, kWave) - (uint64_t)__shfl((int64_t)wt, wave, kWave);
-            const uint64_t sweep_total = (uint64_t)__shfl(wincl, 15, kWave);
-            uint64_t run = carry + before_waves + (uint64_t)incl - mine;
-#pragma unroll
-            for (int k = 0; k < 4; k++) { const uint64_t i = i0 + k; if (i < n) j.out[i] = run; run += v[bb][k]; }
-            carry += sweep_total;
-            turn ^= 1;
-        }
-    }
-}
-
-hipError_t launch_scan_jobs(const ScanJobs& jobs, hipStream_t st)
-{
-    if (jobs.n_jobs == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_scan_jobs, dim3(jobs.n_jobs), dim3(1024), 0, st, jobs);
     return hipGetLastError();
 }
 

@@ -38,15 +38,7 @@ int score_records(const am_weights* w, const am_span_table* t, int case_mode, co
                   am_scores* x, int dev, hipStream_t st)
 {
     if (first + n_hay > x->n_hay) return fail(AM_ERR_HIP, "am_score: a group of haystacks lies beyond the result");
-    SpansIn in{};
-    if (t) {
-        in = spans_in(t, recs, n_rec, scanned, n_hay);
-    } else {
-        const am_needle_ids* ids = w->ids;
-        in.recs = recs; in.n_rec = n_rec;
-        in.vals_off = (const uint64_t*)ids->vals_off.p; in.vals = (const uint32_t*)ids->vals.p; in.n_states = ids->n_states; in.n_values = ids->n_values;
-        in.n_needles = ids->n_needles; in.n_hay = n_hay;
-    }
+    const SpansIn in = t ? spans_in(t, recs, n_rec, scanned, n_hay) : SpansIn{records_in(w->ids, recs, n_rec, n_hay)};      // (no table: no class, only the records part is read)
     ScoreOut out{(const int64_t*)w->w.p, w->n_cols, w->n_needles, (unsigned long long*)x->scores.p + first, x->n_hay};
     Prof pr(t ? "score_words" : "score", st);
     HIP_TRY(launch_score(case_mode == AM_IGNORE_CASE, in, out, g_rt.dev[dev].n_cu, st));
@@ -157,12 +149,7 @@ extern "C" int am_matches_score(const am_matches* m, const am_weights* w, size_t
     AM_TRY(ensure_runtime());
     ON_DEVICE(m->dev);
     hipStream_t st; AM_TRY(get_stream(m->dev, &st));
-    if (m->n) {
-        Record last;                                        // the records are sorted by haystack: the last one carries the largest index
-        HIP_TRY(hipMemcpyAsync(&last, m->d_records + m->first + m->n - 1, sizeof(Record), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (last.haystack >= n_hay) return fail(AM_ERR_INVALID, "am_matches_score: n_hay is not greater than the largest haystack index of the result");
-    }
+    AM_TRY(matches_below(m, n_hay, "am_matches_score", st));
     ScoresPtr x(nullptr, am_scores_free);
     AM_TRY(new_scores(w, n_hay, 0, st, x));
     x->src_total_known = false;                             // (a result does not remember the bytes of its batch: the selects hold such scores to the haystack count)

@@ -26,6 +26,7 @@
 
 #include "am_bounds.h"
 #include "am_device.h"
+#include "am_records.h"
 #include "am_score.h"
 #include "am_wave.h"
 #include "am_words.h"
@@ -42,7 +43,6 @@ constexpr uint32_t kScoreThreads = 256;
 constexpr uint32_t kScorePerThread = 4;                    // records a lane takes per tile: their loads are issued together
 constexpr uint32_t kScoreWaveRecords = kWave * kScorePerThread;      // consecutive records a wavefront owns in a tile
 constexpr uint32_t kScoreTile = kScoreThreads * kScorePerThread;
-constexpr uint32_t kNoHay = 0xFFFFFFFFu;                   // no haystack: indices are < n_hay <= 2^32 - 2
 constexpr int kScoreGroupsPerCu = 4;
 constexpr uint32_t kTopkThreads = 256;
 constexpr uint32_t kTopkPerThread = 8;
@@ -55,9 +55,9 @@ __device__ __forceinline__ uint64_t lane63_u64(uint64_t x)
     return ((uint64_t)hi << 32) | lo;
 }
 
-// NC: the columns the instantiation has registers for (out.n_cols <= NC; the loops over columns are unrolled and skip the columns beyond out.n_cols)
-template <bool WORDS, bool IC, uint32_t NC>
-__device__ __forceinline__ void score_body(const uint32_t* words, const SpansIn& in, const ScoreOut& out)
+// NC: the columns the instantiation has registers for (out.n_cols <= NC; the loops over columns are unrolled and skip those beyond).  View: SpansIn or RecordsIn
+template <bool WORDS, bool IC, uint32_t NC, class View>
+__device__ __forceinline__ void score_body(const uint32_t* words, const View& in, const ScoreOut& out)
 {
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
@@ -81,20 +81,7 @@ __device__ __forceinline__ void score_body(const uint32_t* words, const SpansIn&
         if (base >= in.n_rec) continue;                                      // (wave-uniform; no barrier in the walk)
         Record rec[kScorePerThread];
         uint64_t k[kScorePerThread], ke[kScorePerThread];
-#pragma unroll
-        for (uint32_t u = 0; u < kScorePerThread; u++) {
-            const uint64_t r = base + u * kWave + lane;
-            k[u] = ke[u] = 0;
-            rec[u].haystack = kNoHay; rec[u].state = 0; rec[u].end_pos = 0;
-            if (r < in.n_rec) {
-                rec[u] = in.recs[r];
-                AM_BOUNDS(rec[u].state < in.n_states && rec[u].haystack < in.n_hay);
-                if (rec[u].haystack >= in.n_hay) rec[u].haystack = kNoHay;
-                if (rec[u].state < in.n_states && rec[u].haystack != kNoHay) { k[u] = in.vals_off[rec[u].state]; ke[u] = in.vals_off[rec[u].state + 1]; }
-                AM_BOUNDS(k[u] <= ke[u] && ke[u] <= in.n_values);
-                if (ke[u] > in.n_values) ke[u] = in.n_values;
-            }
-        }
+        load_records<kScorePerThread, true>(in, base + lane, kWave, rec, k, ke);      // (a record of a haystack beyond the batch: kNoHay, nothing added)
 #pragma unroll
         for (uint32_t u = 0; u < kScorePerThread; u++) {
             if (base + u * kWave >= in.n_rec) break;                         // (wave-uniform)
@@ -105,7 +92,7 @@ __device__ __forceinline__ void score_body(const uint32_t* words, const SpansIn&
             for (uint64_t j = k[u]; j < ke[u]; j++) {
                 const uint32_t id = in.vals[j];
                 if (id >= in.n_needles) continue;                            // a handle beyond the table: skipped, as am_count_by_needle skips it
-                if (WORDS) {
+                if constexpr (WORDS) {
                     uint64_t ss, sn;
                     if (!span_of<IC, true>(in, rec[u], id, words, ss, sn)) continue;      // no whole word: no row of the span table, nothing added
                 }
@@ -160,7 +147,7 @@ __device__ __forceinline__ void score_body(const uint32_t* words, const SpansIn&
 }
 
 template <uint32_t NC>
-__global__ void __launch_bounds__(kScoreThreads) k_score(SpansIn in, ScoreOut out)
+__global__ void __launch_bounds__(kScoreThreads) k_score(RecordsIn in, ScoreOut out)
 {
     score_body<false, false, NC>(nullptr, in, out);
 }
@@ -176,10 +163,10 @@ __global__ void __launch_bounds__(kScoreThreads) k_score_words(SpansIn in, Score
 }
 
 template <uint32_t NC>
-void score_launch(bool words, bool ic, dim3 grid, const SpansIn& in, const ScoreOut& out, hipStream_t st)
+void score_launch(bool ic, dim3 grid, const SpansIn& in, const ScoreOut& out, hipStream_t st)
 {
     const dim3 block(kScoreThreads);
-    if (!words) hipLaunchKernelGGL((k_score<NC>), grid, block, 0, st, in, out);
+    if (!in.words) hipLaunchKernelGGL((k_score<NC>), grid, block, 0, st, static_cast<const RecordsIn&>(in), out);
     else if (ic) hipLaunchKernelGGL((k_score_words<true, NC>), grid, block, 0, st, in, out);
     else hipLaunchKernelGGL((k_score_words<false, NC>), grid, block, 0, st, in, out);
 }
@@ -289,10 +276,9 @@ hipError_t launch_score(bool ic, const SpansIn& in, const ScoreOut& out, int n_c
     if (out.n_cols == 0 || out.n_cols > kScoreMaxColumns || out.stride < in.n_hay) return hipErrorInvalidValue;
     const uint64_t n_tiles = (in.n_rec + kScoreTile - 1) / kScoreTile;
     const dim3 grid((uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)(n_cu > 0 ? n_cu : 1) * kScoreGroupsPerCu));
-    const bool words = in.words != nullptr;
-    if (out.n_cols == 1) score_launch<1>(words, ic, grid, in, out, st);
-    else if (out.n_cols <= 4) score_launch<4>(words, ic, grid, in, out, st);
-    else score_launch<8>(words, ic, grid, in, out, st);
+    if (out.n_cols == 1) score_launch<1>(ic, grid, in, out, st);
+    else if (out.n_cols <= 4) score_launch<4>(ic, grid, in, out, st);
+    else score_launch<8>(ic, grid, in, out, st);
     return hipGetLastError();
 }
 

@@ -1,8 +1,7 @@
 // am_select.hip -- select on the device (include/am.h "select"): the haystacks of a batch that a predicate keeps, as ascending indices and as a batch of their own.
 //
-// The predicate arrives as one byte per haystack in HBM: the flags of the containsAny / containsAll scans, or k_hay_flags_spans over the sorted records of a scan --
-// haystack h is flagged when one of its (record, value) pairs is a span the table keeps (span_of, am_words.h: the function the span expansion and the whole-word
-// histogram decide with), i.e. when row h of AM_SPANS_ALL is not empty.
+// The predicate arrives as one byte per haystack in HBM: the flags of the containsAny / containsAll scans, or of k_hay_flags_spans (am_records.hip) over the sorted
+// records of a scan -- haystack h is flagged when row h of AM_SPANS_ALL is not empty.
 //
 // The compaction works on RUNS.  A batch stores its haystacks back to back, so a maximal sequence of consecutive kept haystacks is ONE contiguous piece of the source
 // text.  k_select_plan turns the flags into keep / run_head / the kept lengths, three exclusive sums (am_scan.hip) give every kept haystack its rank and its new offset
@@ -13,8 +12,6 @@
 
 #include "am_bounds.h"
 #include "am_device.h"
-#include "am_wave.h"
-#include "am_words.h"
 
 AM_BOUNDS_TU("am_select.hip")
 
@@ -27,29 +24,6 @@ constexpr uint32_t kSelThreads = 256;
 
 inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kSelThreads - 1) / kSelThreads); }
 __device__ __forceinline__ uint64_t global_lane() { return (uint64_t)blockIdx.x * kSelThreads + threadIdx.x; }
-
-// one lane per record: the first of its values whose span the table keeps flags the record's haystack, the remaining values are skipped (several lanes may store the
-// same 1 into the same byte)
-template <bool IC, bool WORDS>
-__global__ void __launch_bounds__(kSelThreads) k_hay_flags_spans(SpansIn in, uint8_t* __restrict__ flags)
-{
-    const uint64_t i = global_lane();
-    if (i >= in.n_rec) return;
-    const Record r = in.recs[i];
-    AM_BOUNDS(r.haystack < in.n_hay && r.state < in.n_states);
-    if (r.haystack >= in.n_hay || r.state >= in.n_states) return;
-    uint64_t v0 = in.vals_off[r.state], v1 = in.vals_off[r.state + 1];
-    AM_BOUNDS(v0 <= v1 && v1 <= in.n_values);
-    if (v1 > in.n_values) v1 = in.n_values;
-    for (uint64_t k = v0; k < v1; k++) {
-        const uint32_t v = in.vals[k];
-        if (v >= in.n_needles) continue;                               // the am_needle_ids convention: skipped
-        uint64_t s, n;
-        if (!span_of<IC, WORDS>(in, r, v, in.words, s, n)) continue;
-        flags[r.haystack] = 1;
-        return;
-    }
-}
 
 // one lane per haystack (+ one for the trailing zero of the scans' inputs)
 __global__ void __launch_bounds__(kSelThreads) k_select_plan(const uint8_t* __restrict__ flags, uint32_t constant, uint32_t invert, const uint64_t* __restrict__ src_offsets,
@@ -101,16 +75,6 @@ __global__ void __launch_bounds__(kSelThreads) k_select_emit(const uint32_t* __r
 }
 
 }  // namespace
-
-hipError_t launch_hay_flags_spans(bool ic, const SpansIn& in, uint8_t* flags, hipStream_t st)
-{
-    if (in.n_rec == 0) return hipSuccess;
-    const dim3 grid(blocks_for(in.n_rec)), block(kSelThreads);
-    if (!in.words) hipLaunchKernelGGL((k_hay_flags_spans<false, false>), grid, block, 0, st, in, flags);      // (no class: every span is kept, no start is needed, so no case mode)
-    else if (ic) hipLaunchKernelGGL((k_hay_flags_spans<true, true>), grid, block, 0, st, in, flags);
-    else hipLaunchKernelGGL((k_hay_flags_spans<false, true>), grid, block, 0, st, in, flags);
-    return hipGetLastError();
-}
 
 hipError_t launch_select_plan(const uint8_t* flags, uint32_t constant, uint32_t invert, const uint64_t* src_offsets, uint64_t n, uint64_t src_total, uint32_t* keep,
                               uint32_t* run_head, uint64_t* klen, hipStream_t st)

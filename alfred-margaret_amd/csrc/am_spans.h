@@ -17,14 +17,8 @@ namespace host {
 // what the kernels that turn records into spans read: records [0, n_rec) of a scan of `scanned`, whose haystacks count from 0 there, under table t
 inline am::dev::SpansIn spans_in(const am_span_table* t, const am::dev::Record* recs, uint64_t n_rec, const am_batch* scanned, uint32_t n_hay)
 {
-    const am_needle_ids* ids = t->ids;
-    am::dev::SpansIn in;
-    in.recs = recs; in.n_rec = n_rec;
-    in.vals_off = (const uint64_t*)ids->vals_off.p; in.vals = (const uint32_t*)ids->vals.p; in.n_states = ids->n_states; in.n_values = ids->n_values;
-    in.len_bytes = (const uint32_t*)t->len_bytes.p; in.len_cps = (const uint32_t*)t->len_cps.p; in.n_needles = ids->n_needles; in.n_hay = n_hay;
-    in.text = (const uint8_t*)scanned->d_text; in.offsets = scanned->d_offsets; in.total = scanned->total;
-    in.words = t->d_words();
-    return in;
+    return {records_in(t->ids, recs, n_rec, n_hay), (const uint32_t*)t->len_bytes.p, (const uint32_t*)t->len_cps.p, (const uint8_t*)scanned->d_text, scanned->d_offsets,
+            scanned->total, t->d_words()};
 }
 // d_flags[h] = 1 iff row h of am_spans_batch(t, case_mode, AM_SPANS_ALL, b) is not empty, in bounded record memory (am_contains_all.cpp, beside the whole-word counts)
 int spans_flags(const am_span_table* t, int case_mode, am_batch* b, uint8_t* d_flags);

@@ -30,6 +30,7 @@
 
 #include "am_bounds.h"
 #include "am_device.h"
+#include "am_records.h"
 #include "am_wave.h"
 #include "am_words.h"
 
@@ -45,17 +46,6 @@ constexpr uint32_t kSpMaxPer = (uint32_t)(kSpansMaxTile / kSpThreads);      // c
 
 inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kSpThreads - 1) / kSpThreads); }
 __device__ __forceinline__ uint64_t global_lane() { return (uint64_t)blockIdx.x * kSpThreads + threadIdx.x; }
-
-// the value list of record r as [v0, v1) of in.vals; empty when the state is out of range
-__device__ __forceinline__ void value_range(const SpansIn& in, const Record& r, uint64_t& v0, uint64_t& v1)
-{
-    AM_BOUNDS(r.state < in.n_states);
-    if (r.state >= in.n_states) { v0 = v1 = 0; return; }
-    v0 = in.vals_off[r.state]; v1 = in.vals_off[r.state + 1];
-    AM_BOUNDS(v0 <= v1 && v1 <= in.n_values);
-    if (v1 > in.n_values) v1 = in.n_values;
-    if (v0 > v1) v0 = v1;
-}
 
 // one lane per record (+ one for the trailing zero of the scan's input): its values < n_needles; WORDS: those the word class keeps (span_of, am_words.h -- under
 // IC the backwards walk runs here and again in k_spans_write: no span that is dropped is ever written)
@@ -329,24 +319,16 @@ __global__ void __launch_bounds__(kSpThreads) k_spans_ll_offsets(const uint64_t*
 
 hipError_t launch_spans_count(bool ic, const SpansIn& in, uint32_t* cnt, hipStream_t st)
 {
-    const dim3 grid(blocks_for(in.n_rec + 1)), block(kSpThreads);
-    if (!in.words) hipLaunchKernelGGL((k_spans_count<false, false>), grid, block, 0, st, in, cnt);      // (no class: the count needs no start, so no case mode)
-    else if (ic) hipLaunchKernelGGL((k_spans_count<true, true>), grid, block, 0, st, in, cnt);
-    else hipLaunchKernelGGL((k_spans_count<false, true>), grid, block, 0, st, in, cnt);
+    const auto kernel = !in.words ? k_spans_count<false, false> : ic ? k_spans_count<true, true> : k_spans_count<false, true>;      // (no class: the count needs no start, so no case mode)
+    hipLaunchKernelGGL(kernel, dim3(blocks_for(in.n_rec + 1)), dim3(kSpThreads), 0, st, in, cnt);
     return hipGetLastError();
 }
 
 hipError_t launch_spans_write(bool ic, const SpansIn& in, const uint64_t* voff, Span* spans, uint64_t n_span, hipStream_t st)
 {
     if (in.n_rec == 0 || n_span == 0) return hipSuccess;
-    const dim3 grid(blocks_for(in.n_rec)), block(kSpThreads);
-    if (in.words) {
-        if (ic) hipLaunchKernelGGL((k_spans_write<true, true>), grid, block, 0, st, in, voff, spans, n_span);
-        else hipLaunchKernelGGL((k_spans_write<false, true>), grid, block, 0, st, in, voff, spans, n_span);
-    } else {
-        if (ic) hipLaunchKernelGGL((k_spans_write<true, false>), grid, block, 0, st, in, voff, spans, n_span);
-        else hipLaunchKernelGGL((k_spans_write<false, false>), grid, block, 0, st, in, voff, spans, n_span);
-    }
+    const auto kernel = in.words ? (ic ? k_spans_write<true, true> : k_spans_write<false, true>) : (ic ? k_spans_write<true, false> : k_spans_write<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(blocks_for(in.n_rec)), dim3(kSpThreads), 0, st, in, voff, spans, n_span);
     return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
-// am_words.h -- the span of a (record, value) pair and the whole-word predicate on it (include/am.h "whole words"), shared by the span expansion (am_spans.hip) and the
-// whole-word histogram (am_hist.hip): both decide `keep` with the same device function, so a row the expansion writes is a value the histogram adds.
+// am_words.h -- the span of a (record, value) pair and the whole-word predicate on it (include/am.h "whole words"), shared by the span expansion (am_spans.hip), the
+// whole-word histogram (am_hist.hip), the whole-word scores (am_score.hip) and the select's flags (am_records.hip): all decide `keep` with the same device function,
+// so a row the expansion writes is a value the others add or flag.  The record and its value come from the walk of am_records.h.
 // A WORD CLASS is 256 flags packed into 8 dwords (bit b & 31 of word b >> 5): 32 bytes, one cache line for every lane, in HBM beside the table's lengths or staged in
 // LDS.  A span (start, len) of a haystack of L bytes is a whole word iff (start == 0 or hay[start - 1] is no word byte) and (start + len == L or hay[start + len] is no
 // word byte): the neighbours are bytes of the SAME haystack, never of the one before or after it in the batch, never the zero padding behind the text.
