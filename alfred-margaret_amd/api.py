@@ -41,6 +41,10 @@ RULE_NONE = 0xFFFFFFFF               # the label of a haystack on which no rule 
 RULE_FIRED, RULE_FIRST = 0, 1
 SCORED_DTYPE = np.dtype([("score", np.int64), ("haystack", np.uint32), ("reserved", np.uint32)])   # am_scored
 SCORE_MAX_COLUMNS = 8                # AM_SCORE_MAX_COLUMNS
+NEAR_QUERY_DTYPE = np.dtype([("group_a", np.uint32), ("group_b", np.uint32), ("flags", np.uint32), ("reserved", np.uint32), ("max_gap", np.uint64)])   # am_near_query
+NEAR_PAIR_DTYPE = np.dtype([("a", np.uint64), ("b", np.uint64), ("gap", np.uint64), ("haystack", np.uint32), ("query", np.uint32)])   # am_near_pair
+NEAR_MAX_GROUPS, NEAR_MAX_QUERIES, NEAR_ORDERED = 32, 64, 1          # AM_NEAR_MAX_GROUPS, AM_NEAR_MAX_QUERIES, AM_NEAR_ORDERED
+NEAR_ANYWHERE = 2 ** 64 - 1          # a max_gap that every pair of one haystack meets
 SPANS_ALL = 0
 SPANS_LEFTMOST_LONGEST = 1
 EXTRACT_EACH = 0
@@ -176,6 +180,26 @@ ABI = {
     "am_select_top_k": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_int, _vp, C.POINTER(_vp)]),
     "am_select_score": (C.c_int, [_vp, C.c_uint32, C.c_int64, C.c_int64, C.c_int, _vp, C.POINTER(_vp)]),
     "am_score_geometry": (None, [_u32p, _u32p]),
+    "am_near_create": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(_vp)]),
+    "am_near_destroy": (None, [_vp]),
+    "am_near_spans": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "am_near_batch": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "am_near": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, C.POINTER(_vp), C.POINTER(_vp)]),
+    "am_near_hits_size": (C.c_uint64, [_vp]),
+    "am_near_hits_haystacks": (C.c_uint64, [_vp]),
+    "am_near_hits_queries": (C.c_uint64, [_vp]),
+    "am_near_hits_hay_words": (C.c_uint64, [_vp]),
+    "am_near_hits_offsets": (_vp, [_vp]),
+    "am_near_hits_data": (_vp, [_vp]),
+    "am_near_hits_fired": (_vp, [_vp]),
+    "am_near_hits_counts": (_vp, [_vp]),
+    "am_near_hits_device_offsets": (_vp, [_vp]),
+    "am_near_hits_device_data": (_vp, [_vp]),
+    "am_near_hits_device_fired": (_vp, [_vp]),
+    "am_near_hits_device_counts": (_vp, [_vp]),
+    "am_near_hits_free": (None, [_vp]),
+    "am_select_near": (C.c_int, [_vp, C.c_uint32, C.c_int, _vp, C.POINTER(_vp)]),
+    "am_near_geometry": (None, [_u32p, _u32p]),
     "am_fragments_from_spans": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_vp)]),
     "am_extract_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "am_extract": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(Slice), _sz, C.POINTER(_vp), C.POINTER(_vp)]),
@@ -257,6 +281,7 @@ _HOST = {
     "amh_extract_fold": (C.c_int, [_vp, _vp, C.POINTER(Slice), _sz, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
     "amh_rules_fold": (C.c_int, [_vp, _vp, C.c_uint64, _sz, _sz, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "amh_score": (C.c_int, [_vp, _vp, C.c_uint64, _sz, _sz, _vp, C.c_uint32, _vp]),
+    "amh_near_fold": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, C.c_uint32, C.POINTER(_vp), C.POINTER(_vp), _u64p, _vp, _vp]),
     "amh_substitute_fold": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, C.POINTER(_vp), _vp]),
     "amh_substitute_fold_words": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, _vp, C.POINTER(_vp), _vp]),
     "amh_substitute": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, C.POINTER(_vp), _vp]),
@@ -598,6 +623,40 @@ class Automaton:
         n = len(self.needles) if n_values is None else int(n_values)
         hay, _, val = self.run_batch_with_case(case, texts)
         return score_host(hay, val, len(texts), n, weights)
+
+    def near(self, case, texts, groups, queries, whole_words=False):
+        """Which matches lie near which (include/am.h "proximity"): groups = {"brand": [needles], "item": [needles]} over this automaton's needles (a needle may be in
+        several groups or in none), queries = [("brand", "item", 20), ...] or NearQuery objects whose a / b are group names.  Per text a list with one list per query
+        of (a_start, a_len, b_start, b_len, gap): every leftmost-longest match of group a whose nearest other match of group b lies at most max_gap bytes away.
+        am_near: scanned, selected and joined in HBM; the pairs and the spans they index come back.  whole_words: as in spans."""
+        names = list(groups)
+        if len(names) > NEAR_MAX_GROUPS:
+            raise AmError(AM_ERR_INVALID, "near: at most %d groups" % NEAR_MAX_GROUPS)
+        member = {}
+        for g, name in enumerate(names):
+            for n in groups[name]:
+                member[_as_bytes(n)] = member.get(_as_bytes(n), 0) | (1 << g)
+        known = set(_as_bytes(n) for n in self.needles)
+        for n in member:
+            if n not in known:
+                raise AmError(AM_ERR_INVALID, "near: %r is in a group and not among the needles" % (n,))
+        qs = []
+        for q in queries:
+            q = q if isinstance(q, NearQuery) else NearQuery(*q)
+            if q.a not in groups or q.b not in groups:
+                raise AmError(AM_ERR_INVALID, "near: a query names a group that is not given")
+            qs.append(NearQuery(names.index(q.a), names.index(q.b), q.max_gap, q.ordered))
+        t = SpanTable(self, word_bytes=whole_words)
+        hits, (so, sp) = Near(t, [member.get(_as_bytes(n), 0) for n in self.needles], qs).near_texts(case, texts, spans=True)
+        po, pairs = hits.offsets, hits.pairs
+        out = []
+        for i in range(len(texts)):
+            rows = [[] for _ in qs]
+            for r in pairs[int(po[i]):int(po[i + 1])]:
+                a, b = sp[int(r["a"])], sp[int(r["b"])]
+                rows[int(r["query"])].append((int(a["start"]), int(a["len"]), int(b["start"]), int(b["len"]), int(r["gap"])))
+            out.append(rows)
+        return out
 
     def spans(self, case, texts, leftmost_longest=False, whole_words=False):
         """Where every match starts: (offsets np.uint64[len(texts) + 1], spans SPAN_DTYPE[offsets[-1]]); the spans of text i are spans[offsets[i]:offsets[i + 1]],
@@ -1177,6 +1236,173 @@ def _scores(call):
     h = _vp()
     check(call(C.byref(h)))
     return Scores(h)
+
+
+def near_geometry():
+    """(tile_spans, word_spans) of the proximity stage (am_near_geometry): the spans a workgroup step handles -- a sweep of the word links covers 4 x tile_spans words
+    -- and the spans of a bitmap word.  Known without a device."""
+    t, w = C.c_uint32(0), C.c_uint32(0)
+    libam().am_near_geometry(C.byref(t), C.byref(w))
+    return int(t.value), int(w.value)
+
+
+class NearQuery:
+    """One proximity query: every span of group a with its nearest other span of group b, a pair where the gap between them is at most max_gap bytes.  ordered: only
+    a b BEHIND the anchor counts (AM_NEAR_ORDERED).  a / b: group indices 0 .. 31 (Automaton.near takes group names)."""
+
+    def __init__(self, a, b, max_gap, ordered=False):
+        self.a, self.b, self.max_gap, self.ordered = a, b, int(max_gap), bool(ordered)
+
+
+def _near_queries(queries):
+    """NEAR_QUERY_DTYPE[n] of NearQuery objects, (a, b, max_gap[, ordered]) tuples or a ready array (taken as it is: the library checks it)."""
+    if isinstance(queries, np.ndarray) and queries.dtype == NEAR_QUERY_DTYPE:
+        return np.ascontiguousarray(queries)
+    out = np.zeros(len(queries), NEAR_QUERY_DTYPE)
+    for i, q in enumerate(queries):
+        q = q if isinstance(q, NearQuery) else NearQuery(*q)
+        out[i] = (int(q.a), int(q.b), NEAR_ORDERED if q.ordered else 0, 0, q.max_gap)
+    return out
+
+
+def near_host(spans_offsets, spans, group_mask, queries):
+    """amh_near_fold: the sequential definition of am_near_spans (host/near.hpp nearFold: a plain loop to the left and to the right of every anchor) over leftmost-longest
+    spans the caller brings -- CSR offsets and SPAN_DTYPE rows -- a mask per needle handle and queries.  Runs without a device.
+    (offsets np.uint64[n_hay + 1], pairs NEAR_PAIR_DTYPE, fired_words np.uint64[n_queries, hay_words], counts np.uint64[n_queries])."""
+    so = np.ascontiguousarray(spans_offsets, dtype=np.uint64)
+    sp = np.ascontiguousarray(spans, dtype=SPAN_DTYPE)
+    gm = np.ascontiguousarray(group_mask, dtype=np.uint32)
+    qs = _near_queries(queries)
+    n_hay, nq, hw = len(so) - 1, len(qs), (len(so) - 1 + 63) // 64
+    if n_hay < 0 or int(so[-1]) != len(sp):
+        raise AmError(AM_ERR_INVALID, "near_host: the offsets are not those of the spans")
+    pad = lambda a, t: a if a.size else np.zeros(1, t)
+    fired, counts = np.zeros(max(nq * hw, 1), np.uint64), np.zeros(max(nq, 1), np.uint64)
+    po, pp, n = _vp(), _vp(), C.c_uint64(0)
+    _hcheck(libhost().amh_near_fold(so.ctypes.data, pad(sp, SPAN_DTYPE).ctypes.data, n_hay, pad(gm, np.uint32).ctypes.data, len(gm), pad(qs, NEAR_QUERY_DTYPE).ctypes.data, nq,
+                                    C.byref(po), C.byref(pp), C.byref(n), fired.ctypes.data, counts.ctypes.data))
+    k = int(n.value)
+    try:
+        offs = np.frombuffer((C.c_char * ((n_hay + 1) * 8)).from_address(po.value), dtype=np.uint64).copy()
+        pairs = np.frombuffer((C.c_char * (k * NEAR_PAIR_DTYPE.itemsize)).from_address(pp.value), dtype=NEAR_PAIR_DTYPE).copy() if k else np.zeros(0, NEAR_PAIR_DTYPE)
+    finally:
+        libhost().amh_free_u64(po)
+        libhost().amh_free_u64(pp)
+    return offs, pairs, fired[:nq * hw].reshape(nq, hw), counts[:nq]
+
+
+class NearHits:
+    """What a proximity call found (am_near_hits): the pairs as CSR rows, query-major haystack bitmaps and per-query counts in HBM, copied to the host on first use."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            libam().am_near_hits_free(self._h)
+            self._h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def n_hay(self):
+        return int(libam().am_near_hits_haystacks(self._h))
+
+    @property
+    def n_queries(self):
+        return int(libam().am_near_hits_queries(self._h))
+
+    @property
+    def hay_words(self):
+        return int(libam().am_near_hits_hay_words(self._h))
+
+    def _host(self, fn, n, dtype):
+        p = fn(self._h)
+        if not p:
+            check(AM_ERR_HIP)
+        return np.frombuffer((C.c_char * (n * dtype.itemsize)).from_address(p), dtype=dtype).copy() if n else np.zeros(0, dtype)
+
+    @property
+    def pairs(self):
+        """NEAR_PAIR_DTYPE[size]: a and b index the data array of the spans the hits were made from; rows ascend by (haystack, a, query)."""
+        return self._host(libam().am_near_hits_data, int(libam().am_near_hits_size(self._h)), NEAR_PAIR_DTYPE)
+
+    @property
+    def offsets(self):
+        """np.uint64[n_hay + 1]: the pairs of haystack i are pairs[offsets[i]:offsets[i + 1]]."""
+        return self._host(libam().am_near_hits_offsets, self.n_hay + 1, np.dtype(np.uint64))
+
+    @property
+    def fired_words(self):
+        """np.uint64[n_queries, hay_words]: bit h % 64 of word h // 64 of row q is set iff query q has a pair in haystack h; the bits beyond n_hay are zero."""
+        return self._host(libam().am_near_hits_fired, self.n_queries * self.hay_words, np.dtype(np.uint64)).reshape(self.n_queries, self.hay_words)
+
+    @property
+    def fired(self):
+        """bool[n_queries, n_hay]."""
+        return _fired_bits(self.fired_words, self.n_queries, self.n_hay)
+
+    @property
+    def counts(self):
+        """np.uint64[n_queries]: the pairs of each query."""
+        return self._host(libam().am_near_hits_counts, self.n_queries, np.dtype(np.uint64))
+
+    def select(self, query, batch=None, invert=False):
+        """am_select_near: the Selection of the haystacks of `batch` (the am_batch* the spans of the hits were made from) in which `query` has a pair; invert: the others."""
+        return _select(lambda out: libam().am_select_near(self._h, int(query), int(bool(invert)), batch, out))
+
+
+class Near:
+    """Groups and queries of a proximity call over a SpanTable, on the device (am_near): Near(table, group_mask, queries) with one uint32 mask per needle handle (bit g:
+    the needle is in group g) and up to NEAR_MAX_QUERIES NearQuery objects or (a, b, max_gap[, ordered]) tuples."""
+
+    def __init__(self, span_table, group_mask, queries):
+        self._t = span_table                     # the am_span_table must outlive the handle
+        self.group_mask = np.ascontiguousarray(group_mask, dtype=np.uint32)
+        if self.group_mask.shape != (span_table.n_needles,):
+            raise AmError(AM_ERR_INVALID, "group_mask: one mask per value handle (%s given, %d handles)" % (self.group_mask.shape, span_table.n_needles))
+        self.queries = _near_queries(queries)
+        h = _vp()
+        check(libam().am_near_create(span_table.handle, self.group_mask.ctypes.data if self.group_mask.size else None,
+                                     self.queries.ctypes.data if self.queries.size else None, len(self.queries), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            libam().am_near_destroy(self._h)
+            self._h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    def near_spans(self, spans_raw):
+        """am_near_spans: the stage alone over an am_spans* the caller holds (SpanTable.spans_batch(..., SPANS_LEFTMOST_LONGEST, raw=True))."""
+        h = _vp()
+        check(libam().am_near_spans(self._h, spans_raw, C.byref(h)))
+        return NearHits(h)
+
+    def _with_spans(self, call, spans):
+        h, s = _vp(), _vp()
+        check(call(C.byref(h), C.byref(s) if spans else None))
+        hits = NearHits(h)
+        if not spans:
+            return hits
+        try:
+            return hits, spans_to_numpy(s)
+        finally:
+            libam().am_spans_free(s)
+
+    def near_batch(self, case, batch, spans=False):
+        """am_near_batch on a device-resident batch (an am_batch* handle): the NearHits; spans=True: (NearHits, (offsets, SPAN_DTYPE rows)) -- the spans a and b index."""
+        return self._with_spans(lambda out, s: libam().am_near_batch(self._h, case, batch, out, s), spans)
+
+    def near_texts(self, case, texts, spans=False):
+        """am_near: the one-shot form on host texts."""
+        sl = _Slices(texts)
+        return self._with_spans(lambda out, s: libam().am_near(self._h, case, sl.arr, sl.n, out, s), spans)
 
 
 class Not:

@@ -298,6 +298,17 @@ hipError_t launch_score_range(const int64_t* col, uint64_t n, int64_t lo, int64_
 hipError_t launch_topk_gather(const int64_t* col, uint64_t n, const uint32_t* keep, const uint64_t* pos, Scored* out, uint64_t n_out, hipStream_t st);
 // am_score_geometry: records per workgroup step of k_score (a wavefront owns a quarter of them, consecutive), keys per workgroup of the top-k histogram
 void score_geometry(uint32_t* tile_records, uint32_t* topk_block_items);
+// proximity (am_near.hip; the pick, the bitmap arithmetic and the launch struct: am_near.h) over the n_span rows of an AM_SPANS_LEFTMOST_LONGEST result, in this order:
+// the group bitmaps in.bits (every word written), their word links in.prev_nz / in.next_nz, then per span the mask and the number of the queries that hit (in.hit_mask,
+// in.hit_count; in.fired is accumulating: cleared by the caller), and -- with in.pos = the exclusive sum of in.hit_count over n_span + 1 entries -- the pairs at their
+// places, in.out_off and in.counts (accumulating).  launch_near_emit runs for n_span == 0 too (it writes out_off).  Persistent grids sized from n_cu.
+struct NearIn;
+hipError_t launch_near_bits(const NearIn& in, int n_cu, hipStream_t st);
+hipError_t launch_near_words(const NearIn& in, hipStream_t st);
+hipError_t launch_near_count(const NearIn& in, int n_cu, hipStream_t st);
+hipError_t launch_near_emit(const NearIn& in, int n_cu, hipStream_t st);
+// am_near_geometry: spans per workgroup step of the three span kernels (a sweep of k_near_words covers 4 x as many WORDS), spans per bitmap word
+void near_geometry(uint32_t* tile_spans, uint32_t* word_spans);
 // incremental re-scan between Replacer passes (am_replace.hip)
 struct RpWin { uint64_t src_abs; uint64_t ws; uint32_t len; uint32_t own_lo; };   // window: bytes src_abs.. of the next text; ws = its start inside the haystack; records with end > own_lo are its own
 hipError_t launch_rp_win_count(const RpHay* hs, uint32_t n_act, uint32_t* nwin, hipStream_t st);

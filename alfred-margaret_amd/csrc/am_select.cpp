@@ -6,7 +6,7 @@
 // runs is am_select.hip's; the bytes move with am_split.hip's gather.  What crosses to the host during a *_batch select: the kept count, the run count and the kept
 // bytes (one copy of three words), and whatever the scans read back themselves.
 // Every argument is checked before any device work.
-#include "am_spans.h"
+#include "am_near_host.h"
 
 using namespace am;
 using namespace am::dev;
@@ -180,6 +180,28 @@ extern "C" int am_select_rule(const am_rule_hits* x, uint32_t rule, int which, i
             Prof pr("rule_flags", st);
             HIP_TRY(launch_rule_flags(which == AM_RULE_FIRED ? (const uint64_t*)x->fired.p + (uint64_t)rule * x->hay_words : nullptr, (const uint32_t*)x->labels.p, rule,
                                       x->n_hay, x->hay_words, d_flags, st));
+            return AM_OK;
+        }));
+    *out = s.release();
+    return AM_OK;
+}
+
+// the haystacks in which one query of a proximity result (am_near.cpp) has a pair: its row of `fired` as byte flags (k_rule_flags: the layout is am_rule_hits'),
+// then the compaction.  src must be the batch the spans of the hits were made from.
+extern "C" int am_select_near(const am_near_hits* x, uint32_t query, int invert, const am_batch* src, am_selection** out)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    if (!x || !src) return fail(AM_ERR_INVALID, "null proximity hits or batch");
+    if (query >= x->n_queries) return fail(AM_ERR_INVALID, "query is not below the number of queries");
+    if (x->n_hay != src->n_hay || x->src_total != src->total || x->dev != src->dev)
+        return fail(AM_ERR_INVALID, "the proximity hits were not made from a batch with this haystack count and size");
+    AM_TRY(ensure_runtime());
+    SelectionPtr s = new_selection(src);
+    if (src->n_hay != 0)
+        AM_TRY(compact_written(src, invert, s.get(), [&](uint8_t* d_flags, hipStream_t st) -> int {
+            Prof pr("rule_flags", st);
+            HIP_TRY(launch_rule_flags((const uint64_t*)x->fired.p + (uint64_t)query * x->hay_words, nullptr, query, x->n_hay, x->hay_words, d_flags, st));
             return AM_OK;
         }));
     *out = s.release();

@@ -4,6 +4,7 @@
 #include <memory>
 #include <string>
 
+#include "near.hpp"
 #include "replacer.hpp"
 #include "rules.hpp"
 #include "spans.hpp"
@@ -197,6 +198,33 @@ int amh_score(const uint32_t* hay_in, const uint32_t* val_in, uint64_t n, size_t
         if (n_values && !weights) throw AmError(AM_ERR_INVALID, "amh_score: null weights");
         const std::vector<int64_t> r = scoreByHaystack(hay_in, val_in, n, n_hay, n_values, weights, n_cols);
         if (!r.empty()) std::memcpy(scores_out, r.data(), r.size() * 8);
+    });
+}
+
+// ---- proximity (near.hpp): nearFold over leftmost-longest spans the caller brings (CSR: span_offs has n_hay + 1 entries, spans_in span_offs[n_hay] rows of am_span), a
+// group mask per needle handle and queries in the C ABI's form: no device is touched.  fired_out: n_queries x ceil(n_hay / 64) words, counts_out: n_queries, both the
+// caller's; offsets (n_hay + 1) and the pairs as the C ABI lays them out (am_near_pair, 32 bytes each): free both with amh_free_u64
+int amh_near_fold(const uint64_t* span_offs, const am_span* spans_in, size_t n_hay, const uint32_t* group_mask, size_t n_needles, const am_near_query* queries,
+                  uint32_t n_queries, uint64_t** offs_out, uint64_t** pairs_out, uint64_t* n_out, uint64_t* fired_out, uint64_t* counts_out)
+{
+    *offs_out = nullptr; *pairs_out = nullptr; *n_out = 0;
+    return guarded([&] {
+        if (!span_offs || span_offs[0] != 0) throw AmError(AM_ERR_INVALID, "amh_near_fold: span_offs is null or does not begin with 0");
+        if ((n_needles && !group_mask) || (n_queries && !queries)) throw AmError(AM_ERR_INVALID, "amh_near_fold: null group masks or queries");
+        for (size_t h = 0; h < n_hay; h++)
+            if (span_offs[h + 1] < span_offs[h]) throw AmError(AM_ERR_INVALID, "amh_near_fold: span_offs descends");
+        Spans sp;
+        sp.offsets.assign(span_offs, span_offs + n_hay + 1);
+        if (span_offs[n_hay]) sp.spans.assign(spans_in, spans_in + span_offs[n_hay]);
+        const NearHits r = nearFold(sp, std::vector<uint32_t>(group_mask, group_mask + n_needles), std::vector<am_near_query>(queries, queries + n_queries));
+        const uint64_t np = r.pairs.size();
+        uint64_t* offs = (uint64_t*)malloc((n_hay + 1) * sizeof(uint64_t));
+        uint64_t* pr = (uint64_t*)malloc((np ? np : 1) * sizeof(am_near_pair));
+        std::memcpy(offs, r.offsets.data(), (n_hay + 1) * sizeof(uint64_t));
+        if (np) std::memcpy(pr, r.pairs.data(), np * sizeof(am_near_pair));
+        if (!r.fired.empty()) std::memcpy(fired_out, r.fired.data(), r.fired.size() * 8);
+        if (!r.counts.empty()) std::memcpy(counts_out, r.counts.data(), r.counts.size() * 8);
+        *offs_out = offs; *pairs_out = pr; *n_out = np;
     });
 }
 

@@ -570,6 +570,78 @@ AM_API int am_select_top_k(const am_scores* x, uint32_t column, uint64_t k, int 
 AM_API int am_select_score(const am_scores* x, uint32_t column, int64_t lo, int64_t hi, int invert, const am_batch* src, am_selection** out);
 AM_API void am_score_geometry(uint32_t* tile_records, uint32_t* topk_block_items);
 
+/* ---- proximity: which matches lie near which, from one scan, in HBM; per query a haystack bitmap for the select ---------------
+ * `nike w/20 shoe`, a currency word next to an amount, a negation right before a sentiment word, a drug next to a dosage unit, relation candidates for an extraction
+ * model: did a match of one group occur within D bytes of a match of another, and where.  A stage over an AM_SPANS_LEFTMOST_LONGEST result (rows ascending by
+ * (haystack, start), disjoint, len > 0); up to AM_NEAR_MAX_QUERIES queries over up to AM_NEAR_MAX_GROUPS groups are answered from one scan and one spans call.
+ * GROUPS.  group_mask[v] is a uint32 per needle handle of the span table: bit g set = needle v belongs to group g.  A needle may belong to several groups or to none.
+ * QUERY.  am_near_query { group_a, group_b, flags, reserved, max_gap }, 24 bytes at offsets 0, 4, 8, 12, 16; flags is 0 or AM_NEAR_ORDERED, reserved must be 0.
+ * For haystack h with leftmost-longest rows s_0 .. s_{k-1} and e_i = start_i + len_i, span i is in group g iff group_mask[needle_i] has bit g.  For query q and every
+ * i in group group_a, taken as ANCHOR, the candidates are
+ *   p = the largest j < i in group group_b,  gap_p = start_i - e_p
+ *   n = the smallest j > i in group group_b, gap_n = start_n - e_i        (under AM_NEAR_ORDERED only n is a candidate)
+ * The anchor is NEVER ITS OWN PARTNER, even when it is in both groups: group_a == group_b means "a repeated mention".  The partner is the candidate with the smaller
+ * gap; a TIE goes to p, the lower index.  A pair is emitted iff the partner's gap is <= max_gap, compared in 64 bits: max_gap = 2^64 - 1 is valid and means
+ * "anywhere in the haystack".  Partners never come from another haystack; touching spans have gap 0.  Because the rows are disjoint and ascending, this partner IS
+ * the nearest span of the group on each side.
+ * With A = {nike}, B = {shoe} and kids in no group, over "nike kids shoe, shoe nike" the rows are nike[0,4) kids[5,9) shoe[10,14) shoe[16,20) nike[21,25):
+ *   query (A, B, max_gap 1)                       the one pair (a=4, b=3, gap=1)
+ *   max_gap 6                                     (0,2,6) and (4,3,1)
+ *   max_gap 6 with AM_NEAR_ORDERED                (0,2,6) only
+ * Over "shoe nike shoe" both gaps are 1 and b = 0.
+ * RESULT (am_near_hits), in HBM until asked for (the accessors make host copies on first use; never NULL on success):
+ *   pairs   am_near_pair { a, b, gap, haystack, query }, 32 bytes: a and b are indices into the DATA ARRAY of the spans result the hits were made from (global, not
+ *           per row); CSR per haystack, offsets[n_hay + 1], as for am_spans; rows ascend by (haystack, a, query)
+ *   fired   uint64[n_queries][hay_words], hay_words = ceil(n_hay / 64): bit h % 64 of word h / 64 of row q is set iff query q has at least one pair in haystack h; bits
+ *           beyond n_hay are ZERO (am_rule_hits' layout)
+ *   counts  uint64[n_queries]: the pairs of query q
+ * Everything is bit-identical from run to run.  n_queries == 0, no haystacks and no spans are all valid and give empty shapes.
+ *   am_near_create    compiles the groups and queries for a span table; the arrays are copied, the table must outlive the handle.
+ *   am_near_spans     the stage alone over a spans result the caller holds: AM_ERR_INVALID for an AM_SPANS_ALL result (as am_batch_substitute), for spans whose
+ *                     n_needles differs from the table's, for handles on different devices.  The join (csrc/am_near.hip) needs no sort, no atomic per pair and no
+ *                     lane loop whose trip count depends on the text: one bitmap row over the span indices per group, per 64-span word the nearest non-zero word
+ *                     on either side, then a lane per span finds both candidates by bit arithmetic.  WORKSPACE, freed when the call returns: 20 bytes per span and
+ *                     0.25 bytes per span and group a query names (8 at the most); the result holds 32 bytes per pair, 8 per haystack and 8 per query and 64
+ *                     haystacks.  Only the pair count crosses to the host.  The library's device buffers are allocated an eighth larger than asked.
+ *   am_near_batch     am_spans_batch(t, case_mode, AM_SPANS_LEFTMOST_LONGEST, b) and the stage; spans_out (nullable): the spans a and b index (am_spans_free).
+ *                     Record memory is NOT bounded here, as in am_spans_batch.  A span table with a word class gives whole-word proximity (the stage reads spans).
+ *   am_near           the one-shot form on host slices (the calling thread's one-shot batch).
+ *   am_select_near    the haystacks of query `query`'s row of fired as a selection of `src` -- to these hits what am_select_rule(..., AM_RULE_FIRED, ...) is to rule
+ *                     hits; src must be the batch the spans were made from: AM_ERR_INVALID when the haystack count, the total bytes or the device differ.
+ *   am_near_geometry  for tests, known without a device: the spans one workgroup step handles (a sweep of the word links covers four times as many WORDS), and the
+ *                     spans of one bitmap word.
+ * Arguments are checked before any device work (a null group_mask alone is seen after the runtime is up: whether it is needed is the table's needle count):
+ * AM_ERR_INVALID for null handles or a null out, n_queries > AM_NEAR_MAX_QUERIES, a group index >= 32, unknown flag
+ * bits or reserved != 0, query >= n_queries, a case_mode that is neither of the two, slices without memory, n_hay >= 0xFFFFFFFF.  *out and *spans_out are NULL after
+ * every failure. */
+#define AM_NEAR_MAX_GROUPS 32
+#define AM_NEAR_MAX_QUERIES 64
+#define AM_NEAR_ORDERED 1u
+struct am_near;                                         /* (no typedef: am_near alone names the one-shot entry point, as am_spans does) */
+typedef struct am_near_hits am_near_hits;
+typedef struct am_near_query { uint32_t group_a, group_b, flags, reserved; uint64_t max_gap; } am_near_query;   /* 24 bytes: offsets 0, 4, 8, 12, 16 */
+typedef struct am_near_pair { uint64_t a, b, gap; uint32_t haystack, query; } am_near_pair;                     /* 32 bytes: offsets 0, 8, 16, 24, 28 */
+AM_API int am_near_create(const am_span_table* t, const uint32_t* group_mask /* n_needles, host */, const am_near_query* queries, uint32_t n_queries, struct am_near** out);
+AM_API void am_near_destroy(struct am_near* p);
+AM_API int am_near_spans(const struct am_near* p, const struct am_spans* s, am_near_hits** out);
+AM_API int am_near_batch(const struct am_near* p, int case_mode, const am_batch* b, am_near_hits** out, struct am_spans** spans_out /* nullable */);
+AM_API int am_near(const struct am_near* p, int case_mode, const am_slice* hay, size_t n_hay, am_near_hits** out, struct am_spans** spans_out /* nullable */);
+AM_API uint64_t am_near_hits_size(const am_near_hits* x);          /* pairs */
+AM_API uint64_t am_near_hits_haystacks(const am_near_hits* x);
+AM_API uint64_t am_near_hits_queries(const am_near_hits* x);
+AM_API uint64_t am_near_hits_hay_words(const am_near_hits* x);
+AM_API const uint64_t* am_near_hits_offsets(am_near_hits* x);
+AM_API const am_near_pair* am_near_hits_data(am_near_hits* x);
+AM_API const uint64_t* am_near_hits_fired(am_near_hits* x);
+AM_API const uint64_t* am_near_hits_counts(am_near_hits* x);
+AM_API const void* am_near_hits_device_offsets(const am_near_hits* x);
+AM_API const void* am_near_hits_device_data(const am_near_hits* x);
+AM_API const void* am_near_hits_device_fired(const am_near_hits* x);
+AM_API const void* am_near_hits_device_counts(const am_near_hits* x);
+AM_API void am_near_hits_free(am_near_hits* x);
+AM_API int am_select_near(const am_near_hits* x, uint32_t query, int invert, const am_batch* src, am_selection** out);
+AM_API void am_near_geometry(uint32_t* tile_spans, uint32_t* word_spans);
+
 /* ---- extract: the matched text with some characters around it, in HBM; the snippets are a batch of their own ---------------
  * `grep -o`, `grep -o -E '.{0,40}needle.{0,40}'`, a keyword-in-context concordance, the snippets of a search front end, the windows an entity-extraction pipeline gives
  * to its next model -- over a batch, without the spans (24 bytes each) or the snippets crossing the wire.
