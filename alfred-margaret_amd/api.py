@@ -28,6 +28,17 @@ class AmError(RuntimeError):
         self.code = code
 
 
+class _Match:
+    """am.MATCH: the segment of a substitution template that stands for the matched text itself (AM_SEG_MATCH) -- sed's &."""
+    __slots__ = ()
+
+    def __repr__(self):
+        return "am.MATCH"
+
+
+MATCH = _Match()
+
+
 class Slice(C.Structure):          # am_slice
     _fields_ = [("ptr", C.c_void_p), ("off", C.c_size_t), ("len", C.c_size_t)]
 
@@ -47,6 +58,7 @@ NEAR_MAX_GROUPS, NEAR_MAX_QUERIES, NEAR_ORDERED = 32, 64, 1          # AM_NEAR_M
 NEAR_ANYWHERE = 2 ** 64 - 1          # a max_gap that every pair of one haystack meets
 SPANS_ALL = 0
 SPANS_LEFTMOST_LONGEST = 1
+SUBST_MAX_SEGMENTS, SEG_LITERAL, SEG_MATCH = 64, 0, 1          # AM_SUBST_MAX_SEGMENTS, AM_SEG_LITERAL, AM_SEG_MATCH
 EXTRACT_EACH = 0
 EXTRACT_MERGED = 1
 PRIO_MATCH_DTYPE = np.dtype([("start", np.uint64), ("len", np.uint64), ("haystack", np.uint32), ("payload", np.uint32)])   # am_prio_match
@@ -125,6 +137,7 @@ ABI = {
     "am_spans_rounds": (C.c_uint32, [_vp]),
     "am_spans_free": (None, [_vp]),
     "am_subst_table_create": (C.c_int, [_vp, _vp, _vp, C.POINTER(_vp)]),
+    "am_subst_table_create_templates": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "am_subst_table_destroy": (None, [_vp]),
     "am_batch_substitute": (C.c_int, [_vp, _vp, _vp, C.POINTER(_vp)]),
     "am_substitute_batch": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
@@ -285,6 +298,8 @@ _HOST = {
     "amh_substitute_fold": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, C.POINTER(_vp), _vp]),
     "amh_substitute_fold_words": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, _vp, C.POINTER(_vp), _vp]),
     "amh_substitute": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, C.POINTER(_vp), _vp]),
+    "amh_substitute_templates_fold": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), _vp]),
+    "amh_substitute_templates": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, C.POINTER(_vp), _vp]),
     "amh_searcher_build": (C.c_int, [C.c_int, C.c_char_p, _vp, _sz, C.POINTER(_vp)]),
     "amh_searcher_free": (None, [_vp]),
     "amh_searcher_set_case": (None, [_vp, C.c_int]),
@@ -679,8 +694,27 @@ class Automaton:
 
     def substitute(self, case, texts, replacements, whole_words=False):
         """Every leftmost-longest match replaced once, replacements[v] for needle v, never scanned again (include/am.h "substitute"): a list of bytes, one per text.
-        am_substitute: scanned, selected and spliced in HBM.  whole_words: as in spans -- the leftmost-longest WHOLE-WORD matches."""
+        am_substitute: scanned, selected and spliced in HBM.  whole_words: as in spans -- the leftmost-longest WHOLE-WORD matches.  A replacement is bytes / str, or a
+        TEMPLATE: a list or tuple of bytes / str / am.MATCH, where am.MATCH stands for the matched text as it is spelled in the haystack (include/am.h "substitute
+        templates"): ["<b>", am.MATCH, "</b>"]."""
         return SubstTable(SpanTable(self, word_bytes=whole_words), replacements).substitute_texts(case, texts)
+
+    def highlight(self, case, texts, before, after, whole_words=False):
+        """Every leftmost-longest match wrapped: the template [before, am.MATCH, after] for every needle.  Under IGNORE_CASE the text keeps its own spelling:
+        Automaton(["nike"]).highlight(IGNORE_CASE, ["NIKE shoe"], "<b>", "</b>") == [b"<b>NIKE</b> shoe"]."""
+        return self.substitute(case, texts, [[before, MATCH, after]] * len(self.needles), whole_words=whole_words)
+
+    def mask(self, case, texts, fill="*", whole_words=False):
+        """Every leftmost-longest match overwritten, one `fill` per CODE POINT of the match: the fixed replacement fill * code_points(needle), through the plain table.
+        This is exact per code point in both case modes: a span is made by makeMatch (Replacer.hs:264-274), which under CASE_SENSITIVE takes the needle's own bytes
+        and under IGNORE_CASE walks back over exactly the needle's number of code points -- so a match always has as many code points as its needle, whatever its
+        width in bytes (U+212A for k: three bytes, one code point, one `fill`)."""
+        return self.substitute(case, texts, self.mask_replacements(fill), whole_words=whole_words)
+
+    def mask_replacements(self, fill="*"):
+        """The fixed replacements mask() uses: fill * code_points(needle) per needle."""
+        fill = _as_bytes(fill)
+        return [fill * len(_as_bytes(n).decode("utf-8")) for n in self.needles]
 
     def count_whole_words(self, case, texts, word_bytes=True):
         """How often every needle occurs as a whole word over all the texts: np.uint64[len(needles)], the bincount of the whole-word spans(..., whole_words=word_bytes)
@@ -729,6 +763,44 @@ class Automaton:
         blob, out_offs = _vp(), np.zeros(s.n + 1, np.uint64)
         _hcheck(libhost().amh_substitute(self._h, case, s.arr, s.n, lb.ctypes.data, lc.ctypes.data, nv, pool, offs.ctypes.data, C.byref(blob), out_offs.ctypes.data))
         return _take_texts(blob, out_offs)
+
+
+    def substitute_templates_host_mirror(self, case, texts, templates, n_values=None, lengths=None):
+        """substitute with templates through the C++ host mirror (host/spans.hpp substituteTemplates over spansFold over the fold steps of amh_run_list)."""
+        lb, lc = _handle_lengths(self.needles, n_values, lengths)
+        nv = (len(self.needles) if lengths is None else len(lengths[0])) if n_values is None else int(n_values)
+        seg_off, kind, lit_off, pool = _pack_templates(templates, nv)
+        s = _Slices(texts)
+        blob, out_offs = _vp(), np.zeros(s.n + 1, np.uint64)
+        _hcheck(libhost().amh_substitute_templates(self._h, case, s.arr, s.n, lb.ctypes.data, lc.ctypes.data, nv, seg_off.ctypes.data, kind.ctypes.data, lit_off.ctypes.data,
+                                                   pool or None, C.byref(blob), out_offs.ctypes.data))
+        return _take_texts(blob, out_offs)
+
+
+def _is_template(x):
+    return isinstance(x, (list, tuple))
+
+
+def _pack_templates(templates, n):
+    """(seg_off np.uint64[n + 1], seg_kind np.uint8[n_seg (+ 1)], lit_off np.uint64[n_seg + 1], pool bytes) of am_subst_table_create_templates for value handles
+    0 .. n - 1; a plain replacement is the template of that one literal."""
+    tpls = [list(x) if _is_template(x) else [x] for x in templates]
+    if len(tpls) != n:
+        raise AmError(AM_ERR_INVALID, "replacements: one per value handle (%d given, %d handles)" % (len(tpls), n))
+    seg_off, kinds, lits = np.zeros(n + 1, np.uint64), [], []
+    for v, t in enumerate(tpls):
+        for seg in t:
+            if seg is MATCH:
+                kinds.append(SEG_MATCH)
+                lits.append(b"")
+            elif isinstance(seg, (bytes, bytearray, str)):
+                kinds.append(SEG_LITERAL)
+                lits.append(_as_bytes(seg))
+            else:
+                raise AmError(AM_ERR_INVALID, "a template's segments are bytes, str or am.MATCH (needle %d)" % v)
+        seg_off[v + 1] = len(kinds)
+    pool, lit_off = pack_texts(lits)
+    return seg_off, np.array(kinds + [0], np.uint8), lit_off, pool
 
 
 def _pack_replacements(replacements, n):
@@ -789,6 +861,27 @@ def substitute_fold_host(case, triples, texts, len_bytes, len_code_points, repla
     flags = _word_flags(word_bytes)
     _hcheck(libhost().amh_substitute_fold_words(case, hay.ctypes.data, pos.ctypes.data, val.ctypes.data, n, s.arr, s.n, lb.ctypes.data, lc.ctypes.data, nv, pool,
                                                 offs.ctypes.data, None if flags is None else flags.ctypes.data, C.byref(blob), out_offs.ctypes.data))
+    return _take_texts(blob, out_offs)
+
+
+def substitute_templates_fold_host(case, triples, texts, len_bytes, len_code_points, templates, word_bytes=None):
+    """amh_substitute_templates_fold: the sequential definition of am_substitute with templates (a list per value handle of bytes / str / am.MATCH, or a plain
+    replacement) over fold steps the caller brings, as substitute_fold_host.  Runs without a device."""
+    hay = np.ascontiguousarray(triples[0], dtype=np.uint32)
+    pos = np.ascontiguousarray(triples[1], dtype=np.uint64)
+    val = np.ascontiguousarray(triples[2], dtype=np.uint32)
+    lb = np.ascontiguousarray(len_bytes, dtype=np.uint32)
+    lc = np.ascontiguousarray(len_code_points, dtype=np.uint32)
+    n, nv = len(hay), len(lb)
+    pad = lambda a, t: a if a.size else np.zeros(1, t)
+    hay, pos, val, lb, lc = pad(hay, np.uint32), pad(pos, np.uint64), pad(val, np.uint32), pad(lb, np.uint32), pad(lc, np.uint32)
+    seg_off, kind, lit_off, pool = _pack_templates(templates, nv)
+    s = _Slices(texts)
+    blob, out_offs = _vp(), np.zeros(s.n + 1, np.uint64)
+    flags = _word_flags(word_bytes)
+    _hcheck(libhost().amh_substitute_templates_fold(case, hay.ctypes.data, pos.ctypes.data, val.ctypes.data, n, s.arr, s.n, lb.ctypes.data, lc.ctypes.data, nv,
+                                                    seg_off.ctypes.data, kind.ctypes.data, lit_off.ctypes.data, pool or None,
+                                                    None if flags is None else flags.ctypes.data, C.byref(blob), out_offs.ctypes.data))
     return _take_texts(blob, out_offs)
 
 
@@ -1649,14 +1742,23 @@ def batch_to_bytes(batch):
 
 
 class SubstTable:
-    """The replacements beside a SpanTable on the device (am_subst_table): replacements[v] = the bytes that replace a match of value handle v."""
+    """The replacements beside a SpanTable on the device (am_subst_table): replacements[v] = the bytes that replace a match of value handle v, or a template -- a
+    list or tuple of bytes / str / am.MATCH.  A table of plain replacements only is made by am_subst_table_create, as ever; one template among them makes it a table of
+    templates (am_subst_table_create_templates)."""
 
     def __init__(self, span_table, replacements):
         self._t = span_table                                 # (the am_span_table must outlive the table)
         self.n_needles = span_table.n_needles
-        self._pool, self._off = _pack_replacements(replacements, self.n_needles)
+        replacements = list(replacements)
+        self.templates = any(_is_template(x) for x in replacements)
         h = _vp()
-        check(libam().am_subst_table_create(span_table.handle, self._off.ctypes.data, self._pool or None, C.byref(h)))
+        if not self.templates:
+            self._pool, self._off = _pack_replacements(replacements, self.n_needles)
+            check(libam().am_subst_table_create(span_table.handle, self._off.ctypes.data, self._pool or None, C.byref(h)))
+        else:
+            self._off, self._kind, self._lit_off, self._pool = _pack_templates(replacements, self.n_needles)
+            check(libam().am_subst_table_create_templates(span_table.handle, self._off.ctypes.data, self._kind.ctypes.data, self._lit_off.ctypes.data, self._pool or None,
+                                                          C.byref(h)))
         self._h = h
 
     def __del__(self):

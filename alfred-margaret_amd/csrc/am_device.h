@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "am_image.h"
+#include "am_subst_tpl.h"
 
 namespace am {
 namespace dev {
@@ -230,8 +231,8 @@ hipError_t launch_spans_emit(const uint64_t* cand_g, const uint64_t* best, const
 // in.words (not null) keeps: the bincount of the AM_SPANS_ALL rows of that table.  trace / flush_tiles / n_cu as launch_needle_hist
 hipError_t launch_needle_hist_words(bool ic, const SpansIn& in, uint64_t* counts, uint64_t* trace, uint32_t flush_tiles, int n_cu, hipStream_t st);
 // substitute (am_subst.hip): the leftmost-longest spans of a batch spliced into a new text.  P = 2 * n_span + n_hay pieces: span j of haystack h owns 2j + h (the gap
-// before it) and 2j + h + 1 (its replacement), 2 * span_off[h + 1] + h is the tail of h
-constexpr uint64_t kSubstRepl = 1ull << 63;                 // a piece's source: offset into the replacement pool instead of the batch text
+// before it) and 2j + h + 1 (its replacement), 2 * span_off[h + 1] + h is the tail of h.  kSubstRepl (am_subst_tpl.h) tags a piece's source as an offset into the
+// replacement pool instead of the batch text
 struct SubstIn {
     const Span* spans; uint64_t n_span; const uint64_t* span_off;       // an AM_SPANS_LEFTMOST_LONGEST result of the batch below
     const uint64_t* src_off; uint64_t src_total; uint32_t n_hay, n_needles;
@@ -243,7 +244,14 @@ void subst_geometry(uint32_t* group_bytes, uint32_t* tile_bytes);      // k_subs
 // then the bytes (dst: readable and writable to round_up(total, 16))
 hipError_t launch_subst_pieces(const SubstIn& in, uint64_t* lens, uint64_t* src_at, uint32_t* live, hipStream_t st);
 hipError_t launch_subst_compact(const uint64_t* src_at, const uint32_t* live, const uint64_t* dst_at, const uint64_t* cidx, uint64_t n_pieces, uint64_t* cdst, uint64_t* csrc,
-                                uint64_t n_live, const uint64_t* span_off, uint64_t n_span, uint64_t n_hay, uint64_t* out_off, hipStream_t st);
+                                uint64_t n_live, const uint64_t* span_off, const uint64_t* pbase, uint64_t n_span, uint64_t n_hay, uint64_t* out_off, hipStream_t st);
+// a table of templates (am_subst_tpl.h): cnt[j] = 1 + the segments of span j's template (n_span + 1 entries, the last one 0); with pbase = exclusive sum of cnt
+// (launch_scan) there are P = pbase[n_span] + n_hay pieces, and launch_subst_tpl_pieces writes lens / src_at / live as launch_subst_pieces does for 2 * n_span + n_hay.
+// launch_subst_compact takes pbase for out_off (null: the fixed plan)
+struct SubstTpl { const uint64_t* seg_off; const SubstSeg* segs; uint64_t n_seg; };      // template of handle v: segs[seg_off[v], seg_off[v + 1])
+hipError_t launch_subst_tpl_count(const SubstIn& in, const SubstTpl& tpl, uint32_t* cnt, hipStream_t st);
+hipError_t launch_subst_tpl_pieces(const SubstIn& in, const SubstTpl& tpl, const uint64_t* pbase, uint64_t n_pieces, uint64_t* lens, uint64_t* src_at, uint32_t* live,
+                                   hipStream_t st);
 hipError_t launch_subst_gather(const uint8_t* text, uint64_t src_total, const uint8_t* pool, uint64_t pool_bytes, const uint64_t* cdst, const uint64_t* csrc, uint64_t n_live,
                                uint64_t total, uint8_t* dst, int n_cu, hipStream_t st);
 // a select's predicate over the records (am_records.hip): flags[h] = 1 for every haystack that owns a (record, value < n_needles) pair whose span the table keeps

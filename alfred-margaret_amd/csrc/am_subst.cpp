@@ -1,7 +1,8 @@
 // am_subst.cpp -- substitute on the device (include/am.h "substitute"): the leftmost-longest spans of a batch (am_spans.cpp) spliced with the replacements of their
 // needles into a NEW batch in HBM (am_subst.hip), `replace :: [Match] -> Text -> Text` of the reference (src/Data/Text/AhoCorasick/Replacer.hs:163-180) over matches
 // that are never scanned again.  am_batch_substitute is the splice alone -- to am_spans what am_batch_from_fragments is to am_fragments -- and am_substitute_batch /
-// am_substitute put the spans call in front of it.  Every argument is checked before any device work.
+// am_substitute put the spans call in front of it.  A table of TEMPLATES (am_subst_table_create_templates; csrc/am_subst_tpl.h) is the same table type with another
+// piece plan: the splice counts and numbers its pieces first, everything behind the piece kernel is shared.  Every argument is checked before any device work.
 #include "am_spans.h"
 
 using namespace am;
@@ -14,6 +15,9 @@ struct am_subst_table {
     uint32_t n_needles = 0;
     uint64_t pool_bytes = 0;
     DevBuf off, pool;                                       // uint64[n_needles + 1]; the replacements' bytes, padded: a 16-byte group read from any offset stays inside
+    bool templates = false;                                 // am_subst_table_create_templates: off = seg_off, pool = the literals' bytes, segs = SubstSeg[n_seg]
+    uint64_t n_seg = 0;
+    DevBuf segs;
 };
 
 namespace {
@@ -39,12 +43,27 @@ int splice(const am_batch* src, const struct am_spans* s, const am_subst_table* 
     hipStream_t st; AM_TRY(get_stream(src->dev, &st));
     DerivedBatch nb;
     nb.begin(src->dev);
-    const uint64_t n_span = s->n_items, n_hay = src->n_hay, n_pieces = 2 * n_span + n_hay;
+    const uint64_t n_span = s->n_items, n_hay = src->n_hay;
+    uint64_t n_pieces = 2 * n_span + n_hay;
     SubstIn in;
     in.spans = (const Span*)s->data.p; in.n_span = n_span; in.span_off = (const uint64_t*)s->offsets.p;
     in.src_off = src->d_offsets; in.src_total = src->total; in.n_hay = src->n_hay; in.n_needles = r->n_needles;
     in.repl_off = (const uint64_t*)r->off.p; in.pool_bytes = r->pool_bytes;
-    DevBuf lens, src_at, live, dst_at, cidx, cdst, csrc, scan_tmp;
+    DevBuf lens, src_at, live, dst_at, cidx, cdst, csrc, scan_tmp, cnt, pbase, cnt_tmp;
+    SubstTpl tpl{(const uint64_t*)r->off.p, (const SubstSeg*)r->segs.p, r->n_seg};
+    if (r->templates) {                                     // a span owns 1 + nseg pieces: their exclusive sum numbers them, its total is the one scalar read here
+        AM_TRY(cnt.ensure((n_span + 1) * 4));
+        AM_TRY(pbase.ensure((n_span + 1) * 8));
+        size_t cnt_bytes = 0;
+        HIP_TRY(scan_temp_bytes(n_span + 1, &cnt_bytes));
+        AM_TRY(cnt_tmp.ensure(cnt_bytes));
+        { Prof pr("subst_tpl_count", st);
+          HIP_TRY(launch_subst_tpl_count(in, tpl, (uint32_t*)cnt.p, st));
+          HIP_TRY(launch_scan(cnt_tmp.p, cnt_tmp.cap, (const uint32_t*)cnt.p, (uint64_t*)pbase.p, n_span + 1, st)); }
+        uint64_t owned = 0;
+        AM_TRY(read_u64((const uint64_t*)pbase.p + n_span, &owned, st));
+        n_pieces = owned + n_hay;
+    }
     AM_TRY(lens.ensure((n_pieces + 1) * 8));
     AM_TRY(src_at.ensure((n_pieces + 1) * 8));
     AM_TRY(live.ensure((n_pieces + 1) * 4));
@@ -58,7 +77,8 @@ int splice(const am_batch* src, const struct am_spans* s, const am_subst_table* 
     HIP_TRY(hipMemsetAsync(lens.p, 0, (n_pieces + 1) * 8, st));
     HIP_TRY(hipMemsetAsync(live.p, 0, (n_pieces + 1) * 4, st));
     { Prof pr("subst_pieces", st);
-      HIP_TRY(launch_subst_pieces(in, (uint64_t*)lens.p, (uint64_t*)src_at.p, (uint32_t*)live.p, st)); }
+      if (r->templates) HIP_TRY(launch_subst_tpl_pieces(in, tpl, (const uint64_t*)pbase.p, n_pieces, (uint64_t*)lens.p, (uint64_t*)src_at.p, (uint32_t*)live.p, st));
+      else HIP_TRY(launch_subst_pieces(in, (uint64_t*)lens.p, (uint64_t*)src_at.p, (uint32_t*)live.p, st)); }
     { Prof pr("subst_scan", st);
       HIP_TRY(launch_scan64(scan_tmp.p, scan_tmp.cap, (const uint64_t*)lens.p, (uint64_t*)dst_at.p, n_pieces + 1, st));
       HIP_TRY(launch_scan(scan_tmp.p, scan_tmp.cap, (const uint32_t*)live.p, (uint64_t*)cidx.p, n_pieces + 1, st)); }
@@ -69,7 +89,7 @@ int splice(const am_batch* src, const struct am_spans* s, const am_subst_table* 
     AM_TRY(csrc.ensure((n_live + 1) * 8));
     { Prof pr("subst_compact", st);
       HIP_TRY(launch_subst_compact((const uint64_t*)src_at.p, (const uint32_t*)live.p, (const uint64_t*)dst_at.p, (const uint64_t*)cidx.p, n_pieces, (uint64_t*)cdst.p,
-                                   (uint64_t*)csrc.p, n_live, in.span_off, n_span, n_hay, new_off, st)); }
+                                   (uint64_t*)csrc.p, n_live, in.span_off, r->templates ? (const uint64_t*)pbase.p : nullptr, n_span, n_hay, new_off, st)); }
     AM_TRY(nb.text(total, st, &new_text));
     { Prof pr("subst_gather", st);
       HIP_TRY(launch_subst_gather((const uint8_t*)src->d_text, src->total, (const uint8_t*)r->pool.p, r->pool_bytes, (const uint64_t*)cdst.p, (const uint64_t*)csrc.p, n_live,
@@ -104,6 +124,51 @@ extern "C" int am_subst_table_create(const am_span_table* t, const uint64_t* rep
     HIP_TRY(hipMemset(r->pool.p, 0, padded));
     HIP_TRY(hipMemcpy(r->off.p, repl_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
     if (pool_bytes) HIP_TRY(hipMemcpy(r->pool.p, repl_bytes, (size_t)pool_bytes, hipMemcpyHostToDevice));
+    *out = r.release();
+    return AM_OK;
+}
+
+// a table of templates: off = seg_off, segs = one SubstSeg per segment, pool = the literals' bytes as given (padded as the replacements are)
+extern "C" int am_subst_table_create_templates(const am_span_table* t, const uint64_t* seg_off, const uint8_t* seg_kind, const uint64_t* lit_off, const uint8_t* lit_bytes,
+                                               am_subst_table** out)
+{
+    const std::string fn = "am_subst_table_create_templates: ";
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    if (!t || !seg_off) return fail(AM_ERR_INVALID, "null span table or seg_off");
+    const uint32_t n = t->ids->n_needles;
+    if (seg_off[0] != 0) return fail(AM_ERR_INVALID, fn + "seg_off[0] must be 0");
+    for (uint32_t v = 0; v < n; v++) {
+        if (seg_off[v + 1] < seg_off[v]) return fail(AM_ERR_INVALID, fn + "seg_off descends at needle " + std::to_string(v));
+        if (seg_off[v + 1] - seg_off[v] > AM_SUBST_MAX_SEGMENTS) return fail(AM_ERR_INVALID, fn + "more than AM_SUBST_MAX_SEGMENTS segments (needle " + std::to_string(v) + ")");
+    }
+    const uint64_t n_seg = seg_off[n];
+    if (n_seg && (!seg_kind || !lit_off)) return fail(AM_ERR_INVALID, "seg_kind or lit_off is null");
+    std::vector<SubstSeg> segs((size_t)n_seg);
+    if (n_seg && lit_off[0] != 0) return fail(AM_ERR_INVALID, fn + "lit_off[0] must be 0");
+    for (uint64_t s = 0; s < n_seg; s++) {
+        if (seg_kind[s] != AM_SEG_LITERAL && seg_kind[s] != AM_SEG_MATCH) return fail(AM_ERR_INVALID, fn + "unknown segment kind at segment " + std::to_string(s));
+        if (lit_off[s + 1] < lit_off[s]) return fail(AM_ERR_INVALID, fn + "lit_off descends at segment " + std::to_string(s));
+        const uint64_t len = lit_off[s + 1] - lit_off[s];
+        if (seg_kind[s] == AM_SEG_MATCH && len != 0) return fail(AM_ERR_INVALID, fn + "a MATCH segment with literal bytes (segment " + std::to_string(s) + ")");
+        if (len >= (1ull << 32)) return fail(AM_ERR_INVALID, fn + "a literal of 2^32 bytes and more (segment " + std::to_string(s) + ")");
+        segs[(size_t)s] = seg_kind[s] == AM_SEG_MATCH ? SubstSeg{0, 0, kSegMatch} : SubstSeg{lit_off[s], (uint32_t)len, kSegLiteral};
+    }
+    const uint64_t pool_bytes = n_seg ? lit_off[n_seg] : 0;
+    if (pool_bytes && !lit_bytes) return fail(AM_ERR_INVALID, "lit_bytes is null");
+    AM_TRY(ensure_runtime());
+    const int dev = t->ids->a->dev;
+    ON_DEVICE(dev);
+    std::unique_ptr<am_subst_table> r(new am_subst_table());
+    r->t = t; r->dev = dev; r->n_needles = n; r->pool_bytes = pool_bytes; r->templates = true; r->n_seg = n_seg;
+    const size_t padded = (size_t)((pool_bytes + 15) & ~15ull) + kPoolPad;
+    AM_TRY(r->off.ensure(((size_t)n + 1) * 8));
+    AM_TRY(r->segs.ensure(((size_t)n_seg + 1) * sizeof(SubstSeg)));
+    AM_TRY(r->pool.ensure(padded));
+    HIP_TRY(hipMemset(r->pool.p, 0, padded));
+    HIP_TRY(hipMemcpy(r->off.p, seg_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
+    if (n_seg) HIP_TRY(hipMemcpy(r->segs.p, segs.data(), (size_t)n_seg * sizeof(SubstSeg), hipMemcpyHostToDevice));
+    if (pool_bytes) HIP_TRY(hipMemcpy(r->pool.p, lit_bytes, (size_t)pool_bytes, hipMemcpyHostToDevice));
     *out = r.release();
     return AM_OK;
 }

@@ -10,6 +10,9 @@
 //     a piece that began before the tile is clipped to it), a lane owns one aligned 16-byte store and assembles it from the pieces it covers: per piece up to five
 //     aligned dword loads that touch only dwords holding bytes of the piece, a byte shift (v_alignbyte) and a byte mask.  No byte loop: natural text has a piece end in
 //     nearly every group.
+// A table of TEMPLATES (am_subst_tpl.h) changes the piece plan and nothing else: k_subst_tpl_count gives span j its 1 + nseg pieces, their exclusive sum pbase numbers
+// them (gap pbase[j] + h, segment s pbase[j] + h + 1 + s, tail pbase[span_off[h + 1]] + h, P = pbase[S] + n_hay), k_subst_tpl_pieces writes them -- a literal from the
+// pool, the match itself from the text -- and the scans, k_subst_compact and k_subst_gather run as they are.  A table of plain replacements keeps k_subst_pieces.
 // The bytes written depend on nothing but the piece table: no atomic takes part.  All indices are 64-bit.  Plain C++ and vector stores only.
 #include <hip/hip_runtime.h>
 
@@ -80,11 +83,70 @@ __global__ void __launch_bounds__(kSubstThreads) k_subst_pieces(SubstIn in, uint
     put_piece(lens, src_at, live, n_pieces, 2 * (e1 <= in.n_span ? e1 : in.n_span) + h, ok ? hay_len - last_end : 0, base + last_end);
 }
 
-// lanes [0, n_pieces]: a live piece goes to its place in the compacted table, the last lane writes the sentinel; lanes beyond: out_offsets (n_hay + 1)
+// ---- a table of templates (am_subst_tpl.h): span j owns 1 + nseg[needle_j] pieces, numbered through pbase = the exclusive sum of those counts
+
+// lanes [0, n_span): the pieces span j owns; the last lane: the scan's trailing zero
+__global__ void __launch_bounds__(kSubstThreads) k_subst_tpl_count(SubstIn in, SubstTpl tpl, uint32_t* __restrict__ cnt)
+{
+    const uint64_t i = global_lane();
+    if (i > in.n_span) return;
+    if (i == in.n_span) { cnt[i] = 0; return; }
+    const uint32_t needle = in.spans[i].needle;
+    AM_BOUNDS(needle < in.n_needles);
+    cnt[i] = subst_tpl_count(tpl.seg_off, in.n_needles, needle);
+}
+
+// the lanes of k_subst_pieces with the template's pieces in the place of the replacement: lanes [0, n_span): the gap before a span and one piece per segment of its
+// template; lanes [n_span, n_span + n_hay): the tail of a haystack; the last lane: the scans' trailing zero.  A span that fails the checks of k_subst_pieces (never,
+// for the spans of this batch) leaves all its pieces at length 0, as the caller's memset made them.
+__global__ void __launch_bounds__(kSubstThreads) k_subst_tpl_pieces(SubstIn in, SubstTpl tpl, const uint64_t* __restrict__ pbase, uint64_t n_pieces, uint64_t* __restrict__ lens,
+                                                                    uint64_t* __restrict__ src_at, uint32_t* __restrict__ live)
+{
+    const uint64_t i = global_lane();
+    if (i > in.n_span + in.n_hay) return;
+    if (i == in.n_span + in.n_hay) { lens[n_pieces] = 0; live[n_pieces] = 0; return; }
+    if (i < in.n_span) {
+        const Span sp = in.spans[i];
+        const uint32_t h = sp.haystack;
+        AM_BOUNDS(h < in.n_hay && sp.needle < in.n_needles);
+        if (h >= in.n_hay) return;                                     // (its pieces cannot be named; never, see above)
+        const uint64_t base = in.src_off[h], hay_len = in.src_off[h + 1] - base, first = in.span_off[h];
+        AM_BOUNDS(first <= i && i < in.span_off[h + 1]);
+        uint64_t prev_end = 0;
+        if (i > first) { const Span q = in.spans[i - 1]; prev_end = q.start + q.len; }
+        const bool ok = sp.needle < in.n_needles && sp.start >= prev_end && sp.start + sp.len <= hay_len && base + hay_len <= in.src_total;
+        AM_BOUNDS(ok);
+        const uint64_t p0 = pbase[i];
+        AM_BOUNDS(pbase[i + 1] - p0 == subst_tpl_count(tpl.seg_off, in.n_needles, sp.needle));
+        put_piece(lens, src_at, live, n_pieces, subst_tpl_gap_piece(p0, h), ok ? sp.start - prev_end : 0, base + prev_end);
+        if (!ok) return;
+        uint64_t s0;
+        const uint32_t nseg = subst_tpl_segments(tpl.seg_off, in.n_needles, sp.needle, &s0);
+        AM_BOUNDS(s0 + nseg <= tpl.n_seg);
+        if (s0 + nseg > tpl.n_seg) return;
+        for (uint32_t s = 0; s < nseg; s++) {
+            const SubstPiece pc = subst_tpl_piece(tpl.segs[s0 + s], in.pool_bytes, base + sp.start, sp.len);
+            AM_BOUNDS(tpl.segs[s0 + s].kind == kSegMatch || pc.len == tpl.segs[s0 + s].len);
+            put_piece(lens, src_at, live, n_pieces, subst_tpl_seg_piece(p0, h, s), pc.len, pc.src);
+        }
+        return;
+    }
+    const uint64_t h = i - in.n_span;
+    const uint64_t base = in.src_off[h], hay_len = in.src_off[h + 1] - base, e0 = in.span_off[h], e1 = in.span_off[h + 1];
+    AM_BOUNDS(e0 <= e1 && e1 <= in.n_span);
+    uint64_t last_end = 0;
+    if (e1 > e0 && e1 <= in.n_span) { const Span q = in.spans[e1 - 1]; last_end = q.start + q.len; }
+    const bool ok = last_end <= hay_len && base + hay_len <= in.src_total && e1 <= in.n_span;
+    AM_BOUNDS(ok);
+    put_piece(lens, src_at, live, n_pieces, subst_tpl_gap_piece(pbase[e1 <= in.n_span ? e1 : in.n_span], h), ok ? hay_len - last_end : 0, base + last_end);
+}
+
+// lanes [0, n_pieces]: a live piece goes to its place in the compacted table, the last lane writes the sentinel; lanes beyond: out_offsets (n_hay + 1).  pbase: the
+// piece numbering of a table of templates; null: the fixed plan 2j + h
 __global__ void __launch_bounds__(kSubstThreads) k_subst_compact(const uint64_t* __restrict__ src_at, const uint32_t* __restrict__ live, const uint64_t* __restrict__ dst_at,
                                                                  const uint64_t* __restrict__ cidx, uint64_t n_pieces, uint64_t* __restrict__ cdst, uint64_t* __restrict__ csrc,
-                                                                 uint64_t n_live, const uint64_t* __restrict__ span_off, uint64_t n_span, uint64_t n_hay,
-                                                                 uint64_t* __restrict__ out_off)
+                                                                 uint64_t n_live, const uint64_t* __restrict__ span_off, const uint64_t* __restrict__ pbase, uint64_t n_span,
+                                                                 uint64_t n_hay, uint64_t* __restrict__ out_off)
 {
     const uint64_t i = global_lane();
     if (i <= n_pieces) {
@@ -100,8 +162,9 @@ __global__ void __launch_bounds__(kSubstThreads) k_subst_compact(const uint64_t*
     const uint64_t h = i - n_pieces - 1;
     if (h > n_hay) return;
     const uint64_t e = span_off[h];
-    AM_BOUNDS(e <= n_span && 2 * e + h <= n_pieces);
-    out_off[h] = dst_at[std::min<uint64_t>(2 * std::min<uint64_t>(e, n_span) + h, n_pieces)];
+    const uint64_t ec = std::min<uint64_t>(e, n_span), p = pbase ? subst_tpl_gap_piece(pbase[ec], h) : 2 * ec + h;
+    AM_BOUNDS(e <= n_span && p <= n_pieces);
+    out_off[h] = dst_at[std::min<uint64_t>(p, n_pieces)];
 }
 
 // the largest f in [lo, hi] with off[f] <= x (off ascending, off[lo] <= x)
@@ -206,11 +269,24 @@ hipError_t launch_subst_pieces(const SubstIn& in, uint64_t* lens, uint64_t* src_
     return hipGetLastError();
 }
 
+hipError_t launch_subst_tpl_count(const SubstIn& in, const SubstTpl& tpl, uint32_t* cnt, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_subst_tpl_count, dim3(blocks_for(in.n_span + 1)), dim3(kSubstThreads), 0, st, in, tpl, cnt);
+    return hipGetLastError();
+}
+
+hipError_t launch_subst_tpl_pieces(const SubstIn& in, const SubstTpl& tpl, const uint64_t* pbase, uint64_t n_pieces, uint64_t* lens, uint64_t* src_at, uint32_t* live,
+                                   hipStream_t st)
+{
+    hipLaunchKernelGGL(k_subst_tpl_pieces, dim3(blocks_for(in.n_span + in.n_hay + 1)), dim3(kSubstThreads), 0, st, in, tpl, pbase, n_pieces, lens, src_at, live);
+    return hipGetLastError();
+}
+
 hipError_t launch_subst_compact(const uint64_t* src_at, const uint32_t* live, const uint64_t* dst_at, const uint64_t* cidx, uint64_t n_pieces, uint64_t* cdst, uint64_t* csrc,
-                                uint64_t n_live, const uint64_t* span_off, uint64_t n_span, uint64_t n_hay, uint64_t* out_off, hipStream_t st)
+                                uint64_t n_live, const uint64_t* span_off, const uint64_t* pbase, uint64_t n_span, uint64_t n_hay, uint64_t* out_off, hipStream_t st)
 {
     hipLaunchKernelGGL(k_subst_compact, dim3(blocks_for(n_pieces + 1 + n_hay + 1)), dim3(kSubstThreads), 0, st, src_at, live, dst_at, cidx, n_pieces, cdst, csrc, n_live,
-                       span_off, n_span, n_hay, out_off);
+                       span_off, pbase, n_span, n_hay, out_off);
     return hipGetLastError();
 }
 

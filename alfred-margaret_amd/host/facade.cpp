@@ -309,6 +309,67 @@ int amh_substitute(void* h, int case_mode, const am_slice* hay, size_t n_hay, co
     });
 }
 
+// ---- substitute templates (spans.hpp substituteTemplates): the arrays of am_subst_table_create_templates -- template of handle v = segments [seg_off[v],
+// seg_off[v + 1]), segment s of kind seg_kind[s] with the literal lit_bytes[lit_off[s], lit_off[s + 1]) -- checked as the C ABI checks them
+namespace {
+void templatesOut(const Spans& sp, const std::vector<Text>& texts, size_t n_values, const uint64_t* seg_off, const uint8_t* seg_kind, const uint64_t* lit_off,
+                  const uint8_t* lit_bytes, uint8_t** blob_out, uint64_t* offs_out)
+{
+    if (!seg_off || seg_off[0] != 0) throw AmError(AM_ERR_INVALID, "substitute templates: seg_off is null or does not begin with 0");
+    std::vector<Template> tpl(n_values);
+    for (size_t v = 0; v < n_values; v++) {
+        if (seg_off[v + 1] < seg_off[v] || seg_off[v + 1] - seg_off[v] > AM_SUBST_MAX_SEGMENTS) throw AmError(AM_ERR_INVALID, "substitute templates: seg_off descends or a template has too many segments");
+        for (uint64_t s = seg_off[v]; s < seg_off[v + 1]; s++) {
+            if (!seg_kind || !lit_off || lit_off[s + 1] < lit_off[s]) throw AmError(AM_ERR_INVALID, "substitute templates: seg_kind or lit_off is null, or lit_off descends");
+            const uint64_t len = lit_off[s + 1] - lit_off[s];
+            if (seg_kind[s] == AM_SEG_MATCH && len == 0) { tpl[v].push_back(TemplateSegment{true, std::string()}); continue; }
+            if (seg_kind[s] != AM_SEG_LITERAL || (len && !lit_bytes)) throw AmError(AM_ERR_INVALID, "substitute templates: an unknown kind, a MATCH segment with bytes or no lit_bytes");
+            tpl[v].push_back(TemplateSegment{false, len ? std::string((const char*)lit_bytes + lit_off[s], (size_t)len) : std::string()});
+        }
+    }
+    const std::vector<std::string> res = substituteTemplates(sp, texts, tpl);
+    uint64_t total = 0;
+    for (size_t i = 0; i < res.size(); i++) { offs_out[i] = total; total += res[i].size(); }
+    offs_out[res.size()] = total;
+    uint8_t* blob = (uint8_t*)malloc(total ? total : 1);
+    for (size_t i = 0; i < res.size(); i++) if (!res[i].empty()) std::memcpy(blob + offs_out[i], res[i].data(), res[i].size());
+    *blob_out = blob;
+}
+}  // namespace
+// over fold steps the caller brings (as amh_substitute_fold_words; word_bytes nullable: no class): no device is touched
+int amh_substitute_templates_fold(int case_mode, const uint32_t* hay_in, const uint64_t* pos_in, const uint32_t* val_in, uint64_t n, const am_slice* hay, size_t n_hay,
+                                  const uint32_t* len_bytes, const uint32_t* len_code_points, size_t n_values, const uint64_t* seg_off, const uint8_t* seg_kind,
+                                  const uint64_t* lit_off, const uint8_t* lit_bytes, const uint8_t* word_bytes, uint8_t** blob_out, uint64_t* offs_out)
+{
+    *blob_out = nullptr;
+    return guarded([&] {
+        if (case_mode != AM_CASE_SENSITIVE && case_mode != AM_IGNORE_CASE) throw AmError(AM_ERR_INVALID, "amh_substitute_templates_fold: bad case_mode");
+        std::vector<FoldStep> steps((size_t)n);
+        for (uint64_t i = 0; i < n; i++) steps[i] = FoldStep{hay_in[i], pos_in[i], val_in[i]};
+        const std::vector<uint32_t> lb(len_bytes, len_bytes + n_values), lc(len_code_points, len_code_points + n_values);
+        const std::vector<Text> texts = sliceTexts(hay, n_hay);
+        templatesOut(spansFold((CaseSensitivity)case_mode, true, steps, texts, lb, lc, word_bytes), texts, n_values, seg_off, seg_kind, lit_off, lit_bytes, blob_out, offs_out);
+    });
+}
+// amh_run_list's fold (the scan on the device, the fold on the host), then spansFold and substituteTemplates
+int amh_substitute_templates(void* h, int case_mode, const am_slice* hay, size_t n_hay, const uint32_t* len_bytes, const uint32_t* len_code_points, size_t n_values,
+                             const uint64_t* seg_off, const uint8_t* seg_kind, const uint64_t* lit_off, const uint8_t* lit_bytes, uint8_t** blob_out, uint64_t* offs_out)
+{
+    *blob_out = nullptr;
+    return guarded([&] {
+        if (case_mode != AM_CASE_SENSITIVE && case_mode != AM_IGNORE_CASE) throw AmError(AM_ERR_INVALID, "amh_substitute_templates: bad case_mode");
+        struct Acc { std::vector<std::pair<uint64_t, uint32_t>> v; };
+        auto f = [](Acc a, const Match<uint32_t>& m) { a.v.emplace_back(m.matchPos, m.matchValue); return Next<Acc>::Step(std::move(a)); };
+        const std::vector<Text> texts = sliceTexts(hay, n_hay);
+        auto accs = runBatchWithCase((CaseSensitivity)case_mode, Acc{}, f, static_cast<MachineBox*>(h)->m, texts);
+        std::vector<FoldStep> steps;
+        for (size_t i = 0; i < accs.size(); i++)
+            for (auto& pv : accs[i].v) steps.push_back(FoldStep{(uint32_t)i, pv.first, pv.second});
+        const std::vector<uint32_t> lb(len_bytes, len_bytes + n_values), lc(len_code_points, len_code_points + n_values);
+        templatesOut(spansFold((CaseSensitivity)case_mode, true, steps, texts, lb, lc), texts, n_values, seg_off, seg_kind, lit_off, lit_bytes, blob_out, offs_out);
+    });
+}
+
 // ---- Searcher
 int amh_searcher_build(int case_mode, const uint8_t* bytes, const uint64_t* offs, size_t n, void** out)
 {

@@ -108,6 +108,36 @@ inline std::vector<std::string> substitute(CaseSensitivity cs, const std::vector
     return substitute(spansFold(cs, true, steps, texts, lenBytes, lenCodePoints, wordBytes), texts, replacements);
 }
 
+// substitute templates (include/am.h "substitute templates"): the same splice with T(v, m) in the place of repl[v] -- the segments of template v in order, a literal's
+// bytes or the matched bytes m themselves.  The sequential definition: a plain loop, on purpose not built on the piece arithmetic the kernels use.
+struct TemplateSegment { bool match; std::string literal; };            // match: the span's own bytes (the literal is not looked at)
+using Template = std::vector<TemplateSegment>;
+
+inline std::vector<std::string> substituteTemplates(const Spans& spans, const std::vector<Text>& texts, const std::vector<Template>& templates)
+{
+    if (spans.offsets.size() != texts.size() + 1) throw AmError(AM_ERR_INVALID, "substituteTemplates: the spans are not those of these texts");
+    std::vector<std::string> out(texts.size());
+    for (size_t h = 0; h < texts.size(); h++) {
+        const Text& hay = texts[h];
+        const char* bytes = reinterpret_cast<const char*>(hay.begin());
+        std::string& o = out[h];
+        uint64_t cursor = 0;
+        for (uint64_t k = spans.offsets[h]; k < spans.offsets[h + 1]; k++) {
+            const am_span& s = spans.spans.at((size_t)k);
+            if (s.start < cursor || s.start + s.len > hay.len || s.needle >= templates.size())
+                throw AmError(AM_ERR_INVALID, "substituteTemplates: a span overlaps the one before it, leaves its haystack or has no template");
+            if (s.start > cursor) o.append(bytes + cursor, (size_t)(s.start - cursor));
+            for (const TemplateSegment& g : templates[s.needle]) {
+                if (g.match) { if (s.len) o.append(bytes + s.start, (size_t)s.len); }
+                else o.append(g.literal);
+            }
+            cursor = s.start + s.len;
+        }
+        if (hay.len > cursor) o.append(bytes + cursor, (size_t)(hay.len - cursor));
+    }
+    return out;
+}
+
 // extract (include/am.h "extract"): every span with up to `before` code points of its haystack in front of it and up to `after` behind it, as fragments of the
 // haystack; one per span, or -- merged -- the union of the windows per haystack as disjoint ascending pieces.  The sequential definition, a byte at a time.
 struct Extracted {

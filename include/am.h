@@ -382,6 +382,35 @@ AM_API const void* am_batch_device_offsets(const am_batch* b);
 AM_API int am_batch_read_offsets(const am_batch* b, uint64_t* out /* n_hay + 1, host */);
 AM_API int am_batch_read_text(const am_batch* b, uint64_t first_byte, uint64_t n_bytes, uint8_t* dst);
 
+/* ---- substitute templates: the replacement may keep, wrap or repeat the MATCHED TEXT itself, in HBM ---------------
+ * What sed writes as &, re.sub as \g<0> and others as $0.  A TEMPLATE is a sequence of 0 .. AM_SUBST_MAX_SEGMENTS segments, each AM_SEG_LITERAL (bytes) or
+ * AM_SEG_MATCH (the bytes of the span itself, as they stand in the haystack).  For haystack i with the AM_SPANS_LEFTMOST_LONGEST rows (s_1, l_1, v_1) ... (s_k, l_k, v_k):
+ *   out_i = hay[0, s_1) ++ T(v_1, hay[s_1, s_1 + l_1)) ++ hay[s_1 + l_1, s_2) ++ ... ++ T(v_k, hay[s_k, s_k + l_k)) ++ hay[s_k + l_k, len_i)
+ *   T(v, m) = the segments of template v in order: a literal's bytes, or m for AM_SEG_MATCH
+ * Everything "substitute" says above holds: nothing of the output is scanned again, zero-length spans are never selected, handles >= n_needles never appear, every
+ * index is 64-bit and the bytes depend on no order.  A template of NO segments deletes the match; [MATCH] is the identity (bytes and offsets of the input); [literal]
+ * is am_subst_table_create's replacement; MATCH may occur several times.  Under AM_IGNORE_CASE the match keeps THE TEXT'S OWN SPELLING and width, which no fixed
+ * replacement can: a k matched by U+212A puts three bytes where MATCH stands.  A span table with a word class gives whole-word templates (the splice reads spans and
+ * needs no class of its own).
+ *   nike -> [<b>, MATCH, </b>] under AM_IGNORE_CASE over "NIKE nike":  "<b>NIKE</b> <b>nike</b>"
+ *   ab   -> [MATCH, MATCH]  (sed's &&)                  over "xabx":       "xababx"
+ * The table is the same am_subst_table: am_batch_substitute, am_substitute_batch, am_substitute and am_subst_table_destroy take it unchanged, and the result is a
+ * batch as theirs.  On the device only the PIECE PLAN differs (csrc/am_subst_tpl.h, one definition for the kernels and the CPU): span j of haystack h owns
+ * 1 + nseg[v_j] pieces -- its gap, then one piece per segment, a literal read from the pool, a MATCH read from the text -- numbered through the exclusive sum of
+ * those counts; the two piece scans, the compaction and the gather are those of "substitute".  WORKSPACE as there, per piece, plus 12 bytes per span.  A table made
+ * by am_subst_table_create keeps its fixed plan of two pieces per span and its kernel.
+ *   am_subst_table_create_templates  template of handle v = segments [seg_off[v], seg_off[v + 1]) (seg_off: n_needles + 1 entries); segment s has kind seg_kind[s]
+ *                           and, as a literal, the bytes lit_bytes[lit_off[s], lit_off[s + 1]) (lit_off: n_seg + 1 entries, a MATCH segment has an empty range).
+ *                           Host memory, copied; the pool keeps its padding.  `t` must outlive the table.  AM_ERR_INVALID and *out NULL, before any device work, for
+ *                           a null pointer where bytes are needed (seg_kind and lit_off may be null without segments, lit_bytes without literal bytes), seg_off[0] != 0
+ *                           or a descending seg_off, more than AM_SUBST_MAX_SEGMENTS segments in one template, an unknown kind, lit_off[0] != 0, a descending lit_off,
+ *                           a non-empty range on a MATCH segment, a literal of 2^32 bytes and more. */
+#define AM_SUBST_MAX_SEGMENTS 64
+#define AM_SEG_LITERAL 0
+#define AM_SEG_MATCH 1
+AM_API int am_subst_table_create_templates(const am_span_table* t, const uint64_t* seg_off /* n_needles + 1, host */, const uint8_t* seg_kind /* n_seg */,
+                                           const uint64_t* lit_off /* n_seg + 1 */, const uint8_t* lit_bytes, am_subst_table** out);
+
 /* ---- whole words: a span table with a word class -- spans, substitute and term counts over the whole-word matches only, in HBM ---------------
  * A WORD CLASS W is a set of byte values, given as 256 flags (non-zero = word byte).  A span (start, len) of a haystack of L bytes is a WHOLE WORD iff both hold:
  *   start == 0        or  hay[start - 1]    is not in W
