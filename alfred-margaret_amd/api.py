@@ -2226,6 +2226,15 @@ def sf_last_variant():
     return decode_sf_variant(libam().am_debug_sf_last_variant())
 
 
+SF_VARIANT_W2 = 1 << 10
+
+
+def sf_last_variant_w2():
+    """One read of am_debug_sf_last_variant as (decode_sf_variant's dict, W2): W2 = the launch filtered with the derived two-word filter (bit 10, which the dict leaves out)."""
+    word = int(libam().am_debug_sf_last_variant())
+    return decode_sf_variant(word), bool(word & SF_VARIANT_W2)
+
+
 def bounds_report():
     """(failed index assertions, line of the first, translation units that carry assertions) of a -DAM_BOUNDS_CHECK build; (0, 0, 0) in the product build."""
     f, l, u = C.c_uint64(0), C.c_uint32(0), C.c_uint32(0)

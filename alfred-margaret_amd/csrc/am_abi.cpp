@@ -270,6 +270,26 @@ ThreadState::~ThreadState()
 
 uint64_t am::host::next_image_generation() { static std::atomic<uint64_t> g{0}; return g.fetch_add(1, std::memory_order_relaxed) + 1u; }
 
+int am::host::attach_scan2(Flavor& f, const void* host_image)
+{
+    if (!scan2_wanted(f.h)) return AM_OK;
+    std::vector<uint32_t> words;
+    if (host_image) scan2_derive(f.h, (const uint8_t*)host_image + f.h.off_t4_slots, words);
+    else {
+        std::vector<SfSlot> slots((size_t)2 << f.h.tier_log2_cap[3]);
+        HIP_TRY(hipMemcpy(slots.data(), (const uint8_t*)f.d_image + f.h.off_t4_slots, slots.size() * sizeof(SfSlot), hipMemcpyDeviceToHost));
+        scan2_derive(f.h, slots.data(), words);
+    }
+    if (words.empty()) return AM_OK;
+    void* d = nullptr;
+    hipError_t e = hipMalloc(&d, words.size() * 4);
+    if (e != hipSuccess) return fail(AM_ERR_OOM, std::string("hipMalloc(two-word filter): ") + hipGetErrorString(e));
+    e = hipMemcpy(d, words.data(), words.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d); return fail(AM_ERR_HIP, std::string("hipMemcpy(two-word filter): ") + hipGetErrorString(e)); }
+    f.d_scan2 = d;
+    return AM_OK;
+}
+
 int am::host::prepare(const am_automaton* ca, int case_mode, const Flavor** out)
 {
     if (!ca) return fail(AM_ERR_INVALID, "null automaton");
@@ -298,7 +318,9 @@ int am::host::prepare(const am_automaton* ca, int case_mode, const Flavor** out)
         e = hipMemcpy(d, img.data(), img.size(), hipMemcpyHostToDevice);
         if (e != hipSuccess) { (void)hipFree(d); return fail(AM_ERR_HIP, std::string("hipMemcpy(image): ") + hipGetErrorString(e)); }
         std::memcpy(&f.h, img.data(), sizeof(ImageHeader));
-        f.d_image = d; f.bytes = img.size(); f.generation = next_image_generation(); f.ready = true;
+        f.d_image = d;
+        if (int rc = attach_scan2(f, img.data())) { (void)hipFree(d); f.d_image = nullptr; return rc; }
+        f.bytes = img.size(); f.generation = next_image_generation(); f.ready = true;
     }
     *out = &f;
     return AM_OK;
@@ -380,7 +402,7 @@ extern "C" void am_automaton_destroy(am_automaton* a)
 {
     if (!a) return;
     if (a->ic_pending.valid()) a->ic_pending.wait();                      // (the flatten thread reads the handle's arrays)
-    for (Flavor& f : a->fl) if (f.d_image) (void)hipFree(f.d_image);      // hipFree finds the owning device itself
+    for (Flavor& f : a->fl) { if (f.d_image) (void)hipFree(f.d_image); if (f.d_scan2) (void)hipFree(f.d_scan2); }      // hipFree finds the owning device itself
     delete a;
 }
 
@@ -423,11 +445,13 @@ extern "C" int am_automaton_from_image(const void* d_image, size_t nbytes, am_au
     HIP_TRY(hipMalloc(&d, h.total_bytes));
     hipError_t e = hipMemcpy(d, d_image, h.total_bytes, hipMemcpyDeviceToDevice);
     if (e != hipSuccess) { (void)hipFree(d); return fail(AM_ERR_HIP, hipGetErrorString(e)); }
-    am_automaton* a = new am_automaton();
+    std::unique_ptr<am_automaton> a(new am_automaton());
     a->dev = dev;
     Flavor& f = a->fl[h.case_mode];
-    f.h = h; f.d_image = d; f.bytes = h.total_bytes; f.generation = next_image_generation(); f.ready = true;
-    *out = a;
+    f.h = h; f.d_image = d;
+    if (int rc = attach_scan2(f, nullptr)) { (void)hipFree(d); return rc; }
+    f.bytes = h.total_bytes; f.generation = next_image_generation(); f.ready = true;
+    *out = a.release();
     return AM_OK;
 }
 
@@ -467,11 +491,13 @@ extern "C" int am_automaton_from_host_image(const void* image, size_t nbytes, am
     HIP_TRY(hipMalloc(&d, h.total_bytes));
     hipError_t e = hipMemcpy(d, image, h.total_bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(d); return fail(AM_ERR_HIP, hipGetErrorString(e)); }
-    am_automaton* a = new am_automaton();
+    std::unique_ptr<am_automaton> a(new am_automaton());
     a->dev = dev;
     Flavor& f = a->fl[h.case_mode];
-    f.h = h; f.d_image = d; f.bytes = h.total_bytes; f.generation = next_image_generation(); f.ready = true;
-    *out = a;
+    f.h = h; f.d_image = d;
+    if (int rc = attach_scan2(f, image)) { (void)hipFree(d); return rc; }
+    f.bytes = h.total_bytes; f.generation = next_image_generation(); f.ready = true;
+    *out = a.release();
     return AM_OK;
 }
 

@@ -67,7 +67,8 @@ uint32_t sf_unit_chunks(const BatchView& b, int n_cu);
 hipError_t launch_permute(const ScanOut& o, const uint64_t* unit_offsets, Record* out, uint64_t n_units, hipStream_t st);
 uint64_t ac_units(const AcView& a, const BatchView& b);
 size_t sf_lds_bytes(const SfView& s);
-hipError_t launch_sf(bool ic, int mode, const SfView& s, const BatchView& b, const ScanOut& o, int n_cu, hipStream_t st);
+// scan2: the image's derived two-word filter on the device (am_image.h scan2_mask), or null; the launches that can filter with it get it as their SfView::scan_bloom
+hipError_t launch_sf(bool ic, int mode, const SfView& s, const BatchView& b, const ScanOut& o, int n_cu, hipStream_t st, const uint32_t* scan2 = nullptr);
 uint32_t take_sf_last_variant();      // the k_sf instantiation launch_sf launched last in this process (am_debug_sf_last_variant's word), cleared by the read; 0: none since
 hipError_t launch_ac(bool ic, int mode, const AcView& a, const BatchView& b, const ScanOut& o, hipStream_t st);
 // table-walk kernel (am_dfa.hip): same two-pass protocol as the general kernel (count -> scan -> emit), unit = one lane's DfaView::chunk bytes

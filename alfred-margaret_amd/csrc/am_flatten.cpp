@@ -1460,4 +1460,49 @@ bool image_sections_in_bounds(const ImageHeader& h)
     return good;
 }
 
+bool scan2_wanted(const ImageHeader& h)
+{
+    return h.sf_enabled && h.sf_bloom_log2_words == kScan2Log2Words && (h.sf_tiers & 7u) == 0u && (h.sf_tiers & 8u) != 0u;
+}
+
+void scan2_derive(const ImageHeader& h, const void* slots, std::vector<uint32_t>& words)
+{
+    words.clear();
+    if (!scan2_wanted(h)) return;
+    const bool ic = h.case_mode == 1;
+    const size_t n_slots = (size_t)2 << h.tier_log2_cap[3];
+    std::vector<uint32_t> keys;
+    for (size_t i = 0; i < n_slots; i++) {
+        uint32_t kf[2];                                       // SfSlot::key, SfSlot::flags
+        std::memcpy(kf, (const uint8_t*)slots + i * sizeof(SfSlot) + offsetof(SfSlot, key), sizeof(kf));
+        if (kf[1] & kSlotOccupied) keys.push_back(bloom_key(kf[0], ic));
+    }
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    if (keys.size() <= kScan2MinKeys) return;
+    words.assign((size_t)1 << kScan2Log2Words, 0u);
+    for (const uint32_t key : keys) {
+        const uint32_t hh = bloom_hash(key, 4), m = scan2_mask(hh);
+        words[bloom_word(hh, kScan2Log2Words)] |= m; words[scan2_word2(hh)] |= m;
+    }
+}
+
 }  // namespace am
+
+// For the tests: the two-word scan filter of a flattened image on the host, by the routine the upload paths use.  Returns the words written (1 << kScan2Log2Words), 0 when
+// the rule does not apply to the image, -1 for a blob that is no image or a destination that is too small.  libam_imgcheck.so (tests/native) exports it; in libam.so
+// the version script keeps it local.
+extern "C" long long amflat_scan2_filter(const void* image, size_t nbytes, uint32_t* out, size_t cap_words)
+{
+    using namespace am;
+    ImageHeader h;
+    if (!image || nbytes < sizeof(h)) return -1;
+    std::memcpy(&h, image, sizeof(h));
+    if (!image_sections_in_bounds(h) || h.total_bytes > nbytes) return -1;
+    std::vector<uint32_t> words;
+    scan2_derive(h, (const uint8_t*)image + h.off_t4_slots, words);
+    if (words.empty()) return 0;
+    if (!out || cap_words < words.size()) return -1;
+    std::memcpy(out, words.data(), words.size() * 4);
+    return (long long)words.size();
+}

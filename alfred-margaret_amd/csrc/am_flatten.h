@@ -42,6 +42,12 @@ bool image_sections_in_bounds(const ImageHeader& h);
 // every index inside the body stays inside its table (images that come from a file)
 bool image_body_valid(const uint8_t* image, const ImageHeader& h, std::string& err);
 
+// The two-word scan filter of an image (am_image.h scan2_mask): does the rule apply to this header at all (a 2^15-word filter, no needles shorter than 4 bytes)?
+bool scan2_wanted(const ImageHeader& h);
+// ... and its words, from the image's cold tier-4 slots (2 << tier_log2_cap[3] lines of sizeof(SfSlot) bytes at `slots`, which need not be aligned: a caller's
+// buffer may hold the image): 2^15 words, or none when the slots hold at most kScan2MinKeys distinct filter keys.  One routine for every way an image reaches a device.
+void scan2_derive(const ImageHeader& h, const void* slots, std::vector<uint32_t>& words);
+
 uint32_t simple_lower(uint32_t cp);
 void unlower(uint32_t cp, std::vector<uint32_t>& out);
 

@@ -138,8 +138,12 @@ struct Flavor {
     size_t bytes = 0;
     uint64_t generation = 0;     // unique per uploaded image (an address can be reused): what a batch remembers its route by
     ImageHeader h;
+    void* d_scan2 = nullptr;     // the two-word scan filter derived from the image's keys (am_image.h scan2_mask), beside the image; null: the rule does not apply
 };
 uint64_t next_image_generation();
+// The image of `f` is on the current device: derive its two-word scan filter (scan2_derive) and put it there too.  host_image: the image's bytes where the caller
+// has them, else null (the cold slots are read back from the device).
+int attach_scan2(Flavor& f, const void* host_image);
 
 }  // namespace host
 }  // namespace am

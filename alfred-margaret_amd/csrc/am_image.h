@@ -317,13 +317,14 @@ AM_HD uint32_t bloom_tier_key(uint32_t key, uint32_t tier, bool ignore_case) { r
 AM_HD uint32_t bloom_hash(uint32_t key, uint32_t tier) { return (key + (4u - tier) * 0x7F4A7C15u) * kBloomMul; }
 AM_HD uint32_t bloom_word(uint32_t h, uint32_t log2_words) { return h >> (32u - log2_words); }
 AM_HD uint32_t bloom_mask_index(uint32_t h) { return (h >> 2) & (kBloomMasks - 1u); }
-// mask i of the table: four distinct bits chosen by a mix of i (the kernel fills its LDS copy with this at start-up)
-AM_HD uint32_t bloom_mask_entry(uint32_t i)
+// mask i of the table: four distinct bits chosen by a mix of i (the kernel fills its LDS copy with this at start-up); nbits < 4: the first nbits of them (the
+// two-word scan filter's entries, scan2_mask below)
+AM_HD uint32_t bloom_mask_entry(uint32_t i, uint32_t nbits = 4u)
 {
     uint32_t x = (i + 1u) * 0x9E3779B1u;
     x ^= x >> 15; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
     uint32_t m = 0;
-    for (uint32_t k = 0; k < 4u; k++) {
+    for (uint32_t k = 0; k < nbits; k++) {
         uint32_t b = (x >> (5u * k)) & 31u;
         while (m & (1u << b)) b = (b + 1u) & 31u;
         m |= 1u << b;
@@ -345,6 +346,18 @@ AM_HD uint32_t rotr32(uint32_t m, uint32_t r) { return (m >> r) | (m << ((32u - 
 AM_HD uint32_t scan_rot(uint32_t h) { return (h >> kScanRotShift) & 31u; }
 AM_HD uint32_t scan_mask(uint32_t h, const uint32_t* tab = nullptr) { return rotr32(bloom_mask(h, tab), scan_rot(h)); }
 AM_HD bool scan_hit(uint32_t v, uint32_t h, const uint32_t* tab = nullptr) { const uint32_t m = scan_mask(h, tab); return (v & m) == m; }
+// The TWO-WORD scan filter: DERIVED data, not part of the image.  Where the 2^15-word filter is overloaded -- more than three keys per word -- a key sets a
+// THREE-bit rotated mask (its table entry without the bit placed last, bloom_mask_entry(i, 3)) in TWO words: the scan filter's word a1 = h >> 17 and
+// a2 = a1 ^ h[16:2], and a window passes iff both words hold its mask.  a2 costs one AND and one XOR on the byte address and no second multiply; counted on the CPU
+// (tools/experiments/filter_two_words.py) it passes 49.8 positions per KiB of the 100k-needle workload's text where an independent second multiply passes 49.2 and
+// the one-word filter 62.5.  Built from the image's own tier-4 keys when an image is put on a device (scan2_derive, am_flatten.cpp); k_sf's W2 instantiations read
+// it in place of the section at off_scan_bloom.  Only for images without needles shorter than 4 bytes: the tier tests read the same words under the 4-bit masks.
+constexpr uint32_t kScan2Bits = 3u;
+constexpr uint32_t kScan2Log2Words = 15u;
+constexpr uint32_t kScan2MinKeys = 3u << kScan2Log2Words;      // the rule holds for MORE distinct filter keys than this (below, the extra reads cost more than they save)
+AM_HD uint32_t scan2_word2(uint32_t h) { return (h >> (32u - kScan2Log2Words)) ^ ((h >> 2) & ((1u << kScan2Log2Words) - 1u)); }
+AM_HD uint32_t scan2_mask(uint32_t h) { return rotr32(bloom_mask_entry(bloom_mask_index(h), kScan2Bits), scan_rot(h)); }
+AM_HD bool scan2_hit(const uint32_t* f, uint32_t h) { const uint32_t m = scan2_mask(h); return (f[bloom_word(h, kScan2Log2Words)] & f[scan2_word2(h)] & m) == m; }
 
 AM_HD uint32_t tier_slot(uint32_t key, uint32_t log2_cap) { return (key * 0x85EBCA6Bu) >> (32u - log2_cap); }
 

@@ -94,7 +94,14 @@ constexpr uint32_t kSfMaskBytes = kBloomMasks * 4u;      // the Bloom mask table
 // reads an SGPR or needs the VOP3 encoding on gfx950, tools/microbench/valu_rates*.hip); 0 = any size
 // DBG: the phase timing (AM_SF_TRACE) lives in its own instantiations, the production kernel carries none of its
 // code, registers or branches.
-template <bool IC, int MODE, int ILP, int LW, bool SHORT, bool DBG, int NT = kSfThreads, bool CHILDREN = false>
+// W2: the filter is the derived TWO-WORD one (scan2_mask, am_image.h: the launcher points SfView::scan_bloom at it): 3-bit table entries, and a position passes iff its
+// rotated mask is set in both of its words -- a third LDS read, one AND and one XOR for the second address, one more AND in the test.  For <LW 15, no short
+// needles> only; launch_sf_t picks it exactly when the image has the derived filter.
+// W2: positions whose LDS reads (three each) are all in flight before the first is tested -- 8: two halves of the lane's 16 (lgkmcnt counts to 15: with all 48
+// reads out the first test waits for 33 of them).  Measured with ILP (kSfW2Ilp), three runs each, cfg3 / cfg4 GiB/s, parent 1123 / 1129:
+//   16, ILP 2: 1163 / 1167     8, ILP 2: 1161 / 1164     16, ILP 1: 1166 / 1169     8, ILP 1: 1185 / 1189
+constexpr int kSfW2Group = 8;
+template <bool IC, int MODE, int ILP, int LW, bool SHORT, bool DBG, int NT = kSfThreads, bool CHILDREN = false, bool W2 = false>
 __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uint64_t n_chunks)
 {
     constexpr int kSfThreads = NT, kSfWaves = NT / 64;      // (shadow the namespace constants: the body is written against these names)
@@ -116,8 +123,9 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
     uint16_t* q1_all = reinterpret_cast<uint16_t*>(stage_all + kSfWaves * kSfStage);
     uint16_t* q2_all = q1_all + kSfWaves * kSfQ1;
 
-    for (uint32_t i = threadIdx.x; i < kBloomMasks; i += kSfThreads) masks[i] = bloom_mask_entry(i);
-    for (uint32_t i = threadIdx.x; i < words; i += kSfThreads) bloom[i] = s.scan_bloom[i];      // the scan filter: rotated masks (scan_mask, am_image.h)
+    static_assert(!W2 || (LW == (int)kScan2Log2Words && !SHORT && !CHILDREN), "the two-word filter is for 2^15 words without tier probes");
+    for (uint32_t i = threadIdx.x; i < kBloomMasks; i += kSfThreads) masks[i] = W2 ? bloom_mask_entry(i, kScan2Bits) : bloom_mask_entry(i);
+    for (uint32_t i = threadIdx.x; i < words; i += kSfThreads) bloom[i] = s.scan_bloom[i];      // the scan filter: rotated masks (scan_mask, am_image.h); W2: the derived two-word filter
     __syncthreads();
 
     const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // uniform: unit / chunk arithmetic stays scalar
@@ -666,7 +674,8 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
                 // position) are all in flight before the first one is tested.  They go out in the order the tests consume them, 15 .. 0 (DS
                 // operations return in order: the first test waits with lgkmcnt(14) -- for its own two reads and 16 more; the counter's field ends at 15 -- where it waited
                 // for 30 of the 32 reads), and the scheduling barrier keeps the compiler from spreading the reads among the tests (measured both ways, LABNOTES
-                // "k_sf chunk loop").
+                // "k_sf chunk loop").  W2 (the two-word filter): three reads per position -- both filter words and the mask --, 48 per lane, which go out in two
+                // halves of 24, each half tested before the next is read (kSfW2Group).
                 uint32_t h[16], v[16], m[16];
                 const uint32_t sh_word = 32u - log2_words;
 #pragma unroll
@@ -675,17 +684,40 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
                     const uint32_t w = sh == 3 ? f[j + 1] : __builtin_amdgcn_alignbyte(f[j + 1], f[j], sh + 1);
                     h[k] = w * kBloomMul;
                 }
+                if constexpr (W2) {
+                    // both words of a position and its mask: a2's byte address = a1's ^ (h[16:2] << 2) (scan2_word2); bit k of cand = position k, as below
+                    constexpr uint32_t kWordBytes = ((1u << kScan2Log2Words) - 1u) << 2;
+                    uint32_t v2[16];
 #pragma unroll
-                for (int k = 15; k >= 0; k--) {
-                    if (LW) v[k] = lds_read_u32(kSfMaskBytes + ((h[k] >> (30 - LW)) & (((1u << LW) - 1u) << 2)));
-                    else v[k] = lds_read_u32(kSfMaskBytes + ((h[k] >> sh_word) << 2));
-                    m[k] = lds_read_u32(h[k] & ((kBloomMasks - 1u) << 2));
-                }
-                __builtin_amdgcn_sched_barrier(0);
+                    for (int g = 16 - kSfW2Group; g >= 0; g -= kSfW2Group) {
 #pragma unroll
-                for (int k = 15; k >= 0; k--) {      // bit k of cand = position k (the first one shifted in ends up on top); the table mask rotated by product bits 11..15 (scan_mask)
-                    const uint32_t mr = rotr32(m[k], scan_rot(h[k]));
-                    cand = shift_in_eq(cand, v[k] & mr, mr);      // (cand << 1) | ((v[k] & mr) == mr)
+                        for (int k = g + kSfW2Group - 1; k >= g; k--) {
+                            const uint32_t a1 = (h[k] >> (30 - LW)) & kWordBytes;
+                            v[k] = lds_read_u32(kSfMaskBytes + a1);
+                            v2[k] = lds_read_u32(kSfMaskBytes + (a1 ^ (h[k] & kWordBytes)));
+                            m[k] = lds_read_u32(h[k] & ((kBloomMasks - 1u) << 2));
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int k = g + kSfW2Group - 1; k >= g; k--) {
+                            const uint32_t mr = rotr32(m[k], scan_rot(h[k]));
+                            cand = shift_in_eq(cand, v[k] & v2[k] & mr, mr);
+                        }
+                        if (g) __builtin_amdgcn_sched_barrier(0);
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 15; k >= 0; k--) {
+                        if (LW) v[k] = lds_read_u32(kSfMaskBytes + ((h[k] >> (30 - LW)) & (((1u << LW) - 1u) << 2)));
+                        else v[k] = lds_read_u32(kSfMaskBytes + ((h[k] >> sh_word) << 2));
+                        m[k] = lds_read_u32(h[k] & ((kBloomMasks - 1u) << 2));
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int k = 15; k >= 0; k--) {      // bit k of cand = position k (the first one shifted in ends up on top); the table mask rotated by product bits 11..15 (scan_mask)
+                        const uint32_t mr = rotr32(m[k], scan_rot(h[k]));
+                        cand = shift_in_eq(cand, v[k] & mr, mr);      // (cand << 1) | ((v[k] & mr) == mr)
+                    }
                 }
             }
             if (SHORT && (!kFlagMode || !skip)) {    // automata with 1..3-byte needles: extra probes per position
@@ -926,11 +958,11 @@ size_t sf_lds_bytes(const SfView& s) { return sf_lds_bytes_w(s, kSfWaves); }
 // The template arguments of the calling process's last k_sf launch (am_debug_sf_last_variant, include/am_debug.h: the tests of launch_sf_t's choice read it);
 // 0 = none since the last read.
 constexpr uint32_t kSfVariantValid = 1u, kSfVariantIc = 2u, kSfVariantModeShift = 2, kSfVariantIlpShift = 4, kSfVariantShort = 1u << 6, kSfVariantDbg = 1u << 7,
-                   kSfVariantLight = 1u << 8, kSfVariantChildren = 1u << 9, kSfVariantLwShift = 16;
+                   kSfVariantLight = 1u << 8, kSfVariantChildren = 1u << 9, kSfVariantW2 = 1u << 10, kSfVariantLwShift = 16;
 static std::atomic<uint32_t> g_sf_last_variant{0};
 uint32_t take_sf_last_variant() { return g_sf_last_variant.exchange(0, std::memory_order_relaxed); }
 
-template <bool IC, int MODE, int ILP, int LW, bool SHORT, bool DBG = false, int NT = kSfThreads, bool CHILDREN = false>
+template <bool IC, int MODE, int ILP, int LW, bool SHORT, bool DBG = false, int NT = kSfThreads, bool CHILDREN = false, bool W2 = false>
 static hipError_t launch_sf_v(const SfView& s, const BatchView& b, const ScanOut& o, int n_cu, hipStream_t st)
 {
     constexpr int waves_per_wg = NT / 64;
@@ -940,7 +972,7 @@ static hipError_t launch_sf_v(const SfView& s, const BatchView& b, const ScanOut
     static bool attr_set = false;     // per instantiation
     if (!attr_set) {
         // allow the full 160 KiB of a CU's LDS as dynamic shared memory (not fatal if the runtime objects)
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sf<IC, MODE, ILP, LW, SHORT, DBG, NT, CHILDREN>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sf<IC, MODE, ILP, LW, SHORT, DBG, NT, CHILDREN, W2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
             (void)hipGetLastError();
         attr_set = true;
     }
@@ -952,7 +984,7 @@ static hipError_t launch_sf_v(const SfView& s, const BatchView& b, const ScanOut
     if (blocks > need) blocks = need;
     if (blocks == 0) return hipSuccess;
     g_sf_last_variant.store(kSfVariantValid | (IC ? kSfVariantIc : 0u) | ((uint32_t)MODE << kSfVariantModeShift) | ((uint32_t)ILP << kSfVariantIlpShift) | (SHORT ? kSfVariantShort : 0u) |
-                            (DBG ? kSfVariantDbg : 0u) | (NT == kSfLightThreads ? kSfVariantLight : 0u) | (CHILDREN ? kSfVariantChildren : 0u) | ((uint32_t)LW << kSfVariantLwShift),
+                            (DBG ? kSfVariantDbg : 0u) | (NT == kSfLightThreads ? kSfVariantLight : 0u) | (CHILDREN ? kSfVariantChildren : 0u) | (W2 ? kSfVariantW2 : 0u) | ((uint32_t)LW << kSfVariantLwShift),
                             std::memory_order_relaxed);
     ScanOut oo = o;
     oo.wq_cap = wq_cap;
@@ -960,7 +992,7 @@ static hipError_t launch_sf_v(const SfView& s, const BatchView& b, const ScanOut
     if (n_units <= blocks * waves_per_wg) oo.next_unit = nullptr;          // one unit per wavefront at most: nothing to draw
     // (else: *next_unit is zero -- it lives in the batch's 64-byte counter block, which every caller clears before the launch together with
     // its other counters; a memset of its own here was one more dispatch in every call)
-    hipLaunchKernelGGL((k_sf<IC, MODE, ILP, LW, SHORT, DBG, NT, CHILDREN>), dim3((uint32_t)blocks), dim3(NT), lds, st, s, b, oo, n_chunks);
+    hipLaunchKernelGGL((k_sf<IC, MODE, ILP, LW, SHORT, DBG, NT, CHILDREN, W2>), dim3((uint32_t)blocks), dim3(NT), lds, st, s, b, oo, n_chunks);
     return hipGetLastError();
 }
 
@@ -982,8 +1014,9 @@ hipError_t read_sf_phase_cycles(uint64_t* out5)
     return e;
 }
 
+constexpr int kSfW2Ilp = 1;      // a W2 probe round looks at one candidate per lane: ~50 per KiB pass the two-word filter, a round of 64 almost always takes them (table at kSfW2Group)
 template <bool IC, int MODE>
-static hipError_t launch_sf_t(const SfView& s, const BatchView& b, const ScanOut& o, int n_cu, hipStream_t st)
+static hipError_t launch_sf_t(const SfView& s, const BatchView& b, const ScanOut& o, int n_cu, hipStream_t st, const uint32_t* scan2)
 {
     const bool lw15 = s.bloom_log2_words == 15;
     constexpr bool kFlagMode = MODE == kModeAny || MODE == kModeIds;
@@ -994,7 +1027,12 @@ static hipError_t launch_sf_t(const SfView& s, const BatchView& b, const ScanOut
             return (s.tiers & 7u) ? launch_sf_v<IC, MODE, 2, 0, true, false, kSfLightThreads>(s, b, o, n_cu, st) : launch_sf_v<IC, MODE, 2, 0, false, false, kSfLightThreads>(s, b, o, n_cu, st);
         return (s.tiers & 7u) ? launch_sf_v<IC, MODE, 2, 0, true>(s, b, o, n_cu, st) : launch_sf_v<IC, MODE, 2, 0, false>(s, b, o, n_cu, st);
     } else {
+    // the image has a derived two-word filter (an overloaded 2^15-word filter, no short needles): the W2 instantiations read it in place of the scan filter
+    const bool w2 = scan2 != nullptr && lw15 && !(s.tiers & 7u);
+    SfView s2 = s;
+    if (w2) s2.scan_bloom = scan2;
     if (o.dbg && !kFlagMode) {                                                        // the instrumented instantiations (AM_SF_TRACE)
+        if (w2 && sf_chunks(b) > kSfLightChunks) return launch_sf_v<IC, MODE, kSfW2Ilp, 15, false, true, kSfThreads, false, true>(s2, b, o, n_cu, st);
         if (!lw15) return launch_sf_v<IC, MODE, 2, 0, true, true>(s, b, o, n_cu, st);
         return (s.tiers & 7u) ? launch_sf_v<IC, MODE, 2, 15, true, true>(s, b, o, n_cu, st) : launch_sf_v<IC, MODE, 2, 15, false, true>(s, b, o, n_cu, st);
     }
@@ -1004,6 +1042,7 @@ static hipError_t launch_sf_t(const SfView& s, const BatchView& b, const ScanOut
     // a dictionary with heavy suffix nodes (the image has five-byte child entries): its own instantiation, two candidates per lane whatever the table's size
     // (such text leaves hundreds of candidates per chunk)
     if (!lw15 && s.t4_children && !(s.tiers & 7u) && !kFlagMode) return launch_sf_v<IC, MODE, 2, 0, false, false, kSfThreads, true>(s, b, o, n_cu, st);
+    if (w2) return launch_sf_v<IC, MODE, kSfW2Ilp, 15, false, false, kSfThreads, false, true>(s2, b, o, n_cu, st);
     const bool few = s.tier_log2_cap[3] <= 15u;
     if (s.tiers & 7u) {                                                                     // needles shorter than 4 bytes present
         if (few) return lw15 ? launch_sf_v<IC, MODE, 1, 15, true>(s, b, o, n_cu, st) : launch_sf_v<IC, MODE, 1, 0, true>(s, b, o, n_cu, st);
@@ -1014,7 +1053,7 @@ static hipError_t launch_sf_t(const SfView& s, const BatchView& b, const ScanOut
     }
 }
 
-hipError_t launch_sf(bool ic, int mode, const SfView& s, const BatchView& b, const ScanOut& o_in, int n_cu, hipStream_t st)
+hipError_t launch_sf(bool ic, int mode, const SfView& s, const BatchView& b, const ScanOut& o_in, int n_cu, hipStream_t st, const uint32_t* scan2)
 {
     ScanOut o = o_in;
     o.two_always = 0;
@@ -1025,15 +1064,15 @@ hipError_t launch_sf(bool ic, int mode, const SfView& s, const BatchView& b, con
         g_sf_dbg = dbg;
     }
     if (ic) {
-        if (mode == kModeCount) return launch_sf_t<true, kModeCount>(s, b, o, n_cu, st);
-        if (mode == kModeEmit) return launch_sf_t<true, kModeEmit>(s, b, o, n_cu, st);
-        if (mode == kModeIds) return launch_sf_t<true, kModeIds>(s, b, o, n_cu, st);
-        return launch_sf_t<true, kModeAny>(s, b, o, n_cu, st);
+        if (mode == kModeCount) return launch_sf_t<true, kModeCount>(s, b, o, n_cu, st, scan2);
+        if (mode == kModeEmit) return launch_sf_t<true, kModeEmit>(s, b, o, n_cu, st, scan2);
+        if (mode == kModeIds) return launch_sf_t<true, kModeIds>(s, b, o, n_cu, st, scan2);
+        return launch_sf_t<true, kModeAny>(s, b, o, n_cu, st, scan2);
     }
-    if (mode == kModeCount) return launch_sf_t<false, kModeCount>(s, b, o, n_cu, st);
-    if (mode == kModeEmit) return launch_sf_t<false, kModeEmit>(s, b, o, n_cu, st);
-    if (mode == kModeIds) return launch_sf_t<false, kModeIds>(s, b, o, n_cu, st);
-    return launch_sf_t<false, kModeAny>(s, b, o, n_cu, st);
+    if (mode == kModeCount) return launch_sf_t<false, kModeCount>(s, b, o, n_cu, st, scan2);
+    if (mode == kModeEmit) return launch_sf_t<false, kModeEmit>(s, b, o, n_cu, st, scan2);
+    if (mode == kModeIds) return launch_sf_t<false, kModeIds>(s, b, o, n_cu, st, scan2);
+    return launch_sf_t<false, kModeAny>(s, b, o, n_cu, st, scan2);
 }
 
 }  // namespace dev

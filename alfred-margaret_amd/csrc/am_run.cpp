@@ -110,7 +110,7 @@ int launch_scan_kernel(const Plan& p, int mode, const ScanOut& o, hipStream_t st
         ScanOut os = o;
         os.next_unit = p.next_unit;
         Prof pr("sf", st);
-        HIP_TRY(launch_sf(p.ic, mode, p.sf, p.bv, os, p.n_cu, st));
+        HIP_TRY(launch_sf(p.ic, mode, p.sf, p.bv, os, p.n_cu, st, (const uint32_t*)p.f->d_scan2));
     }
     else if (p.use_dfa) {
         Prof pr("dfa", st);

@@ -63,7 +63,8 @@ AM_API uint32_t am_debug_sf_unit_chunks(uint64_t total_bytes, int n_cu);
  * mode and the batch size; a caller cannot see the choice).  Bit 0: valid; bit 1: IgnoreCase; bits 2-3: mode (0 count, 1 emit, 2 any, 3 ids); bits 4-5: ILP (1 or 2);
  * bit 6: SHORT (tier probes for needles of 1-3 bytes); bit 7: DBG (AM_SF_TRACE); bit 8: the light configuration (256-thread workgroups); bit 9: CHILDREN;
  * bits 16-23: LW (0 or 15).  Reading clears the word: 0 = no k_sf launch since the last read (another kernel took the call, or nothing was launched: an empty batch,
- * an automaton without suffix keys).  tests/test_gpu_sf_variants.py. */
+ * an automaton without suffix keys).  tests/test_gpu_sf_variants.py.  Bit 10: W2, the launch filtered with the two-word filter derived from the image's keys
+ * (csrc/am_image.h scan2_mask; tests/test_gpu_scan2_filter.py). */
 AM_API uint32_t am_debug_sf_last_variant(void);
 
 #ifdef __cplusplus
