@@ -207,6 +207,7 @@ struct SpansIn : RecordsIn {                                // the sorted record
     const uint32_t* words;                                  // the table's word class: 256 flags in 8 dwords (am_words.h); null: no class, every span is kept
 };
 constexpr uint64_t kSpansMaxTile = 2048;                    // candidates per workgroup of the prefix maximum
+constexpr uint32_t kSpThreads = 256;                        // lanes per workgroup of am_spans.hip; k_spans_tiles_max takes the tile maxima in sweeps of as many
 // cnt[i] = values < n_needles of record i (n_rec + 1 entries, the last one 0); then, with voff = exclusive sum of cnt and n_span = voff[n_rec], the spans in fold order.
 // With in.words both passes keep the whole-word spans only (ic decides the starts, so the count pass needs it as well)
 hipError_t launch_spans_count(bool ic, const SpansIn& in, uint32_t* cnt, hipStream_t st);

@@ -24,6 +24,7 @@ constexpr uint32_t kNearMaxQueries = 64;                    // AM_NEAR_MAX_QUERI
 constexpr uint32_t kNearOrdered = 1u;                       // AM_NEAR_ORDERED
 constexpr uint64_t kNearNone = ~0ull;                       // no span
 constexpr uint32_t kNearNoWord = ~0u;                       // no word (the links are 32-bit: a data array has fewer than 2^32 - 1 words of 64 spans)
+constexpr uint32_t kNearLdsNeedles = 8192;                  // masks k_near_bits stages in LDS (32 KiB); a larger table is read from HBM
 
 struct alignas(8) NearQuery { uint32_t group_a, group_b, flags, reserved; uint64_t max_gap; };      // = am_near_query in include/am.h
 struct alignas(8) NearPair { uint64_t a, b, gap; uint32_t haystack, query; };                       // = am_near_pair in include/am.h

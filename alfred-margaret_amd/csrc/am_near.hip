@@ -39,7 +39,7 @@ namespace {
 constexpr uint32_t kWave = 64;
 constexpr uint32_t kNearThreads = 256;
 constexpr uint32_t kNearTile = kNearThreads;                // spans per workgroup step: a lane per span
-constexpr uint32_t kNearLdsNeedles = 8192;                  // masks k_near_bits stages in LDS (32 KiB)
+// (kNearLdsNeedles, the masks k_near_bits stages in LDS: am_near.h)
 constexpr uint32_t kNearWordsPerThread = 4;
 constexpr uint32_t kNearSweepWords = kNearThreads * kNearWordsPerThread;      // words per sweep of k_near_words = 4 x tile_spans (am_near_geometry)
 constexpr int kNearGroupsPerCu = 8;

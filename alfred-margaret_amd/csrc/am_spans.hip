@@ -41,7 +41,7 @@ namespace dev {
 
 namespace {
 
-constexpr uint32_t kSpThreads = 256;
+// (kSpThreads, the lanes of a workgroup: am_device.h, beside kSpansMaxTile)
 constexpr uint32_t kSpMaxPer = (uint32_t)(kSpansMaxTile / kSpThreads);      // candidates per lane of the prefix maximum
 
 inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kSpThreads - 1) / kSpThreads); }

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import alfred_margaret_amd as am
-from tests import near_reference as ref, words_reference as wref
+from tests import near_reference as ref, scan_cases as sc, words_reference as wref
 from tests.helpers import fragment_case
 from tests.test_gpu_select import Batch, check_texts, lib, lowered
 
@@ -246,6 +246,50 @@ def test_sixty_four_queries_over_thirty_two_groups():
     keys = list(zip(got["haystack"].tolist(), got["a"].tolist(), got["query"].tolist()))
     assert keys == sorted(keys) and len(set(keys)) == len(keys) and len(pairs) > 2000
     assert x.counts.tolist() == np.bincount(got["query"], minlength=64).tolist() and np.count_nonzero(x.counts) >= 48
+
+
+# ---- 4b. a dictionary whose needle -> mask table does not fit in LDS: k_near_bits reads it in HBM
+
+BIG_ALPHABET = "defghijklmnopqrstuvwx"                     # 21 letters, none of a, b, c: 9261 three-letter words
+
+
+def big_dictionary(n, seed):
+    rng = random.Random(seed)
+    words = ["".join((x, y, z)) for x in BIG_ALPHABET for y in BIG_ALPHABET for z in BIG_ALPHABET]
+    rng.shuffle(words)
+    assert len(set(words)) == len(words) >= n + 50
+    return words[:n], words[n:n + 50], random_masks(rng, n, 4)
+
+
+@pytest.mark.parametrize("beyond", [0, 1])
+def test_a_mask_table_at_and_beyond_the_lds_limit(beyond):
+    """kNearLdsNeedles needles: the last size whose masks are staged in LDS; one more: every mask is read from HBM.  Random masks over four groups, zeros among
+    them, and tokens from all over the dictionary -- the last needle among them: a mask read at the wrong index gives other pairs."""
+    n = sc.limits().near_lds_needles + beyond
+    needles, strangers, masks = big_dictionary(n, 9700 + beyond)
+    rng = random.Random(9710 + beyond)
+    queries = random_queries(rng, 4, 6)
+    hays = []
+    for h in range(40):
+        tokens = [needles[-1] if rng.random() < 0.02 else rng.choice(strangers) if rng.random() < 0.05 else rng.choice(needles) for _ in range(rng.randint(60, 140))]
+        hays.append("".join(t + rng.choice([" ", " ", "", "  "]) for t in tokens))
+    hays[3] = ""
+    assert 12000 <= sum(map(len, hays)) <= 20000 and sum(h.count(needles[-1]) for h in hays) >= 20
+    assert 0 in masks and len(set(masks)) >= 10
+    px = Prox(needles, masks, queries)
+    rows = ref.rows_of(needles, 0, hays)
+    assert len(set(v for r in rows for _, _, v in r)) > 2000 and any(v == n - 1 for r in rows for _, _, v in r)
+    pairs = check_forms(px, 0, hays, rows, ("mask table", n))
+    assert len(pairs) > 500 and len(set(p[4] for p in pairs)) >= 4
+
+
+def test_a_gap_across_a_tile_with_the_mask_table_in_hbm():
+    tile = geometry()[0]
+    extra, _, masks = big_dictionary(sc.limits().near_lds_needles + 1 - len(ABC), 9720)
+    px = Prox(ABC + extra, ABC_MASKS + masks, [(0, 1, tile, False), (0, 1, tile - 1, False), (0, 1, tile, True), (0, 1, tile - 1, True)])
+    assert len(px.masks) > sc.limits().near_lds_needles
+    for lead in (0, 1, 63):
+        seam_case(px, tile, lead)
 
 
 # ---- 5. whole words

@@ -174,6 +174,20 @@ def test_run_seams(route, pattern):
     check_forms(sc, 0, hays, one, exp[:1], (pattern, "one column"))
 
 
+@pytest.mark.parametrize("n_cols", [2, 4, 5, 7])
+def test_column_counts_on_both_sides_of_an_instantiation(n_cols):
+    """k_score is compiled for 1, 4 and 8 columns and launched with the smallest that holds the weights: the last count of one and the first of the next, every
+    column with weights of its own, over runs that end inside a step, at a wavefront's records and at a tile."""
+    tile, _ = am.api.score_geometry()
+    cols = [[c + 1, 10 ** c, -(7 ** c) - c] for c in range(n_cols)]
+    lens = [63, 1, 64, 65, tile // 4 + 1, 0, tile - 1, 1, tile + 1, -4, 2]
+    exp = a3_scores([max(ln, 0) for ln in lens], cols)
+    assert len(set(map(tuple, exp.tolist()))) == n_cols                  # no two columns alike: a column read for another one shows
+    sc = Scorer(A3)
+    for case in (0, 1):
+        check_forms(sc, case, a3_hays(lens), cols, exp, (n_cols, case))
+
+
 def test_one_document_through_every_workgroup(route):
     """One haystack of 3 MiB of a's: three million records of one run, several tiles for every workgroup of the persistent grid; a second haystack behind it."""
     lens = [3 << 20, 5]

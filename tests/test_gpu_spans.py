@@ -10,7 +10,7 @@ import pytest
 
 import alfred_margaret_amd as am
 from oracle import oracle
-from tests import helpers, spans_reference as ref
+from tests import helpers, spans_reference as ref, spans_seam_cases as seams
 
 pytestmark = pytest.mark.gpu
 
@@ -325,3 +325,47 @@ def test_spans_of_the_lines_of_a_document(route):
                     assert same(got, d.expected(case, mode, lines)), (case, mode)
         finally:
             am.api.libam().am_batch_destroy(nb)
+
+
+# ---- 10. covers across the seams of the prefix maximum: a lane, a wavefront, a tile, the sweep of the tile maxima (tests/spans_seam_cases.py)
+
+@functools.lru_cache(maxsize=None)
+def seam_expected(group, name):
+    """(offsets, spans) of the definition over the case's literal rows; shared by the routes and the case modes"""
+    rows = seams.leftmost_longest(group, name)
+    lens = [len(r) for r in rows]
+    offs = np.zeros(len(rows) + 1, np.uint64)
+    offs[1:] = np.cumsum(lens)
+    flat = np.array([x for r in rows for x in r], np.uint64).reshape(-1, 3)
+    spans = np.zeros(len(flat), am.api.SPAN_DTYPE)
+    spans["start"], spans["len"], spans["needle"] = flat[:, 0], flat[:, 1], flat[:, 2]
+    spans["haystack"] = np.repeat(np.arange(len(rows), dtype=np.uint32), lens)
+    return offs, spans
+
+
+def check_seam_case(d, group, name):
+    c = seams.case(group, name)
+    exp = seam_expected(group, name)
+    covered = c.n - len(exp[1])
+    assert covered >= 6 and int(exp[0][-1]) == len(exp[1])
+    for case in (0, 1):
+        # every span there is, as a set, against the literal rows: one per byte -- the model itself
+        offs, every = d.t.spans_texts(case, c.hays, ref.ALL)
+        assert offs.tolist() == np.cumsum([0] + [len(h) for h in c.hays]).tolist(), (name, case)
+        every = every[np.lexsort((every["start"], every["haystack"]))]
+        for field, want in (("start", c.start), ("len", c.length), ("needle", c.needle), ("haystack", c.haystack)):
+            assert np.array_equal(every[field], want), (name, case, field)
+        d.check(case, ref.LEFTMOST_LONGEST, c.hays, exp=exp, mirror=(case == 0))
+
+
+@pytest.mark.parametrize("name", seams.NAMES)
+def test_covers_across_lanes_wavefronts_and_tiles(route, name):
+    """A cover that ends one candidate before a seam, at it, one and five behind it; one that reaches it over a whole tile; haystacks that begin at it; texts whose
+    last tile holds only the trailing element of `kept`."""
+    check_seam_case(Dictionary(seams.needles(seams.geometry()), route), "tiles", name)
+
+
+@pytest.mark.parametrize("name", seams.NAMES)
+def test_covers_across_the_sweep_of_the_tile_maxima(name):
+    """More tiles than one sweep of k_spans_tiles_max: what lies behind the sweep seam is covered only through the carry."""
+    check_seam_case(Dictionary(seams.needles(seams.geometry()), ROUTES["default"]), "sweep", name)
