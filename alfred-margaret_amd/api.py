@@ -61,6 +61,9 @@ SPANS_LEFTMOST_LONGEST = 1
 SUBST_MAX_SEGMENTS, SEG_LITERAL, SEG_MATCH = 64, 0, 1          # AM_SUBST_MAX_SEGMENTS, AM_SEG_LITERAL, AM_SEG_MATCH
 EXTRACT_EACH = 0
 EXTRACT_MERGED = 1
+BYTES, CODE_POINTS, UTF16 = 0, 1, 2                          # AM_UNIT_*: what start / len / columns / positions are counted in
+COORDS_CODE_POINTS, COORDS_UTF16, COORDS_LINES = 1, 2, 4     # AM_COORDS_*: which prefixes a Coords index carries
+SPAN_RANGE_DTYPE = np.dtype([("start_line", np.uint64), ("start_col", np.uint64), ("end_line", np.uint64), ("end_col", np.uint64)])   # am_span_range
 PRIO_MATCH_DTYPE = np.dtype([("start", np.uint64), ("len", np.uint64), ("haystack", np.uint32), ("payload", np.uint32)])   # am_prio_match
 
 _u8p, _u32p, _u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
@@ -216,6 +219,21 @@ ABI = {
     "am_fragments_from_spans": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_vp)]),
     "am_extract_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "am_extract": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(Slice), _sz, C.POINTER(_vp), C.POINTER(_vp)]),
+    "am_coords_create": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp)]),
+    "am_coords_destroy": (None, [_vp]),
+    "am_coords_index_bytes": (C.c_uint64, [_vp]),
+    "am_coords_spans": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(_vp)]),
+    "am_coords_fragments": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(_vp)]),
+    "am_coords_ranges": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(_vp)]),
+    "am_ranges_size": (C.c_uint64, [_vp]),
+    "am_ranges_haystacks": (C.c_uint64, [_vp]),
+    "am_ranges_offsets": (_vp, [_vp]),
+    "am_ranges_data": (_vp, [_vp]),
+    "am_ranges_device_offsets": (_vp, [_vp]),
+    "am_ranges_device_data": (_vp, [_vp]),
+    "am_ranges_free": (None, [_vp]),
+    "am_coords_positions": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_int, _vp]),
+    "am_coords_positions_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_int, _vp]),
     "am_needle_ids_create": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(_vp)]),
     "am_needle_ids_destroy": (None, [_vp]),
     "am_contains_all": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp]),
@@ -537,8 +555,13 @@ class Automaton:
         with open(path, "wb") as f:
             f.write(self.image_bytes(case))
 
-    def run_batch_with_case(self, case, texts):
-        """Per-haystack list fold of runWithCase: returns (haystack, matchPos, value) arrays in fold order."""
+    def run_batch_with_case(self, case, texts, unit=BYTES):
+        """Per-haystack list fold of runWithCase: returns (haystack, matchPos, value) arrays in fold order.  unit: what matchPos is counted in -- BYTES (the
+        reference's code units, the default) or CODE_POINTS / UTF16, converted in HBM (am_coords_positions)."""
+        if unit != BYTES:
+            hay, pos, val = self.run_batch_with_case(case, texts)
+            with _Uploaded(texts) as b:
+                return hay, Coords(b, utf16=unit == UTF16).positions(hay, pos, unit), val
         s = _Slices(texts)
         n = C.c_uint64(0)
         _hcheck(libhost().amh_run_list(self._h, case, s.arr, s.n, None, None, None, 0, C.byref(n)))
@@ -673,13 +696,34 @@ class Automaton:
             out.append(rows)
         return out
 
-    def spans(self, case, texts, leftmost_longest=False, whole_words=False):
+    def spans(self, case, texts, leftmost_longest=False, whole_words=False, unit=BYTES):
         """Where every match starts: (offsets np.uint64[len(texts) + 1], spans SPAN_DTYPE[offsets[-1]]); the spans of text i are spans[offsets[i]:offsets[i + 1]],
         start and len in bytes relative to the text, needle = the value handle.  All fold steps of runWithCase (Automaton.hs:442-553) in fold order with the span
         makeMatch gives them (Replacer.hs:264-274), or -- leftmost_longest -- the non-overlapping selection: smallest start, then longest, then smallest handle, never a
         zero-length span.  am_spans: scanned, expanded and selected in HBM.  whole_words: True (the default word class) or a class as SpanTable takes it -- only the
-        spans whose neighbours inside the text are no word bytes, filtered BEFORE the selection (include/am.h "whole words")."""
-        return SpanTable(self, word_bytes=whole_words).spans_texts(case, texts, SPANS_LEFTMOST_LONGEST if leftmost_longest else SPANS_ALL)
+        spans whose neighbours inside the text are no word bytes, filtered BEFORE the selection (include/am.h "whole words").  unit: CODE_POINTS or UTF16 give start
+        and len in that unit, converted in HBM (include/am.h "coordinates"): Automaton(["nike"]).spans(IGNORE_CASE, ["é NIKE"], unit=CODE_POINTS) has start 2, len 4."""
+        mode = SPANS_LEFTMOST_LONGEST if leftmost_longest else SPANS_ALL
+        if unit == BYTES:
+            return SpanTable(self, word_bytes=whole_words).spans_texts(case, texts, mode)
+        with _Uploaded(texts) as b:
+            return SpanTable(self, word_bytes=whole_words).spans_batch(case, b, mode, unit=unit)
+
+    def locate(self, case, texts, unit=CODE_POINTS, leftmost_longest=True, whole_words=False):
+        """Where every match lies in its document, file:line:col: (offsets np.uint64[len(texts) + 1], spans SPAN_DTYPE in `unit`, ranges SPAN_RANGE_DTYPE) -- row k of
+        ranges is the 0-based line and the column, in `unit`, of the start and of the end of span k (include/am.h "coordinates").  With unit=UTF16 a row is a
+        Language-Server range.  Scanned, selected and converted in HBM."""
+        t = SpanTable(self, word_bytes=whole_words)
+        with _Uploaded(texts) as b:
+            raw = t.spans_batch(case, b, SPANS_LEFTMOST_LONGEST if leftmost_longest else SPANS_ALL, raw=True)
+            try:
+                c = Coords(b, lines=True, utf16=unit == UTF16)
+                offs, spans = c.spans(raw, unit)
+                ranges = c.ranges(raw, unit)[1]
+                del c                                       # (the batch outlives the index)
+                return offs, spans, ranges
+            finally:
+                libam().am_spans_free(raw)
 
     def spans_host_mirror(self, case, texts, leftmost_longest=False, n_values=None, lengths=None):
         """The same through the C++ host mirror (host/spans.hpp spansFold over the fold steps of amh_run_list).  lengths: (len_bytes, len_code_points) per value handle
@@ -1094,10 +1138,17 @@ class SpanTable:
         s = _Slices(texts)
         return self._counts(lambda out: libam().am_count_spans_by_needle(self._h, case, s.arr, s.n, out))
 
-    def spans_batch(self, case, batch, mode, raw=False):
+    def spans_batch(self, case, batch, mode, raw=False, unit=BYTES):
         """am_spans_batch on a device-resident batch (an am_batch* handle: am_batch_upload / am_batch_from_device / Splitter.lines_batch): (offsets np.uint64[n_hay + 1],
-        spans SPAN_DTYPE[offsets[-1]]).  raw: the am_spans* itself, in HBM (measurements; free with am_spans_free)."""
-        return self._spans(lambda out: libam().am_spans_batch(self._h, case, mode, batch, out), raw)
+        spans SPAN_DTYPE[offsets[-1]]).  raw: the am_spans* itself, in HBM (measurements; free with am_spans_free).  unit: CODE_POINTS or UTF16 convert start and len
+        in HBM through an index built for this call (Coords; a caller with many calls on one batch keeps a Coords of its own)."""
+        if unit == BYTES:
+            return self._spans(lambda out: libam().am_spans_batch(self._h, case, mode, batch, out), raw)
+        spans_raw = self._spans(lambda out: libam().am_spans_batch(self._h, case, mode, batch, out), True)
+        try:
+            return Coords(batch, utf16=unit == UTF16).spans(spans_raw, unit, raw)
+        finally:
+            libam().am_spans_free(spans_raw)
 
     def spans_texts(self, case, texts, mode):
         """am_spans: the one-shot form on host texts."""
@@ -1139,6 +1190,71 @@ class SpanTable:
         finally:
             libam().am_fragments_free(fr)
         return nb, offs, frags
+
+
+class _Uploaded:
+    """Host texts as a device-resident batch for the length of a with block (am_batch_upload / am_batch_destroy)."""
+
+    def __init__(self, texts):
+        self._s = _Slices(texts)
+        self._b = _vp()
+
+    def __enter__(self):
+        check(libam().am_batch_upload(self._s.arr, self._s.n, C.byref(self._b)))
+        return self._b
+
+    def __exit__(self, *exc):
+        libam().am_batch_destroy(self._b)
+
+
+class Coords:
+    """The coordinate index of a device-resident batch (am_coords, include/am.h "coordinates"): per 128-byte tile of the text the running counts of code points, of
+    four-byte sequences (utf16) and of newlines (lines), in HBM.  Converts results that are in bytes -- spans, fragments, positions -- into CODE_POINTS or UTF16 and
+    gives every span its line and column, without the rows leaving the device.  The batch must outlive the index."""
+
+    def __init__(self, batch, lines=False, utf16=False):
+        self._batch = batch
+        h = _vp()
+        check(libam().am_coords_create(batch, COORDS_CODE_POINTS | (COORDS_UTF16 if utf16 else 0) | (COORDS_LINES if lines else 0), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            libam().am_coords_destroy(self._h)
+            self._h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def index_bytes(self):
+        """am_coords_index_bytes: the bytes of HBM the index keeps."""
+        return int(libam().am_coords_index_bytes(self._h))
+
+    def spans(self, spans_raw, unit, raw=False):
+        """am_coords_spans: an am_spans* the caller holds (spans_batch(..., raw=True) on this batch) with start and len in `unit`, as (offsets, spans SPAN_DTYPE).
+        raw: the new am_spans* itself, in HBM (free with am_spans_free)."""
+        return _csr_call(lambda out: libam().am_coords_spans(self._h, spans_raw, int(unit), out), spans_to_numpy, libam().am_spans_free, raw)
+
+    def fragments(self, fragments_raw, unit, raw=False):
+        """am_coords_fragments: the same for an am_fragments* (Splitter.split_fragments, fragments_from_spans(..., raw=True)), as (offsets, fragments FRAGMENT_DTYPE)."""
+        return _csr_call(lambda out: libam().am_coords_fragments(self._h, fragments_raw, int(unit), out), fragments_to_numpy, libam().am_fragments_free, raw)
+
+    def ranges(self, spans_raw, unit, raw=False):
+        """am_coords_ranges: (offsets, ranges SPAN_RANGE_DTYPE) -- 0-based line and column, in `unit`, of the start and of the end of every span; needs lines=True.
+        raw: the am_ranges* itself, in HBM (free with am_ranges_free)."""
+        return _csr_call(lambda out: libam().am_coords_ranges(self._h, spans_raw, int(unit), out), ranges_to_numpy, libam().am_ranges_free, raw)
+
+    def positions(self, hay, pos, unit):
+        """am_coords_positions: pos[i], a byte position relative to haystack hay[i], in `unit` (np.uint64).  AmError(AM_ERR_INVALID) for a haystack index or a position
+        outside the batch."""
+        hay, pos = np.ascontiguousarray(hay, dtype=np.uint32), np.ascontiguousarray(pos, dtype=np.uint64)
+        if hay.shape != pos.shape or hay.ndim != 1:
+            raise AmError(AM_ERR_INVALID, "positions: hay and pos are two flat arrays of one length")
+        out = np.zeros(max(len(hay), 1), np.uint64)
+        check(libam().am_coords_positions(self._h, hay.ctypes.data, pos.ctypes.data, len(hay), int(unit), out.ctypes.data))
+        return out[:len(hay)]
 
 
 class Selection:
@@ -1883,6 +1999,11 @@ def matrix_to_numpy(x):
 def spans_to_numpy(x):
     """(offsets np.uint64[n_hay + 1], spans SPAN_DTYPE[n]) of an am_spans* result (host copies)."""
     return _csr_to_numpy(x, "am_spans", SPAN_DTYPE)
+
+
+def ranges_to_numpy(x):
+    """(offsets np.uint64[n_hay + 1], ranges SPAN_RANGE_DTYPE[n]) of an am_ranges* result (host copies)."""
+    return _csr_to_numpy(x, "am_ranges", SPAN_RANGE_DTYPE)
 
 
 def matches_of_haystack(m, haystack):

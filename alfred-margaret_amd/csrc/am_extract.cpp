@@ -36,6 +36,7 @@ int check_stage(const am_batch* src, const struct am_spans* s, int mode)
 {
     AM_TRY(check_extract_mode(mode));
     if (!src || !s) return fail(AM_ERR_INVALID, "null batch or spans");
+    if (s->unit != AM_UNIT_BYTES) return fail(AM_ERR_INVALID, "am_fragments_from_spans: the spans are in converted units (am_coords_spans); the windows are cut from byte spans");
     if (mode == AM_EXTRACT_MERGED && s->mode != AM_SPANS_LEFTMOST_LONGEST)
         return fail(AM_ERR_INVALID, "am_fragments_from_spans: AM_EXTRACT_MERGED takes an AM_SPANS_LEFTMOST_LONGEST result only (overlapping spans do not ascend by window)");
     if (s->n_hay != src->n_hay || s->src_total != src->total || s->dev != src->dev)

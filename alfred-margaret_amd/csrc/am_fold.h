@@ -257,5 +257,6 @@ inline int sub_batch(const am_batch* b, uint64_t h0, uint64_t h1, uint64_t o0, u
 // the result of am_split* (am_splitter.cpp) and of am_fragments_from_spans (am_extract.cpp): what am_batch_from_fragments turns into a batch
 struct am_fragments : am::host::CsrResult<am_fragment> {
     uint64_t src_total = 0;                               // bytes of the batch they were cut from (am_batch_from_fragments checks it)
+    int unit = AM_UNIT_BYTES;                             // what start / len are in; anything else: made by am_coords_fragments, refused by am_batch_from_fragments
 };
 static_assert(sizeof(am_fragment) == sizeof(am::dev::Fragment), "am_fragment and the kernels' Fragment are one layout");

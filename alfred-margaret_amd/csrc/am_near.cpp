@@ -100,6 +100,7 @@ extern "C" int am_near_spans(const NearCall* p, const SpansResult* s, am_near_hi
     if (!out) return fail(AM_ERR_INVALID, "out is null");
     *out = nullptr;
     if (!p || !s) return fail(AM_ERR_INVALID, "null proximity handle or spans");
+    if (s->unit != AM_UNIT_BYTES) return fail(AM_ERR_INVALID, "am_near_spans: the spans are in converted units (am_coords_spans); the gaps are measured between byte spans");
     if (s->mode != AM_SPANS_LEFTMOST_LONGEST) return fail(AM_ERR_INVALID, "am_near_spans takes an AM_SPANS_LEFTMOST_LONGEST result (rows that ascend and do not overlap)");
     if (s->n_needles != p->n_needles) return fail(AM_ERR_INVALID, "the spans were not made under a table with this number of needles");
     if (s->dev != p->dev) return fail(AM_ERR_INVALID, "proximity handle and spans live on different devices");

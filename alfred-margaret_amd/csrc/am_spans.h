@@ -30,4 +30,5 @@ struct am_spans : am::host::CsrResult<am_span> {
     int mode = AM_SPANS_ALL;                                // what am_batch_substitute holds a result to: the selection, the table's handles and the batch it was made from
     uint32_t n_needles = 0;
     uint64_t src_total = 0;
+    int unit = AM_UNIT_BYTES;                               // what start / len are in; anything else: made by am_coords_spans, refused by the stages that read byte spans
 };

@@ -140,6 +140,7 @@ extern "C" int am_batch_from_fragments(const am_batch* src, const am_fragments* 
     if (!out) return fail(AM_ERR_INVALID, "out is null");
     *out = nullptr;
     if (!src || !f) return fail(AM_ERR_INVALID, "null batch or fragments");
+    if (f->unit != AM_UNIT_BYTES) return fail(AM_ERR_INVALID, "am_batch_from_fragments: the fragments are in converted units (am_coords_fragments); the gather reads byte fragments");
     if (f->n_hay != src->n_hay || f->src_total != src->total || f->dev != src->dev)
         return fail(AM_ERR_INVALID, "the fragments were not produced from a batch with this haystack count and size");
     if (f->n_items >= 0xFFFFFFFFull) return fail(AM_ERR_UNSUPPORTED, "am_batch_from_fragments: 2^32 - 1 fragments and more do not fit a batch");

@@ -27,6 +27,7 @@ constexpr size_t kPoolPad = 32;
 int check_splice(const am_batch* src, const struct am_spans* s, const am_subst_table* r)
 {
     if (!src || !s || !r) return fail(AM_ERR_INVALID, "null batch, spans or substitution table");
+    if (s->unit != AM_UNIT_BYTES) return fail(AM_ERR_INVALID, "am_batch_substitute: the spans are in converted units (am_coords_spans); the splice reads byte spans");
     if (s->mode != AM_SPANS_LEFTMOST_LONGEST) return fail(AM_ERR_INVALID, "am_batch_substitute: the spans are not an AM_SPANS_LEFTMOST_LONGEST result (overlapping spans cannot be spliced)");
     if (s->n_hay != src->n_hay || s->src_total != src->total) return fail(AM_ERR_INVALID, "the spans were not produced from a batch with this haystack count and size");
     if (s->dev != src->dev || r->dev != src->dev) return fail(AM_ERR_INVALID, "batch, spans and substitution table live on different devices");

@@ -715,6 +715,66 @@ AM_API int am_extract_batch(const am_span_table* t, int case_mode, int spans_mod
 AM_API int am_extract(const am_span_table* t, int case_mode, int spans_mode, uint32_t before, uint32_t after, int mode,
                       const am_slice* hay, size_t n_hay, am_batch** out, am_fragments** frags_out /* nullable */);
 
+/* ---- coordinates: match positions in code points, UTF-16 code units, line and column, in HBM ---------------
+ * Every position the library returns is a byte offset into the UTF-8 text (am_match.end_pos, am_span.start / .len, am_fragment.start / .len): the reference's contract,
+ * and the default.  A Python caller wants code points (text[start:]), a JavaScript / Java / .NET / Language-Server consumer UTF-16 code units, a code-search or
+ * secret-scanning front end line:column inside a whole document -- and under AM_IGNORE_CASE a match has the text's own width, so none of it follows from the needle.
+ * This stage converts a result in HBM into a result in HBM; it changes no other entry point.
+ * THE DEFINITION is on bytes, so it holds for any input.  For a haystack that occupies the bytes [base, end) of its batch and a position 0 <= p <= end - base:
+ *   cp(p)         the number of bytes b of [base, base + p) with (b & 0xC0) != 0x80 (the START bytes of "extract")
+ *   u16(p)        cp(p) + the number of bytes >= 0xF0 of the same range (a four-byte sequence is a surrogate pair)
+ *   line(p)       the number of 0x0A bytes of [base, base + p), 0-based; 0x0D is not special
+ *   linestart(p)  1 + the position of the last 0x0A of [base, base + p), or 0 if there is none: never in another haystack
+ *   col_U(p)      U(p) - U(linestart(p)), U one of bytes, cp, u16
+ * A span or fragment (start, len) in unit U becomes (U(start), U(start + len) - U(start)).  On valid UTF-8 at code point boundaries these are Python's
+ * len(b[:p].decode()), len(s[:i].encode("utf-16-le")) // 2, s.count("\n", 0, i) and i - (s.rfind("\n", 0, i) + 1).  Bytes outside [base, base + p) NEVER COUNT: not a
+ * neighbouring haystack's, not the padding up to round_up(total, 16), whatever a borrowed batch holds there.
+ * THE INDEX (csrc/am_coords.hip, am_coords.h): one pass over the text counts, per tile of 128 aligned bytes, the bytes of every class `what` asks for; an exclusive sum
+ * per class turns the counts into uint64 prefixes, 8 bytes per class and tile (at most 24 bytes per 128 bytes of text: 19 %), which the index keeps in HBM.  A lookup
+ * is one prefix entry and at most eight 16-byte loads of the position's own tile; a line start is found in the position's tile or by a binary search over the
+ * newline prefix.  What crosses to the host: nothing, except the one flag word of am_coords_positions*.
+ *   am_coords_create      builds the index of a batch for AM_COORDS_CODE_POINTS | AM_COORDS_UTF16 (implies CODE_POINTS) | AM_COORDS_LINES; what == 0 is an index that
+ *                         serves AM_UNIT_BYTES only.  OWNERSHIP: the index borrows the batch's text and offsets, THE BATCH MUST OUTLIVE THE INDEX.  A batch without
+ *                         haystacks gives an index whose calls return empty results.
+ *   am_coords_index_bytes the bytes of HBM the index keeps (0 for NULL).
+ *   am_coords_spans       a result of the same type, row count, offsets, haystack, needle and mode as `s`; only start / len are in `unit`.  The result is MARKED AS
+ *   am_coords_fragments   CONVERTED: the stages that read byte spans -- am_batch_substitute, am_fragments_from_spans, am_near_spans, am_batch_from_fragments and
+ *                         am_coords_* itself -- refuse it with AM_ERR_INVALID.  AM_UNIT_BYTES gives a plain copy that is not marked.
+ *   am_coords_ranges      line and column of every span's start and of its end (start + len), the columns in `unit`; CSR like am_spans, row k belongs to span k and the
+ *                         offsets are the spans'.  Needs an index with AM_COORDS_LINES and the prefixes `unit` needs.
+ *   am_coords_positions   converts any (haystack, relative position) list -- this is how am_match.end_pos is converted -- from host arrays into a host array;
+ *   am_coords_positions_device   the same over arrays in HBM (hay uint32[n], pos uint64[n], out uint64[n]) on the calling thread's stream.  hay[i] >= the batch's
+ *                         haystack count, or pos[i] beyond the haystack's length: the kernel raises one flag word, the host reads that word and the call returns
+ *                         AM_ERR_INVALID (d_out is unspecified then).  n == 0 is AM_OK.
+ * Arguments are checked before any device work: AM_ERR_INVALID for null handles / arrays / out, an unknown unit, bits of `what` that are not defined, a result that
+ * is marked as converted, spans or fragments that were not produced from the index's batch (haystack count, total bytes, device), and an index that lacks what the
+ * call needs -- the message names the missing flag (AM_COORDS_CODE_POINTS, AM_COORDS_UTF16, AM_COORDS_LINES).  No haystacks, and no rows, give empty results and
+ * AM_OK.  *out is NULL after every failure. */
+#define AM_UNIT_BYTES 0
+#define AM_UNIT_CODE_POINTS 1
+#define AM_UNIT_UTF16 2
+#define AM_COORDS_CODE_POINTS 1u   /* which prefixes the index carries */
+#define AM_COORDS_UTF16 2u         /* implies CODE_POINTS */
+#define AM_COORDS_LINES 4u
+typedef struct am_coords am_coords;
+typedef struct am_span_range { uint64_t start_line, start_col, end_line, end_col; } am_span_range;   /* 32 bytes */
+typedef struct am_ranges am_ranges;   /* CSR like am_spans: row k belongs to span k, offsets are the spans' */
+AM_API int am_coords_create(const am_batch* b, uint32_t what, am_coords** out);
+AM_API void am_coords_destroy(am_coords* c);
+AM_API uint64_t am_coords_index_bytes(const am_coords* c);
+AM_API int am_coords_spans(const am_coords* c, const struct am_spans* s, int unit, struct am_spans** out);
+AM_API int am_coords_fragments(const am_coords* c, const am_fragments* f, int unit, am_fragments** out);
+AM_API int am_coords_ranges(const am_coords* c, const struct am_spans* s, int unit /* of the columns */, am_ranges** out);
+AM_API uint64_t am_ranges_size(const am_ranges* r);
+AM_API uint64_t am_ranges_haystacks(const am_ranges* r);
+AM_API const uint64_t* am_ranges_offsets(am_ranges* r);
+AM_API const am_span_range* am_ranges_data(am_ranges* r);
+AM_API const void* am_ranges_device_offsets(const am_ranges* r);
+AM_API const void* am_ranges_device_data(const am_ranges* r);
+AM_API void am_ranges_free(am_ranges* r);
+AM_API int am_coords_positions(const am_coords* c, const uint32_t* hay, const uint64_t* pos, uint64_t n, int unit, uint64_t* out /* host arrays */);
+AM_API int am_coords_positions_device(const am_coords* c, const void* d_hay, const void* d_pos, uint64_t n, int unit, void* d_out /* HBM, the calling stream */);
+
 /* Checksum of the fold sequence of a result (harness aid; SURVEY 8d "parity check at scale",
  * benchmark/benchmark.py:65-69 asserts count identity on every run).  For every haystack i < n_hay:
  *   hash_out[i]  = foldl (\h (pos, v) -> h * 0x100000001B3 + mix pos v) 0  over the matches the reference's
