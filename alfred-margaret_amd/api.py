@@ -234,6 +234,23 @@ ABI = {
     "am_ranges_free": (None, [_vp]),
     "am_coords_positions": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_int, _vp]),
     "am_coords_positions_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_int, _vp]),
+    "am_postings_from_spans": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "am_postings_batch": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
+    "am_postings": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(Slice), _sz, C.POINTER(_vp)]),
+    "am_postings_size": (C.c_uint64, [_vp]),
+    "am_postings_needles": (C.c_uint64, [_vp]),
+    "am_postings_haystacks": (C.c_uint64, [_vp]),
+    "am_postings_offsets": (_vp, [_vp]),
+    "am_postings_data": (_vp, [_vp]),
+    "am_postings_source": (_vp, [_vp]),
+    "am_postings_doc_freq": (_vp, [_vp]),
+    "am_postings_device_offsets": (_vp, [_vp]),
+    "am_postings_device_data": (_vp, [_vp]),
+    "am_postings_device_source": (_vp, [_vp]),
+    "am_postings_device_doc_freq": (_vp, [_vp]),
+    "am_postings_free": (None, [_vp]),
+    "am_spans_of_needle": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp)]),
+    "am_postings_geometry": (None, [C.c_uint64, _u32p, _u32p, _u32p, _u32p]),
     "am_needle_ids_create": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(_vp)]),
     "am_needle_ids_destroy": (None, [_vp]),
     "am_contains_all": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp]),
@@ -696,6 +713,47 @@ class Automaton:
             out.append(rows)
         return out
 
+    def postings(self, case, texts, leftmost_longest=False, whole_words=False):
+        """Where each needle occurs (include/am.h "postings"): a Postings -- the spans of spans(case, texts, leftmost_longest, whole_words) ordered by needle, row v =
+        the occurrences of needle v in (text, start) order, with the row of the spans each came from and the document frequencies.  am_postings: scanned, expanded,
+        selected and sorted in HBM."""
+        return SpanTable(self, word_bytes=whole_words).postings_texts(case, texts, SPANS_LEFTMOST_LONGEST if leftmost_longest else SPANS_ALL)
+
+    def doc_freq(self, case, texts, whole_words=False):
+        """In how many of the texts each needle occurs: np.uint64[len(needles)], the IDF half of TF-IDF (a Weights for score is made from it).  Over every
+        occurrence (SPANS_ALL), with whole_words over the whole-word occurrences."""
+        with self.postings(case, texts, whole_words=whole_words) as p:
+            return p.doc_freq
+
+    def concordance(self, case, texts, needle, before=0, after=0, leftmost_longest=True, whole_words=False):
+        """Every occurrence of ONE needle among this dictionary's matches with up to `before` / `after` code points of its text around it, in (text, start) order: a
+        list of bytes.  needle: one of the needles, or its index.  Postings, then the needle's row as spans (am_spans_of_needle), their windows
+        (am_fragments_from_spans) and the gather (am_batch_from_fragments), all in HBM; the snippets come back.  Under leftmost_longest `he` inside `the` is no
+        occurrence of `he` when `the` is a needle: a one-needle automaton cannot say that."""
+        if isinstance(needle, (int, np.integer)) and not isinstance(needle, bool):
+            v = int(needle)
+        else:
+            known = [_as_bytes(n) for n in self.needles]
+            if _as_bytes(needle) not in known:
+                raise AmError(AM_ERR_INVALID, "concordance: %r is not among the needles" % (needle,))
+            v = known.index(_as_bytes(needle))
+        t = SpanTable(self, word_bytes=whole_words)
+        with _Uploaded(texts) as b, t.postings_batch(case, b, SPANS_LEFTMOST_LONGEST if leftmost_longest else SPANS_ALL) as p:
+            row = p.spans_of(v, raw=True)
+            try:
+                fr = t.fragments_from_spans(b, row, before, after, False, raw=True)
+            finally:
+                libam().am_spans_free(row)
+            nb = _vp()
+            try:
+                check(libam().am_batch_from_fragments(b, fr, C.byref(nb)))
+            finally:
+                libam().am_fragments_free(fr)
+            try:
+                return batch_to_bytes(nb)[1]
+            finally:
+                libam().am_batch_destroy(nb)
+
     def spans(self, case, texts, leftmost_longest=False, whole_words=False, unit=BYTES):
         """Where every match starts: (offsets np.uint64[len(texts) + 1], spans SPAN_DTYPE[offsets[-1]]); the spans of text i are spans[offsets[i]:offsets[i + 1]],
         start and len in bytes relative to the text, needle = the value handle.  All fold steps of runWithCase (Automaton.hs:442-553) in fold order with the span
@@ -1155,6 +1213,26 @@ class SpanTable:
         s = _Slices(texts)
         return self._spans(lambda out: libam().am_spans(self._h, case, mode, s.arr, s.n, out), False)
 
+    def postings_batch(self, case, batch, mode, raw=False):
+        """am_postings_batch on a device-resident batch: the Postings of its spans in `mode` (SPANS_ALL / SPANS_LEFTMOST_LONGEST).  raw: the am_postings* itself
+        (measurements; free with am_postings_free)."""
+        h = _vp()
+        check(libam().am_postings_batch(self._h, case, mode, batch, C.byref(h)))
+        return h if raw else Postings(h)
+
+    def postings_texts(self, case, texts, mode):
+        """am_postings: the one-shot form on host texts."""
+        s = _Slices(texts)
+        h = _vp()
+        check(libam().am_postings(self._h, case, mode, s.arr, s.n, C.byref(h)))
+        return Postings(h)
+
+    def postings_from_spans(self, spans_raw):
+        """am_postings_from_spans: the stage alone over an am_spans* the caller holds (spans_batch(..., raw=True), Coords.spans(..., raw=True))."""
+        h = _vp()
+        check(libam().am_postings_from_spans(spans_raw, C.byref(h)))
+        return Postings(h)
+
     def select_batch(self, case, batch, invert=False):
         """am_select_spans_batch on a device-resident batch: the Selection of the haystacks whose SPANS_ALL row under this table is not empty (with a word class:
         the haystacks that hold a needle as a whole word)."""
@@ -1445,6 +1523,108 @@ def _scores(call):
     h = _vp()
     check(call(C.byref(h)))
     return Scores(h)
+
+
+def postings_geometry(n_needles):
+    """(tile_spans, wave_spans, passes, bits) of the postings sort for n_needles (am_postings_geometry): the spans of a workgroup tile, the consecutive spans of a
+    wavefront's portion (taken 64 per round), the passes and the bits each pass sorts, lowest first (a list of `passes` entries).  Known without a device."""
+    t, w, p = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    bits = (C.c_uint32 * 4)()
+    libam().am_postings_geometry(int(n_needles), C.byref(t), C.byref(w), C.byref(p), bits)
+    return int(t.value), int(w.value), int(p.value), [int(b) for b in bits[:p.value]]
+
+
+def postings_host(offsets, spans, n_needles):
+    """The definition of am_postings_from_spans in numpy over spans the caller brings -- CSR offsets and SPAN_DTYPE rows: (offsets np.uint64[n_needles + 1], spans
+    SPAN_DTYPE, source np.uint64, doc_freq np.uint64[n_needles]).  Runs without a device."""
+    so = np.ascontiguousarray(offsets, dtype=np.uint64)
+    sp = np.ascontiguousarray(spans, dtype=SPAN_DTYPE)
+    n = int(n_needles)
+    if len(so) < 1 or int(so[-1]) != len(sp):
+        raise AmError(AM_ERR_INVALID, "postings_host: the offsets are not those of the spans")
+    if len(sp) and int(sp["needle"].max()) >= n:
+        raise AmError(AM_ERR_INVALID, "postings_host: a needle handle is not below n_needles")
+    perm = np.argsort(sp["needle"], kind="stable")
+    data = sp[perm]
+    offs = np.searchsorted(data["needle"], np.arange(n + 1, dtype=np.uint64), side="left").astype(np.uint64)
+    head = np.ones(len(data), bool)
+    head[1:] = (data["needle"][1:] != data["needle"][:-1]) | (data["haystack"][1:] != data["haystack"][:-1])
+    return offs, data, perm.astype(np.uint64), np.bincount(data["needle"][head], minlength=n).astype(np.uint64)[:n]
+
+
+class Postings:
+    """The spans of a result by needle (am_postings, include/am.h "postings"): row v = the occurrences of needle v, in HBM, copied to the host on first use.  A context
+    manager: leaving the block frees the handle."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def close(self):
+        if getattr(self, "_h", None):
+            libam().am_postings_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def size(self):
+        return int(libam().am_postings_size(self._h))
+
+    @property
+    def n_needles(self):
+        return int(libam().am_postings_needles(self._h))
+
+    @property
+    def n_hay(self):
+        return int(libam().am_postings_haystacks(self._h))
+
+    def _host(self, fn, n, dtype):
+        p = fn(self._h)
+        if not p:
+            raise AmError(AM_ERR_HIP, (libam().am_last_error() or b"").decode())
+        return np.frombuffer((C.c_char * (n * dtype.itemsize)).from_address(p), dtype=dtype).copy() if n else np.zeros(0, dtype)
+
+    @property
+    def offsets(self):
+        """np.uint64[n_needles + 1]: the occurrences of needle v are spans[offsets[v]:offsets[v + 1]]."""
+        return self._host(libam().am_postings_offsets, self.n_needles + 1, np.dtype(np.uint64))
+
+    @property
+    def spans(self):
+        """SPAN_DTYPE[size]: ascending by (needle, haystack, then the order of the spans they were made from)."""
+        return self._host(libam().am_postings_data, self.size, SPAN_DTYPE)
+
+    @property
+    def source(self):
+        """np.uint64[size]: source[k] = the row of the spans result that spans[k] came from."""
+        return self._host(libam().am_postings_source, self.size, np.dtype(np.uint64))
+
+    @property
+    def doc_freq(self):
+        """np.uint64[n_needles]: the distinct haystacks in each row."""
+        return self._host(libam().am_postings_doc_freq, self.n_needles, np.dtype(np.uint64))
+
+    def row(self, v):
+        """The occurrences of needle v: SPAN_DTYPE rows (through the host copies)."""
+        if not 0 <= int(v) < self.n_needles:
+            raise AmError(AM_ERR_INVALID, "row: the needle is not below n_needles")
+        o = self.offsets
+        return self.spans[int(o[int(v)]):int(o[int(v) + 1])]
+
+    def spans_of(self, v, raw=False):
+        """am_spans_of_needle: row v as a spans result of its own, per-haystack offsets rebuilt in HBM: (offsets np.uint64[n_hay + 1], spans SPAN_DTYPE).  raw: the
+        am_spans* itself (fragments_from_spans, Coords and SubstTable.splice take it; free with am_spans_free)."""
+        return _csr_call(lambda out: libam().am_spans_of_needle(self._h, int(v), out), spans_to_numpy, libam().am_spans_free, raw)
 
 
 def near_geometry():

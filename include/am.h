@@ -775,6 +775,71 @@ AM_API void am_ranges_free(am_ranges* r);
 AM_API int am_coords_positions(const am_coords* c, const uint32_t* hay, const uint64_t* pos, uint64_t n, int unit, uint64_t* out /* host arrays */);
 AM_API int am_coords_positions_device(const am_coords* c, const void* d_hay, const void* d_pos, uint64_t n, int unit, void* d_out /* HBM, the calling stream */);
 
+/* ---- postings: the spans of a result by NEEDLE -- a positional inverted index, document frequencies, the concordance of one term, in HBM ---------------
+ * Every other result is keyed by haystack.  The transposed questions -- where does each term occur, in how many documents does it occur (the IDF half of TF-IDF),
+ * show every occurrence of this one term with context -- need the rows of a spans result ordered by needle: a stable sort by a small integer key, done in HBM.
+ * THE DEFINITION.  S is a spans result with n = am_spans_size(S) rows -- AM_SPANS_ALL or AM_SPANS_LEFTMOST_LONGEST, with or without a word class, in any unit --
+ * and N the n_needles of the table it was made with.
+ *   perm         the STABLE sort of 0 .. n-1 by S.data[i].needle
+ *   data[k]      S.data[perm[k]], the same 24-byte am_span
+ *   source[k]    perm[k] as uint64: the row of S that data[k] came from.  It carries am_ranges rows, am_near pair indices or a caller's own per-span array through
+ *                the permutation
+ *   offsets[v]   for v = 0 .. N: the number of rows with needle < v.  Row v is [offsets[v], offsets[v+1]); a needle that never occurs has an empty row;
+ *                offsets[v+1] - offsets[v] equals am_count_spans_by_needle_batch's counts[v] in AM_SPANS_ALL mode.  Inside a row the entries ascend by (haystack, then
+ *                S's own order), because S does
+ *   doc_freq[v]  uint64[N]: the distinct haystacks in row v -- the k of the row that are its first entry or have data[k].haystack != data[k-1].haystack
+ * Everything is bit-identical from run to run.  Needles nike (0) and shoe (1), texts "shoe nike shoe" and "nike", case sensitive, AM_SPANS_ALL:
+ *   S         (0,4,h0,1) (5,4,h0,0) (10,4,h0,1) (0,4,h1,0)            as (start, len, haystack, needle)
+ *   offsets   [0,2,4]
+ *   data      (5,4,h0,0) (0,4,h1,0) (0,4,h0,1) (10,4,h0,1)
+ *   source    [1,3,0,2]
+ *   doc_freq  [2,1]
+ * THE SORT (csrc/am_postings.hip, am_postings.h) is a least-significant-digit radix sort over (needle uint32, row index uint32) pairs in plain launches: no
+ * workgroup waits for another.  passes = 0 for N <= 1, else ceil(bitlen(N-1) / 8), 4 at the most; the bits are divided evenly among the passes.  Per pass a count
+ * table per tile, the library's exclusive sum over it, and a scatter whose order inside a tile comes from wavefront ballots, not from the order of atomics.  Then one
+ * gather of the 24-byte rows, a binary search per needle for the offsets, and a segmented count for doc_freq.
+ * The sort never reads start or len: converted spans (am_coords_spans) are accepted and the result carries S's unit, mode, source size and haystack count.
+ * LIMIT: n >= 0xFFFFFFFF rows are AM_ERR_UNSUPPORTED (the sort carries 32-bit row indices; am_batch_from_fragments has the same limit).  That is 96 GiB of spans:
+ * no test reaches it.  WORKSPACE, freed when the call returns: 16 bytes per span (two key and two index arrays that take turns) and, per pass, 12 bytes per digit
+ * value and tile of am_postings_geometry's tile_spans spans -- at most 3 KiB per tile, 0.4 bytes per span.  The result holds 32 bytes per span (data, source) and
+ * 16 bytes per needle (offsets, doc_freq).  Nothing crosses to the host during the stage.  Record memory is NOT bounded in am_postings_batch, as in am_spans_batch.
+ *   am_postings_from_spans  the stage alone over a spans result the caller holds.  AM_ERR_UNSUPPORTED for a result whose rows are not in HBM.
+ *   am_postings_batch       am_spans_batch(t, case_mode, spans_mode, b) and the stage.  AM_ERR_INVALID for table and batch on different devices.
+ *   am_postings             the one-shot form on host slices (the calling thread's one-shot batch).
+ *   am_postings_size / _needles / _haystacks   n, N and S's haystack count.
+ *   am_postings_offsets / _data / _source / _doc_freq   host copies, made on first use: N + 1, n, n and N entries.  Never NULL on success: an array without entries is
+ *                           one placeholder element.
+ *   am_postings_device_*    the arrays in HBM, NULL where there is nothing: a result without rows (n == 0: no haystacks, no spans, N == 0) keeps nothing in HBM, its
+ *                           offsets are N + 1 zeros ([0] for N == 0) and its doc_freq N zeros.
+ *   am_spans_of_needle      row `needle` as a spans result of its own, with S's haystack count, source size, mode, unit and n_needles: the per-haystack offsets are
+ *                           rebuilt in HBM, one binary search per haystack over the row's haystack field; the row is a device-to-device copy.  What crosses: the
+ *                           row's two offsets.  A subset of leftmost-longest spans still ascends and does not overlap, so am_fragments_from_spans (EACH and MERGED),
+ *                           am_coords_* and am_batch_substitute take it as any spans result; a row of converted-unit postings is refused by the byte-span stages as
+ *                           converted spans are.  The concordance of one term AMONG THE DICTIONARY'S matches: a one-needle automaton cannot give that under
+ *                           leftmost-longest or whole words.  AM_ERR_INVALID for needle >= N.
+ *   am_postings_geometry    for tests, known without a device: the spans of a workgroup tile, the consecutive spans of a wavefront's portion (a round is 64 of
+ *                           them), the passes for n_needles and the bits each pass sorts, lowest first (bits[4], zero beyond passes).
+ * Arguments are checked before any device work: AM_ERR_INVALID for null handles or a null out, a case_mode or spans_mode that is neither of the two, slices without
+ * memory, n_hay >= 0xFFFFFFFF, needle >= N.  *out is NULL after every failure. */
+struct am_postings;                                     /* (no typedef: am_postings alone names the one-shot entry point, as am_spans does) */
+AM_API int am_postings_from_spans(const struct am_spans* s, struct am_postings** out);
+AM_API int am_postings_batch(const am_span_table* t, int case_mode, int spans_mode, const am_batch* b, struct am_postings** out);
+AM_API int am_postings(const am_span_table* t, int case_mode, int spans_mode, const am_slice* hay, size_t n_hay, struct am_postings** out);
+AM_API uint64_t am_postings_size(const struct am_postings* p);
+AM_API uint64_t am_postings_needles(const struct am_postings* p);
+AM_API uint64_t am_postings_haystacks(const struct am_postings* p);
+AM_API const uint64_t* am_postings_offsets(struct am_postings* p);      /* N + 1 */
+AM_API const am_span* am_postings_data(struct am_postings* p);
+AM_API const uint64_t* am_postings_source(struct am_postings* p);
+AM_API const uint64_t* am_postings_doc_freq(struct am_postings* p);     /* N */
+AM_API const void* am_postings_device_offsets(const struct am_postings* p);
+AM_API const void* am_postings_device_data(const struct am_postings* p);
+AM_API const void* am_postings_device_source(const struct am_postings* p);
+AM_API const void* am_postings_device_doc_freq(const struct am_postings* p);
+AM_API void am_postings_free(struct am_postings* p);
+AM_API int am_spans_of_needle(const struct am_postings* p, uint32_t needle, struct am_spans** out);
+AM_API void am_postings_geometry(uint64_t n_needles, uint32_t* tile_spans, uint32_t* wave_spans, uint32_t* passes, uint32_t* bits /* [4] */);
+
 /* Checksum of the fold sequence of a result (harness aid; SURVEY 8d "parity check at scale",
  * benchmark/benchmark.py:65-69 asserts count identity on every run).  For every haystack i < n_hay:
  *   hash_out[i]  = foldl (\h (pos, v) -> h * 0x100000001B3 + mix pos v) 0  over the matches the reference's

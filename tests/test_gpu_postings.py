@@ -1,0 +1,390 @@
+"""Postings on the device (am_postings_* / am_spans_of_needle, csrc/am_postings.hip) against the definition.  Every check compares offsets, data, source and doc_freq
+with what tests/postings_reference.py says -- sorted() by needle over the oracle's spans, or over literal rows where every span is one byte -- never with another
+path of the library.  Shapes sit on the real seams: the 64 spans of a round, a wavefront's portion and a workgroup's tile of the sort, and the digit boundaries of
+every pass (am_postings_geometry)."""
+import ctypes as C
+import random
+import string
+
+import numpy as np
+import pytest
+
+import alfred_margaret_amd as am
+from tests import coords_reference as cref, extract_reference as xref, postings_reference as ref, words_reference as wref
+from tests.helpers import fragment_case
+from tests.test_gpu_select import Batch, lib, lowered
+
+pytestmark = pytest.mark.gpu
+
+ROUTES = {"default": 0, "suffix_filter": 2, "table_walk": 3}
+ALL, LL = am.api.SPANS_ALL, am.api.SPANS_LEFTMOST_LONGEST
+ALPHA = string.ascii_letters + string.digits + "-_"        # 64 one-byte needles: N = 64 is one pass of 6 bits, and a round of 64 spans can hold every digit value
+assert len(set(ALPHA)) == 64
+
+
+@pytest.fixture(params=sorted(ROUTES))
+def route(request):
+    if request.param == "table_walk":
+        am.debug_set("AM_DFA", 1)                          # (read when an image is flattened: every automaton whose table fits gets a DFA section)
+    yield request.param
+    am.debug_set("AM_DFA", -1)
+
+
+class Dict:
+    """An automaton on a route and its span table."""
+
+    def __init__(self, needles, route="default", word_bytes=None, n_needles=None, values=None, lengths=None):
+        self.a = am.Automaton(needles, values)
+        self.a.set_kernel(ROUTES[route])
+        self.t = am.SpanTable(self.a, n_needles, lengths=lengths, word_bytes=word_bytes)
+        self.n = self.t.n_needles
+
+
+def arrays(x):
+    return (x.offsets, x.spans, x.source, x.doc_freq) if isinstance(x, am.Postings) else x
+
+
+def tuples(spans):
+    return list(zip(spans["start"].tolist(), spans["len"].tolist(), spans["haystack"].tolist(), spans["needle"].tolist()))
+
+
+def first_difference(got, want):
+    k = next((j for j in range(min(len(got), len(want))) if got[j] != want[j]), min(len(got), len(want)))
+    return k, got[k:k + 3], want[k:k + 3], len(got), len(want)
+
+
+def check_postings(x, rows, n_needles, what=None):
+    """One result against the definition: offsets, data, source, doc_freq, the shapes and the types."""
+    offsets, data, source, doc_freq = ref.postings(rows, n_needles)
+    if isinstance(x, am.Postings):
+        assert (x.size, x.n_needles, x.n_hay) == (len(data), n_needles, len(rows)), what
+    go, gd, gs, gf = arrays(x)
+    assert go.dtype == gs.dtype == gf.dtype == np.uint64 and gd.dtype == am.api.SPAN_DTYPE, what
+    assert go.tolist() == offsets, (what, "offsets", first_difference(go.tolist(), offsets))
+    assert tuples(gd) == data, (what, "data", first_difference(tuples(gd), data))
+    assert gs.tolist() == source, (what, "source", first_difference(gs.tolist(), source))
+    assert gf.tolist() == doc_freq, (what, "doc_freq", first_difference(gf.tolist(), doc_freq))
+    return offsets, data, source, doc_freq
+
+
+def all_forms(d, case, mode, hays):
+    """am_postings, am_postings_batch, am_postings_from_spans over a held spans result and the numpy definition over the library's spans: four results that must be one."""
+    p1 = d.t.postings_texts(case, hays, mode)
+    with Batch(hays) as b:
+        p2 = d.t.postings_batch(case, b, mode)
+        raw = d.t.spans_batch(case, b, mode, raw=True)
+        try:
+            p3 = d.t.postings_from_spans(raw)
+            so, sp = am.api.spans_to_numpy(raw)
+        finally:
+            lib().am_spans_free(raw)
+    return [p1, p2, p3, am.api.postings_host(so, sp, d.n)]
+
+
+def check_forms(d, case, mode, hays, rows, what=None):
+    for form, x in enumerate(all_forms(d, case, mode, hays)):
+        out = check_postings(x, rows, d.n, (what, "form", form))
+    return out
+
+
+# ---- 1. fragment pools: four forms, three routes, both case modes, both span modes
+
+@pytest.mark.parametrize("seed", range(3))
+def test_fragment_pool_postings(route, seed):
+    rng = random.Random(9900 + seed)
+    n_rows = 0
+    for i in range(8):
+        needles, hays = fragment_case(rng)
+        if i % 4 == 1:
+            hays = hays + [""]
+        if route == "table_walk" and ("" in needles or not any(needles)):
+            continue                                       # the empty needle: no DFA section (the dense route reports those)
+        for case in (0, 1):
+            ns = lowered(needles) if case else needles
+            d = Dict(ns, route)
+            for mode in (ALL, LL):
+                rows = ref.rows_of(ns, case, hays, mode)
+                n_rows += len(check_forms(d, case, mode, hays, rows, (seed, i, case, mode, ns, hays))[1])
+    assert n_rows >= 1
+
+
+# ---- 2. span-count seams: one-byte needles over literal text, so that the span index is the byte index and the spans are known exactly
+
+def literal_rows(hays, handle_of):
+    return [[(i, 1, handle_of[ch]) for i, ch in enumerate(h)] for h in hays]
+
+
+def seam_counts(n_needles):
+    tile, wave, _, _ = am.api.postings_geometry(n_needles)
+    return [0, 1, 63, 64, 65, wave - 1, wave, wave + 1, tile - 1, tile, tile + 1, 2 * tile + 1, 3 * tile + wave + 1]
+
+
+def pattern(name, n, rng):
+    if name == "one needle":
+        return ALPHA[5] * n
+    if name == "two alternating":
+        return (ALPHA[0] + ALPHA[63]) * (n // 2) + ALPHA[0] * (n % 2)
+    if name == "every digit in a round":
+        out = []
+        while len(out) < n:
+            out += rng.sample(ALPHA, 64)
+        return "".join(out[:n])
+    hot = ALPHA[7] + ALPHA[8] + ALPHA[40] + ALPHA[63]
+    return "".join(rng.choice(hot) if rng.random() < 0.5 else rng.choice(ALPHA) for _ in range(n))
+
+
+@pytest.fixture(scope="module")
+def alpha_dict():
+    return Dict(list(ALPHA))
+
+
+@pytest.mark.parametrize("name", ["one needle", "two alternating", "every digit in a round", "skewed random"])
+def test_span_counts_at_the_seams_of_the_sort(alpha_dict, name):
+    rng = random.Random(9910)
+    handle_of = {ch: v for v, ch in enumerate(ALPHA)}
+    assert am.api.postings_geometry(64)[2:] == (1, [6])
+    for n in seam_counts(64):
+        text = pattern(name, n, rng)
+        assert len(text) == n
+        hays = [text[:n // 3], text[n // 3:2 * n // 3], "", text[2 * n // 3:]]      # (the spans of the batch are the bytes of the text, in order)
+        x = alpha_dict.t.postings_texts(0, hays, ALL)
+        offsets, data, source, doc_freq = check_postings(x, literal_rows(hays, handle_of), 64, (name, n))
+        if name == "one needle":
+            assert source == list(range(n)) and offsets == [0] * 6 + [n] * 59 and sum(doc_freq) == doc_freq[5] == sum(1 for h in hays if h)
+        if name == "every digit in a round" and n >= 64:
+            assert all(b > a for a, b in zip(offsets, offsets[1:]))      # every needle occurs
+
+
+# ---- 3. pass seams: handles of the caller's own at 0, N - 1 and on either side of every digit boundary the plan reports
+
+def seam_handles(n_needles):
+    _, _, passes, bits = am.api.postings_geometry(n_needles)
+    hs = {0, n_needles - 1, (n_needles - 1) ^ 1}           # ..., a pair that differs in the lowest digit only
+    shift = 0
+    for b in bits[:-1]:
+        shift += b
+        hs |= {(1 << shift) - 1, 1 << shift}               # either side of a digit boundary
+    if passes:
+        top = sum(bits[:-1])
+        hs |= {1, 1 | (1 << top), (n_needles - 1) & ~(1 << (sum(bits) - 1))}      # pairs that differ in the highest digit only
+    return sorted(h for h in hs if 0 <= h < n_needles)
+
+
+@pytest.mark.parametrize("n_needles", [1, 2, 256, 257, 65536, 65537, 2 ** 24 + 2])
+def test_handles_on_either_side_of_every_digit_boundary(n_needles):
+    _, _, passes, bits = am.api.postings_geometry(n_needles)
+    assert passes == {1: 0, 2: 1, 256: 1, 257: 2, 65536: 2, 65537: 3, 2 ** 24 + 2: 4}[n_needles]
+    handles = seam_handles(n_needles)
+    letters = string.ascii_lowercase[:len(handles)]
+    assert len(letters) == len(handles) and (n_needles < 4 or len(handles) >= 4)
+    handle_of = dict(zip(letters, handles))
+    ones = np.ones(n_needles, np.uint32)
+    d = Dict(list(letters), values=handles, n_needles=n_needles, lengths=(ones, ones))
+    rng = random.Random(9920 + passes)
+    hays = ["".join(rng.choice(letters) for _ in range(rng.choice([0, 1, 64, 65, 300]))) for _ in range(9)] + [letters[::-1] * 3, letters[-1] + letters[0]]
+    rows = literal_rows(hays, handle_of)
+    data, source, df = ref.postings_sparse(rows)
+    assert len(set(x[3] for x in data)) == len(handles)     # every handle occurs
+    for mode in (ALL, LL):
+        with d.t.postings_texts(0, hays, mode) as x:
+            assert (x.size, x.n_needles, x.n_hay) == (len(data), n_needles, len(hays))
+            go, gd, gs, gf = arrays(x)
+        assert tuples(gd) == data, first_difference(tuples(gd), data)
+        assert gs.tolist() == source
+        want = np.searchsorted(np.asarray([r[3] for r in data], np.uint64), np.arange(n_needles + 1, dtype=np.uint64), side="left")
+        assert go.shape == (n_needles + 1,) and np.array_equal(go, want.astype(np.uint64))      # all N + 1 offsets
+        want_df = np.zeros(n_needles, np.uint64)
+        for v, k in df.items():
+            want_df[v] = k
+        assert gf.shape == (n_needles,) and np.array_equal(gf, want_df)      # zero wherever a row is empty
+        assert not gf[np.diff(go) == 0].any()
+
+
+# ---- 4. document frequency
+
+def test_document_frequencies_across_wavefronts_and_tiles():
+    tile, wave, _, _ = am.api.postings_geometry(2)
+    d = Dict(["a", "b"])
+    handle_of = {"a": 0, "b": 1}
+    count = tile + wave + 1
+    # one needle, one haystack: the row crosses wavefronts and a tile inside that haystack
+    hays = ["a" * count, "b"]
+    _, _, _, df = check_postings(d.t.postings_texts(0, hays, ALL), literal_rows(hays, handle_of), 2, "one haystack")
+    assert df == [1, 1]
+    # the same count, one per haystack, haystacks without a match in between
+    hays = []
+    for k in range(count):
+        hays += ["a"] + (["", "zz"] if k % 97 == 0 else [])
+    rows = [[(0, 1, 0)] if h == "a" else [] for h in hays]
+    _, _, _, df = check_postings(d.t.postings_texts(0, hays, ALL), rows, 2, "one per haystack")
+    assert df == [count, 0]
+    # two needles interleaved in haystacks of 1 to 5 bytes: needle runs and haystack runs end inside one wavefront
+    rng = random.Random(9930)
+    hays = []
+    for k in range(700):
+        hays.append("".join(rng.choice("ab") for _ in range(rng.randint(1, 5))) if k % 7 else rng.choice(["", "zzz", "ab" * 40]))
+    rows = [[(i, 1, handle_of[ch]) for i, ch in enumerate(h) if ch in handle_of] for h in hays]
+    offsets, _, _, df = check_postings(d.t.postings_texts(0, hays, ALL), rows, 2, "interleaved")
+    assert 0 < df[0] < offsets[1] and 0 < df[1] < offsets[2] - offsets[1]
+
+
+# ---- 5. one needle's row as a spans result
+
+def check_row(p, rows, needle, what=None):
+    offsets, data, kept = ref.spans_of(rows, needle)
+    go, gs = p.spans_of(needle)
+    assert go.dtype == np.uint64 and go.tolist() == offsets, (what, needle, "offsets", first_difference(go.tolist(), offsets))
+    assert tuples(gs) == data, (what, needle, "rows", first_difference(tuples(gs), data))
+    assert tuples(p.row(needle)) == data, (what, needle, "row")
+    return kept
+
+
+@pytest.mark.parametrize("n_hay", [1, 255, 256, 257])
+def test_the_row_of_a_needle_as_spans(n_hay):
+    needles = ["the", "he", "rare", "absent", "t"]
+    rng = random.Random(9940 + n_hay)
+    words = ["the", "he", "then", "other", "x", "tt", " "]
+    hays = [" ".join(rng.choice(words) for _ in range(rng.randint(0, 12))) if rng.random() < 0.4 else "" for _ in range(n_hay)]
+    hays[n_hay // 2] = "the rare other"
+    hays[-1] = "he then rare" if n_hay > 1 else "the rare he other"
+    d = Dict(needles)
+    for mode in (ALL, LL):
+        rows = ref.rows_of(needles, 0, hays, mode)
+        with Batch(hays) as b, d.t.postings_batch(0, b, mode) as p:
+            check_postings(p, rows, 5, (n_hay, mode))
+            for needle in (0, 1, 2, 3, 4):
+                kept = check_row(p, rows, needle, (n_hay, mode))
+                found = sum(map(len, kept))                # frequent (the, he, t), rare, absent; under leftmost-longest `t` loses to `the` and may have no row
+                assert found == 0 if needle == 3 else found >= 1 or (mode == LL and needle == 4), (n_hay, mode, needle)
+                raw = p.spans_of(needle, raw=True)
+                try:
+                    assert lib().am_spans_haystacks(raw) == n_hay
+                    for merged in ([False, True] if mode == LL else [False]):
+                        want_off, want_fr, want_texts = xref.fragments(hays, kept, 3, 2, xref.MERGED if merged else xref.EACH)
+                        fo, fr = d.t.fragments_from_spans(b, raw, 3, 2, merged)
+                        assert fo.tolist() == want_off and list(zip(fr["start"].tolist(), fr["len"].tolist())) == want_fr, (n_hay, mode, needle, merged)
+                finally:
+                    lib().am_spans_free(raw)
+            out = C.c_void_p(1)
+            for bad in (5, 6, 0xFFFFFFFF):
+                assert lib().am_spans_of_needle(p.handle, bad, C.byref(out)) == am.AM_ERR_INVALID and not out.value and b"needle" in lib().am_last_error()
+                out.value = 1
+        if mode == LL:
+            for needle in (0, 1, 3):
+                kept = ref.spans_of(rows, needle)[2]
+                assert d.a.concordance(0, hays, needles[needle], before=3, after=2) == xref.fragments(hays, kept, 3, 2, xref.EACH)[2]
+    assert d.a.concordance(0, ["a the he"], 1, after=1, leftmost_longest=False) == [b"he ", b"he"]      # by index; ALL: he inside the is an occurrence
+    assert d.a.concordance(0, ["a the he"], "he", after=1) == [b"he"]                                    # leftmost-longest: it is not
+
+
+# ---- 6. inherited semantics
+
+def test_handles_beyond_the_table_are_absent():
+    needles = ["ab", "b", "abc", "c"]
+    hays = ["abcab", "", "cabc", "bbb"]
+    for n in (3, 1, 0):
+        d = Dict(needles, n_needles=n)
+        for mode in (ALL, LL):
+            rows = ref.rows_of(needles, 0, hays, mode, n=n)
+            check_forms(d, 0, mode, hays, rows, ("n_needles", n, mode))
+
+
+def test_a_word_class_gives_whole_word_postings():
+    needles = ["he", "the", "said", "not"]
+    hays = ["the he said not", "she said he did not", "he said; not the", "theatre he not", ""]
+    d = Dict(needles, word_bytes=True)
+    for mode in (ALL, LL):
+        rows = wref.spans(ref.machine(needles), 0, mode, needles, hays, wref.DEFAULT_CLASS)
+        offsets, _, _, df = check_forms(d, 0, mode, hays, rows, ("words", mode))
+        assert np.diff(offsets).tolist() == [4, 2, 3, 4] and df == [4, 2, 3, 4]      # he in the / she / theatre: no row
+    plain = ref.postings(ref.rows_of(needles, 0, hays), 4)
+    assert np.diff(plain[0]).tolist() == [8, 3, 3, 4] and plain[3] == [4, 3, 3, 4]
+    assert d.a.doc_freq(0, hays, whole_words=True).tolist() == [4, 2, 3, 4] and d.a.doc_freq(0, hays).tolist() == plain[3]
+
+
+@pytest.mark.parametrize("unit", [am.CODE_POINTS, am.UTF16])
+def test_postings_of_converted_spans_carry_the_unit(unit):
+    needles = ["nike", "é", "\U0001f600"]
+    hays = ["é NIKE \U0001f600 nike", "", "\U0001f600\U0001f600é", "plain nike"]
+    d = Dict(needles)
+    rows = ref.rows_of(needles, 1, hays, ref.LEFTMOST_LONGEST)
+    _, conv, _ = cref.convert_rows(hays, rows, unit)
+    it = iter(conv)
+    crows = [[next(it) + (r[2],) for r in row] for row in rows]
+    assert crows != rows
+    out = C.c_void_p(1)
+    with Batch(hays) as b:
+        raw = d.t.spans_batch(1, b, LL, raw=True)
+        c = am.Coords(b, utf16=unit == am.UTF16)
+        try:
+            craw = c.spans(raw, unit, raw=True)
+            try:
+                with d.t.postings_from_spans(craw) as p:
+                    check_postings(p, crows, 3, unit)
+                    check_row(p, crows, 0, unit)
+                    row = p.spans_of(0, raw=True)          # a row of converted-unit postings: refused by the byte-span stages as converted spans are
+                    try:
+                        assert lib().am_fragments_from_spans(b, row, 1, 1, am.api.EXTRACT_EACH, C.byref(out)) == am.AM_ERR_INVALID and not out.value
+                        assert b"converted" in lib().am_last_error()
+                    finally:
+                        lib().am_spans_free(row)
+            finally:
+                lib().am_spans_free(craw)
+        finally:
+            lib().am_spans_free(raw)
+            del c
+
+
+# ---- 7. determinism and identities
+
+def test_two_calls_agree_and_the_counts_are_the_library_s_own():
+    rng = random.Random(9950)
+    needles = ["nike", "shoe", "kids", "sale", "s", "never"]
+    words = needles[:5] + ["and", "for", "the", "x"]
+    hays = [" ".join(rng.choice(words) for _ in range(rng.randint(0, 40))) for _ in range(600)]
+    d = Dict(needles)
+    rows = ref.rows_of(needles, 0, hays)
+    with Batch(hays) as b:
+        x, y = d.t.postings_batch(0, b, ALL), d.t.postings_batch(0, b, ALL)
+        check_postings(x, rows, 6)
+        for u, v in zip(arrays(x), arrays(y)):
+            assert np.array_equal(u, v) and u.tobytes() == v.tobytes()
+        assert x.size > 8192                               # more than one tile of the sort
+        # cross-checks, beside the reference: the row lengths are the library's span counts, the document frequencies the matrix's columns
+        assert np.array_equal(np.diff(x.offsets), d.t.count_by_needle_batch(0, b))
+        _, entries = d.t.values.count_matrix_batch(0, b)
+        assert np.array_equal(x.doc_freq, np.bincount(entries["needle"], minlength=6).astype(np.uint64))
+        assert x.doc_freq[5] == 0 and x.doc_freq[:5].all()
+
+
+# ---- 8. empty shapes
+
+def test_empty_shapes():
+    d = Dict(["a", "b", "c"])
+    # no haystacks
+    for mode in (ALL, LL):
+        for x in all_forms(d, 0, mode, []):
+            check_postings(x, [], 3, "no haystacks")
+    with d.t.postings_texts(1, [], ALL) as x:
+        assert (x.size, x.n_needles, x.n_hay) == (0, 3, 0) and x.offsets.tolist() == [0, 0, 0, 0] and x.doc_freq.tolist() == [0, 0, 0]
+        assert x.spans.shape == (0,) and x.source.shape == (0,)
+        for f in (lib().am_postings_device_offsets, lib().am_postings_device_data, lib().am_postings_device_source, lib().am_postings_device_doc_freq):
+            assert not f(x.handle)
+        go, gs = x.spans_of(2)
+        assert go.tolist() == [0] and gs.shape == (0,)
+    # no span at all
+    hays = ["", "zz", ""]
+    for x in all_forms(d, 0, ALL, hays):
+        check_postings(x, [[], [], []], 3, "no spans")
+    with d.t.postings_texts(0, hays, LL) as x:
+        go, gs = x.spans_of(0)
+        assert go.tolist() == [0, 0, 0, 0] and gs.shape == (0,)
+    # N == 0
+    d0 = Dict(["a", "b"], n_needles=0)
+    for hs in ([], ["ab", "", "ba"]):
+        for x in all_forms(d0, 0, ALL, hs):
+            check_postings(x, [[] for _ in hs], 0, "no needles")
+        with d0.t.postings_texts(0, hs, ALL) as x:
+            assert x.offsets.tolist() == [0] and x.doc_freq.shape == (0,) and x.n_needles == 0
+            out = C.c_void_p(1)
+            assert lib().am_spans_of_needle(x.handle, 0, C.byref(out)) == am.AM_ERR_INVALID and not out.value
