@@ -75,7 +75,7 @@ def build_libam(force=False):
     obj_dir = os.path.join(LIB, "obj")
     os.makedirs(obj_dir, exist_ok=True)
     target = os.path.join(LIB, "libam.so")
-    names = ("am_abi.cpp", "am_run.cpp", "am_replacer.cpp", "am_contains_all.cpp", "am_splitter.cpp", "am_spans.cpp", "am_subst.cpp", "am_select.cpp", "am_extract.cpp", "am_coords.cpp", "am_rules.cpp", "am_score.cpp", "am_near.cpp", "am_postings.cpp", "am_flatten.cpp", "am_kernels.hip", "am_dfa.hip", "am_scan.hip", "am_replace.hip", "am_rploop.hip", "am_rplds.hip", "am_dense.hip", "am_records.hip", "am_hist.hip", "am_matrix.hip", "am_split.hip", "am_spans.hip", "am_subst.hip", "am_select.hip", "am_extract.hip", "am_coords.hip", "am_rules.hip", "am_score.hip", "am_near.hip", "am_postings.hip", "am_multi.cpp")
+    names = ("am_abi.cpp", "am_run.cpp", "am_replacer.cpp", "am_contains_all.cpp", "am_splitter.cpp", "am_spans.cpp", "am_subst.cpp", "am_select.cpp", "am_extract.cpp", "am_coords.cpp", "am_rules.cpp", "am_score.cpp", "am_near.cpp", "am_postings.cpp", "am_flatten.cpp", "am_kernels.hip", "am_dfa.hip", "am_scan.hip", "am_replace.hip", "am_rploop.hip", "am_rplds.hip", "am_dense.hip", "am_records.hip", "am_hist.hip", "am_matrix.hip", "am_chain.hip", "am_split.hip", "am_spans.hip", "am_subst.hip", "am_select.hip", "am_extract.hip", "am_coords.hip", "am_rules.hip", "am_score.hip", "am_near.hip", "am_postings.hip", "am_multi.cpp")
     srcs = [os.path.join(CSRC, f) for f in names if os.path.exists(os.path.join(CSRC, f))]
     headers = [d for d in _glob_deps(CSRC) if d.endswith((".h", ".hpp", ".inc"))] + [os.path.join(ROOT, "include", "am.h"), os.path.join(ROOT, "include", "am_debug.h")]
     objs = [os.path.join(obj_dir, os.path.basename(f) + ".o") for f in srcs]

@@ -32,8 +32,8 @@ enum Key {
     kHistRecordsMiB,      // AM_HIST_RECORDS_MIB: MiB of match records am_count_by_needle* keeps in HBM at a time (tests: 1 = many groups of haystacks); unset: 1024
     kHistTrace,           // AM_HIST_TRACE: the instrumented instantiation of k_needle_hist counts the adds its LDS tables absorbed and the adds that went to HBM (am_debug_hist_adds, tests/measure/needle_counts.py)
     kHistFlushTiles,      // AM_HIST_FLUSH_TILES: tiles after which a workgroup of k_needle_hist flushes and clears its LDS counts (tests: 1 = after every tile); unset: 2048, the most that cannot wrap a counter
-    kSplitChainLimit,     // AM_SPLIT_CHAIN_LIMIT: records the lane of a chain's head looks at in k_split_walk before the chain is left to the pointer-doubling rounds (tests: 1 = the head looks at one record: chains of three records and more go to the rounds); unset: 32
-    kSpansChainLimit,     // AM_SPANS_CHAIN_LIMIT: the same for the candidates of am_spans* in leftmost-longest mode (k_spans_walk); unset: 32
+    kSplitChainLimit,     // AM_SPLIT_CHAIN_LIMIT: records the lane of a chain's head looks at in k_chain_walk (am_chain.h) before the chain is left to the pointer-doubling rounds (tests: 1 = the head looks at one record: chains of three records and more go to the rounds); unset: 32
+    kSpansChainLimit,     // AM_SPANS_CHAIN_LIMIT: the same for the candidates of am_spans* in leftmost-longest mode; unset: 32
     kRulesRowsMiB,        // AM_RULES_ROWS_MIB: MiB of slot rows am_rules_eval_batch keeps in HBM at a time (tests: 0 = the smallest group, 64 haystacks); unset: 1024
     kCount
 };

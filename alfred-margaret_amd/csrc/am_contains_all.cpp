@@ -453,12 +453,7 @@ struct MatrixBuild {
         std::unique_ptr<Part> part(new Part());
         part->h0 = h0; part->n = n;
         AM_TRY(part->offsets.ensure(((size_t)n + 1) * 8));
-        size_t tmp_bytes = 0;
-        HIP_TRY(scan_temp_bytes((uint64_t)n + 1, &tmp_bytes));
-        AM_TRY(scan_tmp.ensure(tmp_bytes));
-        HIP_TRY(launch_scan(scan_tmp.p, scan_tmp.cap, (const uint32_t*)row_entries.p, (uint64_t*)part->offsets.p, (uint64_t)n + 1, st));
-        HIP_TRY(hipMemcpyAsync(&part->entries, (const uint64_t*)part->offsets.p + n, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        AM_TRY(exclusive_sum(scan_tmp, (const uint32_t*)row_entries.p, (uint64_t*)part->offsets.p, (uint64_t)n + 1, st, &part->entries));
         const uint64_t n_ent = part->entries;
         if (n_ent == 0) return AM_OK;                       // (every handle was beyond the table)
         if (n_ent > keys_max) return fail(AM_ERR_HIP, "am_count_matrix: more entries than the group's table was sized for");

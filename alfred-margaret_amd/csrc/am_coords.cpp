@@ -135,13 +135,10 @@ extern "C" int am_coords_create(const am_batch* b, uint32_t what, am_coords** ou
     }
     { Prof pr("coords_tiles", st);
       HIP_TRY(launch_coords_tiles((const uint8_t*)b->d_text, b->total, d_counts, st)); }
-    size_t tmp_bytes = 0;
-    HIP_TRY(scan_temp_bytes(n, &tmp_bytes));
-    AM_TRY(scan_tmp.ensure(tmp_bytes));
     for (uint32_t k = 0; k < kCoordsClasses; k++) {
         if (!d_counts[k]) continue;
         Prof pr("coords_scan", st);
-        HIP_TRY(launch_scan(scan_tmp.p, scan_tmp.cap, d_counts[k], (uint64_t*)c->prefix[k].p, n, st));
+        AM_TRY(exclusive_sum(scan_tmp, d_counts[k], (uint64_t*)c->prefix[k].p, n, st));
     }
     HIP_TRY(hipStreamSynchronize(st));                      // (the workspaces are freed; the index may be used from any thread and stream afterwards)
     *out = c.release();

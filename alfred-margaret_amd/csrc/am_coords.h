@@ -8,17 +8,12 @@
 // round_up(total, 16), which every batch can read; a lookup at a tile boundary loads no text at all.  Internal: nothing here is part of the C ABI.
 // Plain C++: the test program compiles all of it with g++.
 #pragma once
-#include <stdint.h>
+#include "am_rows.h"
 
 #if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
 #include "am_bounds.h"
-#define AM_COORDS_HD __host__ __device__ __forceinline__
-#else
-#define AM_COORDS_HD inline
-#ifndef AM_BOUNDS
+#elif !defined(AM_BOUNDS)
 #define AM_BOUNDS(cond) ((void)0)
-#endif
 #endif
 
 namespace am {
@@ -30,11 +25,11 @@ constexpr uint32_t kCoordsGroup = 16;                       // bytes of an align
 enum CoordsClass : uint32_t { kCoordsStart = 0, kCoordsFour = 1, kCoordsNewline = 2, kCoordsClasses = 3 };
 
 // bits 0, 8, 16, 24 of nz gathered into bits 0 .. 3 (the sixteen partial products land on distinct bits: no carry)
-AM_COORDS_HD uint32_t coords_gather4(uint32_t nz) { return ((nz * 0x01020408u) >> 24) & 0xFu; }
+AM_HD uint32_t coords_gather4(uint32_t nz) { return ((nz * 0x01020408u) >> 24) & 0xFu; }
 
 // bit j (0..3) = byte j of the dword (the lowest address first) belongs to the class
 template <uint32_t CLS>
-AM_COORDS_HD uint32_t coords_bits4(uint32_t w)
+AM_HD uint32_t coords_bits4(uint32_t w)
 {
     if (CLS == kCoordsStart) {
         const uint32_t t = (w & 0xC0C0C0C0u) ^ 0x80808080u; // a byte of t is zero iff the byte is a continuation byte; only its bits 7 and 6 can be set
@@ -48,23 +43,23 @@ AM_COORDS_HD uint32_t coords_bits4(uint32_t w)
 }
 
 struct alignas(16) CoordsWords { uint32_t x, y, z, w; };   // an aligned group as one 16-byte load
-AM_COORDS_HD CoordsWords coords_load(const uint8_t* __restrict__ text, uint64_t g)
+AM_HD CoordsWords coords_load(const uint8_t* __restrict__ text, uint64_t g)
 {
     return *reinterpret_cast<const CoordsWords*>(text + g);
 }
 
 // bit j (0..15) = byte j of the aligned group belongs to the class
 template <uint32_t CLS>
-AM_COORDS_HD uint32_t coords_mask16(const CoordsWords& v)
+AM_HD uint32_t coords_mask16(const CoordsWords& v)
 {
     return coords_bits4<CLS>(v.x) | (coords_bits4<CLS>(v.y) << 4) | (coords_bits4<CLS>(v.z) << 8) | (coords_bits4<CLS>(v.w) << 12);
 }
 
 // the bits [0, n) of a 16-bit mask, n <= 16
-AM_COORDS_HD uint32_t coords_low_bits(uint32_t n) { return (1u << n) - 1u; }
+AM_HD uint32_t coords_low_bits(uint32_t n) { return (1u << n) - 1u; }
 
 // position of the n-th set bit of the 16-bit mask m counted from bit 0, 1 <= n <= popcount(m)
-AM_COORDS_HD uint32_t coords_nth_set(uint32_t m, uint32_t n)
+AM_HD uint32_t coords_nth_set(uint32_t m, uint32_t n)
 {
     uint32_t pos = 0, c;
     c = (uint32_t)__builtin_popcount(m & 0xFFu); if (n > c) { n -= c; pos += 8; m >>= 8; }
@@ -76,7 +71,7 @@ AM_COORDS_HD uint32_t coords_nth_set(uint32_t m, uint32_t n)
 
 // the class bits of the group at q, a multiple of 16, cut at `total`: what the tile pass counts (bytes of the padding never count)
 template <uint32_t CLS>
-AM_COORDS_HD uint32_t coords_group_count(const CoordsWords& v, uint64_t q, uint64_t total)
+AM_HD uint32_t coords_group_count(const CoordsWords& v, uint64_t q, uint64_t total)
 {
     uint32_t m = coords_mask16<CLS>(v);
     if (total - q < kCoordsGroup) m &= coords_low_bits((uint32_t)(total - q));
@@ -95,7 +90,7 @@ inline void coords_tile_counts_host(const uint8_t* text, uint64_t total, uint32_
 // the class count of the bytes [0, g), g <= total: one prefix entry and at most eight groups of g's own tile, the last one cut at g.  Every group read begins below
 // g, so it ends at or before round_up(g, 16) <= padded; g at a tile boundary reads no text.
 template <uint32_t CLS>
-AM_COORDS_HD uint64_t coords_count(const uint8_t* __restrict__ text, const uint64_t* __restrict__ prefix, uint64_t g, uint64_t padded)
+AM_HD uint64_t coords_count(const uint8_t* __restrict__ text, const uint64_t* __restrict__ prefix, uint64_t g, uint64_t padded)
 {
     uint64_t c = prefix[g >> kCoordsTileShift];
     for (uint64_t q = g & ~(uint64_t)(kCoordsTile - 1); q < g; q += kCoordsGroup) {
@@ -107,23 +102,16 @@ AM_COORDS_HD uint64_t coords_count(const uint8_t* __restrict__ text, const uint6
     return c;
 }
 
-// last index in [lo, hi] whose entry is <= x (the array ascends; prefix[lo] <= x): rank inverted to select
-AM_COORDS_HD uint64_t coords_last_at_or_below(const uint64_t* __restrict__ prefix, uint64_t lo, uint64_t hi, uint64_t x)
-{
-    while (lo < hi) { const uint64_t mid = lo + ((hi - lo + 1) >> 1); if (prefix[mid] <= x) lo = mid; else hi = mid - 1; }
-    return lo;
-}
-
 // 1 + the index of the last 0x0A among the bytes [base, g), or base when there is none; base <= g <= total.  n_g / n_base: the newlines of [0, g) / [0, base), which
 // the caller has (coords_count).  The newline wanted is the n_g-th of the text.  It lies in g's own tile when that tile's prefix is below n_g -- the common case --,
 // else in the last tile between base's and g's whose prefix is below n_g, found by a binary search; an n-th-set-bit select inside the tile finishes.  The tile found
 // is g's own (the newline lies below g) or a whole tile below g: every group read ends at or before `padded`.
-AM_COORDS_HD uint64_t coords_linestart(const uint8_t* __restrict__ text, const uint64_t* __restrict__ nl_prefix, uint64_t base, uint64_t g, uint64_t n_g,
+AM_HD uint64_t coords_linestart(const uint8_t* __restrict__ text, const uint64_t* __restrict__ nl_prefix, uint64_t base, uint64_t g, uint64_t n_g,
                                        uint64_t n_base, uint64_t padded)
 {
     if (n_g <= n_base) return base;
     uint64_t t = g >> kCoordsTileShift;
-    if (nl_prefix[t] >= n_g) t = coords_last_at_or_below(nl_prefix, base >> kCoordsTileShift, t - 1, n_g - 1);      // (prefix[tile of base] <= n_base <= n_g - 1)
+    if (nl_prefix[t] >= n_g) t = last_at_or_before(nl_prefix, base >> kCoordsTileShift, t - 1, n_g - 1);      // (prefix[tile of base] <= n_base <= n_g - 1)
     uint64_t n = n_g - nl_prefix[t];
     AM_BOUNDS(n >= 1 && n <= kCoordsTile);
     uint64_t q = t << kCoordsTileShift;
@@ -146,7 +134,7 @@ struct CoordsIn {
 };
 
 // U(g) for unit 0 bytes / 1 code points / 2 UTF-16 code units (AM_UNIT_*), over the bytes [0, g)
-AM_COORDS_HD uint64_t coords_units(const CoordsIn& in, int unit, uint64_t g)
+AM_HD uint64_t coords_units(const CoordsIn& in, int unit, uint64_t g)
 {
     if (unit == 0) return g;
     uint64_t u = coords_count<kCoordsStart>(in.text, in.prefix[kCoordsStart], g, in.padded);
@@ -156,7 +144,7 @@ AM_COORDS_HD uint64_t coords_units(const CoordsIn& in, int unit, uint64_t g)
 
 struct CoordsLineCol { uint64_t line, col, linestart, newlines; };
 // line and column of the byte g of the haystack at base (n_base: the newlines of [0, base)); reuse: a position on the same line whose line start is known (null: none)
-AM_COORDS_HD CoordsLineCol coords_line_col(const CoordsIn& in, int unit, uint64_t base, uint64_t n_base, uint64_t g, const CoordsLineCol* reuse)
+AM_HD CoordsLineCol coords_line_col(const CoordsIn& in, int unit, uint64_t base, uint64_t n_base, uint64_t g, const CoordsLineCol* reuse)
 {
     CoordsLineCol r;
     r.newlines = coords_count<kCoordsNewline>(in.text, in.prefix[kCoordsNewline], g, in.padded);

@@ -18,12 +18,9 @@ namespace dev {
 
 namespace {
 
-constexpr uint32_t kCoThreads = 256;
+constexpr uint32_t kCoThreads = 256;                        // lanes of a k_coords_tiles workgroup
 constexpr uint32_t kCoLoads = 4;                            // groups per lane of the tile pass
 constexpr uint32_t kCoGroupsPerTile = kCoordsTile / kCoordsGroup;
-
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kCoThreads - 1) / kCoThreads); }
-__device__ __forceinline__ uint64_t global_lane() { return (uint64_t)blockIdx.x * kCoThreads + threadIdx.x; }
 
 // a workgroup takes kCoThreads * kCoLoads consecutive groups (128 tiles); n_groups = ceil(total / 16): every group read ends at or before round_up(total, 16)
 __global__ void __launch_bounds__(kCoThreads) k_coords_tiles(const uint8_t* __restrict__ text, uint64_t total, uint64_t n_groups, uint32_t* __restrict__ c_start,
@@ -78,9 +75,9 @@ __device__ __forceinline__ void convert_row(const CoordsIn& in, int unit, uint64
     *u_len = ue - us;
 }
 
-__global__ void __launch_bounds__(kCoThreads) k_coords_spans(CoordsIn in, int unit, const Span* __restrict__ spans, uint64_t n, Span* __restrict__ out)
+__global__ void __launch_bounds__(kRowThreads) k_coords_spans(CoordsIn in, int unit, const Span* __restrict__ spans, uint64_t n, Span* __restrict__ out)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     if (i >= n) return;
     const Span sp = spans[i];
     Span o{0, 0, sp.haystack, sp.needle};
@@ -90,22 +87,22 @@ __global__ void __launch_bounds__(kCoThreads) k_coords_spans(CoordsIn in, int un
 }
 
 // fragments carry no haystack: row i belongs to the last haystack whose offset is <= i (empty rows share an offset with the next one)
-__global__ void __launch_bounds__(kCoThreads) k_coords_fragments(CoordsIn in, int unit, const Fragment* __restrict__ frags, const uint64_t* __restrict__ frag_off, uint64_t n,
+__global__ void __launch_bounds__(kRowThreads) k_coords_fragments(CoordsIn in, int unit, const Fragment* __restrict__ frags, const uint64_t* __restrict__ frag_off, uint64_t n,
                                                                  Fragment* __restrict__ out)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     if (i >= n) return;
     const Fragment f = frags[i];
-    const uint32_t hay = (uint32_t)coords_last_at_or_below(frag_off, 0, (uint64_t)in.n_hay - 1, i);      // (frag_off ascends and frag_off[0] = 0 <= i)
+    const uint32_t hay = (uint32_t)last_at_or_before(frag_off, (uint64_t)0, (uint64_t)in.n_hay - 1, i);      // (frag_off ascends and frag_off[0] = 0 <= i)
     Fragment o{0, 0};
     uint64_t base;
     if (row_in_haystack(in, hay, f.start, f.len, &base)) convert_row(in, unit, base, f.start, f.len, &o.start, &o.len);
     out[i] = o;
 }
 
-__global__ void __launch_bounds__(kCoThreads) k_coords_ranges(CoordsIn in, int unit, const Span* __restrict__ spans, uint64_t n, SpanRange* __restrict__ out)
+__global__ void __launch_bounds__(kRowThreads) k_coords_ranges(CoordsIn in, int unit, const Span* __restrict__ spans, uint64_t n, SpanRange* __restrict__ out)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     if (i >= n) return;
     const Span sp = spans[i];
     SpanRange o{0, 0, 0, 0};
@@ -119,10 +116,10 @@ __global__ void __launch_bounds__(kCoThreads) k_coords_ranges(CoordsIn in, int u
     out[i] = o;
 }
 
-__global__ void __launch_bounds__(kCoThreads) k_coords_positions(CoordsIn in, int unit, const uint32_t* __restrict__ hay, const uint64_t* __restrict__ pos, uint64_t n,
+__global__ void __launch_bounds__(kRowThreads) k_coords_positions(CoordsIn in, int unit, const uint32_t* __restrict__ hay, const uint64_t* __restrict__ pos, uint64_t n,
                                                                  uint64_t* __restrict__ out, uint64_t* __restrict__ flag)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     if (i >= n) return;
     const uint32_t h = hay[i];
     const uint64_t p = pos[i];
@@ -151,30 +148,22 @@ hipError_t launch_coords_tiles(const uint8_t* text, uint64_t total, uint32_t* co
 
 hipError_t launch_coords_spans(const CoordsIn& in, int unit, const Span* spans, uint64_t n, Span* out, hipStream_t st)
 {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_coords_spans, dim3(blocks_for(n)), dim3(kCoThreads), 0, st, in, unit, spans, n, out);
-    return hipGetLastError();
+    return launch_rows(k_coords_spans, n, st, in, unit, spans, n, out);
 }
 
 hipError_t launch_coords_fragments(const CoordsIn& in, int unit, const Fragment* frags, const uint64_t* frag_off, uint64_t n, Fragment* out, hipStream_t st)
 {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_coords_fragments, dim3(blocks_for(n)), dim3(kCoThreads), 0, st, in, unit, frags, frag_off, n, out);
-    return hipGetLastError();
+    return launch_rows(k_coords_fragments, n, st, in, unit, frags, frag_off, n, out);
 }
 
 hipError_t launch_coords_ranges(const CoordsIn& in, int unit, const Span* spans, uint64_t n, SpanRange* out, hipStream_t st)
 {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_coords_ranges, dim3(blocks_for(n)), dim3(kCoThreads), 0, st, in, unit, spans, n, out);
-    return hipGetLastError();
+    return launch_rows(k_coords_ranges, n, st, in, unit, spans, n, out);
 }
 
 hipError_t launch_coords_positions(const CoordsIn& in, int unit, const uint32_t* hay, const uint64_t* pos, uint64_t n, uint64_t* out, uint64_t* flag, hipStream_t st)
 {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_coords_positions, dim3(blocks_for(n)), dim3(kCoThreads), 0, st, in, unit, hay, pos, n, out, flag);
-    return hipGetLastError();
+    return launch_rows(k_coords_positions, n, st, in, unit, hay, pos, n, out, flag);
 }
 
 }  // namespace dev

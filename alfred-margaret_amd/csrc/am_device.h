@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "am_chain.h"
 #include "am_image.h"
 #include "am_subst_tpl.h"
 
@@ -14,9 +15,7 @@ constexpr int kModeAny = 2;     // flags[haystack] = 1 if anything matches
 constexpr int kModeIds = 3;     // Searcher.containsAll: the needle ids of everything that matches into the haystack's bitmap row; flags[haystack] = 1 when the row is full
                                 // (k_sf only: a flag mode like kModeAny -- a flagged haystack is not looked at any further)
 
-// 16-byte match record in HBM.  Same layout as am_match in include/am.h.
-struct alignas(16) Record { uint64_t end_pos; uint32_t haystack; uint32_t state; };
-
+// (Record, the 16-byte match record in HBM: am_rows.h)
 struct ScanOut {
     // general (AC) kernel, two passes: count pass fills unit_counts[u], emit pass writes at unit_offsets[u]
     uint32_t* unit_counts;
@@ -184,13 +183,7 @@ struct SplitIn { const Record* recs; uint64_t n_rec; const uint8_t* text; const 
 // start[i] = sepStart of record i (Splitter.hs:105-107 / :117-121), head[i] = first of its haystack or starting at or after the end of record i - 1, kept = head;
 // kept has n_rec + 1 entries (the last one 0: the scan's trailing element)
 hipError_t launch_split_start(bool ic, const SplitIn& in, uint64_t* start, uint8_t* head, uint32_t* kept, hipStream_t st);
-// greedy selection inside the chains between heads: the head's lane looks at up to `limit` records; *long_chains (cleared by the caller) != 0 when a chain needed more
-hipError_t launch_split_walk(const Record* recs, uint64_t n_rec, const uint64_t* start, const uint8_t* head, uint32_t* kept, uint32_t limit, uint32_t* long_chains, hipStream_t st);
-// ... finished by pointer doubling: jump[i] = next[i] (i itself: none), then rounds of { kept records mark jump_in[i]; jump_out = jump_in o jump_in } until a round leaves
-// *marked (cleared by the caller before each) at 0
-hipError_t launch_split_next(const Record* recs, uint64_t n_rec, const uint64_t* start, const uint8_t* head, uint64_t* jump, hipStream_t st);
-hipError_t launch_split_double(const uint64_t* jump_in, uint64_t* jump_out, uint64_t n_rec, uint32_t* kept, uint32_t* marked, hipStream_t st);
-// kidx = exclusive sum of kept (n_rec + 1), rec_first = first record of every haystack (n_hay + 1): frag_off (n_hay + 1) and the n_frag = kidx[n_rec] + n_hay fragments
+// the greedy selection inside the chains between heads: select_chains (am_fold.h) over a SplitChain (am_chain.h).  With kidx = exclusive sum of kept (n_rec + 1), rec_first = first record of every haystack (n_hay + 1): frag_off (n_hay + 1) and the n_frag = kidx[n_rec] + n_hay fragments
 hipError_t launch_split_emit(const SplitIn& in, const uint64_t* start, const uint32_t* kept, const uint64_t* kidx, const uint64_t* rec_first, uint64_t* frag_off,
                              Fragment* frags, uint64_t n_frag, hipStream_t st);
 // am_batch_from_fragments: lens (n_frag + 1, the last one 0) and the source position of every fragment; then, with dst_off = exclusive sum of lens, the bytes
@@ -207,7 +200,7 @@ struct SpansIn : RecordsIn {                                // the sorted record
     const uint32_t* words;                                  // the table's word class: 256 flags in 8 dwords (am_words.h); null: no class, every span is kept
 };
 constexpr uint64_t kSpansMaxTile = 2048;                    // candidates per workgroup of the prefix maximum
-constexpr uint32_t kSpThreads = 256;                        // lanes per workgroup of am_spans.hip; k_spans_tiles_max takes the tile maxima in sweeps of as many
+constexpr uint32_t kSpThreads = 256;                        // lanes per workgroup of the prefix maximum; k_spans_tiles_max takes the tile maxima in sweeps of as many
 // cnt[i] = values < n_needles of record i (n_rec + 1 entries, the last one 0); then, with voff = exclusive sum of cnt and n_span = voff[n_rec], the spans in fold order.
 // With in.words both passes keep the whole-word spans only (ic decides the starts, so the count pass needs it as well)
 hipError_t launch_spans_count(bool ic, const SpansIn& in, uint32_t* cnt, hipStream_t st);
@@ -217,16 +210,13 @@ hipError_t launch_spans_offsets(const uint64_t* rec_first, const uint64_t* voff,
 // AM_SPANS_LEFTMOST_LONGEST, in global byte positions g = offsets[haystack] + start.  In the order of the calls: bit g of `bits` (n_words = ceil(total / 32) words, zero
 // before) for every span with len > 0, pc[w] = popcount(bits[w]) (n_words + 1, the last one 0); with rank = exclusive sum of pc and n_cand = rank[n_words]:
 // best[rank of g] = max(len << 32 | ~needle) (zero before); cand_g[k] = the k-th set bit; head / kept (kept: n_cand + 1, the last one 0) from the exclusive prefix
-// maximum of the candidates' ends (tile_max: ceil((n_cand + 1) / kSpansMaxTile) words); the heads' lanes walk their chains (*long_chains, cleared by the caller, != 0
-// when one needed more than `limit` looks); jump[i] = next[i] for launch_split_double's rounds; with kidx = exclusive sum of kept and n_out = kidx[n_cand]: the spans
-// kept and span_off (n_hay + 1)
+// maximum of the candidates' ends (tile_max: ceil((n_cand + 1) / kSpansMaxTile) words); select_chains (am_fold.h) over a SpansChain (am_chain.h) finishes kept; with
+// kidx = exclusive sum of kept and n_out = kidx[n_cand]: the spans kept and span_off (n_hay + 1)
 hipError_t launch_spans_mark(const Span* spans, uint64_t n_span, const SpansIn& in, uint32_t* bits, uint64_t n_words, hipStream_t st);
 hipError_t launch_spans_popcount(const uint32_t* bits, uint64_t n_words, uint32_t* pc, hipStream_t st);
 hipError_t launch_spans_best(const Span* spans, uint64_t n_span, const SpansIn& in, const uint32_t* bits, const uint64_t* rank, uint64_t n_words, uint64_t* best, uint64_t n_cand, hipStream_t st);
 hipError_t launch_spans_candidates(const uint32_t* bits, const uint64_t* rank, uint64_t n_words, uint64_t* cand_g, uint64_t n_cand, hipStream_t st);
 hipError_t launch_spans_heads(const uint64_t* cand_g, const uint64_t* best, uint64_t n_cand, uint64_t* tile_max, uint8_t* head, uint32_t* kept, hipStream_t st);
-hipError_t launch_spans_walk(const uint64_t* cand_g, const uint64_t* best, uint64_t n_cand, const uint8_t* head, uint32_t* kept, uint32_t limit, uint32_t* long_chains, hipStream_t st);
-hipError_t launch_spans_next(const uint64_t* cand_g, const uint64_t* best, uint64_t n_cand, const uint8_t* head, uint64_t* jump, hipStream_t st);
 hipError_t launch_spans_emit(const uint64_t* cand_g, const uint64_t* best, const uint32_t* kept, const uint64_t* kidx, uint64_t n_cand, const SpansIn& in, Span* out, uint64_t n_out,
                              uint64_t* span_off, hipStream_t st);
 // per-needle counts over the whole-word spans only (am_hist.hip, am_count_spans_by_needle*): counts[id] += the values id < in.n_needles of in.recs whose span the class

@@ -80,10 +80,7 @@ int windows(const am_batch* src, const struct am_spans* s, uint32_t before, uint
             jobs.j[0] = ScanJob{(const uint32_t*)head.p, nullptr, (uint64_t*)rank.p, n_span + 1, nullptr};
             HIP_TRY(launch_scan_jobs(jobs, st));
         } else {
-            size_t tmp_bytes = 0;
-            HIP_TRY(scan_temp_bytes(n_span + 1, &tmp_bytes));
-            AM_TRY(scan_tmp.ensure(tmp_bytes));
-            HIP_TRY(launch_scan(scan_tmp.p, scan_tmp.cap, (const uint32_t*)head.p, (uint64_t*)rank.p, n_span + 1, st));
+            AM_TRY(exclusive_sum(scan_tmp, (const uint32_t*)head.p, (uint64_t*)rank.p, n_span + 1, st));
         }
         uint64_t n_pieces = 0;                              // the one word that crosses
         AM_TRY(read_u64((const uint64_t*)rank.p + n_span, &n_pieces, st));

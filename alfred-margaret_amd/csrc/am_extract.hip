@@ -24,12 +24,8 @@ namespace dev {
 
 namespace {
 
-constexpr uint32_t kExtThreads = 256;
 constexpr uint32_t kGroup = 16;                             // bytes of an aligned group of the walk
 constexpr uint32_t kHeadWalk = 16;                          // spans the last lane of a run looks back at before it searches the ranks for its head
-
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kExtThreads - 1) / kExtThreads); }
-__device__ __forceinline__ uint64_t global_lane() { return (uint64_t)blockIdx.x * kExtThreads + threadIdx.x; }
 
 // bit j (0..3) = byte j of the dword (little endian: the lowest address first) is a START byte
 __host__ __device__ __forceinline__ uint32_t start_bits4(uint32_t w)
@@ -116,11 +112,11 @@ __host__ __device__ __forceinline__ uint64_t walk_right(const uint8_t* __restric
 // one lane per span: its window, relative to its haystack.  EACH: the fragment itself.  MERGED: ws / we for the heads and the emit.  A span that does not lie inside
 // its haystack (not reachable for a row of a spans call over this batch) becomes the empty window at 0 without a read.
 template <bool EACH>
-__global__ void __launch_bounds__(kExtThreads) k_extract_windows(const Span* __restrict__ spans, uint64_t n_span, const uint8_t* __restrict__ text,
+__global__ void __launch_bounds__(kRowThreads) k_extract_windows(const Span* __restrict__ spans, uint64_t n_span, const uint8_t* __restrict__ text,
                                                                  const uint64_t* __restrict__ src_offsets, uint32_t n_hay, uint64_t total, uint32_t before, uint32_t after,
                                                                  Fragment* __restrict__ frags, uint64_t* __restrict__ ws_out, uint64_t* __restrict__ we_out)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     if (i >= n_span) return;
     const Span sp = spans[i];
     uint64_t ws = 0, we = 0;
@@ -141,31 +137,24 @@ __global__ void __launch_bounds__(kExtThreads) k_extract_windows(const Span* __r
 }
 
 // one lane per span (+ one for the trailing zero of the sum's input): the span opens a piece
-__global__ void __launch_bounds__(kExtThreads) k_extract_heads(const Span* __restrict__ spans, uint64_t n_span, const uint64_t* __restrict__ ws, const uint64_t* __restrict__ we,
+__global__ void __launch_bounds__(kRowThreads) k_extract_heads(const Span* __restrict__ spans, uint64_t n_span, const uint64_t* __restrict__ ws, const uint64_t* __restrict__ we,
                                                                uint32_t* __restrict__ head)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     if (i > n_span) return;
     if (i == n_span) { head[i] = 0; return; }
     head[i] = i == 0 || spans[i].haystack != spans[i - 1].haystack || ws[i] > we[i - 1] ? 1u : 0u;
-}
-
-// last index in [lo, hi] whose rank is <= x (rank ascends; rank[lo] <= x)
-__device__ __forceinline__ uint64_t last_rank_at_or_below(const uint64_t* __restrict__ rank, uint64_t lo, uint64_t hi, uint64_t x)
-{
-    while (lo < hi) { const uint64_t mid = lo + ((hi - lo + 1) >> 1); if (rank[mid] <= x) lo = mid; else hi = mid - 1; }
-    return lo;
 }
 
 // lanes [0, n_span): with rank = the exclusive sum of head (rank[n_span] = n_pieces), the head of piece p = rank[head] writes the piece's start and the last span of
 // the run its length -- it finds its head among the kHeadWalk spans before it, or, in a longer run, as the last span whose rank is <= p (every later span of the run
 // has rank p + 1).  Lanes [0, n_hay]: the piece offsets, out_off[h] = rank[span_off[h]] (the first span of a haystack opens a piece, so its rank counts the pieces of
 // the haystacks before it; the closing entry is rank[n_span] = n_pieces).
-__global__ void __launch_bounds__(kExtThreads) k_extract_emit(const uint32_t* __restrict__ head, const uint64_t* __restrict__ rank, const uint64_t* __restrict__ ws,
+__global__ void __launch_bounds__(kRowThreads) k_extract_emit(const uint32_t* __restrict__ head, const uint64_t* __restrict__ rank, const uint64_t* __restrict__ ws,
                                                               const uint64_t* __restrict__ we, uint64_t n_span, uint64_t n_pieces, const uint64_t* __restrict__ span_off,
                                                               uint64_t n_hay, Fragment* __restrict__ frags, uint64_t* __restrict__ out_off)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     if (i <= n_hay) {
         const uint64_t k = span_off[i];
         AM_BOUNDS(k <= n_span && rank[k <= n_span ? k : n_span] <= n_pieces);
@@ -180,7 +169,7 @@ __global__ void __launch_bounds__(kExtThreads) k_extract_emit(const uint32_t* __
     if (!head[i + 1] && i + 1 < n_span) return;             // (head has n_span + 1 entries, the last one 0)
     uint64_t j = i;
     for (uint32_t k = 0; k < kHeadWalk && j > 0 && !head[j]; k++) j--;
-    if (!head[j]) j = last_rank_at_or_below(rank, 0, j, p);
+    if (!head[j]) j = last_at_or_before(rank, (uint64_t)0, j, p);       // (rank ascends, rank[0] = 0 <= p)
     AM_BOUNDS(head[j] && rank[j] == p && ws[j] <= we[i]);
     frags[p].len = we[i] >= ws[j] ? we[i] - ws[j] : 0;
 }
@@ -190,25 +179,18 @@ __global__ void __launch_bounds__(kExtThreads) k_extract_emit(const uint32_t* __
 hipError_t launch_extract_windows(const Span* spans, uint64_t n_span, const uint8_t* text, const uint64_t* src_offsets, uint32_t n_hay, uint64_t total, uint32_t before,
                                   uint32_t after, Fragment* frags, uint64_t* ws, uint64_t* we, hipStream_t st)
 {
-    if (n_span == 0) return hipSuccess;
-    const dim3 grid(blocks_for(n_span)), block(kExtThreads);
-    if (frags) hipLaunchKernelGGL((k_extract_windows<true>), grid, block, 0, st, spans, n_span, text, src_offsets, n_hay, total, before, after, frags, ws, we);
-    else hipLaunchKernelGGL((k_extract_windows<false>), grid, block, 0, st, spans, n_span, text, src_offsets, n_hay, total, before, after, frags, ws, we);
-    return hipGetLastError();
+    return launch_rows(frags ? k_extract_windows<true> : k_extract_windows<false>, n_span, st, spans, n_span, text, src_offsets, n_hay, total, before, after, frags, ws, we);
 }
 
 hipError_t launch_extract_heads(const Span* spans, uint64_t n_span, const uint64_t* ws, const uint64_t* we, uint32_t* head, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_extract_heads, dim3(blocks_for(n_span + 1)), dim3(kExtThreads), 0, st, spans, n_span, ws, we, head);
-    return hipGetLastError();
+    return launch_rows(k_extract_heads, n_span + 1, st, spans, n_span, ws, we, head);
 }
 
 hipError_t launch_extract_emit(const uint32_t* head, const uint64_t* rank, const uint64_t* ws, const uint64_t* we, uint64_t n_span, uint64_t n_pieces, const uint64_t* span_off,
                                uint64_t n_hay, Fragment* frags, uint64_t* out_off, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_extract_emit, dim3(blocks_for(std::max(n_span, n_hay + 1))), dim3(kExtThreads), 0, st, head, rank, ws, we, n_span, n_pieces, span_off, n_hay, frags,
-                       out_off);
-    return hipGetLastError();
+    return launch_rows(k_extract_emit, std::max(n_span, n_hay + 1), st, head, rank, ws, we, n_span, n_pieces, span_off, n_hay, frags, out_off);
 }
 
 }  // namespace dev

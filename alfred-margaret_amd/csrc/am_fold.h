@@ -1,6 +1,6 @@
 // am_fold.h -- the host-side scaffolding the device stages share (am_splitter.cpp, am_spans.cpp, am_subst.cpp, am_select.cpp, am_extract.cpp, am_contains_all.cpp, am_score.cpp and the
-// one-shot entry points of am_abi.cpp): the argument checks of their entry points (a held result's among them: matches_in_hbm, matches_below), the CSR result handle (am_fragments, am_needle_matrix, am_spans), the finisher of long chains
-// (pointer doubling), the one-shot form of an entry point, the loop that sends host slices up in segments and folds each in HBM, and the builder of the batches the
+// one-shot entry points of am_abi.cpp): the argument checks of their entry points (a held result's among them: matches_in_hbm, matches_below), the CSR result handle (am_fragments, am_needle_matrix, am_spans), the exclusive sum, the chain
+// selector's host sequence, the one-shot form of an entry point, the loop that sends host slices up in segments and folds each in HBM, and the builder of the batches the
 // library derives in HBM.  The kernels differ from stage to stage; what is here does not.  Included at the end of am_host.h; internal.
 #pragma once
 
@@ -96,8 +96,8 @@ int empty_result(int dev, Result** out)
     return AM_OK;
 }
 
-// ---- chains.  A fold that keeps a path head, next[head], next[next[head]], ... of every chain lets the head's lane walk a short chain and leaves the long ones to
-// pointer doubling (am_split.hip): this is everything between "the walk kernel has been launched" and "the kept flags are final".
+// ---- exclusive sums (am_scan.hip).  out[i] = in[0] + ... + in[i - 1] for i < n; tmp is the scan's temporary, grown when it is too small (a buffer that moves
+// is freed: no stream work may be pending on it); total (nullable) = out[n - 1], read back -- the callers' inputs end in a zero, so that is the sum of them all.
 inline int read_u64(const void* d_src, uint64_t* out, hipStream_t st)
 {
     HIP_TRY(hipMemcpyAsync(out, d_src, 8, hipMemcpyDeviceToHost, st));
@@ -105,34 +105,64 @@ inline int read_u64(const void* d_src, uint64_t* out, hipStream_t st)
     return AM_OK;
 }
 
-// n elements with their kept flags; flag: 64 bytes the caller cleared before its walk kernel, word 0 = chains the walk left unfinished, word 1 = marks of a round.
-// launch_next(jump) launches the caller's *_next kernel, which writes next[] into jump[n].  *rounds_out = the doubling rounds (0: every chain was short).
-template <class Next>
-int finish_long_chains(uint64_t n, uint32_t* kept, uint32_t* flag, Next&& launch_next, const char* prof_next, const char* prof_double, uint32_t* rounds_out, hipStream_t st)
+inline int exclusive_sum(DevBuf& tmp, const uint32_t* in, uint64_t* out, uint64_t n, hipStream_t st, uint64_t* total = nullptr)
 {
-    *rounds_out = 0;
+    size_t bytes = 0;
+    HIP_TRY(scan_temp_bytes(n, &bytes));
+    AM_TRY(tmp.ensure(bytes));
+    HIP_TRY(launch_scan(tmp.p, tmp.cap, in, out, n, st));
+    return total ? read_u64(out + n - 1, total, st) : AM_OK;
+}
+
+inline int exclusive_sum64(DevBuf& tmp, const uint64_t* in, uint64_t* out, uint64_t n, hipStream_t st, uint64_t* total = nullptr)
+{
+    size_t bytes = 0;
+    HIP_TRY(scan64_temp_bytes(n, &bytes));
+    AM_TRY(tmp.ensure(bytes));
+    HIP_TRY(launch_scan64(tmp.p, tmp.cap, in, out, n, st));
+    return total ? read_u64(out + n - 1, total, st) : AM_OK;
+}
+
+// ---- chains (am_chain.h): everything between "the stage has written head and kept = head" and "kept is final and counted".  The heads' lanes walk the short
+// chains, pointer doubling finishes the ones beyond the limit, kidx = the exclusive sum of kept (v.n + 1 entries each, kept's last one 0) and *n_kept = kidx[v.n].
+// knob: the stage's limit switch (kUnset or 0: dflt).  prof: the profile names of the walk, the next pass and a doubling round.  *rounds = the doubling rounds
+// (0: every chain was short).
+struct ChainProf { const char *walk, *next, *dbl; };
+
+template <class View>
+int select_chains(const View& v, const uint8_t* head, uint32_t* kept, uint64_t* kidx, DevBuf& scan_tmp, long knob, uint32_t dflt, const ChainProf& prof, uint64_t* n_kept,
+                  uint32_t* rounds, hipStream_t st)
+{
+    const uint64_t n = v.n;
+    *rounds = 0;
+    DevBuf flag_buf, jump0, jump1;                          // 64 bytes: word 0 = chains the walk left unfinished, word 1 = marks of a round; next[] and its double
+    AM_TRY(flag_buf.ensure(64));
+    uint32_t* const flag = (uint32_t*)flag_buf.p;
+    HIP_TRY(hipMemsetAsync(flag, 0, 64, st));
+    { Prof pr(prof.walk, st);
+      HIP_TRY(launch_chain_walk(v, head, kept, knob > 0 ? (uint32_t)std::min<long>(knob, 1L << 30) : dflt, flag, st)); }
     uint32_t long_chains = 0;
     if (n > 1) {
         HIP_TRY(hipMemcpyAsync(&long_chains, flag, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
-    if (!long_chains) return AM_OK;
-    DevBuf jump0, jump1;
-    AM_TRY(jump0.ensure(n * 8));
-    AM_TRY(jump1.ensure(n * 8));
-    uint64_t* jump[2] = {(uint64_t*)jump0.p, (uint64_t*)jump1.p};
-    { Prof pr(prof_next, st);
-      HIP_TRY(launch_next(jump[0])); }
-    uint32_t rounds = 0;
-    for (uint32_t marked = 1; marked != 0 && rounds < 64; rounds++) {      // (a path of k elements is marked after log2(k) + 1 rounds: 64 is no limit for 64-bit indices)
-        HIP_TRY(hipMemsetAsync(flag + 1, 0, 4, st));
-        { Prof pr(prof_double, st);
-          HIP_TRY(launch_split_double(jump[rounds & 1], jump[(rounds & 1) ^ 1], n, kept, flag + 1, st)); }
-        HIP_TRY(hipMemcpyAsync(&marked, flag + 1, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));                  // (the last round's: the jump arrays are free to go)
+    if (long_chains) {
+        AM_TRY(jump0.ensure(n * 8));
+        AM_TRY(jump1.ensure(n * 8));
+        uint64_t* jump[2] = {(uint64_t*)jump0.p, (uint64_t*)jump1.p};
+        { Prof pr(prof.next, st);
+          HIP_TRY(launch_chain_next(v, head, jump[0], st)); }
+        uint32_t r = 0;
+        for (uint32_t marked = 1; marked != 0 && r < 64; r++) {      // (a path of k elements is marked after log2(k) + 1 rounds: 64 is no limit for 64-bit indices)
+            HIP_TRY(hipMemsetAsync(flag + 1, 0, 4, st));
+            { Prof pr(prof.dbl, st);
+              HIP_TRY(launch_chain_double(jump[r & 1], jump[(r & 1) ^ 1], n, kept, flag + 1, st)); }
+            HIP_TRY(hipMemcpyAsync(&marked, flag + 1, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));              // (the last round's: the jump arrays are free to go)
+        }
+        *rounds = r;
     }
-    *rounds_out = rounds;
-    return AM_OK;
+    return exclusive_sum(scan_tmp, kept, kidx, n + 1, st, n_kept);
 }
 
 // ---- the one-shot form of an entry point: the slices into the calling thread's batch on `dev`, form(b) -- the *_batch form -- if they went up, and the batch trimmed

@@ -132,9 +132,6 @@ extern "C" int am_near_spans(const NearCall* p, const SpansResult* s, am_near_hi
     AM_TRY(hit_mask.ensure(n * 8));
     AM_TRY(hit_count.ensure((n + 1) * 4));
     AM_TRY(pos.ensure((n + 1) * 8));
-    size_t tmp_bytes = 0;
-    HIP_TRY(scan_temp_bytes(n + 1, &tmp_bytes));
-    AM_TRY(scan_tmp.ensure(tmp_bytes));
     NearIn in{};
     in.spans = (const Span*)s->data.p; in.n_span = n; in.n_words = (uint32_t)n_words;
     in.span_off = (const uint64_t*)s->offsets.p; in.n_hay = n_hay;
@@ -152,10 +149,9 @@ extern "C" int am_near_spans(const NearCall* p, const SpansResult* s, am_near_hi
       HIP_TRY(launch_near_words(in, st)); }
     { Prof pr("near_count", st);
       HIP_TRY(launch_near_count(in, n_cu, st)); }
-    { Prof pr("near_place", st);
-      HIP_TRY(launch_scan(scan_tmp.p, scan_tmp.cap, (const uint32_t*)hit_count.p, (uint64_t*)pos.p, n + 1, st)); }
     uint64_t n_pairs = 0;
-    AM_TRY(read_u64((const uint64_t*)pos.p + n, &n_pairs, st));
+    { Prof pr("near_place", st);
+      AM_TRY(exclusive_sum(scan_tmp, (const uint32_t*)hit_count.p, (uint64_t*)pos.p, n + 1, st, &n_pairs)); }
     if (n_pairs > n * nq) return fail(AM_ERR_HIP, "am_near_spans: the pairs' sum is out of range");
     AM_TRY(x->data.ensure(n_pairs * sizeof(NearPair)));
     x->n_items = n_pairs;

@@ -7,14 +7,7 @@
 // another haystack means there is none in this one).  Plain C++: tests/native/near_pick_main.cpp compiles all of it with g++ and holds it to a brute-force loop under
 // a sanitizer.
 #pragma once
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define AM_NEAR_HD __host__ __device__ __forceinline__
-#else
-#define AM_NEAR_HD inline
-#endif
+#include "am_rows.h"
 
 namespace am {
 namespace dev {
@@ -33,7 +26,7 @@ struct NearPicked { bool hit; uint64_t b, gap; };
 
 // The partner of an anchor among its two candidates: p lies before it, n behind it; a candidate of another haystack is none.  Under kNearOrdered only n counts.  The
 // rows do not overlap, so both gaps are differences of unsigned numbers that do not wrap.  The smaller gap wins, a tie goes to p; a pair iff the gap <= max_gap.
-AM_NEAR_HD NearPicked near_pick(uint64_t a_start, uint64_t a_len, uint32_t a_haystack, const NearSide& p, const NearSide& n, uint32_t flags, uint64_t max_gap)
+AM_HD NearPicked near_pick(uint64_t a_start, uint64_t a_len, uint32_t a_haystack, const NearSide& p, const NearSide& n, uint32_t flags, uint64_t max_gap)
 {
     const bool has_p = (flags & kNearOrdered) == 0 && p.has && p.haystack == a_haystack;
     const bool has_n = n.has && n.haystack == a_haystack;
@@ -46,19 +39,19 @@ AM_NEAR_HD NearPicked near_pick(uint64_t a_start, uint64_t a_len, uint32_t a_hay
 }
 
 // the highest set bit of `word` below bit `bit` / the lowest above it (bit < 64); 64: none
-AM_NEAR_HD uint32_t near_bit_below(uint64_t word, uint32_t bit)
+AM_HD uint32_t near_bit_below(uint64_t word, uint32_t bit)
 {
     const uint64_t below = word & ((1ull << bit) - 1ull);
     return below ? 63u - (uint32_t)__builtin_clzll(below) : 64u;
 }
-AM_NEAR_HD uint32_t near_bit_above(uint64_t word, uint32_t bit)
+AM_HD uint32_t near_bit_above(uint64_t word, uint32_t bit)
 {
     const uint64_t above = bit >= 63u ? 0ull : word & ~((2ull << bit) - 1ull);
     return above ? (uint32_t)__builtin_ctzll(above) : 64u;
 }
 
 // the nearest member of a group below / above span i: `row` = the group's bitmap (n_words words), prev_nz / next_nz = its links; kNearNone: none
-AM_NEAR_HD uint64_t near_prev(const uint64_t* row, const uint32_t* prev_nz, uint64_t i)
+AM_HD uint64_t near_prev(const uint64_t* row, const uint32_t* prev_nz, uint64_t i)
 {
     const uint64_t w = i >> 6;
     const uint32_t b = near_bit_below(row[w], (uint32_t)(i & 63u));
@@ -67,7 +60,7 @@ AM_NEAR_HD uint64_t near_prev(const uint64_t* row, const uint32_t* prev_nz, uint
     if (pw == kNearNoWord) return kNearNone;
     return ((uint64_t)pw << 6) | (63u - (uint32_t)__builtin_clzll(row[pw] | 1ull));      // (| 1: a link names a non-zero word; a zero one would be a bug, not a crash)
 }
-AM_NEAR_HD uint64_t near_next(const uint64_t* row, const uint32_t* next_nz, uint64_t i)
+AM_HD uint64_t near_next(const uint64_t* row, const uint32_t* next_nz, uint64_t i)
 {
     const uint64_t w = i >> 6;
     const uint32_t b = near_bit_above(row[w], (uint32_t)(i & 63u));
@@ -80,9 +73,9 @@ AM_NEAR_HD uint64_t near_next(const uint64_t* row, const uint32_t* next_nz, uint
 // The links are running maxima.  Walking the words in one direction, step k = 0, 1, ... (forwards: word k; backwards: word n_words - 1 - k), a non-zero word has
 // the value k + 1 and a zero word 0; E_k = the maximum of the values of the steps before k (0: none).  Forwards E_k - 1 is the last non-zero word before word k,
 // backwards n_words - E_k is the first non-zero word behind it.  k_near_words takes the maxima in sweeps with a carry; a sequential caller keeps one variable.
-AM_NEAR_HD uint32_t near_link_value(uint64_t word, uint32_t step) { return word ? step + 1u : 0u; }
-AM_NEAR_HD uint32_t near_link_word(uint32_t excl_max, bool backwards, uint32_t n_words) { return excl_max == 0u ? kNearNoWord : (backwards ? n_words - excl_max : excl_max - 1u); }
-AM_NEAR_HD uint32_t near_link_index(uint32_t step, bool backwards, uint32_t n_words) { return backwards ? n_words - 1u - step : step; }
+AM_HD uint32_t near_link_value(uint64_t word, uint32_t step) { return word ? step + 1u : 0u; }
+AM_HD uint32_t near_link_word(uint32_t excl_max, bool backwards, uint32_t n_words) { return excl_max == 0u ? kNearNoWord : (backwards ? n_words - excl_max : excl_max - 1u); }
+AM_HD uint32_t near_link_index(uint32_t step, bool backwards, uint32_t n_words) { return backwards ? n_words - 1u - step : step; }
 
 // the compiled form of a query set: the groups any query names get a bitmap row each, in ascending order of the group
 struct NearPlan {

@@ -88,9 +88,6 @@ int sort_by_needle(const SpansResult* s, Postings** out)
         AM_TRY(idx[1].ensure(n * 4));
         AM_TRY(counts.ensure(cells * 4));
         AM_TRY(base.ensure(cells * 8));
-        size_t tmp_bytes = 0;
-        HIP_TRY(scan_temp_bytes(cells, &tmp_bytes));
-        AM_TRY(scan_tmp.ensure(tmp_bytes));
     }
     AM_TRY(p->data.ensure(n * sizeof(Span)));
     AM_TRY(p->source.ensure(n * 8));
@@ -106,7 +103,7 @@ int sort_by_needle(const SpansResult* s, Postings** out)
         { Prof pr("post_hist", st);
           HIP_TRY(launch_post_hist(plan, k, (const uint32_t*)keys[cur].p, n, (uint32_t*)counts.p, st)); }
         { Prof pr("post_scan", st);
-          HIP_TRY(launch_scan(scan_tmp.p, scan_tmp.cap, (const uint32_t*)counts.p, (uint64_t*)base.p, pass_cells, st)); }
+          AM_TRY(exclusive_sum(scan_tmp, (const uint32_t*)counts.p, (uint64_t*)base.p, pass_cells, st)); }      // (pass 0 has the most cells: the temporary never moves)
         { Prof pr("post_scatter", st);
           HIP_TRY(launch_post_scatter(plan, k, (const uint32_t*)keys[cur].p, (const uint32_t*)idx[cur].p, n, (const uint64_t*)base.p, (uint32_t*)keys[cur ^ 1u].p,
                                       (uint32_t*)idx[cur ^ 1u].p, st)); }

@@ -8,14 +8,7 @@
 // number of keys with a smaller digit anywhere plus the keys with the same digit in an earlier tile: where the cell's first key goes in a stable sort.
 // Plain C++: tests/native/postings_sort_main.cpp compiles all of it with g++ and holds the pass plan, run on the CPU, to std::stable_sort.
 #pragma once
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define AM_POST_HD __host__ __device__ __forceinline__
-#else
-#define AM_POST_HD inline
-#endif
+#include "am_rows.h"
 
 namespace am {
 namespace dev {
@@ -30,16 +23,16 @@ constexpr uint64_t kPostMaxSpans = 0xFFFFFFFFull;           // the sort carries 
 struct PostPlan { uint32_t passes; uint32_t bits[kPostMaxPasses]; uint32_t shift[kPostMaxPasses]; };
 
 // bits that can differ among keys below n_needles
-AM_POST_HD uint32_t post_key_bits(uint64_t n_needles)
+AM_HD uint32_t post_key_bits(uint64_t n_needles)
 {
     uint32_t b = 0;
     if (n_needles > 1) for (uint64_t x = n_needles - 1; x != 0; x >>= 1) b++;
     return b > 32 ? 32 : b;
 }
 
-AM_POST_HD uint32_t post_passes(uint64_t n_needles) { return (post_key_bits(n_needles) + kPostMaxDigitBits - 1) / kPostMaxDigitBits; }
+AM_HD uint32_t post_passes(uint64_t n_needles) { return (post_key_bits(n_needles) + kPostMaxDigitBits - 1) / kPostMaxDigitBits; }
 
-AM_POST_HD PostPlan post_plan(uint64_t n_needles)
+AM_HD PostPlan post_plan(uint64_t n_needles)
 {
     PostPlan p{};
     const uint32_t b = post_key_bits(n_needles);
@@ -53,14 +46,14 @@ AM_POST_HD PostPlan post_plan(uint64_t n_needles)
     return p;
 }
 
-AM_POST_HD uint32_t post_digit(const PostPlan& p, uint32_t key, uint32_t pass) { return (key >> p.shift[pass]) & ((1u << p.bits[pass]) - 1u); }
-AM_POST_HD uint32_t post_digits(const PostPlan& p, uint32_t pass) { return 1u << p.bits[pass]; }
-AM_POST_HD uint64_t post_tiles(uint64_t n) { return (n + kPostTileSpans - 1) / kPostTileSpans; }
-AM_POST_HD uint64_t post_cell(uint32_t digit, uint64_t tile, uint64_t n_tiles) { return (uint64_t)digit * n_tiles + tile; }
+AM_HD uint32_t post_digit(const PostPlan& p, uint32_t key, uint32_t pass) { return (key >> p.shift[pass]) & ((1u << p.bits[pass]) - 1u); }
+AM_HD uint32_t post_digits(const PostPlan& p, uint32_t pass) { return 1u << p.bits[pass]; }
+AM_HD uint64_t post_tiles(uint64_t n) { return (n + kPostTileSpans - 1) / kPostTileSpans; }
+AM_HD uint64_t post_cell(uint32_t digit, uint64_t tile, uint64_t n_tiles) { return (uint64_t)digit * n_tiles + tile; }
 
 // first k in [0, n) with a[k * stride] >= x (n: none); a ascends.  The search of k_post_offsets (stride 1 over the sorted keys) and of k_post_row_offsets (stride 6
 // over the haystack field of 24-byte rows)
-AM_POST_HD uint64_t post_lower_bound(const uint32_t* a, uint64_t n, uint64_t stride, uint64_t x)
+AM_HD uint64_t post_lower_bound(const uint32_t* a, uint64_t n, uint64_t stride, uint64_t x)
 {
     uint64_t lo = 0, hi = n;
     while (lo < hi) {

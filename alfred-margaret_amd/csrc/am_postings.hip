@@ -43,9 +43,9 @@ constexpr uint32_t kPostMaxDigits = 1u << kPostMaxDigitBits;
 constexpr uint32_t kNoKey = 0xFFFFFFFFu;
 static_assert(kPostTileSpans % kPostThreads == 0 && kPostWaveSpans % kWave == 0 && kPostTileSpans == kPostWaveSpans * kPostWaves, "a tile is whole rounds of whole wavefronts");
 
-__global__ void __launch_bounds__(kPostThreads) k_post_keys(const Span* __restrict__ spans, uint64_t n, uint32_t* __restrict__ keys, uint32_t* __restrict__ idx)
+__global__ void __launch_bounds__(kRowThreads) k_post_keys(const Span* __restrict__ spans, uint64_t n, uint32_t* __restrict__ keys, uint32_t* __restrict__ idx)
 {
-    const uint64_t i = (uint64_t)blockIdx.x * kPostThreads + threadIdx.x;
+    const uint64_t i = global_row();
     if (i < n) { keys[i] = spans[i].needle; idx[i] = (uint32_t)i; }
 }
 
@@ -121,10 +121,10 @@ __global__ void __launch_bounds__(kPostThreads) k_post_scatter(PostPlan plan, ui
     }
 }
 
-__global__ void __launch_bounds__(kPostThreads) k_post_gather(const Span* __restrict__ spans, const uint32_t* __restrict__ idx, uint64_t n, Span* __restrict__ data,
+__global__ void __launch_bounds__(kRowThreads) k_post_gather(const Span* __restrict__ spans, const uint32_t* __restrict__ idx, uint64_t n, Span* __restrict__ data,
                                                               uint64_t* __restrict__ source)
 {
-    const uint64_t k = (uint64_t)blockIdx.x * kPostThreads + threadIdx.x;
+    const uint64_t k = global_row();
     if (k >= n) return;
     const uint64_t i = idx[k];
     AM_BOUNDS(i < n);
@@ -136,17 +136,17 @@ __global__ void __launch_bounds__(kPostThreads) k_post_gather(const Span* __rest
     source[k] = i;
 }
 
-__global__ void __launch_bounds__(kPostThreads) k_post_offsets(const uint32_t* __restrict__ keys, uint64_t n, uint64_t n_needles, uint64_t* __restrict__ offsets)
+__global__ void __launch_bounds__(kRowThreads) k_post_offsets(const uint32_t* __restrict__ keys, uint64_t n, uint64_t n_needles, uint64_t* __restrict__ offsets)
 {
-    const uint64_t v = (uint64_t)blockIdx.x * kPostThreads + threadIdx.x;
+    const uint64_t v = global_row();
     if (v <= n_needles) offsets[v] = v == n_needles ? n : post_lower_bound(keys, n, 1, v);
 }
 
-__global__ void __launch_bounds__(kPostThreads) k_post_df(const Span* __restrict__ data, const uint32_t* __restrict__ keys, uint64_t n, uint64_t n_needles,
+__global__ void __launch_bounds__(kRowThreads) k_post_df(const Span* __restrict__ data, const uint32_t* __restrict__ keys, uint64_t n, uint64_t n_needles,
                                                           uint64_t* __restrict__ doc_freq)
 {
     const uint32_t lane = threadIdx.x & (kWave - 1);
-    const uint64_t k = (uint64_t)blockIdx.x * kPostThreads + threadIdx.x;
+    const uint64_t k = global_row();
     const bool active = k < n;
     uint32_t key = kNoKey;
     bool head = false;
@@ -167,23 +167,19 @@ __global__ void __launch_bounds__(kPostThreads) k_post_df(const Span* __restrict
     if (c != 0 && key < n_needles) atomicAdd((unsigned long long*)&doc_freq[key], (unsigned long long)c);
 }
 
-__global__ void __launch_bounds__(kPostThreads) k_post_row_offsets(const Span* __restrict__ row, uint64_t n_row, uint64_t n_hay, uint64_t* __restrict__ out_off)
+__global__ void __launch_bounds__(kRowThreads) k_post_row_offsets(const Span* __restrict__ row, uint64_t n_row, uint64_t n_hay, uint64_t* __restrict__ out_off)
 {
-    const uint64_t h = (uint64_t)blockIdx.x * kPostThreads + threadIdx.x;
+    const uint64_t h = global_row();
     if (h <= n_hay) out_off[h] = h == n_hay ? n_row : post_lower_bound((const uint32_t*)row + 4, n_row, sizeof(Span) / 4, h);      // (haystack: byte 16 of 24)
 }
 static_assert(sizeof(Span) == 24 && offsetof(Span, haystack) == 16 && offsetof(Span, needle) == 20, "Span: 0, 8, 16, 20");
-
-uint32_t lanes_grid(uint64_t n) { return (uint32_t)((n + kPostThreads - 1) / kPostThreads); }
 
 }  // namespace
 
 hipError_t launch_post_keys(const Span* spans, uint64_t n, uint32_t* keys, uint32_t* idx, hipStream_t st)
 {
-    if (n == 0) return hipSuccess;
     if (n >= kPostMaxSpans) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_post_keys, dim3(lanes_grid(n)), dim3(kPostThreads), 0, st, spans, n, keys, idx);
-    return hipGetLastError();
+    return launch_rows(k_post_keys, n, st, spans, n, keys, idx);
 }
 
 hipError_t launch_post_hist(const PostPlan& plan, uint32_t pass, const uint32_t* keys, uint64_t n, uint32_t* counts, hipStream_t st)
@@ -207,30 +203,24 @@ hipError_t launch_post_scatter(const PostPlan& plan, uint32_t pass, const uint32
 
 hipError_t launch_post_gather(const Span* spans, const uint32_t* idx, uint64_t n, Span* data, uint64_t* source, hipStream_t st)
 {
-    if (n == 0) return hipSuccess;
     if (n >= kPostMaxSpans) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_post_gather, dim3(lanes_grid(n)), dim3(kPostThreads), 0, st, spans, idx, n, data, source);
-    return hipGetLastError();
+    return launch_rows(k_post_gather, n, st, spans, idx, n, data, source);
 }
 
 hipError_t launch_post_offsets(const uint32_t* keys, uint64_t n, uint64_t n_needles, uint64_t* offsets, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_post_offsets, dim3(lanes_grid(n_needles + 1)), dim3(kPostThreads), 0, st, keys, n, n_needles, offsets);
-    return hipGetLastError();
+    return launch_rows(k_post_offsets, n_needles + 1, st, keys, n, n_needles, offsets);
 }
 
 hipError_t launch_post_df(const Span* data, const uint32_t* keys, uint64_t n, uint64_t n_needles, uint64_t* doc_freq, hipStream_t st)
 {
-    if (n == 0) return hipSuccess;
     if (n >= kPostMaxSpans) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_post_df, dim3(lanes_grid(n)), dim3(kPostThreads), 0, st, data, keys, n, n_needles, doc_freq);
-    return hipGetLastError();
+    return launch_rows(k_post_df, n, st, data, keys, n, n_needles, doc_freq);
 }
 
 hipError_t launch_post_row_offsets(const Span* row, uint64_t n_row, uint64_t n_hay, uint64_t* out_off, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_post_row_offsets, dim3(lanes_grid(n_hay + 1)), dim3(kPostThreads), 0, st, row, n_row, n_hay, out_off);
-    return hipGetLastError();
+    return launch_rows(k_post_row_offsets, n_hay + 1, st, row, n_row, n_hay, out_off);
 }
 
 }  // namespace dev

@@ -16,16 +16,13 @@ namespace dev {
 
 namespace {
 constexpr int kWave = 64;
-constexpr uint32_t kRecThreads = 256;
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kRecThreads - 1) / kRecThreads); }
-__device__ __forceinline__ uint64_t global_lane() { return (uint64_t)blockIdx.x * kRecThreads + threadIdx.x; }
 
 // ---- a select's predicate over the records: one lane per record, the first of its values whose span the table keeps (span_of, am_words.h) flags the record's
 // haystack, the remaining values are skipped (several lanes may store the same 1 into the same byte)
 template <bool IC, bool WORDS>
-__global__ void __launch_bounds__(kRecThreads) k_hay_flags_spans(SpansIn in, uint8_t* __restrict__ flags)
+__global__ void __launch_bounds__(kRowThreads) k_hay_flags_spans(SpansIn in, uint8_t* __restrict__ flags)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     if (i >= in.n_rec) return;
     const Record r = in.recs[i];
     AM_BOUNDS(r.haystack < in.n_hay);
@@ -46,9 +43,9 @@ __global__ void __launch_bounds__(kRecThreads) k_hay_flags_spans(SpansIn in, uin
 
 // ---- Searcher.containsAll (Searcher.hs:173-187) on the records: the IntSet of needle ids still missing, as one bitmap of `words` 32-bit words per haystack.
 // k_idset sets the bit of every reported id, k_idset_all tests whether all n_needles bits of a haystack are set (IS.null of the final accumulator).
-__global__ void __launch_bounds__(kRecThreads) k_idset(RecordsIn in, uint32_t hay0, uint32_t words, uint32_t* __restrict__ bits)
+__global__ void __launch_bounds__(kRowThreads) k_idset(RecordsIn in, uint32_t hay0, uint32_t words, uint32_t* __restrict__ bits)
 {
-    const uint64_t r = global_lane();
+    const uint64_t r = global_row();
     if (r >= in.n_rec) return;
     const Record rec = in.recs[r];
     const uint32_t h = rec.haystack - hay0;                      // (a haystack below hay0 wraps to a row beyond in.n_hay)
@@ -66,7 +63,7 @@ __global__ void __launch_bounds__(kRecThreads) k_idset(RecordsIn in, uint32_t ha
     }
 }
 
-__global__ void __launch_bounds__(kRecThreads) k_idset_all(const uint32_t* __restrict__ bits, uint32_t words, uint32_t n_needles, uint32_t n_hay, uint8_t* __restrict__ flags)
+__global__ void __launch_bounds__(kRowThreads) k_idset_all(const uint32_t* __restrict__ bits, uint32_t words, uint32_t n_needles, uint32_t n_hay, uint8_t* __restrict__ flags)
 {
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const uint32_t h = blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
@@ -80,15 +77,13 @@ __global__ void __launch_bounds__(kRecThreads) k_idset_all(const uint32_t* __res
 
 hipError_t launch_idset(const RecordsIn& in, uint32_t hay0, uint32_t words, uint32_t* bits, hipStream_t st)
 {
-    if (in.n_rec == 0 || in.n_hay == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_idset, dim3(blocks_for(in.n_rec)), dim3(kRecThreads), 0, st, in, hay0, words, bits);
-    return hipGetLastError();
+    return launch_rows(k_idset, in.n_hay ? in.n_rec : 0, st, in, hay0, words, bits);
 }
 
 hipError_t launch_idset_all(const uint32_t* bits, uint32_t words, uint32_t n_needles, uint32_t n_hay, uint8_t* flags, hipStream_t st)
 {
     if (n_hay == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_idset_all, dim3((n_hay + 3) / 4), dim3(kRecThreads), 0, st, bits, words, n_needles, n_hay, flags);
+    hipLaunchKernelGGL(k_idset_all, dim3((n_hay + 3) / 4), dim3(kRowThreads), 0, st, bits, words, n_needles, n_hay, flags);
     return hipGetLastError();
 }
 
@@ -109,7 +104,7 @@ __device__ __forceinline__ uint64_t fold_pow(uint64_t e)
     while (e) { if (e & 1) r *= b; b *= b; e >>= 1; }
     return r;
 }
-__global__ void __launch_bounds__(kRecThreads) k_fold_hash(RecordsIn in, const uint64_t* __restrict__ rec_first, uint64_t* __restrict__ hash_out, uint64_t* __restrict__ count_out)
+__global__ void __launch_bounds__(kRowThreads) k_fold_hash(RecordsIn in, const uint64_t* __restrict__ rec_first, uint64_t* __restrict__ hash_out, uint64_t* __restrict__ count_out)
 {
     const int lane = threadIdx.x & (kWave - 1);
     const uint32_t h = blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
@@ -140,16 +135,14 @@ __global__ void __launch_bounds__(kRecThreads) k_fold_hash(RecordsIn in, const u
 hipError_t launch_fold_hash(const RecordsIn& in, const uint64_t* rec_first, uint64_t* hash_out, uint64_t* count_out, hipStream_t st)
 {
     if (in.n_hay == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_fold_hash, dim3((in.n_hay + 3) / 4), dim3(kRecThreads), 0, st, in, rec_first, hash_out, count_out);
+    hipLaunchKernelGGL(k_fold_hash, dim3((in.n_hay + 3) / 4), dim3(kRowThreads), 0, st, in, rec_first, hash_out, count_out);
     return hipGetLastError();
 }
 
 hipError_t launch_hay_flags_spans(bool ic, const SpansIn& in, uint8_t* flags, hipStream_t st)
 {
-    if (in.n_rec == 0) return hipSuccess;
     const auto kernel = !in.words ? k_hay_flags_spans<false, false> : ic ? k_hay_flags_spans<true, true> : k_hay_flags_spans<false, true>;      // (no class: no start is needed, so no case mode)
-    hipLaunchKernelGGL(kernel, dim3(blocks_for(in.n_rec)), dim3(kRecThreads), 0, st, in, flags);
-    return hipGetLastError();
+    return launch_rows(kernel, in.n_rec, st, in, flags);
 }
 
 }  // namespace dev

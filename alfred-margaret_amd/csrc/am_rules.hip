@@ -100,10 +100,10 @@ __global__ void __launch_bounds__(kRulesTile) k_rules_eval(RulesEvalIn in)
 }
 
 // one lane per haystack
-__global__ void __launch_bounds__(kRulesTile) k_rule_flags(const uint64_t* __restrict__ fired_row, const uint32_t* __restrict__ labels, uint32_t rule, uint64_t n_hay,
+__global__ void __launch_bounds__(kRowThreads) k_rule_flags(const uint64_t* __restrict__ fired_row, const uint32_t* __restrict__ labels, uint32_t rule, uint64_t n_hay,
                                                            uint64_t hay_words, uint8_t* __restrict__ flags)
 {
-    const uint64_t h = (uint64_t)blockIdx.x * kRulesTile + threadIdx.x;
+    const uint64_t h = global_row();
     if (h >= n_hay) return;
     AM_BOUNDS(h / 64 < hay_words);
     flags[h] = fired_row ? (uint8_t)((fired_row[h / 64] >> (h % 64)) & 1u) : (uint8_t)(labels[h] == rule ? 1 : 0);
@@ -134,9 +134,7 @@ hipError_t launch_rules_eval(const RulesEvalIn& call, int n_cu, hipStream_t st)
 
 hipError_t launch_rule_flags(const uint64_t* fired_row, const uint32_t* labels, uint32_t rule, uint64_t n_hay, uint64_t hay_words, uint8_t* flags, hipStream_t st)
 {
-    if (n_hay == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_rule_flags, dim3((uint32_t)((n_hay + kRulesTile - 1) / kRulesTile)), dim3(kRulesTile), 0, st, fired_row, labels, rule, n_hay, hay_words, flags);
-    return hipGetLastError();
+    return launch_rows(k_rule_flags, n_hay, st, fired_row, labels, rule, n_hay, hay_words, flags);
 }
 
 }  // namespace dev

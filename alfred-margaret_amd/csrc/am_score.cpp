@@ -219,7 +219,7 @@ extern "C" int am_scores_top_k(am_scores* x, uint32_t column, uint64_t k, int la
         AM_TRY(pos.ensure((n + 1) * 8));
         AM_TRY(winners.ensure(kk * sizeof(Scored)));
         AM_TRY(topk_flags(x, column, kk, largest, work, nullptr, (uint32_t*)keep.p, st));
-        HIP_TRY(launch_scan(work.scan_tmp.p, work.scan_tmp.cap, (const uint32_t*)keep.p, (uint64_t*)pos.p, n + 1, st));      // (after the ties' sum on the stream)
+        AM_TRY(exclusive_sum(work.scan_tmp, (const uint32_t*)keep.p, (uint64_t*)pos.p, n + 1, st));      // (after the ties' sum on the stream, which sized the temporary for n + 1)
         { Prof pr("topk_gather", st);
           HIP_TRY(launch_topk_gather(x->column(column), n, (const uint32_t*)keep.p, (const uint64_t*)pos.p, (Scored*)winners.p, kk, st)); }
         uint64_t kept = 0;

@@ -6,14 +6,7 @@
 // the keys equal to T, in ascending haystack order.  Plain C++: tests/native/score_topk_main.cpp compiles both with g++ and holds the eight passes to std::sort under a
 // sanitizer.
 #pragma once
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define AM_SCORE_HD __host__ __device__ __forceinline__
-#else
-#define AM_SCORE_HD inline
-#endif
+#include "am_rows.h"
 
 namespace am {
 namespace dev {
@@ -23,7 +16,7 @@ constexpr uint32_t kTopkDigits = 8, kTopkBins = 256;        // eight passes of e
 
 // order-preserving: a < b as int64 iff score_key(a, true) < score_key(b, true) as uint64 (the sign bit biased); complemented for "smallest", so that the best
 // score has the largest key either way
-AM_SCORE_HD uint64_t score_key(int64_t score, bool largest)
+AM_HD uint64_t score_key(int64_t score, bool largest)
 {
     const uint64_t k = (uint64_t)score ^ 0x8000000000000000ull;
     return largest ? k : ~k;
@@ -32,7 +25,7 @@ AM_SCORE_HD uint64_t score_key(int64_t score, bool largest)
 // the digit d of the k_left-th best key among the keys counted in hist (1 <= k_left <= the sum of hist): fewer than k_left keys carry a digit above d, at least
 // k_left carry d or a digit above it.  *k_left becomes the rank among the keys with digit d (1 .. hist[d]).  A k_left beyond the sum (not reachable for a caller
 // that keeps 1 <= k <= n) answers digit 0.
-AM_SCORE_HD uint32_t topk_pick(const uint64_t* hist, uint64_t* k_left)
+AM_HD uint32_t topk_pick(const uint64_t* hist, uint64_t* k_left)
 {
     uint64_t above = 0;
     for (uint32_t d = kTopkBins; d-- > 0;) {
@@ -44,12 +37,12 @@ AM_SCORE_HD uint32_t topk_pick(const uint64_t* hist, uint64_t* k_left)
 }
 
 // does the key still take part in pass `digit` (7: the top byte, every key does; below: the keys whose bytes above `digit` are the chosen prefix)
-AM_SCORE_HD bool topk_in_prefix(uint64_t key, uint64_t prefix, uint32_t digit)
+AM_HD bool topk_in_prefix(uint64_t key, uint64_t prefix, uint32_t digit)
 {
     return digit + 1 >= kTopkDigits || (key >> (8 * (digit + 1))) == prefix;
 }
 
-AM_SCORE_HD uint32_t topk_digit(uint64_t key, uint32_t digit) { return (uint32_t)(key >> (8 * digit)) & (kTopkBins - 1); }
+AM_HD uint32_t topk_digit(uint64_t key, uint32_t digit) { return (uint32_t)(key >> (8 * digit)) & (kTopkBins - 1); }
 
 // the state of a radix select in HBM: the chosen digits (the key's bytes above the current pass, right-aligned) and what remains of k
 struct TopkState { uint64_t prefix, k_left; };

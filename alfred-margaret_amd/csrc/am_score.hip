@@ -173,9 +173,6 @@ void score_launch(bool ic, dim3 grid, const SpansIn& in, const ScoreOut& out, hi
 
 // ---- top-k and range select over one column
 
-__device__ __forceinline__ uint64_t topk_lane() { return (uint64_t)blockIdx.x * kTopkThreads + threadIdx.x; }
-inline uint32_t topk_blocks(uint64_t n) { return (uint32_t)((n + kTopkThreads - 1) / kTopkThreads); }
-
 __global__ void __launch_bounds__(kTopkBins) k_topk_init(TopkState* __restrict__ state, unsigned long long* __restrict__ hist, uint64_t k)
 {
     hist[threadIdx.x] = 0;
@@ -219,19 +216,19 @@ __global__ void __launch_bounds__(kWave) k_topk_pick(TopkState* __restrict__ sta
 }
 
 // tie[i] = key i is the k-th key (n + 1 entries, the last one 0: the sum's trailing element)
-__global__ void __launch_bounds__(kTopkThreads) k_topk_ties(const int64_t* __restrict__ col, uint64_t n, uint32_t largest, const TopkState* __restrict__ state,
+__global__ void __launch_bounds__(kRowThreads) k_topk_ties(const int64_t* __restrict__ col, uint64_t n, uint32_t largest, const TopkState* __restrict__ state,
                                                             uint32_t* __restrict__ tie)
 {
-    const uint64_t i = topk_lane();
+    const uint64_t i = global_row();
     if (i > n) return;
     tie[i] = i < n && score_key(col[i], largest != 0) == state->prefix ? 1u : 0u;
 }
 
 // with tie_rank = the exclusive sum of tie: the keys above the k-th and the first q of its ties.  flags: n bytes (nullable); keep: n + 1 words, the last one 0 (nullable)
-__global__ void __launch_bounds__(kTopkThreads) k_topk_flags(const int64_t* __restrict__ col, uint64_t n, uint32_t largest, const TopkState* __restrict__ state,
+__global__ void __launch_bounds__(kRowThreads) k_topk_flags(const int64_t* __restrict__ col, uint64_t n, uint32_t largest, const TopkState* __restrict__ state,
                                                              const uint64_t* __restrict__ tie_rank, uint8_t* __restrict__ flags, uint32_t* __restrict__ keep)
 {
-    const uint64_t i = topk_lane();
+    const uint64_t i = global_row();
     if (i > n) return;
     if (i == n) { if (keep) keep[i] = 0; return; }
     const uint64_t key = score_key(col[i], largest != 0), cut = state->prefix, quota = state->k_left;
@@ -240,19 +237,19 @@ __global__ void __launch_bounds__(kTopkThreads) k_topk_flags(const int64_t* __re
     if (keep) keep[i] = f ? 1u : 0u;
 }
 
-__global__ void __launch_bounds__(kTopkThreads) k_score_range(const int64_t* __restrict__ col, uint64_t n, int64_t lo, int64_t hi, uint8_t* __restrict__ flags)
+__global__ void __launch_bounds__(kRowThreads) k_score_range(const int64_t* __restrict__ col, uint64_t n, int64_t lo, int64_t hi, uint8_t* __restrict__ flags)
 {
-    const uint64_t i = topk_lane();
+    const uint64_t i = global_row();
     if (i >= n) return;
     const int64_t s = col[i];
     flags[i] = lo <= s && s <= hi ? 1 : 0;
 }
 
 // with pos = the exclusive sum of keep: the winners in ascending haystack order
-__global__ void __launch_bounds__(kTopkThreads) k_topk_gather(const int64_t* __restrict__ col, uint64_t n, const uint32_t* __restrict__ keep, const uint64_t* __restrict__ pos,
+__global__ void __launch_bounds__(kRowThreads) k_topk_gather(const int64_t* __restrict__ col, uint64_t n, const uint32_t* __restrict__ keep, const uint64_t* __restrict__ pos,
                                                               Scored* __restrict__ out, uint64_t n_out)
 {
-    const uint64_t i = topk_lane();
+    const uint64_t i = global_row();
     if (i >= n || !keep[i]) return;
     const uint64_t p = pos[i];
     AM_BOUNDS(p < n_out);
@@ -292,25 +289,19 @@ hipError_t launch_topk_flags(const int64_t* col, uint64_t n, uint64_t k, bool la
         hipLaunchKernelGGL(k_topk_hist, hist_grid, dim3(kTopkThreads), 0, st, col, n, lg, digit, (const TopkState*)w.state, (unsigned long long*)w.hist);
         hipLaunchKernelGGL(k_topk_pick, dim3(1), dim3(kWave), 0, st, w.state, (unsigned long long*)w.hist);
     }
-    hipLaunchKernelGGL(k_topk_ties, dim3(topk_blocks(n + 1)), dim3(kTopkThreads), 0, st, col, n, lg, (const TopkState*)w.state, w.tie);
-    hipError_t e = launch_scan(w.scan_tmp, w.scan_tmp_bytes, w.tie, w.tie_rank, n + 1, st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_topk_flags, dim3(topk_blocks(n + 1)), dim3(kTopkThreads), 0, st, col, n, lg, (const TopkState*)w.state, (const uint64_t*)w.tie_rank, flags, keep);
-    return hipGetLastError();
+    hipError_t e = launch_rows(k_topk_ties, n + 1, st, col, n, lg, w.state, w.tie);
+    if (e == hipSuccess) e = launch_scan(w.scan_tmp, w.scan_tmp_bytes, w.tie, w.tie_rank, n + 1, st);
+    return e != hipSuccess ? e : launch_rows(k_topk_flags, n + 1, st, col, n, lg, w.state, w.tie_rank, flags, keep);
 }
 
 hipError_t launch_score_range(const int64_t* col, uint64_t n, int64_t lo, int64_t hi, uint8_t* flags, hipStream_t st)
 {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_score_range, dim3(topk_blocks(n)), dim3(kTopkThreads), 0, st, col, n, lo, hi, flags);
-    return hipGetLastError();
+    return launch_rows(k_score_range, n, st, col, n, lo, hi, flags);
 }
 
 hipError_t launch_topk_gather(const int64_t* col, uint64_t n, const uint32_t* keep, const uint64_t* pos, Scored* out, uint64_t n_out, hipStream_t st)
 {
-    if (n == 0 || n_out == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_topk_gather, dim3(topk_blocks(n)), dim3(kTopkThreads), 0, st, col, n, keep, pos, out, n_out);
-    return hipGetLastError();
+    return launch_rows(k_topk_gather, n_out ? n : 0, st, col, n, keep, pos, out, n_out);
 }
 
 }  // namespace dev

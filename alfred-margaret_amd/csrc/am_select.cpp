@@ -47,12 +47,9 @@ int compact(const am_batch* b, const uint8_t* d_flags, uint8_t constant, int inv
         jobs.j[2] = ScanJob{nullptr, (const uint64_t*)klen.p, (uint64_t*)koff.p, n + 1, nullptr};
         HIP_TRY(launch_scan_jobs(jobs, st));
     } else {
-        size_t tmp_bytes = 0;
-        HIP_TRY(scan64_temp_bytes(n + 1, &tmp_bytes));
-        AM_TRY(scan_tmp.ensure(tmp_bytes));
-        HIP_TRY(launch_scan(scan_tmp.p, scan_tmp.cap, (const uint32_t*)keep.p, (uint64_t*)rank.p, n + 1, st));
-        HIP_TRY(launch_scan(scan_tmp.p, scan_tmp.cap, (const uint32_t*)run_head.p, (uint64_t*)run_rank.p, n + 1, st));
-        HIP_TRY(launch_scan64(scan_tmp.p, scan_tmp.cap, (const uint64_t*)klen.p, (uint64_t*)koff.p, n + 1, st));
+        AM_TRY(exclusive_sum(scan_tmp, (const uint32_t*)keep.p, (uint64_t*)rank.p, n + 1, st));      // (one temporary: its size depends on n + 1 alone)
+        AM_TRY(exclusive_sum(scan_tmp, (const uint32_t*)run_head.p, (uint64_t*)run_rank.p, n + 1, st));
+        AM_TRY(exclusive_sum64(scan_tmp, (const uint64_t*)klen.p, (uint64_t*)koff.p, n + 1, st));
     }
     uint64_t tail[3] = {0, 0, 0};                           // the three scalars that cross
     HIP_TRY(hipMemcpyAsync(&tail[0], (const uint64_t*)rank.p + n, 8, hipMemcpyDeviceToHost, st));

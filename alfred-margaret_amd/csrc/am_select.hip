@@ -20,17 +20,12 @@ namespace dev {
 
 namespace {
 
-constexpr uint32_t kSelThreads = 256;
-
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kSelThreads - 1) / kSelThreads); }
-__device__ __forceinline__ uint64_t global_lane() { return (uint64_t)blockIdx.x * kSelThreads + threadIdx.x; }
-
 // one lane per haystack (+ one for the trailing zero of the scans' inputs)
-__global__ void __launch_bounds__(kSelThreads) k_select_plan(const uint8_t* __restrict__ flags, uint32_t constant, uint32_t invert, const uint64_t* __restrict__ src_offsets,
+__global__ void __launch_bounds__(kRowThreads) k_select_plan(const uint8_t* __restrict__ flags, uint32_t constant, uint32_t invert, const uint64_t* __restrict__ src_offsets,
                                                              uint64_t n, uint64_t src_total, uint32_t* __restrict__ keep, uint32_t* __restrict__ run_head,
                                                              uint64_t* __restrict__ klen)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     if (i > n) return;
     if (i == n) { keep[i] = 0; run_head[i] = 0; klen[i] = 0; return; }
     const bool inv = invert != 0;
@@ -45,13 +40,13 @@ __global__ void __launch_bounds__(kSelThreads) k_select_plan(const uint8_t* __re
 }
 
 // one lane per haystack (+ one for the closing entries)
-__global__ void __launch_bounds__(kSelThreads) k_select_emit(const uint32_t* __restrict__ keep, const uint32_t* __restrict__ run_head, const uint64_t* __restrict__ rank,
+__global__ void __launch_bounds__(kRowThreads) k_select_emit(const uint32_t* __restrict__ keep, const uint32_t* __restrict__ run_head, const uint64_t* __restrict__ rank,
                                                              const uint64_t* __restrict__ run_rank, const uint64_t* __restrict__ koff,
                                                              const uint64_t* __restrict__ src_offsets, uint64_t n, uint64_t n_kept, uint64_t n_runs,
                                                              uint32_t* __restrict__ indices, uint64_t* __restrict__ new_off, uint64_t* __restrict__ run_src,
                                                              uint64_t* __restrict__ run_dst)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     if (i > n) return;
     if (i == n) {
         AM_BOUNDS(rank[n] == n_kept && run_rank[n] == n_runs);
@@ -79,16 +74,13 @@ __global__ void __launch_bounds__(kSelThreads) k_select_emit(const uint32_t* __r
 hipError_t launch_select_plan(const uint8_t* flags, uint32_t constant, uint32_t invert, const uint64_t* src_offsets, uint64_t n, uint64_t src_total, uint32_t* keep,
                               uint32_t* run_head, uint64_t* klen, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_select_plan, dim3(blocks_for(n + 1)), dim3(kSelThreads), 0, st, flags, constant, invert, src_offsets, n, src_total, keep, run_head, klen);
-    return hipGetLastError();
+    return launch_rows(k_select_plan, n + 1, st, flags, constant, invert, src_offsets, n, src_total, keep, run_head, klen);
 }
 
 hipError_t launch_select_emit(const uint32_t* keep, const uint32_t* run_head, const uint64_t* rank, const uint64_t* run_rank, const uint64_t* koff, const uint64_t* src_offsets,
                               uint64_t n, uint64_t n_kept, uint64_t n_runs, uint32_t* indices, uint64_t* new_off, uint64_t* run_src, uint64_t* run_dst, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_select_emit, dim3(blocks_for(n + 1)), dim3(kSelThreads), 0, st, keep, run_head, rank, run_rank, koff, src_offsets, n, n_kept, n_runs, indices, new_off,
-                       run_src, run_dst);
-    return hipGetLastError();
+    return launch_rows(k_select_emit, n + 1, st, keep, run_head, rank, run_rank, koff, src_offsets, n, n_kept, n_runs, indices, new_off, run_src, run_dst);
 }
 
 }  // namespace dev

@@ -1,6 +1,6 @@
 // am_spans.cpp -- match spans on the device (include/am.h "match spans"): one scan of the batch, then the records a scan leaves in HBM are expanded through the value
 // lists and the needles' own lengths into (start, len, haystack, needle), all of them in fold order or the leftmost-longest non-overlapping selection
-// (am_spans.hip).  The result is CSR like am_fragments and stays in HBM until asked for: its handle, the finisher of long chains and the argument checks are
+// (am_spans.hip).  The result is CSR like am_fragments and stays in HBM until asked for: its handle, the chain selector's host sequence and the argument checks are
 // am_fold.h's, shared with the other folds.
 // A span table may carry a word class (am_span_table_create_words, include/am.h "whole words"): 8 dwords beside the lengths that the expansion filters with.
 #include "am_spans.h"
@@ -41,22 +41,18 @@ int select_leftmost_longest(const SpansIn& in, const Span* spans, uint64_t n_spa
 {
     uint64_t* const span_off = (uint64_t*)s->offsets.p;
     const uint64_t n_words = (in.total + 31) / 32;
-    DevBuf bits, pc, rank, scan_tmp, best, cand, tile_max, head, kept, kidx, flag;
+    DevBuf bits, pc, rank, scan_tmp, best, cand, tile_max, head, kept, kidx;
     uint64_t n_cand = 0;
     if (n_span != 0 && n_words != 0) {
         AM_TRY(bits.ensure((n_words + 1) * 4));
         AM_TRY(pc.ensure((n_words + 1) * 4));
         AM_TRY(rank.ensure((n_words + 1) * 8));
-        size_t tmp_bytes = 0;
-        HIP_TRY(scan_temp_bytes(n_words + 1, &tmp_bytes));
-        AM_TRY(scan_tmp.ensure(tmp_bytes));
         HIP_TRY(hipMemsetAsync(bits.p, 0, (n_words + 1) * 4, st));
         { Prof pr("spans_mark", st);
           HIP_TRY(launch_spans_mark(spans, n_span, in, (uint32_t*)bits.p, n_words, st)); }
         { Prof pr("spans_rank", st);
           HIP_TRY(launch_spans_popcount((const uint32_t*)bits.p, n_words, (uint32_t*)pc.p, st));
-          HIP_TRY(launch_scan(scan_tmp.p, scan_tmp.cap, (const uint32_t*)pc.p, (uint64_t*)rank.p, n_words + 1, st)); }
-        AM_TRY(read_u64((const uint64_t*)rank.p + n_words, &n_cand, st));
+          AM_TRY(exclusive_sum(scan_tmp, (const uint32_t*)pc.p, (uint64_t*)rank.p, n_words + 1, st, &n_cand)); }
     }
     if (n_cand == 0) {                                      // nothing but zero-length spans, or nothing at all: empty rows
         HIP_TRY(hipMemsetAsync(span_off, 0, ((uint64_t)in.n_hay + 1) * 8, st));
@@ -69,30 +65,19 @@ int select_leftmost_longest(const SpansIn& in, const Span* spans, uint64_t n_spa
     AM_TRY(head.ensure(n_cand + 1));
     AM_TRY(kept.ensure((n_cand + 1) * 4));
     AM_TRY(kidx.ensure((n_cand + 1) * 8));
-    AM_TRY(flag.ensure(64));
-    size_t tmp_bytes = 0;
-    HIP_TRY(scan_temp_bytes(n_cand + 1, &tmp_bytes));
-    AM_TRY(scan_tmp.ensure(tmp_bytes));                     // (the ranks are final: the scan's temporary may move)
-    uint32_t* const fl = (uint32_t*)flag.p;
     uint32_t* const kp = (uint32_t*)kept.p;
     const uint64_t* const cg = (const uint64_t*)cand.p;
     const uint64_t* const bs = (const uint64_t*)best.p;
     HIP_TRY(hipMemsetAsync(best.p, 0, n_cand * 8, st));
-    HIP_TRY(hipMemsetAsync(fl, 0, 64, st));
     { Prof pr("spans_best", st);
       HIP_TRY(launch_spans_best(spans, n_span, in, (const uint32_t*)bits.p, (const uint64_t*)rank.p, n_words, (uint64_t*)best.p, n_cand, st)); }
     { Prof pr("spans_candidates", st);
       HIP_TRY(launch_spans_candidates((const uint32_t*)bits.p, (const uint64_t*)rank.p, n_words, (uint64_t*)cand.p, n_cand, st)); }
     { Prof pr("spans_heads", st);
       HIP_TRY(launch_spans_heads(cg, bs, n_cand, (uint64_t*)tile_max.p, (uint8_t*)head.p, kp, st)); }
-    const long lim = cfg::get(cfg::kSpansChainLimit);
-    { Prof pr("spans_walk", st);
-      HIP_TRY(launch_spans_walk(cg, bs, n_cand, (const uint8_t*)head.p, kp, lim > 0 ? (uint32_t)std::min<long>(lim, 1L << 30) : kSpansChainLimit, fl, st)); }
-    AM_TRY(finish_long_chains(n_cand, kp, fl, [&](uint64_t* jump) { return launch_spans_next(cg, bs, n_cand, (const uint8_t*)head.p, jump, st); },
-                              "spans_next", "spans_double", &s->rounds, st));
-    HIP_TRY(launch_scan(scan_tmp.p, scan_tmp.cap, kp, (uint64_t*)kidx.p, n_cand + 1, st));
-    uint64_t n_out = 0;
-    AM_TRY(read_u64((const uint64_t*)kidx.p + n_cand, &n_out, st));
+    uint64_t n_out = 0;                                     // (the ranks are final, read back above: the scan's temporary may move)
+    AM_TRY(select_chains(SpansChain{cg, bs, n_cand}, (const uint8_t*)head.p, kp, (uint64_t*)kidx.p, scan_tmp, cfg::get(cfg::kSpansChainLimit), kSpansChainLimit,
+                         {"spans_walk", "spans_next", "spans_double"}, &n_out, &s->rounds, st));
     AM_TRY(s->data.ensure(n_out * sizeof(Span)));
     s->n_items = n_out;
     { Prof pr("spans_emit", st);
@@ -198,14 +183,10 @@ extern "C" int am_spans_batch(const am_span_table* t, int case_mode, int mode, c
     AM_TRY(voff.ensure((n_rec + 1) * 8));
     AM_TRY(rec_first.ensure(((uint64_t)b->n_hay + 1) * 8));
     AM_TRY(s->offsets.ensure(((uint64_t)b->n_hay + 1) * 8));
-    size_t tmp_bytes = 0;
-    HIP_TRY(scan_temp_bytes(n_rec + 1, &tmp_bytes));
-    AM_TRY(scan_tmp.ensure(tmp_bytes));
+    uint64_t n_span = 0;
     { Prof pr("spans_count", st);
       HIP_TRY(launch_spans_count(case_mode == AM_IGNORE_CASE, in, (uint32_t*)cnt.p, st));
-      HIP_TRY(launch_scan(scan_tmp.p, scan_tmp.cap, (const uint32_t*)cnt.p, (uint64_t*)voff.p, n_rec + 1, st)); }
-    uint64_t n_span = 0;
-    AM_TRY(read_u64((const uint64_t*)voff.p + n_rec, &n_span, st));
+      AM_TRY(exclusive_sum(scan_tmp, (const uint32_t*)cnt.p, (uint64_t*)voff.p, n_rec + 1, st, &n_span)); }
     DevBuf& spans = mode == AM_SPANS_ALL ? s->data : all_spans;
     AM_TRY(spans.ensure(n_span * sizeof(Span)));
     { Prof pr("spans_write", st);

@@ -19,9 +19,7 @@
 //       (2) the selection takes the smallest start >= cursor, which is <= g_i because g_i qualifies, and no candidate before i ends beyond g_i, so it cannot step over g_i;
 //       (3) hence it arrives at start g_i exactly, where candidate i is the longest span with the smallest handle.
 //     What happens before a head has no influence on what happens from it on: the CHAINS between heads are independent;
-//   * next[i] = the first candidate with g >= g_i + len_i (a galloping search on the sorted positions); the kept candidates of a chain are head, next[head], ...  A chain
-//     of up to `limit` looks is walked by its head's lane; longer ones are finished by pointer doubling (k_split_double of am_split.hip, same arrays), the host stops
-//     when a round marks nothing;
+//   * inside a chain the kept candidates are head, next[head], ... with next[i] = the first candidate with g >= g_i + len_i: the chain selector of am_chain.h;
 //   * kept flags -> exclusive sum -> the spans, and per haystack the index of its first one.
 // All indices are 64-bit.  Plain C++ and vector stores only.
 #include <hip/hip_runtime.h>
@@ -41,18 +39,15 @@ namespace dev {
 
 namespace {
 
-// (kSpThreads, the lanes of a workgroup: am_device.h, beside kSpansMaxTile)
+// (kSpThreads, the lanes of a workgroup of the prefix maximum: am_device.h, beside kSpansMaxTile)
 constexpr uint32_t kSpMaxPer = (uint32_t)(kSpansMaxTile / kSpThreads);      // candidates per lane of the prefix maximum
-
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kSpThreads - 1) / kSpThreads); }
-__device__ __forceinline__ uint64_t global_lane() { return (uint64_t)blockIdx.x * kSpThreads + threadIdx.x; }
 
 // one lane per record (+ one for the trailing zero of the scan's input): its values < n_needles; WORDS: those the word class keeps (span_of, am_words.h -- under
 // IC the backwards walk runs here and again in k_spans_write: no span that is dropped is ever written)
 template <bool IC, bool WORDS>
-__global__ void __launch_bounds__(kSpThreads) k_spans_count(SpansIn in, uint32_t* __restrict__ cnt)
+__global__ void __launch_bounds__(kRowThreads) k_spans_count(SpansIn in, uint32_t* __restrict__ cnt)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     if (i > in.n_rec) return;
     if (i == in.n_rec) { cnt[i] = 0; return; }
     const Record r = in.recs[i];
@@ -71,9 +66,9 @@ __global__ void __launch_bounds__(kSpThreads) k_spans_count(SpansIn in, uint32_t
 
 // one lane per record: its spans, in list order, at voff[i]
 template <bool IC, bool WORDS>
-__global__ void __launch_bounds__(kSpThreads) k_spans_write(SpansIn in, const uint64_t* __restrict__ voff, Span* __restrict__ spans, uint64_t n_span)
+__global__ void __launch_bounds__(kRowThreads) k_spans_write(SpansIn in, const uint64_t* __restrict__ voff, Span* __restrict__ spans, uint64_t n_span)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     if (i >= in.n_rec) return;
     const Record r = in.recs[i];
     if (i > 0) {
@@ -97,10 +92,10 @@ __global__ void __launch_bounds__(kSpThreads) k_spans_write(SpansIn in, const ui
 }
 
 // one lane per haystack (+ one for the end): the index of its first span
-__global__ void __launch_bounds__(kSpThreads) k_spans_offsets(const uint64_t* __restrict__ rec_first, const uint64_t* __restrict__ voff, uint64_t n_rec, uint32_t n_hay,
+__global__ void __launch_bounds__(kRowThreads) k_spans_offsets(const uint64_t* __restrict__ rec_first, const uint64_t* __restrict__ voff, uint64_t n_rec, uint32_t n_hay,
                                                               uint64_t* __restrict__ span_off)
 {
-    const uint64_t h = global_lane();
+    const uint64_t h = global_row();
     if (h > n_hay) return;
     const uint64_t r0 = rec_first[h];
     AM_BOUNDS(r0 <= n_rec);
@@ -119,9 +114,9 @@ __device__ __forceinline__ bool span_global(const SpansIn& in, const Span& x, ui
     return g < in.total;
 }
 
-__global__ void __launch_bounds__(kSpThreads) k_spans_mark(const Span* __restrict__ spans, uint64_t n_span, SpansIn in, uint32_t* __restrict__ bits, uint64_t n_words)
+__global__ void __launch_bounds__(kRowThreads) k_spans_mark(const Span* __restrict__ spans, uint64_t n_span, SpansIn in, uint32_t* __restrict__ bits, uint64_t n_words)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     if (i >= n_span) return;
     const Span x = spans[i];
     uint64_t g;
@@ -131,17 +126,17 @@ __global__ void __launch_bounds__(kSpThreads) k_spans_mark(const Span* __restric
     atomicOr(&bits[g >> 5], 1u << (g & 31u));
 }
 
-__global__ void __launch_bounds__(kSpThreads) k_spans_popcount(const uint32_t* __restrict__ bits, uint64_t n_words, uint32_t* __restrict__ pc)
+__global__ void __launch_bounds__(kRowThreads) k_spans_popcount(const uint32_t* __restrict__ bits, uint64_t n_words, uint32_t* __restrict__ pc)
 {
-    const uint64_t w = global_lane();
+    const uint64_t w = global_row();
     if (w > n_words) return;
     pc[w] = w < n_words ? (uint32_t)__popc(bits[w]) : 0u;
 }
 
-__global__ void __launch_bounds__(kSpThreads) k_spans_best(const Span* __restrict__ spans, uint64_t n_span, SpansIn in, const uint32_t* __restrict__ bits,
+__global__ void __launch_bounds__(kRowThreads) k_spans_best(const Span* __restrict__ spans, uint64_t n_span, SpansIn in, const uint32_t* __restrict__ bits,
                                                            const uint64_t* __restrict__ rank, uint64_t n_words, uint64_t* __restrict__ best, uint64_t n_cand)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     if (i >= n_span) return;
     const Span x = spans[i];
     uint64_t g;
@@ -157,10 +152,10 @@ __global__ void __launch_bounds__(kSpThreads) k_spans_best(const Span* __restric
 }
 
 // one lane per bitmap word: the positions of its set bits, ascending, from rank[w] on
-__global__ void __launch_bounds__(kSpThreads) k_spans_candidates(const uint32_t* __restrict__ bits, const uint64_t* __restrict__ rank, uint64_t n_words,
+__global__ void __launch_bounds__(kRowThreads) k_spans_candidates(const uint32_t* __restrict__ bits, const uint64_t* __restrict__ rank, uint64_t n_words,
                                                                  uint64_t* __restrict__ cand_g, uint64_t n_cand)
 {
-    const uint64_t w = global_lane();
+    const uint64_t w = global_row();
     if (w >= n_words) return;
     uint32_t m = bits[w];
     uint64_t k = rank[w];
@@ -256,44 +251,14 @@ __global__ void __launch_bounds__(kSpThreads) k_spans_heads(const uint64_t* __re
     }
 }
 
-// the head's lane walks its chain; a chain that needs more than `limit` looks is left to the doubling rounds (*long_chains != 0)
-__global__ void __launch_bounds__(kSpThreads) k_spans_walk(const uint64_t* __restrict__ cand_g, const uint64_t* __restrict__ best, uint64_t n_cand,
-                                                           const uint8_t* __restrict__ head, uint32_t* __restrict__ kept, uint32_t limit, uint32_t* __restrict__ long_chains)
-{
-    const uint64_t i = global_lane();
-    if (i >= n_cand || !head[i]) return;
-    uint64_t end = cand_end(cand_g, best, i);
-    uint32_t looks = 0;
-    for (uint64_t j = i + 1; j < n_cand && !head[j]; j++) {
-        if (++looks > limit) { *long_chains = 1; return; }
-        if (cand_g[j] >= end) { kept[j] = 1; end = cand_end(cand_g, best, j); }      // (only this lane writes inside its chain)
-    }
-}
-
-// jump[i] = next[i]: the first candidate of i's chain at or after the end of i; i itself when there is none or when it is a head (the next chain's own)
-__global__ void __launch_bounds__(kSpThreads) k_spans_next(const uint64_t* __restrict__ cand_g, const uint64_t* __restrict__ best, uint64_t n_cand,
-                                                           const uint8_t* __restrict__ head, uint64_t* __restrict__ jump)
-{
-    const uint64_t i = global_lane();
-    if (i >= n_cand) return;
-    const uint64_t end = cand_end(cand_g, best, i);
-    uint64_t lo = i + 1, step = 1, probe = i + 1;
-    while (probe < n_cand && cand_g[probe] < end) { lo = probe + 1; step <<= 1; probe = i + step; }
-    uint64_t hi = probe < n_cand ? probe : n_cand;
-    while (lo < hi) { const uint64_t mid = lo + ((hi - lo) >> 1); if (cand_g[mid] < end) lo = mid + 1; else hi = mid; }
-    AM_BOUNDS(lo > i && lo <= n_cand);
-    jump[i] = (lo >= n_cand || head[lo]) ? i : lo;
-}
-
 // one lane per candidate: a kept one becomes a span of the haystack its position lies in
-__global__ void __launch_bounds__(kSpThreads) k_spans_emit(const uint64_t* __restrict__ cand_g, const uint64_t* __restrict__ best, const uint32_t* __restrict__ kept,
+__global__ void __launch_bounds__(kRowThreads) k_spans_emit(const uint64_t* __restrict__ cand_g, const uint64_t* __restrict__ best, const uint32_t* __restrict__ kept,
                                                            const uint64_t* __restrict__ kidx, uint64_t n_cand, SpansIn in, Span* __restrict__ out, uint64_t n_out)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     if (i >= n_cand || !kept[i]) return;
     const uint64_t g = cand_g[i], b = best[i];
-    uint64_t lo = 0, hi = in.n_hay - 1;                                // the largest h with offsets[h] <= g: offsets[h + 1] > g, the haystack that owns byte g
-    while (lo < hi) { const uint64_t mid = lo + ((hi - lo + 1) >> 1); if (in.offsets[mid] <= g) lo = mid; else hi = mid - 1; }
+    const uint64_t lo = last_at_or_before(in.offsets, (uint64_t)0, (uint64_t)in.n_hay - 1, g);      // offsets[lo] <= g < offsets[lo + 1]: the haystack that owns byte g
     const uint64_t o = kidx[i];
     AM_BOUNDS(o < n_out && in.offsets[lo] <= g && g + (b >> 32) <= in.offsets[lo + 1]);
     if (o >= n_out) return;
@@ -303,10 +268,10 @@ __global__ void __launch_bounds__(kSpThreads) k_spans_emit(const uint64_t* __res
 }
 
 // one lane per haystack (+ one for the end): the index of its first kept span = kidx of the first candidate at or after its first byte
-__global__ void __launch_bounds__(kSpThreads) k_spans_ll_offsets(const uint64_t* __restrict__ cand_g, const uint64_t* __restrict__ kidx, uint64_t n_cand, SpansIn in,
+__global__ void __launch_bounds__(kRowThreads) k_spans_ll_offsets(const uint64_t* __restrict__ cand_g, const uint64_t* __restrict__ kidx, uint64_t n_cand, SpansIn in,
                                                                  uint64_t* __restrict__ span_off, uint64_t n_out)
 {
-    const uint64_t h = global_lane();
+    const uint64_t h = global_row();
     if (h > in.n_hay) return;
     const uint64_t at = in.offsets[h];
     uint64_t lo = 0, hi = n_cand;
@@ -320,50 +285,40 @@ __global__ void __launch_bounds__(kSpThreads) k_spans_ll_offsets(const uint64_t*
 hipError_t launch_spans_count(bool ic, const SpansIn& in, uint32_t* cnt, hipStream_t st)
 {
     const auto kernel = !in.words ? k_spans_count<false, false> : ic ? k_spans_count<true, true> : k_spans_count<false, true>;      // (no class: the count needs no start, so no case mode)
-    hipLaunchKernelGGL(kernel, dim3(blocks_for(in.n_rec + 1)), dim3(kSpThreads), 0, st, in, cnt);
-    return hipGetLastError();
+    return launch_rows(kernel, in.n_rec + 1, st, in, cnt);
 }
 
 hipError_t launch_spans_write(bool ic, const SpansIn& in, const uint64_t* voff, Span* spans, uint64_t n_span, hipStream_t st)
 {
-    if (in.n_rec == 0 || n_span == 0) return hipSuccess;
+    if (n_span == 0) return hipSuccess;
     const auto kernel = in.words ? (ic ? k_spans_write<true, true> : k_spans_write<false, true>) : (ic ? k_spans_write<true, false> : k_spans_write<false, false>);
-    hipLaunchKernelGGL(kernel, dim3(blocks_for(in.n_rec)), dim3(kSpThreads), 0, st, in, voff, spans, n_span);
-    return hipGetLastError();
+    return launch_rows(kernel, in.n_rec, st, in, voff, spans, n_span);
 }
 
 hipError_t launch_spans_offsets(const uint64_t* rec_first, const uint64_t* voff, uint64_t n_rec, uint32_t n_hay, uint64_t* span_off, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_spans_offsets, dim3(blocks_for((uint64_t)n_hay + 1)), dim3(kSpThreads), 0, st, rec_first, voff, n_rec, n_hay, span_off);
-    return hipGetLastError();
+    return launch_rows(k_spans_offsets, (uint64_t)n_hay + 1, st, rec_first, voff, n_rec, n_hay, span_off);
 }
 
 hipError_t launch_spans_mark(const Span* spans, uint64_t n_span, const SpansIn& in, uint32_t* bits, uint64_t n_words, hipStream_t st)
 {
-    if (n_span == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_spans_mark, dim3(blocks_for(n_span)), dim3(kSpThreads), 0, st, spans, n_span, in, bits, n_words);
-    return hipGetLastError();
+    return launch_rows(k_spans_mark, n_span, st, spans, n_span, in, bits, n_words);
 }
 
 hipError_t launch_spans_popcount(const uint32_t* bits, uint64_t n_words, uint32_t* pc, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_spans_popcount, dim3(blocks_for(n_words + 1)), dim3(kSpThreads), 0, st, bits, n_words, pc);
-    return hipGetLastError();
+    return launch_rows(k_spans_popcount, n_words + 1, st, bits, n_words, pc);
 }
 
 hipError_t launch_spans_best(const Span* spans, uint64_t n_span, const SpansIn& in, const uint32_t* bits, const uint64_t* rank, uint64_t n_words, uint64_t* best, uint64_t n_cand,
                              hipStream_t st)
 {
-    if (n_span == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_spans_best, dim3(blocks_for(n_span)), dim3(kSpThreads), 0, st, spans, n_span, in, bits, rank, n_words, best, n_cand);
-    return hipGetLastError();
+    return launch_rows(k_spans_best, n_span, st, spans, n_span, in, bits, rank, n_words, best, n_cand);
 }
 
 hipError_t launch_spans_candidates(const uint32_t* bits, const uint64_t* rank, uint64_t n_words, uint64_t* cand_g, uint64_t n_cand, hipStream_t st)
 {
-    if (n_words == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_spans_candidates, dim3(blocks_for(n_words)), dim3(kSpThreads), 0, st, bits, rank, n_words, cand_g, n_cand);
-    return hipGetLastError();
+    return launch_rows(k_spans_candidates, n_words, st, bits, rank, n_words, cand_g, n_cand);
 }
 
 hipError_t launch_spans_heads(const uint64_t* cand_g, const uint64_t* best, uint64_t n_cand, uint64_t* tile_max, uint8_t* head, uint32_t* kept, hipStream_t st)
@@ -376,26 +331,11 @@ hipError_t launch_spans_heads(const uint64_t* cand_g, const uint64_t* best, uint
     return hipGetLastError();
 }
 
-hipError_t launch_spans_walk(const uint64_t* cand_g, const uint64_t* best, uint64_t n_cand, const uint8_t* head, uint32_t* kept, uint32_t limit, uint32_t* long_chains, hipStream_t st)
-{
-    if (n_cand == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_spans_walk, dim3(blocks_for(n_cand)), dim3(kSpThreads), 0, st, cand_g, best, n_cand, head, kept, limit, long_chains);
-    return hipGetLastError();
-}
-
-hipError_t launch_spans_next(const uint64_t* cand_g, const uint64_t* best, uint64_t n_cand, const uint8_t* head, uint64_t* jump, hipStream_t st)
-{
-    if (n_cand == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_spans_next, dim3(blocks_for(n_cand)), dim3(kSpThreads), 0, st, cand_g, best, n_cand, head, jump);
-    return hipGetLastError();
-}
-
 hipError_t launch_spans_emit(const uint64_t* cand_g, const uint64_t* best, const uint32_t* kept, const uint64_t* kidx, uint64_t n_cand, const SpansIn& in, Span* out, uint64_t n_out,
                              uint64_t* span_off, hipStream_t st)
 {
-    if (n_cand && in.n_hay) hipLaunchKernelGGL(k_spans_emit, dim3(blocks_for(n_cand)), dim3(kSpThreads), 0, st, cand_g, best, kept, kidx, n_cand, in, out, n_out);
-    hipLaunchKernelGGL(k_spans_ll_offsets, dim3(blocks_for((uint64_t)in.n_hay + 1)), dim3(kSpThreads), 0, st, cand_g, kidx, n_cand, in, span_off, n_out);
-    return hipGetLastError();
+    const hipError_t e = launch_rows(k_spans_emit, in.n_hay ? n_cand : 0, st, cand_g, best, kept, kidx, n_cand, in, out, n_out);
+    return e != hipSuccess ? e : launch_rows(k_spans_ll_offsets, (uint64_t)in.n_hay + 1, st, cand_g, kidx, n_cand, in, span_off, n_out);
 }
 
 }  // namespace dev

@@ -1,16 +1,9 @@
 // am_split.hip -- Splitter's fold on the device: stepAccum / finalizeAccum (reference: src/Data/Text/AhoCorasick/Splitter.hs:141-170) over the sorted records a scan of
 // the one-needle automaton has left in HBM, and the gather that turns the fragments into a batch of their own.
 //
-// The fold is sequential as written: a match is a separator iff it starts at or after the end of the last separator kept (:163-164).  What makes it parallel:
-//   * a record is a HEAD when it is the first of its haystack or starts at or after the end of the record before it.  A head is always kept: the records are sorted
-//     by end, so every record kept before it ends at or before the end of its predecessor, which is at or before the head's start.  What happens before a head has
-//     no influence on what happens from it on: the CHAINS between heads are independent.  For "\n" or "," every chain has length 1.
-//   * inside a chain, next[i] = the first record that starts at or after the end of i (starts are ordered like ends: every match spans the same number of code
-//     points), and the kept records are exactly the path head, next[head], next[next[head]], ...  A short chain is walked by its head's lane (k_split_walk, at most
-//     `limit` records looked at).  A chain beyond the limit -- "aa" over a run of a's is ONE chain through the whole text -- is finished by pointer doubling over all
-//     records: per round every kept record marks J[i] and J becomes J o J (k_split_double), so a path of k records is marked after log2(k) rounds; the host stops when
-//     a round marks nothing.  Every mark is a record of the true path (J[i] is a power of `next` applied to a kept record), so marks from partly walked chains and
-//     marks seen within the same round do no harm.
+// The fold is sequential as written: a match is a separator iff it starts at or after the end of the last separator kept (:163-164).  Heads, chains and pointer
+// doubling make it parallel: am_chain.h.  A record is a HEAD when it is the first of its haystack or starts at or after the end of the record before it (the records
+// are sorted by end, so every record kept before it ends at or before its start; starts are ordered like ends: every match spans the same number of code points).
 //   * kept flags -> exclusive sum -> fragment k of a haystack runs from the end of its kept separator k - 1 (or 0) to the start of kept separator k (or the length).
 //     A haystack with m kept separators has m + 1 fragments, so the fragment that ends at kept record i has the global index kidx[i] + haystack(i).
 // IgnoreCase: the start of a match is found by walking sep_len_code_points - 1 code points backwards from its last byte (Splitter.hs:117-121, Utf8.hs:256-276); the
@@ -31,13 +24,10 @@ namespace dev {
 
 namespace {
 
-constexpr uint32_t kSplitThreads = 256;
+constexpr uint32_t kGatherThreads = 256;                                // lanes of a k_split_gather workgroup
 constexpr uint32_t kGatherGroup = 16;                                  // bytes a lane of k_split_gather writes with one store
-constexpr uint64_t kGatherTile = (uint64_t)kSplitThreads * kGatherGroup;
+constexpr uint64_t kGatherTile = (uint64_t)kGatherThreads * kGatherGroup;
 constexpr int kGatherGroupsPerCu = 8;
-
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kSplitThreads - 1) / kSplitThreads); }
-__device__ __forceinline__ uint64_t global_lane() { return (uint64_t)blockIdx.x * kSplitThreads + threadIdx.x; }
 
 // sepStart of the match that record r reports, relative to its haystack (Splitter.hs:105-107 / :117-121)
 template <bool IC>
@@ -55,9 +45,9 @@ __device__ __forceinline__ uint64_t sep_start(const SplitIn& in, const Record& r
 
 // one lane per record (+ one for the trailing zero of the scan's input): start, head, kept = head
 template <bool IC>
-__global__ void __launch_bounds__(kSplitThreads) k_split_start(SplitIn in, uint64_t* __restrict__ start, uint8_t* __restrict__ head, uint32_t* __restrict__ kept)
+__global__ void __launch_bounds__(kRowThreads) k_split_start(SplitIn in, uint64_t* __restrict__ start, uint8_t* __restrict__ head, uint32_t* __restrict__ kept)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     if (i > in.n_rec) return;
     if (i == in.n_rec) { kept[i] = 0; return; }
     const Record r = in.recs[i];
@@ -73,55 +63,11 @@ __global__ void __launch_bounds__(kSplitThreads) k_split_start(SplitIn in, uint6
     kept[i] = h ? 1u : 0u;
 }
 
-// the head's lane walks its chain; a chain that needs more than `limit` looks is left to the doubling rounds (*long_chains != 0)
-__global__ void __launch_bounds__(kSplitThreads) k_split_walk(const Record* __restrict__ recs, uint64_t n_rec, const uint64_t* __restrict__ start,
-                                                              const uint8_t* __restrict__ head, uint32_t* __restrict__ kept, uint32_t limit, uint32_t* __restrict__ long_chains)
-{
-    const uint64_t i = global_lane();
-    if (i >= n_rec || !head[i]) return;
-    uint64_t end = recs[i].end_pos;
-    uint32_t looks = 0;
-    for (uint64_t j = i + 1; j < n_rec && !head[j]; j++) {
-        if (++looks > limit) { *long_chains = 1; return; }
-        if (start[j] >= end) { kept[j] = 1; end = recs[j].end_pos; }   // (only this lane writes inside its chain)
-    }
-}
-
-// J[i] = next[i]: the first record of i's chain that starts at or after the end of i; i itself when there is none.  (haystack, start) is sorted, so a galloping
-// search from i + 1 finds it; it stops at the next head at the latest (a head starts at or after the end of every record before it in its haystack).
-__global__ void __launch_bounds__(kSplitThreads) k_split_next(const Record* __restrict__ recs, uint64_t n_rec, const uint64_t* __restrict__ start,
-                                                              const uint8_t* __restrict__ head, uint64_t* __restrict__ jump)
-{
-    const uint64_t i = global_lane();
-    if (i >= n_rec) return;
-    const Record r = recs[i];
-    auto before = [&](uint64_t j) { return recs[j].haystack == r.haystack && start[j] < r.end_pos; };      // j > i: its haystack is r's or a later one
-    uint64_t lo = i + 1, step = 1, probe = i + 1;
-    while (probe < n_rec && before(probe)) { lo = probe + 1; step <<= 1; probe = i + step; }
-    uint64_t hi = probe < n_rec ? probe : n_rec;
-    while (lo < hi) { const uint64_t mid = lo + ((hi - lo) >> 1); if (before(mid)) lo = mid + 1; else hi = mid; }
-    AM_BOUNDS(lo > i && lo <= n_rec);
-    jump[i] = (lo >= n_rec || head[lo]) ? i : lo;
-}
-
-// one round of pointer doubling: kept records mark where they jump to, the jumps double
-__global__ void __launch_bounds__(kSplitThreads) k_split_double(const uint64_t* __restrict__ jump_in, uint64_t* __restrict__ jump_out, uint64_t n_rec,
-                                                                uint32_t* __restrict__ kept, uint32_t* __restrict__ marked)
-{
-    const uint64_t i = global_lane();
-    if (i >= n_rec) return;
-    uint64_t j = jump_in[i];
-    AM_BOUNDS(j < n_rec);
-    if (j >= n_rec) j = i;
-    jump_out[i] = jump_in[j];
-    if (kept[i] && !kept[j]) { kept[j] = 1; *marked = 1; }
-}
-
 // one lane per haystack (+ one for the end): its first fragment index; the start of its first fragment and the end of its last
-__global__ void __launch_bounds__(kSplitThreads) k_split_offsets(SplitIn in, const uint64_t* __restrict__ rec_first, const uint64_t* __restrict__ kidx,
+__global__ void __launch_bounds__(kRowThreads) k_split_offsets(SplitIn in, const uint64_t* __restrict__ rec_first, const uint64_t* __restrict__ kidx,
                                                                  uint64_t* __restrict__ frag_off, Fragment* __restrict__ frags, uint64_t n_frag)
 {
-    const uint64_t h = global_lane();
+    const uint64_t h = global_row();
     if (h > in.n_hay) return;
     const uint64_t r0 = rec_first[h];
     AM_BOUNDS(r0 <= in.n_rec);
@@ -137,11 +83,11 @@ __global__ void __launch_bounds__(kSplitThreads) k_split_offsets(SplitIn in, con
 }
 
 // one lane per record: a kept separator ends one fragment and starts the next
-__global__ void __launch_bounds__(kSplitThreads) k_split_emit(const Record* __restrict__ recs, uint64_t n_rec, const uint64_t* __restrict__ start,
+__global__ void __launch_bounds__(kRowThreads) k_split_emit(const Record* __restrict__ recs, uint64_t n_rec, const uint64_t* __restrict__ start,
                                                               const uint32_t* __restrict__ kept, const uint64_t* __restrict__ kidx,
                                                               Fragment* __restrict__ frags, uint64_t n_frag)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     if (i >= n_rec || !kept[i]) return;
     const Record r = recs[i];
     const uint64_t f = kidx[i] + r.haystack;
@@ -151,9 +97,9 @@ __global__ void __launch_bounds__(kSplitThreads) k_split_emit(const Record* __re
     frags[f + 1].start = r.end_pos;
 }
 
-__global__ void __launch_bounds__(kSplitThreads) k_split_lengths(Fragment* __restrict__ frags, uint64_t n_frag)
+__global__ void __launch_bounds__(kRowThreads) k_split_lengths(Fragment* __restrict__ frags, uint64_t n_frag)
 {
-    const uint64_t f = global_lane();
+    const uint64_t f = global_row();
     if (f >= n_frag) return;
     Fragment v = frags[f];
     AM_BOUNDS(v.start <= v.len);
@@ -163,23 +109,16 @@ __global__ void __launch_bounds__(kSplitThreads) k_split_lengths(Fragment* __res
 
 // ---- am_batch_from_fragments
 
-// the largest f in [lo, hi] with off[f] <= x (off ascending, off[lo] <= x)
-__device__ __forceinline__ uint64_t last_at_or_before(const uint64_t* __restrict__ off, uint64_t lo, uint64_t hi, uint64_t x)
-{
-    while (lo < hi) { const uint64_t mid = lo + ((hi - lo + 1) >> 1); if (off[mid] <= x) lo = mid; else hi = mid - 1; }
-    return lo;
-}
-
 // one lane per fragment (+ one for the trailing zero of the scan's input): its length, and where its bytes start in the source batch's text
-__global__ void __launch_bounds__(kSplitThreads) k_split_sources(const Fragment* __restrict__ frags, uint64_t n_frag, const uint64_t* __restrict__ frag_off,
+__global__ void __launch_bounds__(kRowThreads) k_split_sources(const Fragment* __restrict__ frags, uint64_t n_frag, const uint64_t* __restrict__ frag_off,
                                                                  const uint64_t* __restrict__ src_offsets, uint64_t n_hay, uint64_t src_total,
                                                                  uint64_t* __restrict__ lens, uint64_t* __restrict__ src_at)
 {
-    const uint64_t k = global_lane();
+    const uint64_t k = global_row();
     if (k > n_frag) return;
     if (k == n_frag) { lens[k] = 0; return; }
     const Fragment v = frags[k];
-    const uint64_t h = last_at_or_before(frag_off, 0, n_hay, k);      // frag_off[h] <= k < frag_off[h + 1]: every haystack has a fragment
+    const uint64_t h = last_at_or_before(frag_off, (uint64_t)0, n_hay, k);      // frag_off[h] <= k < frag_off[h + 1]: every haystack has a fragment
     AM_BOUNDS(h < n_hay);
     const uint64_t at = src_offsets[h < n_hay ? h : 0] + v.start;
     AM_BOUNDS(at + v.len <= src_total);
@@ -202,7 +141,7 @@ __device__ __forceinline__ uint4 load16_unaligned(const uint8_t* __restrict__ te
 // persistent grid over tiles of the NEW text: every lane owns 16 destination bytes (one aligned 16-byte store), finds the fragment its first byte belongs to --
 // between the fragments of the tile's first and last byte, which two lanes look up for the workgroup -- and reads the source wherever it lies.  Fragments of
 // length 0 own no byte and are never found.  Bytes beyond the end of the text are written as zeros.
-__global__ void __launch_bounds__(kSplitThreads) k_split_gather(const uint8_t* __restrict__ src, uint64_t src_total, const uint64_t* __restrict__ src_at,
+__global__ void __launch_bounds__(kGatherThreads) k_split_gather(const uint8_t* __restrict__ src, uint64_t src_total, const uint64_t* __restrict__ src_at,
                                                                 const uint64_t* __restrict__ dst_off, uint64_t n_frag, uint64_t total, uint8_t* __restrict__ dst)
 {
     __shared__ uint64_t tile_frag[2];
@@ -210,7 +149,7 @@ __global__ void __launch_bounds__(kSplitThreads) k_split_gather(const uint8_t* _
     for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {      // (the same tiles for every lane of the workgroup: the barriers are uniform)
         const uint64_t t0 = t * kGatherTile, t1 = std::min<uint64_t>(total, t0 + kGatherTile) - 1;
         __syncthreads();
-        if (threadIdx.x < 2) tile_frag[threadIdx.x] = last_at_or_before(dst_off, 0, n_frag - 1, threadIdx.x == 0 ? t0 : t1);
+        if (threadIdx.x < 2) tile_frag[threadIdx.x] = last_at_or_before(dst_off, (uint64_t)0, n_frag - 1, threadIdx.x == 0 ? t0 : t1);
         __syncthreads();
         const uint64_t d = t0 + (uint64_t)threadIdx.x * kGatherGroup;
         if (d >= total) continue;
@@ -251,46 +190,22 @@ uint32_t split_gather_tile_bytes() { return (uint32_t)kGatherTile; }
 
 hipError_t launch_split_start(bool ic, const SplitIn& in, uint64_t* start, uint8_t* head, uint32_t* kept, hipStream_t st)
 {
-    if (ic) hipLaunchKernelGGL(k_split_start<true>, dim3(blocks_for(in.n_rec + 1)), dim3(kSplitThreads), 0, st, in, start, head, kept);
-    else hipLaunchKernelGGL(k_split_start<false>, dim3(blocks_for(in.n_rec + 1)), dim3(kSplitThreads), 0, st, in, start, head, kept);
-    return hipGetLastError();
-}
-
-hipError_t launch_split_walk(const Record* recs, uint64_t n_rec, const uint64_t* start, const uint8_t* head, uint32_t* kept, uint32_t limit, uint32_t* long_chains, hipStream_t st)
-{
-    if (n_rec == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_split_walk, dim3(blocks_for(n_rec)), dim3(kSplitThreads), 0, st, recs, n_rec, start, head, kept, limit, long_chains);
-    return hipGetLastError();
-}
-
-hipError_t launch_split_next(const Record* recs, uint64_t n_rec, const uint64_t* start, const uint8_t* head, uint64_t* jump, hipStream_t st)
-{
-    if (n_rec == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_split_next, dim3(blocks_for(n_rec)), dim3(kSplitThreads), 0, st, recs, n_rec, start, head, jump);
-    return hipGetLastError();
-}
-
-hipError_t launch_split_double(const uint64_t* jump_in, uint64_t* jump_out, uint64_t n_rec, uint32_t* kept, uint32_t* marked, hipStream_t st)
-{
-    if (n_rec == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_split_double, dim3(blocks_for(n_rec)), dim3(kSplitThreads), 0, st, jump_in, jump_out, n_rec, kept, marked);
-    return hipGetLastError();
+    return launch_rows(ic ? k_split_start<true> : k_split_start<false>, in.n_rec + 1, st, in, start, head, kept);
 }
 
 hipError_t launch_split_emit(const SplitIn& in, const uint64_t* start, const uint32_t* kept, const uint64_t* kidx, const uint64_t* rec_first, uint64_t* frag_off,
                              Fragment* frags, uint64_t n_frag, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_split_offsets, dim3(blocks_for((uint64_t)in.n_hay + 1)), dim3(kSplitThreads), 0, st, in, rec_first, kidx, frag_off, frags, n_frag);
-    if (in.n_rec) hipLaunchKernelGGL(k_split_emit, dim3(blocks_for(in.n_rec)), dim3(kSplitThreads), 0, st, in.recs, in.n_rec, start, kept, kidx, frags, n_frag);
-    if (n_frag) hipLaunchKernelGGL(k_split_lengths, dim3(blocks_for(n_frag)), dim3(kSplitThreads), 0, st, frags, n_frag);
-    return hipGetLastError();
+    hipError_t e = launch_rows(k_split_offsets, (uint64_t)in.n_hay + 1, st, in, rec_first, kidx, frag_off, frags, n_frag);
+    if (e == hipSuccess) e = launch_rows(k_split_emit, in.n_rec, st, in.recs, in.n_rec, start, kept, kidx, frags, n_frag);
+    if (e == hipSuccess) e = launch_rows(k_split_lengths, n_frag, st, frags, n_frag);
+    return e;
 }
 
 hipError_t launch_split_sources(const Fragment* frags, uint64_t n_frag, const uint64_t* frag_off, const uint64_t* src_offsets, uint64_t n_hay, uint64_t src_total,
                                 uint64_t* lens, uint64_t* src_at, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_split_sources, dim3(blocks_for(n_frag + 1)), dim3(kSplitThreads), 0, st, frags, n_frag, frag_off, src_offsets, n_hay, src_total, lens, src_at);
-    return hipGetLastError();
+    return launch_rows(k_split_sources, n_frag + 1, st, frags, n_frag, frag_off, src_offsets, n_hay, src_total, lens, src_at);
 }
 
 hipError_t launch_split_gather(const uint8_t* src, uint64_t src_total, const uint64_t* src_at, const uint64_t* dst_off, uint64_t n_frag, uint64_t total, uint8_t* dst,
@@ -299,7 +214,7 @@ hipError_t launch_split_gather(const uint8_t* src, uint64_t src_total, const uin
     if (total == 0 || n_frag == 0) return hipSuccess;
     const uint64_t n_tiles = (total + kGatherTile - 1) / kGatherTile;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)(n_cu > 0 ? n_cu : 1) * kGatherGroupsPerCu);
-    hipLaunchKernelGGL(k_split_gather, dim3(grid), dim3(kSplitThreads), 0, st, src, src_total, src_at, dst_off, n_frag, total, dst);
+    hipLaunchKernelGGL(k_split_gather, dim3(grid), dim3(kGatherThreads), 0, st, src, src_total, src_at, dst_off, n_frag, total, dst);
     return hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 // am_splitter.cpp -- Data.Text.AhoCorasick.Splitter on the device (reference: src/Data/Text/AhoCorasick/Splitter.hs): one scan of the batch with the one-needle
 // automaton, then stepAccum / finalizeAccum (:141-170) over the sorted records in HBM (am_split.hip).  What comes back is a list of (start, length) per haystack that
 // stays in HBM until asked for, and am_batch_from_fragments turns it into a batch of its own: document -> lines -> any *_batch entry point, without the host.
-// The result handle, the chain finisher and the argument checks are am_fold.h's, shared with the other folds.
+// The result handle, the chain selector's host sequence and the argument checks are am_fold.h's, shared with the other folds.
 #include "am_host.h"
 
 using namespace am;
@@ -19,7 +19,7 @@ constexpr uint32_t kSplitChainLimit = 32;                 // records the lane of
 std::atomic<uint32_t> g_split_rounds{0};                  // doubling rounds of the last am_split_batch (am_debug_split_rounds)
 
 struct Bufs {
-    DevBuf start, head, kept, kidx, scan_tmp, rec_first, flag;
+    DevBuf start, head, kept, kidx, scan_tmp, rec_first;
 };
 
 }  // namespace
@@ -71,27 +71,15 @@ extern "C" int am_split_batch(const am_splitter* s, int case_mode, const am_batc
     AM_TRY(w.kept.ensure((n_rec + 1) * 4));
     AM_TRY(w.kidx.ensure((n_rec + 1) * 8));
     AM_TRY(w.rec_first.ensure(((uint64_t)b->n_hay + 1) * 8));
-    AM_TRY(w.flag.ensure(64));
-    size_t tmp_bytes = 0;
-    HIP_TRY(scan_temp_bytes(n_rec + 1, &tmp_bytes));
-    AM_TRY(w.scan_tmp.ensure(tmp_bytes));
-    uint32_t* const flag = (uint32_t*)w.flag.p;
     uint32_t* const kept = (uint32_t*)w.kept.p;
-    HIP_TRY(hipMemsetAsync(flag, 0, 64, st));
     { Prof pr("split_start", st);
       HIP_TRY(launch_split_start(case_mode == AM_IGNORE_CASE, in, (uint64_t*)w.start.p, (uint8_t*)w.head.p, kept, st)); }
     HIP_TRY(launch_rp_ranges(in.recs, n_rec, (uint64_t*)w.rec_first.p, kNoRoute, b->n_hay, st));
-    const long lim = cfg::get(cfg::kSplitChainLimit);
-    { Prof pr("split_walk", st);
-      HIP_TRY(launch_split_walk(in.recs, n_rec, (const uint64_t*)w.start.p, (const uint8_t*)w.head.p, kept, lim > 0 ? (uint32_t)std::min<long>(lim, 1L << 30) : kSplitChainLimit, flag, st)); }
     uint32_t rounds = 0;
-    AM_TRY(finish_long_chains(n_rec, kept, flag, [&](uint64_t* jump) {
-        return launch_split_next(in.recs, n_rec, (const uint64_t*)w.start.p, (const uint8_t*)w.head.p, jump, st);
-    }, "split_next", "split_double", &rounds, st));
-    g_split_rounds.store(rounds, std::memory_order_relaxed);
-    HIP_TRY(launch_scan(w.scan_tmp.p, w.scan_tmp.cap, kept, (uint64_t*)w.kidx.p, n_rec + 1, st));
     uint64_t n_kept = 0;
-    AM_TRY(read_u64((const uint64_t*)w.kidx.p + n_rec, &n_kept, st));
+    AM_TRY(select_chains(SplitChain{in.recs, (const uint64_t*)w.start.p, n_rec}, (const uint8_t*)w.head.p, kept, (uint64_t*)w.kidx.p, w.scan_tmp,
+                         cfg::get(cfg::kSplitChainLimit), kSplitChainLimit, {"split_walk", "split_next", "split_double"}, &n_kept, &rounds, st));
+    g_split_rounds.store(rounds, std::memory_order_relaxed);
     f->n_items = n_kept + b->n_hay;
     AM_TRY(f->data.ensure(f->n_items * sizeof(Fragment)));
     AM_TRY(f->offsets.ensure(((uint64_t)b->n_hay + 1) * 8));
@@ -155,13 +143,9 @@ extern "C" int am_batch_from_fragments(const am_batch* src, const am_fragments* 
     AM_TRY(src_at.ensure((n + 1) * 8));
     uint64_t* new_off; uint8_t* new_text;
     AM_TRY(nb.offsets(n, &new_off));
-    size_t tmp_bytes = 0;
-    HIP_TRY(scan64_temp_bytes(n + 1, &tmp_bytes));
-    AM_TRY(scan_tmp.ensure(tmp_bytes));
     HIP_TRY(launch_split_sources((const Fragment*)f->data.p, n, (const uint64_t*)f->offsets.p, src->d_offsets, src->n_hay, src->total, (uint64_t*)lens.p, (uint64_t*)src_at.p, st));
-    HIP_TRY(launch_scan64(scan_tmp.p, scan_tmp.cap, (const uint64_t*)lens.p, new_off, n + 1, st));
     uint64_t total = 0;
-    AM_TRY(read_u64(new_off + n, &total, st));
+    AM_TRY(exclusive_sum64(scan_tmp, (const uint64_t*)lens.p, new_off, n + 1, st, &total));
     AM_TRY(nb.text(total, st, &new_text));
     { Prof pr("split_gather", st);
       HIP_TRY(launch_split_gather((const uint8_t*)src->d_text, src->total, (const uint64_t*)src_at.p, new_off, n, total, new_text, g_rt.dev[src->dev].n_cu, st)); }

@@ -55,14 +55,10 @@ int splice(const am_batch* src, const struct am_spans* s, const am_subst_table* 
     if (r->templates) {                                     // a span owns 1 + nseg pieces: their exclusive sum numbers them, its total is the one scalar read here
         AM_TRY(cnt.ensure((n_span + 1) * 4));
         AM_TRY(pbase.ensure((n_span + 1) * 8));
-        size_t cnt_bytes = 0;
-        HIP_TRY(scan_temp_bytes(n_span + 1, &cnt_bytes));
-        AM_TRY(cnt_tmp.ensure(cnt_bytes));
+        uint64_t owned = 0;
         { Prof pr("subst_tpl_count", st);
           HIP_TRY(launch_subst_tpl_count(in, tpl, (uint32_t*)cnt.p, st));
-          HIP_TRY(launch_scan(cnt_tmp.p, cnt_tmp.cap, (const uint32_t*)cnt.p, (uint64_t*)pbase.p, n_span + 1, st)); }
-        uint64_t owned = 0;
-        AM_TRY(read_u64((const uint64_t*)pbase.p + n_span, &owned, st));
+          AM_TRY(exclusive_sum(cnt_tmp, (const uint32_t*)cnt.p, (uint64_t*)pbase.p, n_span + 1, st, &owned)); }
         n_pieces = owned + n_hay;
     }
     AM_TRY(lens.ensure((n_pieces + 1) * 8));
@@ -72,17 +68,14 @@ int splice(const am_batch* src, const struct am_spans* s, const am_subst_table* 
     AM_TRY(cidx.ensure((n_pieces + 1) * 8));
     uint64_t* new_off; uint8_t* new_text;
     AM_TRY(nb.offsets(n_hay, &new_off));
-    size_t tmp_bytes = 0;
-    HIP_TRY(scan64_temp_bytes(n_pieces + 1, &tmp_bytes));
-    AM_TRY(scan_tmp.ensure(tmp_bytes));
     HIP_TRY(hipMemsetAsync(lens.p, 0, (n_pieces + 1) * 8, st));
     HIP_TRY(hipMemsetAsync(live.p, 0, (n_pieces + 1) * 4, st));
     { Prof pr("subst_pieces", st);
       if (r->templates) HIP_TRY(launch_subst_tpl_pieces(in, tpl, (const uint64_t*)pbase.p, n_pieces, (uint64_t*)lens.p, (uint64_t*)src_at.p, (uint32_t*)live.p, st));
       else HIP_TRY(launch_subst_pieces(in, (uint64_t*)lens.p, (uint64_t*)src_at.p, (uint32_t*)live.p, st)); }
     { Prof pr("subst_scan", st);
-      HIP_TRY(launch_scan64(scan_tmp.p, scan_tmp.cap, (const uint64_t*)lens.p, (uint64_t*)dst_at.p, n_pieces + 1, st));
-      HIP_TRY(launch_scan(scan_tmp.p, scan_tmp.cap, (const uint32_t*)live.p, (uint64_t*)cidx.p, n_pieces + 1, st)); }
+      AM_TRY(exclusive_sum64(scan_tmp, (const uint64_t*)lens.p, (uint64_t*)dst_at.p, n_pieces + 1, st));      // (one temporary: its size depends on n_pieces + 1 alone)
+      AM_TRY(exclusive_sum(scan_tmp, (const uint32_t*)live.p, (uint64_t*)cidx.p, n_pieces + 1, st)); }
     uint64_t total = 0, n_live = 0;
     HIP_TRY(hipMemcpyAsync(&total, (const uint64_t*)dst_at.p + n_pieces, 8, hipMemcpyDeviceToHost, st));
     AM_TRY(read_u64((const uint64_t*)cidx.p + n_pieces, &n_live, st));

@@ -28,13 +28,10 @@ namespace dev {
 
 namespace {
 
-constexpr uint32_t kSubstThreads = 256;
+constexpr uint32_t kSubstThreads = 256;                                // lanes of a k_subst_gather workgroup
 constexpr uint32_t kSubstGroup = 16;                                   // bytes a lane of k_subst_gather writes with one store
 constexpr uint32_t kSubstTile = kSubstThreads * kSubstGroup;           // bytes of new text per staging of the piece table
 constexpr int kSubstBlocksPerCu = 3;                                   // 40 KiB of LDS each
-
-inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kSubstThreads - 1) / kSubstThreads); }
-__device__ __forceinline__ uint64_t global_lane() { return (uint64_t)blockIdx.x * kSubstThreads + threadIdx.x; }
 
 __device__ __forceinline__ void put_piece(uint64_t* __restrict__ lens, uint64_t* __restrict__ src_at, uint32_t* __restrict__ live, uint64_t n_pieces, uint64_t i,
                                           uint64_t len, uint64_t at)
@@ -48,9 +45,9 @@ __device__ __forceinline__ void put_piece(uint64_t* __restrict__ lens, uint64_t*
 
 // lanes [0, n_span): the gap before a span and its replacement; lanes [n_span, n_span + n_hay): the tail of a haystack; the last lane: the scans' trailing zero.
 // A piece whose source would leave the text or the pool (never, for the spans of this batch) is written with length 0.
-__global__ void __launch_bounds__(kSubstThreads) k_subst_pieces(SubstIn in, uint64_t* __restrict__ lens, uint64_t* __restrict__ src_at, uint32_t* __restrict__ live)
+__global__ void __launch_bounds__(kRowThreads) k_subst_pieces(SubstIn in, uint64_t* __restrict__ lens, uint64_t* __restrict__ src_at, uint32_t* __restrict__ live)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     const uint64_t n_pieces = 2 * in.n_span + in.n_hay;
     if (i > in.n_span + in.n_hay) return;
     if (i == in.n_span + in.n_hay) { lens[n_pieces] = 0; live[n_pieces] = 0; return; }
@@ -86,9 +83,9 @@ __global__ void __launch_bounds__(kSubstThreads) k_subst_pieces(SubstIn in, uint
 // ---- a table of templates (am_subst_tpl.h): span j owns 1 + nseg[needle_j] pieces, numbered through pbase = the exclusive sum of those counts
 
 // lanes [0, n_span): the pieces span j owns; the last lane: the scan's trailing zero
-__global__ void __launch_bounds__(kSubstThreads) k_subst_tpl_count(SubstIn in, SubstTpl tpl, uint32_t* __restrict__ cnt)
+__global__ void __launch_bounds__(kRowThreads) k_subst_tpl_count(SubstIn in, SubstTpl tpl, uint32_t* __restrict__ cnt)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     if (i > in.n_span) return;
     if (i == in.n_span) { cnt[i] = 0; return; }
     const uint32_t needle = in.spans[i].needle;
@@ -99,10 +96,10 @@ __global__ void __launch_bounds__(kSubstThreads) k_subst_tpl_count(SubstIn in, S
 // the lanes of k_subst_pieces with the template's pieces in the place of the replacement: lanes [0, n_span): the gap before a span and one piece per segment of its
 // template; lanes [n_span, n_span + n_hay): the tail of a haystack; the last lane: the scans' trailing zero.  A span that fails the checks of k_subst_pieces (never,
 // for the spans of this batch) leaves all its pieces at length 0, as the caller's memset made them.
-__global__ void __launch_bounds__(kSubstThreads) k_subst_tpl_pieces(SubstIn in, SubstTpl tpl, const uint64_t* __restrict__ pbase, uint64_t n_pieces, uint64_t* __restrict__ lens,
+__global__ void __launch_bounds__(kRowThreads) k_subst_tpl_pieces(SubstIn in, SubstTpl tpl, const uint64_t* __restrict__ pbase, uint64_t n_pieces, uint64_t* __restrict__ lens,
                                                                     uint64_t* __restrict__ src_at, uint32_t* __restrict__ live)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     if (i > in.n_span + in.n_hay) return;
     if (i == in.n_span + in.n_hay) { lens[n_pieces] = 0; live[n_pieces] = 0; return; }
     if (i < in.n_span) {
@@ -143,12 +140,12 @@ __global__ void __launch_bounds__(kSubstThreads) k_subst_tpl_pieces(SubstIn in, 
 
 // lanes [0, n_pieces]: a live piece goes to its place in the compacted table, the last lane writes the sentinel; lanes beyond: out_offsets (n_hay + 1).  pbase: the
 // piece numbering of a table of templates; null: the fixed plan 2j + h
-__global__ void __launch_bounds__(kSubstThreads) k_subst_compact(const uint64_t* __restrict__ src_at, const uint32_t* __restrict__ live, const uint64_t* __restrict__ dst_at,
+__global__ void __launch_bounds__(kRowThreads) k_subst_compact(const uint64_t* __restrict__ src_at, const uint32_t* __restrict__ live, const uint64_t* __restrict__ dst_at,
                                                                  const uint64_t* __restrict__ cidx, uint64_t n_pieces, uint64_t* __restrict__ cdst, uint64_t* __restrict__ csrc,
                                                                  uint64_t n_live, const uint64_t* __restrict__ span_off, const uint64_t* __restrict__ pbase, uint64_t n_span,
                                                                  uint64_t n_hay, uint64_t* __restrict__ out_off)
 {
-    const uint64_t i = global_lane();
+    const uint64_t i = global_row();
     if (i <= n_pieces) {
         if (i == n_pieces) { AM_BOUNDS(cidx[i] == n_live); cdst[n_live] = dst_at[i]; csrc[n_live] = 0; return; }
         if (!live[i]) return;
@@ -165,14 +162,6 @@ __global__ void __launch_bounds__(kSubstThreads) k_subst_compact(const uint64_t*
     const uint64_t ec = std::min<uint64_t>(e, n_span), p = pbase ? subst_tpl_gap_piece(pbase[ec], h) : 2 * ec + h;
     AM_BOUNDS(e <= n_span && p <= n_pieces);
     out_off[h] = dst_at[std::min<uint64_t>(p, n_pieces)];
-}
-
-// the largest f in [lo, hi] with off[f] <= x (off ascending, off[lo] <= x)
-template <class T, class X>
-__device__ __forceinline__ X last_at_or_before(const T* off, X lo, X hi, uint64_t x)
-{
-    while (lo < hi) { const X mid = lo + ((hi - lo + 1) >> 1); if ((uint64_t)off[mid] <= x) lo = mid; else hi = mid - 1; }
-    return lo;
 }
 
 __device__ __forceinline__ uint32_t bytes_below(int x) { return x <= 0 ? 0u : x >= 4 ? 0xFFFFFFFFu : (1u << (8 * x)) - 1u; }
@@ -265,29 +254,24 @@ void subst_geometry(uint32_t* group_bytes, uint32_t* tile_bytes) { *group_bytes 
 
 hipError_t launch_subst_pieces(const SubstIn& in, uint64_t* lens, uint64_t* src_at, uint32_t* live, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_subst_pieces, dim3(blocks_for(in.n_span + in.n_hay + 1)), dim3(kSubstThreads), 0, st, in, lens, src_at, live);
-    return hipGetLastError();
+    return launch_rows(k_subst_pieces, in.n_span + in.n_hay + 1, st, in, lens, src_at, live);
 }
 
 hipError_t launch_subst_tpl_count(const SubstIn& in, const SubstTpl& tpl, uint32_t* cnt, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_subst_tpl_count, dim3(blocks_for(in.n_span + 1)), dim3(kSubstThreads), 0, st, in, tpl, cnt);
-    return hipGetLastError();
+    return launch_rows(k_subst_tpl_count, in.n_span + 1, st, in, tpl, cnt);
 }
 
 hipError_t launch_subst_tpl_pieces(const SubstIn& in, const SubstTpl& tpl, const uint64_t* pbase, uint64_t n_pieces, uint64_t* lens, uint64_t* src_at, uint32_t* live,
                                    hipStream_t st)
 {
-    hipLaunchKernelGGL(k_subst_tpl_pieces, dim3(blocks_for(in.n_span + in.n_hay + 1)), dim3(kSubstThreads), 0, st, in, tpl, pbase, n_pieces, lens, src_at, live);
-    return hipGetLastError();
+    return launch_rows(k_subst_tpl_pieces, in.n_span + in.n_hay + 1, st, in, tpl, pbase, n_pieces, lens, src_at, live);
 }
 
 hipError_t launch_subst_compact(const uint64_t* src_at, const uint32_t* live, const uint64_t* dst_at, const uint64_t* cidx, uint64_t n_pieces, uint64_t* cdst, uint64_t* csrc,
                                 uint64_t n_live, const uint64_t* span_off, const uint64_t* pbase, uint64_t n_span, uint64_t n_hay, uint64_t* out_off, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_subst_compact, dim3(blocks_for(n_pieces + 1 + n_hay + 1)), dim3(kSubstThreads), 0, st, src_at, live, dst_at, cidx, n_pieces, cdst, csrc, n_live,
-                       span_off, pbase, n_span, n_hay, out_off);
-    return hipGetLastError();
+    return launch_rows(k_subst_compact, n_pieces + 1 + n_hay + 1, st, src_at, live, dst_at, cidx, n_pieces, cdst, csrc, n_live, span_off, pbase, n_span, n_hay, out_off);
 }
 
 hipError_t launch_subst_gather(const uint8_t* text, uint64_t src_total, const uint8_t* pool, uint64_t pool_bytes, const uint64_t* cdst, const uint64_t* csrc, uint64_t n_live,

@@ -158,6 +158,22 @@ def test_chains_with_varying_gaps(route, seed):
         check_split("aabaa", hays, False, route, strings=(limit == -1), exp=exp)
 
 
+def test_chains_end_at_a_haystack_boundary(route):
+    """"aa" over 9, 2 and 11 a's with the head's lane looking at one record: chains of three records and more end where a haystack ends, and the next haystack's
+    first records start below the ends before them -- the search for next[] must not leave its haystack.  Over runs of a's alone every haystack keeps its even
+    starts, so a jump that strays into the next haystack lands on a record that is kept anyway; with a "b" in front of the last run its kept starts are the odd
+    ones, and a stray jump marks a record the fold drops."""
+    am.debug_set("AM_SPLIT_CHAIN_LIMIT", 1)
+    try:
+        exp = check_split("aa", ["a" * 9, "a" * 2, "a" * 11], False, route)
+        assert am.api.libam().am_debug_split_rounds() >= 1      # (the doubling rounds ran)
+        odd = check_split("aa", ["a" * 9, "a" * 2, "b" + "a" * 11], False, route)
+    finally:
+        am.debug_set("AM_SPLIT_CHAIN_LIMIT", -1)
+    assert exp == [[(0, 0), (2, 0), (4, 0), (6, 0), (8, 1)], [(0, 0), (2, 0)], [(0, 0), (2, 0), (4, 0), (6, 0), (8, 0), (10, 1)]]
+    assert odd == exp[:2] + [[(0, 1), (3, 0), (5, 0), (7, 0), (9, 0), (11, 1)]]
+
+
 def test_ignore_case_matches_of_other_byte_lengths(route):
     # "k" matches U+212A KELVIN SIGN (three bytes)
     hays = ["aKbKKc", "K", "kKKk", "x" * 100 + "K" + "y" * 29 + "K"]
