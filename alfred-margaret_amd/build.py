@@ -5,6 +5,7 @@
   libam_check.so     TEST-ONLY (tests/native/am_ac.hip): k_ac, the general AC-walk kernel = the parity gate's independent second algorithm;
                      registers itself with libam when loaded (tests, bench.py's gate, smoke()); the product never loads it
   libam_scancheck.so TEST-ONLY (tests/native/am_scan_check.hip): csrc/am_scan.hip's launchers over host arrays, compiled with libam.so's flags
+  libam_postcheck.so TEST-ONLY (tests/native/am_post_check.hip): csrc/am_postings.hip's launchers over host arrays, compiled with libam.so's flags
   libam_imgcheck.so  TEST-ONLY (tests/native/am_imgcheck.cpp) host interpreter of the device image (g++, no HIP)
   libam_synth.so     synthetic haystack generator (bench/test input; device kernel + identical host loop)
 
@@ -63,7 +64,8 @@ def _glob_deps(*dirs):
 
 
 def _libam_flags(src):
-    """What hipcc gets for one source of libam.so -- and for tests/native/am_scan_check.hip, which carries csrc/am_scan.hip's kernels as libam.so carries them."""
+    """What hipcc gets for one source of libam.so -- and for tests/native/am_scan_check.hip and am_post_check.hip, which carry csrc/am_scan.hip's and am_postings.hip's
+    kernels as libam.so carries them."""
     san = SAN_FLAGS if src.endswith(".cpp") else []                  # host translation units only
     return ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", *san, *BOUNDS]
 
@@ -147,6 +149,19 @@ def build_scancheck(force=False):
     return target
 
 
+def build_postcheck(force=False):
+    """TEST-ONLY libam_postcheck.so (tests/native/am_post_check.hip): csrc/am_postings.hip included textually and compiled with libam.so's own flags, its seven
+    launchers behind a C interface over host arrays (tests/postings_cases.py).  Links nothing of the product and is loaded by nothing but the tests; built on demand."""
+    os.makedirs(LIB, exist_ok=True)
+    target = os.path.join(LIB, "libam_postcheck.so")
+    src = os.path.join(NATIVE_TESTS, "am_post_check.hip")
+    deps = [src, os.path.join(CSRC, "am_postings.hip")] + [d for d in _glob_deps(CSRC) if d.endswith((".h", ".inc"))]
+    if force or _stale(target, deps):
+        subprocess.check_call([_hipcc(), *_libam_flags(src), "-shared", "-I", CSRC, "-I", os.path.join(ROOT, "include"), "-x", "hip", src, "-o", target + ".tmp"])
+        os.replace(target + ".tmp", target)
+    return target
+
+
 def build_host(force=False):
     os.makedirs(LIB, exist_ok=True)
     target = os.path.join(LIB, "libam_host.so")
@@ -173,7 +188,8 @@ def build_synth(force=False):
 
 def build_all(force=False):
     return {"libam": build_libam(force), "libam_host": build_host(force), "libam_check": build_check(force), "libam_imgcheck": build_imgcheck(force),
-            "libam_synth": build_synth(force), "libam_rccl_stub": build_rccl_stub(force), "libam_scancheck": build_scancheck(force)}
+            "libam_synth": build_synth(force), "libam_rccl_stub": build_rccl_stub(force), "libam_scancheck": build_scancheck(force),
+            "libam_postcheck": build_postcheck(force)}
 
 
 if __name__ == "__main__":

@@ -200,6 +200,137 @@ def test_handles_on_either_side_of_every_digit_boundary(n_needles):
         assert not gf[np.diff(go) == 0].any()
 
 
+# ---- 3b. the host sequence (am_postings.cpp: keys, per pass hist + exclusive sum + scatter with the two buffer pairs taking turns, gather, offsets, df) on several
+# tiles, for every pass count.  Two-letter needles over an alphabet without the space and haystacks of two-letter tokens separated by spaces: the spans are exactly
+# the tokens (start 3 i, length 2), in order, in both span modes.  About 600 handles of the caller's own that fill the lowest digit and spread over every higher one.
+
+PAIRS = [a + b for a in string.ascii_lowercase for b in string.ascii_lowercase]
+
+
+def wide_handles(n_needles):
+    """the seam handles, every value of the lowest digit, and 64 values of every higher digit (all of them where a key below n_needles has fewer), with random
+    bits below"""
+    _, _, passes, bits = am.api.postings_geometry(n_needles)
+    rng = random.Random(9960 + passes)
+    hs = set(seam_handles(n_needles)) | set(range(min(1 << bits[0], n_needles)))
+    shift = bits[0]
+    for b in bits[1:]:
+        top = min((1 << b) - 1, (n_needles - 1) >> shift)  # the largest value of this digit below n_needles
+        count = min(64, top + 1)
+        for k in range(count):
+            v = (k * (top + 1) // count) << shift
+            h = v | rng.randrange(1 << shift)
+            hs.add(h if h < n_needles else v)
+        hs.add(top << shift)
+        shift += b
+    while len(hs) < min(600, n_needles):                   # ... and random ones up to about 600
+        hs.add(rng.randrange(n_needles))
+    return sorted(hs)
+
+
+def digit_values(handles, n_needles):
+    _, _, _, bits = am.api.postings_geometry(n_needles)
+    out, shift = [], 0
+    for b in bits:
+        out.append(len({(h >> shift) & ((1 << b) - 1) for h in handles}))
+        shift += b
+    return out
+
+
+def token_dict(n_needles):
+    handles = wide_handles(n_needles)
+    assert len(handles) <= len(PAIRS) and max(handles) == n_needles - 1 and min(handles) == 0
+    twos = np.full(n_needles, 2, np.uint32)
+    needles = PAIRS[:len(handles)]
+    return Dict(needles, values=handles, n_needles=n_needles, lengths=(twos, twos)), needles, dict(zip(needles, handles))
+
+
+def token_hays(tokens, cuts):
+    return [" ".join(tokens[a:b]) for a, b in zip(cuts, cuts[1:])]
+
+
+def token_rows(hays, handle_of):
+    return [[(3 * i, 2, handle_of[tok]) for i, tok in enumerate(h.split(" "))] if h else [] for h in hays]
+
+
+def check_sparse(d, hays, rows, n_needles, mode, what):
+    """One result of the public API against the definition over literal rows: data, source, all N + 1 offsets, doc_freq zero wherever a row is empty; and a second
+    call's bytes.  Returns the postings (the caller closes them)."""
+    data, source, df = ref.postings_sparse(rows)
+    x = d.t.postings_texts(0, hays, mode)
+    try:
+        assert (x.size, x.n_needles, x.n_hay) == (len(data), n_needles, len(hays)), what
+        go, gd, gs, gf = arrays(x)
+        assert tuples(gd) == data, (what, first_difference(tuples(gd), data))
+        assert gs.tolist() == source, (what, first_difference(gs.tolist(), source))
+        want = np.searchsorted(np.asarray([r[3] for r in data], np.uint64), np.arange(n_needles + 1, dtype=np.uint64), side="left")
+        assert go.shape == (n_needles + 1,) and np.array_equal(go, want.astype(np.uint64)), what      # all N + 1 offsets
+        want_df = np.zeros(n_needles, np.uint64)
+        for v, k in df.items():
+            want_df[v] = k
+        assert gf.shape == (n_needles,) and np.array_equal(gf, want_df), what      # zero wherever a row is empty
+        assert not gf[np.diff(go) == 0].any(), what
+        with d.t.postings_texts(0, hays, mode) as y:       # the same text twice: the same bytes in all four arrays
+            for u, v in zip((go, gd, gs, gf), arrays(y)):
+                assert u.dtype == v.dtype and u.tobytes() == v.tobytes(), what
+    except BaseException:
+        x.close()
+        raise
+    return x
+
+
+@pytest.mark.parametrize("n_needles", [256, 257, 65536, 65537, 2 ** 24 + 2])
+def test_every_pass_count_on_several_tiles(n_needles):
+    tile, wave, passes, bits = am.api.postings_geometry(n_needles)
+    assert passes == {256: 1, 257: 2, 65536: 2, 65537: 3, 2 ** 24 + 2: 4}[n_needles]      # both parities of the buffer that holds the sorted pairs
+    d, needles, handle_of = token_dict(n_needles)
+    values = digit_values(handle_of.values(), n_needles)
+    assert values[0] == 1 << bits[0] and all(v >= min(64, 1 << bits[k], ((n_needles - 1) >> sum(bits[:k])) + 1) for k, v in enumerate(values)), values
+    assert len(needles) == min(600, n_needles)
+    n = 3 * tile + wave + 1
+    rng = random.Random(9961 + passes)
+    tokens = [rng.choice(needles) for _ in range(n)]
+    tokens[:len(needles)] = rng.sample(needles, len(needles))      # every handle occurs
+    cuts = [0, 0, 5, 69, wave, wave, tile - 70, tile + wave + 3, 2 * tile, 2 * tile, 2 * tile + 1, 3 * tile - 1, n, n]      # 13 haystacks, four of them empty, one
+    hays = token_hays(tokens, cuts)                                                                                          # across a tile of the sort
+    rows = token_rows(hays, handle_of)
+    assert sum(map(len, rows)) == n > 3 * tile and len(hays) == 13 and hays.count("") == 4
+    for mode in (ALL, LL):
+        check_sparse(d, hays, rows, n_needles, mode, (n_needles, mode)).close()
+
+
+def test_a_count_table_beyond_one_tile_of_the_prefix_sum():
+    """N = 256, one pass of 8 bits: 256 x n_tiles cells.  With more tiles than one workgroup of the exclusive sum takes cells for, the bases of the high digit
+    values come through the sum's second level; one tile of spans more than that needs.  Many haystacks, empty ones among them: am_spans_of_needle for the most
+    frequent and the rarest needle searches more haystack offsets than one workgroup of the row kernels writes."""
+    from tests import postings_cases as pc, scan_cases as sc
+    tile, wave, passes, bits = am.api.postings_geometry(256)
+    scan_tile, row_threads = sc.limits().tile, pc.limits().row_threads
+    assert (passes, bits) == (1, [8])
+    n_tiles = scan_tile // 256 + 2
+    n = (n_tiles - 1) * tile + wave + 1
+    assert 256 * (n_tiles - 1) > scan_tile and n <= 400000, (n, scan_tile)
+    d, needles, handle_of = token_dict(256)
+    assert sorted(handle_of.values()) == list(range(256))
+    rng = random.Random(9962)
+    hot, rare = needles[200], needles[77]
+    pool = [x for x in needles if x != rare]
+    tokens = [hot if rng.random() < 0.3 else rng.choice(pool) for _ in range(n)]
+    tokens[n // 2] = rare                                  # once
+    n_hay = 3 * row_threads + 1
+    cuts = sorted([0, n] + [rng.randrange(n + 1) for _ in range(n_hay - 41)] + [rng.randrange(n + 1)] * 20 + [0] * 10 + [n] * 10)
+    hays = token_hays(tokens, cuts)
+    rows = token_rows(hays, handle_of)
+    assert len(hays) == n_hay > 257 and sum(map(len, rows)) == n and hays[0] == "" and hays[-1] == "" and hays.count("") >= 30
+    for mode in (ALL, LL):
+        with check_sparse(d, hays, rows, 256, mode, mode) as p:
+            counts = np.diff(p.offsets)
+            assert int(np.argmax(counts)) == handle_of[hot] and counts[handle_of[rare]] == 1 == counts.min()
+            for needle in (handle_of[hot], handle_of[rare]):
+                kept = check_row(p, rows, needle, mode)
+                assert sum(map(len, kept)) == counts[needle]
+
+
 # ---- 4. document frequency
 
 def test_document_frequencies_across_wavefronts_and_tiles():
