@@ -58,6 +58,7 @@ NEAR_MAX_GROUPS, NEAR_MAX_QUERIES, NEAR_ORDERED = 32, 64, 1          # AM_NEAR_M
 NEAR_ANYWHERE = 2 ** 64 - 1          # a max_gap that every pair of one haystack meets
 SPANS_ALL = 0
 SPANS_LEFTMOST_LONGEST = 1
+SPAN_TABLE_WORDS = 1                 # AM_SPAN_TABLE_WORDS: a flag of am_span_table_create_cased
 SUBST_MAX_SEGMENTS, SEG_LITERAL, SEG_MATCH = 64, 0, 1          # AM_SUBST_MAX_SEGMENTS, AM_SEG_LITERAL, AM_SEG_MATCH
 EXTRACT_EACH = 0
 EXTRACT_MERGED = 1
@@ -127,6 +128,9 @@ ABI = {
     "am_word_bytes_default": (None, [_vp]),
     "am_span_table_create_words": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "am_span_table_word_bytes": (C.c_int, [_vp, _vp]),
+    "am_span_table_create_cased": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.POINTER(_vp)]),
+    "am_span_table_check_exact": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp]),
+    "am_span_table_exact": (C.c_int, [_vp, C.c_uint32, C.POINTER(_vp), _u64p]),
     "am_count_spans_by_needle_batch": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "am_count_spans_by_needle": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp]),
     "am_spans_batch": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.POINTER(_vp)]),
@@ -326,12 +330,15 @@ _HOST = {
     "amh_spans_fold": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
     "amh_spans_fold_words": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
     "amh_spans": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(Slice), _sz, _vp, _vp, _sz, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
+    "amh_spans_fold_cased": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
+    "amh_spans_cased": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
     "amh_extract_fold": (C.c_int, [_vp, _vp, C.POINTER(Slice), _sz, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(_vp), C.POINTER(_vp), _u64p]),
     "amh_rules_fold": (C.c_int, [_vp, _vp, C.c_uint64, _sz, _sz, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "amh_score": (C.c_int, [_vp, _vp, C.c_uint64, _sz, _sz, _vp, C.c_uint32, _vp]),
     "amh_near_fold": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp, C.c_uint32, C.POINTER(_vp), C.POINTER(_vp), _u64p, _vp, _vp]),
     "amh_substitute_fold": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, C.POINTER(_vp), _vp]),
     "amh_substitute_fold_words": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, _vp, C.POINTER(_vp), _vp]),
+    "amh_substitute_fold_cased": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), _vp]),
     "amh_substitute": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, C.POINTER(_vp), _vp]),
     "amh_substitute_templates_fold": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_uint64, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), _vp]),
     "amh_substitute_templates": (C.c_int, [_vp, C.c_int, C.POINTER(Slice), _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, C.POINTER(_vp), _vp]),
@@ -519,6 +526,19 @@ class Automaton:
         _hcheck(libhost().amh_build_ex(blob, offs.ctypes.data, len(needles), vptr, la.from_ptr, la.to_ptr, la.n, C.byref(h)))
         self._h = h
 
+    def _span_table(self, whole_words=False, n_needles=None):
+        """The span table the methods below scan with: the needles' lengths and the word class where one is asked for.  The one place where they make a table:
+        am.Cased's automaton overrides it to add its spellings."""
+        return SpanTable(self, n_needles=n_needles, word_bytes=whole_words)
+
+    def _needs_span_table(self, whole_words):
+        """Whether a call has to go through a span table (a predicate decides its rows) or may take the route over the values alone."""
+        return bool(whole_words)
+
+    def _group_names(self):
+        """The names by which near's groups refer to the needles."""
+        return self.needles
+
     @property
     def lower_hash(self):
         return int(libam().am_automaton_lower_hash(self.device))
@@ -661,9 +681,9 @@ class Automaton:
         up to SCORE_MAX_COLUMNS of them.  am_score: scanned and summed in HBM, the scores come back.  whole_words: True (the default word class) or a class as
         SpanTable takes it -- only the whole-word occurrences add (include/am.h "whole words")."""
         n = len(self.needles) if n_values is None else int(n_values)
-        if not whole_words:
+        if not self._needs_span_table(whole_words):
             return Weights(ValuesTable(self, n), weights).score_texts(case, texts).scores
-        t = SpanTable(self, n_needles=n, word_bytes=whole_words)
+        t = self._span_table(whole_words, n)
         w = Weights(t.values, weights)
         s = _Slices(texts)
         b = _vp()
@@ -691,7 +711,8 @@ class Automaton:
         for g, name in enumerate(names):
             for n in groups[name]:
                 member[_as_bytes(n)] = member.get(_as_bytes(n), 0) | (1 << g)
-        known = set(_as_bytes(n) for n in self.needles)
+        needle_names = self._group_names()
+        known = set(_as_bytes(n) for n in needle_names)
         for n in member:
             if n not in known:
                 raise AmError(AM_ERR_INVALID, "near: %r is in a group and not among the needles" % (n,))
@@ -701,8 +722,8 @@ class Automaton:
             if q.a not in groups or q.b not in groups:
                 raise AmError(AM_ERR_INVALID, "near: a query names a group that is not given")
             qs.append(NearQuery(names.index(q.a), names.index(q.b), q.max_gap, q.ordered))
-        t = SpanTable(self, word_bytes=whole_words)
-        hits, (so, sp) = Near(t, [member.get(_as_bytes(n), 0) for n in self.needles], qs).near_texts(case, texts, spans=True)
+        t = self._span_table(whole_words)
+        hits, (so, sp) = Near(t, [member.get(_as_bytes(n), 0) for n in needle_names], qs).near_texts(case, texts, spans=True)
         po, pairs = hits.offsets, hits.pairs
         out = []
         for i in range(len(texts)):
@@ -717,7 +738,7 @@ class Automaton:
         """Where each needle occurs (include/am.h "postings"): a Postings -- the spans of spans(case, texts, leftmost_longest, whole_words) ordered by needle, row v =
         the occurrences of needle v in (text, start) order, with the row of the spans each came from and the document frequencies.  am_postings: scanned, expanded,
         selected and sorted in HBM."""
-        return SpanTable(self, word_bytes=whole_words).postings_texts(case, texts, SPANS_LEFTMOST_LONGEST if leftmost_longest else SPANS_ALL)
+        return self._span_table(whole_words).postings_texts(case, texts, SPANS_LEFTMOST_LONGEST if leftmost_longest else SPANS_ALL)
 
     def doc_freq(self, case, texts, whole_words=False):
         """In how many of the texts each needle occurs: np.uint64[len(needles)], the IDF half of TF-IDF (a Weights for score is made from it).  Over every
@@ -737,7 +758,7 @@ class Automaton:
             if _as_bytes(needle) not in known:
                 raise AmError(AM_ERR_INVALID, "concordance: %r is not among the needles" % (needle,))
             v = known.index(_as_bytes(needle))
-        t = SpanTable(self, word_bytes=whole_words)
+        t = self._span_table(whole_words)
         with _Uploaded(texts) as b, t.postings_batch(case, b, SPANS_LEFTMOST_LONGEST if leftmost_longest else SPANS_ALL) as p:
             row = p.spans_of(v, raw=True)
             try:
@@ -763,15 +784,15 @@ class Automaton:
         and len in that unit, converted in HBM (include/am.h "coordinates"): Automaton(["nike"]).spans(IGNORE_CASE, ["é NIKE"], unit=CODE_POINTS) has start 2, len 4."""
         mode = SPANS_LEFTMOST_LONGEST if leftmost_longest else SPANS_ALL
         if unit == BYTES:
-            return SpanTable(self, word_bytes=whole_words).spans_texts(case, texts, mode)
+            return self._span_table(whole_words).spans_texts(case, texts, mode)
         with _Uploaded(texts) as b:
-            return SpanTable(self, word_bytes=whole_words).spans_batch(case, b, mode, unit=unit)
+            return self._span_table(whole_words).spans_batch(case, b, mode, unit=unit)
 
     def locate(self, case, texts, unit=CODE_POINTS, leftmost_longest=True, whole_words=False):
         """Where every match lies in its document, file:line:col: (offsets np.uint64[len(texts) + 1], spans SPAN_DTYPE in `unit`, ranges SPAN_RANGE_DTYPE) -- row k of
         ranges is the 0-based line and the column, in `unit`, of the start and of the end of span k (include/am.h "coordinates").  With unit=UTF16 a row is a
         Language-Server range.  Scanned, selected and converted in HBM."""
-        t = SpanTable(self, word_bytes=whole_words)
+        t = self._span_table(whole_words)
         with _Uploaded(texts) as b:
             raw = t.spans_batch(case, b, SPANS_LEFTMOST_LONGEST if leftmost_longest else SPANS_ALL, raw=True)
             try:
@@ -799,7 +820,7 @@ class Automaton:
         am_substitute: scanned, selected and spliced in HBM.  whole_words: as in spans -- the leftmost-longest WHOLE-WORD matches.  A replacement is bytes / str, or a
         TEMPLATE: a list or tuple of bytes / str / am.MATCH, where am.MATCH stands for the matched text as it is spelled in the haystack (include/am.h "substitute
         templates"): ["<b>", am.MATCH, "</b>"]."""
-        return SubstTable(SpanTable(self, word_bytes=whole_words), replacements).substitute_texts(case, texts)
+        return SubstTable(self._span_table(whole_words), replacements).substitute_texts(case, texts)
 
     def highlight(self, case, texts, before, after, whole_words=False):
         """Every leftmost-longest match wrapped: the template [before, am.MATCH, after] for every needle.  Under IGNORE_CASE the text keeps its own spelling:
@@ -829,9 +850,9 @@ class Automaton:
         """The texts that contain a needle -- `grep -F -f needles`; invert: `grep -v`; whole_words (True or a class as SpanTable takes it): `grep -w` -- as
         (indices np.uint32, [bytes]): the kept texts' indices, ascending, and the kept texts.  Decided and compacted in HBM (include/am.h "select")."""
         s = _Slices(texts)
-        if not whole_words:
+        if not self._needs_span_table(whole_words):
             return _grep_texts(texts, _select(lambda out: libam().am_select_any(self.device, case, int(bool(invert)), s.arr, s.n, out)))
-        t = SpanTable(self, word_bytes=whole_words)
+        t = self._span_table(whole_words)
         b = _vp()
         check(libam().am_batch_upload(s.arr, s.n, C.byref(b)))
         try:
@@ -844,7 +865,7 @@ class Automaton:
         text -- a snippet per match (`grep -o` with context), or -- merged -- the union of overlapping and touching windows per text, as `grep -C` prints them
         (leftmost-longest matches only).  am_extract: scanned, selected, windowed and gathered in HBM.  whole_words: as in spans."""
         s = _Slices(texts)
-        t = SpanTable(self, word_bytes=whole_words)
+        t = self._span_table(whole_words)
         nb, fr = _vp(), _vp()
         check(libam().am_extract(t.handle, case, SPANS_LEFTMOST_LONGEST if leftmost_longest else SPANS_ALL, int(before), int(after),
                                  EXTRACT_MERGED if merged else EXTRACT_EACH, s.arr, s.n, C.byref(nb), C.byref(fr)))
@@ -946,9 +967,26 @@ def _word_flags(word_bytes):
     return flags
 
 
-def substitute_fold_host(case, triples, texts, len_bytes, len_code_points, replacements, word_bytes=None):
+def _pack_exact(exact, n):
+    """(exact_off np.uint64[n + 1], pool bytes or None) of am_span_table_create_cased for value handles 0 .. n - 1, or (None, None) where no handle has a spelling.
+    exact: None, or one entry per handle -- None (no spelling), bytes or str.  An empty spelling cannot be told from none by the C ABI and is refused here."""
+    if exact is None:
+        return None, None
+    exact = list(exact)
+    if len(exact) != n:
+        raise AmError(AM_ERR_INVALID, "exact: one entry per value handle (%d given, %d handles)" % (len(exact), n))
+    bs = [None if x is None else _as_bytes(x) for x in exact]
+    if any(x is not None and len(x) == 0 for x in bs):
+        raise AmError(AM_ERR_INVALID, "exact: an empty spelling (None means: no spelling)")
+    if all(x is None for x in bs):
+        return None, None
+    pool, offs = pack_texts([x or b"" for x in bs])
+    return offs, pool
+
+
+def substitute_fold_host(case, triples, texts, len_bytes, len_code_points, replacements, word_bytes=None, exact=None):
     """amh_substitute_fold: the sequential definition of am_substitute over fold steps the caller brings (as spans_fold_host).  Runs without a device.  word_bytes: a
-    word class as SpanTable takes it (amh_substitute_fold_words)."""
+    word class as SpanTable takes it (amh_substitute_fold_words).  exact: spellings as SpanTable takes them (amh_substitute_fold_cased)."""
     hay = np.ascontiguousarray(triples[0], dtype=np.uint32)
     pos = np.ascontiguousarray(triples[1], dtype=np.uint64)
     val = np.ascontiguousarray(triples[2], dtype=np.uint32)
@@ -961,6 +999,12 @@ def substitute_fold_host(case, triples, texts, len_bytes, len_code_points, repla
     s = _Slices(texts)
     blob, out_offs = _vp(), np.zeros(s.n + 1, np.uint64)
     flags = _word_flags(word_bytes)
+    eoff, epool = _pack_exact(exact, nv)
+    if eoff is not None:
+        _hcheck(libhost().amh_substitute_fold_cased(case, hay.ctypes.data, pos.ctypes.data, val.ctypes.data, n, s.arr, s.n, lb.ctypes.data, lc.ctypes.data, nv, pool,
+                                                    offs.ctypes.data, None if flags is None else flags.ctypes.data, eoff.ctypes.data, epool, C.byref(blob),
+                                                    out_offs.ctypes.data))
+        return _take_texts(blob, out_offs)
     _hcheck(libhost().amh_substitute_fold_words(case, hay.ctypes.data, pos.ctypes.data, val.ctypes.data, n, s.arr, s.n, lb.ctypes.data, lc.ctypes.data, nv, pool,
                                                 offs.ctypes.data, None if flags is None else flags.ctypes.data, C.byref(blob), out_offs.ctypes.data))
     return _take_texts(blob, out_offs)
@@ -1025,9 +1069,10 @@ def _take_spans(po, pe, n_hay, k):
     return offs, spans
 
 
-def spans_fold_host(case, mode, triples, texts, len_bytes, len_code_points, word_bytes=None):
+def spans_fold_host(case, mode, triples, texts, len_bytes, len_code_points, word_bytes=None, exact=None):
     """amh_spans_fold: the sequential definition of am_spans over fold steps the caller brings -- (haystack, matchPos, value) arrays in fold order -- the texts and the
-    two length arrays.  Runs without a device.  word_bytes: a word class as SpanTable takes it (amh_spans_fold_words)."""
+    two length arrays.  Runs without a device.  word_bytes: a word class as SpanTable takes it (amh_spans_fold_words).  exact: spellings as SpanTable takes them
+    (amh_spans_fold_cased, include/am.h "exact case")."""
     hay = np.ascontiguousarray(triples[0], dtype=np.uint32)
     pos = np.ascontiguousarray(triples[1], dtype=np.uint64)
     val = np.ascontiguousarray(triples[2], dtype=np.uint32)
@@ -1039,6 +1084,11 @@ def spans_fold_host(case, mode, triples, texts, len_bytes, len_code_points, word
     s = _Slices(texts)
     po, pe, ne = _vp(), _vp(), C.c_uint64(0)
     flags = _word_flags(word_bytes)
+    eoff, epool = _pack_exact(exact, nv)
+    if eoff is not None:
+        _hcheck(libhost().amh_spans_fold_cased(case, mode, hay.ctypes.data, pos.ctypes.data, val.ctypes.data, n, s.arr, s.n, lb.ctypes.data, lc.ctypes.data, nv,
+                                               None if flags is None else flags.ctypes.data, eoff.ctypes.data, epool, C.byref(po), C.byref(pe), C.byref(ne)))
+        return _take_spans(po, pe, s.n, int(ne.value))
     _hcheck(libhost().amh_spans_fold_words(case, mode, hay.ctypes.data, pos.ctypes.data, val.ctypes.data, n, s.arr, s.n, lb.ctypes.data, lc.ctypes.data, nv,
                                            None if flags is None else flags.ctypes.data, C.byref(po), C.byref(pe), C.byref(ne)))
     return _take_spans(po, pe, s.n, int(ne.value))
@@ -1147,17 +1197,24 @@ class SpanTable:
     """The needles' lengths beside machineValues on the device (am_span_table): what am_spans* turns a fold step into a span with.  Lengths come from
     automaton.needles, handle = needle index; n_needles below len(needles) skips the handles from n_needles on.  lengths: (len_bytes, len_code_points) per value handle
     for an automaton built with handles of its own.  word_bytes: None -- no word class, every span is a row; True -- the default class; bytes or an iterable of byte
-    values -- the class of those values (am_span_table_create_words): every consumer of the table then sees the whole-word spans only."""
+    values -- the class of those values (am_span_table_create_words): every consumer of the table then sees the whole-word spans only.  exact: None, or one entry
+    per handle -- None, bytes or str: the spelling a span of that handle must have in the text to be a row (am_span_table_create_cased, include/am.h "exact case");
+    all None is the plain or the words table, made through the old entry points."""
 
-    def __init__(self, automaton, n_needles=None, lengths=None, word_bytes=None):
+    def __init__(self, automaton, n_needles=None, lengths=None, word_bytes=None, exact=None):
         if n_needles is None and lengths is not None:
             n_needles = len(lengths[0])
         self._values = ValuesTable(automaton, n_needles)      # (the am_needle_ids must outlive the table)
         self.n_needles = self._values.n_needles
         self._lb, self._lc = _handle_lengths(automaton.needles, self.n_needles, lengths)
         self._words = _word_flags(word_bytes)
+        self._exact_off, self._exact_pool = _pack_exact(exact, self.n_needles)
         h = _vp()
-        if self._words is None:
+        if self._exact_off is not None:
+            check(libam().am_span_table_create_cased(self._values.handle, self._lb.ctypes.data, self._lc.ctypes.data, 0 if self._words is None else SPAN_TABLE_WORDS,
+                                                     None if self._words is None else self._words.ctypes.data, self._exact_off.ctypes.data, self._exact_pool,
+                                                     C.byref(h)))
+        elif self._words is None:
             check(libam().am_span_table_create(self._values.handle, self._lb.ctypes.data, self._lc.ctypes.data, C.byref(h)))
         else:
             check(libam().am_span_table_create_words(self._values.handle, self._lb.ctypes.data, self._lc.ctypes.data, self._words.ctypes.data, C.byref(h)))
@@ -1177,6 +1234,15 @@ class SpanTable:
         """am_span_table_word_bytes: the table's class as 256 flags (bytes of 0 / 1), None for a table without one."""
         out = (C.c_uint8 * 256)()
         return bytes(out) if libam().am_span_table_word_bytes(self._h, out) else None
+
+    @property
+    def exact(self):
+        """am_span_table_exact per handle: the table's spellings as a list of bytes / None."""
+        out = []
+        for v in range(self.n_needles):
+            p, n = _vp(), C.c_uint64(0)
+            out.append(C.string_at(p.value, int(n.value)) if libam().am_span_table_exact(self._h, v, C.byref(p), C.byref(n)) else None)
+        return out
 
     def _spans(self, call, raw):
         return _csr_call(call, spans_to_numpy, libam().am_spans_free, raw)
@@ -2089,6 +2155,100 @@ class SubstTable:
     def splice(self, batch, spans_raw, raw=False):
         """am_batch_substitute: the splice alone over an am_spans* the caller holds (SpanTable.spans_batch(..., SPANS_LEFTMOST_LONGEST, raw=True) on `batch`)."""
         return self._texts(lambda out: libam().am_batch_substitute(batch, spans_raw, self._h, out), raw)
+
+
+def _lower_needle(needle, lower_pairs):
+    """The needle as the automaton of a Cased holds it: lower_utf8 under the built-in table; under the caller's pairs ASCII lower-casing and those pairs, a code point
+    at a time (what am_automaton_create_ex lowers the haystack with)."""
+    if lower_pairs is None:
+        return lower_utf8(needle)
+    table = {int(a): int(b) for a, b in lower_pairs}
+    text = _as_bytes(needle).decode("utf-8")
+    return "".join(chr(table.get(ord(c), ord(c) + 32 if "A" <= c <= "Z" else ord(c))) for c in text).encode("utf-8")
+
+
+class _CasedAutomaton(Automaton):
+    """The automaton of a Cased: lower-cased needles, and every span table its methods make carries the spellings (include/am.h "exact case")."""
+
+    def __init__(self, lowered, given, exact, lower_pairs):
+        super().__init__(lowered, lower_pairs=lower_pairs)
+        self._given, self._spellings = given, exact
+
+    def _span_table(self, whole_words=False, n_needles=None):
+        exact = self._spellings if self._spellings is None or n_needles is None else self._spellings[:n_needles]
+        return SpanTable(self, n_needles=n_needles, word_bytes=whole_words, exact=exact)
+
+    def _needs_span_table(self, whole_words):
+        return bool(whole_words) or self._spellings is not None
+
+    def _group_names(self):
+        return self._given                                   # (the groups of near name the needles as given)
+
+
+class Cased:
+    """A dictionary whose needles are case-insensitive or exact, needle by needle, in ONE scan (include/am.h "exact case").  needles: as given, in the spelling
+    that counts for the exact ones.  exact: a mask with one boolean per needle, or a set (any container) of the needles that are exact.  The automaton holds the
+    lower-cased needles, every call scans under IGNORE_CASE, and the span table carries exact[v] = needle v as given for the flagged needles: a span of such a needle
+    is a row only where the text spells it that way -- filtered before the leftmost-longest selection, so every stage that reads spans sees the kept rows only.
+      am.Cased(["US", "Apple", "nike"], exact=[1, 1, 0]).highlight(["us, US and NIKE's apple"], "<b>", "</b>") == [b"us, <b>US</b> and <b>NIKE</b>'s apple"]
+    RuleSet, count_matrix, contains_any / contains_all and Replacer do not go through a span table and stay single-mode."""
+
+    def __init__(self, needles, exact, lower_pairs=None):
+        given = [_as_bytes(n) for n in needles]
+        exact = list(exact) if isinstance(exact, (list, tuple, np.ndarray)) else exact
+        if isinstance(exact, list) and len(exact) == len(given) and all(isinstance(x, (bool, int, np.integer, np.bool_)) for x in exact):
+            mask = [bool(x) for x in exact]
+        else:
+            if isinstance(exact, list) and any(isinstance(x, (bool, int, np.integer, np.bool_)) for x in exact):
+                raise AmError(AM_ERR_INVALID, "Cased: an exact mask has one boolean per needle (%d given, %d needles)" % (len(exact), len(given)))
+            chosen = set(_as_bytes(x) for x in exact)
+            unknown = chosen - set(given)
+            if unknown:
+                raise AmError(AM_ERR_INVALID, "Cased: %r is exact and not among the needles" % (sorted(unknown)[0],))
+            mask = [n in chosen for n in given]
+        if any(m and not n for m, n in zip(mask, given)):
+            raise AmError(AM_ERR_INVALID, "Cased: the empty needle cannot be exact")
+        self.needles = given
+        self.exact = [n if m else None for n, m in zip(given, mask)]
+        self.automaton = _CasedAutomaton([_lower_needle(n, lower_pairs) for n in given], given, self.exact if any(mask) else None, lower_pairs)
+
+    def table(self, whole_words=False):
+        """The SpanTable of this dictionary (with a word class where asked for): what the *_batch calls of the device stages take."""
+        return self.automaton._span_table(whole_words)
+
+    def spans(self, texts, leftmost_longest=False, whole_words=False, unit=BYTES):
+        return self.automaton.spans(IGNORE_CASE, texts, leftmost_longest=leftmost_longest, whole_words=whole_words, unit=unit)
+
+    def substitute(self, texts, replacements, whole_words=False):
+        return self.automaton.substitute(IGNORE_CASE, texts, replacements, whole_words=whole_words)
+
+    def highlight(self, texts, before, after, whole_words=False):
+        return self.automaton.highlight(IGNORE_CASE, texts, before, after, whole_words=whole_words)
+
+    def grep(self, texts, invert=False, whole_words=False):
+        return self.automaton.grep(IGNORE_CASE, texts, invert=invert, whole_words=whole_words)
+
+    def extract(self, texts, before=0, after=0, merged=False, leftmost_longest=True, whole_words=False):
+        return self.automaton.extract(IGNORE_CASE, texts, before=before, after=after, merged=merged, leftmost_longest=leftmost_longest, whole_words=whole_words)
+
+    def count_by_needle(self, texts, whole_words=False):
+        """How often every needle occurs, spelled as it must be: np.uint64[len(needles)], the bincount of the spans(texts) rows."""
+        if not self.needles:
+            return np.zeros(0, np.uint64)
+        return self.table(whole_words).count_by_needle_texts(IGNORE_CASE, texts)
+
+    def score(self, texts, weights, whole_words=False):
+        return self.automaton.score(IGNORE_CASE, texts, weights, whole_words=whole_words)
+
+    def postings(self, texts, leftmost_longest=False, whole_words=False):
+        return self.automaton.postings(IGNORE_CASE, texts, leftmost_longest=leftmost_longest, whole_words=whole_words)
+
+    def doc_freq(self, texts, whole_words=False):
+        return self.automaton.doc_freq(IGNORE_CASE, texts, whole_words=whole_words)
+
+    def near(self, texts, groups, queries, whole_words=False):
+        """Automaton.near over the kept rows; groups name the needles as given."""
+        return self.automaton.near(IGNORE_CASE, texts, groups, queries, whole_words=whole_words)
 
 
 class ImageAutomaton:

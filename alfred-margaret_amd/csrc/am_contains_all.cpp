@@ -350,7 +350,7 @@ extern "C" int am_count_by_needle_batch(const am_needle_ids* ids, int case_mode,
 extern "C" int am_count_spans_by_needle_batch(const am_span_table* t, int case_mode, const am_batch* cb, uint64_t* counts_out)
 {
     if (!t || !cb) return fail(AM_ERR_INVALID, "null span table or batch");
-    if (!t->has_words) return am_count_by_needle_batch(t->ids, case_mode, cb, counts_out);      // no class: every span is a row, the rows are the values
+    if (!t->has_predicate()) return am_count_by_needle_batch(t->ids, case_mode, cb, counts_out);      // no class, no spelling: every span is a row, the rows are the values
     return count_batch(t->ids, "span table", case_mode, cb, counts_out, [&](am_batch* b, uint64_t* d_counts, uint64_t* d_trace) { return hist_words_batch(t, case_mode, b, d_counts, d_trace); });
 }
 
@@ -362,7 +362,7 @@ extern "C" int am_count_spans_by_needle(const am_span_table* t, int case_mode, c
     if (!t) return fail(AM_ERR_INVALID, "null span table");      // (last of the checks a caller without a device can see; n_needles is the table's)
     const am_needle_ids* ids = t->ids;
     if (ids->n_needles && !counts_out) return fail(AM_ERR_INVALID, "counts_out is null");
-    if (!t->has_words) return am_count_by_needle(ids, case_mode, hay, n_hay, counts_out);
+    if (!t->has_predicate()) return am_count_by_needle(ids, case_mode, hay, n_hay, counts_out);
     if (ids->n_needles == 0) return AM_OK;
     AM_TRY(ensure_runtime());
     if (total == 0) { std::memset(counts_out, 0, (size_t)ids->n_needles * 8); return AM_OK; }

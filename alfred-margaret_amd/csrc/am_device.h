@@ -194,10 +194,12 @@ hipError_t launch_split_gather(const uint8_t* src, uint64_t src_total, const uin
 // match spans (am_spans.hip): every fold step `Match pos v` with v < n_needles as (start, len, haystack, needle), all of them or the leftmost-longest selection
 struct Span { uint64_t start, len; uint32_t haystack, needle; };      // = am_span in include/am.h
 constexpr uint32_t kWordClassWords = 8;                     // a word class: 256 flags, bit b & 31 of word b >> 5
-struct SpansIn : RecordsIn {                                // the sorted records of the batch and machineValues, and what only spans need:
+struct ExactRef { uint32_t at16, len; };                    // the spelling of a handle: `len` bytes at 16 * at16 of the pool (am_cased.h); len == 0: none
+struct SpansIn : RecordsIn {                             // the sorted records of the batch and machineValues, and what only spans need:
     const uint32_t* len_bytes; const uint32_t* len_cps;     // the needles' own lengths (am_span_table)
     const uint8_t* text; const uint64_t* offsets; uint64_t total;
     const uint32_t* words;                                  // the table's word class: 256 flags in 8 dwords (am_words.h); null: no class, every span is kept
+    const ExactRef* exact; const uint8_t* exact_pool;       // the table's spellings (include/am.h "exact case"): one ExactRef per handle and the pool; null: no spelling
 };
 constexpr uint64_t kSpansMaxTile = 2048;                    // candidates per workgroup of the prefix maximum
 constexpr uint32_t kSpThreads = 256;                        // lanes per workgroup of the prefix maximum; k_spans_tiles_max takes the tile maxima in sweeps of as many

@@ -48,10 +48,10 @@ static_assert((uint64_t)kHistTile * kHistLdsPerRecord * kHistTilesPerFlush < (1u
 // ids are handles in the caller's order (alphabetical, by frequency, ...): a multiplicative hash spreads neighbours over the table
 __device__ __forceinline__ uint32_t hist_slot(uint32_t id) { return (id * 0x9E3779B1u) >> (32 - kHistSlotBits); }
 
-// The walk over the tiles with the workgroup's LDS table (tag / cnt: kHistSlots words each, declared by the kernel).  WORDS (View = SpansIn, otherwise RecordsIn): a
-// value is added only where the span it gives with its record is a whole word -- span_of (am_words.h), the function the span expansion decides its rows with --
-// against the class in `words` (LDS).
-template <bool kTrace, bool WORDS, bool IC, class View>
+// The walk over the tiles with the workgroup's LDS table (tag / cnt: kHistSlots words each, declared by the kernel).  WORDS / EXACT (View = SpansIn, otherwise
+// RecordsIn): a value is added only where the table keeps the span it gives with its record -- span_of (am_words.h), the function the span expansion decides its rows
+// with -- against the class in `words` (LDS) and the table's spellings.
+template <bool kTrace, bool WORDS, bool IC, class View, bool EXACT = false>
 __device__ __forceinline__ void hist_body(const View& in, uint32_t* tag, uint32_t* cnt, const uint32_t* words, unsigned long long* __restrict__ counts,
                                           unsigned long long* __restrict__ trace, uint32_t tiles_per_flush)
 {
@@ -85,9 +85,9 @@ __device__ __forceinline__ void hist_body(const View& in, uint32_t* tag, uint32_
             for (uint64_t j = 0; k[u] + j < ke[u]; j++) {
                 const uint32_t id = vals[k[u] + j];
                 if (id >= n_needles) continue;                               // a handle beyond the table: skipped, as containsAll skips it (k_idset)
-                if constexpr (WORDS) {
+                if constexpr (WORDS || EXACT) {
                     uint64_t ss, sn;
-                    if (!span_of<IC, true>(in, rec[u], id, words, ss, sn)) continue;      // no whole word: no row of the span table, no count
+                    if (!span_of<IC, WORDS, EXACT>(in, rec[u], id, words, ss, sn)) continue;      // not kept: no row of the span table, no count
                 }
                 uint32_t s = 0;
                 bool hit = false;
@@ -130,15 +130,15 @@ __global__ void __launch_bounds__(kHistThreads) k_needle_hist(RecordsIn in, unsi
 
 // the whole-word form: the workgroup stages the table's 32-byte class in LDS beside its tables; the LDS-counter wrap argument is the plain kernel's (a record adds
 // at most as often as there)
-template <bool kTrace, bool IC>
+template <bool kTrace, bool IC, bool WORDS = true, bool EXACT = false>
 __global__ void __launch_bounds__(kHistThreads) k_needle_hist_words(SpansIn in, unsigned long long* __restrict__ counts, unsigned long long* __restrict__ trace,
                                                                     uint32_t tiles_per_flush)
 {
     __shared__ uint32_t tag[kHistSlots];
     __shared__ uint32_t cnt[kHistSlots];
     __shared__ uint32_t words[kWordClassWords];
-    if (threadIdx.x < kWordClassWords) words[threadIdx.x] = in.words[threadIdx.x];      // (hist_body's first barrier comes before any read)
-    hist_body<kTrace, true, IC>(in, tag, cnt, words, counts, trace, tiles_per_flush);
+    if (WORDS && threadIdx.x < kWordClassWords) words[threadIdx.x] = in.words[threadIdx.x];      // (hist_body's first barrier comes before any read)
+    hist_body<kTrace, WORDS, IC, SpansIn, EXACT>(in, tag, cnt, words, counts, trace, tiles_per_flush);
 }
 
 // what both launchers decide the same way: the persistent grid, and the flush interval (never more than the bound the wrap argument rests on)
@@ -162,8 +162,16 @@ hipError_t launch_needle_hist(const RecordsIn& in, uint64_t* counts, uint64_t* t
 hipError_t launch_needle_hist_words(bool ic, const SpansIn& in, uint64_t* counts, uint64_t* trace, uint32_t flush_tiles, int n_cu, hipStream_t st)
 {
     if (in.n_rec == 0 || in.n_needles == 0) return hipSuccess;
-    if (!in.words) return hipErrorInvalidValue;
-    const auto kernel = trace ? (ic ? k_needle_hist_words<true, true> : k_needle_hist_words<true, false>) : (ic ? k_needle_hist_words<false, true> : k_needle_hist_words<false, false>);
+    if (!in.words && !in.exact) return hipErrorInvalidValue;
+    if (!in.exact) {
+        const auto kernel = trace ? (ic ? k_needle_hist_words<true, true> : k_needle_hist_words<true, false>) : (ic ? k_needle_hist_words<false, true> : k_needle_hist_words<false, false>);
+        return hist_run(kernel, in, counts, trace, flush_tiles, n_cu, st);
+    }
+    // spellings (include/am.h "exact case"), with a class or without one
+    const auto kernel = in.words ? (trace ? (ic ? k_needle_hist_words<true, true, true, true> : k_needle_hist_words<true, false, true, true>)
+                                          : (ic ? k_needle_hist_words<false, true, true, true> : k_needle_hist_words<false, false, true, true>))
+                                 : (trace ? (ic ? k_needle_hist_words<true, true, false, true> : k_needle_hist_words<true, false, false, true>)
+                                          : (ic ? k_needle_hist_words<false, true, false, true> : k_needle_hist_words<false, false, false, true>));
     return hist_run(kernel, in, counts, trace, flush_tiles, n_cu, st);
 }
 

@@ -19,7 +19,7 @@ constexpr int kWave = 64;
 
 // ---- a select's predicate over the records: one lane per record, the first of its values whose span the table keeps (span_of, am_words.h) flags the record's
 // haystack, the remaining values are skipped (several lanes may store the same 1 into the same byte)
-template <bool IC, bool WORDS>
+template <bool IC, bool WORDS, bool EXACT>
 __global__ void __launch_bounds__(kRowThreads) k_hay_flags_spans(SpansIn in, uint8_t* __restrict__ flags)
 {
     const uint64_t i = global_row();
@@ -33,7 +33,7 @@ __global__ void __launch_bounds__(kRowThreads) k_hay_flags_spans(SpansIn in, uin
         const uint32_t v = in.vals[k];
         if (v >= in.n_needles) continue;                               // the am_needle_ids convention: skipped
         uint64_t s, n;
-        if (!span_of<IC, WORDS>(in, r, v, in.words, s, n)) continue;
+        if (!span_of<IC, WORDS, EXACT>(in, r, v, in.words, s, n)) continue;
         flags[r.haystack] = 1;
         return;
     }
@@ -141,7 +141,10 @@ hipError_t launch_fold_hash(const RecordsIn& in, const uint64_t* rec_first, uint
 
 hipError_t launch_hay_flags_spans(bool ic, const SpansIn& in, uint8_t* flags, hipStream_t st)
 {
-    const auto kernel = !in.words ? k_hay_flags_spans<false, false> : ic ? k_hay_flags_spans<true, true> : k_hay_flags_spans<false, true>;      // (no class: no start is needed, so no case mode)
+    // (no predicate: no start is needed, so no case mode)
+    const auto kernel = in.exact ? (in.words ? (ic ? k_hay_flags_spans<true, true, true> : k_hay_flags_spans<false, true, true>)
+                                             : (ic ? k_hay_flags_spans<true, false, true> : k_hay_flags_spans<false, false, true>))
+                                 : !in.words ? k_hay_flags_spans<false, false, false> : ic ? k_hay_flags_spans<true, true, false> : k_hay_flags_spans<false, true, false>;
     return launch_rows(kernel, in.n_rec, st, in, flags);
 }
 

@@ -114,7 +114,7 @@ extern "C" int am_score_spans_batch(const am_span_table* t, const am_weights* w,
     if (!t || !w || !cb) return fail(AM_ERR_INVALID, "null span table, weights or batch");
     if (t->ids != w->ids) return fail(AM_ERR_INVALID, "the span table and the weights were not made over the same needle ids");
     if (w->dev != cb->dev) return fail(AM_ERR_INVALID, "weights and batch live on different devices");
-    return score_batch(w, t->has_words ? t : nullptr, case_mode, cb, out);      // no class: every span is a row, the rows are the values
+    return score_batch(w, t->has_predicate() ? t : nullptr, case_mode, cb, out);      // no class, no spelling: every span is a row, the rows are the values
 }
 
 extern "C" int am_score(const am_weights* w, int case_mode, const am_slice* hay, size_t n_hay, am_scores** out)

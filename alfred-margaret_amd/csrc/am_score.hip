@@ -13,7 +13,8 @@
 // So there is no atomic per value or per record: at most one add per column for each run of equal haystacks a wavefront holds.  A 1-MiB document costs a handful of
 // adds per wavefront; a corpus of lines costs about one add per line and column, to addresses that are spread out.  Integer adds commute and wrap modulo 2^64: the
 // scores are bit-identical from run to run and across groups and segments.  A sum of zero is not sent (the scores start at zero).
-// k_score<WORDS = true> adds a value only where span_of (am_words.h) keeps the span it gives with its record: the rows am_count_spans_by_needle* counts.
+// k_score<WORDS = true> adds a value only where span_of (am_words.h) keeps the span it gives with its record: the rows am_count_spans_by_needle* counts.  EXACT: the
+// same with the table's spellings (include/am.h "exact case").
 //
 // Top-k of a column: score_key / topk_pick (am_score.h) in eight passes of an 8-bit radix select -- k_topk_hist counts the next digit of the keys that share the
 // digits chosen so far in LDS bins and adds the bins to 256 words of HBM, k_topk_pick (one wavefront) chooses the digit and clears the words -- leave the k-th key T
@@ -56,7 +57,7 @@ __device__ __forceinline__ uint64_t lane63_u64(uint64_t x)
 }
 
 // NC: the columns the instantiation has registers for (out.n_cols <= NC; the loops over columns are unrolled and skip those beyond).  View: SpansIn or RecordsIn
-template <bool WORDS, bool IC, uint32_t NC, class View>
+template <bool WORDS, bool IC, uint32_t NC, class View, bool EXACT = false>
 __device__ __forceinline__ void score_body(const uint32_t* words, const View& in, const ScoreOut& out)
 {
     const uint32_t lane = threadIdx.x & (kWave - 1);
@@ -92,9 +93,9 @@ __device__ __forceinline__ void score_body(const uint32_t* words, const View& in
             for (uint64_t j = k[u]; j < ke[u]; j++) {
                 const uint32_t id = in.vals[j];
                 if (id >= in.n_needles) continue;                            // a handle beyond the table: skipped, as am_count_by_needle skips it
-                if constexpr (WORDS) {
+                if constexpr (WORDS || EXACT) {
                     uint64_t ss, sn;
-                    if (!span_of<IC, true>(in, rec[u], id, words, ss, sn)) continue;      // no whole word: no row of the span table, nothing added
+                    if (!span_of<IC, WORDS, EXACT>(in, rec[u], id, words, ss, sn)) continue;      // not kept: no row of the span table, nothing added
                 }
 #pragma unroll
                 for (uint32_t c = 0; c < NC; c++)
@@ -153,20 +154,25 @@ __global__ void __launch_bounds__(kScoreThreads) k_score(RecordsIn in, ScoreOut 
 }
 
 // the whole-word form: the workgroup stages the table's 32-byte class in LDS
-template <bool IC, uint32_t NC>
+template <bool IC, uint32_t NC, bool WORDS = true, bool EXACT = false>
 __global__ void __launch_bounds__(kScoreThreads) k_score_words(SpansIn in, ScoreOut out)
 {
     __shared__ uint32_t words[kWordClassWords];
-    if (threadIdx.x < kWordClassWords) words[threadIdx.x] = in.words[threadIdx.x];
+    if (WORDS && threadIdx.x < kWordClassWords) words[threadIdx.x] = in.words[threadIdx.x];
     __syncthreads();
-    score_body<true, IC, NC>(words, in, out);
+    score_body<WORDS, IC, NC, SpansIn, EXACT>(words, in, out);
 }
 
 template <uint32_t NC>
 void score_launch(bool ic, dim3 grid, const SpansIn& in, const ScoreOut& out, hipStream_t st)
 {
     const dim3 block(kScoreThreads);
-    if (!in.words) hipLaunchKernelGGL((k_score<NC>), grid, block, 0, st, static_cast<const RecordsIn&>(in), out);
+    if (in.exact) {                                          // spellings (include/am.h "exact case"), with a class or without one
+        if (in.words) { if (ic) hipLaunchKernelGGL((k_score_words<true, NC, true, true>), grid, block, 0, st, in, out); else hipLaunchKernelGGL((k_score_words<false, NC, true, true>), grid, block, 0, st, in, out); }
+        else if (ic) hipLaunchKernelGGL((k_score_words<true, NC, false, true>), grid, block, 0, st, in, out);
+        else hipLaunchKernelGGL((k_score_words<false, NC, false, true>), grid, block, 0, st, in, out);
+    }
+    else if (!in.words) hipLaunchKernelGGL((k_score<NC>), grid, block, 0, st, static_cast<const RecordsIn&>(in), out);
     else if (ic) hipLaunchKernelGGL((k_score_words<true, NC>), grid, block, 0, st, in, out);
     else hipLaunchKernelGGL((k_score_words<false, NC>), grid, block, 0, st, in, out);
 }

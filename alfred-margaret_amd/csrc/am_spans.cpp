@@ -3,7 +3,10 @@
 // (am_spans.hip).  The result is CSR like am_fragments and stays in HBM until asked for: its handle, the chain selector's host sequence and the argument checks are
 // am_fold.h's, shared with the other folds.
 // A span table may carry a word class (am_span_table_create_words, include/am.h "whole words"): 8 dwords beside the lengths that the expansion filters with.
+// It may also carry an exact spelling per handle (am_span_table_create_cased, include/am.h "exact case"): a pool beside the lengths, compared by am_cased.h.
 #include "am_spans.h"
+
+#include "am_cased.h"
 
 #include <cstddef>
 #include <cstring>
@@ -90,8 +93,62 @@ int select_leftmost_longest(const SpansIn& in, const Span* spans, uint64_t n_spa
 
 namespace {
 
-// am_span_table_create and am_span_table_create_words: one set of checks, one set of messages; word_bytes (256 flags, not null) only where has_words
-int create_table(const am_needle_ids* ids, const uint32_t* len_bytes, const uint32_t* len_code_points, bool has_words, const uint8_t* word_bytes, am_span_table** out)
+// the spellings of am_span_table_create_cased, checked on the host before any device work: what span_of's shortcut (am_words.h) rests on
+int check_exact(const uint32_t* len_bytes, const uint32_t* len_code_points, uint32_t n, const uint64_t* exact_off, const uint8_t* exact_bytes, bool* any)
+{
+    *any = false;
+    if (exact_off[0] != 0) return fail(AM_ERR_INVALID, "am_span_table_create_cased: exact_off[0] is not 0");
+    for (uint32_t v = 0; v < n; v++)
+        if (exact_off[v + 1] < exact_off[v]) return fail(AM_ERR_INVALID, "am_span_table_create_cased: exact_off descends at needle " + std::to_string(v));
+    if (exact_off[n] != 0 && !exact_bytes) return fail(AM_ERR_INVALID, "am_span_table_create_cased: exact_bytes is null");
+    uint64_t groups = 0;
+    for (uint32_t v = 0; v < n; v++) {
+        const uint64_t e = exact_off[v + 1] - exact_off[v];
+        if (e == 0) continue;
+        const std::string who = "am_span_table_create_cased: the spelling of needle " + std::to_string(v);
+        if (e >= (1ull << 32)) return fail(AM_ERR_INVALID, who + " has 2^32 bytes or more");
+        if (len_bytes[v] == 0) return fail(AM_ERR_INVALID, who + " belongs to a needle of length 0");
+        const uint8_t* p = exact_bytes + exact_off[v];
+        if ((p[0] & 0xC0) == 0x80) return fail(AM_ERR_INVALID, who + " begins with a continuation byte");
+        uint64_t starts = 0;
+        for (uint64_t i = 0; i < e; i++) starts += (p[i] & 0xC0) != 0x80 ? 1u : 0u;
+        if (starts != len_code_points[v]) return fail(AM_ERR_INVALID, who + " has " + std::to_string(starts) + " code points, the needle has " + std::to_string(len_code_points[v]));
+        groups += cased_padded(e) / kCasedGroup;
+        *any = true;
+    }
+    if (groups >= (1ull << 32)) return fail(AM_ERR_INVALID, "am_span_table_create_cased: the spellings take 64 GiB or more");      // (ExactRef::at16 is 32 bits)
+    return AM_OK;
+}
+
+// the spellings to the table's device: the host copy as given, an ExactRef per handle and the pool, every spelling at a multiple of kCasedGroup and zero-filled to
+// the next one, kCasedPoolPad zero bytes behind the last (as the replacement pool of am_subst_table_create: a group read at any offset stays inside)
+int upload_exact(am_span_table* t, uint32_t n, const uint64_t* exact_off, const uint8_t* exact_bytes)
+{
+    t->exact_off.assign(exact_off, exact_off + n + 1);
+    if (exact_off[n]) t->exact_bytes.assign(exact_bytes, exact_bytes + exact_off[n]);
+    std::vector<ExactRef> refs((size_t)n + 1, ExactRef{0, 0});
+    uint64_t at = 0;
+    for (uint32_t v = 0; v < n; v++) {
+        const uint64_t e = exact_off[v + 1] - exact_off[v];
+        if (e == 0) continue;
+        refs[v] = ExactRef{(uint32_t)(at / kCasedGroup), (uint32_t)e};
+        at += cased_padded(e);
+    }
+    std::vector<uint8_t> pool((size_t)at + kCasedPoolPad, 0);
+    for (uint32_t v = 0; v < n; v++)
+        if (refs[v].len) std::memcpy(pool.data() + (size_t)refs[v].at16 * kCasedGroup, exact_bytes + exact_off[v], refs[v].len);
+    AM_TRY(t->exact_refs.ensure(refs.size() * sizeof(ExactRef)));
+    AM_TRY(t->exact_pool.ensure(pool.size()));
+    HIP_TRY(hipMemcpy(t->exact_refs.p, refs.data(), refs.size() * sizeof(ExactRef), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(t->exact_pool.p, pool.data(), pool.size(), hipMemcpyHostToDevice));
+    t->has_exact = true;
+    return AM_OK;
+}
+
+// am_span_table_create, am_span_table_create_words and am_span_table_create_cased: one set of checks, one set of messages; word_bytes (256 flags, not null) only
+// where has_words; exact_off (n_needles + 1 offsets into exact_bytes) nullable: no spelling
+int create_table(const am_needle_ids* ids, const uint32_t* len_bytes, const uint32_t* len_code_points, bool has_words, const uint8_t* word_bytes, am_span_table** out,
+                 const uint64_t* exact_off = nullptr, const uint8_t* exact_bytes = nullptr)
 {
     if (!out) return fail(AM_ERR_INVALID, "out is null");
     *out = nullptr;
@@ -103,6 +160,8 @@ int create_table(const am_needle_ids* ids, const uint32_t* len_bytes, const uint
         if ((len_code_points[v] == 0) != (len_bytes[v] == 0)) return fail(AM_ERR_INVALID, "am_span_table_create: exactly one length of needle " + std::to_string(v) + " is 0");
         if (len_code_points[v] >= (1u << 30)) return fail(AM_ERR_INVALID, "am_span_table_create: 2^30 code points and more (a span length must fit 32 bits)");
     }
+    bool any_exact = false;
+    if (exact_off) AM_TRY(check_exact(len_bytes, len_code_points, n, exact_off, exact_bytes, &any_exact));
     AM_TRY(ensure_runtime());
     ON_DEVICE(ids->a->dev);
     std::unique_ptr<am_span_table> t(new am_span_table());
@@ -123,11 +182,45 @@ int create_table(const am_needle_ids* ids, const uint32_t* len_bytes, const uint
         HIP_TRY(hipMemcpy(t->words.p, packed, sizeof(packed), hipMemcpyHostToDevice));
         t->has_words = true;
     }
+    if (any_exact) AM_TRY(upload_exact(t.get(), n, exact_off, exact_bytes));      // (no spelling at all: the table of today, byte for byte)
     *out = t.release();
     return AM_OK;
 }
 
 }  // namespace
+
+extern "C" int am_span_table_create_cased(const am_needle_ids* ids, const uint32_t* len_bytes, const uint32_t* len_code_points, uint32_t flags, const uint8_t* word_bytes,
+                                          const uint64_t* exact_off, const uint8_t* exact_bytes, am_span_table** out)
+{
+    if (!out) return fail(AM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    if (flags & ~AM_SPAN_TABLE_WORDS) return fail(AM_ERR_INVALID, "am_span_table_create_cased: unknown flag bits");
+    const bool has_words = (flags & AM_SPAN_TABLE_WORDS) != 0;
+    uint8_t dflt[256];
+    if (has_words && !word_bytes) am_word_bytes_default(dflt);
+    return create_table(ids, len_bytes, len_code_points, has_words, word_bytes ? word_bytes : dflt, out, exact_off, exact_bytes);
+}
+
+// the checks of the spellings alone, for a caller that wants them before a device exists (and for the tests of a machine without one)
+extern "C" int am_span_table_check_exact(const uint32_t* len_bytes, const uint32_t* len_code_points, uint32_t n_needles, const uint64_t* exact_off, const uint8_t* exact_bytes)
+{
+    if (!exact_off) return AM_OK;
+    if (n_needles && (!len_bytes || !len_code_points)) return fail(AM_ERR_INVALID, "len_bytes or len_code_points is null");
+    bool any = false;
+    return check_exact(len_bytes, len_code_points, n_needles, exact_off, exact_bytes, &any);
+}
+
+extern "C" int am_span_table_exact(const am_span_table* t, uint32_t needle, const uint8_t** bytes, uint64_t* len)
+{
+    if (bytes) *bytes = nullptr;
+    if (len) *len = 0;
+    if (!t || !t->has_exact || (uint64_t)needle + 1 >= t->exact_off.size()) return 0;
+    const uint64_t e = t->exact_off[needle + 1] - t->exact_off[needle];
+    if (e == 0) return 0;
+    if (bytes) *bytes = t->exact_bytes.data() + t->exact_off[needle];
+    if (len) *len = e;
+    return 1;
+}
 
 extern "C" int am_span_table_create(const am_needle_ids* ids, const uint32_t* len_bytes, const uint32_t* len_code_points, am_span_table** out)
 {

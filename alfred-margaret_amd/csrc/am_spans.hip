@@ -6,7 +6,8 @@
 // IgnoreCase walks len_code_points - 1 code points backwards from the last byte of the match (src/Data/Text/Utf8.hs:256-276), per value; the walk never leaves the
 // haystack (clamped to 0 where the reference calls `error`).
 // A table with a WORD CLASS (am_span_table_create_words) keeps the whole-word spans only: both passes decide that with span_of (am_words.h), the count pass counts
-// kept rows, and everything below runs on a compact span array as if the other spans had never matched.
+// kept rows, and everything below runs on a compact span array as if the other spans had never matched.  A table with SPELLINGS (am_span_table_create_cased) is
+// filtered at the same place by the same function: a handle with a spelling is a row only where the text spells it so.
 //
 // LEFTMOST-LONGEST without a sort, in global byte positions g = offsets[haystack] + start.  Haystacks are contiguous and len > 0 implies g < total, so ascending g is
 // ascending (haystack, start), and a span of an earlier haystack ends at or before every g of a later one: nothing below needs a haystack comparison.
@@ -42,9 +43,9 @@ namespace {
 // (kSpThreads, the lanes of a workgroup of the prefix maximum: am_device.h, beside kSpansMaxTile)
 constexpr uint32_t kSpMaxPer = (uint32_t)(kSpansMaxTile / kSpThreads);      // candidates per lane of the prefix maximum
 
-// one lane per record (+ one for the trailing zero of the scan's input): its values < n_needles; WORDS: those the word class keeps (span_of, am_words.h -- under
-// IC the backwards walk runs here and again in k_spans_write: no span that is dropped is ever written)
-template <bool IC, bool WORDS>
+// one lane per record (+ one for the trailing zero of the scan's input): its values < n_needles; WORDS / EXACT: those the word class and the spellings keep (span_of,
+// am_words.h -- under IC the backwards walk runs here and again in k_spans_write: no span that is dropped is ever written)
+template <bool IC, bool WORDS, bool EXACT>
 __global__ void __launch_bounds__(kRowThreads) k_spans_count(SpansIn in, uint32_t* __restrict__ cnt)
 {
     const uint64_t i = global_row();
@@ -56,16 +57,16 @@ __global__ void __launch_bounds__(kRowThreads) k_spans_count(SpansIn in, uint32_
     uint32_t c = 0;
     for (uint64_t k = v0; k < v1; k++) {
         const uint32_t v = in.vals[k];
-        if (!WORDS) { c += v < in.n_needles ? 1u : 0u; continue; }
+        if (!WORDS && !EXACT) { c += v < in.n_needles ? 1u : 0u; continue; }
         if (v >= in.n_needles) continue;
         uint64_t s, n;
-        c += span_of<IC, true>(in, r, v, in.words, s, n) ? 1u : 0u;
+        c += span_of<IC, WORDS, EXACT>(in, r, v, in.words, s, n) ? 1u : 0u;
     }
     cnt[i] = c;
 }
 
 // one lane per record: its spans, in list order, at voff[i]
-template <bool IC, bool WORDS>
+template <bool IC, bool WORDS, bool EXACT>
 __global__ void __launch_bounds__(kRowThreads) k_spans_write(SpansIn in, const uint64_t* __restrict__ voff, Span* __restrict__ spans, uint64_t n_span)
 {
     const uint64_t i = global_row();
@@ -82,7 +83,7 @@ __global__ void __launch_bounds__(kRowThreads) k_spans_write(SpansIn in, const u
         const uint32_t v = in.vals[k];
         if (v >= in.n_needles) continue;                               // the am_needle_ids convention: skipped
         uint64_t s, n;
-        if (!span_of<IC, WORDS>(in, r, v, in.words, s, n)) continue;   // (WORDS only: no whole word, no row -- voff counted the kept ones)
+        if (!span_of<IC, WORDS, EXACT>(in, r, v, in.words, s, n)) continue;      // (a predicate only: not kept, no row -- voff counted the kept ones)
         AM_BOUNDS(o < n_span && o < voff[i + 1] && s <= r.end_pos);
         if (o >= n_span) return;
         Span x;
@@ -284,14 +285,17 @@ __global__ void __launch_bounds__(kRowThreads) k_spans_ll_offsets(const uint64_t
 
 hipError_t launch_spans_count(bool ic, const SpansIn& in, uint32_t* cnt, hipStream_t st)
 {
-    const auto kernel = !in.words ? k_spans_count<false, false> : ic ? k_spans_count<true, true> : k_spans_count<false, true>;      // (no class: the count needs no start, so no case mode)
+    // (no predicate: the count needs no start, so no case mode)
+    const auto kernel = in.exact ? (in.words ? (ic ? k_spans_count<true, true, true> : k_spans_count<false, true, true>) : (ic ? k_spans_count<true, false, true> : k_spans_count<false, false, true>))
+                                 : !in.words ? k_spans_count<false, false, false> : ic ? k_spans_count<true, true, false> : k_spans_count<false, true, false>;
     return launch_rows(kernel, in.n_rec + 1, st, in, cnt);
 }
 
 hipError_t launch_spans_write(bool ic, const SpansIn& in, const uint64_t* voff, Span* spans, uint64_t n_span, hipStream_t st)
 {
     if (n_span == 0) return hipSuccess;
-    const auto kernel = in.words ? (ic ? k_spans_write<true, true> : k_spans_write<false, true>) : (ic ? k_spans_write<true, false> : k_spans_write<false, false>);
+    const auto kernel = in.exact ? (in.words ? (ic ? k_spans_write<true, true, true> : k_spans_write<false, true, true>) : (ic ? k_spans_write<true, false, true> : k_spans_write<false, false, true>))
+                                 : in.words ? (ic ? k_spans_write<true, true, false> : k_spans_write<false, true, false>) : (ic ? k_spans_write<true, false, false> : k_spans_write<false, false, false>);
     return launch_rows(kernel, in.n_rec, st, in, voff, spans, n_span);
 }
 

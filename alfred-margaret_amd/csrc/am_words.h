@@ -4,10 +4,13 @@
 // A WORD CLASS is 256 flags packed into 8 dwords (bit b & 31 of word b >> 5): 32 bytes, one cache line for every lane, in HBM beside the table's lengths or staged in
 // LDS.  A span (start, len) of a haystack of L bytes is a whole word iff (start == 0 or hay[start - 1] is no word byte) and (start + len == L or hay[start + len] is no
 // word byte): the neighbours are bytes of the SAME haystack, never of the one before or after it in the batch, never the zero padding behind the text.
+// EXACT CASE (include/am.h "exact case") is a second predicate of the same kind, between the expansion and the selection: a handle may carry a spelling, and a span
+// of it is a row only where the text spells it so.  The byte comparison is am_cased.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "am_bounds.h"
+#include "am_cased.h"
 #include "am_device.h"
 #include "am_wave.h"
 
@@ -47,10 +50,31 @@ __device__ __forceinline__ bool whole_word(const SpansIn& in, uint32_t h, uint64
     return true;
 }
 
-// (start, len) of value v < n_needles of record r, and whether the table keeps it: always without a word class, the whole-word rule with one
-template <bool IC, bool WORDS>
+// (start, len) of value v < n_needles of record r, and whether the table keeps it: always without a predicate; WORDS: the whole-word rule; EXACT (include/am.h
+// "exact case"): a handle with a spelling of e bytes is kept only where the text spells it so, byte for byte -- with both, both must hold.
+// EXACT takes a shortcut the definition allows: the row is kept iff end_pos >= e and hay[end_pos - e, end_pos) == exact[v], and then start = end_pos - e, without the
+// backwards walk.  The table was made only after checking that the spelling begins with a START byte and holds exactly len_code_points[v] of them, so where the bytes
+// are equal skip_code_points_backwards lands on end_pos - e (len == e, the definition keeps the row), and where they are not the definition drops the row whatever its
+// len is.  Case-sensitive spans take the needle's own len_bytes instead of a walk: there the definition's len == e is tested as it stands.
+template <bool IC, bool WORDS, bool EXACT = false>
 __device__ __forceinline__ bool span_of(const SpansIn& in, const Record& r, uint32_t v, const uint32_t* words, uint64_t& start, uint64_t& len)
 {
+    if (EXACT) {
+        AM_BOUNDS(v < in.n_needles);
+        const ExactRef x = in.exact[v];
+        if (x.len != 0) {
+            start = r.end_pos; len = 0;
+            AM_BOUNDS(r.haystack < in.n_hay);
+            if (r.haystack >= in.n_hay || r.end_pos < x.len) return false;
+            if (!IC && in.len_bytes[v] != x.len) return false;
+            const uint64_t base = in.offsets[r.haystack], next = in.offsets[r.haystack + 1];
+            AM_BOUNDS(base <= next && next <= in.total && r.end_pos <= next - base);
+            if (base > next || next > in.total || r.end_pos > next - base) return false;
+            start = r.end_pos - x.len; len = x.len;
+            if (!cased_equal(in.text, base, next, base + start, in.exact_pool, (uint64_t)x.at16 * kCasedGroup, x.len)) return false;
+            return WORDS ? whole_word(in, r.haystack, start, len, words) : true;
+        }
+    }
     start = span_start<IC>(in, r, v);
     len = r.end_pos >= start ? r.end_pos - start : 0;
     if (!WORDS) return true;

@@ -168,6 +168,58 @@ int amh_spans(void* h, int case_mode, int mode, const am_slice* hay, size_t n_ha
     });
 }
 
+// ---- exact case (include/am.h "exact case"): the siblings of amh_spans_fold_words / amh_spans / amh_substitute_fold_words that take the spellings as
+// am_span_table_create_cased does -- exact_off: n_values + 1 offsets into exact_bytes, an empty range = no spelling, exact_off null = none at all; word_bytes nullable
+namespace {
+ExactSpellings spellingsOf(const uint64_t* exact_off, const uint8_t* exact_bytes, size_t n_values)
+{
+    ExactSpellings out(n_values);
+    if (!exact_off) return out;
+    if (exact_off[0] != 0) throw AmError(AM_ERR_INVALID, "exact_off[0] is not 0");
+    for (size_t v = 0; v < n_values; v++) {
+        if (exact_off[v + 1] < exact_off[v]) throw AmError(AM_ERR_INVALID, "exact_off descends");
+        if (exact_off[v + 1] > exact_off[v]) out[v] = std::string(reinterpret_cast<const char*>(exact_bytes) + exact_off[v], (size_t)(exact_off[v + 1] - exact_off[v]));
+    }
+    return out;
+}
+}  // namespace
+int amh_spans_fold_cased(int case_mode, int mode, const uint32_t* hay_in, const uint64_t* pos_in, const uint32_t* val_in, uint64_t n, const am_slice* hay, size_t n_hay,
+                         const uint32_t* len_bytes, const uint32_t* len_code_points, size_t n_values, const uint8_t* word_bytes, const uint64_t* exact_off,
+                         const uint8_t* exact_bytes, uint64_t** offs_out, uint64_t** spans_out, uint64_t* n_out)
+{
+    *offs_out = nullptr; *spans_out = nullptr; *n_out = 0;
+    return guarded([&] {
+        if ((case_mode != AM_CASE_SENSITIVE && case_mode != AM_IGNORE_CASE) || (mode != AM_SPANS_ALL && mode != AM_SPANS_LEFTMOST_LONGEST))
+            throw AmError(AM_ERR_INVALID, "amh_spans_fold_cased: bad case_mode or mode");
+        std::vector<FoldStep> steps((size_t)n);
+        for (uint64_t i = 0; i < n; i++) steps[i] = FoldStep{hay_in[i], pos_in[i], val_in[i]};
+        const std::vector<uint32_t> lb(len_bytes, len_bytes + n_values), lc(len_code_points, len_code_points + n_values);
+        const ExactSpellings exact = spellingsOf(exact_off, exact_bytes, n_values);
+        spansOut(spansFold((CaseSensitivity)case_mode, mode == AM_SPANS_LEFTMOST_LONGEST, steps, sliceTexts(hay, n_hay), lb, lc, word_bytes, &exact), n_hay, offs_out, spans_out,
+                 n_out);
+    });
+}
+// amh_spans with a class and spellings: amh_run_list's fold, then amh_spans_fold_cased's
+int amh_spans_cased(void* h, int case_mode, int mode, const am_slice* hay, size_t n_hay, const uint32_t* len_bytes, const uint32_t* len_code_points, size_t n_values,
+                    const uint8_t* word_bytes, const uint64_t* exact_off, const uint8_t* exact_bytes, uint64_t** offs_out, uint64_t** spans_out, uint64_t* n_out)
+{
+    *offs_out = nullptr; *spans_out = nullptr; *n_out = 0;
+    return guarded([&] {
+        if ((case_mode != AM_CASE_SENSITIVE && case_mode != AM_IGNORE_CASE) || (mode != AM_SPANS_ALL && mode != AM_SPANS_LEFTMOST_LONGEST))
+            throw AmError(AM_ERR_INVALID, "amh_spans_cased: bad case_mode or mode");
+        struct Acc { std::vector<std::pair<uint64_t, uint32_t>> v; };
+        auto f = [](Acc a, const Match<uint32_t>& m) { a.v.emplace_back(m.matchPos, m.matchValue); return Next<Acc>::Step(std::move(a)); };
+        const std::vector<Text> texts = sliceTexts(hay, n_hay);
+        auto accs = runBatchWithCase((CaseSensitivity)case_mode, Acc{}, f, static_cast<MachineBox*>(h)->m, texts);
+        std::vector<FoldStep> steps;
+        for (size_t i = 0; i < accs.size(); i++)
+            for (auto& pv : accs[i].v) steps.push_back(FoldStep{(uint32_t)i, pv.first, pv.second});
+        const std::vector<uint32_t> lb(len_bytes, len_bytes + n_values), lc(len_code_points, len_code_points + n_values);
+        const ExactSpellings exact = spellingsOf(exact_off, exact_bytes, n_values);
+        spansOut(spansFold((CaseSensitivity)case_mode, mode == AM_SPANS_LEFTMOST_LONGEST, steps, texts, lb, lc, word_bytes, &exact), n_hay, offs_out, spans_out, n_out);
+    });
+}
+
 // ---- rule sets (rules.hpp): rulesFold over fold steps the caller brings (n (haystack, value) pairs in fold order, haystacks ascending) and a program in the C ABI's
 // form (rule_off: n_rules + 1, clause_off: rule_off[n_rules] + 1, literals: clause_off[last]): no device is touched.  fired_out: n_rules x ceil(n_hay / 64) words,
 // labels_out: n_hay, counts_out: n_rules, all the caller's
@@ -289,6 +341,22 @@ int amh_substitute_fold(int case_mode, const uint32_t* hay_in, const uint64_t* p
                         uint8_t** blob_out, uint64_t* offs_out)
 {
     return amh_substitute_fold_words(case_mode, hay_in, pos_in, val_in, n, hay, n_hay, len_bytes, len_code_points, n_values, repl_bytes, repl_off, nullptr, blob_out, offs_out);
+}
+// amh_substitute_fold_words with spellings (as amh_spans_fold_cased takes them): substituteFold over the kept rows
+int amh_substitute_fold_cased(int case_mode, const uint32_t* hay_in, const uint64_t* pos_in, const uint32_t* val_in, uint64_t n, const am_slice* hay, size_t n_hay,
+                              const uint32_t* len_bytes, const uint32_t* len_code_points, size_t n_values, const uint8_t* repl_bytes, const uint64_t* repl_off,
+                              const uint8_t* word_bytes, const uint64_t* exact_off, const uint8_t* exact_bytes, uint8_t** blob_out, uint64_t* offs_out)
+{
+    *blob_out = nullptr;
+    return guarded([&] {
+        if (case_mode != AM_CASE_SENSITIVE && case_mode != AM_IGNORE_CASE) throw AmError(AM_ERR_INVALID, "amh_substitute_fold_cased: bad case_mode");
+        std::vector<FoldStep> steps((size_t)n);
+        for (uint64_t i = 0; i < n; i++) steps[i] = FoldStep{hay_in[i], pos_in[i], val_in[i]};
+        const std::vector<uint32_t> lb(len_bytes, len_bytes + n_values), lc(len_code_points, len_code_points + n_values);
+        const std::vector<Text> texts = sliceTexts(hay, n_hay);
+        const ExactSpellings exact = spellingsOf(exact_off, exact_bytes, n_values);
+        substituteOut(spansFold((CaseSensitivity)case_mode, true, steps, texts, lb, lc, word_bytes, &exact), texts, repl_bytes, repl_off, n_values, blob_out, offs_out);
+    });
 }
 // amh_run_list's fold (the scan on the device, the fold on the host), then spansFold and substitute
 int amh_substitute(void* h, int case_mode, const am_slice* hay, size_t n_hay, const uint32_t* len_bytes, const uint32_t* len_code_points, size_t n_values,

@@ -3,6 +3,8 @@
 // all of them in fold order, or the leftmost-longest non-overlapping selection.  spansFold takes the fold steps as they are and touches no device.
 #pragma once
 #include <algorithm>
+#include <cstring>
+#include <optional>
 #include <string>
 
 #include "automaton.hpp"
@@ -41,9 +43,22 @@ inline void defaultWordBytes(uint8_t out[256])
     for (unsigned b = 0; b < 256; b++) out[b] = ((b >= '0' && b <= '9') || (b >= 'A' && b <= 'Z') || (b >= 'a' && b <= 'z') || b == '_' || b >= 0x80) ? 1 : 0;
 }
 
-// wordBytes (nullable: no class): only the whole-word spans are rows, and the leftmost-longest selection runs over those -- filter, then select
+// the exact-case rule of include/am.h "exact case": a handle may carry a spelling, and a span of it is a row only where len == |spelling| and the haystack spells it
+// so, byte for byte.  The definition as it stands: the span comes from spanStart, no shortcut.
+using ExactSpellings = std::vector<std::optional<std::string>>;      // one entry per value handle (shorter: the handles beyond have none)
+
+inline bool exactCase(const Text& hay, uint64_t start, uint64_t len, const std::optional<std::string>& spelling)
+{
+    if (!spelling) return true;
+    if (start > hay.len || len > hay.len - start) return false;
+    return len == spelling->size() && (len == 0 || std::memcmp(hay.begin() + start, spelling->data(), (size_t)len) == 0);
+}
+
+// wordBytes (nullable: no class): only the whole-word spans are rows, and the leftmost-longest selection runs over those -- filter, then select.  exact (nullable:
+// no spelling): the exact-case rule, applied where the whole-word rule is; with both, both must hold
 inline Spans spansFold(CaseSensitivity cs, bool leftmostLongest, const std::vector<FoldStep>& steps, const std::vector<Text>& texts,
-                       const std::vector<uint32_t>& lenBytes, const std::vector<uint32_t>& lenCodePoints, const uint8_t* wordBytes = nullptr)
+                       const std::vector<uint32_t>& lenBytes, const std::vector<uint32_t>& lenCodePoints, const uint8_t* wordBytes = nullptr,
+                       const ExactSpellings* exact = nullptr)
 {
     if (lenBytes.size() != lenCodePoints.size()) throw AmError(AM_ERR_INVALID, "spansFold: the two length arrays differ in size");
     const size_t nValues = lenBytes.size();
@@ -59,6 +74,7 @@ inline Spans spansFold(CaseSensitivity cs, bool leftmostLongest, const std::vect
             if (v >= nValues) continue;                     // the am_needle_ids convention: skipped
             const uint64_t start = spanStart(cs, texts[h], steps[k].matchPos, lenBytes[v], lenCodePoints[v]);
             const uint64_t len = steps[k].matchPos >= start ? steps[k].matchPos - start : 0;
+            if (exact && v < exact->size() && !exactCase(texts[h], start, len, (*exact)[v])) continue;
             if (wordBytes && !wholeWord(texts[h], start, len, wordBytes)) continue;
             all.push_back(am_span{start, len, (uint32_t)h, v});
         }
@@ -101,11 +117,18 @@ inline std::vector<std::string> substitute(const Spans& spans, const std::vector
     return out;
 }
 
-// ... straight from the fold steps, with an optional word class: substitute over spansFold(cs, leftmost-longest, ..., wordBytes)
+// ... straight from the fold steps, with an optional word class and optional spellings: substitute over spansFold(cs, leftmost-longest, ..., wordBytes, exact)
 inline std::vector<std::string> substitute(CaseSensitivity cs, const std::vector<FoldStep>& steps, const std::vector<Text>& texts, const std::vector<uint32_t>& lenBytes,
-                                           const std::vector<uint32_t>& lenCodePoints, const std::vector<std::string>& replacements, const uint8_t* wordBytes = nullptr)
+                                           const std::vector<uint32_t>& lenCodePoints, const std::vector<std::string>& replacements, const uint8_t* wordBytes = nullptr,
+                                           const ExactSpellings* exact = nullptr)
 {
-    return substitute(spansFold(cs, true, steps, texts, lenBytes, lenCodePoints, wordBytes), texts, replacements);
+    return substitute(spansFold(cs, true, steps, texts, lenBytes, lenCodePoints, wordBytes, exact), texts, replacements);
+}
+inline std::vector<std::string> substituteFold(CaseSensitivity cs, const std::vector<FoldStep>& steps, const std::vector<Text>& texts, const std::vector<uint32_t>& lenBytes,
+                                               const std::vector<uint32_t>& lenCodePoints, const std::vector<std::string>& replacements, const uint8_t* wordBytes = nullptr,
+                                               const ExactSpellings* exact = nullptr)
+{
+    return substitute(cs, steps, texts, lenBytes, lenCodePoints, replacements, wordBytes, exact);
 }
 
 // substitute templates (include/am.h "substitute templates"): the same splice with T(v, m) in the place of repl[v] -- the segments of template v in order, a literal's

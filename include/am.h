@@ -447,6 +447,43 @@ AM_API int am_span_table_word_bytes(const am_span_table* t, uint8_t* out256 /* n
 AM_API int am_count_spans_by_needle_batch(const am_span_table* t, int case_mode, const am_batch* b, uint64_t* counts_out /* n_needles, host */);
 AM_API int am_count_spans_by_needle(const am_span_table* t, int case_mode, const am_slice* hay, size_t n_hay, uint64_t* counts_out /* n_needles, host */);
 
+/* ---- exact case: a span table with a spelling per needle -- most needles match in any casing, some only as spelled, in ONE scan ---------------
+ * A dictionary mixes terms that should match in any casing (nike) with terms that mean something only as spelled (US, WHO, Apple).  The automaton holds the
+ * lower-cased needles and the scan runs under AM_IGNORE_CASE, as ever; the span table says, per needle handle, how the text must spell it:
+ *   exact[v]       the spelling of handle v: a byte string, or absent.
+ *   (start, len)   the span makeMatch gives a fold step `Match pos v` -- the span of "match spans", untouched.
+ *   The table KEEPS the span iff exact[v] is absent, or both hold:  len == |exact[v]|  and  hay[start, start + len) == exact[v], byte for byte.
+ * The rule is the same in both case modes; under AM_CASE_SENSITIVE it is a constant per needle (the needle is its own spelling, or no span of it is a row).  With
+ * a word class too, both predicates must hold.  This is still FILTER, THEN SELECT: AM_SPANS_LEFTMOST_LONGEST, substitute, extract, coordinates, near and postings see
+ * only the kept rows.  A handle without a spelling behaves exactly as before, and a table with no spelling at all IS the table of am_span_table_create /
+ * am_span_table_create_words: the same kernels, the same bytes.
+ *   Plain filtering.    us, apple, nike with exact = [US, Apple, -] over "us, US and NIKE's apple" under AM_IGNORE_CASE: AM_SPANS_ALL gives (4,2,us) (11,4,nike).
+ *   Width.              k with exact = K: the text K is kept, k is dropped, and so is U+212A (Kelvin sign): its len is 3, not 1.  With exact = U+212A the keeps
+ *                       and the drops swap.
+ *   Filter, then select. `ab c` with exact = `AB C` and ab without a spelling over "ab c": the plain table selects (0,4); filtering afterwards would leave nothing.
+ *                       The cased table gives (0,2,ab).
+ *   Duplicate needles.  us twice with exact = [US, -]: two handles of one state.  Over "US" both rows appear, over "us" only the second.
+ * The predicate sits where the whole-word predicate sits (csrc/am_words.h, one device function for the expansion, the histogram, the scores and the select's
+ * flags); the byte comparison is csrc/am_cased.h's.  Record memory stays bounded wherever it is bounded for a table with a class.  Nothing about the scans, the
+ * record format or the image changes.
+ *   am_span_table_create_cased   am_span_table_create (the same checks, the same messages) with flags (AM_SPAN_TABLE_WORDS: word_bytes applies, NULL for the default
+ *                                class; otherwise word_bytes is not looked at) and spellings: the spelling of v is exact_bytes[exact_off[v], exact_off[v + 1]), an
+ *                                empty range means none.  exact_off == NULL: no spelling -- with flags == 0 exactly am_span_table_create, with AM_SPAN_TABLE_WORDS
+ *                                exactly am_span_table_create_words.  AM_ERR_INVALID, before any device work and with *out == NULL, for unknown flag bits,
+ *                                exact_off[0] != 0 or descending offsets, a spelling of 2^32 bytes or more, and a non-empty spelling that begins with a continuation
+ *                                byte, whose number of START bytes ((b & 0xC0) != 0x80) differs from len_code_points[v] (which catches a list that is off by one
+ *                                handle), or that belongs to a needle of length 0.  The spellings are copied: the table keeps a host copy and a padded pool on its device.
+ *   am_span_table_check_exact    the checks am_span_table_create_cased makes on its spellings, alone: AM_OK or AM_ERR_INVALID with the same message.  Needs no device.
+ *   am_span_table_exact          1 and the spelling of `needle` (bytes / len nullable; the host copy, owned by the table) where it has one; 0 otherwise.
+ * RuleSet, count_matrix, contains_any / contains_all and the Replacer do not go through a span table: they stay single-mode. */
+#define AM_SPAN_TABLE_WORDS 1u   /* word_bytes (NULL: the default class) applies */
+AM_API int am_span_table_create_cased(const am_needle_ids* ids, const uint32_t* len_bytes, const uint32_t* len_code_points,
+                                      uint32_t flags, const uint8_t* word_bytes,
+                                      const uint64_t* exact_off /* n_needles + 1, host; NULL: no spelling */, const uint8_t* exact_bytes,
+                                      am_span_table** out);
+AM_API int am_span_table_check_exact(const uint32_t* len_bytes, const uint32_t* len_code_points, uint32_t n_needles, const uint64_t* exact_off, const uint8_t* exact_bytes);
+AM_API int am_span_table_exact(const am_span_table* t, uint32_t needle, const uint8_t** bytes, uint64_t* len);   /* 1: has a spelling (host copy owned by the table), 0: none */
+
 /* ---- select: keep the haystacks that match and drop the rest, in HBM; the kept haystacks are a batch of their own ---------------
  * `grep -F -f needles` (am_select_any*), `grep -v` (invert), `grep -w` (am_select_spans_batch with a table that carries a word class) and "the lines that mention all of
  * these terms" (am_select_all*) over a batch, without the flags, the texts or the kept texts crossing the wire.  A SELECTION says which haystacks of a batch were kept:
