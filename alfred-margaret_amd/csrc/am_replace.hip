@@ -14,49 +14,18 @@
 // chosen in one pass of one haystack belong to ONE payload: they have the same code-point length, hence
 // their start positions are ordered like their end positions and the derived-Ord sort (:159, :241) is the
 // identity on the record order.  am_replacer_create rejects payload tables with duplicate priorities.
+// prependMatch, makeMatch, removeOverlap and the piece splice themselves are stated once, in am_rp_fold.h, for these kernels, k_rp_loop and k_rp_lds.
 #include <hip/hip_runtime.h>
 
 #include "am_device.h"
+#include "am_rp_fold.h"
+#include "am_wave.h"
 
 namespace am {
 namespace dev {
 
 namespace {
-
 constexpr int kWave = 64;
-
-__device__ __forceinline__ int64_t wave_max_i64(int64_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const int64_t o = __shfl_xor(v, d, kWave); v = o > v ? o : v; }
-    return v;
-}
-
-__device__ __forceinline__ int64_t wave_sum_i64(int64_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
-    return v;
-}
-
-__device__ __forceinline__ int64_t wave_inclusive_sum_i64(int64_t v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) { const int64_t o = __shfl_up(v, d, kWave); if (lane >= d) v += o; }
-    return v;
-}
-
-// Utf8.hs:256-276 skipCodePointsBackwards, relative to the haystack start; never leaves the haystack.
-__device__ __forceinline__ uint64_t skip_code_points_backwards(const uint8_t* hay, uint64_t index, uint64_t n)
-{
-    int64_t i = (int64_t)index;
-    for (;;) {
-        while (i > 0 && (hay[i] & 0xC0u) == 0x80u) i--;      // atTrailingByte
-        if (n == 0 || i <= 0) return (uint64_t)(i < 0 ? 0 : i);
-        i--; n--;
-    }
-}
-
 }  // namespace
 
 __global__ void __launch_bounds__(256) k_rp_ranges(const Record* __restrict__ recs, uint64_t n_rec, const uint64_t* __restrict__ n_rec_dev, uint64_t* __restrict__ rec_first,
@@ -109,13 +78,7 @@ __global__ void __launch_bounds__(256) k_rp_pass(RpTables t, const uint8_t* __re
 
     // ---- prependMatch, first half: the best priority below the threshold (Replacer.hs:255-258)
     int64_t best = INT64_MIN;
-    for (uint64_t r = r0 + lane; r < r1; r += kWave) {
-        const uint32_t st = recs[r].state;
-        for (uint64_t k = t.vals_off[st], ke = t.vals_off[st + 1]; k < ke; k++) {
-            const int64_t p = t.payloads[t.vals[k]].priority;
-            if (p < threshold && p > best) best = p;
-        }
-    }
+    for (uint64_t r = r0 + lane; r < r1; r += kWave) rp_best_in_values(t, recs[r].state, threshold, best);
     best = wave_max_i64(best);
 
     uint32_t status = kRpFinished, nkept = 0, payload = 0;
@@ -130,46 +93,23 @@ __global__ void __launch_bounds__(256) k_rp_pass(RpTables t, const uint8_t* __re
             if (r < r1) {
                 const Record rec = recs[r];
                 end_pos = rec.end_pos;
-                for (uint64_t k = t.vals_off[rec.state], ke = t.vals_off[rec.state + 1]; k < ke; k++) {
-                    const uint32_t v = t.vals[k];
-                    if (t.payloads[v].priority == best) { sel = true; pl = v; }
-                }
+                rp_pick_in_values(t, rec.state, best, sel, pl);
             }
             uint64_t start = 0, len = 0; int64_t delta = 0;
             if (sel) {
                 const RpPayload pp = t.payloads[pl];
                 if (!IC) { len = pp.len_bytes; start = end_pos - len; }                       // Replacer.hs:266-267
                 else {                                                                        // :268-274
-                    start = pp.len_code_points == 0 ? end_pos : skip_code_points_backwards(text + hoff, end_pos - 1, pp.len_code_points - 1);
+                    start = pp.len_code_points == 0 ? end_pos : skip_code_points_backwards(text + hoff, end_pos, pp.len_code_points - 1);
                     len = end_pos - start;
                 }
                 delta = (int64_t)pp.repl_len - (int64_t)len;
             }
             delta_all += delta;
-            // removeOverlap (:191-198): in position order keep a match iff it starts at or after the end of the last kept one
-            uint64_t pending = keep_all ? 0ull : __ballot(sel);
-            bool keep = keep_all && sel;          // am_run_priority: the caller removes overlaps itself
-            while (pending) {
-                const uint64_t ok = __ballot(sel && start >= last_end) & pending;
-                if (!ok) break;
-                const int l = __ffsll((unsigned long long)ok) - 1;
-                if (lane == l) keep = true;
-                last_end = __shfl(start + len, l, kWave);
-                pending &= l == 63 ? 0ull : ~((2ull << l) - 1ull);
-            }
-            const uint64_t keepmask = __ballot(keep);
-            if (keepmask) {
-                const int64_t kd = keep ? delta : 0;
-                const int64_t incl = wave_inclusive_sum_i64(kd, lane);
-                if (keep) {
-                    const uint32_t rank = __popcll(keepmask & ((1ull << lane) - 1ull));
-                    RpKept e; e.src_start = start; e.src_len = len; e.dst = (uint64_t)((int64_t)start + delta_kept + (incl - kd));
-                    kept[r0 + nkept + rank] = e;
-                    payload = pl;
-                }
-                delta_kept += __shfl(incl, kWave - 1, kWave);
-                nkept += __popcll(keepmask);
-            }
+            // removeOverlap (:191-198); am_run_priority keeps every match: the caller removes overlaps itself
+            const bool keep = keep_all ? sel : rp_remove_overlap(sel, start, len, last_end, lane);
+            rp_keep_block(keep, start, len, delta, kept + r0, nkept, delta_kept, lane);
+            if (keep) payload = pl;
         }
         delta_all = wave_sum_i64(delta_all);
         payload = (uint32_t)wave_max_i64((int64_t)payload);     // uniform: every kept match has the same payload
@@ -210,11 +150,7 @@ __global__ void __launch_bounds__(256) k_rpp_best(RpTables t, const Record* __re
     if (r < n_rec) {
         const Record rec = recs[r];
         hay = rec.haystack;
-        const int64_t threshold = thr[hay];
-        for (uint64_t k = t.vals_off[rec.state], ke = t.vals_off[rec.state + 1]; k < ke; k++) {
-            const int64_t p = t.payloads[t.vals[k]].priority;
-            if (p < threshold && p > b) b = p;
-        }
+        rp_best_in_values(t, rec.state, thr[hay], b);
     }
     const uint32_t h0 = __shfl(hay, 0, kWave);
     if (__ballot(hay != h0 && hay != 0xFFFFFFFFu) == 0) {          // the usual case: the whole wavefront inside one haystack
@@ -234,26 +170,22 @@ __global__ void __launch_bounds__(256) k_rpp_select(RpTables t, const uint8_t* _
     if (r == n_rec) { selflag[r] = 0; return; }                    // the scan's trailing element
     const Record rec = recs[r];
     const int64_t b = best[rec.haystack];
-    uint32_t flag = 0;
-    if (b != INT64_MIN) {
-        for (uint64_t k = t.vals_off[rec.state], ke = t.vals_off[rec.state + 1]; k < ke; k++) {
-            const uint32_t v = t.vals[k];
-            const RpPayload pp = t.payloads[v];
-            if (pp.priority != b) continue;
-            uint64_t start, len;
-            if (!IC) { len = pp.len_bytes; start = rec.end_pos - len; }
-            else {
-                start = pp.len_code_points == 0 ? rec.end_pos : skip_code_points_backwards(text + offsets[rec.haystack], rec.end_pos - 1, pp.len_code_points - 1);
-                len = rec.end_pos - start;
-            }
-            RpSel c; c.start = start; c.len = len; c.haystack = rec.haystack; c.pad = 0;
-            cand[r] = c;
-            payload_of[rec.haystack] = v;
-            atomicAdd((unsigned long long*)(delta_all + rec.haystack), (unsigned long long)((int64_t)pp.repl_len - (int64_t)len));
-            flag = 1;
+    bool sel = false; uint32_t v = 0;
+    if (b != INT64_MIN) rp_pick_in_values(t, rec.state, b, sel, v);
+    if (sel) {
+        const RpPayload pp = t.payloads[v];
+        uint64_t start, len;
+        if (!IC) { len = pp.len_bytes; start = rec.end_pos - len; }
+        else {
+            start = pp.len_code_points == 0 ? rec.end_pos : skip_code_points_backwards(text + offsets[rec.haystack], rec.end_pos, pp.len_code_points - 1);
+            len = rec.end_pos - start;
         }
+        RpSel c; c.start = start; c.len = len; c.haystack = rec.haystack; c.pad = 0;
+        cand[r] = c;
+        payload_of[rec.haystack] = v;
+        atomicAdd((unsigned long long*)(delta_all + rec.haystack), (unsigned long long)((int64_t)pp.repl_len - (int64_t)len));
     }
-    selflag[r] = flag;
+    selflag[r] = sel ? 1u : 0u;
 }
 
 __global__ void __launch_bounds__(256) k_rpp_compact(const uint32_t* __restrict__ selflag, const uint64_t* __restrict__ sidx, const RpSel* __restrict__ cand,
@@ -771,10 +703,7 @@ __global__ void __launch_bounds__(256) k_pt_count(const RpHay* __restrict__ hs, 
     nwin[h] = (h < n_act && hs[h].status == kRpActive) ? hs[h].nkept : 0u;
 }
 
-// One wavefront per haystack.  Old piece i = old text [ls, le).  The kept matches (sorted, disjoint) cut it into fragments; a
-// fragment that starts at old position x lies, in the new text, at x + (sum of the length changes of the matches before it)
-// = K[j].dst + repl_len + (x - end of K[j]) for the last match j before x.  The replacement of match j is emitted by the piece
-// that contains its first byte.  Two sweeps over the pieces (count, then write) with a wave prefix sum between them.
+// One wavefront per haystack: the next piece list from the old one and the kept matches (rp_splice_pieces, am_rp_fold.h)
 __global__ void __launch_bounds__(256) k_pt_build(RpTables t, const RpHay* __restrict__ hs, const uint64_t* __restrict__ rec_first, const RpKept* __restrict__ kept,
                                                   const RpPiece* __restrict__ pieces, const uint64_t* __restrict__ pc_start, const uint32_t* __restrict__ pc_cnt,
                                                   const uint64_t* __restrict__ need_off, RpRouted rt, uint32_t n_act,
@@ -793,47 +722,7 @@ __global__ void __launch_bounds__(256) k_pt_build(RpTables t, const RpHay* __res
     const RpPayload pp = t.payloads[s.payload];
     const uint64_t repl_len = nk ? pp.repl_len : 0;
     RpPiece* Q = out + need_off[h];
-    // what piece i contributes: the matches j in [ja, jb) are those that end after its start and start before its end
-    auto span = [&](uint64_t ls, uint64_t le, uint32_t& ja, uint32_t& jb) {
-        uint32_t a = 0, b = nk;
-        while (a < b) { const uint32_t mid = (a + b) >> 1; if (K[mid].src_start + K[mid].src_len <= ls) a = mid + 1; else b = mid; }
-        ja = a; jb = a;
-        while (jb < nk && K[jb].src_start < le) jb++;
-    };
-    // walks piece i: f(kind, src, new_pos) for every entry it emits, in order
-    auto emit = [&](uint32_t i, auto&& f) {
-        const uint64_t ls = P[i].lstart, le = P[i + 1].lstart;
-        if (le == ls) return;
-        uint32_t ja, jb; span(ls, le, ja, jb);
-        uint64_t x = ls;                                  // old position where the next fragment would start
-        // new position of old position x when it is not inside a match: after the last match that ends at or before x
-        auto new_pos = [&](uint64_t xx, uint32_t jprev_plus1) -> uint64_t {
-            if (jprev_plus1 == 0) return xx;
-            const RpKept k = K[jprev_plus1 - 1];
-            return k.dst + repl_len + (xx - (k.src_start + k.src_len));
-        };
-        uint32_t jp = ja;                                 // matches [0, jp) end at or before x
-        for (uint32_t j = ja; j < jb; j++) {
-            const RpKept k = K[j];
-            if (k.src_start > x) f(P[i].src + (x - ls), new_pos(x, jp));                          // fragment before the match
-            if (k.src_start >= ls && repl_len) f(kPieceRepl | pp.repl_off, k.dst);                  // the match starts in this piece: its replacement
-            x = k.src_start + k.src_len;
-            jp = j + 1;
-            if (x >= le) break;
-        }
-        if (x < le) f(P[i].src + (x - ls), new_pos(x, jp));
-    };
-    // 64 pieces per round, lane = piece within the round: count, prefix over the lanes, write -- rounds follow each other in order
-    uint32_t base = 0;
-    for (uint32_t r0 = 0; r0 < n; r0 += kWave) {
-        const uint32_t i = r0 + lane;
-        uint32_t c = 0;
-        if (i < n) emit(i, [&](uint64_t, uint64_t) { c++; });
-        const uint32_t incl = (uint32_t)wave_inclusive_sum_i64((int64_t)c, lane);
-        uint32_t at = base + incl - c;
-        if (i < n) emit(i, [&](uint64_t src, uint64_t pos) { Q[at++] = RpPiece{src, pos}; });
-        base += __shfl(incl, kWave - 1, kWave);
-    }
+    const uint32_t base = rp_splice_pieces(P, n, K, nk, repl_len, kPieceRepl | pp.repl_off, Q, lane, [] { return true; });
     if (lane == 0) {
         Q[base] = RpPiece{0, s.newlen};                   // sentinel
         if (s.status == kRpActive) { const uint64_t a = rt.act_idx[h]; next_start[a] = need_off[h]; next_cnt[a] = base; }
@@ -841,23 +730,11 @@ __global__ void __launch_bounds__(256) k_pt_build(RpTables t, const RpHay* __res
     }
 }
 
-// bytes [lo, lo + len) of a piece list into dst, one wavefront
-__device__ __forceinline__ void pt_gather(const RpPiece* __restrict__ P, uint32_t n, const uint8_t* __restrict__ text, const uint8_t* __restrict__ repl,
-                                          uint64_t lo, uint64_t len, uint8_t* __restrict__ dst, int lane)
+// bytes [lo, lo + len) of a piece list into dst, one wavefront; the first piece by a binary search
+__device__ __forceinline__ void pt_copy(const RpPiece* __restrict__ P, uint32_t n, const uint8_t* __restrict__ text, const uint8_t* __restrict__ repl,
+                                        uint64_t lo, uint64_t len, uint8_t* __restrict__ dst, int lane)
 {
-    if (len == 0) return;
-    uint32_t a = 0, b = n;                               // last piece whose start is <= lo
-    while (b - a > 1) { const uint32_t mid = (a + b) >> 1; if (P[mid].lstart <= lo) a = mid; else b = mid; }
-    uint64_t pos = lo;
-    const uint64_t end = lo + len;
-    for (uint32_t i = a; pos < end; i++) {
-        const uint64_t pe = P[i + 1].lstart < end ? P[i + 1].lstart : end;
-        const uint64_t s = P[i].src;
-        const uint8_t* from = ((s & kPieceRepl) ? repl + (s & ~kPieceRepl) : text + s) + (pos - P[i].lstart);
-        uint8_t* to = dst + (pos - lo);
-        for (uint64_t x = lane; x < pe - pos; x += kWave) to[x] = from[x];
-        pos = pe;
-    }
+    rp_gather(P, n, text, repl, lo, len, dst, lane, [&] { return rp_piece_at(P, n, lo); }, [] { return true; });
 }
 
 // finished haystacks: their text, once.  One workgroup per haystack, a wavefront per piece -- and a piece is a few hundred bytes reached through its list entry, so a
@@ -894,7 +771,7 @@ __global__ void __launch_bounds__(256) k_pt_materialise(const RpPiece* __restric
             if (i < n) {
                 const RpPiece a = staged ? s_p[i] : P[i], b = staged ? s_p[i + 1] : P[i + 1];
                 len[u] = b.lstart - a.lstart;
-                from[u] = (a.src & kPieceRepl) ? repl + (a.src & ~kPieceRepl) : text + a.src;
+                from[u] = rp_piece_base(a.src, text, repl);
                 to[u] = dst + a.lstart;
             }
         }
@@ -933,7 +810,7 @@ __global__ void __launch_bounds__(256) k_pt_materialise_next(const RpPiece* __re
     const int lane = threadIdx.x & (kWave - 1);
     const uint32_t a = blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
     if (a >= n_next) return;
-    pt_gather(pieces + next_start[a], next_cnt[a], text, repl, 0, next_offsets[a + 1] - next_offsets[a], out + next_offsets[a], lane);
+    pt_copy(pieces + next_start[a], next_cnt[a], text, repl, 0, next_offsets[a + 1] - next_offsets[a], out + next_offsets[a], lane);
 }
 
 hipError_t launch_pt_materialise_next(const RpPiece* pieces, const uint64_t* next_start, const uint32_t* next_cnt, const uint64_t* next_offsets, uint32_t n_next,
@@ -956,7 +833,7 @@ __global__ void __launch_bounds__(256) k_pt_win_copy(const RpWin* __restrict__ w
     if (wi > n_win) return;
     const RpWin w = wins[wi];
     const uint64_t a = w.src_abs >> 40, lo = w.src_abs & ((1ull << 40) - 1ull);
-    pt_gather(pieces + next_start[a], next_cnt[a], text, repl, lo, w.len, wtext + woffs[wi], lane);
+    pt_copy(pieces + next_start[a], next_cnt[a], text, repl, lo, w.len, wtext + woffs[wi], lane);
 }
 
 hipError_t launch_pt_init(const uint64_t* offsets, uint32_t n_act, RpPiece* pieces, uint64_t* pc_start, uint32_t* pc_cnt, hipStream_t st)

@@ -266,7 +266,7 @@ extern "C" int am_replacer_create(const am_automaton* a, int case_mode, const ui
             if (n == 1) {
                 const uint32_t v = values[values_offsets[s]];
                 const int64_t pr = payloads[v].priority;
-                // (INT32_MIN itself is k_rp_lds's "nothing below the threshold", am_rplds.hip:181-185: it takes the value list, like everything below it)
+                // (INT32_MIN itself is k_rp_lds's "nothing below the threshold", am_rplds.hip:151-155: it takes the value list, like everything below it)
                 if (pr > INT32_MIN) { e.priority = (int32_t)pr; e.payload = v; }
             }
             one[s] = e;

@@ -20,10 +20,13 @@
 // A haystack that does not fit (more records / pieces than the LDS lists hold, positions beyond 2^31, more than 64 new records in one window, a pass
 // that keeps more matches than its kept list holds) raises ITS redo flag and k_rp_loop -- launched right behind this kernel -- runs that haystack from
 // its first scan; nothing is shared between haystacks, so nothing else repeats.
+// The value lists of prependMatch, makeMatch's walk and removeOverlap are those of am_rp_fold.h, where Replacer.hs:191-198, 252-274 are stated; the lists' LDS
+// layout, the in-place piece editing and the window scan are this kernel's own.
 #include <hip/hip_runtime.h>
 
 #include "am_device.h"
 #include "am_bounds.h"
+#include "am_rp_fold.h"
 #include "am_wave.h"
 
 AM_BOUNDS_TU("am_rplds.hip")
@@ -49,39 +52,6 @@ struct LpLds {
     uint32_t psrc[kLdsPc + 2]; uint32_t pls[kLdsPc + 2];
     alignas(16) uint8_t win[kLdsWin + 16];                // the window's text: gathered through the piece list, read back by the probe / resolve lanes
 };
-
-__device__ __forceinline__ int64_t ld_wave_max_i64(int64_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const int64_t o = __shfl_xor(v, d, kWave); v = o > v ? o : v; }
-    return v;
-}
-__device__ __forceinline__ int64_t ld_wave_sum_i64(int64_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
-    return v;
-}
-// maximum over the 64 lanes with DPP (the shape of am_wave.h's prefix sum: inside each row of 16, then across the rows); uniform result
-__device__ __forceinline__ int32_t ld_wave_max_i32(int32_t x)
-{
-    x = [&] { const int32_t o = __builtin_amdgcn_update_dpp(INT32_MIN, x, 0x111, 0xf, 0xf, false); return o > x ? o : x; }();      // row_shr:1
-    x = [&] { const int32_t o = __builtin_amdgcn_update_dpp(INT32_MIN, x, 0x112, 0xf, 0xf, false); return o > x ? o : x; }();      // row_shr:2
-    x = [&] { const int32_t o = __builtin_amdgcn_update_dpp(INT32_MIN, x, 0x114, 0xf, 0xf, false); return o > x ? o : x; }();      // row_shr:4
-    x = [&] { const int32_t o = __builtin_amdgcn_update_dpp(INT32_MIN, x, 0x118, 0xf, 0xf, false); return o > x ? o : x; }();      // row_shr:8
-    x = [&] { const int32_t o = __builtin_amdgcn_update_dpp(INT32_MIN, x, 0x142, 0xa, 0xf, false); return o > x ? o : x; }();      // row_bcast:15 -> rows 1, 3
-    x = [&] { const int32_t o = __builtin_amdgcn_update_dpp(INT32_MIN, x, 0x143, 0xc, 0xf, false); return o > x ? o : x; }();      // row_bcast:31 -> rows 2, 3
-    return __builtin_amdgcn_readlane(x, 63);
-}
-__device__ __forceinline__ uint32_t ld_u32(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-
-// what the lanes of this wavefront wrote to GLOBAL memory is visible to its other lanes (the window scratch, the kept list)
-__device__ __forceinline__ void ld_global_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 // elements [from, to) of an LDS array move to [from + g, to + g), `add` added to each: 64 per trip, from the top down when they move up (a trip's
 // reads are issued before its writes and DS operations of a wavefront execute in order; across trips the writes land where everything has been read)
@@ -181,21 +151,18 @@ __device__ __forceinline__ void ld_run_haystack(const RpLoop& a, LpLds<PLI>& L, 
         int32_t b32 = INT32_MIN;
 #pragma unroll
         for (uint32_t b = 0; b < kLdsBlocks; b++) { const int32_t v = p_[b] < thr32 ? p_[b] : INT32_MIN; b32 = v > b32 ? v : b32; }
-        b32 = ld_wave_max_i32(b32);
+        b32 = wave_max_i32(b32);
         int64_t best = b32 == INT32_MIN ? INT64_MIN : (int64_t)b32;
         if (has_walk) {                                                  // ... and the value lists of the states that carry several
             int64_t bw = INT64_MIN;
 #pragma unroll
             for (uint32_t b = 0; b < kLdsBlocks; b++) {
                 if (pl_of(p_[b], l_[b]) == kRpWalkList && p_[b] != kDead) {
-                    const uint32_t st = (uint32_t)p_[b]; AM_BOUNDS(p_[b] > 0);      // (a walk-list slot holds a state id, never a priority: vals_off[] is indexed with it)
-                    for (uint64_t k = a.t.vals_off[st], ke = a.t.vals_off[st + 1]; k < ke; k++) {
-                        const int64_t p = a.t.payloads[a.t.vals[k]].priority;
-                        if (p < threshold && p > bw) bw = p;
-                    }
+                    AM_BOUNDS(p_[b] > 0);                                // (a walk-list slot holds a state id, never a priority: vals_off[] is indexed with it)
+                    rp_best_in_values(a.t, (uint32_t)p_[b], threshold, bw);
                 }
             }
-            bw = (int64_t)uniform_u64((uint64_t)ld_wave_max_i64(bw));
+            bw = (int64_t)uniform_u64((uint64_t)wave_max_i64(bw));
             if (bw > best) best = bw;
         }
         tick(0);
@@ -217,20 +184,17 @@ __device__ __forceinline__ void ld_run_haystack(const RpLoop& a, LpLds<PLI>& L, 
             for (uint32_t b = 0; b < kLdsBlocks; b++) {
                 bool sel = false;
                 if (pl_of(p_[b], l_[b]) == kRpWalkList && p_[b] != kDead) {
-                    const uint32_t st = (uint32_t)p_[b]; AM_BOUNDS(p_[b] > 0);
-                    for (uint64_t k = a.t.vals_off[st], ke = a.t.vals_off[st + 1]; k < ke; k++) {
-                        const uint32_t v = a.t.vals[k];
-                        if (a.t.payloads[v].priority == best) { sel = true; pw = v; }
-                    }
+                    AM_BOUNDS(p_[b] > 0);
+                    rp_pick_in_values(a.t, (uint32_t)p_[b], best, sel, pw);
                 }
                 selmask[b] |= __ballot(sel);
             }
-            pw = ld_u32((uint32_t)ld_wave_max_i64((int64_t)pw));
+            pw = uniform_u32((uint32_t)wave_max_i64((int64_t)pw));
             if (pw > payload) payload = pw;
         }
         RpPayload pp = a.t.payloads[payload];                             // uniform index: one load for the pass (requesting it a pass ahead on a guess was measured: no gain)
-        const uint32_t m_len = ld_u32(pp.len_bytes), m_cps = ld_u32(pp.len_code_points), rl = ld_u32(pp.repl_len);
-        const uint32_t repl_off = ld_u32((uint32_t)pp.repl_off);
+        const uint32_t m_len = uniform_u32(pp.len_bytes), m_cps = uniform_u32(pp.len_code_points), rl = uniform_u32(pp.repl_len);
+        const uint32_t repl_off = uniform_u32((uint32_t)pp.repl_off);
         tick(1);
 
         // ---- makeMatch (:264-274) + removeOverlap (:191-198): 64 records at a time, in position order (positions are 32-bit here)
@@ -251,41 +215,21 @@ __device__ __forceinline__ void ld_run_haystack(const RpLoop& a, LpLds<PLI>& L, 
                         uint32_t lo = 0, hi = np;                        // last piece that starts at or before the match's last byte
                         const uint32_t index = end_pos - 1u;
                         while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (L.pls[mid] <= index) lo = mid; else hi = mid; }
-                        uint32_t pi = lo;
-                        int64_t i = (int64_t)index; uint32_t n = m_cps - 1u;
-                        for (;;) {
-                            for (;;) {
-                                if (i <= 0) break;
-                                while ((uint32_t)i < L.pls[pi]) pi--;     // (pieces may be empty: a loop)
-                                if ((byte_in(pi, (uint32_t)i) & 0xC0u) != 0x80u) break;      // atTrailingByte
-                                i--;
-                            }
-                            if (n == 0 || i <= 0) break;
-                            i--; n--;
-                        }
-                        start = (uint32_t)(i < 0 ? 0 : i);
+                        uint32_t pi = lo;                                // the walk's cursor into the LDS piece list (pieces may be empty: a loop)
+                        start = skip_code_points_backwards_by([&](uint32_t pos) -> uint32_t { while (pos < L.pls[pi]) pi--; return byte_in(pi, pos); }, end_pos, m_cps - 1u);
                     }
                     len = end_pos - start;
                     delta_sum += (int32_t)rl - (int32_t)len;
                 }
             }
-            uint64_t pending = selmask[b];
-            bool keep = false;
-            while (pending) {
-                const uint64_t ok = __ballot(sel && start >= last_end) & pending;
-                if (!ok) break;
-                const int l = __ffsll((unsigned long long)ok) - 1;
-                if (lane == l) keep = true;
-                last_end = (uint32_t)__builtin_amdgcn_readlane((int)(start + len), l);
-                pending &= l == 63 ? 0ull : ~((2ull << l) - 1ull);
-            }
+            const bool keep = rp_remove_overlap(sel, start, len, last_end, lane);
             const uint64_t keepmask = __ballot(keep);
             if (keepmask) {
                 const uint32_t nk = (uint32_t)__popcll(keepmask);
                 if ((uint64_t)nkept + nk > cap_r) { redo = true; break; }
                 if (nkept == 0) {                                        // the first kept match stays in scalar registers (a pass usually keeps one)
                     const int l = __ffsll((unsigned long long)keepmask) - 1;
-                    k0_start = (uint32_t)__builtin_amdgcn_readlane((int)start, l); k0_len = (uint32_t)__builtin_amdgcn_readlane((int)len, l);
+                    k0_start = wave_read_lane(start, l); k0_len = wave_read_lane(len, l);
                 }
                 if (nkept + nk > 1u && keep) {                           // several: the list goes through the haystack's kept region (global memory)
                     const uint32_t rank = (uint32_t)__popcll(keepmask & ((1ull << lane) - 1ull));
@@ -298,18 +242,18 @@ __device__ __forceinline__ void ld_run_haystack(const RpLoop& a, LpLds<PLI>& L, 
         }
         if (redo) break;
         int64_t delta_all = (int64_t)n_sel * ((int64_t)rl - (int64_t)m_len);      // replacementLength over ALL matches (:240), before removeOverlap
-        if (IC) delta_all = (int64_t)uniform_u64((uint64_t)ld_wave_sum_i64((int64_t)delta_sum));
+        if (IC) delta_all = (int64_t)uniform_u64((uint64_t)wave_sum_i64((int64_t)delta_sum));
         const int64_t newlen_all = (int64_t)curlen + delta_all;
         if (newlen_all > 0 && (uint64_t)newlen_all > a.max_len) { status = kRpNothing; break; }
         status = best == a.t.min_priority ? kRpFinished : kRpActive;    // :241-242
-        if (nkept > 1) ld_global_sync();                                  // K is read back below
+        if (nkept > 1) wave_global_sync();                                  // K is read back below
         tick(2);
 
         // ---- replace (:163-180), one kept match at a time, the last one first
         for (uint32_t jj = nkept; jj-- > 0 && !redo;) {
             if ((jj & 15u) == 15u && timed_out(2)) { redo = true; break; }
             uint32_t ms = k0_start, ml = k0_len;
-            if (nkept > 1) { const RpKept k = K[jj]; ms = ld_u32((uint32_t)k.src_start); ml = ld_u32((uint32_t)k.src_len); }
+            if (nkept > 1) { const RpKept k = K[jj]; ms = uniform_u32((uint32_t)k.src_start); ml = uniform_u32((uint32_t)k.src_len); }
             const uint32_t me = ms + ml;
             const int32_t delta = (int32_t)rl - (int32_t)ml;
             const uint64_t newlen = (uint64_t)((int64_t)curlen + delta);
@@ -369,8 +313,8 @@ __device__ __forceinline__ void ld_run_haystack(const RpLoop& a, LpLds<PLI>& L, 
                 }
             }
             const uint32_t i = c_ms - 1u, j2 = c_me - 1u, first = c_ws - 1u;     // (>= 0: piece 0 starts at 0; first <= i: ws <= ms)
-            const uint32_t pi_ls = ld_u32(L.pls[i]);
-            const uint32_t pj_ls = ld_u32(L.pls[j2]), pj_src = ld_u32(L.psrc[j2]), pj_le = ld_u32(L.pls[j2 + 1]);
+            const uint32_t pi_ls = uniform_u32(L.pls[i]);
+            const uint32_t pj_ls = uniform_u32(L.pls[j2]), pj_src = uniform_u32(L.psrc[j2]), pj_le = uniform_u32(L.pls[j2 + 1]);
             const uint32_t keep_head = ms > pi_ls ? 1u : 0u, has_repl = rl ? 1u : 0u, has_tail = me < pj_le ? 1u : 0u;
             const int32_t s = (int32_t)(keep_head + has_repl + has_tail) - (int32_t)(j2 - i + 1u);
             if ((int64_t)np + s + 1 > (int64_t)kLdsPc) { redo = true; break; }
@@ -412,7 +356,7 @@ __device__ __forceinline__ void ld_run_haystack(const RpLoop& a, LpLds<PLI>& L, 
 #pragma unroll
                     for (int q = 0; q < 6; q++) { const uint32_t k = first + (uint32_t)q <= np ? first + (uint32_t)q : np; ls[q] = L.pls[k]; sr[q] = L.psrc[k]; }
 #pragma unroll
-                    for (int q = 0; q < 6; q++) { ls[q] = ld_u32(ls[q]); sr[q] = ld_u32(sr[q]); }
+                    for (int q = 0; q < 6; q++) { ls[q] = uniform_u32(ls[q]); sr[q] = uniform_u32(sr[q]); }
                     const bool all_here = first + 5u >= np || ls[5] >= ws + wlen;      // the window ends inside the five pieces
                     for (uint32_t x = (uint32_t)lane; x < wlen; x += kWave) {
                         const uint32_t p = ws + x;
@@ -488,7 +432,7 @@ __device__ __forceinline__ void ld_run_haystack(const RpLoop& a, LpLds<PLI>& L, 
                     if ((int64_t)nr + g > (int64_t)kLdsRec) { redo = true; break; }
                     ld_move(L.end, c_gone, nr, g, 0u, lane);
                     ld_move(reinterpret_cast<uint32_t*>(L.prio), c_gone, nr, g, 0u, lane);
-                    if (!PLI) ld_move(L.pl, c_gone, nr, g, 0u, lane);      // (not "result only": a slot whose pl says "walk the list" while its prio holds a priority indexes vals_off[] with it; what moves end / prio moves pl, here and at :345)
+                    if (!PLI) ld_move(L.pl, c_gone, nr, g, 0u, lane);      // (not "result only": a slot whose pl says "walk the list" while its prio holds a priority indexes vals_off[] with it; what moves end / prio moves pl, here and at :289)
                     nr = (uint32_t)((int32_t)nr + g);
                 }
                 AM_BOUNDS(c_before + nf <= kLdsRec && staged + nf <= kLdsRec);

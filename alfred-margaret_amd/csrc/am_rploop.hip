@@ -13,9 +13,11 @@
 // Every haystack owns fixed regions (two record lists, two piece lists, a kept list, a window scratch) sized from its first scan; a
 // haystack that outgrows them raises the overflow flag and the host runs the batch through the piece-table path instead.
 // Replacers on the suffix-filter route, both case modes (IgnoreCase: makeMatch walks the text backwards through the piece list).
+// prependMatch's value lists, makeMatch's walk, removeOverlap, the kept list and the piece splice are those of am_rp_fold.h, where Replacer.hs:191-198, 252-274 are stated.
 #include <hip/hip_runtime.h>
 
 #include "am_device.h"
+#include "am_rp_fold.h"
 #include "am_wave.h"
 
 namespace am {
@@ -25,35 +27,6 @@ namespace {
 
 constexpr int kWave = 64;
 constexpr int kFold = 4;                                  // records per lane the fold keeps in registers (lists of up to 256 records are read once per pass)
-
-__device__ __forceinline__ int64_t lp_wave_max_i64(int64_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const int64_t o = __shfl_xor(v, d, kWave); v = o > v ? o : v; }
-    return v;
-}
-__device__ __forceinline__ int64_t lp_wave_sum_i64(int64_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
-    return v;
-}
-__device__ __forceinline__ int64_t lp_wave_incl_i64(int64_t v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) { const int64_t o = __shfl_up(v, d, kWave); if (lane >= d) v += o; }
-    return v;
-}
-
-__device__ __forceinline__ uint32_t lp_u32(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }      // a value that is the same in every lane: scalar from here on
-
-// what the lanes of this wavefront wrote to global memory is visible to its other lanes (one L1 per workgroup: a wait, no cache control)
-__device__ __forceinline__ void lp_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 // number of elements of the sorted key(0..n) that are <= x: a 64-ary search, one trip per factor of 64 (all arguments uniform)
 template <class Key>
@@ -74,48 +47,6 @@ __device__ __forceinline__ uint64_t lp_count_le(Key key, uint64_t n, uint64_t x,
         lo = nlo; hi = nlo + step < hi ? nlo + step : hi;               // the first element > x lies in block c
     }
     return lo;
-}
-
-// bytes [lo, lo + len) of a piece list (P[n] = sentinel) into dst
-__device__ __forceinline__ void lp_gather(const RpPiece* __restrict__ P, uint32_t n, const uint8_t* __restrict__ text, const uint8_t* __restrict__ repl,
-                                          uint64_t lo, uint64_t len, uint8_t* __restrict__ dst, int lane, uint64_t deadline)
-{
-    if (len == 0) return;
-    const uint64_t cnt = lp_count_le([&](uint64_t i) { return P[i].lstart; }, n, lo, lane, deadline);      // pieces that start at or before lo (>= 1: P[0] starts at 0)
-    uint64_t pos = lo;
-    const uint64_t end = lo + len;
-    for (uint64_t i = cnt - 1; pos < end && i < n; i++) {
-        const uint64_t ps = P[i].lstart, pn = P[i + 1].lstart, pe = pn < end ? pn : end, s = P[i].src;
-        if (pe <= pos) continue;                                         // (an empty piece)
-        if (__builtin_amdgcn_s_memtime() > deadline) return;
-        const uint8_t* from = ((s & kPieceRepl) ? repl + (s & ~kPieceRepl) : text + s) + (pos - ps);
-        uint8_t* to = dst + (pos - lo);
-        for (uint64_t x = lane; x < pe - pos; x += kWave) to[x] = from[x];
-        pos = pe;
-    }
-}
-
-// Utf8.hs:256-276 skipCodePointsBackwards on the text a piece list describes (makeMatch of an IgnoreCase replacer, Replacer.hs:268-274): from
-// byte `index` back over n code points, to the first byte of the code point reached; never leaves the text.  One lane, its own cursor into the
-// list (the bytes of a match almost always lie in one piece).
-__device__ __forceinline__ uint64_t lp_skip_code_points_backwards(const RpPiece* __restrict__ P, uint32_t np, const uint8_t* __restrict__ text, const uint8_t* __restrict__ repl,
-                                                               uint64_t index, uint64_t n)
-{
-    uint32_t lo = 0, hi = np;                                // last piece that starts at or before index (np >= 1 here: the text holds a match)
-    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (P[mid].lstart <= index) lo = mid; else hi = mid; }
-    uint32_t pi = lo;
-    uint64_t ls = P[pi].lstart, src = P[pi].src;
-    auto byte_at = [&](uint64_t pos) -> uint32_t {
-        while (pos < ls) { pi--; ls = P[pi].lstart; src = P[pi].src; }      // (pieces may be empty: a loop)
-        const uint8_t* from = (src & kPieceRepl) ? repl + (src & ~kPieceRepl) : text + src;
-        return from[pos - ls];
-    };
-    int64_t i = (int64_t)index;
-    for (;;) {
-        while (i > 0 && (byte_at((uint64_t)i) & 0xC0u) == 0x80u) i--;      // atTrailingByte
-        if (n == 0 || i <= 0) return (uint64_t)(i < 0 ? 0 : i);
-        i--; n--;
-    }
 }
 
 // how many of the sorted key(0 .. m) are <= x1 / <= x2 (x1 <= x2): lists of up to 1024 keys are looked at 256 per trip (four per lane in flight), stopping
@@ -194,7 +125,7 @@ __device__ void lp_run_haystack(const RpLoop& a, const uint32_t h, const int lan
     uint32_t passes = 0, status = kRpFinished;
     uint64_t scanned = 0;
     bool overflow = nr > cap_r || cap_p < 4;
-    lp_sync();
+    wave_global_sync();
 
     while (!overflow) {
         passes++;
@@ -218,26 +149,20 @@ __device__ void lp_run_haystack(const RpLoop& a, const uint32_t h, const int lan
             if (c_valid[u]) one = a.t.one[c_st[u]];
             c_prio[u] = one.priority; c_pl[u] = one.payload;
         }
-        auto best_of_list = [&](uint32_t st) {
-            for (uint64_t k = a.t.vals_off[st], ke = a.t.vals_off[st + 1]; k < ke; k++) {
-                const int64_t p = a.t.payloads[a.t.vals[k]].priority;
-                if (p < threshold && p > best) best = p;
-            }
-        };
 #pragma unroll
         for (int u = 0; u < kFold; u++) {
             if (c_valid[u]) {
                 if (c_pl[u] != kRpWalkList) { if ((int64_t)c_prio[u] < threshold && (int64_t)c_prio[u] > best) best = c_prio[u]; }
-                else best_of_list(c_st[u]);
+                else rp_best_in_values(a.t, c_st[u], threshold, best);
             }
         }
         for (uint64_t r = (uint64_t)kFold * kWave + lane; r < nr; r += kWave) {
             const uint32_t st = R[r].state;
             const RpStateOne one = a.t.one[st];
             if (one.payload != kRpWalkList) { if ((int64_t)one.priority < threshold && (int64_t)one.priority > best) best = one.priority; }
-            else best_of_list(st);
+            else rp_best_in_values(a.t, st, threshold, best);
         }
-        best = (int64_t)uniform_u64((uint64_t)lp_wave_max_i64(best));
+        best = (int64_t)uniform_u64((uint64_t)wave_max_i64(best));
         tick(0);
         if (best == INT64_MIN) { status = kRpFinished; break; }           // no match below the threshold: the text stays (:228-230)
 
@@ -245,47 +170,20 @@ __device__ void lp_run_haystack(const RpLoop& a, const uint32_t h, const int lan
         int64_t delta_all = 0, delta_kept = 0;
         uint64_t last_end = 0;
         uint32_t nkept = 0, payload = 0;
-        // the value of the state's list that carries `best` (a state with several values)
-        auto pick_of_list = [&](uint32_t st, bool& sel, uint32_t& pl) {
-            for (uint64_t k = a.t.vals_off[st], ke = a.t.vals_off[st + 1]; k < ke; k++) {
-                const uint32_t v = a.t.vals[k];
-                if (a.t.payloads[v].priority == best) { sel = true; pl = v; }
-            }
-        };
         // one block of 64 records: sel = carries the best priority (then pl, len, cps, rl are its payload's)
         auto block = [&](bool sel, uint32_t pl, uint64_t end_pos) {
             uint64_t len = 0; uint32_t cps = 0, rl = 0;
             if (sel) { const RpPayload pp = a.t.payloads[pl]; len = pp.len_bytes; cps = pp.len_code_points; rl = pp.repl_len; }      // (the few records that carry the best priority)
             uint64_t start = end_pos - len;                              // makeMatch, CaseSensitive (Replacer.hs:266-267)
             if (IC && sel) {                                             // IgnoreCase (:268-274): the match is as long as its code points are in the haystack
-                start = cps == 0 ? end_pos : lp_skip_code_points_backwards(P, np, a.text, a.t.repl, end_pos - 1, cps - 1);
+                start = cps == 0 ? end_pos : rp_skip_code_points_backwards(P, np, a.text, a.t.repl, end_pos, cps - 1);
                 len = end_pos - start;
             }
             const int64_t delta = sel ? (int64_t)rl - (int64_t)len : 0;
             delta_all += delta;
-            uint64_t pending = __ballot(sel);
-            bool keep = false;
-            while (pending) {
-                const uint64_t ok = __ballot(sel && start >= last_end) & pending;
-                if (!ok) break;
-                const int l = __ffsll((unsigned long long)ok) - 1;
-                if (lane == l) keep = true;
-                last_end = uniform_u64(__shfl(start + len, l, kWave));
-                pending &= l == 63 ? 0ull : ~((2ull << l) - 1ull);
-            }
-            const uint64_t keepmask = __ballot(keep);
-            if (keepmask) {
-                const int64_t kd = keep ? delta : 0;
-                const int64_t incl = lp_wave_incl_i64(kd, lane);
-                if (keep) {
-                    const uint32_t rank = __popcll(keepmask & ((1ull << lane) - 1ull));
-                    RpKept e; e.src_start = start; e.src_len = len; e.dst = (uint64_t)((int64_t)start + delta_kept + (incl - kd));
-                    K[nkept + rank] = e;
-                    payload = pl;
-                }
-                delta_kept += (int64_t)uniform_u64((uint64_t)__shfl(incl, kWave - 1, kWave));
-                nkept += __popcll(keepmask);
-            }
+            const bool keep = rp_remove_overlap(sel, start, len, last_end, lane);
+            rp_keep_block(keep, start, len, delta, K, nkept, delta_kept, lane);
+            if (keep) payload = pl;
         };
 #pragma unroll
         for (int u = 0; u < kFold; u++) {
@@ -293,7 +191,7 @@ __device__ void lp_run_haystack(const RpLoop& a, const uint32_t h, const int lan
                 bool sel = false; uint32_t pl = 0;
                 if (c_valid[u]) {
                     if (c_pl[u] != kRpWalkList) { if ((int64_t)c_prio[u] == best) { sel = true; pl = c_pl[u]; } }
-                    else pick_of_list(c_st[u], sel, pl);
+                    else rp_pick_in_values(a.t, c_st[u], best, sel, pl);
                 }
                 block(sel, pl, c_end[u]);
             }
@@ -307,22 +205,22 @@ __device__ void lp_run_haystack(const RpLoop& a, const uint32_t h, const int lan
                 end_pos = rec.end_pos;
                 const RpStateOne one = a.t.one[rec.state];
                 if (one.payload != kRpWalkList) { if ((int64_t)one.priority == best) { sel = true; pl = one.payload; } }
-                else pick_of_list(rec.state, sel, pl);
+                else rp_pick_in_values(a.t, rec.state, best, sel, pl);
             }
             block(sel, pl, end_pos);
         }
-        delta_all = (int64_t)uniform_u64((uint64_t)lp_wave_sum_i64(delta_all));
-        payload = lp_u32((uint32_t)lp_wave_max_i64((int64_t)payload));    // uniform: every kept match has the same payload
+        delta_all = (int64_t)uniform_u64((uint64_t)wave_sum_i64(delta_all));
+        payload = uniform_u32((uint32_t)wave_max_i64((int64_t)payload));    // uniform: every kept match has the same payload
         const int64_t newlen_all = (int64_t)curlen + delta_all;           // replacementLength over ALL matches (:240)
         if (newlen_all > 0 && (uint64_t)newlen_all > a.max_len) { status = kRpNothing; break; }
         const uint64_t newlen = (uint64_t)((int64_t)curlen + delta_kept);
         status = best == a.t.min_priority ? kRpFinished : kRpActive;    // :241-242
-        lp_sync();                                                       // K is read by every lane from here on
+        wave_global_sync();                                              // K is read by every lane from here on
         tick(1);
 
         // ---- replace (:163-180) on the piece list: P -> Q (the scheme of k_pt_build; the two lists of a haystack take turns)
         RpPayload pp = a.t.payloads[payload];
-        pp.repl_off = uniform_u64(pp.repl_off); pp.repl_len = lp_u32(pp.repl_len);
+        pp.repl_off = uniform_u64(pp.repl_off); pp.repl_len = uniform_u32(pp.repl_len);
         const uint64_t repl_len = nkept ? pp.repl_len : 0;
         if ((uint64_t)np + 2ull * nkept + 2ull > cap_p) { overflow = true; break; }
         uint32_t nq = 0, near = 0;                                       // near: index (new list) of the first entry of the piece the match starts in: where the window's gather begins to look
@@ -359,54 +257,17 @@ __device__ void lp_run_haystack(const RpLoop& a, const uint32_t h, const int lan
                 if (c > 1) Q[at + 1] = e[1];
                 if (c > 2) Q[at + 2] = e[2];
                 const uint64_t hm = __ballot(has_ms);
-                if (hm) near = lp_u32(__shfl(at, __ffsll((unsigned long long)hm) - 1, kWave));
-                nq += lp_u32(__shfl(incl, kWave - 1, kWave));
+                if (hm) near = uniform_u32(__shfl(at, __ffsll((unsigned long long)hm) - 1, kWave));
+                nq += uniform_u32(__shfl(incl, kWave - 1, kWave));
             }
             if (lane == 0) Q[nq] = RpPiece{0, newlen};                    // sentinel
         } else {
-            const uint32_t nk = nkept;
-            auto span = [&](uint64_t ls, uint64_t le, uint32_t& ja, uint32_t& jb) {
-                uint32_t lo = 0, hi = nk;
-                while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (K[mid].src_start + K[mid].src_len <= ls) lo = mid + 1; else hi = mid; }
-                ja = lo; jb = lo;
-                while (jb < nk && K[jb].src_start < le) jb++;
-            };
-            auto emit = [&](uint32_t i, auto&& f) {
-                const uint64_t ls = P[i].lstart, le = P[i + 1].lstart;
-                if (le == ls) return;
-                uint32_t ja, jb; span(ls, le, ja, jb);
-                uint64_t x = ls;
-                auto new_pos = [&](uint64_t xx, uint32_t jprev_plus1) -> uint64_t {
-                    if (jprev_plus1 == 0) return xx;
-                    const RpKept k = K[jprev_plus1 - 1];
-                    return k.dst + repl_len + (xx - (k.src_start + k.src_len));
-                };
-                uint32_t jp = ja;
-                for (uint32_t j = ja; j < jb; j++) {
-                    const RpKept k = K[j];
-                    if (k.src_start > x) f(P[i].src + (x - ls), new_pos(x, jp));
-                    if (k.src_start >= ls && repl_len) f(kPieceRepl | pp.repl_off, k.dst);
-                    x = k.src_start + k.src_len;
-                    jp = j + 1;
-                    if (x >= le) break;
-                }
-                if (x < le) f(P[i].src + (x - ls), new_pos(x, jp));
-            };
-            for (uint32_t r0 = 0; r0 < np && !overflow; r0 += kWave) {
-                LP_STEP(5);
-                const uint32_t i = r0 + lane;
-                uint32_t c = 0;
-                if (i < np) emit(i, [&](uint64_t, uint64_t) { c++; });
-                const uint32_t incl = wave_inclusive_sum(c, (uint32_t)lane);
-                uint32_t at = nq + incl - c;
-                if (i < np) emit(i, [&](uint64_t src, uint64_t pos) { Q[at++] = RpPiece{src, pos}; });
-                nq += lp_u32(__shfl(incl, kWave - 1, kWave));
-            }
+            nq = rp_splice_pieces(P, np, K, nkept, repl_len, kPieceRepl | pp.repl_off, Q, lane, [&] { LP_STEP(5); return !overflow; });
             if (lane == 0) Q[nq] = RpPiece{0, newlen};                    // sentinel
         }
         { RpPiece* t = P; P = Q; Q = t; }
         np = nq;
-        lp_sync();
+        wave_global_sync();
         tick(2);
         if (status == kRpFinished) { curlen = newlen; break; }
 
@@ -460,8 +321,7 @@ __device__ void lp_run_haystack(const RpLoop& a, const uint32_t h, const int lan
                     if (pp >= l1) { pls = l1; psr = s1; }
                     if (pp >= l2) { pls = l2; psr = s2; }
                     if (pp >= l3) { pls = l3; psr = s3; }
-                    const uint8_t* from = (psr & kPieceRepl) ? a.t.repl + (psr & ~kPieceRepl) : a.text + psr;
-                    wt[x] = from[pp - pls];
+                    wt[x] = rp_piece_base(psr, a.text, a.t.repl)[pp - pls];
                 }
             }
             return true;
@@ -490,8 +350,12 @@ __device__ void lp_run_haystack(const RpLoop& a, const uint32_t h, const int lan
             const uint32_t wlen = hi > dst ? (uint32_t)(hi - ws) : 0u, own_lo = (uint32_t)(dst - ws);
             if (wlen > a.wcap) { overflow = true; break; }
             if (wlen) {
-                if (!(nkept == 1 && gather_small(ws, wlen))) lp_gather(P, np, a.text, a.t.repl, ws, wlen, wt, lane, deadline);
-                lp_sync();
+                if (!(nkept == 1 && gather_small(ws, wlen))) {
+                    // (the first piece by the 64-ary search: pieces that start at or before ws are >= 1, P[0] starts at 0)
+                    rp_gather(P, np, a.text, a.t.repl, ws, wlen, wt, lane, [&] { return lp_count_le([&](uint64_t i) { return P[i].lstart; }, np, ws, lane, deadline) - 1; },
+                              [&] { return __builtin_amdgcn_s_memtime() <= deadline; });
+                }
+                wave_global_sync();
                 tick(4);
                 scanned += wlen;
                 for (uint32_t base = own_lo; base < wlen && !overflow; base += kWave) {
@@ -512,7 +376,7 @@ __device__ void lp_run_haystack(const RpLoop& a, const uint32_t h, const int lan
                         cursor += nf;
                     }
                 }
-                if (j + 1 < nkept) lp_sync();                            // (the scratch is rewritten by the next window; after the last one the pass's closing wait covers it)
+                if (j + 1 < nkept) wave_global_sync();                            // (the scratch is rewritten by the next window; after the last one the pass's closing wait covers it)
                 tick(5);
             }
             // old records that touch the replaced bytes are gone
@@ -524,7 +388,7 @@ __device__ void lp_run_haystack(const RpLoop& a, const uint32_t h, const int lan
             const int64_t g = (int64_t)(e_first + nf) - (int64_t)at, delta = (int64_t)newlen - (int64_t)curlen;
             if ((int64_t)nr + g > (int64_t)cap_r) { overflow = true; break; }
             Record* const Rw = const_cast<Record*>(R);
-            lp_sync();                                                   // (the lanes that found them wrote the window's records)
+            wave_global_sync();                                                   // (the lanes that found them wrote the window's records)
             if (g != 0 || delta != 0) lp_move(Rw, at, nr, g, [&](Record& r) { r.end_pos = (uint64_t)((int64_t)r.end_pos + delta); }, lane);
             for (uint64_t i = lane; i < nf; i += kWave) Rw[e_first + i] = Rn[i];
             nr = (uint64_t)((int64_t)nr + g);
@@ -535,7 +399,7 @@ __device__ void lp_run_haystack(const RpLoop& a, const uint32_t h, const int lan
             R = Rn; nr = cursor;
         }
         curlen = newlen; threshold = best;
-        lp_sync();
+        wave_global_sync();
         tick(3);
     }
 

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "am_device.h"
+#include "am_wave.h"
 
 namespace am {
 namespace dev {
@@ -14,19 +15,12 @@ namespace {
 constexpr int kScanThreads = 256, kScanPer = 16;
 constexpr uint64_t kScanTile = (uint64_t)kScanThreads * kScanPer;      // 4096 elements per workgroup
 
-__device__ __forceinline__ uint64_t wave_incl_u64(uint64_t x, uint32_t lane)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint64_t y = __shfl_up(x, d, 64); if (lane >= (uint32_t)d) x += y; }
-    return x;
-}
-
 // exclusive sum over the workgroup's 256 values; returns this thread's base, *total = the workgroup's sum
 __device__ __forceinline__ uint64_t block_exclusive(uint64_t v, uint64_t* total)
 {
     __shared__ uint64_t wsum[kScanThreads / 64];
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const uint64_t incl = wave_incl_u64(v, lane);
+    const uint64_t incl = wave_inclusive_sum_u64(v, lane);
     __syncthreads();                                         // (wsum may still be read by the previous call's last phase)
     if (lane == 63u) wsum[w] = incl;
     __syncthreads();
@@ -132,11 +126,11 @@ __global__ void __launch_bounds__(1024) k_scan_jobs(ScanJobs jobs)
             if (base >= n) break;                         // (uniform)
             const uint64_t i0 = base + (uint64_t)threadIdx.x * 4;
             const uint64_t mine = v[bb][0] + v[bb][1] + v[bb][2] + v[bb][3];
-            const uint64_t incl = wave_incl_u64(mine, lane);
+            const uint64_t incl = wave_inclusive_sum_u64(mine, lane);
             if (lane == 63u) wave_tot[turn][wave] = incl;
             __syncthreads();
             const uint64_t wt = lane < 16 ? wave_tot[turn][lane] : 0ull;
-            const uint64_t wincl = wave_incl_u64(wt, lane);               // lanes 0..15: totals of the wavefronts up to and including `lane`
+            const uint64_t wincl = wave_inclusive_sum_u64(wt, lane);               // lanes 0..15: totals of the wavefronts up to and including `lane`
             const uint64_t before_waves = __shfl(wincl, (int)wave, 64) - __shfl(wt, (int)wave, 64);
             const uint64_t sweep_total = __shfl(wincl, 15, 64);
             uint64_t run = carry + before_waves + incl - mine;

@@ -50,12 +50,6 @@ constexpr uint32_t kTopkPerThread = 8;
 constexpr uint32_t kTopkBlock = kTopkThreads * kTopkPerThread;       // keys per workgroup of k_topk_hist
 static_assert(kTopkThreads == kTopkBins, "a thread per bin");
 
-__device__ __forceinline__ uint64_t lane63_u64(uint64_t x)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, 63), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), 63);
-    return ((uint64_t)hi << 32) | lo;
-}
-
 // NC: the columns the instantiation has registers for (out.n_cols <= NC; the loops over columns are unrolled and skip those beyond).  View: SpansIn or RecordsIn
 template <bool WORDS, bool IC, uint32_t NC, class View, bool EXACT = false>
 __device__ __forceinline__ void score_body(const uint32_t* words, const View& in, const ScoreOut& out)
@@ -141,7 +135,7 @@ __device__ __forceinline__ void score_body(const uint32_t* words, const View& in
             if (last_of_run && h != kNoHay) send(h, s);
             carry_h = (uint32_t)__builtin_amdgcn_readlane((int)h, 63);
 #pragma unroll
-            for (uint32_t c = 0; c < NC; c++) carry[c] = c < n_cols ? lane63_u64(s[c]) : 0;
+            for (uint32_t c = 0; c < NC; c++) carry[c] = c < n_cols ? wave_read_lane(s[c], 63) : 0;
         }
     }
     if (carry_h != kNoHay && lane == 0) send(carry_h, carry);

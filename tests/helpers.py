@@ -221,11 +221,11 @@ class AbiReplacer:
 
 
 # ---- the limits of k_rp_lds (csrc/am_rplds.hip), one sweep per limit -------------------------------------------------------------------------
-LDS_REC = 512          # kLdsRec   (am_rplds.hip:37): records of a haystack; first scan :126, list + staged new records :461, list growth :488
-LDS_PC = 448           # kLdsPc    (am_rplds.hip:39): piece entries INCLUDING the sentinel (:376: np + s + 1 > kLdsPc gives up), so 447 pieces of text
-LDS_WIN = 448          # kLdsWin   (am_rplds.hip:41): bytes of a re-scan window (:322)
-LDS_NEW = 64           # new records of one window (:461, nf + nfb > kWave)
-NEVER = ("zz", "y")    # the lowest priority of every sweep, never matches: the measured pass is not the last priority (:317, :328 edit the piece list only there)
+LDS_REC = 512          # kLdsRec   (am_rplds.hip:40): records of a haystack; first scan :96, list + staged new records :405, list growth :432
+LDS_PC = 448           # kLdsPc    (am_rplds.hip:42): piece entries INCLUDING the sentinel (:320: np + s + 1 > kLdsPc gives up), so 447 pieces of text
+LDS_WIN = 448          # kLdsWin   (am_rplds.hip:44): bytes of a re-scan window (:266)
+LDS_NEW = 64           # new records of one window (:405, nf + nfb > kWave)
+NEVER = ("zz", "y")    # the lowest priority of every sweep, never matches: the measured pass is not the last priority (:261, :272 edit the piece list only there)
 NAMES = "abcdefghijklmnopqrstuvwxyz0123456789"
 
 
@@ -264,7 +264,7 @@ def sweep_first_scan_records(case):
 def sweep_growing_list(case):
     """2a. The list grows during the first pass: twenty replacements, each brings 25 match positions of the lower-priority needle (eight "q"s in a run of 32) and frees
     one slot; j + 20 records of the first scan become j + 500.  The new records are STAGED behind the list (:461 nr + nf + nfb > kLdsRec) before they move into it, so a
-    step that frees `room` slots needs nr + nf <= 512 and the list can end at 512 - room = 511 at most; the growth check behind it (:488) can then never fire."""
+    step that frees `room` slots needs nr + nf <= 512 and the list can end at 512 - room = 511 at most; the growth check behind it (:432) can then never fire."""
     pairs = [("m", "q" * 32), ("q" * 8, "r"), NEVER]
     values = list(range(LDS_REC - 4, LDS_REC + 5))               # records after the first pass
     hays = [_up(case, "q" * (n - 500 + 7) + "x" * 40 + ("m" + "x" * 40) * 20) for n in values]
@@ -281,7 +281,7 @@ def sweep_staging(case):
 
 def sweep_pieces(case, variant):
     """3. k non-adjacent single-byte replacements.  variant "inner": b + (ab)^k, 2k + 1 pieces; "edge": (ab)^k starts with a match, 2k pieces; "tail": (ba)^k ENDS with a
-    match, 2k pieces (no tail piece behind the last replacement, has_tail :374, in a text that goes on to fill the list); "empty": the empty
+    match, 2k pieces (no tail piece behind the last replacement, has_tail :318, in a text that goes on to fill the list); "empty": the empty
     replacement leaves k + 1 pieces of text around k holes (no replacement piece, has_repl :374).  The list holds kLdsPc entries with its sentinel (:376)."""
     if variant == "empty":
         values = list(range(LDS_PC - 5, LDS_PC + 4))                # pieces
@@ -324,7 +324,7 @@ def sweep_new_records(case, variant):
 def sweep_quantities(sw, i):
     """What haystack i of a sweep does to the lists of k_rp_lds, computed with the oracle's automaton and plain Python (no kernel): the first pass is the one
     the sweeps measure.  first_scan: positions with a match (= records); pieces: entries of the piece list after the first pass; window: the longest re-scan window
-    (hi - ws, am_rplds.hip:318-321); new_records: the most lower-priority match positions one window finds; records_after: the list after the first pass."""
+    (hi - ws, am_rplds.hip:262-265); new_records: the most lower-priority match positions one window finds; records_after: the list after the first pass."""
     case, hay = sw.case, sw.hays[i].encode("utf-8")
     orig = [n.encode("utf-8") for n, _ in sw.pairs]
     repl = [r.encode("utf-8") for _, r in sw.pairs]
@@ -968,7 +968,7 @@ def long_route_cap(case, pairs):
 
 class LongReplacerCase:
     """pairs over docs (str); `expect` the final texts, `passes` the scans the longest-running document needs (Replacer.hs:219-242), `fits[i]`: document i's first
-    re-scan window (am_rplds.hip:318-322) is within LDS_WIN."""
+    re-scan window (am_rplds.hip:262-266) is within LDS_WIN."""
 
     def __init__(self, name, case, pairs, docs, expect, passes):
         self.name, self.case, self.pairs, self.docs, self.expect, self.passes = name, case, pairs, docs, expect, passes

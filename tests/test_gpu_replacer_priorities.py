@@ -3,11 +3,11 @@ capacity limits, crossed one step at a time.
 
 include/am.h promises any distinct priorities <= 0; the host mirror (host/replacer.hpp) only ever builds priority = -index, which am_replacer_create recognises
 (am_replacer.cpp:151-152) and runs on the payload-implicit instantiation of k_rp_lds.  Everything here that passes `priorities` runs the OTHER instantiation
-(payload column in LDS, am_rplds.hip:43-51) and, with priorities below INT32_MIN, the value-list side path of single-valued states (am_replacer.cpp:166).
+(payload column in LDS, am_rplds.hip:46-54) and, with priorities below INT32_MIN, the value-list side path of single-valued states (am_replacer.cpp:166).
 The reference is the oracle with the same priorities (tests/test_oracle_priorities.py pins it on the CPU); the limit inputs come from tests/helpers.py, where
 the same CPU test file checks that each moves the one quantity it claims to move.
 
-Left out: the 2-GiB text limit of k_rp_lds (am_rplds.hip:126, :316).  A Replacer run of that size belongs with the large-document tests
+Left out: the 2-GiB text limit of k_rp_lds (am_rplds.hip:96, :260).  A Replacer run of that size belongs with the large-document tests
 (tests/test_gpu_one_large_document.py) and would dominate this file's time."""
 import random
 
@@ -132,7 +132,7 @@ def test_priorities_that_differ_from_build_in_one_place_and_single_needles():
 
 def test_multi_valued_states_under_shuffled_priorities():
     """Duplicate needles and needles that are suffixes of others: one state's value list holds several payloads, in the automaton's order -- with shuffled
-    priorities a HIGHER priority sits behind a lower one in the list (am_rplds.hip:186-199, :214-230; am_rploop.hip:221-226, :249-254)."""
+    priorities a HIGHER priority sits behind a lower one in the list (am_rp_fold.h:19-33, called at am_rplds.hip:156-167, :181-194 and am_rploop.hip:156, :163, :194, :208)."""
     pairs = [("abc", "1"), ("bc", "2b"), ("c", "3"), ("abc", "c4"), ("c", "5bc"), ("xbc", "ab6"), ("bc", "")]
     rng = random.Random(94)
     hays = ["abcxbcabc", "xbc" * 40, "c" * 100, "", "ab"] + ["".join(rng.choice("abcx") for _ in range(rng.randint(1, 300))) for _ in range(25)]
@@ -166,7 +166,7 @@ def test_priorities_beyond_32_bits():
 
 
 def test_priority_int32_min_on_a_single_valued_state():
-    """The smallest priority RpStateOne can hold.  k_rp_lds folds 32-bit priorities with INT32_MIN as its "nothing below the threshold" (am_rplds.hip:181-185), so
+    """The smallest priority RpStateOne can hold.  k_rp_lds folds 32-bit priorities with INT32_MIN as its "nothing below the threshold" (am_rplds.hip:151-155), so
     a single-valued state must not carry INT32_MIN in that field: am_replacer_create gives it to the value-list side path like the priorities below it."""
     hays = ["abab", "b" * 30, "xaxbx" * 10]
     for prio, expect in (([0, INT32_MIN], [b"cccc", b"c" * 30, b"xcxcx" * 10]), ([INT32_MIN, 0], [b"bcbc", b"c" * 30, b"xbxcx" * 10])):

@@ -46,7 +46,7 @@ def _loop_equals_oracle(pairs, hays, max_len=-1, case=0):
 
 def _twin_with_own_priorities(pairs, hays, max_len, case, exp, passes, lds_haystacks, built_case=None):
     """The mirror trick: the pair list reversed with priorities -(n-1-i) is the same replacer, but am_replacer_create does not recognise it as Replacer.build's
-    (am_replacer.cpp:151-152), so k_rp_lds runs with its payload column (am_rplds.hip:43-51) instead of the payload-implicit layout: identical bytes, identical
+    (am_replacer.cpp:151-152), so k_rp_lds runs with its payload column (am_rplds.hip:46-54) instead of the payload-implicit layout: identical bytes, identical
     passes, and -- the limits are the same in both layouts -- the same haystacks finished out of LDS."""
     twin_pairs, twin_prio = mirror_twin(pairs)
     t = AbiReplacer(case, twin_pairs, twin_prio, built_case=built_case)

@@ -103,7 +103,7 @@ def test_the_limit_inputs_are_what_they_claim_to_be(sw):
                 continue
             assert q[key] <= bound, (sw, i, key, q)
     if sw.name.startswith("new records"):
-        # where the new match positions lie in the window's trips of 64 positions (am_rplds.hip:437: from the replacement's first byte)
+        # where the new match positions lie in the window's trips of 64 positions (am_rplds.hip:381: from the replacement's first byte)
         for i, m in enumerate(sw.values):
             rep = sw.pairs[i][1].lower()
             first_trip = rep[:64].count("q")
