@@ -502,7 +502,13 @@ AM_HD uint32_t t4_slot_diff(uint32_t slot, uint32_t expect)
 // buckets + the word a matching slot must equal; sf_probe_decide looks at them: defer[k] = true: a needle may end here, phase 2
 // must look (exactly); hint[k] = which of the four candidate slots agreed.  No data-dependent loop, the only memory traffic is the
 // two 8-byte buckets.
-template <int N>
+// ALWAYS (k_sf's chunk loop, where the number of loads in flight has to be a compile-time constant: see the latch there): every lane requests its
+// two buckets, no branch around the loads.  A lane that does not probe reads bucket 0 -- the table's first eight bytes, or the image's own first
+// eight where there is no table (am_flatten.cpp clears the whole header and sets off_tier[3] only where it writes the table, sf_view adds it to the image's
+// base): mapped, and in cache -- and expects kT4NoSlot, a word no slot of a table agrees with: occupied slots differ from
+// it in bit 15, empty ones (0) in bit 5.  sf_probe_decide then says of it what it says of two empty buckets: no hit, hint 3.
+constexpr uint32_t kT4NoSlot = 1u << 5;
+template <int N, bool ALWAYS = false>
 AM_HD void sf_probe_issue(const SfView& s, const uint32_t (&w)[N], const uint32_t (&nbs)[N], const uint64_t (&avail)[N], const bool (&valid)[N],
                           u32x2 (&ba)[N], u32x2 (&bb)[N], uint32_t (&expect)[N])
 {
@@ -512,14 +518,27 @@ AM_HD void sf_probe_issue(const SfView& s, const uint32_t (&w)[N], const uint32_
         const bool probe = valid[k] && (s.tiers & 8u) && avail[k] >= 4;
         const uint32_t ha = t4_hash_a(w[k]), hb = t4_hash_b(w[k]);
         expect[k] = t4_expect(t4_fingerprint(ha, lb), nbs[k] & 0xFFFFu);
-        ba[k] = u32x2{0, 0}; bb[k] = ba[k];                      // empty buckets for the lanes that do not probe
-        if (probe) {
+        if constexpr (ALWAYS) {
+            if (!probe) expect[k] = kT4NoSlot;
+            const uint32_t ia = probe ? t4_bucket(ha, lb) : 0u, ib = probe ? t4_bucket(hb, lb) : 0u;
 #if defined(__HIP_DEVICE_COMPILE__)
-            const uint2 ra = *reinterpret_cast<const uint2*>(s.t4_hot + t4_bucket(ha, lb)), rb = *reinterpret_cast<const uint2*>(s.t4_hot + t4_bucket(hb, lb));
+            const uint2 ra = *reinterpret_cast<const uint2*>(s.t4_hot + ia), rb = *reinterpret_cast<const uint2*>(s.t4_hot + ib);
             ba[k] = u32x2{ra.x, ra.y}; bb[k] = u32x2{rb.x, rb.y};
 #else
-            ba[k] = s.t4_hot[t4_bucket(ha, lb)]; bb[k] = s.t4_hot[t4_bucket(hb, lb)];
+            ba[k] = s.t4_hot[ia]; bb[k] = s.t4_hot[ib];
 #endif
+        } else {
+            // (its own body, word for word what it was: folded into the one above with the index selected by `probe`, the compiler orders the address arithmetic
+            // of the instantiations that do not request on every chunk differently, and those keep their instructions)
+            ba[k] = u32x2{0, 0}; bb[k] = ba[k];                      // empty buckets for the lanes that do not probe
+            if (probe) {
+#if defined(__HIP_DEVICE_COMPILE__)
+                const uint2 ra = *reinterpret_cast<const uint2*>(s.t4_hot + t4_bucket(ha, lb)), rb = *reinterpret_cast<const uint2*>(s.t4_hot + t4_bucket(hb, lb));
+                ba[k] = u32x2{ra.x, ra.y}; bb[k] = u32x2{rb.x, rb.y};
+#else
+                ba[k] = s.t4_hot[t4_bucket(ha, lb)]; bb[k] = s.t4_hot[t4_bucket(hb, lb)];
+#endif
+            }
         }
     }
 }

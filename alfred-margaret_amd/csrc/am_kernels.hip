@@ -85,6 +85,11 @@ constexpr uint32_t kSfMaskBytes = kBloomMasks * 4u;      // the Bloom mask table
 //   look at  the buckets requested for the PREVIOUS chunk's survivors; park the few that agree in a ring
 //   request  both cuckoo buckets of this chunk's survivors, up to 128 at a time (window bytes from the
 //            chunk staged in LDS); no data-dependent loop                             (phase 1)
+//            (kStraight -- count / emit, 1024 threads, no short needles, no child entries: issued by every
+//            chunk, a lane without a survivor reads bucket 0 and ignores it, so that the latch below
+//            can count them)
+//   latch    the prefetched next chunk becomes the current one: waits for that load alone (vmcnt(2):
+//            the round's two bucket loads stay in flight under the next chunk's filter)
 //   resolve  when 64 are parked, and at the end of every 16-chunk epoch: one slot line per item, the
 //            trie walk for the rare long ones                                         (phase 2)
 // Phase 2 is FIFO, so the records of a unit come out in position order: ballot + popcount rank them,
@@ -115,6 +120,12 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
     // chunks per ring epoch (the ring is drained at its end; an entry names its chunk within the epoch): flag mode drains every 4 chunks -- the first match is
     // what everybody waits for --, with child entries every 8 (bit 15 of an entry says "the slot of a child entry")
     constexpr uint32_t kEpoch = kFlagMode ? 4u : CH ? 8u : kSfEpochChunks;
+    // kStraight: every pass of the chunk loop requests its round's buckets, with no branch around the loads -- a chunk without a survivor requests bucket 0 in
+    // every lane and ignores it (sf_probe_issue<N, true>) --, so that the number of loads issued between the prefetch of the next chunk and the latch that takes
+    // it over is a compile-time constant and the latch waits for the prefetch alone (vmcnt counts in order; see the latch).  Not in flag mode, whose skipped
+    // chunks request nothing, nor with child entries, whose look-at requests further buckets: those keep the request behind its scalar branch, and so do the
+    // short-needle and the light instantiations, whose time goes elsewhere (the tier probes of every position; one small document).
+    constexpr bool kStraight = !kFlagMode && !CHILDREN && !SHORT && NT == am::dev::kSfThreads;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t words = 1u << s.bloom_log2_words;
     uint32_t* masks = lds;                                            // LDS bytes [0, kSfMaskBytes)
@@ -151,7 +162,7 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
 
     // optional phase timing (AM_SF_TRACE): s_memtime deltas per wavefront, summed into o.dbg
     const bool timing = DBG && o.dbg != nullptr;
-    uint64_t t_filter = 0, t_compact = 0, t_probe = 0, t_resolve = 0, t_probe_pre = 0, t_mark = 0;
+    uint64_t t_filter = 0, t_compact = 0, t_probe = 0, t_resolve = 0, t_probe_pre = 0, t_latch = 0, t_mark = 0;
     uint64_t dbg_iters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t t_r0 = 0, t_r1 = 0, t_r2 = 0, t_r3 = 0, n_batches = 0, n_cand = 0, n_probes = 0, n_defer = 0, n_found = 0;
     auto tick = [&](uint64_t& acc) { if (timing) { const uint64_t now = __builtin_amdgcn_s_memtime(); acc += now - t_mark; t_mark = now; } };
@@ -446,6 +457,10 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
         }
         if (timing) { const uint64_t now = __builtin_amdgcn_s_memtime(); t_r3 += now - t_mark; t_mark = now; }
         q2_head += nb;
+        // the batch ends with its own wait (vmcnt(0); expcnt and lgkmcnt left alone): a load or a store it left pending -- the walk has loads whose
+        // result only some paths read -- would be pending at the join with the chunk loop's straight path, and the compiler would then wait for
+        // everything in flight, the prefetch and the round's buckets included, at the next register it reuses there
+        if (kStraight) __builtin_amdgcn_s_waitcnt(0x0F70);
         __builtin_amdgcn_s_setprio(2);
     };
 
@@ -612,7 +627,23 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
                                       (c + 1) * kSfChunk >= hs0 && (c + 2) * kSfChunk <= he0;
             // (the chunk after this one of the same unit, anywhere but at the batch's end: requested without a test; the next unit's first chunk and
             // the batch's last chunk take the tested form behind a scalar branch)
-            if (!next_skipped) {
+            if (kStraight) {
+                // ONE load on every path, its address chosen by scalar selects: a load behind a branch is pending at the join as far as the compiler can tell, and it
+                // then waits vmcnt(0) before the other form's address arithmetic, which reuses the registers -- at the top of every chunk, for the buckets requested a
+                // moment ago.  Where nothing follows (no next unit) the wave reads chunk 0 and never looks at it; in the batch's last chunk the lanes past the end
+                // read its last 16-byte block again instead of zeros: no window of a position inside the batch reaches them, and the positions past the end are
+                // masked out of `cand` below (ci == tail_ci).
+                uint64_t cc = !last_of_unit ? c + 1 : u_next * UC;
+                uint32_t lim = kSfChunk - 16u;
+                if (ci >= n_whole) {
+                    if (cc >= n_chunks) cc = 0;
+                    if (cc + 1 >= n_chunks) lim = (uint32_t)((b.total - 1) & (kSfChunk - 1u)) & ~15u;
+                }
+                const uint32_t off = lane * 16u < lim ? lane * 16u : lim;
+                typedef uint32_t u32x4_native __attribute__((ext_vector_type(4)));
+                const u32x4_native t = *reinterpret_cast<const u32x4_native*>(b.text + cc * kSfChunk + off);
+                next_v = make_uint4(t.x, t.y, t.z, t.w);
+            } else if (!next_skipped) {
                 if (ci < n_whole) fetch_whole(c + 1, next_v);
                 else fetch(!last_of_unit ? c + 1 : u_next * UC, next_v);
             }
@@ -741,7 +772,7 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
                 const uint32_t n = __popc(cand);
                 const uint32_t incl = wave_inclusive_sum(n, lane);
                 const uint32_t total = wave_last_lane(incl);      // in an SGPR: n_q1, the loop's exits and every `if` on the round's size are scalar branches
-                if (total == 0 && !(first && pending)) break;
+                if (!kStraight && total == 0 && !(first && pending)) break;      // (kStraight: a chunk without a survivor still requests -- and total == 0 only ever on the first pass)
                 uint32_t idx = incl - n;
                 // the loop runs as long as the busiest lane has candidates, so it only queues positions; the probe
                 // (dense, one candidate per lane) picks the window and the two bytes before it out of the staged chunk
@@ -776,7 +807,7 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
                     tick(t_resolve);
                 }
                 // request this round: up to 128 survivors, two per lane
-                if (n_q1) {
+                if (kStraight || n_q1) {
                     uint64_t avail[2] = {0, 0};
                     uint32_t w[2] = {0, 0}, nb[2] = {0, 0};
                     bool valid[2] = {false, false};
@@ -813,13 +844,13 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
                         if (valid[k] && !single) avail[k] = gpos - b.offsets[find_haystack(b, gpos)] + 1;
                         p_pos[k] = valid[k] ? (pos | 0x8000u) : 0u;
                     }
-                    if (two) sf_probe_issue<2>(s, w, nb, avail, valid, p_a, p_b, p_e);
+                    if (two) sf_probe_issue<2, kStraight>(s, w, nb, avail, valid, p_a, p_b, p_e);
                     else {
                         const uint32_t w1[1] = {w[0]}, nb1[1] = {nb[0]};
                         const uint64_t av1[1] = {avail[0]};
                         const bool v1[1] = {valid[0]};
                         u32x2 a1[1], b1[1]; uint32_t e1[1];
-                        sf_probe_issue<1>(s, w1, nb1, av1, v1, a1, b1, e1);
+                        sf_probe_issue<1, kStraight>(s, w1, nb1, av1, v1, a1, b1, e1);
                         p_a[0] = a1[0]; p_b[0] = b1[0]; p_e[0] = e1[0];
                     }
                     p_two = two;
@@ -830,7 +861,11 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
                 if (total <= (uint32_t)kSfQ1) break;
                 wave_lds_fence();
             }
+            // The latch.  kStraight: the round's bucket requests, issued just above on every path, are the only loads younger than the prefetch, so the wait
+            // for next_v is vmcnt(2) and the buckets' trip through L2 passes under the next chunk's filter, as the probe pipeline means it to.  (Behind a branch the
+            // requests cannot be counted, the wait is vmcnt(0) and covers them: the flag-mode and child-entry instantiations.)
             cur_v = next_v; carry3 = next_c3; carry4 = next_c4;
+            if (timing) { asm volatile("" : "+v"(cur_v.x), "+v"(cur_v.y), "+v"(cur_v.z), "+v"(cur_v.w)); tick(t_latch); }      // t_latch: from the request to the prefetched chunk's arrival
             // end of an epoch (and of the unit): drain the ring, so that every item of a batch belongs to one epoch of one unit
             if ((ci & (kEpoch - 1u)) == kEpoch - 1u || last_of_unit) {
                 if (pending) consume_round();                 // not overlapped: once per 16 chunks
@@ -861,6 +896,7 @@ __global__ __launch_bounds__(NT) void k_sf(SfView s, BatchView b, ScanOut o, uin
         atomicAdd(reinterpret_cast<unsigned long long*>(o.dbg + 9), (unsigned long long)t_r2);
         atomicAdd(reinterpret_cast<unsigned long long*>(o.dbg + 10), (unsigned long long)t_r3);
         for (int i = 0; i < 7; i++) atomicAdd(reinterpret_cast<unsigned long long*>(o.dbg + 16 + 2 * 8192 + i), (unsigned long long)dbg_iters[i]);
+        atomicAdd(reinterpret_cast<unsigned long long*>(o.dbg + 16 + 2 * 8192 + 7), (unsigned long long)t_latch);      // (dbg_iters[7] is the resolve's own time mark)
         atomicAdd(reinterpret_cast<unsigned long long*>(o.dbg + 11), (unsigned long long)n_cand);
         atomicAdd(reinterpret_cast<unsigned long long*>(o.dbg + 12), (unsigned long long)n_probes);
         atomicAdd(reinterpret_cast<unsigned long long*>(o.dbg + 13), (unsigned long long)n_defer);

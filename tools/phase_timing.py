@@ -54,5 +54,8 @@ for mode in ("count", "emit"):
     print("   slowest wave: %.0f cycles = %.0f per chunk (the averages below are over all waves)" % (out[15], out[15] / (n_bytes / 1024 / max(out[4], 1))))
     print("   per chunk: candidates %.2f, probe batches %.3f, deferred %.2f, resolve batches %.3f, found %.3f" % (out[11] / nch, out[12] / nch, out[13] / nch, out[6] / nch, out[14] / nch))
     print("   resolve batches/wave %.1f, cycles per batch: before the lookup %.0f, lookup + walk %.0f" % (out[6] / waves, out[7] / nbat, (out[8] + out[10]) / nbat))
-    print("%s %s: waves %d, chunks/wave %.0f, cycles/chunk: filter %.0f compact %.0f probe-setup %.0f probe-mem %.0f resolve %.0f  total %.0f" % (
-        wl, mode, waves, chunks, out[0] / waves / chunks, out[1] / waves / chunks, out[5] / waves / chunks, out[2] / waves / chunks, (out[3] + out[7] + out[8] + out[10]) / waves / chunks, (tot_c + out[5] + out[7] + out[8] + out[10]) / waves / chunks))
+    # latch: from the round's request to the arrival of the prefetched chunk (steps[7]; before this column existed the wait was booked under the next chunk's filter)
+    total = (tot_c + out[5] + out[7] + out[8] + out[10] + steps[7]) / waves / chunks
+    print("%s %s: waves %d, chunks/wave %.0f, cycles/chunk: filter %.0f compact %.0f probe-setup %.0f probe-mem %.0f resolve %.0f latch %.0f (%.1f %%)  total %.0f" % (
+        wl, mode, waves, chunks, out[0] / waves / chunks, out[1] / waves / chunks, out[5] / waves / chunks, out[2] / waves / chunks, (out[3] + out[7] + out[8] + out[10]) / waves / chunks,
+        steps[7] / waves / chunks, 100.0 * steps[7] / waves / chunks / max(total, 1e-9), total))
